@@ -18,9 +18,15 @@ with the parameter gradients ACCUMULATING over the views of the batch.
   N > 1 (default config C4): a batch is the EIGHT views of the 8-GPU training batch.  Rank r renders its
         8 / N views (gaussiansplat_amd.distributed.shard_views) one after the other, then the ranks sum the flat 59 N-float
         gradient buffer over RCCL.  `--config C4 --gpus 1` is the same batch on one GPU (the anchor of the scaling curve; the
-        default N = 1 line carries it as "c4_batch").  Strong scaling: the batch is fixed, value = 8 n steps / time.
+        N = 1 line of --full carries it as "c4_batch").  Strong scaling: the batch is fixed, value = 8 n steps / time.
 
 Inputs (model, dC of every view) are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, the settle frames and W warm-up steps, the K timed steps, the outputs
+(--dump-outputs DIR) and the result line.  --full adds everything else the line has carried: the survey pass with hipEvents
+around every stage (stage_ms, roofline, dominant kernel timed inside the timed region), the unsettled and no-view-slot side
+runs, the other exchange and the compute / exchange split (N > 1), the 8-view anchor, the literal t_min = 0 run, the clustered
+scene, the training iteration and the CPU baseline (each still switched off by its --no-* option).
 """
 from __future__ import annotations
 
@@ -166,6 +172,38 @@ def cpu_baseline(t_min: float, order: int):
                       "bands (lists) and tiles (composite); depth order by qsort on one thread; fp64 adjoint)"}
 
 
+DUMP_GAUSSIANS = 1 << 16          # --dump-outputs: gradient rows written per array (all of them on smaller models)
+DUMP_PIXELS = 1 << 21             # pixels of the image / transmittance written (all of them up to 1920x1080)
+
+
+def dump_outputs(out_dir: str, r, seed: int) -> None:
+    """--dump-outputs: what the timed path returned after its last step, as float32 DIR/<name>.npy -- the image (3, H, W) and
+    transmittance (H, W) of the last view rendered and the parameter gradients as the step returns them (they accumulate over
+    every step of the run: the timed path never resets them).  Above DUMP_GAUSSIANS gaussians / DUMP_PIXELS pixels a sample
+    of rows / pixels is written instead (sorted, drawn from numpy's default_rng(seed)), so the same arguments always dump the
+    same elements: at most 59 x 4 x 2^16 + 16 x 2^21 bytes = 49 MB."""
+    import torch
+    hv = r._bench_hv
+    last = next((t for t, _ in (getattr(hv, "_tw", None) or []) if t.ctx is hv.last_ctx), r)   # the renderer of the last view
+    g = r.splatGrads                                             # the twins of a pipelined batch accumulate into r's buffer
+    n = g.Δmeans.shape[0]
+    H, W = last.transmittance.shape
+    dev = last.imageData.device
+    rng = np.random.default_rng(seed)
+    rows = torch.as_tensor(np.sort(rng.choice(n, DUMP_GAUSSIANS, replace=False)), device=dev) if n > DUMP_GAUSSIANS else None
+    pix = torch.as_tensor(np.sort(rng.choice(H * W, DUMP_PIXELS, replace=False)), device=dev) if H * W > DUMP_PIXELS else None
+    arrays = {}
+    for name, t in (("d_means", g.Δmeans), ("d_scales", g.Δscales), ("d_quaternions", g.Δquaternions), ("d_opacities", g.Δopacities),
+                    ("d_shs", g.Δshs)):
+        t = t.reshape(n, -1)
+        arrays[name] = t if rows is None else t.index_select(0, rows)
+    arrays["image"] = last.imageData if pix is None else last.imageData.reshape(3, H * W).index_select(1, pix)
+    arrays["transmittance"] = last.transmittance if pix is None else last.transmittance.reshape(H * W).index_select(0, pix)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(t.detach().to(torch.float32).cpu().numpy()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -204,6 +242,12 @@ def main():
     ap.add_argument("--pipeline-depth", type=int, default=3, help="view batches: views of a rank in flight at once (renderers / streams over the same model; 3: + 2 % over 2 at C4 on one GPU, 4 and 5 no better)")
     ap.add_argument("--own-renderer-in-flight", action="store_true", help="A/B: the pipelined view batches use the rank's own renderer + depth-1 new ones instead of depth new ones (measured slower: distributed.HipViewRenderer)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
+    ap.add_argument("--full", action="store_true", help="also run and report every measurement beside the headline (stage survey, "
+                    "roofline, side runs, exchange split, 8-view anchor, literal, clustered, training iteration, CPU baseline); "
+                    "off by default: a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path returned "
+                    "after its last step as DIR/<name>.npy (float32): the image and transmittance of the last view rendered and the "
+                    "accumulated parameter gradients (a fixed seeded sample of gaussians / pixels on large frames; < 64 MB in all)")
     args = ap.parse_args()
     if args.config is None:
         args.config = "C3" if args.gpus == 1 else "C4"
@@ -336,30 +380,32 @@ def main():
             dt = float(t.item())
         return dt
 
-    # Pass A (untimed survey): hipEvents around EVERY stage for a few steps -> per-stage table, dominant kernel.
+    # Pass A (untimed survey, --full): hipEvents around EVERY stage for a few steps -> per-stage table, dominant kernel.
     # Recording 18 events per frame costs ~3 % of a C3 frame, so the timed region below keeps only the dominant
-    # kernel's pair (gs_config.profile_stages = 2 + stage).
-    from gaussiansplat_amd.backend import STAGES
-    ra = make(args.t_min, 1)
-    ka = max(2 * len(batches), min(args.steps, 6))
-    timed(ra, ka, max(len(batches), min(args.warmup, 4)))
-    survey = stage_stats(ra)
-    stage_ms = {k: (s / c if c else 0.0) for k, (s, c) in survey.items()}
-    dom = max(stage_ms, key=stage_ms.get)
-    if world > 1:                                                          # every rank must time the same stage
-        di = torch.tensor([STAGES.index(dom)], device="cuda")
-        dist.broadcast(di, 0)
-        dom = STAGES[int(di.item())]
-    del ra
+    # kernel's pair (gs_config.profile_stages = 2 + stage).  A plain run records no events in its timed region.
     import gc
-    gc.collect()
-    torch.cuda.empty_cache()
+    from gaussiansplat_amd.backend import STAGES
+    dom, stage_ms, ka = None, {}, 0
+    if args.full:
+        ra = make(args.t_min, 1)
+        ka = max(2 * len(batches), min(args.steps, 6))
+        timed(ra, ka, max(len(batches), min(args.warmup, 4)))
+        survey = stage_stats(ra)
+        stage_ms = {k: (s / c if c else 0.0) for k, (s, c) in survey.items()}
+        dom = max(stage_ms, key=stage_ms.get)
+        if world > 1:                                                      # every rank must time the same stage
+            di = torch.tensor([STAGES.index(dom)], device="cuda")
+            dist.broadcast(di, 0)
+            dom = STAGES[int(di.item())]
+        del ra
+        gc.collect()
+        torch.cuda.empty_cache()
 
-    # Beside the headline (N = 1, single-view configs): the same K steps (a) on a FRESH renderer with the driver's W warm-up steps
-    # only -- no settle frames: what the first frames of a run cost (settle transient) -- and (b) without view slots: no
-    # launch-order history and no list caps, i.e. every frame rendered as if its camera had never been seen.
+    # Beside the headline (--full, N = 1, single-view configs): the same K steps (a) on a FRESH renderer with only the W warm-up
+    # steps -- no settle frames: what the first frames of a run cost (settle transient) -- and (b) without view
+    # slots: no launch-order history and no list caps, i.e. every frame rendered as if its camera had never been seen.
     side_runs = {}
-    if world == 1 and views_per_step == 1 and args.settle_frames > 0 and not args.no_view_slots:
+    if args.full and world == 1 and views_per_step == 1 and args.settle_frames > 0 and not args.no_view_slots:
         ru = make(args.t_min, 0)
         side_runs["ms_per_step_unsettled"] = timed(ru, args.steps, args.warmup) / args.steps * 1e3
         del ru
@@ -376,11 +422,14 @@ def main():
         gc.collect(); torch.cuda.empty_cache()
 
     # Pass B: THE timed region -- W warmup steps, then exactly K steps between barriers + synchronize.
-    r = make(args.t_min, 2 + STAGES.index(dom))
+    r = make(args.t_min, 2 + STAGES.index(dom) if dom else 0)
     dt = timed(r, args.steps, args.warmup, settle_frames=args.settle_frames)
     host_ms = host_enqueue["ms_per_step"]
-    dom_sum, dom_cnt = stage_stats(r)[dom]
-    dom_ms = dom_sum / dom_cnt if dom_cnt else 0.0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r, seed)
+    if dom:
+        dom_sum, dom_cnt = stage_stats(r)[dom]
+        dom_ms = dom_sum / dom_cnt if dom_cnt else 0.0
     lctx = r._bench_hv.last_ctx                              # the ctx of the last view rendered
     I = lctx.num_instances
     I1 = lctx.num_coarse_instances
@@ -391,7 +440,7 @@ def main():
     value = views_per_step * n * args.steps / dt / 1e6
     nranks = dist.get_world_size() if world > 1 else 1
     other = None
-    if world > 1:                                              # the other exchange, same renderer, same K steps, beside the headline
+    if world > 1 and args.full:                                # the other exchange, same renderer, same K steps, beside the headline
         head = sync_mode[0]
         sync_mode[0] = "factored" if head == "allreduce" else "allreduce"
         dt_o = timed(r, args.steps, max(2, args.warmup // 2))
@@ -402,7 +451,7 @@ def main():
         sync_mode[0] = head
     factored = world > 1 and args.grad_sync == "factored"
     split_record = None
-    if world > 1:
+    if world > 1 and args.full:
         # So that a shortfall against DESIGN.md's prediction can be split into compute and exchange from this one line:
         # (a) compute_ms -- the same K steps with every collective left out (per rank, and the slowest rank);
         # (b) exchange_ms -- the collectives of a step alone on the final gradient buffer, back to back, timed with events on the
@@ -457,26 +506,6 @@ def main():
     out = None
     if rank == 0:
         P, Tn, K = W * H, gx * gy, (deg + 1) ** 2
-        early = args.t_min > 0
-        pmc, pmc_src = _pmc_summary(args.config) if (abs(args.t_min - 1e-5) < 1e-12 or args.t_min == 0.0) else (None, None)
-        by = algorithmic_bytes(dom, n, I, I1, wf, wb, P, Tn, K, ls["listed"])
-        ach = by / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        dom_pmc = _pmc_entry(pmc, dom, early)
-        dom_valu = valu_view(dom_pmc, dom_ms, pmc_src)
-        # a kernel is called VALU-bound only on counter evidence of THIS build: its share of the VALU issue peak above its share of HBM peak
-        bound = "valu" if dom_valu and dom_valu["valu_issue_frac"] > ach / HBM_PEAK_GBS else "hbm"
-        stages = {}
-        for st, ms in stage_ms.items():
-            if ms <= 0:
-                continue
-            b = algorithmic_bytes(st, n, I, I1, wf, wb, P, Tn, K, ls["listed"])
-            e = {"algorithmic_bytes": b, "ms": round(ms, 5), "achieved_GBs": round(b / (ms * 1e-3) / 1e9, 1), "frac": round(b / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-            v = valu_view(_pmc_entry(pmc, st, early), ms, pmc_src)
-            if v:
-                e["valu_issue_frac"] = round(v["valu_issue_frac"], 4)
-                e["mean_waves_per_simd"] = v["mean_waves_per_simd"]
-                e["bound"] = "valu" if v["valu_issue_frac"] > e["frac"] else "hbm"
-            stages[st] = e
         single = views_per_step == 1
         if single:
             what = (f"{args.config}: {n} gaussians, {W}x{H}, SH{deg}, ONE camera view per step, fwd+bwd; the steps cycle over the cameras "
@@ -513,25 +542,46 @@ def main():
                        "list_cap": args.list_cap, "bin_path_of_frame": lctx.bin_path_of_frame(), "host_enqueue_ms_per_step": round(host_ms, 4), "tile_parts": tile_parts, "lists_capped": ls["capped"], "listed_entries": ls["listed"], "list_segments_appended_by_waves": ls["extended_segments"],
                        "evaluated_fwd": wc["evaluated_fwd"], "evaluated_bwd": wc["evaluated_bwd"], "counters_of": "the last view rendered",
                        "seed": seed},
-            "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
-            "stage_ms_note": f"survey pass ({ka} steps, hipEvents around every stage, averaged over the views rendered; not the timed region)",
-            "roofline": {"kernel": dom, "bound": bound, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                         "traffic": dom_pmc.get("hbm_bytes_total") if dom_pmc else None, "algorithmic_bytes": by, "avg_ms": dom_ms, "launches": dom_cnt,
-                         "valu": dom_valu, "csrc_sha": csrc_sha(), "stages": stages,
-                         "note": "achieved / frac: algorithmic HBM bytes over the kernel time, against the 8 TB/s spec peak, as BASELINE.json "
-                                 "asks -- for every stage under `stages`.  avg_ms: hipEvents around the kernel launch on the ctx stream, inside "
-                                 "the timed region.  traffic (HBM bytes per launch, FETCH_SIZE x2 + WRITE_SIZE), valu and `bound` come from "
-                                 "the rocprofv3 --pmc summary under profiles/ stamped with this csrc_sha (else null / 'hbm'): bound = 'valu' when "
-                                 "the kernel's share of the VALU issue peak (1024 SIMDs x 1 wave64 instruction per 2 cycles) exceeds its share of "
-                                 "the HBM peak (DESIGN.md s5)"},
         }
-        out["roofline"]["loop_cost"] = loop_cost_model(dom, dom_ms, wc["evaluated_bwd"] if dom == "composite_bwd" else wc["evaluated_fwd"])
+        if dom:                                                # --full: the survey's stage table and the dominant kernel's roofline
+            early = args.t_min > 0
+            pmc, pmc_src = _pmc_summary(args.config) if (abs(args.t_min - 1e-5) < 1e-12 or args.t_min == 0.0) else (None, None)
+            by = algorithmic_bytes(dom, n, I, I1, wf, wb, P, Tn, K, ls["listed"])
+            ach = by / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+            dom_pmc = _pmc_entry(pmc, dom, early)
+            dom_valu = valu_view(dom_pmc, dom_ms, pmc_src)
+            # a kernel is called VALU-bound only on counter evidence of THIS build: its share of the VALU issue peak above its share of HBM peak
+            bound = "valu" if dom_valu and dom_valu["valu_issue_frac"] > ach / HBM_PEAK_GBS else "hbm"
+            stages = {}
+            for st, ms in stage_ms.items():
+                if ms <= 0:
+                    continue
+                b = algorithmic_bytes(st, n, I, I1, wf, wb, P, Tn, K, ls["listed"])
+                e = {"algorithmic_bytes": b, "ms": round(ms, 5), "achieved_GBs": round(b / (ms * 1e-3) / 1e9, 1), "frac": round(b / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+                v = valu_view(_pmc_entry(pmc, st, early), ms, pmc_src)
+                if v:
+                    e["valu_issue_frac"] = round(v["valu_issue_frac"], 4)
+                    e["mean_waves_per_simd"] = v["mean_waves_per_simd"]
+                    e["bound"] = "valu" if v["valu_issue_frac"] > e["frac"] else "hbm"
+                stages[st] = e
+            out["stage_ms"] = {k: round(v, 4) for k, v in stage_ms.items()}
+            out["stage_ms_note"] = f"survey pass ({ka} steps, hipEvents around every stage, averaged over the views rendered; not the timed region)"
+            out["roofline"] = {"kernel": dom, "bound": bound, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                               "traffic": dom_pmc.get("hbm_bytes_total") if dom_pmc else None, "algorithmic_bytes": by, "avg_ms": dom_ms, "launches": dom_cnt,
+                               "valu": dom_valu, "csrc_sha": csrc_sha(), "stages": stages,
+                               "note": "achieved / frac: algorithmic HBM bytes over the kernel time, against the 8 TB/s spec peak, as BASELINE.json "
+                                       "asks -- for every stage under `stages`.  avg_ms: hipEvents around the kernel launch on the ctx stream, inside "
+                                       "the timed region.  traffic (HBM bytes per launch, FETCH_SIZE x2 + WRITE_SIZE), valu and `bound` come from "
+                                       "the rocprofv3 --pmc summary under profiles/ stamped with this csrc_sha (else null / 'hbm'): bound = 'valu' when "
+                                       "the kernel's share of the VALU issue peak (1024 SIMDs x 1 wave64 instruction per 2 cycles) exceeds its share of "
+                                       "the HBM peak (DESIGN.md s5)"}
+            out["roofline"]["loop_cost"] = loop_cost_model(dom, dom_ms, wc["evaluated_bwd"] if dom == "composite_bwd" else wc["evaluated_fwd"])
         if other:
             out["factored_exchange" if other["grad_sync"] == "factored" else "allreduce_exchange"] = other
         if split_record:
             out.update({"compute_ms": split_record["compute_ms"], "exchange_ms": split_record["exchange_ms"]})
             out["compute_exchange_split"] = split_record
-    extras = world == 1 and views_per_step == 1
+    extras = args.full and world == 1 and views_per_step == 1
     if extras and not args.no_c4_anchor and args.config == "C3":
         # the N = 1 anchor of the C4 scaling curve, in the same run: the 8-view batch on one GPU, gradients accumulating
         v8 = list(range(8))
@@ -627,7 +677,7 @@ def main():
         out["train_iteration"]["ms_with_fused_backward_sgd"] = (time.perf_counter() - t0) / kt * 1e3
         del rt
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:                # rank 0, N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0, N = 1 only
             out["cpu_baseline"] = cpu_baseline(args.t_min, args.order)
         print(json.dumps(out), flush=True)
     if world > 1:

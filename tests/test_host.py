@@ -87,6 +87,39 @@ def test_bench_self_launch_command():
     assert cmd[-6:] == ["--gpus", "4", "--steps", "7", "--backend", "gloo"] and cmd[-7].endswith("bench.py")
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample_in_float32(tmp_path):
+    """bench.py --dump-outputs: above DUMP_GAUSSIANS gaussians / DUMP_PIXELS pixels a seeded sample of rows / pixels, the same
+    for the same seed, float32, and under 64 MB in all at the largest stated size (5 M gaussians at 3840x2160, SH3)."""
+    import os
+    import sys
+    from types import SimpleNamespace
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    n, H, W, K = bench.DUMP_GAUSSIANS + 1000, 1500, 1500, 48
+    flat = torch.randn(n * (11 + K), generator=torch.Generator().manual_seed(5))
+    views, o = {}, 0
+    for name, k in (("Δmeans", 3), ("Δscales", 3), ("Δquaternions", 4), ("Δopacities", 1), ("Δshs", K)):
+        views[name] = flat[o:o + k * n].view(n, k)
+        o += k * n
+    ctx = object()
+    r = SimpleNamespace(splatGrads=SimpleNamespace(flat=flat, **views), imageData=torch.rand(3, H, W), transmittance=torch.rand(H, W),
+                        ctx=ctx, _bench_hv=SimpleNamespace(last_ctx=ctx))
+    bench.dump_outputs(str(tmp_path / "a"), r, 7)
+    bench.dump_outputs(str(tmp_path / "b"), r, 7)
+    names = ["d_means", "d_scales", "d_quaternions", "d_opacities", "d_shs", "image", "transmittance"]
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f + ".npy" for f in names)
+    rng = np.random.default_rng(7)
+    rows = np.sort(rng.choice(n, bench.DUMP_GAUSSIANS, replace=False))
+    pix = np.sort(rng.choice(H * W, bench.DUMP_PIXELS, replace=False))
+    for f in names:
+        a, b = np.load(tmp_path / "a" / (f + ".npy")), np.load(tmp_path / "b" / (f + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b), f
+    assert np.array_equal(np.load(tmp_path / "a" / "d_shs.npy"), views["Δshs"].numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "image.npy"), r.imageData.reshape(3, -1).numpy()[:, pix])
+    assert np.array_equal(np.load(tmp_path / "a" / "transmittance.npy"), r.transmittance.reshape(-1).numpy()[pix])
+    assert (59 * 4 * bench.DUMP_GAUSSIANS + 16 * bench.DUMP_PIXELS) < 64 * 2 ** 20
+
 def test_view_record_is_kept_with_the_camera_and_follows_its_fields():
     """renderer._set_view (the host side of preprocess(renderer, camera), forward.jl:35-53): a small frame is bound by its caller, so the
     view's matrices (computeTransform / computeProjection, camera.jl:53-111) are built once per camera and again whenever one of its

@@ -2,7 +2,7 @@
 # Same-box A/B of library variants (payload row size x work classes of the launch order): composite kernel time and HBM traffic.
 #   python -m gaussiansplat_amd.build --tag p48b16 -DGS_LPT_BUCKETS=16 ; ... --tag p64b32 -DGS_PAYLOAD_QUADS=4 ; ... ; tools/ab_traffic.sh
 export TMPDIR=/tmp
-B="python3 bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-literal --no-train-iteration --no-c4-anchor"
+B="python3 bench.py --full --steps 12 --warmup 4 --no-cpu-baseline --no-literal --no-train-iteration --no-c4-anchor"
 for lib in lib lib_p48b16 lib_p64b32 lib_p64b16 lib; do
   export GSPLAT_HIP_LIB=$PWD/gaussiansplat_amd/$lib/libgsplat_hip.so
   O=$PWD/gpurun_out/abt_$lib; rm -rf $O; mkdir -p $O

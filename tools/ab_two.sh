@@ -4,7 +4,7 @@ A=$PWD/$1; B=$PWD/$2; CFGS=${3:-"C3 C5"}
 for rep in 1 2 3; do
   for lib in $A $B; do
     for c in $CFGS; do
-      GSPLAT_HIP_LIB=$lib timeout -k 10 200 python3 bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline --no-literal --no-train-iteration --no-c4-anchor 2>/dev/null | tail -1 | \
+      GSPLAT_HIP_LIB=$lib timeout -k 10 200 python3 bench.py --full --config $c --steps 20 --warmup 5 --no-cpu-baseline --no-literal --no-train-iteration --no-c4-anchor 2>/dev/null | tail -1 | \
         python3 -c "import json,sys; d=json.loads(sys.stdin.read()); s=d['stage_ms']; print('$(basename $(dirname $lib))', '$c', 'ms/frame %.4f' % d['ms_per_step'], 'fwd %.4f bwd %.4f tile_sort %.4f' % (s['composite_fwd'], s['composite_bwd'], s['tile_sort']))"
     done
   done

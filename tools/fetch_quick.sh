@@ -4,7 +4,7 @@ set -e -o pipefail
 export TMPDIR=/tmp
 [ -n "$1" ] && export GSPLAT_HIP_LIB=$PWD/$1/libgsplat_hip.so
 D=$PWD/gpurun_out/fetchq_$(basename ${1:-lib}); mkdir -p $D
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D -- python3 bench.py --steps 20 --warmup 4 --no-cpu-baseline --no-train-iteration --no-c4-anchor --no-literal > $D/run.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D -- python3 bench.py --full --steps 20 --warmup 4 --no-cpu-baseline --no-train-iteration --no-c4-anchor --no-literal > $D/run.log 2>&1
 python3 - "$D" <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(list)

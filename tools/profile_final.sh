@@ -15,7 +15,8 @@ python3 tools/pmc_summary.py $O/pmc_summary.json $O/pmc_valu $O/pmc_fetch $O/pmc
 find $O/stats -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \;
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*counter_collection.csv" -delete
 grep us_per_call $O/loss_stats.log | tail -1
-python3 bench.py --steps 100 --warmup 10 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-for c in C1 C2 C5; do python3 bench.py --config $c --steps 40 --warmup 6 --no-cpu-baseline > gpurun_out/${TAG}_bench_$c.json 2> gpurun_out/${TAG}_bench_$c.err; done
-python3 bench.py --config C4 --steps 20 --warmup 4 --no-cpu-baseline > gpurun_out/${TAG}_bench_C4.json 2> gpurun_out/${TAG}_bench_C4.err
+D=$(dirname "$O")                    # the folder of every output above
+python3 bench.py --full --steps 100 --warmup 10 > $D/${TAG}_bench.json 2> $D/${TAG}_bench.err
+for c in C1 C2 C5; do python3 bench.py --full --config $c --steps 40 --warmup 6 --no-cpu-baseline > $D/${TAG}_bench_$c.json 2> $D/${TAG}_bench_$c.err; done
+python3 bench.py --full --config C4 --steps 20 --warmup 4 --no-cpu-baseline > $D/${TAG}_bench_C4.json 2> $D/${TAG}_bench_C4.err
 echo done
