@@ -29,7 +29,8 @@ SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs
            "gs_comm_init", "gs_allreduce_grads", "gs_comm_destroy", "gs_color_grads_pack", "gs_sh_grads_from_views", "gs_grads_alloc", "gs_grads_read", "gs_num_gaussians", "gs_num_instances", "gs_get_array",
            "gs_get_stage_times", "gs_get_stage_stats", "gs_get_work_counters", "gs_get_work_counters_ex", "gs_debug_time_composite",
            "gs_debug_tile_clock", "gs_debug_clock_mhz", "gs_rank_probe_result", "gs_num_rounds", "gs_set_view_slot", "gs_num_coarse_instances",
-           "gs_get_list_stats", "gs_get_tile_parts", "gs_get_bin_path", "gs_debug_set_window", "gs_debug_tile_clock_rows")
+           "gs_get_list_stats", "gs_get_tile_parts", "gs_get_bin_path", "gs_debug_set_window", "gs_debug_tile_clock_rows",
+           "gs_adam_step", "gs_backward_adam")
 
 GS_ABI_VERSION = 3          # include/gsplat.h; load() refuses a library that reports another version
 GS_DEBUG_WIDE_CURSORS = 1
@@ -38,6 +39,9 @@ GS_DEBUG_SUPER16 = 8          # two-level binning: super-tiles of 16 x 16 tiles 
 GS_DEBUG_SUPER8 = 16          # ... of 8 x 8 tiles whatever the grid
 GS_DEBUG_TINY_CAPS = 4        # capped lists with the minimum cap on every tile (tests: every busy tile extends its list in the composite kernel)
 GS_MAX_VIEW_SLOTS = 4096
+GS_ADAM_GROUPS = 6            # lr[0] means, [1] scales, [2] quaternions, [3] opacities, [4] SH band 0, [5] SH bands >= 1
+GS_ADAM_SELECTIVE = 1         # step only the gaussians with a non-zero gradient float ("selective Adam")
+GS_ERR_INVALID, GS_ERR_UNSUPPORTED = -1, -5
 
 
 class GsConfig(C.Structure):
@@ -98,6 +102,9 @@ def load():
     L.gs_reset_grads.argtypes = [vp, C.POINTER(GsGrads)]
     L.gs_loss_l1_dssim.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, C.POINTER(C.c_double), C.c_int]
     L.gs_sgd_step.argtypes = [vp, C.c_float, C.POINTER(GsGrads)]
+    G = C.POINTER(GsGrads)
+    L.gs_adam_step.argtypes = [vp, G, G, G, fp, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_int]
+    L.gs_backward_adam.argtypes = [vp, vp, C.c_int, G, G, fp, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_int]
     L.gs_comm_unique_id.argtypes = [vp]
     L.gs_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gs_allreduce_grads.argtypes = [vp, C.POINTER(GsGrads)]
@@ -354,6 +361,22 @@ class Context:
 
     def sgd_step(self, lr: float, grads: GsGrads):
         self._chk(self.L.gs_sgd_step(self.h, lr, C.byref(grads)))
+
+    def adam_step(self, grads: GsGrads, exp_avg: GsGrads, exp_avg_sq: GsGrads, lr, beta1: float, beta2: float, eps: float, step: int,
+                  selective: bool = False, flags: "int | None" = None):
+        """gs_adam_step: Adam on the resident model from the gradients of `grads` (a NULL array freezes its group); exp_avg /
+        exp_avg_sq: caller-owned moment arrays of the same layout; lr: GS_ADAM_GROUPS rates; step counts from 1."""
+        lr6 = (C.c_float * GS_ADAM_GROUPS)(*[float(x) for x in lr])
+        f = (GS_ADAM_SELECTIVE if selective else 0) if flags is None else int(flags)
+        self._chk(self.L.gs_adam_step(self.h, C.byref(grads), C.byref(exp_avg), C.byref(exp_avg_sq), lr6, beta1, beta2, eps, int(step), f))
+
+    def backward_adam(self, dC_ptr: int, exp_avg: GsGrads, exp_avg_sq: GsGrads, lr, beta1: float, beta2: float, eps: float, step: int,
+                      selective: bool = False, flags: "int | None" = None):
+        """gs_backward_adam: backward and gs_adam_step in one pass on the resident model (3-D renderer); dC on the device."""
+        lr6 = (C.c_float * GS_ADAM_GROUPS)(*[float(x) for x in lr])
+        f = (GS_ADAM_SELECTIVE if selective else 0) if flags is None else int(flags)
+        self._chk(self.L.gs_backward_adam(self.h, C.c_void_p(int(dC_ptr)), GS_MEM_DEVICE, C.byref(exp_avg), C.byref(exp_avg_sq), lr6,
+                                          beta1, beta2, eps, int(step), f))
 
     def reset_grads(self, grads: GsGrads):
         self._chk(self.L.gs_reset_grads(self.h, C.byref(grads)))

@@ -39,6 +39,8 @@ SOURCES = {
     "gs_composite.hip": ["-fno-slp-vectorize"],
     # the SLP vectoriser turns the stencil into v_pk_* (no faster than two plain ops on gfx950) plus 270 register moves per loop body
     "gs_loss.hip": ["-fno-slp-vectorize"],
+    # Adam: the per-float update must round exactly as documented in include/gsplat.h (and as gs_sh_bwd_kernel's fused form does)
+    "gs_adam.hip": ["-ffp-contract=off"],
     "gs_api.hip": [],
     "gs_api_bin.hip": [],
     "gs_api_composite.hip": [],

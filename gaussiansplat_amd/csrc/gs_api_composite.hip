@@ -208,7 +208,8 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
 
 int gs_backward(gs_ctx *c, const float *dC, int mem, const gs_grads *grads) { return gs_backward_ex(c, dC, mem, grads, 0); }
 
-static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *grads, int flags, float sgd_scale);
+static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *grads, int flags, float sgd_scale,
+                         const GsAdamFused *adam = nullptr, int adam_mode = 0);
 int gs_backward_ex(gs_ctx *c, const float *dC, int mem, const gs_grads *grads, int flags) { return backward_impl(c, dC, mem, grads, flags, 0.0f); }
 
 // backward + SGD in one pass: the per-gaussian kernels apply param = fma(-lr, gradient, param) to the resident model instead
@@ -225,7 +226,34 @@ int gs_backward_sgd(gs_ctx *c, const float *dC, int mem, float lr) {
     return rc;
 }
 
-static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *grads, int flags, float sgd_scale) {
+// backward + Adam in one pass (gs_sh_bwd_kernel<.., ADAM>): the OVERWRITE backward whose per-gaussian kernel steps p, m and v with each
+// gradient float instead of storing it -- bit-identical to gs_backward_ex(GS_BWD_OVERWRITE) + gs_adam_step, without the gradient's store
+// and re-read.  The checks come first: a refused call enqueues nothing.
+int gs_backward_adam(gs_ctx *c, const float *dC, int mem, const gs_grads *exp_avg, const gs_grads *exp_avg_sq, const float lr[GS_ADAM_GROUPS],
+                     float beta1, float beta2, float eps, int64_t step, int flags) {
+    if (!c) return GS_ERR_INVALID;
+    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_backward_adam: 3-D renderer only");
+    if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_backward: gs_forward first");
+    if (!dC || !exp_avg || !exp_avg_sq) return fail(c, GS_ERR_INVALID, "gs_backward_adam: NULL argument");
+    GsAdamFused ad{};
+    float *m[5] = {exp_avg->d_means, exp_avg->d_scales, exp_avg->d_quats, exp_avg->d_opacities, exp_avg->d_shs};
+    float *v[5] = {exp_avg_sq->d_means, exp_avg_sq->d_scales, exp_avg_sq->d_quats, exp_avg_sq->d_opacities, exp_avg_sq->d_shs};
+    for (int i = 0; i < 5; ++i) {
+        if (!m[i] || !v[i]) return fail(c, GS_ERR_INVALID, "gs_backward_adam: all ten moment arrays must be non-NULL");
+        ad.m[i] = m[i]; ad.v[i] = v[i];
+    }
+    const float *p[5] = {c->means, c->scales, c->quats, c->opac, c->shs};
+    const int rc0 = gs_adam_prepare(c, "gs_backward_adam", p, nullptr, m, v, lr, beta1, beta2, eps, step, flags, &ad.h);
+    if (rc0 != GS_OK) return rc0;
+    gs_grads g{const_cast<float *>(c->means), const_cast<float *>(c->scales), const_cast<float *>(c->quats),
+               const_cast<float *>(c->opac), const_cast<float *>(c->shs)};
+    const int rc = backward_impl(c, dC, mem, &g, GS_BWD_OVERWRITE, 0.0f, &ad, (flags & GS_ADAM_SELECTIVE) ? 2 : 1);
+    if (rc == GS_OK) c->did_pre = c->did_bin = c->did_fwd = c->did_bwd = false;       // the model changed
+    return rc;
+}
+
+static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *grads, int flags, float sgd_scale, const GsAdamFused *adam,
+                         int adam_mode) {
     if (!c) return GS_ERR_INVALID;
     if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_backward: gs_forward first");
     const bool params_only = (flags & GS_BWD_PARAMS_ONLY) != 0, composite_only = (flags & GS_BWD_COMPOSITE_ONLY) != 0;
@@ -329,7 +357,7 @@ static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *gr
     b.d_opac = grads->d_opacities; b.d_shs = grads->d_shs;
     {
         StageTimer t(c, GS_STAGE_PREPROCESS_BWD);
-        HIPCHK(c, gs_launch_preprocess_bwd(b, c->cam, c->stream, chain ? chain : 3));
+        HIPCHK(c, gs_launch_preprocess_bwd(b, c->cam, c->stream, chain ? chain : 3, adam, adam_mode));
     }
     if (mem == GS_MEM_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));   // dC host buffer no longer needed
     c->did_bwd = true;

@@ -371,6 +371,8 @@ int gs_composite_grid_blocks(const GsCompositeArgs &a, int bwd);      // workgro
 hipError_t gs_launch_composite_fwd(const GsCompositeArgs &a, hipStream_t s);
 hipError_t gs_launch_composite_bwd(const GsCompositeArgs &a, hipStream_t s);
 
+#include "gs_adam.h"
+
 struct GsPreprocessBwdArgs {
     int64_t n;
     int sh_degree;
@@ -383,8 +385,10 @@ struct GsPreprocessBwdArgs {
     float sgd_scale;      // != 0 (accumulate mode only): target = fma(sgd_scale, gradient, target) -- with the parameter arrays as
                           // targets and sgd_scale = -lr this IS the SGD step, fused (gs_backward_sgd)
 };
-// phases: bit 0 the SH / colour kernel (d_shs, dpc), bit 1 the geometry chain (reads dpc); 3 = both, in that order
-hipError_t gs_launch_preprocess_bwd(const GsPreprocessBwdArgs &a, const GsCamera &cam, hipStream_t s, int phases = 3);
+// phases: bit 0 the SH / colour kernel (d_shs, dpc), bit 1 the geometry chain (reads dpc); 3 = both, in that order.
+// adam_mode 1 (dense) / 2 (selective), with adam and phases = 3 and overwrite = 1: the fused backward + Adam (gs_backward_adam)
+hipError_t gs_launch_preprocess_bwd(const GsPreprocessBwdArgs &a, const GsCamera &cam, hipStream_t s, int phases = 3,
+                                    const GsAdamFused *adam = nullptr, int adam_mode = 0);
 
 // colour-factored gradient exchange (gs_preprocess_bwd.hip)
 hipError_t gs_launch_pack_drgb(const float *g2d, const long long *g2d_fixed, float *out, int64_t n, hipStream_t s);

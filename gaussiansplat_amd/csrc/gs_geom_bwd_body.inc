@@ -1,8 +1,9 @@
 // gs_geom_bwd_body.inc -- the geometry chain of gaussian g, as TEXT included into a kernel body inside do { ... } while (0):
 // gs_geom_bwd_kernel (d L / d tps through the colour read back from a.dpc) and the fused form of gs_sh_bwd_kernel (handed over in
 // registers).  Expects: a (GsPreprocessBwdArgs), cam (GsCamera), g, g2f (float[10], the gaussian's row of 2-D gradients), OVERWRITE,
-// and the macro GS_GEOM_DPC (a float4 expression).  Text, not a function: as a __forceinline__ function the same statements took 186
-// VGPRs instead of 148 (two waves per SIMD instead of three).  Contraction is off: which products the compiler fuses into fma depends on
+// and the macro GS_GEOM_DPC (a float4 expression); with GS_GEOM_ADAM defined (gs_sh_bwd_kernel) also ADAM, ad (GsAdamFused), sh (the
+// thread's row of SH gradients in the LDS tile), K and srow_live -- ADAM != 0 steps p, m, v with the gradients instead of storing them.
+// Text, not a function: as a __forceinline__ function the same statements took 186 VGPRs instead of 148 (two waves per SIMD instead of three).  Contraction is off: which products the compiler fuses into fma depends on
 // the code around them, and both kernels must produce the same bits (a backward in two steps == a backward in one, tests/test_gpu_multiview.py).
 #pragma clang fp contract(off)
     const float *T = cam.T, *P = cam.P;
@@ -141,6 +142,45 @@
     for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int i = 0; i < 4; ++i) dt[j] += P[i + 4 * j] * dp[i];
+#ifdef GS_GEOM_ADAM
+    if constexpr (ADAM != 0) {
+        // the eleven gradients exactly as the OVERWRITE instantiation below stores them (its quaternion row is 0 + v, added to zeros)
+        float gq[11];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) gq[j] = live ? (float)(T[4 * j] * dt[0] + T[1 + 4 * j] * dt[1] + T[2 + 4 * j] * dt[2] + T[3 + 4 * j] * dt[3]) : 0.0f;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) gq[3 + j] = live ? (float)(de[j] * e[j]) : 0.0f;
+        gq[6] = live ? add_exact(0.0f, (float)dw) : 0.0f; gq[7] = live ? add_exact(0.0f, (float)dx) : 0.0f;
+        gq[8] = live ? add_exact(0.0f, (float)dy) : 0.0f; gq[9] = live ? add_exact(0.0f, (float)dz) : 0.0f;
+        gq[10] = live ? (float)(gsig * sg * (1.0 - sg)) : 0.0f;
+        bool stepped = true;
+        if (ADAM == 2) {   // selective: live if any of the 11 + 3K gradient floats != 0 (the SH ones are this thread's row of the LDS tile)
+            bool any = false;
+#pragma unroll
+            for (int i = 0; i < 11; ++i) any = any || gq[i] != 0.0f;
+#pragma unroll
+            for (int i = 0; i < 3 * K; ++i) any = any || sh[i] != 0.0f;
+            srow_live[threadIdx.x] = any ? 1 : 0;
+            stepped = any;
+        }
+        if (stepped) {
+            float *pp[4] = {const_cast<float *>(a.means) + 3 * g, const_cast<float *>(a.scales) + 3 * g, const_cast<float *>(a.quats) + 4 * g,
+                            const_cast<float *>(a.opac) + g};
+            float *mp[4] = {ad.m[0] + 3 * g, ad.m[1] + 3 * g, ad.m[2] + 4 * g, ad.m[3] + g};
+            float *vp[4] = {ad.v[0] + 3 * g, ad.v[1] + 3 * g, ad.v[2] + 4 * g, ad.v[3] + g};
+            constexpr int first[5] = {0, 3, 6, 10, 11};
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int j = 0; j < first[q + 1] - first[q]; ++j) {
+                    float pv = pp[q][j], mv = mp[q][j], vv = vp[q][j];
+                    gs_adam_update(pv, mv, vv, gq[first[q] + j], ad.h, ad.h.step_size[q]);
+                    pp[q][j] = pv; mp[q][j] = mv; vp[q][j] = vv;
+                }
+        }
+    } else
+#endif
+    {
     if (a.d_means) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -164,4 +204,5 @@
     if (a.d_opac) {
         const float v = live ? (float)(gsig * sg * (1.0 - sg)) : 0.0f;
         if (OVERWRITE) { if (GS_NT_STORES > 1) __builtin_nontemporal_store(v, &a.d_opac[g]); else a.d_opac[g] = v; } else a.d_opac[g] = acc_or_step(a.d_opac[g], v, a.sgd_scale);
+    }
     }

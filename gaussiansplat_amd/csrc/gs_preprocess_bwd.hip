@@ -62,8 +62,12 @@ __device__ __forceinline__ float acc_or_step(float old, float v, float sgd_scale
 // FUSED: the geometry chain of the gaussian follows in the same thread (gs_backward's usual case: both phases) -- its row of 2-D gradients
 // and its mean are read once, d L / d tps stays in registers, one launch less.  The two-kernel form remains for callers that run the
 // phases apart (a multi-GPU host starts the exchange of the SH gradients between them).
-template <int DEG, bool OVERWRITE, bool FUSED>
-__global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, GsCamera cam) {
+// ADAM (with OVERWRITE and FUSED; gs_backward_adam): 1 dense, 2 selective -- where the OVERWRITE instantiation stores a gradient, the
+// same float steps p, m and v instead (gs_adam_update): the geometry rows in the thread, the SH rows in the coalesced loop behind the
+// LDS tile.  Every row is visited (dense Adam moves untouched rows too: the moments decay); selective mode decides liveness per
+// gaussian on all 11 + 3K gradient floats, as gs_adam_step does.
+template <int DEG, bool OVERWRITE, bool FUSED, int ADAM = 0>
+__global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, GsCamera cam, GsAdamFused ad) {
 #pragma clang fp contract(off)   // the fused and the two-kernel form must produce the same bits: no context-dependent fma formation
     constexpr int K = (DEG + 1) * (DEG + 1);
     constexpr int ROW = 3 * K + 1;
@@ -167,14 +171,61 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
         if (FUSED) {
             const float (&g2f)[10] = g2;
 #define GS_GEOM_DPC dpc_sh
+#define GS_GEOM_ADAM
             do {
 #include "gs_geom_bwd_body.inc"
             } while (0);
+#undef GS_GEOM_ADAM
 #undef GS_GEOM_DPC
         } else reinterpret_cast<float4 *>(a.dpc)[g] = dpc_sh;
     }
     __syncthreads();
-    if (a.d_shs) {
+    if constexpr (ADAM != 0) {
+        // p, m, v of the SH rows: group 4 for the first three floats of a row, 5 for the rest
+        const int64_t o = gb * 3 * K;
+        float *ps = const_cast<float *>(a.shs) + o, *ms = ad.m[4] + o, *vs = ad.v[4] + o;
+        const bool vec = VEC && ((reinterpret_cast<uintptr_t>(a.shs) | reinterpret_cast<uintptr_t>(ad.m[4]) | reinterpret_cast<uintptr_t>(ad.v[4])) & 15) == 0;
+        const float ss4 = ad.h.step_size[4], ss5 = ad.h.step_size[5];
+        // selective: the live rows compacted (a ballot per wave), so that every lane of the loops below steps a live float -- the
+        // correctly rounded update is ~55 VALU operations per float, which the masked lanes of a mixed wave would pay as well
+        int nrow = nb;
+        __shared__ int srow_order[ADAM == 2 ? 256 : 1], swave_live[16];
+        if constexpr (ADAM == 2) {
+            const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+            const bool l = threadIdx.x < nb && srow_live[threadIdx.x];
+            const unsigned long long b = __ballot(l);
+            if (lane == 0) swave_live[wv] = __popcll(b);
+            __syncthreads();
+            int off = 0;
+            nrow = 0;
+            for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { off += w < wv ? swave_live[w] : 0; nrow += swave_live[w]; }
+            if (l) srow_order[off + __popcll(b & ((1ull << lane) - 1ull))] = threadIdx.x;
+            __syncthreads();
+        }
+        if (vec) {
+            for (int c4 = threadIdx.x; c4 < nrow * (3 * K / 4); c4 += blockDim.x) {
+                const int ri = (c4 * 4) / (3 * K), j = (c4 * 4) % (3 * K);
+                const int row = ADAM == 2 ? srow_order[ri] : ri;
+                const int i4 = (row * 3 * K + j) / 4;
+                const float *t = tile + row * ROW + j;
+                float4 p = reinterpret_cast<float4 *>(ps)[i4], m = reinterpret_cast<float4 *>(ms)[i4], v = reinterpret_cast<float4 *>(vs)[i4];
+                gs_adam_update(p.x, m.x, v.x, t[0], ad.h, j < 3 ? ss4 : ss5);
+                gs_adam_update(p.y, m.y, v.y, t[1], ad.h, j + 1 < 3 ? ss4 : ss5);
+                gs_adam_update(p.z, m.z, v.z, t[2], ad.h, j + 2 < 3 ? ss4 : ss5);
+                gs_adam_update(p.w, m.w, v.w, t[3], ad.h, j + 3 < 3 ? ss4 : ss5);
+                reinterpret_cast<float4 *>(ps)[i4] = p; reinterpret_cast<float4 *>(ms)[i4] = m; reinterpret_cast<float4 *>(vs)[i4] = v;
+            }
+        } else {
+            for (int c = threadIdx.x; c < nrow * 3 * K; c += blockDim.x) {
+                const int ri = c / (3 * K), j = c % (3 * K);
+                const int row = ADAM == 2 ? srow_order[ri] : ri;
+                const int idx = row * 3 * K + j;
+                float p = ps[idx], m = ms[idx], v = vs[idx];
+                gs_adam_update(p, m, v, tile[row * ROW + j], ad.h, j < 3 ? ss4 : ss5);
+                ps[idx] = p; ms[idx] = m; vs[idx] = v;
+            }
+        }
+    } else if (a.d_shs) {
         if (vec_out) {
             float4 *dst = reinterpret_cast<float4 *>(a.d_shs + gb * 3 * K);
             for (int i4 = threadIdx.x; i4 < nb * (3 * K / 4); i4 += blockDim.x) {
@@ -320,14 +371,30 @@ hipError_t gs_launch_sh_from_views(int64_t n, int sh_degree, const float *means,
 #define GS_SHBWD_THREADS 256
 #endif
 static int sh_bwd_threads() { return GS_SHBWD_THREADS; }
-hipError_t gs_launch_preprocess_bwd(const GsPreprocessBwdArgs &a, const GsCamera &cam, hipStream_t s, int phases) {
+hipError_t gs_launch_preprocess_bwd(const GsPreprocessBwdArgs &a, const GsCamera &cam, hipStream_t s, int phases, const GsAdamFused *adam,
+                                    int adam_mode) {
     if (a.n <= 0) return hipSuccess;
     const int T = sh_bwd_threads();
     dim3 block(T), grid((unsigned)((a.n + T - 1) / T));
     const int K = (a.sh_degree + 1) * (a.sh_degree + 1);
     const size_t lds = sizeof(float) * T * (3 * K + 1);
-#define GS_SH2(D, F) do { if (a.overwrite) hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, F>), grid, block, lds, s, a, cam); \
-                         else hipLaunchKernelGGL((gs_sh_bwd_kernel<D, false, F>), grid, block, lds, s, a, cam); } while (0)
+    const GsAdamFused ad = adam ? *adam : GsAdamFused{};
+    if (adam_mode) {                                                   // fused backward + Adam: one launch, both phases
+        if (!adam || !a.overwrite || (phases & 3) != 3 || (adam_mode != 1 && adam_mode != 2)) return hipErrorInvalidValue;
+#define GS_SHA(D) do { if (adam_mode == 2) hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, true, 2>), grid, block, lds, s, a, cam, ad); \
+                       else hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, true, 1>), grid, block, lds, s, a, cam, ad); } while (0)
+        switch (a.sh_degree) {
+            case 0: GS_SHA(0); break;
+            case 1: GS_SHA(1); break;
+            case 2: GS_SHA(2); break;
+            case 3: GS_SHA(3); break;
+            default: return hipErrorInvalidValue;
+        }
+#undef GS_SHA
+        return hipGetLastError();
+    }
+#define GS_SH2(D, F) do { if (a.overwrite) hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, F>), grid, block, lds, s, a, cam, ad); \
+                         else hipLaunchKernelGGL((gs_sh_bwd_kernel<D, false, F>), grid, block, lds, s, a, cam, ad); } while (0)
 #define GS_SH(D) do { if (fused) GS_SH2(D, true); else GS_SH2(D, false); } while (0)
     const bool fused = (phases & 3) == 3;
     if (phases & 1)

@@ -1,0 +1,186 @@
+"""Adam on the device (gs_adam_step / gs_backward_adam), with per-group learning rates.
+
+The reference steps with plain SGD, one rate for everything (train.jl:42-46: `param .-= lr*Δparam`).  3-D splats live on very
+different scales (world-unit means, log scales, raw quaternions, logit opacities, SH band 0 vs the higher bands), so every 3DGS
+trainer uses Adam with rates that span about three orders of magnitude.  torch.optim.Adam cannot stand in: the SH band-0 and
+higher-band coefficients are interleaved inside one [n, 3K] row, so they cannot be two torch parameter groups.
+
+    opt = Adam.for_3dgs(renderer, scene_extent)          # or Adam(renderer, lr=1e-3 | {group: rate}, ...)
+    train.trainStep(renderer, gt, 0.0, loss, camera, optimizer=opt)
+
+The optimiser owns two flat moment buffers in the initGrads layout ([means | scales | quats | opacities | shs], the buffer
+distributed.multi_view_step returns) and the step count; the model is updated in place on the device.
+"""
+from __future__ import annotations
+
+import math
+
+from . import backend as B
+
+GROUPS_3D = ("means", "scales", "quaternions", "opacities", "sh_dc", "sh_rest")
+GROUPS_2D = ("means", "scales", "rotations", "opacities", "colors")     # colors -> lr[4]; lr[5] unused
+
+
+def _is_2d(renderer) -> bool:
+    from .renderer import GaussianRenderer2D
+    return isinstance(renderer, GaussianRenderer2D)
+
+
+def _check_rate(name: str, value) -> float:
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"Adam: lr[{name!r}] must be a number, got {value!r}") from None
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError(f"Adam: lr[{name!r}] must be finite and >= 0, got {v}")
+    return v
+
+
+class Adam:
+    """Adam(renderer, lr, betas=(0.9, 0.999), eps=1e-8, selective=False, fused=False).
+
+    lr: one rate for every group, or a dict with one rate per group -- 3-D: means, scales, quaternions, opacities, sh_dc (SH band 0,
+    the first three floats of a shs row), sh_rest (the higher bands); 2-D renderer: means, scales, rotations, opacities, colors.
+    selective: step only the gaussians with a non-zero gradient float (gs_adam_step's GS_ADAM_SELECTIVE).
+    fused (3-D): train.trainStep runs backward_step, the backward and the step in one pass (gs_backward_adam).
+    The rates may be changed between steps (set_lr), e.g. the exponential decay of the position rate."""
+
+    def __init__(self, renderer, lr=1e-3, betas=(0.9, 0.999), eps: float = 1e-8, selective: bool = False, fused: bool = False):
+        self.renderer = renderer
+        self.is_2d = _is_2d(renderer)
+        self.groups = GROUPS_2D if self.is_2d else GROUPS_3D
+        self.lr = self._rates(lr)
+        b1, b2 = (float(b) for b in betas)
+        for b in (b1, b2):
+            if not (0.0 <= b < 1.0):
+                raise ValueError(f"Adam: betas must lie in [0, 1), got {tuple(betas)}")
+        eps = float(eps)
+        if not math.isfinite(eps) or eps <= 0.0:
+            raise ValueError(f"Adam: eps must be finite and > 0, got {eps}")
+        if fused and self.is_2d:
+            raise ValueError("Adam: fused=True needs the 3-D renderer (gs_backward_adam)")
+        self.betas, self.eps, self.selective, self.fused = (b1, b2), eps, bool(selective), bool(fused)
+        self.step_count = 0
+        import torch
+        flat = renderer._splatGrads.flat
+        self.exp_avg = torch.zeros_like(flat)
+        self.exp_avg_sq = torch.zeros_like(flat)
+        g = renderer._splatGrads
+        views = (g.Δmeans, g.Δscales, g.Δrotations, g.Δopacities, g.Δcolors) if self.is_2d else \
+                (g.Δmeans, g.Δscales, g.Δquaternions, g.Δopacities, g.Δshs)
+        # floats from the start of the flat buffer to each of the five arrays (the initGrads layout)
+        self._offsets = tuple((v.data_ptr() - flat.data_ptr()) // 4 for v in views)
+        self._numel = flat.numel()
+
+    @classmethod
+    def for_3dgs(cls, renderer, scene_extent: float, selective: bool = False, fused: bool = False) -> "Adam":
+        """The 3DGS defaults (Kerbl et al. 2023): position rate scaled by the scene extent, eps 1e-15."""
+        lr = dict(means=1.6e-4 * float(scene_extent), scales=5e-3, quaternions=1e-3, opacities=5e-2, sh_dc=2.5e-3, sh_rest=1.25e-4)
+        return cls(renderer, lr, betas=(0.9, 0.999), eps=1e-15, selective=selective, fused=fused)
+
+    # -- rates
+    def _rates(self, lr) -> dict:
+        if isinstance(lr, dict):
+            unknown = sorted(set(lr) - set(self.groups))
+            if unknown:
+                raise ValueError(f"Adam: unknown parameter groups {unknown}; the groups are {list(self.groups)}")
+            missing = [k for k in self.groups if k not in lr]
+            if missing:
+                raise ValueError(f"Adam: no rate for the groups {missing}")
+            return {k: _check_rate(k, lr[k]) for k in self.groups}
+        v = _check_rate("*", lr)
+        return {k: v for k in self.groups}
+
+    def set_lr(self, lr=None, **rates):
+        """Replace every rate (lr: a number or a full dict) and/or some of them by name: set_lr(means=1e-5)."""
+        new = self._rates(lr) if lr is not None else dict(self.lr)
+        for k, v in rates.items():
+            if k not in self.groups:
+                raise ValueError(f"Adam: unknown parameter group {k!r}; the groups are {list(self.groups)}")
+            new[k] = _check_rate(k, v)
+        self.lr = new
+
+    def lr_vector(self) -> list:
+        """The GS_ADAM_GROUPS rates of the C ABI (2-D: lr[5] unused, 0)."""
+        v = [self.lr[k] for k in self.groups]
+        return v + [0.0] * (B.GS_ADAM_GROUPS - len(v))
+
+    # -- the buffers of the C ABI
+    def _struct(self, flat) -> B.GsGrads:
+        base = flat.data_ptr()
+        return B.GsGrads(*(base + 4 * o for o in self._offsets))
+
+    def _grads_struct(self, grads) -> B.GsGrads:
+        import torch
+        if grads is None:
+            self.renderer.splatGrads                       # a pending resetGrads zero-fills here: the step sees zeros, not stale values
+            return self.renderer._grads
+        if isinstance(grads, B.GsGrads):
+            return grads
+        if isinstance(grads, torch.Tensor):                # a flat buffer in the initGrads layout (distributed.multi_view_step)
+            if grads.numel() != self._numel or grads.dtype != torch.float32 or not grads.is_contiguous() or grads.device != self.exp_avg.device:
+                raise ValueError("Adam.step: grads must be a contiguous float32 flat gradient buffer of the renderer's layout on its device")
+            self._keep = grads
+            return self._struct(grads)
+        flat = getattr(grads, "flat", None)                # SplatGrads3D / SplatGrads2D
+        if flat is not None:
+            return self._grads_struct(flat)
+        raise TypeError("Adam.step: grads must be None, a flat tensor, a SplatGrads3D / 2D or a backend.GsGrads")
+
+    # -- steps
+    def step(self, grads=None):
+        """One Adam step from `grads` (default renderer.splatGrads); the model is updated in place on the device."""
+        g = self._grads_struct(grads)
+        r = self.renderer
+        t = self.step_count + 1
+        r._begin()
+        r.ctx.adam_step(g, self._struct(self.exp_avg), self._struct(self.exp_avg_sq), self.lr_vector(), self.betas[0], self.betas[1],
+                        self.eps, t, selective=self.selective)
+        r._end()
+        self.step_count = t
+
+    def backward_step(self, dC):
+        """Backward of the current frame and the Adam step in one pass (gs_backward_adam, 3-D renderer).  renderer.splatGrads is
+        not filled."""
+        import numpy as np
+        import torch
+        r = self.renderer
+        if self.is_2d:
+            raise ValueError("Adam.backward_step needs the 3-D renderer (gs_backward_adam)")
+        d = dC if isinstance(dC, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(dC, np.float32))
+        d = d.to(r.imageData.device, torch.float32).contiguous()
+        if tuple(d.shape) != tuple(r.imageData.shape):
+            raise ValueError("Adam.backward_step: dC must have the shape of renderer.imageData")
+        r._dC_keepalive = d
+        t = self.step_count + 1
+        r._begin()
+        r.ctx.backward_adam(d.data_ptr(), self._struct(self.exp_avg), self._struct(self.exp_avg_sq), self.lr_vector(), self.betas[0],
+                            self.betas[1], self.eps, t, selective=self.selective)
+        r._end()
+        self.step_count = t
+
+    # -- checkpoints
+    def state_dict(self) -> dict:
+        return dict(step=self.step_count, lr=dict(self.lr), betas=tuple(self.betas), eps=self.eps, selective=self.selective,
+                    fused=self.fused, exp_avg=self.exp_avg.detach().clone(), exp_avg_sq=self.exp_avg_sq.detach().clone())
+
+    def load_state_dict(self, state: dict):
+        import torch
+        for k in ("exp_avg", "exp_avg_sq"):
+            t = state[k]
+            if not isinstance(t, torch.Tensor) or t.numel() != self._numel:
+                raise ValueError(f"Adam.load_state_dict: {k} does not match this renderer's gradient layout ({self._numel} floats)")
+        step = int(state["step"])
+        if step < 0:
+            raise ValueError("Adam.load_state_dict: negative step")
+        lr = self._rates(state["lr"])
+        b1, b2 = (float(b) for b in state["betas"])
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError("Adam.load_state_dict: betas must lie in [0, 1)")
+        eps = float(state["eps"])
+        if not math.isfinite(eps) or eps <= 0.0:
+            raise ValueError("Adam.load_state_dict: eps must be finite and > 0")
+        self.exp_avg.copy_(state["exp_avg"].reshape(-1))
+        self.exp_avg_sq.copy_(state["exp_avg_sq"].reshape(-1))
+        self.step_count, self.lr, self.betas, self.eps = step, lr, (b1, b2), eps
+        self.selective = bool(state.get("selective", self.selective))

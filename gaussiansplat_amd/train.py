@@ -7,7 +7,8 @@ backward/SGD lines are commented out, train.jl:39-46); what it intends is implem
     preprocess -> compactIdxs -> forward -> loss + dL/dimage -> backward -> param .-= lr*grad -> resetGrads
 
 with the loss, its image gradient and the SGD update running on the GPU (csrc/gs_loss.hip) so the
-step has no host round trip.
+step has no host round trip.  `optimizer=optim.Adam(...)` replaces the SGD update by Adam with per-group rates
+(csrc/gs_adam.hip; fused with the backward when the optimiser was made with fused=True).
 """
 from __future__ import annotations
 
@@ -66,14 +67,27 @@ def getLossFunction(imSize, windowSize: int, nChannels: int, renderer=None, λ: 
     return LossFunction(renderer, imSize, windowSize, nChannels, λ)
 
 
-def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, want_loss: bool = True, fused_sgd: bool = False):
+def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, want_loss: bool = True, fused_sgd: bool = False,
+              optimizer=None):
     """One iteration of train.jl:33-56 as intended (see module docstring).
     fused_sgd (3-D renderer): backward and the parameter update in one pass (gs_backward_sgd) -- the same parameters bit for
-    bit (deterministic mode), but renderer.splatGrads is not filled."""
+    bit (deterministic mode), but renderer.splatGrads is not filled.
+    optimizer (optim.Adam): it does the parameter update instead of SGD and `lr` is ignored -- optimizer.backward_step when it
+    was made with fused=True (renderer.splatGrads then is not filled), else backward, optimizer.step() and resetGrads."""
+    if optimizer is not None and fused_sgd:
+        raise ValueError("trainStep: fused_sgd and optimizer exclude each other (make the optimiser with fused=True instead)")
     tps = R.preprocess(renderer, camera)
     R.compactIdxs(renderer)
     R.forward(renderer, tps)
     loss, ΔC = lossFunc.value_and_grad(renderer.imageData, gtimg, want_loss)
+    if optimizer is not None:
+        if optimizer.fused:
+            optimizer.backward_step(ΔC)
+            return loss
+        R.backward(renderer, ΔC)
+        optimizer.step()
+        R.resetGrads(renderer)
+        return loss
     if fused_sgd:
         renderer._dC_keepalive = ΔC
         renderer._begin()
@@ -88,11 +102,12 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
     return loss
 
 
-def train(renderer, gtimg, lr: float, lossFunc: LossFunction, iterations: int = 100, camera=None, log_every: int = 0):
-    """train.jl:16-59 without the GUI; the reference loops `while score < 0.99` on a score it never updates."""
+def train(renderer, gtimg, lr: float, lossFunc: LossFunction, iterations: int = 100, camera=None, log_every: int = 0, optimizer=None):
+    """train.jl:16-59 without the GUI; the reference loops `while score < 0.99` on a score it never updates.
+    optimizer: an optim.Adam that replaces the SGD update (lr is then ignored)."""
     losses = []
     for it in range(iterations):
-        l = trainStep(renderer, gtimg, lr, lossFunc, camera, want_loss=True)
+        l = trainStep(renderer, gtimg, lr, lossFunc, camera, want_loss=True, optimizer=optimizer)
         losses.append(l)
         if log_every and it % log_every == 0:
             print(f"loss : {l}")                             # loss.jl:69

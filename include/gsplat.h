@@ -335,6 +335,33 @@ int gs_loss_l1_dssim(gs_ctx *ctx, const float *img, const float *gt, int32_t W, 
 /* train.jl:42-46: param .-= lr * grad on the ctx's resident model arrays (DEVICE gradients). */
 int gs_sgd_step(gs_ctx *ctx, float lr, const gs_grads *grads);
 
+/* Adam on the ctx's resident model arrays, updated in place exactly like gs_sgd_step (the ctx's frame state is dropped: the next
+ * frame starts at gs_preprocess).  Six learning rates, one per parameter group:
+ *   lr[0] means, [1] scales, [2] quaternions, [3] opacities, [4] SH band 0 (floats 0..2 of a d_shs row), [5] SH bands >= 1
+ *   (floats 3..3K-1).  2-D renderer: means, scales, rotations, opacities, colors -> lr[4]; lr[5] is unused.
+ * Moments are caller-owned: exp_avg (m) and exp_avg_sq (v) are two gs_grads-shaped sets of DEVICE arrays with the parameters' layout
+ * (zero before the first step; checkpointing is the caller's copy of them).  t = step counts from 1.  The host computes, each in
+ * double and rounded to float once, omb1 = 1-beta1, omb2 = 1-beta2, step_size[grp] = lr[grp] / (1-beta1^t) and
+ * sqrt_bc2 = sqrt(1-beta2^t); every float is then stepped in float32, without fma contraction, with correctly rounded sqrt and '/':
+ *   m = beta1*m + omb1*g;   v = beta2*v + (omb2*g)*g;   p = p - step_size[grp] * (m / (sqrt(v)/sqrt_bc2 + eps))
+ * (torch.optim.Adam's order; torch forms m with lerp, so it agrees to rounding, this statement bit for bit).
+ * Frozen groups: a NULL array in `grads` leaves that group's p, m and v untouched; a non-NULL gradient array with a NULL moment array
+ * is GS_ERR_INVALID.  lr[grp] = 0 leaves p unchanged and still updates m and v.
+ * GS_ADAM_SELECTIVE: a gaussian is live if any float of its non-NULL gradient rows (11 + 3K for 3-D) compares != 0.0f (-0 is dead,
+ * NaN live); the p, m and v rows of a dead gaussian are neither read nor written.  Without the flag every row is stepped (torch).
+ * GS_ERR_INVALID, with nothing written: step < 1, a beta outside [0, 1), eps not finite or not > 0, an lr negative or not finite,
+ * unknown flag bits, or any two of the stepped p, g, m, v arrays overlapping. */
+#define GS_ADAM_GROUPS 6
+#define GS_ADAM_SELECTIVE 1
+int gs_adam_step(gs_ctx *ctx, const gs_grads *grads, const gs_grads *exp_avg, const gs_grads *exp_avg_sq,
+                 const float lr[GS_ADAM_GROUPS], float beta1, float beta2, float eps, int64_t step, int flags);
+/* Backward AND gs_adam_step in one pass (3-D renderer: the 2-D one gets GS_ERR_UNSUPPORTED; needs gs_forward on the frame, as
+ * gs_backward does): the per-gaussian kernels step p, m and v where gs_backward would store the gradient, which never reaches memory.
+ * All ten moment arrays must be non-NULL; no gradient buffer is filled.  Contract: the result is bit-identical to
+ * gs_backward_ex(GS_BWD_OVERWRITE) into a scratch gs_grads followed by gs_adam_step with the same arguments, dense and selective. */
+int gs_backward_adam(gs_ctx *ctx, const float *dC, int mem, const gs_grads *exp_avg, const gs_grads *exp_avg_sq,
+                     const float lr[GS_ADAM_GROUPS], float beta1, float beta2, float eps, int64_t step, int flags);
+
 /* ---- introspection (parity tests, profiling) ------------------------------------------- */
 
 typedef enum {

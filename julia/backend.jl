@@ -227,6 +227,27 @@ end
 hip_sgdStep!(r::HipRenderer, lr::Real, grads::GsGrads) =
     check(r, ccall((:gs_sgd_step, libgs), Cint, (Ptr{Cvoid}, Cfloat, Ref{GsGrads}), r.ctx, lr, grads))
 
+# Adam with six rates (gs_adam_step): lr = Float32[means, scales, quaternions, opacities, SH band 0, SH bands >= 1].  expAvg / expAvgSq
+# are caller-owned moment buffers with the gradients' layout (e.g. two more hip_initGrads-style flat buffers, zeroed); `step` counts
+# from 1 and is the caller's to keep.  A C_NULL gradient array freezes its group.
+const GS_ADAM_GROUPS = 6
+const GS_ADAM_SELECTIVE = Cint(1)
+function hip_adamStep!(r::HipRenderer, grads::GsGrads, expAvg::GsGrads, expAvgSq::GsGrads, lr::Vector{Float32}, step::Integer;
+                       beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-8, selective = false)
+    length(lr) == GS_ADAM_GROUPS || throw(ArgumentError("lr: $GS_ADAM_GROUPS rates"))
+    check(r, ccall((:gs_adam_step, libgs), Cint,
+                   (Ptr{Cvoid}, Ref{GsGrads}, Ref{GsGrads}, Ref{GsGrads}, Ptr{Float32}, Cfloat, Cfloat, Cfloat, Int64, Cint),
+                   r.ctx, grads, expAvg, expAvgSq, lr, beta1, beta2, eps, Int64(step), selective ? GS_ADAM_SELECTIVE : Cint(0)))
+end
+# backward and Adam in one pass (gs_backward_adam, 3-D renderer; after hip_forward! of the frame); no gradient buffer is filled
+function hip_backward_adam!(r::HipRenderer, ΔC::Array{Float32, 3}, expAvg::GsGrads, expAvgSq::GsGrads, lr::Vector{Float32}, step::Integer;
+                            beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-8, selective = false)
+    length(lr) == GS_ADAM_GROUPS || throw(ArgumentError("lr: $GS_ADAM_GROUPS rates"))
+    check(r, ccall((:gs_backward_adam, libgs), Cint,
+                   (Ptr{Cvoid}, Ptr{Float32}, Cint, Ref{GsGrads}, Ref{GsGrads}, Ptr{Float32}, Cfloat, Cfloat, Cfloat, Int64, Cint),
+                   r.ctx, ΔC, GS_MEM_HOST, expAvg, expAvgSq, lr, beta1, beta2, eps, Int64(step), selective ? GS_ADAM_SELECTIVE : Cint(0)))
+end
+
 # ---- plumbing and introspection -----------------------------------------------------------------------------------
 
 # enqueue on an existing hipStream_t (C_NULL: the ctx's own stream)

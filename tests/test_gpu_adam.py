@@ -1,0 +1,386 @@
+"""Adam on the device (gs_adam_step, gs_backward_adam, optim.Adam): bit for bit against the NumPy restatement of include/gsplat.h
+(tests/adam_ref.py), against torch.optim.Adam to rounding, the fused backward + Adam against the backward followed by the step, and
+the argument checks."""
+import numpy as np
+import pytest
+
+import adam_ref as A
+from common import rel_l2
+
+pytestmark = pytest.mark.gpu
+
+LR6 = (1e-3, 4e-3, 2e-3, 5e-2, 2.5e-3, 1.25e-4)
+RATES = dict(means=1e-3, scales=4e-3, quaternions=2e-3, opacities=5e-2, sh_dc=2.5e-3, sh_rest=1.25e-4)
+B1, B2, EPS = 0.9, 0.999, 1e-8
+W, H = 128, 96
+N = 1281                                    # n % 4 == 1 and not a multiple of 256
+
+
+def _renderer(n, deg, seed, W=W, H=H, **kw):
+    from gaussiansplat_amd import renderer as R, synthetic
+    scene = synthetic.make_scene(n, W, H, deg, seed=seed)
+    return R.getRenderer("GAUSSIAN_3D", (W, H, 3), (16, 16), None, scene, **kw)
+
+
+def _params(r):
+    sd = r.splatData
+    return [sd.means, sd.scales, sd.quaternions, sd.opacities, sd.shs]
+
+
+def _host(ts):
+    import torch
+    torch.cuda.synchronize()
+    return [t.detach().cpu().numpy().reshape(t.shape[0], -1).copy() for t in ts]
+
+
+def _bits_equal(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def _rand_grads(rng, n, widths):
+    out = []
+    for w in widths:
+        g = (rng.standard_normal((n, w)) * 10.0 ** rng.uniform(-3, 0)).astype(np.float32)
+        u = rng.random((n, w))
+        g[u < 0.1] = 0.0
+        g[(u >= 0.1) & (u < 0.2)] = -0.0
+        out.append(g)
+    return out
+
+
+class _Buffers:
+    """g, m, v: five device arrays each -- views into flat buffers of the initGrads layout (slices at 12n / 40n / 44n bytes, not
+    16-byte aligned when n % 4 != 0: the kernel's one-float-per-lane path), or five separate tensors (16-byte aligned: float4 + tail)."""
+
+    def __init__(self, n, widths, layout):
+        import torch
+
+        def alloc():
+            if layout == "flat":
+                flat = torch.zeros(sum(widths) * n, device="cuda")
+                parts, o = [], 0
+                for w in widths:
+                    parts.append(flat[o:o + w * n].view(n, w)); o += w * n
+                return parts
+            return [torch.zeros((n, w), device="cuda") for w in widths]
+        self.g, self.m, self.v = alloc(), alloc(), alloc()
+
+    @staticmethod
+    def struct(parts, null=()):
+        from gaussiansplat_amd import backend as B
+        return B.GsGrads(*[None if k in null else t.data_ptr() for k, t in enumerate(parts)])
+
+    @staticmethod
+    def fill(parts, arrays):
+        import torch
+        for t, a in zip(parts, arrays):
+            t.copy_(torch.from_numpy(np.ascontiguousarray(a, np.float32)))
+
+
+def _step(r, buf, t, lr=LR6, null=(), selective=False):
+    r._begin()
+    r.ctx.adam_step(buf.struct(buf.g, null), buf.struct(buf.m), buf.struct(buf.v), lr, B1, B2, EPS, t, selective=selective)
+
+
+@pytest.mark.parametrize("layout", ["flat", "separate"])
+@pytest.mark.parametrize("deg", [0, 1, 2, 3])
+def test_standalone_dense_bitwise_and_against_torch(deg, layout):
+    widths = [3, 3, 4, 1, 3 * (deg + 1) ** 2]
+    r = _renderer(N, deg, seed=40 + deg)
+    buf = _Buffers(N, widths, layout)
+    rng = np.random.default_rng(deg)
+    P, M, V = _host(_params(r)), [np.zeros((N, w), np.float32) for w in widths], [np.zeros((N, w), np.float32) for w in widths]
+    p0, seq = [a.copy() for a in P], []
+    for t in range(1, 6):
+        g = _rand_grads(rng, N, widths)
+        seq.append(g)
+        _Buffers.fill(buf.g, g)
+        _step(r, buf, t)
+        P, M, V = A.step(P, g, M, V, LR6, B1, B2, EPS, t)
+    got = _host(_params(r)) + _host(buf.m) + _host(buf.v)
+    for k, (a, b) in enumerate(zip(got, P + M + V)):
+        assert _bits_equal(a, b), (k, np.flatnonzero(a.view(np.uint32) != b.view(np.uint32))[:5])
+    for k in range(5):                                         # torch: one run per group, the SH columns as two
+        for j, cs in enumerate([slice(None)] if k < 4 else [slice(0, 3), slice(3, None)]):
+            if cs.start == 3 and widths[4] == 3:
+                continue
+            tp, tm, tv = A.torch_adam(p0[k][:, cs], [g[k][:, cs] for g in seq], LR6[k if k < 4 else 4 + j], (B1, B2), EPS)
+            for a, b in ((got[k][:, cs], tp), (got[5 + k][:, cs], tm), (got[10 + k][:, cs], tv)):
+                assert rel_l2(a, b) <= 1e-6, (k, j, rel_l2(a, b))
+
+
+@pytest.mark.parametrize("layout", ["flat", "separate"])
+@pytest.mark.parametrize("deg", [0, 3])
+def test_standalone_selective_leaves_dead_rows_alone(deg, layout):
+    widths = [3, 3, 4, 1, 3 * (deg + 1) ** 2]
+    r = _renderer(N, deg, seed=50 + deg)
+    buf = _Buffers(N, widths, layout)
+    rng = np.random.default_rng(10 + deg)
+    for t in (1, 2):                                           # dense steps first: non-zero moments
+        _Buffers.fill(buf.g, _rand_grads(rng, N, widths))
+        _step(r, buf, t)
+    g = _rand_grads(rng, N, widths)
+    dead = rng.random(N) < 0.5
+    for a in g:
+        a[dead] = 0.0
+        a[dead & (rng.random(N) < 0.5)] = -0.0                 # some dead rows are all -0
+    g[4][np.flatnonzero(dead)[::3], 0] = -0.0                 # and some mix +0 and -0
+    _Buffers.fill(buf.g, g)
+    before = _host(_params(r)) + _host(buf.m) + _host(buf.v)
+    _step(r, buf, 3, selective=True)
+    after = _host(_params(r)) + _host(buf.m) + _host(buf.v)
+    P, M, V = A.step(before[0:5], g, before[5:10], before[10:15], LR6, B1, B2, EPS, 3)   # the dense step
+    for a, b, d in zip(after, before, P + M + V):
+        assert _bits_equal(a[dead], b[dead])
+        assert _bits_equal(a[~dead], d[~dead])
+    assert 0.3 < dead.mean() < 0.7
+
+
+def test_null_gradient_freezes_group_and_zero_rate_still_moves_moments():
+    deg, widths = 1, [3, 3, 4, 1, 12]
+    r = _renderer(N, deg, seed=60)
+    buf = _Buffers(N, widths, "flat")
+    rng = np.random.default_rng(60)
+    _Buffers.fill(buf.m, [rng.standard_normal((N, w)).astype(np.float32) * 0.01 for w in widths])
+    _Buffers.fill(buf.v, [rng.random((N, w)).astype(np.float32) * 0.01 for w in widths])
+    g = _rand_grads(rng, N, widths)
+    _Buffers.fill(buf.g, g)
+    lr = list(LR6); lr[3] = 0.0                                # opacities: lr 0
+    before = _host(_params(r)) + _host(buf.m) + _host(buf.v)
+    r._begin()
+    r.ctx.adam_step(buf.struct(buf.g, null=(1,)), buf.struct(buf.m), buf.struct(buf.v), lr, B1, B2, EPS, 4)
+    after = _host(_params(r)) + _host(buf.m) + _host(buf.v)
+    g2 = list(g); g2[1] = None
+    P, M, V = A.step(before[0:5], g2, before[5:10], before[10:15], lr, B1, B2, EPS, 4)
+    for a, b in zip(after, P + M + V):
+        assert _bits_equal(a, b)
+    for k in (1, 6, 11):                                       # scales frozen: p, m, v untouched
+        assert _bits_equal(after[k], before[k])
+    assert _bits_equal(after[3], before[3])                    # lr 0: p unchanged ...
+    assert not _bits_equal(after[8], before[8]) and not _bits_equal(after[13], before[13])   # ... m and v moved
+    # a frozen group may come without moments at all
+    r.ctx.adam_step(buf.struct(buf.g, null=(1,)), buf.struct(buf.m, null=(1,)), buf.struct(buf.v, null=(1,)), lr, B1, B2, EPS, 5)
+
+
+def test_2d_renderer_step_and_no_fused_form():
+    import torch
+    from gaussiansplat_amd import backend as B, renderer as R
+    from gaussiansplat_amd.optim import Adam
+    r = R.getRenderer("GAUSSIAN_2D", (W, H, 3), (16, 16), None, N)
+    widths = [2, 2, 1, 1, 3]
+    opt = Adam(r, lr=dict(means=1e-3, scales=2e-3, rotations=3e-3, opacities=4e-3, colors=5e-3))
+    assert opt.lr_vector() == [1e-3, 2e-3, 3e-3, 4e-3, 5e-3, 0.0]
+    sd = r.splatData
+    params = [sd.means, sd.scales, sd.rotations, sd.opacities, sd.colors]
+    P = _host(params)
+    M, V = [np.zeros((N, w), np.float32) for w in widths], [np.zeros((N, w), np.float32) for w in widths]
+    rng = np.random.default_rng(70)
+    for t in (1, 2):
+        g = _rand_grads(rng, N, widths)
+        r.splatGrads.flat.copy_(torch.from_numpy(np.concatenate([a.reshape(-1) for a in g])))
+        opt.step()
+        P, M, V = A.step(P, g, M, V, opt.lr_vector(), B1, B2, EPS, t)
+    got = _host(params) + A.split_flat(opt.exp_avg.cpu().numpy(), N, widths) + A.split_flat(opt.exp_avg_sq.cpu().numpy(), N, widths)
+    for a, b in zip(got, P + M + V):
+        assert _bits_equal(a, b)
+    dC = torch.zeros((3, H, W), device="cuda")
+    with pytest.raises(B.GsError) as e:
+        r.ctx.backward_adam(dC.data_ptr(), opt._struct(opt.exp_avg), opt._struct(opt.exp_avg_sq), opt.lr_vector(), B1, B2, EPS, 3)
+    assert e.value.code == B.GS_ERR_UNSUPPORTED
+    with pytest.raises(ValueError):
+        Adam(r, lr=1e-3, fused=True)
+
+
+def _fused_vs_unfused(n, Wi, Hi, deg, selective, steps=3):
+    """Three train steps each way from the same scene: gs_backward_adam, and gs_backward_ex(GS_BWD_OVERWRITE) + gs_adam_step."""
+    import torch
+    from gaussiansplat_amd import renderer as R, synthetic, train as TR
+    from gaussiansplat_amd.optim import Adam
+    scene = synthetic.make_scene(n, Wi, Hi, deg, seed=80 + deg)
+    cam = synthetic.scene_camera(Wi)
+    gt = torch.rand((3, Hi, Wi), device="cuda", generator=torch.Generator("cuda").manual_seed(deg))
+    out = []
+    for fused in (False, True):
+        r = R.getRenderer("GAUSSIAN_3D", (Wi, Hi, 3), (16, 16), None, scene, deterministic=True, tile_parts=1)
+        R.resetGrads(r)                                        # the unfused backward overwrites, as the contract states
+        lf = TR.getLossFunction((Wi, Hi, 3), 11, 3, renderer=r)
+        opt = Adam(r, lr=RATES, selective=selective, fused=fused)
+        for _ in range(steps):
+            TR.trainStep(r, gt, 0.0, lf, cam, want_loss=False, optimizer=opt)
+        torch.cuda.synchronize()
+        out.append([x.clone() for x in _params(r)] + [opt.exp_avg.clone(), opt.exp_avg_sq.clone()])
+        del r, lf, opt
+    for k, (a, b) in enumerate(zip(*out)):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), k
+    start = torch.as_tensor(scene["shs"]).reshape(out[0][4].shape).cuda()
+    assert not torch.equal(out[0][4], start)                   # the model moved
+
+
+@pytest.mark.parametrize("selective", [False, True])
+@pytest.mark.parametrize("deg", [0, 1, 2, 3])
+def test_fused_backward_adam_equals_backward_then_step(deg, selective):
+    _fused_vs_unfused(3001, 160, 112, deg, selective)
+
+
+@pytest.mark.parametrize("selective", [False, True])
+def test_fused_backward_adam_equals_backward_then_step_c3(selective):
+    _fused_vs_unfused(1_000_000, 1920, 1080, 3, selective)
+
+
+def _perturbed_start(n, Wi, Hi, deg):
+    """The scene and start of tests/test_gpu_loss.py::test_sgd_step_and_training_reduces_loss."""
+    from gaussiansplat_amd import renderer as R, synthetic
+    target = synthetic.make_scene(n, Wi, Hi, deg, seed=1)
+    cam = synthetic.scene_camera(Wi)
+    rt = R.getRenderer("GAUSSIAN_3D", (Wi, Hi, 3), (16, 16), None, target)
+    R.forward(rt, (R.preprocess(rt, cam), R.compactIdxs(rt))[0])
+    gt = rt.imageData.clone()
+    start = {k: v.copy() for k, v in target.items()}
+    start["shs"] = (start["shs"] + 0.2 * np.random.default_rng(2).standard_normal(start["shs"].shape)).astype(np.float32)
+    start["opacities"] = (start["opacities"] - 0.5).astype(np.float32)
+    return start, cam, gt
+
+
+def test_trajectory_against_torch_adam():
+    """Three trainStep(optimizer=Adam) iterations against a loop that takes gs_backward's gradients and steps torch.optim.Adam."""
+    import torch
+    from gaussiansplat_amd import renderer as R, train as TR
+    from gaussiansplat_amd.optim import Adam
+    n, Wi, Hi, deg = 3000, 128, 96, 1
+    start, cam, gt = _perturbed_start(n, Wi, Hi, deg)
+    r1 = R.getRenderer("GAUSSIAN_3D", (Wi, Hi, 3), (16, 16), None, start, deterministic=True, tile_parts=1)
+    lf1 = TR.getLossFunction((Wi, Hi, 3), 11, 3, renderer=r1)
+    opt = Adam(r1, lr=RATES)
+    for _ in range(3):
+        TR.trainStep(r1, gt, 0.0, lf1, cam, optimizer=opt)
+    r2 = R.getRenderer("GAUSSIAN_3D", (Wi, Hi, 3), (16, 16), None, start, deterministic=True, tile_parts=1)
+    lf2 = TR.getLossFunction((Wi, Hi, 3), 11, 3, renderer=r2)
+    sd = r2.splatData
+    dc, rest = sd.shs[:, :3].clone(), sd.shs[:, 3:].clone()
+    groups = [(sd.means, "means"), (sd.scales, "scales"), (sd.quaternions, "quaternions"), (sd.opacities, "opacities"), (dc, "sh_dc"),
+              (rest, "sh_rest")]
+    b = tuple(float(np.float32(x)) for x in (B1, B2))
+    topt = torch.optim.Adam([{"params": [p], "lr": float(np.float32(RATES[k]))} for p, k in groups], betas=b, eps=float(np.float32(EPS)),
+                            foreach=False)
+    for _ in range(3):
+        tps = R.preprocess(r2, cam); R.compactIdxs(r2); R.forward(r2, tps)
+        _, dC = lf2.value_and_grad(r2.imageData, gt)
+        R.resetGrads(r2)
+        R.backward(r2, dC)
+        g = r2.splatGrads
+        for (p, _), gr in zip(groups, (g.Δmeans, g.Δscales, g.Δquaternions, g.Δopacities, g.Δshs[:, :3], g.Δshs[:, 3:])):
+            p.grad = gr.clone()
+        topt.step()
+        sd.shs[:, :3] = dc; sd.shs[:, 3:] = rest
+    torch.cuda.synchronize()
+    for a, b2 in zip(_params(r1), _params(r2)):
+        assert rel_l2(a.cpu().numpy(), b2.cpu().numpy()) <= 1e-5, rel_l2(a.cpu().numpy(), b2.cpu().numpy())
+
+
+def test_adam_for_3dgs_beats_the_sgd_run():
+    """The scene and iteration count of the SGD training test: Adam with the 3DGS rates ends at a lower loss than SGD at lr 2."""
+    from gaussiansplat_amd import renderer as R, train as TR
+    from gaussiansplat_amd.optim import Adam
+    n, Wi, Hi, deg = 3000, 128, 96, 1
+    start, cam, gt = _perturbed_start(n, Wi, Hi, deg)
+    extent = float(np.linalg.norm(start["means"].max(0) - start["means"].min(0)) / 2)
+    finals = {}
+    for name in ("sgd", "adam"):
+        r = R.getRenderer("GAUSSIAN_3D", (Wi, Hi, 3), (16, 16), None, start)
+        lf = TR.getLossFunction((Wi, Hi, 3), 11, 3, renderer=r)
+        opt = Adam.for_3dgs(r, extent) if name == "adam" else None
+        losses = TR.train(r, gt, 2.0, lf, iterations=26, camera=cam, optimizer=opt)
+        assert all(np.isfinite(losses))
+        finals[name] = (losses[0], losses[-1])
+    print("first / final loss after 26 iterations: sgd lr 2.0 %.6f / %.6f, Adam.for_3dgs %.6f / %.6f"
+          % (*finals["sgd"], *finals["adam"]))
+    assert finals["adam"][1] < finals["sgd"][1], finals
+
+
+def test_multi_view_flat_buffer_step():
+    """distributed.multi_view_step on one GPU (two views, no exchange), then Adam.step on the flat buffer it returns."""
+    import torch
+    from gaussiansplat_amd import distributed as D, synthetic
+    from gaussiansplat_amd.optim import Adam
+    n, deg = 3000, 2
+    widths = [3, 3, 4, 1, 27]
+    r = _renderer(n, deg, seed=90, deterministic=True, tile_parts=1)
+    hv = D.HipViewRenderer(r)
+    cams = [synthetic.scene_camera(W, view=v) for v in (0, 1)]
+    dCs = [torch.as_tensor(synthetic.make_dC(W, H, 600 + v)).cuda() for v in (0, 1)]
+    flat = D.multi_view_step(hv, cams, dCs, exchange=False)
+    torch.cuda.synchronize()
+    g = A.split_flat(flat.cpu().numpy().copy(), n, widths)
+    assert any(np.any(a != 0) for a in g)
+    P = _host(_params(r))
+    opt = Adam(r, lr=RATES)
+    opt.step(flat)
+    zeros = [np.zeros((n, w), np.float32) for w in widths]
+    P, M, V = A.step(P, g, zeros, zeros, opt.lr_vector(), B1, B2, EPS, 1)
+    got = _host(_params(r)) + A.split_flat(opt.exp_avg.cpu().numpy(), n, widths) + A.split_flat(opt.exp_avg_sq.cpu().numpy(), n, widths)
+    for a, b in zip(got, P + M + V):
+        assert _bits_equal(a, b)
+
+
+def test_invalid_arguments_are_refused_and_write_nothing():
+    import torch
+    from gaussiansplat_amd import backend as B, renderer as R, synthetic
+    deg, widths = 1, [3, 3, 4, 1, 12]
+    r = _renderer(N, deg, seed=95)
+    cam = synthetic.scene_camera(W)
+    # gs_backward_adam before any gs_forward fails like gs_backward
+    buf = _Buffers(N, widths, "separate")
+    rng = np.random.default_rng(95)
+    for parts in (buf.g, buf.m, buf.v):
+        _Buffers.fill(parts, [rng.random((N, w)).astype(np.float32) for w in widths])
+    dC = torch.as_tensor(synthetic.make_dC(W, H, 95)).cuda()
+    r._begin()
+    codes = []
+    for call in (lambda: r.ctx.backward(dC.data_ptr(), buf.struct(buf.g), overwrite=True),
+                 lambda: r.ctx.backward_adam(dC.data_ptr(), buf.struct(buf.m), buf.struct(buf.v), LR6, B1, B2, EPS, 1)):
+        with pytest.raises(B.GsError) as e:
+            call()
+        codes.append((e.value.code, "gs_forward first" in str(e.value)))
+    assert codes == [(B.GS_ERR_INVALID, True)] * 2
+    R.forward(r, (R.preprocess(r, cam), R.compactIdxs(r))[0])  # from here on gs_backward_adam would run: only the arguments are wrong
+    model = _params(r)
+    snap = [t.clone() for t in model + buf.g + buf.m + buf.v]
+    nan, inf = float("nan"), float("inf")
+    good = dict(lr=LR6, beta1=B1, beta2=B2, eps=EPS, step=1, flags=0)
+    bad = [dict(step=0), dict(step=-3), dict(beta1=1.0), dict(beta1=-0.1), dict(beta1=nan), dict(beta2=1.0), dict(beta2=-1e-3),
+           dict(eps=0.0), dict(eps=-1e-8), dict(eps=nan), dict(eps=inf), dict(flags=2), dict(flags=1 | 8)]
+    for k in range(6):
+        for x in (-1e-3, nan, inf):
+            lr = list(LR6); lr[k] = x
+            bad.append(dict(lr=lr))
+    g, m, v = buf.struct(buf.g), buf.struct(buf.m), buf.struct(buf.v)
+
+    def swap(s, field, ptr):
+        t = B.GsGrads(s.d_means, s.d_scales, s.d_quats, s.d_opacities, s.d_shs)
+        setattr(t, field, ptr)
+        return t
+    aliased = [(g, m, g), (g, g, v), (swap(g, "d_means", model[0].data_ptr()), m, v), (g, swap(m, "d_shs", buf.v[4].data_ptr()), v),
+               (g, swap(m, "d_scales", buf.m[0].data_ptr() + 4), v), (g, m, swap(v, "d_quats", buf.g[2].data_ptr() + 8)),
+               (g, swap(m, "d_opacities", None), v)]
+    for case in bad:
+        a = dict(good, **case)
+        for call in (lambda: r.ctx.adam_step(g, m, v, a["lr"], a["beta1"], a["beta2"], a["eps"], a["step"], flags=a["flags"]),
+                     lambda: r.ctx.backward_adam(dC.data_ptr(), m, v, a["lr"], a["beta1"], a["beta2"], a["eps"], a["step"], flags=a["flags"])):
+            with pytest.raises(B.GsError) as e:
+                call()
+            assert e.value.code == B.GS_ERR_INVALID, case
+    for gg, mm, vv in aliased:
+        with pytest.raises(B.GsError) as e:
+            r.ctx.adam_step(gg, mm, vv, LR6, B1, B2, EPS, 1)
+        assert e.value.code == B.GS_ERR_INVALID
+    for mm, vv in ((swap(m, "d_means", model[0].data_ptr()), v), (m, swap(v, "d_shs", buf.m[4].data_ptr())), (swap(m, "d_quats", None), v)):
+        with pytest.raises(B.GsError) as e:
+            r.ctx.backward_adam(dC.data_ptr(), mm, vv, LR6, B1, B2, EPS, 1)
+        assert e.value.code == B.GS_ERR_INVALID
+    torch.cuda.synchronize()
+    for a, b in zip(snap, model + buf.g + buf.m + buf.v):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+    r.ctx.backward_adam(dC.data_ptr(), m, v, LR6, B1, B2, EPS, 1)   # the frame was left intact: a valid call runs
+    torch.cuda.synchronize()
+    assert not torch.equal(snap[0], model[0])

@@ -8,10 +8,14 @@ W=$(mktemp -d)
 git archive "$C" gaussiansplat_amd/csrc include | tar -x -C "$W"
 OUT=$PWD/gaussiansplat_amd/lib_$TAG; mkdir -p "$OUT"
 grep -q gs_get_bin_path "$W/include/gsplat.h" || echo 'extern "C" int gs_get_bin_path(gs_ctx *c) { return c ? 0 : -1; }' >> "$W/gaussiansplat_amd/csrc/gs_api_debug.hip"
+grep -q gs_adam_step "$W/include/gsplat.h" || cat >> "$W/gaussiansplat_amd/csrc/gs_api_debug.hip" <<'STUB'
+extern "C" int gs_adam_step(gs_ctx *, const gs_grads *, const gs_grads *, const gs_grads *, const float *, float, float, float, int64_t, int) { return GS_ERR_UNSUPPORTED; }
+extern "C" int gs_backward_adam(gs_ctx *, const float *, int, const gs_grads *, const gs_grads *, const float *, float, float, float, int64_t, int) { return GS_ERR_UNSUPPORTED; }
+STUB
 objs=()
 for s in "$W"/gaussiansplat_amd/csrc/*.hip; do
   b=$(basename "$s" .hip); extra=""
-  case $b in gs_preprocess|gs_preprocess2d) extra="-ffp-contract=off";; gs_composite|gs_loss) extra="-fno-slp-vectorize";; esac
+  case $b in gs_preprocess|gs_preprocess2d|gs_adam) extra="-ffp-contract=off";; gs_composite|gs_loss) extra="-fno-slp-vectorize";; esac
   /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wno-unused-function $extra -c "$s" -o "$OUT/$b.o" &
   objs+=("$OUT/$b.o")
 done
