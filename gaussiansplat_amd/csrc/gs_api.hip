@@ -73,7 +73,7 @@ int gs_create(gs_ctx **out, int device, const gs_config *cfg) {
     if ((e = hipSetDevice(device)) != hipSuccess) { delete c; return hipfail(nullptr, e, "hipSetDevice"); }
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) { delete c; return hipfail(nullptr, e, "hipStreamCreate"); }
     c->own_stream = true;
-    {   // wave slots of the composite kernels (their __launch_bounds__ ask for five waves per SIMD): what "the grid fills the chip" means
+    {   // wave slots: CUs x 4 SIMDs x 5 by definition -- what "the grid fills the chip" means (the composite backward holds six waves per SIMD by now)
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->wave_slots = prop.multiProcessorCount * 4 * 5;
         else (void)hipGetLastError();

@@ -75,8 +75,7 @@ static int two_level_count(gs_ctx *c, const uint32_t *perm_slab, int64_t n_all, 
     if (to_host) {                                                          // the layout settle_totals reads: counter block at pinned + 8
         b.host_totals = c->pinned + 8 + 32; b.host_walked = c->pinned + 8; b.walked_src = c->counters.as<uint32_t>();
         // the previous forward's walked entries, per tile (valid only if that forward ran on this grid: prev_counters_valid)
-        const bool same_grid = c->counters_grid == (((int64_t)c->gx << 32) | (int64_t)c->gy) && c->last_walked;
-        if (!same_grid) c->prev_counters_valid = false;
+        if (!c->counters_here()) c->prev_counters_valid = false;
         b.tile_walked = c->prev_counters_valid ? c->last_walked : nullptr; b.n_tile_walked = c->gx * c->gy;
     }
     HIPCHK(c, gs_bin3_l1_count(b, c->stream));
@@ -123,7 +122,7 @@ static int two_level_lists(gs_ctx *c, const uint32_t *perm_slab, int64_t n_all, 
 #define GS_LIST_CAP_MAX_RATIO 0.15
 static int list_cap_source(gs_ctx *c, int rounds, const uint32_t **out) {
     *out = nullptr;
-    const int64_t ntiles = (int64_t)c->gx * c->gy, grid = ((int64_t)c->gx << 32) | (int64_t)c->gy;
+    const int64_t ntiles = (int64_t)c->gx * c->gy, grid = c->grid_key();
     if (!c->two_level || rounds != 1 || c->cfg.list_cap == 1 || !(c->cfg.t_min > 0.0f) || ntiles <= 0) return GS_OK;
     if (c->cfg.debug_flags & GS_DEBUG_TINY_CAPS) {          // tests: every tile capped at the minimum, whatever it walked
         if (c->zero_tiles.cap < sizeof(uint32_t) * (size_t)ntiles) {
@@ -320,8 +319,7 @@ static int bin_small(gs_ctx *c) {
     a.n = (int)c->n; a.gx = c->gx; a.gy = c->gy; a.ntiles = (int)nt;
     a.ranges = c->ranges.as<uint32_t>(); a.ids = c->ids.as<uint32_t>(); a.totals = c->bin_totals();
     a.host_totals = c->pinned + 8 + 32; a.host_walked = c->pinned + 8; a.walked_src = c->counters.as<uint32_t>();
-    const bool same_grid = c->counters_grid == (((int64_t)c->gx << 32) | (int64_t)c->gy) && c->last_walked;
-    if (!same_grid) c->prev_counters_valid = false;
+    if (!c->counters_here()) c->prev_counters_valid = false;
     a.tile_walked = c->prev_counters_valid ? c->last_walked : nullptr; a.n_tile_walked = (int)nt;
     {   // the rows the composite backward accumulates into (64 B per gaussian; nothing touches them between here and that kernel)
         const size_t bytes = (c->cfg.deterministic ? sizeof(long long) : sizeof(float)) * GS_G2D_STRIDE * n;
@@ -377,7 +375,7 @@ static int bin_frame(gs_ctx *c, bool special_paths) {
     c->sgx = (c->gx + sb - 1) / sb; c->sgy = (c->gy + sb - 1) / sb;
     c->two_level = small || (fast && bin_path == 0 && gs_bin3_supported(c->sgx * c->sgy));
     c->tile_bits = tile_bits; c->gid_bits = gid_bits; c->lo_bits = lo_bits; c->hi_bits = hi_bits; c->fast_bin = fast;
-    HIPCHK(c, c->ranges.ensure(sizeof(uint32_t) * 2 * (size_t)(ntiles ? ntiles : 1)));
+    HIPCHK(c, c->ranges.ensure(sizeof(uint32_t) * 2 * c->ntiles1()));
     HIPCHK(c, c->counters.ensure(GS_COUNTER_BYTES));
     // the slab plan needs the previous frame's walked share, which the read-back below delivers: the plan of THIS frame uses
     // the share known so far (one frame of lag; only speed depends on it)
@@ -426,7 +424,7 @@ static int bin_frame(gs_ctx *c, bool special_paths) {
     // ranges) is enqueued BEFORE the host waits, so the GPU stays busy while the host wakes up and launches the instance passes.
     HIPCHK(c, hipMemcpyAsync(c->pinned, c->offsets.as<uint32_t>() + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->pinned + 1, c->offsets.as<uint32_t>() + n0, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (c->prev_counters_valid && (c->counters_grid != (((int64_t)c->gx << 32) | (int64_t)c->gy) || !c->last_walked)) c->prev_counters_valid = false;
+    if (!c->counters_here()) c->prev_counters_valid = false;
     if (c->prev_counters_valid) {
         HIPCHK(c, gs_launch_sum_tiles(c->last_walked, c->tile_work.as<uint32_t>(), c->gx * c->gy, c->counters.as<unsigned long long>(), c->stream));
         HIPCHK(c, hipMemcpyAsync(c->pinned + 2, c->counters.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));

@@ -1,62 +1,145 @@
-// gs_api_composite.hip -- gs_forward / gs_backward (reference src/forward.jl:163-198, src/backward.jl:3-38): the composite launches,
-// the per-gaussian chain behind the backward, and the longest-first launch orders kept per view slot.
+// gs_api_composite.hip -- gs_forward / gs_backward (reference src/forward.jl:163-198, src/backward.jl:3-38): the frame's plan, the
+// composite launches, the per-gaussian chain behind the backward, and the longest-first launch orders kept per view slot.
 #include "gs_ctx.h"
 
-// Launch order of the frame's composite kernels (gs_config.schedule 3 / 4): what the last forward under the same view slot
-// measured, else (schedule 4) what this ctx's previous slot-less forward measured; null = no history: tile order for the forward.
-const uint32_t *forward_order(gs_ctx *c) {
+using Snap = gs_ctx::FramePlan::Snap;
+
+// Launch order of the frame's forward (gs_config.schedule 3 / 4): what the last forward under the same view slot measured, else
+// (schedule 4) what this ctx's previous slot-less forward measured; null = no history: tile order.  *split: the order's split-count word.
+static const uint32_t *forward_order(gs_ctx *c, const uint32_t **split) {
     const int64_t ntiles = (int64_t)c->gx * c->gy;
     if (!lpt_schedule(c) || ntiles <= 0 || ntiles > GS_LPT_MAX_TILES) return nullptr;
     const int k = order_index(c);
     if (k == GS_MAX_VIEW_SLOTS && c->cfg.schedule != 4) return nullptr;
-    if (c->slots[k].tiles != (((int64_t)c->gx << 32) | (int64_t)c->gy)) return nullptr;         // (the order's length and groups belong to one grid)
+    gs_ctx::ViewSlot &vs = c->slots[k];
+    if (vs.tiles != c->grid_key()) return nullptr;                        // (the order's length and groups belong to one grid)
     if (c->order_pending) {                                              // (long complete by now; an event wait on the stream costs nothing)
         if (hipStreamWaitEvent(c->stream, c->ev_order, 0) != hipSuccess) return nullptr;
         c->order_pending = false;
     }
-    c->frame_order_split = c->pinned_split ? c->pinned_split + 2 * k + c->slots[k].sel : nullptr;
-    return c->slots[k].order[c->slots[k].sel].as<uint32_t>();
+    *split = c->split_word(k, vs.sel);
+    return vs.order[vs.sel].as<uint32_t>();
+}
+
+// pixel parts (waves per tile, each owning 4 / parts of its pixel strips) that fit the wave slots when a tile runs as `units` waves already
+static int parts_that_fit(const gs_ctx *c, int units) {
+    const long long w = (long long)units * c->gx * c->gy;
+    return 4 * w <= c->wave_slots ? 4 : 2 * w <= c->wave_slots ? 2 : 1;
+}
+
+// In which mode do this frame's composite launches run, and why: decided HERE, once per frame, from the config, the grid, the lists as
+// gs_bin left them, the forward's launch order and the walk history of the view slot (null: none on this grid).  Beside it: lpt_schedule
+// and lpt_front (gs_ctx.h), which are properties of ctx and grid -- they fix the layout of every order of a slot.
+static void plan_frame(gs_ctx *c, const uint32_t *order, const uint32_t *order_split, const uint32_t *hist) {   // order_split: the order's word of pinned_split
+    gs_ctx::FramePlan p;
+    const int want = c->cfg.tile_parts;
+    // launches that composite whole tiles, one wave each: no early-out, slab rounds, capped lists
+    const bool whole = !(c->cfg.t_min > 0.0f) || c->n_rounds > 1 || c->frame_capped;
+    p.parts = p.bwd_parts = want == 1 || whole ? 1 : (want == 2 || want == 4) ? want : parts_that_fit(c, 1);
+    p.order = p.bwd_order = order;
+    // The backward runs in the forward's order while the order kernel works beside it, on the side stream, for the slot's next frame; else
+    // (a slot's first frame; no side stream) it waits for that kernel and takes the fresh order: build_frame_order then sets bwd_order
+    p.side = order && use_side_stream(c);
+    p.front = lpt_front(c);
+    p.split = p.front > 0 && p.parts == 1 && c->n_rounds == 1;            // heavy tiles run as the orders' split entries say (full lists: asked at every launch, frame_capped is live)
+    // neither snapshot mode looks at cfg.deterministic, so deterministic gradients depend on the slot's history
+    const bool may_split = !order_split || *order_split != 0u;            // (the order kernel's count; 0xFFFFFFFF: not reported yet)
+    if (order && p.split && c->snap_walked.p && may_split) {
+        p.snap = Snap::HEAVY;                                              // ... and leave snapshots for the list segments of their backward
+        p.snap_walked = c->snap_walked.as<uint32_t>() + (size_t)c->snap_parity * GS_SEG_SLOTS;
+    } else if (hist && want == 0 && p.parts > 1 && !lpt_schedule(c) && c->kind == 0 && (int64_t)c->gx * c->gy > 0) {
+        // small grids (the automatic choice gave pixel parts: full lists, one round, at most half as many tiles as wave slots; no launch order):
+        // with the slot's previous walk at hand EVERY tile's backward runs as list segments instead, the forward's waves leave the
+        // snapshots.  Two segments, and as many pixel parts on top as still fit the wave slots (C1: 4 x 2 waves per tile; C2: 1 x 2)
+        // (C1, lists of two or three batches: four segments instead of four pixel parts lost, 0.049 against 0.034 ms; three segments x four
+        // parts ran like two, 0.0239 against 0.0243 -- a lone wave needs 0.33 us per evaluated entry and the launch lasts as long as the
+        // batch with the most of them, which no cut at a batch boundary shortens)
+        p.snap = Snap::ALL;
+        p.seg_n = 2; p.seg_hist = hist;
+        p.bwd_parts = parts_that_fit(c, p.seg_n);
+    }
+    c->plan = p;
+}
+
+// The arguments of a composite launch of the frame, as its plan says: round r of the forward, or the backward (every round's lists).
+// The callers add what is theirs alone -- forward: per-tile counters, slab state, bw_*; backward: dC, its counters; debug: variant, clocks,
+// window.  debug = an isolated launch over the finished frame: the forward then runs in the BACKWARD's order (what the slot's next forward
+// will use), leaves no snapshots, and keeps its hands off the per-tile counters.
+GsCompositeArgs composite_args(gs_ctx *c, bool bwd, int r, bool debug) {
+    const gs_ctx::FramePlan &p = c->plan;
+    GsCompositeArgs a{};
+    a.W = c->cam.W; a.H = c->cam.H; a.gx = c->gx; a.gy = c->gy; a.t_min = c->cfg.t_min;
+    a.payload = c->payload.as<GsPayload>(); a.image = c->img(); a.trans = c->tr();
+    a.cull = c->cfg.alpha_cull != 0;
+    for (int q = 0; q < c->n_rounds; ++q) {                                // the lists, round by round (a round that listed nothing: skipped)
+        if (q > 0 && c->round_gen[q] == 0) continue;
+        a.seg_ranges[a.nseg] = q == 0 ? c->ranges.as<uint32_t>() : c->ranges_r[q].as<uint32_t>();
+        a.seg_ids[a.nseg] = c->ids.as<uint32_t>() + c->round_ids_off[q];
+        ++a.nseg;
+    }
+    a.ranges = r == 0 ? c->ranges.as<uint32_t>() : c->ranges_r[r].as<uint32_t>(); a.ids = c->ids.as<uint32_t>() + c->round_ids_off[r];
+    if (bwd) { a.g2d = c->cfg.deterministic ? nullptr : c->g2d.as<float>(); a.g2d_fixed = c->cfg.deterministic ? c->g2d.as<long long>() : nullptr; }
+    a.tile_order = bwd || debug ? p.bwd_order : p.order; a.order_len = a.tile_order ? lpt_order_entries(c) : 0;
+    a.parts = bwd ? p.bwd_parts : p.parts;
+    a.split_ok = a.tile_order && p.split && !c->frame_capped;
+    if (c->frame_capped && c->n_rounds == 1) {
+        a.tile_ext = c->tile_ext.as<uint2>();                              // the lists end where gs_bin / the forward stopped writing them
+        if (!bwd) {                                                        // the forward's wave extends its tile's list when it must
+            a.cranges = c->cranges.as<uint32_t>(); a.cids = c->cids.as<uint32_t>(); a.clr = c->clr.as<uint16_t>();
+            a.ids_w = c->ids.as<uint32_t>(); a.sgx = c->sgx; a.sbs = c->sbs; a.ext_count = c->ext_count();
+        }
+    }
+    if (bwd ? p.bwd_segments : !debug) {                                   // snapshots: the forward leaves them, the backward starts its list segments from them
+        if (p.snap == Snap::ALL) { a.snap = c->snap.as<float>(); a.seg_hist = p.seg_hist; a.seg_n = p.seg_n; }
+        if (p.snap == Snap::HEAVY && a.split_ok) {
+            a.snap = c->snap.as<float>(); a.seg_len = order_seg_len(c, a.tile_order); a.front = p.front; a.snap_walked = p.snap_walked;
+        }
+    }
+    return a;
 }
 
 // After the frame's (last) forward: ONE order kernel turns its per-tile work into a launch order.  When the forward already ran
 // on the slot's history, the backward uses the same order and the kernel runs on the SIDE stream, beside the backward, into the
 // slot's other buffer -- for the slot's next frame; nothing of this frame waits for it.  Without history (a slot's first frame)
 // the backward waits for it: it is its only source of a longest-first order.
-int build_frame_order(gs_ctx *c, const uint32_t *used) {
+static int build_frame_order(gs_ctx *c) {
+    gs_ctx::FramePlan &p = c->plan;
     const int64_t ntiles = (int64_t)c->gx * c->gy;
-    c->frame_order = used;
     if (!lpt_schedule(c) || ntiles <= 0 || ntiles > GS_LPT_MAX_TILES) return GS_OK;
     const int k = order_index(c);
-    const int dst = used ? 1 - c->slots[k].sel : c->slots[k].sel;
-    DevBuf &ob = c->slots[k].order[dst];
+    gs_ctx::ViewSlot &vs = c->slots[k];
+    const int dst = vs.order_dst(p.order != nullptr);
+    DevBuf &ob = vs.order[dst];
     HIPCHK(c, ob.ensure(sizeof(uint32_t) * ((size_t)lpt_order_entries(c) + GS_SEG_SLOTS + 16)));
     // heavy tiles: the order kernel also sizes the backward's list segments (from what this forward walked) and re-arms the walked
     // lengths of the NEXT frame's snapshots (this frame's are being read by its backward)
-    const uint32_t *walked = lpt_front(c) > 0 ? c->last_walked : nullptr;
-    uint32_t *rearm = nullptr, *nsplit = c->pinned_split ? c->pinned_split + 2 * k + dst : nullptr;
+    const uint32_t *walked = p.front > 0 ? c->last_walked : nullptr;
+    uint32_t *rearm = nullptr, *nsplit = c->split_word(k, dst);
     if (nsplit) *nsplit = 0xFFFFFFFFu;                                     // unknown until the order kernel has stored its count
-    if (lpt_front(c) > 0) {
+    if (p.front > 0) {
         if (!c->snap_walked.p) {
             HIPCHK(c, c->snap_walked.ensure(sizeof(uint32_t) * 2 * GS_SEG_SLOTS));
             HIPCHK(c, hipMemsetAsync(c->snap_walked.p, 0, sizeof(uint32_t) * 2 * GS_SEG_SLOTS, c->stream));
         }
         rearm = c->snap_walked.as<uint32_t>() + (size_t)(c->snap_parity ^ 1) * GS_SEG_SLOTS;
     }
-    if (used && use_side_stream(c)) {
+    if (p.side) {
         if (c->order_pending) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_order, 0));      // (never two in flight)
         HIPCHK(c, hipEventRecord(c->ev_main, c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0));
-        HIPCHK(c, gs_launch_tile_lpt_order(c->tile_work.as<uint32_t>(), 0, c->gx, c->gy, ob.as<uint32_t>(), c->side, nullptr, 0, lpt_front(c), lpt_split_div(c), walked, rearm, nsplit));
+    }
+    HIPCHK(c, gs_launch_tile_lpt_order(c->tile_work.as<uint32_t>(), 0, c->gx, c->gy, ob.as<uint32_t>(), p.side ? c->side : c->stream, nullptr, 0, p.front,
+                                       lpt_split_div(c), walked, rearm, nsplit));
+    if (p.side) {
         HIPCHK(c, hipEventRecord(c->ev_order, c->side));
         c->order_pending = true;
-        c->slots[k].sel = dst;
+        vs.order_written(dst, c->grid_key());
         // (tile_work is rewritten by the next forward of this ctx: it waits for ev_order first, see forward_order / gs_forward)
     } else {
-        HIPCHK(c, gs_launch_tile_lpt_order(c->tile_work.as<uint32_t>(), 0, c->gx, c->gy, ob.as<uint32_t>(), c->stream, nullptr, 0, lpt_front(c), lpt_split_div(c), walked, rearm, nsplit));
-        c->frame_order = ob.as<uint32_t>();
-        c->frame_order_split = nsplit;
+        p.bwd_order = ob.as<uint32_t>();
+        // with p.order (no side stream) the fresh order sits in order[dst] but sel is not flipped: the slot's forwards keep the old one
+        vs.order_written(vs.sel, c->grid_key());
     }
-    c->slots[k].tiles = ((int64_t)c->gx << 32) | (int64_t)c->gy;
     return GS_OK;
 }
 
@@ -77,55 +160,19 @@ int gs_set_view_slot(gs_ctx *c, int32_t slot) {
     return GS_OK;
 }
 
-// waves per tile of this frame's composite launches (gs_config.tile_parts)
-static int composite_parts(const gs_ctx *c) {
-    const int want = c->cfg.tile_parts;
-    if (want == 1 || !(c->cfg.t_min > 0.0f) || c->n_rounds > 1 || c->frame_capped) return 1;
-    if (want == 2 || want == 4) return want;
-    const long long ntiles = (long long)c->gx * c->gy, slots = c->wave_slots;   // 256 CUs x 4 SIMDs x five waves (GS_FWD_MINW, GS_BWD_MINW)
-    return 4 * ntiles <= slots ? 4 : 2 * ntiles <= slots ? 2 : 1;
-}
-
 // the composite launch of round r of the frame (r = 0 unless the frame is binned in depth slabs)
-static int enqueue_forward_round(gs_ctx *c, int r, const uint32_t *order) {
-    const int R = c->n_rounds;
-    GsCompositeArgs a{};
-    a.W = c->cam.W; a.H = c->cam.H; a.gx = c->gx; a.gy = c->gy; a.t_min = c->cfg.t_min;
-    a.ranges = r == 0 ? c->ranges.as<uint32_t>() : c->ranges_r[r].as<uint32_t>();
-    a.ids = c->ids.as<uint32_t>() + c->round_ids_off[r]; a.payload = c->payload.as<GsPayload>();
-    a.image = c->img(); a.trans = c->tr();
-    a.walked = nullptr;                                                     // per tile: tile_walked / tile_work (GsCompositeArgs.walked)
-    a.cull = c->cfg.alpha_cull != 0;
-    a.resume = r > 0; a.final_round = r == R - 1;
+static int enqueue_forward_round(gs_ctx *c, int r) {
+    gs_ctx::FramePlan &p = c->plan;
+    if (p.snap != Snap::NONE && !c->frame_capped) {                         // this launch leaves snapshots (composite_args)
+        HIPCHK(c, c->snap.ensure(sizeof(float) * (p.snap == Snap::ALL ? (size_t)c->gx * c->gy * (size_t)(p.seg_n - 1) * 4 * 256 : (size_t)GS_SEG_SLOTS * GS_SEG_SNAP_FLOATS)));
+        HIPCHK(c, c->ensure_bwd_counters());
+    }
+    GsCompositeArgs a = composite_args(c, false, r);
+    a.resume = r > 0; a.final_round = r == c->n_rounds - 1;
     a.tile_work = c->tile_work.as<uint32_t>(); a.tile_walked = const_cast<uint32_t *>(c->last_walked);
-    a.tile_order = order; a.order_len = order ? lpt_order_entries(c) : 0;
-    a.parts = c->frame_parts;
-    a.split_ok = order && lpt_front(c) > 0 && c->frame_parts == 1 && !c->frame_capped && R == 1;   // heavy tiles run as the order's entries say
-    c->snap_order = nullptr;
-    if (c->frame_seg_n && R == 1) {                                         // small grid: every tile leaves snapshots for its backward's list segments
-        const size_t nt = (size_t)c->gx * c->gy;
-        HIPCHK(c, c->snap.ensure(sizeof(float) * nt * (size_t)(c->frame_seg_n - 1) * 4 * 256));
-        HIPCHK(c, c->tile_walked_b.ensure(sizeof(uint32_t) * (nt ? nt : 1)));
-        HIPCHK(c, c->tile_work_b.ensure(sizeof(uint32_t) * (nt ? nt : 1)));
-        a.snap = c->snap.as<float>(); a.seg_hist = c->seg_hist; a.seg_n = c->frame_seg_n;
-        a.bw_walked = c->tile_walked_b.as<uint32_t>(); a.bw_work = c->tile_work_b.as<uint32_t>();
-    }
-    const bool may_split = !c->frame_order_split || *c->frame_order_split != 0u;   // (the order kernel's count; 0xFFFFFFFF: not reported yet)
-    if (a.split_ok && c->snap_walked.p && may_split) {                      // ... and leave snapshots for the list segments of their backward
-        HIPCHK(c, c->snap.ensure(sizeof(float) * (size_t)GS_SEG_SLOTS * GS_SEG_SNAP_FLOATS));
-        const size_t nt = (size_t)c->gx * c->gy;
-        HIPCHK(c, c->tile_walked_b.ensure(sizeof(uint32_t) * (nt ? nt : 1)));
-        HIPCHK(c, c->tile_work_b.ensure(sizeof(uint32_t) * (nt ? nt : 1)));
-        a.snap = c->snap.as<float>(); a.seg_len = order_seg_len(c, order); a.front = lpt_front(c);
-        a.snap_walked = c->snap_walked.as<uint32_t>() + (size_t)c->snap_parity * GS_SEG_SLOTS;
-        a.bw_walked = c->tile_walked_b.as<uint32_t>(); a.bw_work = c->tile_work_b.as<uint32_t>();
-        c->snap_order = order;
-    }
-    if (c->frame_capped && R == 1) {                                        // capped lists: the wave extends its tile's list when it must
-        a.tile_ext = c->tile_ext.as<uint2>(); a.cranges = c->cranges.as<uint32_t>(); a.cids = c->cids.as<uint32_t>(); a.clr = c->clr.as<uint16_t>();
-        a.ids_w = c->ids.as<uint32_t>(); a.sgx = c->sgx; a.sbs = c->sbs; a.ext_count = c->ext_count();
-    }
-    if (R > 1) { a.tile_pos = c->tile_pos.as<uint32_t>(); a.tile_done = c->tile_done.as<uint8_t>(); a.tile_dead = c->tile_dead.as<unsigned long long>(); }
+    p.bwd_segments = a.snap && (p.side || !p.order);                       // snapshots left, and (HEAVY) the backward takes the order they belong to
+    if (a.snap) { a.bw_walked = c->tile_walked_b.as<uint32_t>(); a.bw_work = c->tile_work_b.as<uint32_t>(); }   // (its waves zero the segmented tiles' words)
+    if (c->n_rounds > 1) { a.tile_pos = c->tile_pos.as<uint32_t>(); a.tile_done = c->tile_done.as<uint8_t>(); a.tile_dead = c->tile_dead.as<unsigned long long>(); }
     StageTimer t(c, GS_STAGE_COMPOSITE_FWD);                               // the kernel alone
     HIPCHK(c, gs_launch_composite_fwd(a, c->stream));
     return GS_OK;
@@ -137,66 +184,48 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
     if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(c, GS_ERR_INVALID, "gs_forward: bad mem");
     if (bind_device(c)) return GS_ERR_HIP;
     const size_t px = (size_t)c->cam.W * c->cam.H;
-    const size_t ntiles = (size_t)c->gx * c->gy;
+    const size_t ntiles = (size_t)c->gx * c->gy, nt1 = c->ntiles1();
     if (!c->bound_image) {
         HIPCHK(c, c->image.ensure(sizeof(float) * 3 * px));
         HIPCHK(c, c->trans.ensure(sizeof(float) * px));
     }
     HIPCHK(c, c->counters.ensure(GS_COUNTER_BYTES));
-    HIPCHK(c, c->tile_work.ensure(sizeof(uint32_t) * (ntiles ? ntiles : 1)));
-    c->counters_grid = ((int64_t)c->gx << 32) | (int64_t)c->gy;
-    c->frame_seg_n = 0; c->seg_hist = nullptr;
-    int flip_slot = -1;
-    {   // the per-tile walked counts go to the frame's view slot (the caps of the slot's next lists; double buffered: this frame may read the
-        // previous walk while it writes its own), else to the ctx's own array
-        const int k = order_index(c);
-        if (k < GS_MAX_VIEW_SLOTS || c->cfg.schedule == 4) {
-            gs_ctx::ViewSlot &vs = c->slots[k];
-            DevBuf &wb = vs.walkbuf[vs.wsel ^ 1];
-            HIPCHK(c, wb.ensure(sizeof(uint32_t) * (ntiles ? ntiles : 1)));
-            const bool hist = vs.walked_grid == c->counters_grid && vs.walked().p;
-            // small grids (no launch order, fewer tiles than half the wave slots): with the slot's previous walk at hand EVERY tile's backward
-            // runs as 2 / 4 list segments; the forward's waves leave the snapshots
-            if (hist && c->cfg.tile_parts == 0 && c->cfg.t_min > 0.0f && c->n_rounds == 1 && !c->frame_capped && !lpt_schedule(c) && c->kind == 0 &&
-                2 * (int64_t)ntiles <= c->wave_slots && ntiles > 0) {
-                // (C1, lists of two or three batches: four segments instead of four pixel parts lost, 0.049 against 0.034 ms; three segments x four
-                // parts ran like two, 0.0239 against 0.0243 -- a lone wave needs 0.33 us per evaluated entry and the launch lasts as long as the
-                // batch with the most of them, which no cut at a batch boundary shortens)
-                c->frame_seg_n = 2;
-                c->seg_hist = vs.walked().as<uint32_t>();
-            }
-            c->last_walked = wb.as<uint32_t>();
-            flip_slot = k;
-        } else {
-            HIPCHK(c, c->tile_walked.ensure(sizeof(uint32_t) * (ntiles ? ntiles : 1)));
-            c->last_walked = c->tile_walked.as<uint32_t>();
-        }
+    HIPCHK(c, c->tile_work.ensure(sizeof(uint32_t) * nt1));
+    c->counters_grid = c->grid_key();
+    // the per-tile walked counts go to the frame's view slot (its next frame's list caps and segment lengths), else to the ctx's own array
+    gs_ctx::ViewSlot *vs = order_index(c) < GS_MAX_VIEW_SLOTS || c->cfg.schedule == 4 ? &c->slots[order_index(c)] : nullptr;
+    const uint32_t *hist = nullptr;                                        // the slot's previous walk of this grid
+    if (vs) {
+        HIPCHK(c, vs->walk_dst().ensure(sizeof(uint32_t) * nt1));
+        if (vs->walked_grid == c->counters_grid) hist = vs->walked().as<uint32_t>();
+        c->last_walked = vs->walk_dst().as<uint32_t>();
+    } else {
+        HIPCHK(c, c->tile_walked.ensure(sizeof(uint32_t) * nt1));
+        c->last_walked = c->tile_walked.as<uint32_t>();
     }
     const int R = c->n_rounds;
     if (R > 1) {
-        HIPCHK(c, c->tile_pos.ensure(sizeof(uint32_t) * (ntiles ? ntiles : 1)));
-        HIPCHK(c, c->tile_done.ensure(ntiles ? ntiles : 1));
-        HIPCHK(c, c->tile_dead.ensure(sizeof(unsigned long long) * 4 * (ntiles ? ntiles : 1)));
+        HIPCHK(c, c->tile_pos.ensure(sizeof(uint32_t) * nt1));
+        HIPCHK(c, c->tile_done.ensure(nt1));
+        HIPCHK(c, c->tile_dead.ensure(sizeof(unsigned long long) * 4 * nt1));
         HIPCHK(c, hipMemsetAsync(c->tile_pos.p, 0, sizeof(uint32_t) * ntiles, c->stream));
     }
-    c->frame_parts = composite_parts(c);
     c->snap_parity ^= 1;                                                   // (the order kernel behind the previous forward re-armed this parity)
-    const uint32_t *order = forward_order(c);
+    const uint32_t *order_split = nullptr, *const order = forward_order(c, &order_split);
     if (c->order_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_order, 0)); c->order_pending = false; }     // the order kernel in flight reads tile_work
+    plan_frame(c, order, order_split, hist);
     for (int r = 0; r < R; ++r) {
         if (r > 0) { if (int rc = bin_round(c, r)) return rc; }
-        if (int rc = enqueue_forward_round(c, r, order)) return rc;
+        if (int rc = enqueue_forward_round(c, r)) return rc;
         if (r == 0) {
             // the frame's totals: by now the composite is enqueued behind the lists, so the GPU has work while the host looks
             bool redo = false;
             if (int rc = settle_totals(c, &redo, true)) return rc;
-            if (redo) {                                                    // the lists outgrew a buffer and were rebuilt: composite again
-                if (int rc = enqueue_forward_round(c, 0, order)) return rc;
-            }
+            if (redo) { if (int rc = enqueue_forward_round(c, 0)) return rc; }     // the lists outgrew a buffer and were rebuilt: composite again, same plan
         }
     }
-    if (flip_slot >= 0) { c->slots[flip_slot].wsel ^= 1; c->slots[flip_slot].walked_grid = c->counters_grid; }   // this frame's walk is the slot's history now
-    if (int rc = build_frame_order(c, order)) return rc;
+    if (vs) vs->walk_written(c->counters_grid);
+    if (int rc = build_frame_order(c)) return rc;
     const hipMemcpyKind kind = mem == GS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (image && image != c->img()) HIPCHK(c, hipMemcpyAsync(image, c->img(), sizeof(float) * 3 * px, kind, c->stream));
     if (transmittance && transmittance != c->tr()) HIPCHK(c, hipMemcpyAsync(transmittance, c->tr(), sizeof(float) * px, kind, c->stream));
@@ -274,33 +303,11 @@ static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *gr
     }
     const bool det = c->cfg.deterministic != 0;
     HIPCHK(c, c->g2d.ensure((det ? sizeof(long long) : sizeof(float)) * GS_G2D_STRIDE * n1));
-    GsCompositeArgs a{};
-    a.W = c->cam.W; a.H = c->cam.H; a.gx = c->gx; a.gy = c->gy; a.t_min = c->cfg.t_min;
-    a.ranges = c->ranges.as<uint32_t>(); a.ids = c->ids.as<uint32_t>(); a.payload = c->payload.as<GsPayload>();
-    a.image = c->img(); a.trans = c->tr();
-    a.nseg = 0;
-    for (int r = 0; r < c->n_rounds; ++r) {
-        if (r > 0 && c->round_gen[r] == 0) continue;                       // a round that listed nothing
-        a.seg_ranges[a.nseg] = r == 0 ? c->ranges.as<uint32_t>() : c->ranges_r[r].as<uint32_t>();
-        a.seg_ids[a.nseg] = c->ids.as<uint32_t>() + c->round_ids_off[r];
-        ++a.nseg;
-    }
-    a.dC = dC_dev; a.g2d = det ? nullptr : c->g2d.as<float>(); a.g2d_fixed = det ? c->g2d.as<long long>() : nullptr;
-    {
-        const size_t nt = (size_t)c->gx * c->gy;
-        HIPCHK(c, c->tile_walked_b.ensure(sizeof(uint32_t) * (nt ? nt : 1)));
-        HIPCHK(c, c->tile_work_b.ensure(sizeof(uint32_t) * (nt ? nt : 1)));
-    }
-    a.walked = nullptr; a.tile_walked = c->tile_walked_b.as<uint32_t>(); a.tile_work = c->tile_work_b.as<uint32_t>();
-    if (c->frame_capped && c->n_rounds == 1) a.tile_ext = c->tile_ext.as<uint2>();      // the lists end where gs_bin / the forward stopped writing them
-    a.cull = c->cfg.alpha_cull != 0;
-    a.parts = c->frame_parts;                                              // as the frame's forward
-    if (c->frame_seg_n && c->n_rounds == 1 && !c->frame_capped) {          // small grid: list segments instead of pixel parts (the forward left the snapshots)
-        // two list segments, and as many pixel parts on top as still fit the wave slots (C1: 4 x 2 waves per tile; C2: 1 x 2)
-        const long long nt = (long long)c->gx * c->gy;
-        a.snap = c->snap.as<float>(); a.seg_hist = c->seg_hist; a.seg_n = c->frame_seg_n;
-        a.parts = 4 * a.seg_n * nt <= c->wave_slots ? 4 : 2 * a.seg_n * nt <= c->wave_slots ? 2 : 1;
-    }
+    HIPCHK(c, c->ensure_bwd_counters());
+    GsCompositeArgs a = composite_args(c, true, 0);                        // order, parts, list segments: as the frame's plan says
+    a.dC = dC_dev;
+    // the segments of a tile ADD to these words, which only the frame's forward zeroed: a second backward launch of the frame inflates them
+    a.tile_walked = c->tile_walked_b.as<uint32_t>(); a.tile_work = c->tile_work_b.as<uint32_t>();
     if (!params_only) {
         c->last_dC = dC_dev;
         // zero fill of the gradient rows (64 B per gaussian), in line: on a side stream beside the forward composite it cost more than
@@ -311,13 +318,6 @@ static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *gr
         // (a small frame's gs_bin kernel has cleared them already: gs_bin_small.hip)
         if (!c->g2d_clean) HIPCHK(c, hipMemsetAsync(c->g2d.p, 0, (det ? sizeof(long long) : sizeof(float)) * GS_G2D_STRIDE * n1, c->stream));
         c->g2d_clean = false;
-        // launch order: the one the frame's forward used, or (no history) what the order kernel made of that forward
-        if (lpt_schedule(c)) { a.tile_order = c->frame_order; a.order_len = c->frame_order ? lpt_order_entries(c) : 0; }
-        a.split_ok = a.tile_order && lpt_front(c) > 0 && c->frame_parts == 1 && !c->frame_capped && c->n_rounds == 1;
-        if (a.split_ok && c->snap_order && c->snap_order == a.tile_order) {      // the forward left snapshots for this order's split tiles: list segments
-            a.snap = c->snap.as<float>(); a.seg_len = order_seg_len(c, a.tile_order); a.front = lpt_front(c);
-            a.snap_walked = c->snap_walked.as<uint32_t>() + (size_t)c->snap_parity * GS_SEG_SLOTS;
-        }
         {
             StageTimer t(c, GS_STAGE_COMPOSITE_BWD);                   // the kernel alone (what rocprof reports for it)
             HIPCHK(c, gs_launch_composite_bwd(a, c->stream));

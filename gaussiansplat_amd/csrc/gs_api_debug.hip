@@ -73,7 +73,7 @@ int gs_get_array(gs_ctx *c, int which, void *dst, int64_t bytes) {
             const size_t ni = (size_t)c->n_inst, nt = (size_t)c->gx * c->gy;
             const size_t w = which == GS_ARR_SORTED_IDS ? sizeof(uint32_t) : sizeof(uint64_t);
             if ((size_t)bytes != w * ni) return fail(c, GS_ERR_INVALID, "gs_get_array: size mismatch");
-            std::vector<uint32_t> h(ni ? ni : 1), dk(n ? n : 1), rg(2 * (nt ? nt : 1));
+            std::vector<uint32_t> h(ni ? ni : 1), dk(n ? n : 1), rg(2 * c->ntiles1());
             HIPCHK(c, hipMemcpyAsync(h.data(), c->ids.p, sizeof(uint32_t) * ni, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemcpyAsync(dk.data(), c->depth_key.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemcpyAsync(rg.data(), c->ranges.p, sizeof(uint32_t) * 2 * nt, hipMemcpyDeviceToHost, c->stream));
@@ -153,46 +153,21 @@ int gs_get_stage_stats(gs_ctx *c, double sum_ms[GS_STAGE_COUNT], int64_t count[G
     return GS_OK;
 }
 
+// An isolated launch over the finished frame, as the frame's plan ran it (composite_args) -- but for: no per-tile counters, a forward
+// without snapshots in the order the backward had, and what the variant asks for.
+// variant tens digit (gs_composite.hip: apply_sched_variant): 0 the frame's own launch order (what production uses for the
+// backward and for the next forward of the slot), 1 tile order, 3 = 0 explicitly
 static int debug_composite_args(gs_ctx *c, int which, int variant, GsCompositeArgs &a) {
-    a.W = c->cam.W; a.H = c->cam.H; a.gx = c->gx; a.gy = c->gy; a.t_min = c->cfg.t_min;
-    a.ranges = c->ranges.as<uint32_t>(); a.ids = c->ids.as<uint32_t>(); a.payload = c->payload.as<GsPayload>();
-    a.image = c->img(); a.trans = c->tr();
-    a.dC = c->last_dC; a.walked = nullptr;
+    a = composite_args(c, which != 0, 0, true);
+    a.dC = c->last_dC;
     if (variant >= 10000) {                                                  // + 10000: with the two work-counter atomics per tile of a real frame (scratch words; tools/atomics_tail.py)
         variant -= 10000;
         a.walked = reinterpret_cast<unsigned long long *>(static_cast<char *>(c->counters.p) + 160);
     }
     a.final_round = 1;
-    a.nseg = 0;
-    for (int r = 0; r < c->n_rounds; ++r) {
-        if (r > 0 && c->round_gen[r] == 0) continue;
-        a.seg_ranges[a.nseg] = r == 0 ? c->ranges.as<uint32_t>() : c->ranges_r[r].as<uint32_t>();
-        a.seg_ids[a.nseg] = c->ids.as<uint32_t>() + c->round_ids_off[r];
-        ++a.nseg;
-    }
-    a.g2d = c->cfg.deterministic ? nullptr : c->g2d.as<float>(); a.g2d_fixed = c->cfg.deterministic ? c->g2d.as<long long>() : nullptr;
     c->g2d_clean = false;
-    if (c->frame_capped && c->n_rounds == 1) {
-        a.tile_ext = c->tile_ext.as<uint2>(); a.cranges = c->cranges.as<uint32_t>(); a.cids = c->cids.as<uint32_t>(); a.clr = c->clr.as<uint16_t>();
-        a.ids_w = c->ids.as<uint32_t>(); a.sgx = c->sgx; a.sbs = c->sbs; a.ext_count = c->ext_count();
-    }
     a.variant = variant % 100;
     a.cull = (c->cfg.alpha_cull != 0) != (variant >= 1000);                  // +1000: the other cull setting
-    // variant tens digit (gs_composite.hip: apply_sched_variant): 0 the frame's own launch order (what production uses for the
-    // backward and for the next forward of the slot), 1 tile order, 3 = 0 explicitly
-    a.tile_order = lpt_schedule(c) ? c->frame_order : nullptr;
-    a.order_len = a.tile_order ? lpt_order_entries(c) : 0;
-    a.split_ok = a.tile_order && lpt_front(c) > 0 && c->frame_parts == 1 && !c->frame_capped && c->n_rounds == 1;
-    if (which == 1 && a.split_ok && c->snap_order && c->snap_order == a.tile_order) {          // the backward's list segments, as the frame ran them
-        a.snap = c->snap.as<float>(); a.seg_len = order_seg_len(c, a.tile_order); a.front = lpt_front(c);
-        a.snap_walked = c->snap_walked.as<uint32_t>() + (size_t)c->snap_parity * GS_SEG_SLOTS;
-    }
-    a.parts = c->frame_parts;                                                // as the frame's own launches (tile clocks: one wave per tile only)
-    if (which == 1 && c->frame_seg_n && c->n_rounds == 1 && !c->frame_capped && !a.tile_order) {   // small grid: the backward's list segments
-        const long long nt = (long long)c->gx * c->gy;
-        a.snap = c->snap.as<float>(); a.seg_hist = c->seg_hist; a.seg_n = c->frame_seg_n;
-        a.parts = 4 * a.seg_n * nt <= c->wave_slots ? 4 : 2 * a.seg_n * nt <= c->wave_slots ? 2 : 1;
-    }
     if (c->dbg_win_len > 0) {                                                // gs_debug_set_window: a slice of the launch order
         if (!a.tile_order || a.parts > 1) return fail(c, GS_ERR_INVALID, "gs_debug_set_window: the frame has no launch order (or several waves per tile)");
         if (c->dbg_win_start + c->dbg_win_len > a.order_len) return fail(c, GS_ERR_INVALID, "gs_debug_set_window: beyond the launch order");
@@ -237,7 +212,6 @@ int gs_debug_tile_clock(gs_ctx *c, int which, int variant, uint64_t *out) {
     if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_debug_tile_clock: gs_forward first");
     if (which == 1 && !c->did_bwd) return fail(c, GS_ERR_INVALID, "gs_debug_tile_clock: gs_backward first");
     if (bind_device(c)) return GS_ERR_HIP;
-    const size_t ntiles = (size_t)c->gx * c->gy;
     GsCompositeArgs a{};
     const bool by_block = variant < 0;                                        // negative variant: records per WORKGROUP (launches with split tiles):
     if (by_block) variant = -variant;                                         // out holds gs_debug_tile_clock_rows() rows
@@ -248,7 +222,7 @@ int gs_debug_tile_clock(gs_ctx *c, int which, int variant, uint64_t *out) {
             return fail(c, GS_ERR_INVALID, "gs_debug_tile_clock: records by workgroup need the frame's launch order (or a small grid's tile parts)");
         a.clock_by_block = 1;
     } else { a.split_ok = 0; a.snap = nullptr; }                              // records by tile: whole tiles only
-    const size_t rows = !a.clock_by_block ? ntiles : a.tile_order ? (size_t)(lpt_order_entries(c) + gs_seg_units(lpt_front(c))) : (size_t)gs_debug_tile_clock_rows(c);
+    const size_t rows = a.clock_by_block ? (size_t)gs_debug_tile_clock_rows(c) : (size_t)c->gx * c->gy;
     if (a.clock_by_block && (size_t)gs_composite_grid_blocks(a, which) > rows) return fail(c, GS_ERR_INVALID, "gs_debug_tile_clock: launch larger than its record");
     HIPCHK(c, c->tile_clock.ensure(sizeof(uint64_t) * GS_TILE_CLOCK_WORDS * (rows ? rows : 1)));
     HIPCHK(c, hipMemsetAsync(c->tile_clock.p, 0, sizeof(uint64_t) * GS_TILE_CLOCK_WORDS * rows, c->stream));
@@ -266,7 +240,7 @@ int gs_debug_tile_clock_rows(gs_ctx *c) {
     if (lpt_schedule(c)) return lpt_order_entries(c) + gs_seg_units(lpt_front(c));
     // small grids: blocks of one part x the most waves a tile is given (pixel parts x list segments of the backward); 0: one wave per tile
     const int len = ((c->gx * c->gy + 7) / 8) * 8;
-    const int units = std::max(c->frame_parts, 1) * (c->frame_seg_n ? 4 * c->frame_seg_n : 1);
+    const int units = c->plan.parts * (c->plan.snap == gs_ctx::FramePlan::Snap::ALL ? 4 * c->plan.seg_n : 1);   // (an upper bound: at most four parts on top of the segments)
     return units > 1 ? len * units : 0;
 }
 
@@ -328,7 +302,7 @@ int gs_get_list_stats(gs_ctx *c, int64_t out[3]) {
 int gs_get_tile_parts(gs_ctx *c) {
     if (!c) return GS_ERR_INVALID;
     if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_get_tile_parts: gs_forward first");
-    return c->frame_parts;
+    return c->plan.parts;
 }
 
 int gs_get_bin_path(gs_ctx *c) {

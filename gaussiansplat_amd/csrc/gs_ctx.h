@@ -2,9 +2,10 @@
 // Internal: nothing here is part of the ABI.  The entry points live in
 //   gs_api.hip            create / destroy, model, camera, gs_preprocess, gradients buffers, loss, SGD
 //   gs_api_bin.hip        gs_bin: depth order, two-level tile lists (speculative launch, capped lists, depth slabs), radix paths
-//   gs_api_composite.hip  gs_forward / gs_backward and the launch orders of the view slots
+//   gs_api_composite.hip  gs_forward / gs_backward: the frame's plan (plan_frame), the one builder of the composite launches' arguments
+//                         (composite_args), the launch orders of the view slots
 //   gs_api_comm.hip       RCCL below the boundary (gs_comm_*, gs_allreduce_grads)
-//   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters)
+//   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
 #pragma once
 #include "../../include/gsplat.h"
 #include "gs_common.h"
@@ -55,6 +56,8 @@ struct gs_ctx {
     GsCamera cam{};
     bool have_cam = false, did_pre = false, did_bin = false, did_fwd = false, did_bwd = false, did_bwd_composite = false;
     int gx = 0, gy = 0;
+    int64_t grid_key() const { return ((int64_t)gx << 32) | (int64_t)gy; }        // what per-grid history is tagged with (0: none)
+    size_t ntiles1() const { const size_t nt = (size_t)gx * gy; return nt ? nt : 1; }   // tiles, for buffer sizes (never zero)
 
     DevBuf invcov;                           // 4 x n raw conic (introspection; the payload rows carry it scaled)
     DevBuf payload, depth_key, rect, pairs_a, pairs_b, perm, offsets, block_sums;
@@ -77,36 +80,55 @@ struct gs_ctx {
     // ---- longest-first launch orders (gs_config.schedule 3 / 4).  After every forward ONE order kernel turns the frame's per-tile
     // work into a launch order: this frame's backward uses it, and so does the NEXT forward rendered under the same view slot.
     int view_slot = -1;                      // gs_set_view_slot: the slot of the frame being rendered (-1: none)
-    // Orders are double buffered: [slot][sel] is the newest one; the order kernel of a frame writes the OTHER buffer on the side
-    // stream while this frame's backward still reads the one its forward used.  Index GS_MAX_VIEW_SLOTS = frames without a slot.
+    // Index GS_MAX_VIEW_SLOTS = frames without a slot.  A slot owns two double buffers, each tagged with the grid (grid_key) it is valid for:
     struct ViewSlot {
-        DevBuf order[2];                     // launch orders, double buffered
-        int sel = 0;                         // the newest one
-        int64_t tiles = 0;                   // ... is valid for this grid (gx << 32 | gy; 0: no history)
-        DevBuf walkbuf[2];                   // per tile: list entries the slot's forwards walked, double buffered: [wsel] = the last completed forward's
-        int wsel = 0;                        // (the next frame's list caps and segment lengths), the other one is what the frame being rendered writes
-        int64_t walked_grid = 0;             // ... on this grid (0: none yet)
+        // launch orders: [sel] is the newest one; a frame that runs on it has its order kernel write the OTHER buffer (on the side stream,
+        // while the frame's backward still reads [sel]), a frame without history writes [sel] itself
+        DevBuf order[2];
+        int sel = 0;
+        int64_t tiles = 0;                   // grid of order[sel] (0: no history)
+        int order_dst(bool in_use) const { return in_use ? sel ^ 1 : sel; }
+        void order_written(int buf, int64_t grid) { sel = buf; tiles = grid; }          // order[buf] is the newest one now
+        // per tile: list entries the slot's forwards walked (the next frame's list caps and segment lengths): [wsel] = the last completed
+        // forward's, which the frame being rendered may still read while it writes its own into the other one
+        DevBuf walkbuf[2];
+        int wsel = 0;
+        int64_t walked_grid = 0;             // grid of walkbuf[wsel] (0: none yet)
         DevBuf &walked() { return walkbuf[wsel]; }
+        DevBuf &walk_dst() { return walkbuf[wsel ^ 1]; }
+        void walk_written(int64_t grid) { wsel ^= 1; walked_grid = grid; }      // the frame's forward is enqueued: its walk is the slot's history now
     };
     std::vector<ViewSlot> slots;             // GS_MAX_VIEW_SLOTS + 1 (allocated at gs_create; device buffers on first use)
     const uint32_t *last_walked = nullptr;   // per-tile walked counts of the most recent forward (the slot's array, or tile_walked)
     // ---- capped lists (gs_config.list_cap): this frame's tile lists were written only as far as the slot's history says they are walked
-    bool frame_capped = false;
-    int frame_parts = 1;                   // waves per tile of the frame's composite launches (gs_config.tile_parts; decided by gs_forward)
-    int wave_slots = 5120;                 // waves of the composite kernels the device holds at once: CUs x 4 SIMDs x 5 (GS_FWD_MINW, GS_BWD_MINW); gs_create
+    bool frame_capped = false;               // LIVE state, not plan: gs_get_array(GS_ARR_SORTED_IDS / _KEYS) completes the lists and clears it
+    int wave_slots = 5120;                   // CUs x 4 SIMDs x 5 BY DEFINITION (gs_create): the unit of every threshold; the backward holds six waves per SIMD by now
     const uint32_t *cap_src = nullptr;       // the history the caps of this frame come from (null: none)
     DevBuf tile_nopen, smax, tile_ext, zero_tiles;
     GsBin3Args last_l2{};                    // the level-2 arguments of the frame's lists (gs_get_array writes the capped rest with them)
     bool have_l2 = false;
-    const uint32_t *frame_order = nullptr;   // the launch order of THIS frame's composite kernels (null: tile order)
-    // ---- heavy tiles: list segments of the backward (GsCompositeArgs.snap)
-    DevBuf snap, snap_walked;                // the forward's snapshots of the split tiles; their walked lengths, two frame parities
-    const uint32_t *snap_order = nullptr;    // the order whose split tiles this frame's forward left snapshots for (null: none)
-    int frame_seg_n = 0;                     // small grids: list segments per tile of this frame's backward (0: none; the forward left snapshots for them)
-    const uint32_t *seg_hist = nullptr;      // ... and the walk history their lengths come from (the slot's previous forward)
+    // ---- the frame's plan: HOW its composite launches run.  Filled once per frame by plan_frame (gs_api_composite.hip), the one place that
+    // decides; composite_args turns it into the arguments of every launch of the frame: forward rounds, backward, debug launches.
+    struct FramePlan {
+        int parts = 1;                       // waves per tile of the forward (pixel parts; gs_config.tile_parts, gs_get_tile_parts)
+        int bwd_parts = 1;                   // ... and of the backward: the same, or (Snap::ALL) what still fits on top of the list segments
+        const uint32_t *order = nullptr;     // launch order of the forward (null: tile order) ...
+        const uint32_t *bwd_order = nullptr; // ... and of the backward: the same, or (a slot's first frame; no side stream) what build_frame_order made of this forward
+        bool side = false;                   // the order kernel behind the forward runs on the side stream, for the slot's NEXT frame: bwd_order == order
+        int front = 0;                       // lpt_front: entries of the orders' front region
+        bool split = false;                  // launches over an order honour its split entries (heavy tiles run as several waves) while the lists are full
+        // snapshots the forward leaves for list segments of the backward (GsCompositeArgs.snap)
+        enum class Snap { NONE, HEAVY, ALL } snap = Snap::NONE;
+        uint32_t *snap_walked = nullptr;     // HEAVY (the split tiles of `order`; seg_len sits behind its entries): this frame's parity slice of gs_ctx::snap_walked
+        int seg_n = 0;                       // ALL (small grid): every tile, seg_n segments each ...
+        const uint32_t *seg_hist = nullptr;  // ... their lengths from the walk of the slot's previous forward
+        bool bwd_segments = false;           // the backward runs as list segments: the forward LEFT snapshots, and for the order the backward takes
+    } plan;
+    // ---- heavy tiles: list segments of the backward
+    DevBuf snap, snap_walked;                // the forward's snapshots (HEAVY: of the split tiles, ALL: of every tile); HEAVY: their walked lengths, two frame parities
     uint32_t *pinned_split = nullptr;        // coherent pinned host words, two per view slot (one per order buffer): split tiles of that order, as its
                                              // order kernel counted them (0xFFFFFFFF: the kernel has not reported yet); null: unknown, assume some
-    const uint32_t *frame_order_split = nullptr;   // ... the word of this frame's order
+    uint32_t *split_word(int slot, int buf) { return pinned_split ? pinned_split + 2 * slot + buf : nullptr; }
     int snap_parity = 0;                     // the parity of snap_walked this frame's forward writes (and its backward reads); the order kernel
                                              // behind every forward re-arms the other one and the parities swap
     // ---- side stream: the order kernel (needed by the slot's NEXT frame, not by this one) runs beside the backward composite
@@ -140,7 +162,9 @@ struct gs_ctx {
     // after sum_work_counters() (gs_get_work_counters, the radix binning paths); the two-level path sums the walked counts of the
     // previous forward inside l1_rowscan on their way to the host
     DevBuf tile_walked, tile_walked_b, tile_work_b;
-    int64_t counters_grid = 0;               // the grid (gx << 32 | gy) the forward's per-tile counters were written for
+    hipError_t ensure_bwd_counters() { const hipError_t e = tile_walked_b.ensure(sizeof(uint32_t) * ntiles1()); return e != hipSuccess ? e : tile_work_b.ensure(sizeof(uint32_t) * ntiles1()); }
+    int64_t counters_grid = 0;               // the grid (grid_key) the forward's per-tile counters were written for
+    bool counters_here() const { return counters_grid == grid_key() && last_walked; }   // ... is the one at hand
     // ---- depth sort in two steps (gs_depth_sort_buckets; gs_config.depth_sort)
     DevBuf key_range;                        // two frame parities of the key-range accumulators the preprocess kernel fills
     int range_parity = 0;                    // parity of the frame being built
@@ -235,7 +259,7 @@ inline int bind_device(gs_ctx *c) {
     return GS_OK;
 }
 
-// A launch order is built only when there are more tiles than wave slots (gs_ctx::wave_slots: 256 CUs x 4 SIMDs x 5 waves on MI355X).  Below that the isolated
+// A launch order is built only when there are more tiles than wave slots (gs_ctx::wave_slots: 256 CUs x 4 SIMDs x 5 on MI355X).  Below that the isolated
 // kernels do gain from it (C2, 2500 tiles: forward 68 -> 61 us, backward 145 -> 122 us, tools/xcd_order.py C2 -- in tile order the
 // heavy tiles of the image centre land on neighbouring SIMDs), but the frame does not: its forward is bound by cold gathers, not by
 // balance, and the order kernel is one more launch in a frame that is bound by launches (C2 0.382 -> 0.400 ms, C1 0.183 -> 0.205 ms
@@ -246,7 +270,7 @@ inline bool lpt_schedule(const gs_ctx *c) {
 // Heavy tiles (round 5): the launch orders reserve a front region for the extra parts of split tiles (tile_lpt_order_kernel) when the
 // ctx may use them at all: automatic tile_parts, the early-out on, and a grid on which the frame-wide 2 / 4 waves per tile cannot engage.
 // A property of the ctx and the grid, so every order of a slot has one layout; whether a LAUNCH honours the split entries is decided
-// per frame (split_ok: full lists, one binning round).
+// per frame (plan_frame: FramePlan::split).
 inline int lpt_front(const gs_ctx *c) {
     const int64_t ntiles = (int64_t)c->gx * c->gy;
     return (lpt_schedule(c) && c->cfg.tile_parts == 0 && c->cfg.t_min > 0.0f && 2 * ntiles > c->wave_slots && ntiles <= GS_LPT_MAX_TILES) ? GS_LPT_FRONT : 0;
@@ -267,6 +291,5 @@ int bin_round(gs_ctx *c, int r);
 int depth_order(gs_ctx *c, uint32_t **perm_out);
 // gs_api_comm.hip
 void comm_release(gs_ctx *c);                // destroys the ctx's RCCL communicator, if any
-// gs_api_composite.hip
-const uint32_t *forward_order(gs_ctx *c);
-int build_frame_order(gs_ctx *c, const uint32_t *used);
+// gs_api_composite.hip: the arguments of a composite launch of the frame, as its plan says (round r of the forward / the backward; debug: an isolated launch)
+GsCompositeArgs composite_args(gs_ctx *c, bool bwd, int r, bool debug = false);
