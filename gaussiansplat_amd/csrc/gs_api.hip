@@ -78,7 +78,7 @@ int gs_create(gs_ctx **out, int device, const gs_config *cfg) {
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->wave_slots = prop.multiProcessorCount * 4 * 5;
         else (void)hipGetLastError();
     }
-    if ((e = hipHostMalloc((void **)&c->pinned, 512, hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return hipfail(nullptr, e, "hipHostMalloc"); }
+    if ((e = hipHostMalloc((void **)&c->pinned, sizeof(PinnedWords), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return hipfail(nullptr, e, "hipHostMalloc"); }
     if ((e = hipHostMalloc((void **)&c->pinned_split, sizeof(uint32_t) * 2 * (GS_MAX_VIEW_SLOTS + 1), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess) {
         (void)hipGetLastError(); c->pinned_split = nullptr;              // (speed only: without it every order counts as "may hold split tiles")
     } else std::memset(c->pinned_split, 0, sizeof(uint32_t) * 2 * (GS_MAX_VIEW_SLOTS + 1));
@@ -291,7 +291,7 @@ int gs_preprocess(gs_ctx *c) {
             HIPCHK(c, gs_depth_range_reset(c->key_range.as<uint32_t>(), c->stream));
         }
         c->range_parity ^= 1;
-        a.key_range = c->key_range.as<uint32_t>() + (size_t)c->range_parity * gs_depth_range_parity_words();
+        a.key_range = key_range_of(c, c->range_parity);
         c->range_valid = true;
     }
     if (c->cfg.export_debug) {

@@ -34,14 +34,14 @@ static void plan_frame(gs_ctx *c, const uint32_t *order, const uint32_t *order_s
     gs_ctx::FramePlan p;
     const int want = c->cfg.tile_parts;
     // launches that composite whole tiles, one wave each: no early-out, slab rounds, capped lists
-    const bool whole = !(c->cfg.t_min > 0.0f) || c->n_rounds > 1 || c->frame_capped;
+    const bool whole = !(c->cfg.t_min > 0.0f) || c->bin.n_rounds > 1 || c->frame_capped;
     p.parts = p.bwd_parts = want == 1 || whole ? 1 : (want == 2 || want == 4) ? want : parts_that_fit(c, 1);
     p.order = p.bwd_order = order;
     // The backward runs in the forward's order while the order kernel works beside it, on the side stream, for the slot's next frame; else
     // (a slot's first frame; no side stream) it waits for that kernel and takes the fresh order: build_frame_order then sets bwd_order
     p.side = order && use_side_stream(c);
     p.front = lpt_front(c);
-    p.split = p.front > 0 && p.parts == 1 && c->n_rounds == 1;            // heavy tiles run as the orders' split entries say (full lists: asked at every launch, frame_capped is live)
+    p.split = p.front > 0 && p.parts == 1 && c->bin.n_rounds == 1;            // heavy tiles run as the orders' split entries say (full lists: asked at every launch, frame_capped is live)
     // neither snapshot mode looks at cfg.deterministic, so deterministic gradients depend on the slot's history
     const bool may_split = !order_split || *order_split != 0u;            // (the order kernel's count; 0xFFFFFFFF: not reported yet)
     if (order && p.split && c->snap_walked.p && may_split) {
@@ -71,7 +71,7 @@ GsCompositeArgs composite_args(gs_ctx *c, bool bwd, int r, bool debug) {
     a.W = c->cam.W; a.H = c->cam.H; a.gx = c->gx; a.gy = c->gy; a.t_min = c->cfg.t_min;
     a.payload = c->payload.as<GsPayload>(); a.image = c->img(); a.trans = c->tr();
     a.cull = c->cfg.alpha_cull != 0;
-    for (int q = 0; q < c->n_rounds; ++q) {                                // the lists, round by round (a round that listed nothing: skipped)
+    for (int q = 0; q < c->bin.n_rounds; ++q) {                                // the lists, round by round (a round that listed nothing: skipped)
         if (q > 0 && c->round_gen[q] == 0) continue;
         a.seg_ranges[a.nseg] = q == 0 ? c->ranges.as<uint32_t>() : c->ranges_r[q].as<uint32_t>();
         a.seg_ids[a.nseg] = c->ids.as<uint32_t>() + c->round_ids_off[q];
@@ -82,11 +82,11 @@ GsCompositeArgs composite_args(gs_ctx *c, bool bwd, int r, bool debug) {
     a.tile_order = bwd || debug ? p.bwd_order : p.order; a.order_len = a.tile_order ? lpt_order_entries(c) : 0;
     a.parts = bwd ? p.bwd_parts : p.parts;
     a.split_ok = a.tile_order && p.split && !c->frame_capped;
-    if (c->frame_capped && c->n_rounds == 1) {
+    if (c->frame_capped && c->bin.n_rounds == 1) {
         a.tile_ext = c->tile_ext.as<uint2>();                              // the lists end where gs_bin / the forward stopped writing them
         if (!bwd) {                                                        // the forward's wave extends its tile's list when it must
             a.cranges = c->cranges.as<uint32_t>(); a.cids = c->cids.as<uint32_t>(); a.clr = c->clr.as<uint16_t>();
-            a.ids_w = c->ids.as<uint32_t>(); a.sgx = c->sgx; a.sbs = c->sbs; a.ext_count = c->ext_count();
+            a.ids_w = c->ids.as<uint32_t>(); a.sgx = c->bin.sgx; a.sbs = c->bin.sbs; a.ext_count = c->ext_count();
         }
     }
     if (bwd ? p.bwd_segments : !debug) {                                   // snapshots: the forward leaves them, the backward starts its list segments from them
@@ -168,11 +168,11 @@ static int enqueue_forward_round(gs_ctx *c, int r) {
         HIPCHK(c, c->ensure_bwd_counters());
     }
     GsCompositeArgs a = composite_args(c, false, r);
-    a.resume = r > 0; a.final_round = r == c->n_rounds - 1;
+    a.resume = r > 0; a.final_round = r == c->bin.n_rounds - 1;
     a.tile_work = c->tile_work.as<uint32_t>(); a.tile_walked = const_cast<uint32_t *>(c->last_walked);
     p.bwd_segments = a.snap && (p.side || !p.order);                       // snapshots left, and (HEAVY) the backward takes the order they belong to
     if (a.snap) { a.bw_walked = c->tile_walked_b.as<uint32_t>(); a.bw_work = c->tile_work_b.as<uint32_t>(); }   // (its waves zero the segmented tiles' words)
-    if (c->n_rounds > 1) { a.tile_pos = c->tile_pos.as<uint32_t>(); a.tile_done = c->tile_done.as<uint8_t>(); a.tile_dead = c->tile_dead.as<unsigned long long>(); }
+    if (c->bin.n_rounds > 1) { a.tile_pos = c->tile_pos.as<uint32_t>(); a.tile_done = c->tile_done.as<uint8_t>(); a.tile_dead = c->tile_dead.as<unsigned long long>(); }
     StageTimer t(c, GS_STAGE_COMPOSITE_FWD);                               // the kernel alone
     HIPCHK(c, gs_launch_composite_fwd(a, c->stream));
     return GS_OK;
@@ -203,7 +203,7 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
         HIPCHK(c, c->tile_walked.ensure(sizeof(uint32_t) * nt1));
         c->last_walked = c->tile_walked.as<uint32_t>();
     }
-    const int R = c->n_rounds;
+    const int R = c->bin.n_rounds;
     if (R > 1) {
         HIPCHK(c, c->tile_pos.ensure(sizeof(uint32_t) * nt1));
         HIPCHK(c, c->tile_done.ensure(nt1));

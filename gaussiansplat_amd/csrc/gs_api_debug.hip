@@ -6,8 +6,8 @@ extern "C" {
 
 int64_t gs_num_gaussians(const gs_ctx *c) { return c ? c->n : 0; }
 int64_t gs_num_instances(gs_ctx *c) { if (!c) return 0; (void)settle_totals(c, nullptr, true); return c->n_inst; }
-int64_t gs_num_coarse_instances(gs_ctx *c) { if (!c) return 0; (void)settle_totals(c, nullptr, true); return c->two_level ? c->n_coarse : 0; }
-int gs_num_rounds(const gs_ctx *c) { return c ? c->n_rounds : 0; }
+int64_t gs_num_coarse_instances(gs_ctx *c) { if (!c) return 0; (void)settle_totals(c, nullptr, true); return c->bin.radix() ? 0 : c->n_coarse; }
+int gs_num_rounds(const gs_ctx *c) { return c ? c->bin.n_rounds : 0; }
 
 int gs_get_array(gs_ctx *c, int which, void *dst, int64_t bytes) {
     if (!c || !dst) return GS_ERR_INVALID;
@@ -22,7 +22,7 @@ int gs_get_array(gs_ctx *c, int which, void *dst, int64_t bytes) {
     if (which <= GS_ARR_TILE_RECT && !c->did_pre) return fail(c, GS_ERR_INVALID, "gs_get_array: gs_preprocess first");
     if (which >= GS_ARR_SORT_IDXS && which <= GS_ARR_SORTED_KEYS && !c->did_bin) return fail(c, GS_ERR_INVALID, "gs_get_array: gs_bin first");
     if (which >= GS_ARR_TILE_RANGES && which <= GS_ARR_SORTED_KEYS) { if (int rc = settle_totals(c, nullptr, true)) return rc; }
-    if (which >= GS_ARR_TILE_RANGES && which <= GS_ARR_SORTED_KEYS && c->n_rounds > 1)
+    if (which >= GS_ARR_TILE_RANGES && which <= GS_ARR_SORTED_KEYS && c->bin.n_rounds > 1)
         return fail(c, GS_ERR_INVALID, "gs_get_array: this frame was binned in depth slabs (lists spread over rounds); use gs_config.slab_mode = 0");
     if ((which == GS_ARR_SORTED_IDS || which == GS_ARR_SORTED_KEYS) && c->frame_capped && c->have_l2) {
         // capped lists: only the part of every list the view slot's history says is walked has been written.  Write the rest now (the
@@ -58,10 +58,8 @@ int gs_get_array(gs_ctx *c, int which, void *dst, int64_t bytes) {
         case GS_ARR_TILE_RECT: src = c->rect.p; need = sizeof(uint16_t) * 4 * n; break;
         case GS_ARR_SORT_IDXS: {
             if ((size_t)bytes != sizeof(uint32_t) * n) return fail(c, GS_ERR_INVALID, "gs_get_array: size mismatch");
-            if (c->perm_pending) {                                  // a frame binned by the small path (gs_bin_small.hip) sorted nothing globally
-                uint32_t *perm = nullptr;
-                if (int rc = depth_order(c, &perm)) return rc;
-                c->perm_ptr = c->perm_all = perm; c->perm_pending = false;
+            if (c->bin.perm_on_demand && !c->perm_ptr) {            // a frame binned by the small path (gs_bin_small.hip) sorted nothing globally
+                if (int rc = depth_order(c, &c->perm_ptr)) return rc;
             }
             if (c->perm_ptr) { src = c->perm_ptr; need = sizeof(uint32_t) * n; break; }
             uint32_t *o = static_cast<uint32_t *>(dst);
@@ -162,7 +160,7 @@ static int debug_composite_args(gs_ctx *c, int which, int variant, GsCompositeAr
     a.dC = c->last_dC;
     if (variant >= 10000) {                                                  // + 10000: with the two work-counter atomics per tile of a real frame (scratch words; tools/atomics_tail.py)
         variant -= 10000;
-        a.walked = reinterpret_cast<unsigned long long *>(static_cast<char *>(c->counters.p) + 160);
+        a.walked = c->counters.as<CounterBlock>()->scratch;
     }
     a.final_round = 1;
     c->g2d_clean = false;
@@ -248,7 +246,7 @@ int gs_debug_clock_mhz(gs_ctx *c, float *mhz) {
     if (!c || !mhz) return GS_ERR_INVALID;
     if (bind_device(c)) return GS_ERR_HIP;
     HIPCHK(c, c->counters.ensure(GS_COUNTER_BYTES));
-    unsigned long long *d = reinterpret_cast<unsigned long long *>(static_cast<char *>(c->counters.p) + 160), h[2] = {0, 1};
+    unsigned long long *d = c->counters.as<CounterBlock>()->scratch, h[2] = {0, 1};
     HIPCHK(c, gs_launch_clock_probe(d, c->stream));
     HIPCHK(c, hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -288,8 +286,8 @@ int gs_get_list_stats(gs_ctx *c, int64_t out[3]) {
     if (bind_device(c)) return GS_ERR_HIP;
     if (int rc = settle_totals(c, nullptr, true)) return rc;
     out[0] = c->n_inst; out[1] = 0; out[2] = 0;
-    if (!c->frame_capped || c->n_rounds != 1) return GS_OK;
-    unsigned long long *d = reinterpret_cast<unsigned long long *>(static_cast<char *>(c->counters.p) + 160), h = 0;
+    if (!c->frame_capped || c->bin.n_rounds != 1) return GS_OK;
+    unsigned long long *d = c->counters.as<CounterBlock>()->scratch, h = 0;
     uint32_t e = 0;
     HIPCHK(c, gs_launch_sum_listed(c->tile_ext.as<uint2>(), c->gx * c->gy, d, c->stream));
     HIPCHK(c, hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -308,7 +306,7 @@ int gs_get_tile_parts(gs_ctx *c) {
 int gs_get_bin_path(gs_ctx *c) {
     if (!c) return GS_ERR_INVALID;
     if (!c->did_bin) return fail(c, GS_ERR_INVALID, "gs_get_bin_path: gs_bin first");
-    return c->small_bin ? 3 : c->two_level ? 0 : c->fast_bin ? 2 : 1;
+    return (int)c->bin.path;
 }
 
 int gs_get_work_counters_ex(gs_ctx *c, int64_t out[4]) {

@@ -1,7 +1,7 @@
 // gs_ctx.h -- the renderer context behind the C ABI (include/gsplat.h) and the host-side helpers its translation units share.
 // Internal: nothing here is part of the ABI.  The entry points live in
 //   gs_api.hip            create / destroy, model, camera, gs_preprocess, gradients buffers, loss, SGD
-//   gs_api_bin.hip        gs_bin: depth order, two-level tile lists (speculative launch, capped lists, depth slabs), radix paths
+//   gs_api_bin.hip        gs_bin: the frame's bin plan (plan_bin), depth order, one function per path (bin_small, bin_two_level, bin_radix), settle_totals
 //   gs_api_composite.hip  gs_forward / gs_backward: the frame's plan (plan_frame), the one builder of the composite launches' arguments
 //                         (composite_args), the launch orders of the view slots
 //   gs_api_comm.hip       RCCL below the boundary (gs_comm_*, gs_allreduce_grads)
@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,7 +39,30 @@ struct DevBuf {
 
 extern std::string g_create_error;         // message of the last failed gs_create (gs_last_error(NULL))
 
-#define GS_COUNTER_BYTES 192      // 32 B of work-counter sums (on demand) | byte 128: the binning totals | 144: list segments appended by waves | 160: debug scratch
+#define GS_COUNTER_BYTES 192
+struct CounterBlock {                        // gs_ctx::counters on the device, and its copy inside the pinned block
+    uint32_t work[8];                        // 4 x u64 {walked, evaluated} of the forward and of the backward: sums, on demand (sum_work_counters)
+    uint32_t pad0[24];
+    uint32_t totals[4];                      // byte 128: the binning totals {coarse instances listed, fine instances of the slab, of all n}
+    uint32_t ext_count;                      // byte 144: list segments appended by composite waves (capped lists)
+    uint32_t pad1[3];
+    unsigned long long scratch[4];           // byte 160: debug scratch (clock probe, listed-entry sum, the work-counter atomics of a debug launch)
+};
+// The 512 coherent pinned host bytes of a ctx: what kernels and copies of the frame in flight leave for the host behind ev_count.
+struct PinnedWords {
+    uint32_t readback[2];                    // words 0, 1: copied back by the paths whose host waits.  Radix frame: {instances, generated positions of round 0};
+                                             // later radix round: {its instances}; later two-level round: {coarse, fine instances of its slab}
+    uint32_t walked_prev[2];                 // word 2: u64, entries the previous forward walked (radix paths)
+    uint32_t pad0[4];
+    CounterBlock counters;                   // word 8: two-level and small paths: `work[0..1]` = the previous forward's walk, `totals` = this frame's
+    uint32_t pad1[44];
+    uint32_t dsort_stat[2];                  // word 100: status of the depth sort's bucket path, two frame parities
+    uint32_t pad2[26];
+};
+static_assert(sizeof(CounterBlock) == GS_COUNTER_BYTES && offsetof(CounterBlock, totals) == 128 && offsetof(CounterBlock, ext_count) == 144 &&
+              offsetof(CounterBlock, scratch) == 160, "counter block layout (the kernels address it by these offsets)");
+static_assert(sizeof(PinnedWords) == 512 && offsetof(PinnedWords, readback) == 0 && offsetof(PinnedWords, walked_prev) == 8 &&
+              offsetof(PinnedWords, counters) == 32 && offsetof(PinnedWords, dsort_stat) == 400, "pinned block layout");
 struct gs_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -66,7 +90,7 @@ struct gs_ctx {
     DevBuf ids, words, cs, diff;             // sorted gaussian ids; pass-1 words; chunk owners; 2-D difference array
     uint32_t *perm_ptr = nullptr;
     int64_t n_inst = 0;
-    uint32_t *pinned = nullptr;
+    PinnedWords *pinned = nullptr;
     const float *last_dC = nullptr;          // device dC of the last gs_backward (debug timing)
 
     hipEvent_t ev_count = nullptr;           // instance count landed in pinned memory
@@ -107,6 +131,18 @@ struct gs_ctx {
     DevBuf tile_nopen, smax, tile_ext, zero_tiles;
     GsBin3Args last_l2{};                    // the level-2 arguments of the frame's lists (gs_get_array writes the capped rest with them)
     bool have_l2 = false;
+    // ---- the frame's bin plan: HOW gs_bin builds its lists.  Filled once per frame by plan_bin (gs_api_bin.hip), the one place that decides.  What later calls
+    // change is LIVE state and stays outside: frame_capped, have_l2 / last_l2, cap_src, pending_totals, spec_lists, perm_ptr, n_inst, n_coarse, round_gen, round_ids_off.
+    struct BinPlan {
+        enum class Path { TWO_LEVEL = 0, RADIX64 = 1, RADIX32 = 2, SMALL = 3 } path = Path::RADIX64;   // the values: what gs_get_bin_path reports
+        int tile_bits = 0, gid_bits = 0, lo_bits = 0, hi_bits = 0;                        // bits of a tile index (low / high radix pass) and of a gaussian id
+        int sbs = 3, sgx = 0, sgy = 0;       // two-level path: log2 of the super-tile edge in tiles (3, or 4 on 4K-class grids), super-tile grid
+        int n_rounds = 1;                    // binning rounds of the frame (depth slabs, gs_config.slab_mode) ...
+        int64_t slab_lo[GS_MAX_ROUNDS + 1] = {};   // ... round r covers the list positions [slab_lo[r], slab_lo[r+1]) of the depth order
+        bool perm_on_demand = false;         // SMALL sorts nothing globally: the depth order (renderer.sortIdxs) is built when gs_get_array asks (perm_ptr null until then)
+        int ns() const { return sgx * sgy; }
+        bool radix() const { return path == Path::RADIX32 || path == Path::RADIX64; }
+    } bin;
     // ---- the frame's plan: HOW its composite launches run.  Filled once per frame by plan_frame (gs_api_composite.hip), the one place that
     // decides; composite_args turns it into the arguments of every launch of the frame: forward rounds, backward, debug launches.
     struct FramePlan {
@@ -139,25 +175,19 @@ struct gs_ctx {
     bool pending_totals = false;             // ev_count recorded, pinned totals not read yet
     bool spec_lists = false;                 // the lists of this frame were enqueued before the totals were known ...
     size_t spec_cap_coarse = 0, spec_cap_fine = 0;   // ... against these capacities (entries)
-    int64_t n_coarse = 0;
+    int64_t n_coarse = 0;                    // coarse instances listed by the frame (two-level and small paths; 0 on the radix paths)
     DevBuf tile_dead;                        // slab frames: 4 lane masks per tile (frozen pixels between rounds)
     int dbg_win_start = 0, dbg_win_len = 0;  // gs_debug_set_window: the part of the launch order the debug launches cover (len 0: all)
     int rank_probe = -1;                     // lane-order probe of the LDS atomic rank: -1 not run, 0 passed, 1 failed (ballots forced)
-    // ---- binning in depth slabs (gs_config.slab_mode)
-    int n_rounds = 1;                        // binning rounds of the current frame
-    int64_t slab_lo[GS_MAX_ROUNDS + 1] = {}; // round r covers the list positions [slab_lo[r], slab_lo[r+1]) of the depth order
+    // ---- binning in depth slabs (BinPlan::n_rounds, slab_lo)
     int64_t round_gen[GS_MAX_ROUNDS] = {};   // generated instance positions of the round (>= the instances it lists)
     size_t round_ids_off[GS_MAX_ROUNDS] = {};// where the round's ids start inside `ids`
     DevBuf ranges_r[GS_MAX_ROUNDS];          // tile ranges of rounds 1.. (round 0 uses `ranges`)
     DevBuf tile_pos, tile_done, live2d, rect_r, offsets_r, live_total;
-    uint32_t *perm_all = nullptr;            // the whole depth order (perm_ptr)
     // ---- two-level binning (gs_bin3.hip): lists per super-tile of 8 x 8 tiles, then per tile
-    bool two_level = false;
-    int sgx = 0, sgy = 0, sbs = 3;           // super-tile grid and log2 of the super-tile edge in tiles (3, or 4 on 4K-class grids)
-    int64_t coarse_listed = 0;               // coarse instances of the current round
     DevBuf rect_sorted, l1_table, l1_rows, l1_partials, cids, clr, cranges, segcnt, sdone, tilecnt;
-    uint32_t *bin_totals() { return counters.as<uint32_t>() + 32; }
-    uint32_t *ext_count() { return counters.as<uint32_t>() + 36; }          // byte 144: list segments appended by composite waves (capped lists)
+    uint32_t *bin_totals() { return counters.as<CounterBlock>()->totals; }
+    uint32_t *ext_count() { return &counters.as<CounterBlock>()->ext_count; }
     // ---- per-tile work counters of the composite launches (walked / evaluated list entries): counters[0..3] hold their sums only
     // after sum_work_counters() (gs_get_work_counters, the radix binning paths); the two-level path sums the walked counts of the
     // previous forward inside l1_rowscan on their way to the host
@@ -173,16 +203,14 @@ struct gs_ctx {
     int64_t dsort_classic_until = 0;         // frame id up to which the classic sort is used (an oversize bucket was reported)
     int dsort_stat_parity = 0;               // the parity gs_bin used for the bucket path's pinned stat word (gs_preprocess of the NEXT frame flips range_parity
                                              // before settle_totals of this one may run)
-    uint32_t *dsort_stat() { return pinned + 100 + (dsort_stat_parity & 1); }
+    uint32_t *dsort_stat() { return &pinned->dsort_stat[dsort_stat_parity & 1]; }
     // the bucket path is possible for the frame being built (same predicate in gs_preprocess, which then folds the key range, and in gs_bin)
     bool dsort_can_bucket() const {
         return cfg.depth_sort != 1 && (cfg.depth_sort == 2 || (n <= gs_depth_buckets_max_n() && frame_id > dsort_classic_until));
     }
     // ---- small frames (gs_bin_small.hip): the whole of gs_bin in one launch.  Same predicate in gs_preprocess (which then folds no key
     // range: nothing is sorted globally) and in gs_bin.  bin_path 0 only (3 = the two-level path whatever the size; tests, A/B)
-    bool small_bin = false;                  // the frame being built was binned by the small path
-    bool perm_pending = false;               // ... and its depth order (renderer.sortIdxs) has not been asked for yet
-    bool g2d_clean = false;                  // ... and its kernel cleared the gradient rows: the frame's first composite backward needs no fill
+    bool g2d_clean = false;                  // the small path's kernel cleared the gradient rows: the frame's first composite backward needs no fill
     bool small_bin_possible() const {
         if (cfg.bin_path != 0 || cfg.depth_sort != 0 || cfg.list_cap == 2 || cfg.slab_fractions[0] > 0.0f) return false;
         if (cfg.debug_flags & (GS_DEBUG_WIDE_CURSORS | GS_DEBUG_SUPER8 | GS_DEBUG_SUPER16 | GS_DEBUG_TINY_CAPS)) return false;
@@ -191,8 +219,6 @@ struct gs_ctx {
     float *bound_image = nullptr, *bound_trans = nullptr;   // gs_bind_outputs: caller-owned device buffers the forward writes directly
     float *img() { return bound_image ? bound_image : image.as<float>(); }
     float *tr() { return bound_trans ? bound_trans : trans.as<float>(); }
-    int tile_bits = 0, gid_bits = 0, lo_bits = 0, hi_bits = 0;
-    bool fast_bin = false;
     double walked_ratio = -1.0;              // entries walked / instances of the last completed frame (-1: none yet)
     int64_t prev_n_inst = 0;
     bool prev_counters_valid = false;        // `counters` holds the walked count of a completed forward
@@ -282,6 +308,7 @@ inline int lpt_split_div(const gs_ctx *c) { return c->wave_slots * 4 / 5; }     
 // The side stream (order kernel beside the backward) costs four more runtime calls per frame: it pays when the composite kernels
 // are long, and costs when the frame is bound by the host's launch rate (config C2, together with the zero fill it once carried: + 9 %).
 inline bool use_side_stream(const gs_ctx *c) { return c->n >= 262144 || (c->cfg.debug_flags & GS_DEBUG_ALWAYS_ORDER); }
+inline uint32_t *key_range_of(const gs_ctx *c, int parity) { return c->key_range.as<uint32_t>() + (size_t)parity * gs_depth_range_parity_words(); }   // one frame parity's accumulators
 inline int order_index(const gs_ctx *c) { return c->view_slot >= 0 ? c->view_slot : GS_MAX_VIEW_SLOTS; }   // index into gs_ctx::slots of the frame being rendered
 
 // ---------------------------------------------------------------- across the translation units

@@ -89,8 +89,9 @@ typedef struct {
                                  2 + s: around stage s (gs_stage) only; 0: none */
     int32_t bin_path;         /* tile lists (same lists on every path, bit for bit): 0 (default) two-level binning -- lists per
                                  super-tile of 8 x 8 tiles from an LDS bitmap, tile lists as filtered copies -- and, for SMALL frames
-                                 (up to 16 384 gaussians, 1024 tiles, 4 M gaussian x tile pairs: BASELINE C1), the whole of gs_bin in two
-                                 launches: depth order + tile ranges inside one workgroup's LDS, lists by one workgroup per tile;
+                                 (up to 16 384 gaussians, 1024 tiles, 4 M gaussian x tile pairs: BASELINE C1), the whole of gs_bin in ONE
+                                 launch, one workgroup per tile that ranks the tile's gaussians by depth in up to 128 KB of dynamic LDS
+                                 (no global depth order: renderer.sortIdxs is computed on demand, gs_get_array(GS_ARR_SORT_IDXS));
                                  3: two-level whatever the size (tests, A/B); 2: radix sort of instances generated in-pass (32-bit
                                  words); 1: explicit 64-bit tile|id instances + two radix passes */
     int32_t rank_mode;        /* radix-sort stable ranks: 1 (default) = wave64 ballots (portable); 0 = one LDS atomic-add-return per
@@ -418,8 +419,9 @@ int gs_get_list_stats(gs_ctx *ctx, int64_t out[3]);
 int gs_get_tile_parts(gs_ctx *ctx);
 
 /* The path that built the last frame's tile lists (gs_config.bin_path says what was asked for): 0 two-level binning, 1 / 2 the radix
- * paths, 3 the small-frame path (gs_bin_small.hip: depth order and tile ranges in one workgroup, the lists by one workgroup per tile;
- * taken by bin_path 0 for up to 16 384 gaussians x 1024 tiles).  Same lists on every path.  Negative: error.  Call after gs_bin. */
+ * paths, 3 the small-frame path (gs_bin_small.hip: one launch, one workgroup per tile, up to 128 KB of dynamic LDS; no global depth
+ * order, sortIdxs on demand; taken by bin_path 0 for up to 16 384 gaussians x 1024 tiles x 4 M gaussian x tile pairs).  Same lists on
+ * every path.  Negative: error.  Call after gs_bin. */
 int gs_get_bin_path(gs_ctx *ctx);
 
 /* out = {walked_fwd, walked_bwd, evaluated_fwd, evaluated_bwd}: `evaluated` counts the walked entries that
