@@ -29,7 +29,7 @@ SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs
            "gs_comm_init", "gs_allreduce_grads", "gs_comm_destroy", "gs_color_grads_pack", "gs_sh_grads_from_views", "gs_grads_alloc", "gs_grads_read", "gs_num_gaussians", "gs_num_instances", "gs_get_array",
            "gs_get_stage_times", "gs_get_stage_stats", "gs_get_work_counters", "gs_get_work_counters_ex", "gs_debug_time_composite",
            "gs_debug_tile_clock", "gs_debug_clock_mhz", "gs_rank_probe_result", "gs_num_rounds", "gs_set_view_slot", "gs_num_coarse_instances",
-           "gs_get_list_stats", "gs_get_tile_parts", "gs_get_bin_path", "gs_debug_set_window", "gs_debug_tile_clock_rows",
+           "gs_get_list_stats", "gs_get_tile_parts", "gs_get_bin_path", "gs_debug_set_window", "gs_debug_tile_clock_rows", "gs_debug_tail_fill",
            "gs_adam_step", "gs_backward_adam")
 
 GS_ABI_VERSION = 3          # include/gsplat.h; load() refuses a library that reports another version
@@ -37,6 +37,7 @@ GS_DEBUG_WIDE_CURSORS = 1
 GS_DEBUG_ALWAYS_ORDER = 2     # launch orders + side stream also on small frames (tests)
 GS_DEBUG_SUPER16 = 8          # two-level binning: super-tiles of 16 x 16 tiles whatever the grid (tests)
 GS_DEBUG_SUPER8 = 16          # ... of 8 x 8 tiles whatever the grid
+GS_DEBUG_NO_TAIL_FILL = 32    # the frame's zero fills in line instead of at the end of the composite launches' grids (A/B runs, tests)
 GS_DEBUG_TINY_CAPS = 4        # capped lists with the minimum cap on every tile (tests: every busy tile extends its list in the composite kernel)
 GS_MAX_VIEW_SLOTS = 4096
 GS_ADAM_GROUPS = 6            # lr[0] means, [1] scales, [2] quaternions, [3] opacities, [4] SH band 0, [5] SH bands >= 1
@@ -472,6 +473,18 @@ class Context:
         out = np.zeros((rows, 15), np.uint64)
         self._chk(self.L.gs_debug_tile_clock(self.h, which, variant, C.c_void_p(out.ctypes.data)))
         return out
+
+    def tail_fill_blocks(self):
+        """(forward, backward): fill workgroups the last frame's composite launches carried at the end of their grids (0: the in-line form)"""
+        o = (C.c_int32 * 2)()
+        f = self.L.gs_debug_tail_fill                       # (bound here: an older library built for an A/B run loads without it)
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        self._chk(f(self.h, o))
+        return int(o[0]), int(o[1])
+
+    def tile_clock_rows(self) -> int:
+        """workgroups of the frame's composite launches as gs_debug_tile_clock records them (0: one wave per tile, no launch order)"""
+        return int(self.L.gs_debug_tile_clock_rows(self.h))
 
     def set_debug_window(self, start: int = 0, length: int = 0):
         """debug launches cover only order[start : start + length] of the frame's launch order (0, 0: all of it)"""

@@ -173,8 +173,12 @@ static int enqueue_forward_round(gs_ctx *c, int r) {
     p.bwd_segments = a.snap && (p.side || !p.order);                       // snapshots left, and (HEAVY) the backward takes the order they belong to
     if (a.snap) { a.bw_walked = c->tile_walked_b.as<uint32_t>(); a.bw_work = c->tile_work_b.as<uint32_t>(); }   // (its waves zero the segmented tiles' words)
     if (c->bin.n_rounds > 1) { a.tile_pos = c->tile_pos.as<uint32_t>(); a.tile_done = c->tile_done.as<uint8_t>(); a.tile_dead = c->tile_dead.as<unsigned long long>(); }
+    if (r == 0 && c->fwd_fills_g2d) {                                      // the zero fill of the gradient rows, at the end of this launch's grid (gs_forward)
+        a.fill_dst = c->g2d.p; a.fill_bytes = c->g2d_bytes(); a.fill_blocks = gs_composite_fill_blocks(a.fill_dst, a.fill_bytes);
+    }
     StageTimer t(c, GS_STAGE_COMPOSITE_FWD);                               // the kernel alone
     HIPCHK(c, gs_launch_composite_fwd(a, c->stream));
+    if (r == 0) c->fill_blocks_fwd = a.fill_blocks;
     return GS_OK;
 }
 
@@ -214,6 +218,17 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
     const uint32_t *order_split = nullptr, *const order = forward_order(c, &order_split);
     if (c->order_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_order, 0)); c->order_pending = false; }     // the order kernel in flight reads tile_work
     plan_frame(c, order, order_split, hist);
+    // The zero fill of the 2-D gradient rows (64 B per gaussian) rides at the END of the forward's grid (round 0): workgroups appended behind
+    // the tiles', which the dispatcher hands out last, into the launch's ragged end -- no fill command and no kernel boundary in front of the
+    // composite backward.  Plain stores: the backward's atomics must find the rows where the in-line fill leaves them.
+    // Why the rows may be cleared HERE: nothing reads a frame's g2d after the next gs_forward of the ctx.  Its readers are the composite
+    // backward and the per-gaussian kernels of gs_backward (both renderers), gs_color_grads_pack and gs_get_array(GS_ARR_GRAD2D); all of
+    // them ask for did_bwd or did_bwd_composite (GS_BWD_PARAMS_ONLY), which this call resets below (and gs_bin before it), and all of them
+    // run on c->stream, in front of this launch.  Only when the buffer stands as the coming backward will want it (same n, same mode:
+    // DevBuf never shrinks, so its ensure() will not move it) and is not clean already; a ctx's first frame, a ctx that only renders and a
+    // model that grew keep the fill command in backward_impl.
+    c->fwd_fills_g2d = c->tail_fill() && !c->g2d_clean && c->g2d.p && c->g2d.cap >= c->g2d_bytes() &&
+                       gs_composite_fill_blocks(c->g2d.p, c->g2d_bytes()) > 0;
     for (int r = 0; r < R; ++r) {
         if (r > 0) { if (int rc = bin_round(c, r)) return rc; }
         if (int rc = enqueue_forward_round(c, r)) return rc;
@@ -224,6 +239,7 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
             if (redo) { if (int rc = enqueue_forward_round(c, 0)) return rc; }     // the lists outgrew a buffer and were rebuilt: composite again, same plan
         }
     }
+    if (c->fwd_fills_g2d) c->g2d_clean = true;                             // (a forward enqueued again after settle_totals filled again: idempotent)
     if (vs) vs->walk_written(c->counters_grid);
     if (int rc = build_frame_order(c)) return rc;
     const hipMemcpyKind kind = mem == GS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
@@ -308,6 +324,15 @@ static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *gr
     a.dC = dC_dev;
     // the segments of a tile ADD to these words, which only the frame's forward zeroed: a second backward launch of the frame inflates them
     a.tile_walked = c->tile_walked_b.as<uint32_t>(); a.tile_work = c->tile_work_b.as<uint32_t>();
+    // An overwriting backward of the 3-D renderer, both phases in this call, no fused optimiser: the zeros of the SH gradient rows no pixel
+    // touched (63 % of the gaussians at C3, 90 % at C5; 192 B each at degree 3) depend on nothing -- the fill workgroups at the end of the
+    // composite backward's grid zero ALL of d_shs, and gs_sh_bwd_kernel then stores the live rows only.  Past the caches, like that kernel's
+    // own stores (GS_NT_STORES): the model's SH rows stay in the infinity cache for the next preprocess.  Split phases, GS_BWD_PARAMS_SH /
+    // _GEOM, the fused optimisers and accumulating views keep the kernel's own zeros.
+    const size_t shs_bytes = sizeof(float) * c->width[4] * (size_t)(c->n > 0 ? c->n : 0);            // 3K x n floats
+    const bool fill_shs = c->tail_fill() && !params_only && !composite_only && c->kind == 0 && (flags & GS_BWD_OVERWRITE) && sgd_scale == 0.0f &&
+                          !adam && !adam_mode && grads && gs_composite_fill_blocks(grads->d_shs, shs_bytes) > 0;
+    if (fill_shs) { a.fill_dst = grads->d_shs; a.fill_bytes = shs_bytes; a.fill_blocks = gs_composite_fill_blocks(a.fill_dst, a.fill_bytes); a.fill_nt = 1; }
     if (!params_only) {
         c->last_dC = dC_dev;
         // zero fill of the gradient rows (64 B per gaussian), in line: on a side stream beside the forward composite it cost more than
@@ -316,12 +341,14 @@ static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *gr
         // (a fill with streaming stores, which would spare the caches 64 B per gaussian, was measured: the atomics of the composite backward then
         // find their rows in memory instead of the cache, C3 + 1 %; profiles/r04t_ab_nontemporal.log)
         // (a small frame's gs_bin kernel has cleared them already: gs_bin_small.hip)
+        // (... and otherwise the fill workgroups of the frame's forward: gs_forward)
         if (!c->g2d_clean) HIPCHK(c, hipMemsetAsync(c->g2d.p, 0, (det ? sizeof(long long) : sizeof(float)) * GS_G2D_STRIDE * n1, c->stream));
         c->g2d_clean = false;
         {
             StageTimer t(c, GS_STAGE_COMPOSITE_BWD);                   // the kernel alone (what rocprof reports for it)
             HIPCHK(c, gs_launch_composite_bwd(a, c->stream));
         }
+        c->fill_blocks_bwd = a.fill_blocks;
         c->did_bwd_composite = true;
     }
     if (composite_only) {
@@ -352,6 +379,7 @@ static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *gr
     HIPCHK(c, c->dpc.ensure(sizeof(float) * 4 * n1));
     b.dpc = c->dpc.as<float>();
     b.overwrite = (flags & GS_BWD_OVERWRITE) ? 1 : 0;
+    b.shs_zeroed = fill_shs ? 1 : 0;
     b.sgd_scale = sgd_scale;
     b.d_means = grads->d_means; b.d_scales = grads->d_scales; b.d_quats = grads->d_quats;
     b.d_opac = grads->d_opacities; b.d_shs = grads->d_shs;

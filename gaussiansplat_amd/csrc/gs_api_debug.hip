@@ -233,6 +233,13 @@ int gs_debug_tile_clock(gs_ctx *c, int which, int variant, uint64_t *out) {
     return GS_OK;
 }
 
+int gs_debug_tail_fill(gs_ctx *c, int32_t blocks[2]) {
+    if (!c || !blocks) return GS_ERR_INVALID;
+    if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_debug_tail_fill: gs_forward first");
+    blocks[0] = c->fill_blocks_fwd; blocks[1] = c->did_bwd_composite ? c->fill_blocks_bwd : 0;
+    return GS_OK;
+}
+
 int gs_debug_tile_clock_rows(gs_ctx *c) {
     if (!c) return GS_ERR_INVALID;
     if (lpt_schedule(c)) return lpt_order_entries(c) + gs_seg_units(lpt_front(c));

@@ -325,7 +325,23 @@ struct GsCompositeArgs {
     const uint32_t *seg_hist;
     int seg_n;
     int clock_by_block;        // debug (tile_clock): records indexed by workgroup instead of by tile (launches with split tiles)
+    // tail fill: fill_blocks workgroups APPENDED behind every tile / segment workgroup of the launch store fill_bytes zero bytes at
+    // fill_dst (both multiples of 4) and return.  The dispatcher hands workgroups out in index order, so they get their wave slots only once
+    // every tile workgroup has been dispatched: in the launch's ragged end.  fill_blocks = 0: none; else it must be what gs_composite_fill_blocks
+    // says for (fill_dst, fill_bytes) -- the launch refuses anything else, and a fill on a debug-clock launch -- so a caller that asked for a
+    // fill and got hipSuccess knows it was carried.  fill_first is set by the launch (= the tile workgroups in front).
+    void *fill_dst;
+    unsigned long long fill_bytes;
+    int fill_blocks, fill_first;
+    int fill_nt;               // 1: the stores bypass the caches (rows nothing on the GPU reads again this frame)
 };
+#define GS_TAIL_FILL_BYTES 32768     // bytes one appended workgroup fills (a wave: 32 x 16 B per lane; 16 / 32 / 64 KB measured equal, profiles/HISTORY.md 5h.10)
+// the fill workgroups for `bytes` at dst; 0: not fillable this way (null, empty, or not in 4-byte words)
+inline int gs_composite_fill_blocks(const void *dst, unsigned long long bytes) {
+    if (!dst || bytes == 0 || ((uintptr_t)dst & 3) || (bytes & 3)) return 0;
+    const unsigned long long b = (bytes + GS_TAIL_FILL_BYTES - 1) / GS_TAIL_FILL_BYTES;
+    return b > (1u << 20) ? (1 << 20) : (int)b;                     // (a share then grows beyond GS_TAIL_FILL_BYTES: 32 GB and more)
+}
 // the written entries of capped lists, summed over the tiles: out[0] = sum ext[t].x
 hipError_t gs_launch_sum_listed(const uint2 *ext, int n, unsigned long long *out, hipStream_t s);
 // longest-first launch order of the tiles for a plain launch (gs_composite.hip: groups of 8 x 8 tiles dealt to the XCDs by work,
@@ -382,6 +398,8 @@ struct GsPreprocessBwdArgs {
     float *d_means, *d_scales, *d_quats, *d_opac, *d_shs;   // accumulate (+=) or overwrite; may be null
     float *dpc;           // scratch 4 x n: d L / d tps[1:3] through the colour
     int overwrite;        // 1: store instead of accumulate
+    int shs_zeroed;       // overwrite, both phases, no fused optimiser: d_shs holds zeros already (the composite backward's fill workgroups wrote
+                          // them): gs_sh_bwd_kernel stores the SH rows of the gaussians a pixel touched and leaves the others alone
     float sgd_scale;      // != 0 (accumulate mode only): target = fma(sgd_scale, gradient, target) -- with the parameter arrays as
                           // targets and sgd_scale = -lr this IS the SGD step, fused (gs_backward_sgd)
 };

@@ -104,6 +104,27 @@ __device__ __forceinline__ uint32_t strips_of_part(int nparts, int part) {
     return nparts == 4 ? (1u << part) : nparts == 2 ? (3u << (2 * part)) : 0xFu;
 }
 
+// An appended workgroup of the launch (GsCompositeArgs.fill_*; blockIdx >= fill_first): zero bits over its share of fill_dst, 16-byte stores
+// over the aligned middle, 4-byte stores over a head / tail that is not (the first fill workgroup does both).  No LDS, no barrier; the tile
+// workgroups in front keep their indices, hence their XCDs.
+__device__ __forceinline__ void tail_fill(void *dst, unsigned long long bytes, int fb, int nfb, int nt) {
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    char *p = static_cast<char *>(dst);
+    const int lane = (int)threadIdx.x;
+    const unsigned long long head0 = (16u - (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u, head = head0 < bytes ? head0 : bytes;
+    const unsigned long long n16 = (bytes - head) >> 4, tail = bytes - head - (n16 << 4);
+    if (fb == 0) {
+        if ((unsigned long long)lane * 4u < head) *reinterpret_cast<uint32_t *>(p + 4 * lane) = 0u;
+        if ((unsigned long long)lane * 4u < tail) *reinterpret_cast<uint32_t *>(p + head + (n16 << 4) + 4 * lane) = 0u;
+    }
+    const unsigned long long share = (n16 + (unsigned long long)nfb - 1u) / (unsigned long long)nfb, lo = (unsigned long long)fb * share;
+    const unsigned long long hi = lo + share < n16 ? lo + share : n16;
+    v4u *q = reinterpret_cast<v4u *>(p + head);
+    const v4u z = {0u, 0u, 0u, 0u};
+    if (nt) { for (unsigned long long i = lo + (unsigned)lane; i < hi; i += 64u) __builtin_nontemporal_store(z, q + i); }
+    else { for (unsigned long long i = lo + (unsigned)lane; i < hi; i += 64u) q[i] = z; }
+}
+
 __device__ __forceinline__ unsigned long long wave_hw_id() {
     // HW_REG_HW_ID (4): wave, simd, cu, sh, se ids; HW_REG_XCC_ID (20): the XCD
     const uint32_t hw = (uint32_t)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
@@ -645,6 +666,10 @@ template <bool EARLY, int MINW, bool CULL, bool CLK = false, bool SLAB = false, 
 __global__ __launch_bounds__(64, MINW) void composite_fwd_kernel(GsCompositeArgs a) {
     __shared__ float4 sp[CB * 3];
     __shared__ float syhi[CB];
+    if (a.fill_blocks > 0 && (int)blockIdx.x >= a.fill_first) {               // an appended workgroup: the launch's zero fill, nothing else
+        tail_fill(a.fill_dst, a.fill_bytes, (int)blockIdx.x - a.fill_first, a.fill_blocks, a.fill_nt);
+        return;
+    }
     const int ntiles = a.gx * a.gy;
     const float nbig = vgpr_const(-GS_BIG);
     int part, nparts;
@@ -973,6 +998,10 @@ __global__ __launch_bounds__(64, MINW) void composite_bwd_kernel(GsCompositeArgs
     __shared__ uint32_t sid[CB];
     __shared__ uint32_t sstrip[CB];
     __shared__ __attribute__((aligned(16))) float red[PAIR ? 2 * RED_FLOATS : RED_FLOATS];
+    if (a.fill_blocks > 0 && (int)blockIdx.x >= a.fill_first) {               // an appended workgroup: the launch's zero fill, nothing else
+        tail_fill(a.fill_dst, a.fill_bytes, (int)blockIdx.x - a.fill_first, a.fill_blocks, a.fill_nt);
+        return;
+    }
     const int ntiles = a.gx * a.gy;
     const float nbig = vgpr_const(-GS_BIG);
     int part = 0, nparts = 1, tile;
@@ -1267,12 +1296,19 @@ hipError_t gs_launch_clock_probe(unsigned long long *out, hipStream_t s) {
 
 // workgroups in front of the order's in a backward launch: list segments 1 .. GS_SEG_MAX - 1 of the tiles that may be split (composite_bwd_kernel)
 int gs_seg_units(int front) { return 8 * (front / 24) * (GS_SEG_MAX - 1); }
-static dim3 composite_grid(const GsCompositeArgs &a, int ntiles, bool bwd = false) {   // (tile_of_block computes the same length of one part)
+static int composite_tile_blocks(const GsCompositeArgs &a, int ntiles, bool bwd) {   // (tile_of_block computes the same length of one part)
     const int len = (a.tile_order && a.order_len > 0) ? a.order_len : ((ntiles + 7) / 8) * 8;
-    if (bwd && a.snap && a.seg_hist && a.t_min > 0.0f) return dim3((unsigned)(len * a.seg_n * (a.parts > 1 ? a.parts : 1)));   // small grid: segments x pixel parts per tile
-    return dim3((unsigned)(len * (a.parts > 1 ? a.parts : 1) + ((bwd && a.snap && a.t_min > 0.0f) ? gs_seg_units(a.front) : 0)));
+    if (bwd && a.snap && a.seg_hist && a.t_min > 0.0f) return len * a.seg_n * (a.parts > 1 ? a.parts : 1);   // small grid: segments x pixel parts per tile
+    return len * (a.parts > 1 ? a.parts : 1) + ((bwd && a.snap && a.t_min > 0.0f) ? gs_seg_units(a.front) : 0);
 }
-
+// ... and the fill workgroups of the launch (tail_fill) appended: every tile / segment workgroup keeps its index
+static dim3 composite_grid(const GsCompositeArgs &a, int ntiles, bool bwd = false) {
+    return dim3((unsigned)(composite_tile_blocks(a, ntiles, bwd) + (a.fill_blocks > 0 ? a.fill_blocks : 0)));
+}
+// a fill descriptor the launch cannot carry as asked is an error, never dropped: its caller has told others that the zeros are there
+static bool fill_ok(const GsCompositeArgs &a) {
+    return a.fill_blocks == 0 || (a.fill_blocks == gs_composite_fill_blocks(a.fill_dst, a.fill_bytes) && !a.tile_clock);
+}
 int gs_composite_grid_blocks(const GsCompositeArgs &a, int bwd) { return (int)composite_grid(a, a.gx * a.gy, bwd != 0).x; }   // (debug clocks by workgroup: rows of the record)
 
 // variant (debug launches, gs_debug_time_composite / gs_debug_tile_clock): tens digit 1 = tile order instead of the frame's launch order
@@ -1282,9 +1318,17 @@ static GsCompositeArgs apply_sched_variant(const GsCompositeArgs &a0) {
     return a;
 }
 
+// the arguments as launched: schedule variant applied, the fill workgroups placed behind the others
+static GsCompositeArgs launch_args(const GsCompositeArgs &a0, bool bwd) {
+    GsCompositeArgs a = apply_sched_variant(a0);
+    a.fill_first = composite_tile_blocks(a, a.gx * a.gy, bwd);
+    return a;
+}
+
 hipError_t gs_launch_composite_fwd(const GsCompositeArgs &a0, hipStream_t s) {
-    const GsCompositeArgs a = apply_sched_variant(a0);
+    const GsCompositeArgs a = launch_args(a0, false);
     const int ntiles = a.gx * a.gy;
+    if (!fill_ok(a) || (ntiles <= 0 && a.fill_blocks)) return hipErrorInvalidValue;
     if (ntiles <= 0) return hipSuccess;
     const dim3 grid = composite_grid(a, ntiles), block(64);
     const bool early = a.t_min > 0.0f;
@@ -1320,8 +1364,9 @@ hipError_t gs_launch_composite_fwd(const GsCompositeArgs &a0, hipStream_t s) {
 }
 
 hipError_t gs_launch_composite_bwd(const GsCompositeArgs &a0, hipStream_t s) {
-    const GsCompositeArgs a = apply_sched_variant(a0);
+    const GsCompositeArgs a = launch_args(a0, true);
     const int ntiles = a.gx * a.gy;
+    if (!fill_ok(a) || (ntiles <= 0 && a.fill_blocks)) return hipErrorInvalidValue;
     if (ntiles <= 0) return hipSuccess;
     const bool early = a.t_min > 0.0f;
     const dim3 grid = composite_grid(a, ntiles, true), block(64);

@@ -210,7 +210,12 @@ struct gs_ctx {
     }
     // ---- small frames (gs_bin_small.hip): the whole of gs_bin in one launch.  Same predicate in gs_preprocess (which then folds no key
     // range: nothing is sorted globally) and in gs_bin.  bin_path 0 only (3 = the two-level path whatever the size; tests, A/B)
-    bool g2d_clean = false;                  // the small path's kernel cleared the gradient rows: the frame's first composite backward needs no fill
+    bool g2d_clean = false;                  // the gradient rows are cleared (enqueued: by the small path's kernel, or by the fill workgroups of the frame's
+                                             // forward): the frame's first composite backward needs no fill
+    bool fwd_fills_g2d = false;              // this frame's forward (round 0) carries the zero fill of g2d: decided once, in gs_forward
+    bool tail_fill() const { return !(cfg.debug_flags & GS_DEBUG_NO_TAIL_FILL) && (int64_t)gx * gy > 0; }   // the composite launches may carry zero fills
+    int fill_blocks_fwd = 0, fill_blocks_bwd = 0;   // fill workgroups the frame's last forward (round 0) / composite backward launch carried (gs_debug_tail_fill)
+    size_t g2d_bytes() const { return (cfg.deterministic ? sizeof(long long) : sizeof(float)) * GS_G2D_STRIDE * (n ? (size_t)n : 1); }
     bool small_bin_possible() const {
         if (cfg.bin_path != 0 || cfg.depth_sort != 0 || cfg.list_cap == 2 || cfg.slab_fractions[0] > 0.0f) return false;
         if (cfg.debug_flags & (GS_DEBUG_WIDE_CURSORS | GS_DEBUG_SUPER8 | GS_DEBUG_SUPER16 | GS_DEBUG_TINY_CAPS)) return false;

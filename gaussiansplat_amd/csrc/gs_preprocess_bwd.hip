@@ -75,7 +75,10 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
     // Untouched gaussians.  With the transmittance early-out most gaussians of a dense view are never composited (C3: 63 %, C5: 90 %,
     // tools/touched_rows.py): their colour gradient d rgb is exactly zero, hence d shs = basis * 0 and the colour -> direction term are
     // exactly zero.  When ACCUMULATING (views after the first of a batch) their d_shs rows are neither read nor written: C4 on one GPU
-    // 8.85 -> 8.71 ms per 8 views, same box (profiles/r04j_ab_untouched_rows.log).  When OVERWRITING the zeros have to be written.
+    // 8.85 -> 8.71 ms per 8 views, same box (profiles/r04j_ab_untouched_rows.log).  When OVERWRITING the zeros have to be written -- by
+    // this kernel, or (a.shs_zeroed) by the fill workgroups at the end of the composite backward's launch, which zeroed ALL of d_shs: then
+    // only the live rows are stored here.  Either way an untouched row ends as + 0.0 in every float (the store loop writes 0.0f for it,
+    // not the tile's basis * 0, whose sign depends on the basis).
     constexpr bool SKIP = !OVERWRITE;
     __shared__ uint8_t srow_live[256];
     const int64_t gb = (int64_t)blockIdx.x * blockDim.x;
@@ -130,6 +133,7 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
 #pragma unroll
             for (int c = 0; c < 3; ++c) sh[c + 3 * k] = bs[k] * grgb[c];   // the tile carries d L / d sh (stored coalesced below)
         }
+        if (OVERWRITE && ADAM == 0) srow_live[threadIdx.x] = live ? 1 : 0;     // (the barrier below stands between this and its readers)
         float ddir[3] = {0.0f, 0.0f, 0.0f};
         if (live) {
             // d L / d dir through the colour needs the coefficients: those of THIS gaussian, read by its own thread as twelve 16-byte
@@ -230,9 +234,11 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
             float4 *dst = reinterpret_cast<float4 *>(a.d_shs + gb * 3 * K);
             for (int i4 = threadIdx.x; i4 < nb * (3 * K / 4); i4 += blockDim.x) {
                 const int row = (i4 * 4) / (3 * K);
-                if (!OVERWRITE && !srow_live[row]) continue;             // + 0 (or a step of 0): the row stays as it is
+                const bool lv = srow_live[row] != 0;
+                if ((!OVERWRITE || a.shs_zeroed) && !lv) continue;       // + 0 (or a step of 0): the row stays as it is; overwriting: it holds its zeros already
                 const float *t = tile + row * ROW + (i4 * 4) % (3 * K);
                 float4 v = make_float4(t[0], t[1], t[2], t[3]);
+                if (OVERWRITE && !lv) v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (!OVERWRITE) {
                     const float4 o = dst[i4];
                     if (a.sgd_scale != 0.0f) { v.x = fmaf(a.sgd_scale, v.x, o.x); v.y = fmaf(a.sgd_scale, v.y, o.y); v.z = fmaf(a.sgd_scale, v.z, o.z); v.w = fmaf(a.sgd_scale, v.w, o.w); }
@@ -250,8 +256,9 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
             }
         } else {
             for (int idx = threadIdx.x; idx < nb * 3 * K; idx += blockDim.x) {
-                if (!OVERWRITE && !srow_live[idx / (3 * K)]) continue;
-                const float v = tile[(idx / (3 * K)) * ROW + idx % (3 * K)];
+                const bool lv = srow_live[idx / (3 * K)] != 0;
+                if ((!OVERWRITE || a.shs_zeroed) && !lv) continue;
+                const float v = (OVERWRITE && !lv) ? 0.0f : tile[(idx / (3 * K)) * ROW + idx % (3 * K)];
                 if (OVERWRITE) a.d_shs[gb * 3 * K + idx] = v;
                 else if (a.sgd_scale != 0.0f) a.d_shs[gb * 3 * K + idx] = fmaf(a.sgd_scale, v, a.d_shs[gb * 3 * K + idx]);
                 else a.d_shs[gb * 3 * K + idx] += v;

@@ -175,6 +175,9 @@ typedef struct {
 #define GS_DEBUG_SUPER8 16
 #define GS_DEBUG_TINY_CAPS 4       /* capped lists with the minimum cap on every tile, history or not: every tile that walks more than its
                                       first segment extends its list in the composite kernel (tests)                               */
+#define GS_DEBUG_NO_TAIL_FILL 32   /* no zero fills at the end of the composite launches' grids: the 2-D gradient rows are cleared by a fill command in
+                                      front of the composite backward and the per-gaussian kernel of an overwriting backward writes the zeros of the
+                                      untouched SH rows itself -- the in-line forms; same results bit for bit (A/B runs, tests)         */
 
 typedef struct gs_ctx gs_ctx;
 
@@ -446,6 +449,9 @@ int gs_debug_tile_clock(gs_ctx *ctx, int which, int variant, uint64_t *out);
  * it, heavy tiles split into two or four waves (the parts of a split tile would overwrite each other's per-tile record): out then
  * holds gs_debug_tile_clock_rows(ctx) rows of 15 words, rows of workgroups without a tile all zero.  0: the frame has no launch order. */
 int gs_debug_tile_clock_rows(gs_ctx *ctx);
+/* Fill workgroups the composite launches of the last frame carried at the end of their grids: blocks[0] the forward (zero fill of the 2-D
+ * gradient rows), blocks[1] the composite backward (zeros of d_shs; 0 before a backward of the frame).  0: the in-line form ran (tests). */
+int gs_debug_tail_fill(gs_ctx *ctx, int32_t blocks[2]);
 
 /* Profiling hook: the shader clock (MHz) the chip runs at right now, from one wave that counts s_memtime cycles over 20 us of
  * s_memrealtime on the ctx stream (waits for the stream).  tools/frames_probe.py samples it between frames. */

@@ -311,6 +311,11 @@ function hip_debugTileClock(r::HipRenderer, which::Integer, variant::Integer, nt
     return out
 end
 hip_debugTileClockRows(r::HipRenderer) = ccall((:gs_debug_tile_clock_rows, libgs), Cint, (Ptr{Cvoid},), r.ctx)
+function hip_debugTailFill(r::HipRenderer)          # (forward, backward): fill workgroups the last frame's composite launches carried
+    b = zeros(Int32, 2)
+    check(r, ccall((:gs_debug_tail_fill, libgs), Cint, (Ptr{Cvoid}, Ptr{Int32}), r.ctx, b))
+    return Int(b[1]), Int(b[2])
+end
 function hip_clockMHz(r::HipRenderer)
     mhz = Ref{Cfloat}(0f0)
     check(r, ccall((:gs_debug_clock_mhz, libgs), Cint, (Ptr{Cvoid}, Ref{Cfloat}), r.ctx, mhz))
