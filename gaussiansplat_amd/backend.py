@@ -26,7 +26,7 @@ STAGES = ("preprocess", "depth_sort", "count_scan", "emit", "tile_sort", "ranges
 SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs_last_error", "gs_set_stream",
            "gs_synchronize", "gs_set_model", "gs_set_model_2d", "gs_set_image_size", "gs_set_camera", "gs_preprocess", "gs_bin", "gs_bind_outputs", "gs_forward", "gs_backward_sgd",
            "gs_backward", "gs_backward_ex", "gs_reset_grads", "gs_loss_l1_dssim", "gs_sgd_step", "gs_comm_unique_id",
-           "gs_comm_init", "gs_allreduce_grads", "gs_comm_destroy", "gs_color_grads_pack", "gs_sh_grads_from_views", "gs_grads_alloc", "gs_grads_read", "gs_num_gaussians", "gs_num_instances", "gs_get_array",
+           "gs_comm_init", "gs_allreduce_grads", "gs_comm_destroy", "gs_color_grads_pack", "gs_sh_grads_from_views", "gs_color_rows_pack", "gs_sh_grads_from_touched", "gs_grads_alloc", "gs_grads_read", "gs_num_gaussians", "gs_num_instances", "gs_get_array",
            "gs_get_stage_times", "gs_get_stage_stats", "gs_get_work_counters", "gs_get_work_counters_ex", "gs_debug_time_composite",
            "gs_debug_tile_clock", "gs_debug_clock_mhz", "gs_rank_probe_result", "gs_num_rounds", "gs_set_view_slot", "gs_num_coarse_instances",
            "gs_get_list_stats", "gs_get_tile_parts", "gs_get_bin_path", "gs_debug_set_window", "gs_debug_tile_clock_rows", "gs_debug_tail_fill",
@@ -43,6 +43,7 @@ GS_MAX_VIEW_SLOTS = 4096
 GS_ADAM_GROUPS = 6            # lr[0] means, [1] scales, [2] quaternions, [3] opacities, [4] SH band 0, [5] SH bands >= 1
 GS_ADAM_SELECTIVE = 1         # step only the gaussians with a non-zero gradient float ("selective Adam")
 GS_ERR_INVALID, GS_ERR_UNSUPPORTED = -1, -5
+TOUCHED_CHUNK = 256           # gaussians per workgroup of the touched-rows pack (GS_TOUCHED_CHUNK in csrc/gs_common.h; tests pick their sizes around it)
 
 
 class GsConfig(C.Structure):
@@ -122,6 +123,8 @@ def load():
     L.gs_set_image_size.argtypes = [vp, C.c_int32, C.c_int32]
     L.gs_color_grads_pack.argtypes = [vp, vp]
     L.gs_sh_grads_from_views.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int]
+    L.gs_color_rows_pack.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
+    L.gs_sh_grads_from_touched.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int64, vp, C.c_int]
     L.gs_get_work_counters_ex.argtypes = [vp, C.POINTER(C.c_int64)]
     L.gs_debug_time_composite.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.gs_debug_tile_clock.argtypes = [vp, C.c_int, C.c_int, vp]
@@ -301,6 +304,20 @@ class Context:
         assert cr.ndim == 2 and cr.shape[1] == 38
         self._chk(self.L.gs_sh_grads_from_views(self.h, cr.shape[0], C.c_void_p(cr.ctypes.data), C.c_void_p(int(drgb_ptr)),
                                                 C.c_void_p(int(d_shs_ptr)), 1 if overwrite else 0))
+
+    def color_rows_pack(self, drgb_ptr: "int | None", n: int, bits_ptr: int, rows_ptr: int, count_ptr: int):
+        """gs_color_rows_pack: one view as a bitmap of touched gaussians (int32 words), their d rgb rows in gaussian order and an
+        int64 count, all device buffers; drgb_ptr None / 0 = the ctx's own sums of the last backward (n = num_gaussians).  No sync."""
+        self._chk(self.L.gs_color_rows_pack(self.h, C.c_void_p(int(drgb_ptr or 0)), int(n), C.c_void_p(int(bits_ptr)),
+                                            C.c_void_p(int(rows_ptr)), C.c_void_p(int(count_ptr))))
+
+    def sh_grads_from_touched(self, cam_records: np.ndarray, bits_ptr: int, rows_ptr: int, rows_cap: int, d_shs_ptr: int,
+                              overwrite: bool = True):
+        """cam_records as sh_grads_from_views; bits [nviews, ceil(n / 32)] int32 and rows [nviews, rows_cap, 3] float32, device."""
+        cr = np.ascontiguousarray(cam_records, np.float32)
+        assert cr.ndim == 2 and cr.shape[1] == 38
+        self._chk(self.L.gs_sh_grads_from_touched(self.h, cr.shape[0], C.c_void_p(cr.ctypes.data), C.c_void_p(int(bits_ptr)),
+                                                  C.c_void_p(int(rows_ptr)), int(rows_cap), C.c_void_p(int(d_shs_ptr)), 1 if overwrite else 0))
 
     def backward_sgd(self, dC_ptr: int, lr: float):
         """gs_backward_sgd: backward and `param .-= lr * grad` (train.jl:42-46) in one pass on the resident model; dC on the device."""

@@ -30,6 +30,8 @@ SOURCES = {
     "gs_preprocess.hip": ["-ffp-contract=off"],
     "gs_preprocess2d.hip": ["-ffp-contract=off"],
     "gs_preprocess_bwd.hip": [],
+    # same flags as gs_preprocess_bwd.hip: the two kernels that rebuild SH gradients from views share one body (gs_sh_views_body.inc) and must round alike
+    "gs_touched.hip": [],
     "gs_sort.hip": [],
     "gs_bin2.hip": [],
     "gs_bin3.hip": [],
@@ -45,6 +47,7 @@ SOURCES = {
     "gs_api_bin.hip": [],
     "gs_api_composite.hip": [],
     "gs_api_comm.hip": [],
+    "gs_api_touched.hip": [],
     "gs_api_debug.hip": [],
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
@@ -58,7 +61,7 @@ def _hipcc() -> str:
 
 
 def _deps() -> float:
-    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
     hdrs.append(os.path.join(HERE, "..", "include", "gsplat.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 

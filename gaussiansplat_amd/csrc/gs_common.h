@@ -412,6 +412,16 @@ hipError_t gs_launch_preprocess_bwd(const GsPreprocessBwdArgs &a, const GsCamera
 hipError_t gs_launch_pack_drgb(const float *g2d, const long long *g2d_fixed, float *out, int64_t n, hipStream_t s);
 hipError_t gs_launch_sh_from_views(int64_t n, int sh_degree, const float *means, int nviews, const float *cams, const float *drgb,
                                    float *d_shs, int overwrite, hipStream_t s);
+// touched-rows exchange (gs_touched.hip): a view as a bitmap plus the colour-gradient rows of the gaussians it touched.  chunk_cnt /
+// chunk_off: scratch of gs_touched_chunks(n) words per view (the pack has one view).  Source of the pack: `dense` [n][3], or
+// (dense null) the composite backward's sums g2d / g2d_fixed as gs_launch_pack_drgb takes them.
+#define GS_TOUCHED_CHUNK 256
+inline int64_t gs_touched_chunks(int64_t n) { return (n + GS_TOUCHED_CHUNK - 1) / GS_TOUCHED_CHUNK; }
+hipError_t gs_launch_touched_pack(const float *dense, const float *g2d, const long long *g2d_fixed, int64_t n, int32_t *bits, float *rows,
+                                  int64_t *count, uint32_t *chunk_cnt, int64_t *chunk_off, hipStream_t s);
+hipError_t gs_launch_sh_from_touched(int64_t n, int sh_degree, const float *means, int nviews, const float *cams, const int32_t *bits,
+                                     const float *rows, int64_t rows_cap, uint32_t *chunk_cnt, int64_t *chunk_off, const float *zero3,
+                                     float *d_shs, int overwrite, hipStream_t s);   // zero3: three +0 floats in device memory
 
 // The composite backward accumulates, per gaussian, the colour gradient and the RAW moments of dd = dL/d(log alpha)
 // about the splat's 2-D mean: row = [dr dg db | S0 Sx Sy Sxx Sxy - Syy].  With the view's sig and conic M (column

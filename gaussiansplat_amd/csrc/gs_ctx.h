@@ -5,6 +5,7 @@
 //   gs_api_composite.hip  gs_forward / gs_backward: the frame's plan (plan_frame), the one builder of the composite launches' arguments
 //                         (composite_args), the launch orders of the view slots
 //   gs_api_comm.hip       RCCL below the boundary (gs_comm_*, gs_allreduce_grads)
+//   gs_api_touched.hip    the touched-rows colour exchange (gs_color_rows_pack, gs_sh_grads_from_touched)
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
 #pragma once
 #include "../../include/gsplat.h"
@@ -232,6 +233,7 @@ struct gs_ctx {
     DevBuf grads_flat;                       // gs_grads_alloc
     DevBuf dpc;                              // 4 x n scratch between the two backward kernels
     DevBuf loss_maps, loss_acc, loss_in[2], loss_dc, view_cams;
+    DevBuf touched_cnt, touched_off, touched_zero;   // touched-rows exchange: per (view, chunk) counts and exclusive row offsets; three +0 floats (gs_api_touched.hip)
     ncclComm_t comm = nullptr;
     int comm_ranks = 0;
 };

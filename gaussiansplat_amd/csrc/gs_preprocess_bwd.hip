@@ -24,18 +24,12 @@
 // `overwrite` stores instead of accumulating: used for the first backward after resetGrads, so
 // the reset needs no 4(11+3K)-byte/gaussian zero fill and this pass no read of the old gradients.
 #include "gs_common.h"
+#include "gs_sh_views.h"      // SH_C0 / SH_C1 / bC2 / bC3
 #include <stdlib.h>
 
 #ifndef GS_NT_STORES
 #define GS_NT_STORES 2               // overwrite-mode gradient stores bypass the caches: 1 the SH gradients, 2 the geometry chain's too (0: A/B builds)
 #endif
-#define SH_C0 0.28209479177387814f
-#define SH_C1 0.48860251190291990f
-__constant__ float bC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                             -1.0925484305920792f, 0.5462742152960396f};
-__constant__ float bC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
-                             -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
-
 // 2-D gradient row of gaussian g: float atomics buffer, or the deterministic fixed-point buffer
 __device__ __forceinline__ void load_g2(const GsPreprocessBwdArgs &a, int64_t g, float (&o)[10]) {
     if (a.g2d_fixed) {
@@ -294,57 +288,17 @@ __global__ __launch_bounds__(256) void gs_pack_drgb_kernel(const float *__restri
 }
 
 // cams: nviews records of 38 floats {T[16], P[16], eye[3], lookAt[3]}; drgb: [nviews][3n]; the direction and the
-// basis are computed exactly as in gs_sh_bwd_kernel.
+// basis are computed exactly as in gs_sh_bwd_kernel.  The body (gs_sh_views_body.inc) is shared with the kernel that reads the
+// views' colour gradients from bitmaps and compacted rows (gs_touched.hip).
 template <int DEG, bool OVERWRITE>
 __global__ __launch_bounds__(256) void gs_sh_from_views_kernel(int64_t n, const float *__restrict__ means, int nviews,
                                                                 const float *__restrict__ cams, const float *__restrict__ drgb,
                                                                 float *__restrict__ d_shs) {
-    constexpr int K = (DEG + 1) * (DEG + 1);
-    constexpr int ROW = 3 * K + 1;
-    extern __shared__ __attribute__((aligned(16))) float tile[];       // [256][ROW] accumulators
-    const int64_t gb = (int64_t)blockIdx.x * blockDim.x;
-    const int nb = (int)min((int64_t)blockDim.x, n - gb);
-    const int64_t g = gb + threadIdx.x;
-    float *acc = tile + threadIdx.x * ROW;
-#pragma unroll
-    for (int i = 0; i < 3 * K; ++i) acc[i] = 0.0f;
-    if (g < n) {
-        const float m1 = means[3 * g], m2 = means[3 * g + 1], m3 = means[3 * g + 2];
-        for (int v = 0; v < nviews; ++v) {
-            const float *T = cams + 38 * v, *P = T + 16, *eye = T + 32, *lookAt = T + 35;
-            float t[4], p[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) t[i] = T[i] * m1 + T[i + 4] * m2 + T[i + 8] * m3 + T[i + 12];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) p[i] = P[i] * t[0] + P[i + 4] * t[1] + P[i + 8] * t[2] + P[i + 12] * t[3];
-            const float v0 = p[0] - (lookAt[0] - eye[0]);
-            const float v1 = p[1] - (lookAt[1] - eye[1]);
-            const float v2 = p[2] - (lookAt[2] - eye[2]);
-            const float inrm = rsqrtf(v0 * v0 + v1 * v1 + v2 * v2);
-            const float X = v0 * inrm, Y = v1 * inrm, Z = v2 * inrm;
-            float bs[K];
-            bs[0] = SH_C0;
-            if constexpr (DEG >= 1) { bs[1] = -Y * SH_C1; bs[2] = Z * SH_C1; bs[3] = -X * SH_C1; }
-            if constexpr (DEG >= 2) {
-                const float xx = X * X, yy = Y * Y, zz = Z * Z, xy = X * Y, yz = Y * Z, xz = X * Z;
-                bs[4] = bC2[0] * xy; bs[5] = bC2[1] * yz; bs[6] = bC2[2] * (2 * zz - xx - yy); bs[7] = bC2[3] * xz; bs[8] = bC2[4] * (xx - yy);
-                if constexpr (DEG >= 3) {
-                    bs[9] = bC3[0] * Y * (3 * xx - yy); bs[10] = bC3[1] * xy * Z; bs[11] = bC3[2] * Y * (4 * zz - xx - yy);
-                    bs[12] = bC3[3] * Z * (2 * zz - 3 * xx - 3 * yy); bs[13] = bC3[4] * X * (4 * zz - xx - yy);
-                    bs[14] = bC3[5] * Z * (xx - yy); bs[15] = bC3[6] * X * (xx - 3 * yy);
-                }
-            }
-            const float *gr = drgb + (size_t)v * 3 * (size_t)n + 3 * g;
-            const float g0 = gr[0], g1 = gr[1], g2 = gr[2];
-#pragma unroll
-            for (int k = 0; k < K; ++k) { acc[3 * k] += bs[k] * g0; acc[3 * k + 1] += bs[k] * g1; acc[3 * k + 2] += bs[k] * g2; }
-        }
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < nb * 3 * K; idx += blockDim.x) {     // coalesced rows
-        const float v = tile[(idx / (3 * K)) * ROW + idx % (3 * K)];
-        if (OVERWRITE) d_shs[gb * 3 * K + idx] = v; else d_shs[gb * 3 * K + idx] += v;
-    }
+#define GS_SH_VIEWS_BEGIN
+#define GS_SH_VIEWS_DRGB const float *gr = drgb + (size_t)v * 3 * (size_t)n + 3 * g; const float g0 = gr[0], g1 = gr[1], g2 = gr[2];
+#include "gs_sh_views_body.inc"
+#undef GS_SH_VIEWS_DRGB
+#undef GS_SH_VIEWS_BEGIN
 }
 
 hipError_t gs_launch_pack_drgb(const float *g2d, const long long *g2d_fixed, float *out, int64_t n, hipStream_t s) {

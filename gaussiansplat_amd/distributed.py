@@ -23,8 +23,11 @@ gaussians.  Sums over views are taken in view order, so the result is also repro
 as the rows of the gaussians the view TOUCHED only: a view's composite adjoint leaves d rgb = 0 for every gaussian no pixel
 evaluated (63 % of them at C3, 90 % at C5: tools/touched_rows.py), so a view travels as a bitmap of N bits plus 12 bytes per
 touched gaussian -- 0.125 + 4.4 MB instead of 12 MB at C3 -- padded to the largest count among the views (two small
-all-gathers: counts, then bitmaps and rows).  The receiver scatters the rows back and rebuilds the SH gradients as "factored"
-does, so the result is the same, bit for bit.
+all-gathers: counts, then bitmaps and rows).  The receiver rebuilds the SH gradients as "factored" does, so the result is the same,
+bit for bit.  With the HIP renderer the whole data path is device code: gs_color_rows_pack packs a view straight from the ctx's sums of
+its backward (no dense slot), gs_sh_grads_from_touched rebuilds the SH gradients straight from the gathered bitmaps and rows (no dense
+[views, N, 3] array); the host reads ONE number per step, the largest count, to size the gather of the rows.  A renderer without
+these methods (the CPU renderer of the gloo tests) goes through the torch functions pack_touched_rows / unpack_touched_rows below.
 """
 from __future__ import annotations
 
@@ -66,6 +69,9 @@ def multi_view_step(r: ViewRenderer, cameras: Sequence, dCs: Sequence, group=Non
     per-gaussian chains stay in view order (event-chained), so the sums are the same bits as one view after the other.
     sync = "factored": see the module docstring (needs a renderer with render_view_factored / color_slots / sh_from_views, and
     the same number of views on every rank).
+    sync = "touched": "factored" with a view's colour gradients sent as a bitmap plus the rows of the gaussians it touched.  A renderer
+    with render_view_touched / touched_buffers / sh_from_touched (the HIP renderer) packs and rebuilds on the device, also at world
+    size 1 (no gathers, the buffers used in place); any other renderer goes through the torch functions below.
     exchange = False (measurement only, bench.py's compute_ms): this rank's share of the views exactly as in a real step -- the same
     kernels on the same streams -- but no collective is posted; the buffer then holds the rank's partial sums."""
     import torch
@@ -118,6 +124,8 @@ def multi_view_step(r: ViewRenderer, cameras: Sequence, dCs: Sequence, group=Non
         raise ValueError(sync)
     if len(cameras) % world:
         raise ValueError("factored / touched sync needs the same number of views on every rank")
+    if sync == "touched" and all(hasattr(r, m) for m in ("render_view_touched", "touched_buffers", "sh_from_touched")):
+        return _touched_step_device(r, cameras, dCs, mine, world, group, dist)
     slots = r.color_slots(len(mine))                                        # [len(mine), n, 3] on the renderer's device
     for i, v in enumerate(mine):
         r.render_view_factored(cameras[v], dCs[v], slots[i])                # geometry grads accumulate, d rgb -> slot i
@@ -136,10 +144,37 @@ def multi_view_step(r: ViewRenderer, cameras: Sequence, dCs: Sequence, group=Non
     return r.flat
 
 
+def _touched_step_device(r, cameras, dCs, mine, world, group, dist):
+    """sync = "touched" with pack and rebuild on the device: per view three launches (gs_color_rows_pack), per step one geometry
+    all-reduce, the all-gather of the counts, ONE host read (the largest count), the all-gathers of the bitmaps and of the rows
+    padded to that count, and the rebuild (gs_sh_grads_from_touched).  What lies behind a view's count in its rows is never read, so
+    `cap` rows per view are sent as they are, without looking at the view's own count on the host."""
+    import torch
+    bits, rows, counts = r.touched_buffers(len(mine))                       # [V, ceil(N / 32)] int32, [V, N, 3] float32, [V] int64
+    for i, v in enumerate(mine):
+        r.render_view_touched(cameras[v], dCs[v], i)                        # geometry grads accumulate; view i -> bits[i], rows[i], counts[i]
+    if world == 1:
+        r.sh_from_touched(list(cameras), bits, rows, rows.shape[1])         # in place: every view keeps its N rows of room
+        return r.flat
+    V = len(mine)
+    dist.all_reduce(r.flat[:r.geometry_floats], op=dist.ReduceOp.SUM, group=group)     # 11 N floats
+    all_counts = torch.zeros(world * V, dtype=torch.int64, device=counts.device)
+    dist.all_gather_into_tensor(all_counts, counts, group=group)
+    cap = max(int(all_counts.max()), 1)                                     # the step's one host read
+    send = rows[:, :cap].contiguous()
+    all_bits = torch.empty((world * V, bits.shape[1]), dtype=torch.int32, device=bits.device)
+    all_rows = torch.empty((world * V, cap, 3), dtype=rows.dtype, device=rows.device)
+    dist.all_gather_into_tensor(all_bits.reshape(-1), bits.reshape(-1), group=group)   # N / 8 bytes per view
+    dist.all_gather_into_tensor(all_rows.reshape(-1), send.reshape(-1), group=group)   # 12 bytes per touched gaussian (padded)
+    r.sh_from_touched(list(cameras), all_bits, all_rows, cap)               # overwrites the Δshs part of flat
+    return r.flat
+
+
 def pack_touched_rows(slots):
     """slots [views, N, 3] -> (bits [views, ceil(N / 32)] int32: bit g % 32 of word g / 32 set when view v left gaussian g a non-zero
     colour gradient; counts [views] int64; rows: list of [count_v, 3] tensors, the touched rows in gaussian order).  Host-side
-    torch plumbing (boolean indexing synchronises); a device kernel would pack in one pass -- not built: no N > 1 hardware to time it on."""
+    torch plumbing (boolean indexing synchronises), for renderers without device code; the HIP renderer packs on the device
+    (gs_color_rows_pack, HipViewRenderer.render_view_touched), and these functions are the reference its tests compare against."""
     import torch
     V, N, _ = slots.shape
     touched = (slots != 0).any(dim=2)                                       # an exactly-zero row adds nothing to the SH sums either way
@@ -329,6 +364,41 @@ class HipViewRenderer:
         R.forward(self.r, tps)
         R.backward(self.r, dC, skip_shs=True)
         self.r.ctx.color_grads_pack(slot.data_ptr())
+
+    # ---- touched-rows exchange on the device
+    def touched_buffers(self, nviews: int):
+        """(bits [nviews, ceil(N / 32)] int32, rows [nviews, N, 3] float32, counts [nviews] int64) on the renderer's device: what
+        gs_color_rows_pack fills per view (allocated once per shape; rows behind a view's count keep whatever they held)"""
+        import torch
+        key = (nviews, self.r.nGaussians)
+        if getattr(self, "_touched_key", None) != key:
+            n, dev = self.r.nGaussians, self.r.imageData.device
+            self._touched = (torch.zeros((nviews, (n + 31) // 32), dtype=torch.int32, device=dev),
+                             torch.zeros((nviews, max(n, 1), 3), dtype=torch.float32, device=dev),
+                             torch.zeros((nviews,), dtype=torch.int64, device=dev))
+            self._touched_key = key
+        return self._touched
+
+    def render_view_touched(self, camera, dC, i: int) -> None:
+        """render_view_factored without the dense slot: view i of touched_buffers is packed straight from the ctx's sums"""
+        from . import renderer as R
+        bits, rows, counts = self._touched
+        tps = R.preprocess(self.r, camera)
+        R.compactIdxs(self.r)
+        R.forward(self.r, tps)
+        R.backward(self.r, dC, skip_shs=True)
+        self.r.ctx.color_rows_pack(None, self.r.nGaussians, bits[i].data_ptr(), rows[i].data_ptr(), counts[i].data_ptr())
+        self.device_touched_packs = getattr(self, "device_touched_packs", 0) + 1     # introspection: the device path was taken
+        self.last_ctx = self.r.ctx
+
+    def sh_from_touched(self, cameras, bits_all, rows_all, rows_cap: int) -> None:
+        R_ = self.r
+        H, W = R_.transmittance.shape
+        assert bits_all.is_contiguous() and rows_all.is_contiguous() and rows_all.shape[1] == rows_cap
+        R_._begin()
+        R_.ctx.sh_grads_from_touched(view_records(cameras, W, H), bits_all.data_ptr(), rows_all.data_ptr(), rows_cap,
+                                     R_.splatGrads.Δshs.data_ptr(), overwrite=True)
+        self.device_touched_rebuilds = getattr(self, "device_touched_rebuilds", 0) + 1
 
     def sh_from_views(self, cameras, drgb_all) -> None:
         R_ = self.r

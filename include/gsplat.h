@@ -320,6 +320,27 @@ int gs_grads_read(gs_ctx *ctx, const gs_grads *grads, float *h_means, float *h_s
 #define GS_VIEW_RECORD_FLOATS 38
 int gs_color_grads_pack(gs_ctx *ctx, float *drgb);
 int gs_sh_grads_from_views(gs_ctx *ctx, int32_t nviews, const float *cams, const float *drgb, float *d_shs, int flags);
+/* Touched-rows exchange (optional; the colour-factored exchange with fewer bytes still).  A view's composite adjoint leaves
+ * d rgb = 0 for every gaussian no pixel evaluated, so a view travels as a bitmap plus the rows of the gaussians it TOUCHED:
+ *   touched:  any of the gaussian's three floats has (bit pattern & 0x7fffffff) != 0 -- +0 and -0 are untouched; denormals, NaN
+ *             and Inf are touched (the bits are tested, not the float value)
+ *   bits:     bit g % 32 of int32 word g / 32, ceil(n / 32) words; the bits of the last word beyond n are 0
+ *   rows:     the touched rows in ascending gaussian order from row 0, copied bit for bit; rows at and beyond *count are not written
+ *   per view: gs_backward as above, then gs_color_rows_pack(ctx, NULL, N, bits, rows, count) -- straight from the ctx's sums, no
+ *             dense 3 x N slot (or from a caller's dense array: drgb != NULL, any n)
+ *   per step: all-reduce of the 11 N geometry floats; all-gather of the counts, of the bitmaps, and of the rows padded to the
+ *             largest count (rows_cap); gs_sh_grads_from_touched(ctx, nviews, cams, bits_all, rows_all, rows_cap, d_shs, flags)
+ * gs_sh_grads_from_touched gives what gs_sh_grads_from_views gives on the unpacked views, bit for bit, without building them.  It
+ * reads nothing outside a view's rows_cap rows whatever the bitmaps say: bits at positions >= N are ignored, a row index
+ * >= rows_cap (a truncated gather) reads as a zero row, and the padding rows behind a view's count are never read.
+ * Neither call synchronises; both are 3-D-renderer only (GS_ERR_UNSUPPORTED otherwise).
+ * drgb: DEVICE [3 x n] or NULL = the ctx's own sums of the last backward (then n must equal gs_num_gaussians and a gs_backward of the
+ * frame must have run: GS_ERR_INVALID otherwise).  bits: DEVICE, ceil(n/32) words; rows: DEVICE, room for 3*n floats; count: DEVICE.
+ * n == 0: GS_OK, *count = 0. */
+int gs_color_rows_pack(gs_ctx *ctx, const float *drgb, int64_t n, int32_t *bits, float *rows, int64_t *count);
+/* bits: DEVICE [nviews][ceil(N/32)]; rows: DEVICE [nviews][rows_cap][3], rows_cap >= 1; cams, d_shs, flags as gs_sh_grads_from_views. */
+int gs_sh_grads_from_touched(gs_ctx *ctx, int32_t nviews, const float *cams, const int32_t *bits, const float *rows,
+                             int64_t rows_cap, float *d_shs, int flags);
 
 #define GS_COMM_ID_BYTES 128
 int gs_comm_unique_id(void *id128);

@@ -196,6 +196,18 @@ hip_packColorGrads!(r::HipRenderer, drgb::Ptr{Float32}) =
 hip_shGradsFromViews!(r::HipRenderer, camRecords::Matrix{Float32}, drgbAll::Ptr{Float32}, Δshs::Ptr{Float32}; overwrite = true) =
     check(r, ccall((:gs_sh_grads_from_views, libgs), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cint),
                    r.ctx, size(camRecords, 2), camRecords, drgbAll, Δshs, overwrite ? 1 : 0))
+# touched-rows exchange: a view travels as a bitmap (bit g % 32 of Int32 word g ÷ 32) plus the d rgb rows of the gaussians it touched
+# (any of the three floats non-zero by its bits), in gaussian order, and an Int64 count -- all DEVICE pointers.  drgb = C_NULL packs
+# the renderer's own sums of the last backward (n = nGaussians).  Per step: gather counts, bitmaps and rows padded to the largest
+# count (rowsCap), then rebuild Δshs from all views; same result as hip_shGradsFromViews! on the unpacked views, bit for bit.
+hip_packColorRows!(r::HipRenderer, drgb::Ptr{Float32}, n::Integer, bits::Ptr{Int32}, rows::Ptr{Float32}, count::Ptr{Int64}) =
+    check(r, ccall((:gs_color_rows_pack, libgs), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int64, Ptr{Int32}, Ptr{Float32}, Ptr{Int64}),
+                   r.ctx, drgb, n, bits, rows, count))
+hip_shGradsFromTouched!(r::HipRenderer, camRecords::Matrix{Float32}, bitsAll::Ptr{Int32}, rowsAll::Ptr{Float32}, rowsCap::Integer,
+                        Δshs::Ptr{Float32}; overwrite = true) =
+    check(r, ccall((:gs_sh_grads_from_touched, libgs), Cint,
+                   (Ptr{Cvoid}, Int32, Ptr{Float32}, Ptr{Int32}, Ptr{Float32}, Int64, Ptr{Float32}, Cint),
+                   r.ctx, size(camRecords, 2), camRecords, bitsAll, rowsAll, rowsCap, Δshs, overwrite ? 1 : 0))
 
 # resetGrads(renderer.splatGrads)  (src/splat.jl:158-173)
 hip_resetGrads!(r::HipRenderer, grads::GsGrads) =
