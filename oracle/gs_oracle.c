@@ -948,3 +948,482 @@ void gso_backward2d(int64_t n, const float *means, const float *scales, const fl
     free(g2d); free(F); free(bbs);
 }
 
+/* ------------------------------------------------------------------ per-gaussian composite reference */
+
+/* The composite adjoint at a GIVEN payload, per gaussian, with the amount of fp32 rounding that is legitimate for
+ * every (gaussian, component) -- what a per-gaussian comparison of the HIP composite backward needs (tests/pergaussian_ref.py).
+ * gso_backward evaluates the adjoint at the fp64 forward; the kernels evaluate it at the fp32 payload, and on an
+ * ill-conditioned 2-D covariance the two differ by far more than the composite's own rounding.  The functions below
+ * take the payload as given, so what is left is the composite alone.
+ *
+ * Rows are in the device layout: [dr dg db | S0 Sx Sy Sxx Sxy - Syy], the colour gradient and the raw moments of
+ * dd = dL/d(log alpha) about the splat's mean (slot 8 unused).
+ *
+ * Error mass of one pixel with contributors q = 0 .. m-1 in list order (alpha a, transmittance T in front, offsets
+ * dX dY, conic M, cd = rgb . dC, |cd| = sum_c |rgb_c dC_c| -- fp32 sees no cancellation between the channels, neither in the dot
+ * product nor in S): the kernel forms S = image . dC, then per entry S -= cd a T, dalpha = T cd - S/(1-a).
+ *   Xabs_q = 1/2 (|M0| dX^2 + |M1+M2| |dX dY| + |M3| dY^2)     relative error of a_q per ulp of the exponent's terms
+ *   P_q    = sum_{j<q} [1 + (1 + Xabs_j) a_j/(1-a_j)]           what T_q inherited
+ *   w_q    = 8 + Xabs_q + P_q                                   ulps on the term a_q T_q (.)
+ *   Q = sum_j a_j T_j |cd_j|,  Qw = sum_j w_j a_j T_j |cd_j|     S and its rounding
+ *   E_q    = w_q T_q |cd_q| + (Qw + w_q Q)/(1-a_q)              mass of dalpha_q
+ *   colour c: w_q a_q T_q |dC_c|;  S0: a_q E_q;  moments: a_q E_q times |dX|, |dY|, dX^2, |dX dY|, dY^2.
+ * A correct fp32 evaluation stays inside kappa * 2^-24 * mass + floor (kappa measured on the fp32 twin below).
+ * floor: an intermediate that underflows loses at most 2^-126 before the remaining factors multiply it; 2^-120 times
+ * those factors per term covers the handful of products of a term.
+ * dropped: what a kernel may omit whole -- contributions whose alpha is below 2^-27 (no-op rule of the kernels'
+ * alpha_cull; with several waves per tile the forward and the backward need not drop the same ones, so S may keep
+ * the sum D of the dropped a T |cd| of the pixel: every contributor gets a_q D/(1-a_q) on top of its own term). */
+
+#define GSO_DROP_ALPHA (7.4505805969238281e-09 * (1.0 + 1.0 / 1024.0))   /* 2^-27, with room for the kernels' fp32 bound */
+#define GSO_FLOOR_UNIT 7.5231638452626401e-37                            /* 2^-120: the one underflow unit (composite floor, SH path, driver) */
+#define GSO_ALPHA_MAX 0.99999994                                         /* largest float below 1 */
+double gso_floor_unit(void) { return GSO_FLOOR_UNIT; }
+
+void gso_forward64(int64_t n, int sh_degree, const float *means, const float *scales, const float *quats,
+                   const float *opacities, const float *shs, const gso_camera *cam,
+                   double *mu, double *M, double *sig, double *rgb) {
+#pragma omp parallel for schedule(static)
+    for (int64_t g = 0; g < n; ++g) {
+        g64 f;
+        fwd64(g, sh_degree, means, scales, quats, opacities, shs, cam, &f);
+        mu[2 * g] = f.mu[0]; mu[2 * g + 1] = f.mu[1];
+        for (int i = 0; i < 4; ++i) M[4 * g + i] = f.M[i];
+        sig[g] = f.sig;
+        for (int i = 0; i < 3; ++i) rgb[3 * g + i] = f.rgb[i];
+    }
+}
+
+static const int ROW_OF[9] = { 0, 1, 2, 3, 4, 5, 6, 7, 9 };    /* nine sums -> words of the device row */
+
+void gso_composite_rows(const gso_camera *cam, int tile, int gx, int gy, const uint32_t *ranges, const uint32_t *ids,
+                        int64_t n, const double *mu, const double *M, const float *bbs, const double *sig,
+                        const double *rgb, const float *tps, float t_min, const float *dC,
+                        double *rows, double *mass, double *dropped, double *floor_, int32_t *ntiles) {
+    (void)n;
+    const int W = cam->W, H = cam->H;
+    const int64_t plane = (int64_t)W * H, nt = (int64_t)gx * gy;
+#pragma omp parallel
+    {
+        size_t capk = 1024;
+        /* per contributor of the pixel: a, T, dX, dY, cd, w, |cd| */
+        double *al = (double *)malloc(sizeof(double) * capk * 7);
+        uint32_t *who = (uint32_t *)malloc(sizeof(uint32_t) * capk);
+        /* per list entry of the tile: rows, mass, dropped, floor (9 each) and a touched flag */
+        double *acc = (double *)malloc(sizeof(double) * capk * 36);
+        uint8_t *hit = (uint8_t *)malloc(capk);
+#pragma omp for schedule(dynamic, 1)
+        for (int64_t t = 0; t < nt; ++t) {
+            int bx = (int)(t % gx) + 1, by = (int)(t / gx) + 1;
+            uint32_t s0 = ranges[2 * t], s1 = ranges[2 * t + 1];
+            const size_t len = (size_t)(s1 - s0);
+            if (len + 1 > capk) {
+                capk = len + 1;
+                al = (double *)realloc(al, sizeof(double) * capk * 7);
+                who = (uint32_t *)realloc(who, sizeof(uint32_t) * capk);
+                acc = (double *)realloc(acc, sizeof(double) * capk * 36);
+                hit = (uint8_t *)realloc(hit, capk);
+            }
+            memset(acc, 0, sizeof(double) * (len + 1) * 36);
+            memset(hit, 0, len + 1);
+            for (int tyi = 1; tyi <= tile; ++tyi)
+                for (int txi = 1; txi <= tile; ++txi) {
+                    int i = (bx - 1) * tile + txi, j = (by - 1) * tile + tyi;
+                    if (i > W || j > H) continue;
+                    int64_t px = (int64_t)(i - 1) + (int64_t)W * (j - 1);
+                    double dc[3] = { dC[px], dC[px + plane], dC[px + 2 * plane] };
+                    double Tr = 1.0, Pq = 0.0, Q = 0.0, Qw = 0.0, D = 0.0;
+                    size_t m = 0;
+                    float fi = (float)i, fj = (float)j;
+                    for (uint32_t k = s0; k < s1; ++k) {
+                        if (t_min > 0.0f && ((k - s0) % GSO_EARLY_BATCH) == 0 && Tr < (double)t_min) break;
+                        uint32_t b = ids[k];
+                        if (tps) {
+                            float cz = tps[4 * (int64_t)b + 2];
+                            if (cz < cam->near_ || cz > cam->far_) continue;
+                        }
+                        const float *bb = bbs + 4 * (int64_t)b;
+                        if (!((bb[0] <= fi) && (fi <= bb[2]) && (bb[1] <= fj) && (fj <= bb[3]))) continue;
+                        const double *Mb = M + 4 * (int64_t)b, *cb = rgb + 3 * (int64_t)b;
+                        double dX = (double)i - mu[2 * (int64_t)b], dY = (double)j - mu[2 * (int64_t)b + 1];
+                        double v1 = Mb[0] * dX + Mb[2] * dY, v2 = Mb[1] * dX + Mb[3] * dY;
+                        double a = sig[b] * exp(-0.5 * (v1 * dX + v2 * dY));
+                        if (!(a > 0.0)) continue;                       /* exp underflowed in fp64: contributes nothing at all */
+                        if (a > GSO_ALPHA_MAX) a = GSO_ALPHA_MAX;       /* alpha < 1 strictly, as in the kernels and the twin: 1/(1-a) stays finite */
+                        double Xabs = 0.5 * (fabs(Mb[0]) * dX * dX + fabs(Mb[1] + Mb[2]) * fabs(dX * dY) + fabs(Mb[3]) * dY * dY);
+                        double cd = cb[0] * dc[0] + cb[1] * dc[1] + cb[2] * dc[2];
+                        double acd = fabs(cb[0] * dc[0]) + fabs(cb[1] * dc[1]) + fabs(cb[2] * dc[2]);   /* |cd| as fp32 sees it: no cancellation between the channels */
+                        double wq = 8.0 + Xabs + Pq;
+                        al[7 * m] = a; al[7 * m + 1] = Tr; al[7 * m + 2] = dX; al[7 * m + 3] = dY; al[7 * m + 4] = cd; al[7 * m + 5] = wq; al[7 * m + 6] = acd;
+                        who[m] = k - s0; ++m;
+                        Q += a * Tr * acd; Qw += wq * a * Tr * acd;
+                        if (a < GSO_DROP_ALPHA) D += a * Tr * acd;
+                        Pq += 1.0 + (1.0 + Xabs) * a / (1.0 - a);
+                        Tr *= (1.0 - a);
+                    }
+                    const double dcs = fabs(dc[0]) + fabs(dc[1]) + fabs(dc[2]);
+                    double B = 0.0;
+                    for (size_t q = m; q-- > 0;) {
+                        double a = al[7 * q], Tk = al[7 * q + 1], dX = al[7 * q + 2], dY = al[7 * q + 3], cd = al[7 * q + 4], wq = al[7 * q + 5], acd = al[7 * q + 6];
+                        double da = Tk * (cd - B);
+                        B = cd * a + (1.0 - a) * B;
+                        double wgt = a * Tk, dd = -a * da;
+                        double Eq = wq * Tk * acd + (Qw + wq * Q) / (1.0 - a);
+                        const double mf[6] = { 1.0, fabs(dX), fabs(dY), dX * dX, fabs(dX * dY), dY * dY };
+                        const double sf[6] = { 1.0, dX, dY, dX * dX, dX * dY, dY * dY };
+                        double *r = acc + 36 * (size_t)who[q];
+                        const int isdrop = a < GSO_DROP_ALPHA;
+                        const double fl = GSO_FLOOR_UNIT * (1.0 + acd + dcs + Q / (1.0 - a));
+                        hit[who[q]] = 1;
+                        for (int c = 0; c < 3; ++c) {
+                            r[c] += wgt * dc[c];
+                            r[9 + c] += wq * wgt * fabs(dc[c]);
+                            if (isdrop) r[18 + c] += wgt * fabs(dc[c]);
+                            r[27 + c] += fl;
+                        }
+                        for (int c = 0; c < 6; ++c) {
+                            r[3 + c] += dd * sf[c];
+                            r[12 + c] += a * Eq * mf[c];
+                            r[21 + c] += ((isdrop ? fabs(dd) : 0.0) + a * D / (1.0 - a)) * mf[c];
+                            r[30 + c] += fl * (mf[c] > 1.0 ? mf[c] : 1.0);
+                        }
+                    }
+                }
+            for (size_t k = 0; k < len; ++k) {
+                if (!hit[k]) continue;
+                const int64_t b = ids[s0 + k];
+                const double *r = acc + 36 * k;
+                for (int c = 0; c < 9; ++c) {
+                    const int64_t o = 10 * b + ROW_OF[c];
+#pragma omp atomic
+                    rows[o] += r[c];
+#pragma omp atomic
+                    mass[o] += r[9 + c];
+#pragma omp atomic
+                    dropped[o] += r[18 + c];
+#pragma omp atomic
+                    floor_[o] += r[27 + c];
+                }
+#pragma omp atomic
+                ntiles[b] += 1;
+            }
+        }
+        free(al); free(who); free(acc); free(hit);
+    }
+}
+
+/* The fp32 twin: the same adjoint in float, in the kernel's own formulation and order of operations (backward_entry
+ * and the reduction of gs_composite.hip): one lane per column and row-in-strip, four strips per lane, S = image . dC from
+ * a forward in the same arithmetic, per entry w = a T, S -= cd w, dalpha = T cd - S/(1-a), T -= w; a lane's nine sums,
+ * sixteen-lane quarters summed pairwise, the four quarters pairwise; then the tiles in order.  expf and / stand in for
+ * the GPU's exp2 and reciprocal instructions.  It measures how much of the bound a correct fp32 evaluation uses. */
+typedef struct { float mux, muy, i0, i1, i2, i3, sig, r, g, b, bb[4]; } twin_pay;
+
+static inline float twin_alpha(const twin_pay *e, float fx, float fy, float *dXo, float *dYo) {
+    const float dX = fx - e->mux, dY = fy - e->muy;
+    *dXo = dX; *dYo = dY;
+    if (!((e->bb[0] <= fx) && (fx <= e->bb[2]) && (e->bb[1] <= fy) && (fy <= e->bb[3]))) return 0.0f;
+    const float v1 = e->i0 * dX + e->i2 * dY, v2 = e->i1 * dX + e->i3 * dY;
+    const float dist = 0.5f * (v1 * dX + v2 * dY);
+    float a = e->sig * expf(-dist);
+    if (!(a <= (float)GSO_ALPHA_MAX)) a = (float)GSO_ALPHA_MAX;
+    return a;
+}
+
+void gso_composite_rows_f32(const gso_camera *cam, int tile, int gx, int gy, const uint32_t *ranges, const uint32_t *ids,
+                            int64_t n, const float *mu, const float *invcov, const float *bbs, const float *sig,
+                            const float *rgb, const float *tps, float t_min, const float *dC, float *rows) {
+    (void)n;
+    const int W = cam->W, H = cam->H;
+    const int64_t plane = (int64_t)W * H, nt = (int64_t)gx * gy;
+    if (tile != 16) return;                                  /* the lane layout below is the kernel's 16 x 16 tile */
+    const int64_t total = nt > 0 ? (int64_t)ranges[2 * (nt - 1) + 1] : 0;
+    float *tsum = (float *)calloc((size_t)(total > 0 ? total : 1) * 9, sizeof(float));
+    uint8_t *done = (uint8_t *)calloc((size_t)(total > 0 ? total : 1), 1);
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int64_t t = 0; t < nt; ++t) {
+        const int tx0 = (int)(t % gx) * 16 + 1, ty0 = (int)(t / gx) * 16 + 1;
+        const uint32_t s0 = ranges[2 * t], s1 = ranges[2 * t + 1];
+        float dc[64][4][3], T[64][4], S[64][4], C[64][4][3];
+        int dead[64][4], in[64][4];
+        for (int pass = 0; pass < 2; ++pass) {               /* 0: forward (image), 1: backward */
+            for (int l = 0; l < 64; ++l)
+                for (int p = 0; p < 4; ++p) {
+                    const int x = tx0 + (l & 15), y = ty0 + (l >> 4) + 4 * p;
+                    in[l][p] = x <= W && y <= H;
+                    dead[l][p] = !in[l][p];
+                    T[l][p] = in[l][p] ? 1.0f : 0.0f;
+                    if (pass == 0) {
+                        const int64_t o = in[l][p] ? (int64_t)(x - 1) + (int64_t)W * (y - 1) : 0;
+                        for (int c = 0; c < 3; ++c) { dc[l][p][c] = in[l][p] ? dC[o + c * plane] : 0.0f; C[l][p][c] = 0.0f; }
+                    } else {
+                        S[l][p] = in[l][p] ? (C[l][p][0] * dc[l][p][0] + C[l][p][1] * dc[l][p][1] + C[l][p][2] * dc[l][p][2]) : 0.0f;
+                    }
+                }
+            for (uint32_t k = s0; k < s1; ++k) {
+                if (t_min > 0.0f && ((k - s0) % GSO_EARLY_BATCH) == 0) {
+                    int alive = 0;
+                    for (int l = 0; l < 64; ++l)
+                        for (int p = 0; p < 4; ++p) {
+                            if (!dead[l][p] && T[l][p] < t_min) { dead[l][p] = 1; T[l][p] = 0.0f; if (pass) S[l][p] = 0.0f; }
+                            alive |= !dead[l][p];
+                        }
+                    if (!alive) break;
+                }
+                const int64_t b = ids[k];
+                if (tps) {
+                    const float cz = tps[4 * b + 2];
+                    if (cz < cam->near_ || cz > cam->far_) continue;
+                }
+                twin_pay e = { mu[2 * b], mu[2 * b + 1], invcov[4 * b], invcov[4 * b + 1], invcov[4 * b + 2], invcov[4 * b + 3], sig[b],
+                               rgb[3 * b], rgb[3 * b + 1], rgb[3 * b + 2], { bbs[4 * b], bbs[4 * b + 1], bbs[4 * b + 2], bbs[4 * b + 3] } };
+                float v[9][64];
+                int any = 0;
+                for (int l = 0; l < 64; ++l) {
+                    const float fx = (float)(tx0 + (l & 15));
+                    float ar = 0.0f, ag = 0.0f, ab = 0.0f, q0s = 0.0f, q1s = 0.0f, q2s = 0.0f, dX = fx - e.mux;
+                    for (int p = 0; p < 4; ++p) {
+                        if (dead[l][p]) continue;             /* T = S = 0 (or outside the image): exact zeros */
+                        const float fy = (float)(ty0 + (l >> 4) + 4 * p);
+                        float dY;
+                        const float a = twin_alpha(&e, fx, fy, &dX, &dY);
+                        if (a == 0.0f) continue;
+                        any = 1;
+                        const float w = a * T[l][p];
+                        if (pass == 0) {
+                            C[l][p][0] = fmaf(e.r, w, C[l][p][0]); C[l][p][1] = fmaf(e.g, w, C[l][p][1]); C[l][p][2] = fmaf(e.b, w, C[l][p][2]);
+                        } else {
+                            const float cdot = fmaf(e.r, dc[l][p][0], fmaf(e.g, dc[l][p][1], e.b * dc[l][p][2]));
+                            S[l][p] = fmaf(-cdot, w, S[l][p]);
+                            const float inv = 1.0f / (1.0f - a);
+                            const float dalpha = fmaf(T[l][p], cdot, -(S[l][p] * inv));
+                            const float dd = -(a * dalpha);
+                            const float ddy = dd * dY;
+                            ar = fmaf(w, dc[l][p][0], ar); ag = fmaf(w, dc[l][p][1], ag); ab = fmaf(w, dc[l][p][2], ab);
+                            q0s += dd; q1s += ddy; q2s = fmaf(ddy, dY, q2s);
+                        }
+                        T[l][p] = T[l][p] - w;
+                    }
+                    if (pass) {
+                        const float qx = dX * q0s;
+                        v[0][l] = ar; v[1][l] = ag; v[2][l] = ab; v[3][l] = q0s; v[4][l] = qx; v[5][l] = q1s;
+                        v[6][l] = dX * qx; v[7][l] = dX * q1s; v[8][l] = q2s;
+                    }
+                }
+                if (pass && any) {
+                    for (int c = 0; c < 9; ++c) {
+                        float qs[4];
+                        for (int s = 0; s < 4; ++s) {
+                            const float *r = v[c] + 16 * s;
+                            float x = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+                            x += ((r[8] + r[9]) + (r[10] + r[11])) + ((r[12] + r[13]) + (r[14] + r[15]));
+                            qs[s] = x;
+                        }
+                        tsum[9 * (int64_t)k + c] = (qs[0] + qs[1]) + (qs[2] + qs[3]);
+                    }
+                    done[k] = 1;
+                }
+            }
+        }
+    }
+    for (int64_t k = 0; k < total; ++k) {
+        if (!done[k]) continue;
+        for (int c = 0; c < 9; ++c) rows[10 * (int64_t)ids[k] + ROW_OF[c]] += tsum[9 * k + c];
+    }
+    free(tsum); free(done);
+}
+
+/* Parameter gradients of caller-supplied rows: bwd64 per gaussian.  raw != 0: the rows are device rows (raw moments) and
+ * are first turned into d{sig, mu, conic} with the fp64 sig and conic of fwd64 -- what the geometry kernel does with the
+ * row it reads; raw == 0: the rows are gso_backward's g2d.  Linear in the rows; gradients ACCUMULATE.  All-zero rows
+ * are skipped (exactly zero gradient, whatever the recomputed forward holds). */
+void gso_chain(int64_t n, int sh_degree, const float *means, const float *scales, const float *quats,
+               const float *opacities, const float *shs, const gso_camera *cam, const double *rows, int raw,
+               double *dmeans, double *dscales, double *dquats, double *dopac, double *dshs) {
+#pragma omp parallel for schedule(static)
+    for (int64_t g = 0; g < n; ++g) {
+        double g2[10];
+        int live = 0;
+        for (int i = 0; i < 10; ++i) { g2[i] = rows[10 * g + i]; live |= g2[i] != 0.0; }
+        if (!live) continue;
+        if (raw) {
+            g64 f;
+            fwd64(g, sh_degree, means, scales, quats, opacities, shs, cam, &f);
+            const double S0 = g2[3], Sx = g2[4], Sy = g2[5], Sxx = g2[6], Sxy = g2[7], Syy = g2[9];
+            const double mc = 0.5 * (f.M[1] + f.M[2]);
+            g2[3] = f.sig > 0.0 ? -S0 / f.sig : 0.0;
+            g2[4] = -(f.M[0] * Sx + mc * Sy);
+            g2[5] = -(mc * Sx + f.M[3] * Sy);
+            g2[6] = 0.5 * Sxx; g2[7] = 0.5 * Sxy; g2[8] = 0.5 * Sxy; g2[9] = 0.5 * Syy;
+        }
+        bwd64(g, sh_degree, means, scales, quats, opacities, shs, cam, g2, dmeans, dscales, dquats, dopac, dshs);
+    }
+}
+
+/* ------------------------------------------------------------------ SH colour path of the backward: reference, mass, fp32 twin */
+
+/* The one part of the parameter chain the kernels run in fp32 (gs_sh_bwd_kernel): direction from the fp32 clip position, basis,
+ * d_shs = basis (x) d rgb, and the colour's pull on the position dpc = d L / d tps[0:3].  gso_sh_path evaluates it in fp64 at a
+ * given d rgb [n,3] and states, per output float, how much fp32 rounding is legitimate: an error budget in units of 2^-24 carried
+ * through the statements (first order), every polynomial taken with absolute-valued monomials:
+ *   t = T m, p = P t        4 sum |term| per dot product, plus the inputs' budgets through |P|
+ *   v = p - (lookAt - eye)  + |v| + |lookAt - eye|
+ *   1/|v|                   relative: sum |v_a| e(v_a) / |v|^2 + 4
+ *   dir = v / |v|           e(v)/|v| + |dir| (rel + 1)
+ *   basis_k                 sum_a |d b_k / d dir_a|abs e(dir_a) + 6 |b_k|abs
+ *   d_shs[k][c]             (e(b_k) + |b_k|) |d rgb_c|
+ *   cs_k = d rgb . sh_k     3 sum_c |d rgb_c sh_kc|
+ *   ddir_a                  sum_k |d b_k / d dir_a|abs (e(cs_k) + (8 + K) |cs_k|abs) + H |cs_k| sum_b e(dir_b)
+ *                           (H bounds the basis' second derivatives on the unit sphere: 0, 2.2, 4.5 for degree 1, 2, 3)
+ *   dd = dir . ddir, dpc = (ddir - dir dd) / |v|   product rule, 2 .. 3 per operation.
+ * A correct fp32 evaluation stays inside kappa * 2^-24 * mass + gso_floor_unit() (kappa measured on gso_sh_path_f32, the kernel's
+ * statements in float; the floor: a product that underflows loses at most 2^-126 before factors below 2^6 multiply it). */
+static void sh_basis_abs(int deg, double x, double y, double z, double b[16], double db[16][3]) {
+    memset(db, 0, sizeof(double) * 16 * 3);
+    x = fabs(x); y = fabs(y); z = fabs(z);
+    b[0] = D_C0;
+    if (deg < 1) return;
+    b[1] = y * D_C1; db[1][1] = D_C1;
+    b[2] = z * D_C1; db[2][2] = D_C1;
+    b[3] = x * D_C1; db[3][0] = D_C1;
+    if (deg < 2) return;
+    const double xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+    double c;
+    c = fabs(D_C2[0]); b[4] = c * xy; db[4][0] = c * y; db[4][1] = c * x;
+    c = fabs(D_C2[1]); b[5] = c * yz; db[5][1] = c * z; db[5][2] = c * y;
+    c = fabs(D_C2[2]); b[6] = c * (2 * zz + xx + yy); db[6][0] = 2 * c * x; db[6][1] = 2 * c * y; db[6][2] = 4 * c * z;
+    c = fabs(D_C2[3]); b[7] = c * xz; db[7][0] = c * z; db[7][2] = c * x;
+    c = fabs(D_C2[4]); b[8] = c * (xx + yy); db[8][0] = 2 * c * x; db[8][1] = 2 * c * y;
+    if (deg < 3) return;
+    c = fabs(D_C3[0]); b[9] = c * y * (3 * xx + yy); db[9][0] = 6 * c * xy; db[9][1] = c * (3 * xx + 3 * yy);
+    c = fabs(D_C3[1]); b[10] = c * xy * z; db[10][0] = c * yz; db[10][1] = c * xz; db[10][2] = c * xy;
+    c = fabs(D_C3[2]); b[11] = c * y * (4 * zz + xx + yy); db[11][0] = 2 * c * xy; db[11][1] = c * (4 * zz + xx + 3 * yy); db[11][2] = 8 * c * yz;
+    c = fabs(D_C3[3]); b[12] = c * z * (2 * zz + 3 * xx + 3 * yy); db[12][0] = 6 * c * xz; db[12][1] = 6 * c * yz; db[12][2] = c * (6 * zz + 3 * xx + 3 * yy);
+    c = fabs(D_C3[4]); b[13] = c * x * (4 * zz + xx + yy); db[13][0] = c * (4 * zz + 3 * xx + yy); db[13][1] = 2 * c * xy; db[13][2] = 8 * c * xz;
+    c = fabs(D_C3[5]); b[14] = c * z * (xx + yy); db[14][0] = 2 * c * xz; db[14][1] = 2 * c * yz; db[14][2] = c * (xx + yy);
+    c = fabs(D_C3[6]); b[15] = c * x * (xx + 3 * yy); db[15][0] = c * (3 * xx + 3 * yy); db[15][1] = 6 * c * xy;
+}
+
+/* outputs [n,3K] dshs, mass_shs and [n,3] dpc, mass_dpc (masses in units of the value: multiply by kappa * 2^-24); overwritten.
+ * Gaussians with an all-zero d rgb are skipped (exact zeros, as in the kernel). */
+void gso_sh_path(int64_t n, int sh_degree, const float *means, const float *shs, const gso_camera *cam, const double *drgb,
+                 double *dshs, double *mass_shs, double *dpc, double *mass_dpc) {
+    const int K = (sh_degree + 1) * (sh_degree + 1);
+    const double Hs = sh_degree >= 3 ? 4.5 : (sh_degree == 2 ? 2.2 : 0.0);
+#pragma omp parallel for schedule(static)
+    for (int64_t g = 0; g < n; ++g) {
+        const double *gr = drgb + 3 * g;
+        for (int i = 0; i < 3 * K; ++i) { dshs[3 * K * g + i] = 0.0; mass_shs[3 * K * g + i] = 0.0; }
+        for (int i = 0; i < 3; ++i) { dpc[3 * g + i] = 0.0; mass_dpc[3 * g + i] = 0.0; }
+        if (gr[0] == 0.0 && gr[1] == 0.0 && gr[2] == 0.0) continue;
+        const double m[4] = { means[3 * g], means[3 * g + 1], means[3 * g + 2], 1.0 };
+        double t[4], et[4], p[4], ep[4];
+        for (int i = 0; i < 4; ++i) {
+            double s = 0.0, a = 0.0;
+            for (int j = 0; j < 4; ++j) { s += cam->T[i + 4 * j] * m[j]; a += fabs(cam->T[i + 4 * j] * m[j]); }
+            t[i] = s; et[i] = 4.0 * a;
+        }
+        for (int i = 0; i < 4; ++i) {
+            double s = 0.0, a = 0.0, e = 0.0;
+            for (int j = 0; j < 4; ++j) { s += cam->P[i + 4 * j] * t[j]; a += fabs(cam->P[i + 4 * j] * t[j]); e += fabs(cam->P[i + 4 * j]) * et[j]; }
+            p[i] = s; ep[i] = e + 4.0 * a;
+        }
+        double v[3], ev[3], n2 = 0.0, rel = 4.0;
+        for (int a = 0; a < 3; ++a) {
+            const double le = (double)cam->lookAt[a] - (double)cam->eye[a];
+            v[a] = p[a] - le; ev[a] = ep[a] + fabs(v[a]) + fabs(le);
+            n2 += v[a] * v[a];
+        }
+        const double nrm = sqrt(n2);
+        for (int a = 0; a < 3; ++a) rel += fabs(v[a]) * ev[a] / n2;
+        double X[3], eX[3], seX = 0.0;
+        for (int a = 0; a < 3; ++a) { X[a] = v[a] / nrm; eX[a] = ev[a] / nrm + fabs(X[a]) * (rel + 1.0); seX += eX[a]; }
+        double b[16], db[16][3], ab[16], adb[16][3];
+        sh_basis_f64(sh_degree, X[0], X[1], X[2], b, db);
+        sh_basis_abs(sh_degree, X[0], X[1], X[2], ab, adb);
+        double ddir[3] = { 0, 0, 0 }, addir[3] = { 0, 0, 0 }, eddir[3] = { 0, 0, 0 };
+        for (int k = 0; k < K; ++k) {
+            const double eb = adb[k][0] * eX[0] + adb[k][1] * eX[1] + adb[k][2] * eX[2] + 6.0 * ab[k];
+            double cs = 0.0, acs = 0.0;
+            for (int c = 0; c < 3; ++c) {
+                const double sh = shs[(int64_t)3 * K * g + c + 3 * k];
+                dshs[3 * K * g + c + 3 * k] = b[k] * gr[c];
+                mass_shs[3 * K * g + c + 3 * k] = (eb + ab[k]) * fabs(gr[c]);
+                cs += gr[c] * sh; acs += fabs(gr[c] * sh);
+            }
+            for (int a = 0; a < 3; ++a) {
+                ddir[a] += cs * db[k][a];
+                addir[a] += acs * adb[k][a];
+                eddir[a] += adb[k][a] * (3.0 * acs + (8.0 + K) * acs) + (k >= 4 ? Hs * fabs(cs) * seX : 0.0);
+            }
+        }
+        double dd = 0.0, add = 0.0, edd = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            dd += X[a] * ddir[a]; add += fabs(X[a]) * addir[a];
+            edd += fabs(X[a]) * eddir[a] + addir[a] * eX[a] + 3.0 * fabs(X[a]) * addir[a];
+        }
+        for (int a = 0; a < 3; ++a) {
+            dpc[3 * g + a] = (ddir[a] - X[a] * dd) / nrm;
+            const double mag = addir[a] + fabs(X[a]) * add;
+            mass_dpc[3 * g + a] = (eddir[a] + fabs(X[a]) * edd + add * eX[a] + 2.0 * mag) / nrm + mag / nrm * (rel + 1.0);
+        }
+    }
+}
+
+/* the fp32 twin: gs_sh_bwd_kernel's statements in float, in the written order (no contraction); 1/sqrtf stands in for rsqrtf */
+void gso_sh_path_f32(int64_t n, int sh_degree, const float *means, const float *shs, const gso_camera *cam, const float *drgb,
+                     float *dshs, float *dpc) {
+    const int K = (sh_degree + 1) * (sh_degree + 1);
+    const float *T = cam->T, *P = cam->P;
+#pragma omp parallel for schedule(static)
+    for (int64_t g = 0; g < n; ++g) {
+        const float *grgb = drgb + 3 * g;
+        for (int i = 0; i < 3 * K; ++i) dshs[3 * K * g + i] = 0.0f;
+        for (int i = 0; i < 3; ++i) dpc[3 * g + i] = 0.0f;
+        if (grgb[0] == 0.0f && grgb[1] == 0.0f && grgb[2] == 0.0f) continue;
+        const float m1 = means[3 * g], m2 = means[3 * g + 1], m3 = means[3 * g + 2];
+        float t[4], p[4];
+        for (int i = 0; i < 4; ++i) t[i] = T[i] * m1 + T[i + 4] * m2 + T[i + 8] * m3 + T[i + 12];
+        for (int i = 0; i < 4; ++i) p[i] = P[i] * t[0] + P[i + 4] * t[1] + P[i + 8] * t[2] + P[i + 12] * t[3];
+        const float v0 = p[0] - (cam->lookAt[0] - cam->eye[0]);
+        const float v1 = p[1] - (cam->lookAt[1] - cam->eye[1]);
+        const float v2 = p[2] - (cam->lookAt[2] - cam->eye[2]);
+        const float inrm = 1.0f / sqrtf(v0 * v0 + v1 * v1 + v2 * v2);
+        const float X = v0 * inrm, Y = v1 * inrm, Z = v2 * inrm;
+        float bs[16];
+        const float xx = X * X, yy = Y * Y, zz = Z * Z, xy = X * Y, yz = Y * Z, xz = X * Z;
+        bs[0] = SH_C0;
+        if (sh_degree >= 1) { bs[1] = -Y * SH_C1; bs[2] = Z * SH_C1; bs[3] = -X * SH_C1; }
+        if (sh_degree >= 2) {
+            bs[4] = SH_C2[0] * xy; bs[5] = SH_C2[1] * yz; bs[6] = SH_C2[2] * (2 * zz - xx - yy); bs[7] = SH_C2[3] * xz; bs[8] = SH_C2[4] * (xx - yy);
+        }
+        if (sh_degree >= 3) {
+            bs[9] = SH_C3[0] * Y * (3 * xx - yy); bs[10] = SH_C3[1] * xy * Z; bs[11] = SH_C3[2] * Y * (4 * zz - xx - yy);
+            bs[12] = SH_C3[3] * Z * (2 * zz - 3 * xx - 3 * yy); bs[13] = SH_C3[4] * X * (4 * zz - xx - yy);
+            bs[14] = SH_C3[5] * Z * (xx - yy); bs[15] = SH_C3[6] * X * (xx - 3 * yy);
+        }
+        float cs[16];
+        for (int k = 0; k < K; ++k) {
+            const float *sh = shs + (int64_t)3 * K * g + 3 * k;
+            for (int c = 0; c < 3; ++c) dshs[3 * K * g + c + 3 * k] = bs[k] * grgb[c];
+            cs[k] = grgb[0] * sh[0] + grgb[1] * sh[1] + grgb[2] * sh[2];
+        }
+        float ddir[3] = { 0.0f, 0.0f, 0.0f };
+        if (sh_degree >= 1) { ddir[0] += -SH_C1 * cs[3]; ddir[1] += -SH_C1 * cs[1]; ddir[2] += SH_C1 * cs[2]; }
+        if (sh_degree >= 2) {
+            ddir[0] += SH_C2[0] * Y * cs[4] - 2 * SH_C2[2] * X * cs[6] + SH_C2[3] * Z * cs[7] + 2 * SH_C2[4] * X * cs[8];
+            ddir[1] += SH_C2[0] * X * cs[4] + SH_C2[1] * Z * cs[5] - 2 * SH_C2[2] * Y * cs[6] - 2 * SH_C2[4] * Y * cs[8];
+            ddir[2] += SH_C2[1] * Y * cs[5] + 4 * SH_C2[2] * Z * cs[6] + SH_C2[3] * X * cs[7];
+        }
+        if (sh_degree >= 3) {
+            ddir[0] += 6 * SH_C3[0] * xy * cs[9] + SH_C3[1] * yz * cs[10] - 2 * SH_C3[2] * xy * cs[11] - 6 * SH_C3[3] * xz * cs[12]
+                       + SH_C3[4] * (4 * zz - 3 * xx - yy) * cs[13] + 2 * SH_C3[5] * xz * cs[14] + SH_C3[6] * (3 * xx - 3 * yy) * cs[15];
+            ddir[1] += SH_C3[0] * (3 * xx - 3 * yy) * cs[9] + SH_C3[1] * xz * cs[10] + SH_C3[2] * (4 * zz - xx - 3 * yy) * cs[11]
+                       - 6 * SH_C3[3] * yz * cs[12] - 2 * SH_C3[4] * xy * cs[13] - 2 * SH_C3[5] * yz * cs[14] - 6 * SH_C3[6] * xy * cs[15];
+            ddir[2] += SH_C3[1] * xy * cs[10] + 8 * SH_C3[2] * yz * cs[11] + SH_C3[3] * (6 * zz - 3 * xx - 3 * yy) * cs[12]
+                       + 8 * SH_C3[4] * xz * cs[13] + SH_C3[5] * (xx - yy) * cs[14];
+        }
+        const float dd = X * ddir[0] + Y * ddir[1] + Z * ddir[2];
+        dpc[3 * g] = (ddir[0] - X * dd) * inrm; dpc[3 * g + 1] = (ddir[1] - Y * dd) * inrm; dpc[3 * g + 2] = (ddir[2] - Z * dd) * inrm;
+    }
+}

@@ -126,6 +126,50 @@ void gso_backward2d(int64_t n, const float *means, const float *scales, const fl
                     double *dmeans, double *dscales, double *drots, double *dopac, double *dcolors,
                     double *g2d /* optional n*10 */);
 
+/* ---- per-gaussian reference of the composite backward (tests/pergaussian_ref.py) ------------------ */
+
+/* The fp64 forward's payload per gaussian: mu[n,2], M[n,4] (inverse 2-D covariance, column-major), sig[n], rgb[n,3]. */
+void gso_forward64(int64_t n, int sh_degree, const float *means, const float *scales, const float *quats,
+                   const float *opacities, const float *shs, const gso_camera *cam,
+                   double *mu, double *M, double *sig, double *rgb);
+
+/* fp64 composite adjoint at a GIVEN payload (mu, M, sig, rgb as doubles: the fp32 payload widened, or gso_forward64's),
+ * with the fp32 forward's discrete decisions (bbs, lists, near/far when tps != NULL, early-out rule).  All outputs are
+ * [n,10] in the device row's layout [dr dg db S0 Sx Sy Sxx Sxy - Syy] (slot 8 unused) and ACCUMULATE:
+ *   rows     the colour gradient and the raw moments of dL/d(log alpha);
+ *   mass     error mass: a correct fp32 evaluation differs from rows by at most kappa * 2^-24 * mass + floor_;
+ *   dropped  sum |term| of what a kernel may legitimately omit whole (alpha below 2^-27);
+ *   floor_   absolute allowance for fp32 underflow;
+ *   ntiles   [n] tiles in which at least one pixel takes the gaussian.
+ * See gs_oracle.c for the definition of the mass. */
+void gso_composite_rows(const gso_camera *cam, int tile, int gx, int gy, const uint32_t *ranges, const uint32_t *ids,
+                        int64_t n, const double *mu, const double *M, const float *bbs, const double *sig,
+                        const double *rgb, const float *tps, float t_min, const float *dC,
+                        double *rows, double *mass, double *dropped, double *floor_, int32_t *ntiles);
+
+/* The fp32 twin of the above: the same adjoint in float, in the HIP kernel's formulation and order of operations
+ * (tile == 16 only).  rows[n,10] float, ACCUMULATES.  Measures kappa_ref on the CPU. */
+void gso_composite_rows_f32(const gso_camera *cam, int tile, int gx, int gy, const uint32_t *ranges, const uint32_t *ids,
+                            int64_t n, const float *mu, const float *invcov, const float *bbs, const float *sig,
+                            const float *rgb, const float *tps, float t_min, const float *dC, float *rows);
+
+/* Parameter gradients of caller-supplied rows[n,10] (bwd64 per gaussian; linear in the rows; ACCUMULATES).
+ * raw != 0: device rows (raw moments), converted with the fp64 sig and conic; raw == 0: gso_backward's g2d. */
+void gso_chain(int64_t n, int sh_degree, const float *means, const float *scales, const float *quats,
+               const float *opacities, const float *shs, const gso_camera *cam, const double *rows, int raw,
+               double *dmeans, double *dscales, double *dquats, double *dopac, double *dshs);
+
+/* The SH colour path of the backward (fp32 in the kernels) at a given d rgb [n,3]: d_shs [n,3K] = basis (x) d rgb and
+ * dpc [n,3] = d L / d tps[0:3] through the colour, in fp64, with an error mass per output float (units of the value:
+ * a correct fp32 evaluation differs by at most kappa * 2^-24 * mass); and its fp32 twin.  Outputs are overwritten. */
+void gso_sh_path(int64_t n, int sh_degree, const float *means, const float *shs, const gso_camera *cam, const double *drgb,
+                 double *dshs, double *mass_shs, double *dpc, double *mass_dpc);
+void gso_sh_path_f32(int64_t n, int sh_degree, const float *means, const float *shs, const gso_camera *cam, const float *drgb,
+                     float *dshs, float *dpc);
+
+/* the absolute underflow allowance per term (2^-120) that floor_ is built from and the SH path's bound adds */
+double gso_floor_unit(void);
+
 int gso_num_threads(void);
 
 #ifdef __cplusplus

@@ -60,6 +60,15 @@ def lib(omp: bool = False):
         L.gso_backward2d.argtypes = ([C.c_int64] + [fp] * 5 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u32p, u32p, C.c_float, fp]
                                      + [dp] * 6)
         L.gso_num_threads.restype = C.c_int
+        i32p = C.POINTER(C.c_int32)
+        L.gso_forward64.argtypes = [C.c_int64, C.c_int] + [fp] * 5 + [C.POINTER(Camera)] + [dp] * 4
+        L.gso_composite_rows.argtypes = ([C.POINTER(Camera), C.c_int, C.c_int, C.c_int, u32p, u32p, C.c_int64, dp, dp, fp, dp, dp, fp,
+                                          C.c_float, fp] + [dp] * 4 + [i32p])
+        L.gso_composite_rows_f32.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_int, u32p, u32p, C.c_int64] + [fp] * 6 + [C.c_float, fp, fp]
+        L.gso_floor_unit.restype = C.c_double; L.gso_floor_unit.argtypes = []
+        L.gso_sh_path.argtypes = [C.c_int64, C.c_int, fp, fp, C.POINTER(Camera)] + [dp] * 5
+        L.gso_sh_path_f32.argtypes = [C.c_int64, C.c_int, fp, fp, C.POINTER(Camera)] + [fp] * 3
+        L.gso_chain.argtypes = [C.c_int64, C.c_int] + [fp] * 5 + [C.POINTER(Camera), dp, C.c_int] + [dp] * 5
         _libs[key] = L
     return _libs[key]
 
@@ -242,3 +251,94 @@ def backward2d(means, scales, rots, opacities, colors, W, H, ranges, ids, dC, ti
                             _p(ranges, C.c_uint32), _p(ids, C.c_uint32), C.c_float(t_min), _fp(dC),
                             *(g[k].ctypes.data_as(dp) for k in ("means", "scales", "rots", "opacities", "colors", "g2d")))
     return g
+
+
+# ---------------------------------------------------------------- per-gaussian reference of the composite backward
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def forward64(means, scales, quats, opacities, shs, sh_degree, cam: Camera, omp=False) -> dict:
+    """The fp64 forward's payload: mu[n,2], M[n,4], sig[n], rgb[n,3] (float64)."""
+    means, scales, quats, shs = (_c32(a) for a in (means, scales, quats, shs))
+    opac = _c32(opacities).reshape(-1)
+    n = means.shape[0]
+    o = dict(mu=np.zeros((n, 2)), M=np.zeros((n, 4)), sig=np.zeros(n), rgb=np.zeros((n, 3)))
+    lib(omp).gso_forward64(n, sh_degree, _fp(means), _fp(scales), _fp(quats), _fp(opac), _fp(shs), C.byref(cam),
+                           *(_dp(o[k]) for k in ("mu", "M", "sig", "rgb")))
+    return o
+
+
+def _lists(ranges, ids):
+    ranges = np.ascontiguousarray(ranges, np.uint32)
+    ids = np.ascontiguousarray(ids, np.uint32) if len(ids) else np.zeros(1, np.uint32)
+    return ranges, ids
+
+
+def composite_rows(pay, bbs, tps, ranges, ids, cam: Camera, dC, tile=16, t_min=0.0, omp=False) -> dict:
+    """fp64 composite adjoint at the payload `pay` (mu, M or invcov, sig, rgb: any float type, widened to float64); tps None:
+    the 2-D renderer.  -> rows, mass, dropped, floor [n,10] in the device row's layout, ntiles [n]."""
+    mu = np.ascontiguousarray(pay["mu"], np.float64)
+    M = np.ascontiguousarray(pay["M"] if "M" in pay else pay["invcov"], np.float64)
+    sig = np.ascontiguousarray(pay["sig"], np.float64).reshape(-1)
+    rgb = np.ascontiguousarray(pay["rgb"], np.float64)
+    n = mu.shape[0]
+    bbs = _c32(bbs); tps = None if tps is None else _c32(tps); dC = _c32(dC)
+    ranges, ids = _lists(ranges, ids)
+    gx, gy = (cam.W + tile - 1) // tile, (cam.H + tile - 1) // tile
+    o = dict(rows=np.zeros((n, 10)), mass=np.zeros((n, 10)), dropped=np.zeros((n, 10)), floor=np.zeros((n, 10)),
+             ntiles=np.zeros(n, np.int32))
+    lib(omp).gso_composite_rows(C.byref(cam), tile, gx, gy, _p(ranges, C.c_uint32), _p(ids, C.c_uint32), n, _dp(mu), _dp(M), _fp(bbs),
+                                _dp(sig), _dp(rgb), _fp(tps), C.c_float(t_min), _fp(dC),
+                                *(_dp(o[k]) for k in ("rows", "mass", "dropped", "floor")), _p(o["ntiles"], C.c_int32))
+    return o
+
+
+def composite_rows_f32(pre, ranges, ids, cam: Camera, dC, t_min=0.0, use_tps=True, omp=False) -> np.ndarray:
+    """The fp32 twin of composite_rows at the fp32 payload `pre` (preprocess / preprocess2d) -> rows [n,10] float32."""
+    n = pre["mu"].shape[0]
+    ranges, ids = _lists(ranges, ids)
+    dC = _c32(dC)
+    gx, gy = (cam.W + 15) // 16, (cam.H + 15) // 16
+    rows = np.zeros((n, 10), np.float32)
+    lib(omp).gso_composite_rows_f32(C.byref(cam), 16, gx, gy, _p(ranges, C.c_uint32), _p(ids, C.c_uint32), n, _fp(_c32(pre["mu"])),
+                                    _fp(_c32(pre["invcov"])), _fp(_c32(pre["bbs"])), _fp(_c32(pre["sig"])), _fp(_c32(pre["rgb"])),
+                                    _fp(_c32(pre["tps"])) if use_tps else None, C.c_float(t_min), _fp(dC), _fp(rows))
+    return rows
+
+
+def chain(means, scales, quats, opacities, shs, sh_degree, cam: Camera, rows, raw=True, omp=False) -> dict:
+    """Parameter gradients (float64) of rows [n,10]: device rows (raw=True) or gso_backward's g2d (raw=False)."""
+    means, scales, quats, shs = (_c32(a) for a in (means, scales, quats, shs))
+    opac = _c32(opacities).reshape(-1)
+    n = means.shape[0]
+    rows = np.ascontiguousarray(rows, np.float64)
+    g = dict(means=np.zeros((n, 3)), scales=np.zeros((n, 3)), quats=np.zeros((n, 4)), opacities=np.zeros(n), shs=np.zeros(shs.shape))
+    lib(omp).gso_chain(n, sh_degree, _fp(means), _fp(scales), _fp(quats), _fp(opac), _fp(shs), C.byref(cam), _dp(rows), int(bool(raw)),
+                       *(_dp(g[k]) for k in ("means", "scales", "quats", "opacities", "shs")))
+    return g
+
+
+def sh_path(means, shs, sh_degree, cam: Camera, drgb, omp=False) -> dict:
+    """The backward's SH colour path at d rgb [n,3] in fp64: dshs [n,3K], dpc [n,3] and their error masses."""
+    means, shs = _c32(means), _c32(shs)
+    n, K3 = means.shape[0], 3 * (sh_degree + 1) ** 2
+    drgb = np.ascontiguousarray(drgb, np.float64)
+    o = dict(dshs=np.zeros((n, K3)), mass_shs=np.zeros((n, K3)), dpc=np.zeros((n, 3)), mass_dpc=np.zeros((n, 3)))
+    lib(omp).gso_sh_path(n, sh_degree, _fp(means), _fp(shs), C.byref(cam), _dp(drgb), *(_dp(o[k]) for k in ("dshs", "mass_shs", "dpc", "mass_dpc")))
+    return o
+
+
+def sh_path_f32(means, shs, sh_degree, cam: Camera, drgb, omp=False) -> dict:
+    """The fp32 twin of sh_path (the kernel's statements in float)."""
+    means, shs, drgb = _c32(means), _c32(shs), _c32(drgb)
+    n, K3 = means.shape[0], 3 * (sh_degree + 1) ** 2
+    o = dict(dshs=np.zeros((n, K3), np.float32), dpc=np.zeros((n, 3), np.float32))
+    lib(omp).gso_sh_path_f32(n, sh_degree, _fp(means), _fp(shs), C.byref(cam), _fp(drgb), _fp(o["dshs"]), _fp(o["dpc"]))
+    return o
+
+
+def floor_unit() -> float:
+    """the underflow allowance per term (2^-120) shared by the composite floor and the SH path's bound"""
+    return float(lib().gso_floor_unit())
