@@ -193,13 +193,9 @@ extern "C" int gs_adam_step(gs_ctx *c, const gs_grads *grads, const gs_grads *ex
                             float beta1, float beta2, float eps, int64_t step, int flags) {
     if (!c) return GS_ERR_INVALID;
     if (!grads || !exp_avg || !exp_avg_sq) return fail(c, GS_ERR_INVALID, "gs_adam_step: NULL argument");
-    const float *p[5] = {c->means, c->scales, c->quats, c->opac, c->shs};
-    const float *g[5] = {grads->d_means, grads->d_scales, grads->d_quats, grads->d_opacities, grads->d_shs};
-    float *m[5] = {exp_avg->d_means, exp_avg->d_scales, exp_avg->d_quats, exp_avg->d_opacities, exp_avg->d_shs};
-    float *v[5] = {exp_avg_sq->d_means, exp_avg_sq->d_scales, exp_avg_sq->d_quats, exp_avg_sq->d_opacities, exp_avg_sq->d_shs};
+    const Five<float> p = c->model5_mut(), g = five(*grads), m = five(*exp_avg), v = five(*exp_avg_sq);
     AdamArgs a{};
-    const int rc = gs_adam_prepare(c, "gs_adam_step", p, g, m, v, lr, beta1, beta2, eps, step, flags, &a.h);
-    if (rc != GS_OK) return rc;
+    if (const int rc = gs_adam_prepare(c, "gs_adam_step", p.p, g.p, m.p, v.p, lr, beta1, beta2, eps, step, flags, &a.h)) return rc;
     if (bind_device(c)) return GS_ERR_HIP;
     const int64_t n = c->n;
     int64_t most = 0;
@@ -207,7 +203,7 @@ extern "C" int gs_adam_step(gs_ctx *c, const gs_grads *grads, const gs_grads *ex
     for (int i = 0; i < 5; ++i) {
         if (!g[i] || n <= 0) continue;
         AdamSeg &s = a.seg[a.nseg++];
-        s.p = const_cast<float *>(p[i]); s.g = g[i]; s.m = m[i]; s.v = v[i];
+        s.p = p[i]; s.g = g[i]; s.m = m[i]; s.v = v[i];
         s.w = (int)c->width[i]; s.len = (int64_t)s.w * n;
         s.sh = i == 4; s.ss = a.h.step_size[i < 4 ? i : 4];
         s.vec = ((reinterpret_cast<uintptr_t>(s.p) | reinterpret_cast<uintptr_t>(s.g) | reinterpret_cast<uintptr_t>(s.m) |
@@ -228,6 +224,6 @@ extern "C" int gs_adam_step(gs_ctx *c, const gs_grads *grads, const gs_grads *ex
         }
         HIPCHK(c, hipGetLastError());
     }
-    c->did_pre = c->did_bin = c->did_fwd = c->did_bwd = false;       // the model changed
+    c->inputs_changed();
     return GS_OK;
 }

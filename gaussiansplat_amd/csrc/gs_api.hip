@@ -78,13 +78,12 @@ int gs_create(gs_ctx **out, int device, const gs_config *cfg) {
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->wave_slots = prop.multiProcessorCount * 4 * 5;
         else (void)hipGetLastError();
     }
-    if ((e = hipHostMalloc((void **)&c->pinned, sizeof(PinnedWords), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return hipfail(nullptr, e, "hipHostMalloc"); }
+    if ((e = hipHostMalloc((void **)&c->pinned, sizeof(PinnedWords), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess) { delete c; return hipfail(nullptr, e, "hipHostMalloc"); }
     if ((e = hipHostMalloc((void **)&c->pinned_split, sizeof(uint32_t) * 2 * (GS_MAX_VIEW_SLOTS + 1), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess) {
         (void)hipGetLastError(); c->pinned_split = nullptr;              // (speed only: without it every order counts as "may hold split tiles")
     } else std::memset(c->pinned_split, 0, sizeof(uint32_t) * 2 * (GS_MAX_VIEW_SLOTS + 1));
-    for (int s = 0; s < GS_STAGE_COUNT; ++s)
-        for (int k = 0; k < 2; ++k)
-            if ((e = hipEventCreate(&c->ev[s][k])) != hipSuccess) { delete c; return hipfail(nullptr, e, "hipEventCreate"); }
+    for (auto &pair : c->ev)
+        for (hipEvent_t &ev : pair) if ((e = hipEventCreate(&ev)) != hipSuccess) { delete c; return hipfail(nullptr, e, "hipEventCreate"); }
     if ((e = hipEventCreateWithFlags(&c->ev_count, hipEventDisableTiming | hipEventReleaseToSystem)) != hipSuccess) { delete c; return hipfail(nullptr, e, "hipEventCreate"); }
     if ((e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking)) != hipSuccess) { delete c; return hipfail(nullptr, e, "hipStreamCreate"); }
     for (hipEvent_t *ev : {&c->ev_main, &c->ev_order})
@@ -93,7 +92,7 @@ int gs_create(gs_ctx **out, int device, const gs_config *cfg) {
         // The one-instruction stable rank (ds_add_rtn pre-values in ascending lane order) is a measured property of
         // gfx950's LDS, not an architectural guarantee: check it on THIS device before relying on it; ballots otherwise.
         int bad = 0;
-        if ((e = gs_probe_lds_atomic_order(c->stream, &bad)) != hipSuccess) { (void)gs_destroy(c); return hipfail(nullptr, e, "gs_probe_lds_atomic_order"); }
+        if ((e = gs_probe_lds_atomic_order(c->stream, &bad)) != hipSuccess) { delete c; return hipfail(nullptr, e, "gs_probe_lds_atomic_order"); }
         c->rank_probe = bad ? 1 : 0;
         if (bad) c->cfg.rank_mode = 1;
     }
@@ -106,29 +105,6 @@ int gs_destroy(gs_ctx *c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     if (c->side) (void)hipStreamSynchronize(c->side);
-    comm_release(c);
-    DevBuf *bufs[] = {&c->payload, &c->depth_key, &c->rect, &c->pairs_a, &c->pairs_b, &c->perm, &c->offsets, &c->block_sums,
-                      &c->inst_a, &c->inst_b, &c->table, &c->digit_total, &c->ranges, &c->image, &c->trans, &c->g2d, &c->stage_in,
-                      &c->counters, &c->snap, &c->snap_walked, &c->grads_flat, &c->dpc, &c->ids, &c->words, &c->cs, &c->diff,
-                      &c->tile_work, &c->tile_clock,
-                      &c->tile_pos, &c->tile_done, &c->live2d, &c->rect_r, &c->offsets_r, &c->live_total,
-                      &c->rect_sorted, &c->l1_table, &c->l1_rows, &c->l1_partials, &c->cids, &c->clr, &c->cranges, &c->segcnt, &c->sdone, &c->tilecnt,
-                      &c->ranges_r[0], &c->ranges_r[1], &c->ranges_r[2], &c->ranges_r[3],
-                      &c->invcov, &c->loss_maps, &c->loss_acc, &c->loss_in[0], &c->loss_in[1], &c->loss_dc, &c->view_cams, &c->touched_cnt, &c->touched_off, &c->touched_zero, &c->tile_dead, &c->key_range, &c->tile_walked, &c->tile_walked_b, &c->tile_work_b};
-    for (DevBuf *b : bufs) b->release();
-    for (auto &v : c->slots) { v.order[0].release(); v.order[1].release(); v.walkbuf[0].release(); v.walkbuf[1].release(); }
-    for (DevBuf *b : {&c->tile_nopen, &c->smax, &c->tile_ext, &c->zero_tiles}) b->release();
-    for (auto &b : c->model) b.release();
-    for (auto &b : c->dbg) b.release();
-    for (int s = 0; s < GS_STAGE_COUNT; ++s)
-        for (int k = 0; k < 2; ++k)
-            if (c->ev[s][k]) (void)hipEventDestroy(c->ev[s][k]);
-    if (c->ev_count) (void)hipEventDestroy(c->ev_count);
-    for (hipEvent_t ev : {c->ev_main, c->ev_order}) if (ev) (void)hipEventDestroy(ev);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    if (c->pinned_split) (void)hipHostFree(c->pinned_split);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return GS_OK;
 }
@@ -155,6 +131,26 @@ int gs_synchronize(gs_ctx *c) {
     return GS_OK;
 }
 
+// the five arrays of a model become the ctx's: copied into its own buffers (host arrays) or borrowed (device arrays)
+static int adopt_model(gs_ctx *c, int64_t n, int sh_degree, int kind, const float *const src[5], const size_t (&width)[5], int mem) {
+    if (bind_device(c)) return GS_ERR_HIP;
+    const float *dst[5];
+    for (int i = 0; i < 5; ++i) {
+        dst[i] = src[i];
+        if (mem != GS_MEM_HOST) continue;
+        const size_t bytes = sizeof(float) * width[i] * (size_t)n;
+        HIPCHK(c, c->model[i].ensure(bytes ? bytes : 4));
+        if (bytes) HIPCHK(c, hipMemcpyAsync(c->model[i].p, src[i], bytes, hipMemcpyHostToDevice, c->stream));
+        dst[i] = c->model[i].as<float>();
+    }
+    if (mem == GS_MEM_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));            // caller may free its host arrays on return
+    c->n = n; c->sh_degree = sh_degree; c->kind = kind;
+    for (int i = 0; i < 5; ++i) c->width[i] = width[i];
+    c->set_model5(dst);
+    c->inputs_changed();
+    return GS_OK;
+}
+
 int gs_set_model(gs_ctx *c, int64_t n, int sh_degree, const float *means, const float *scales, const float *quats,
                  const float *opacities, const float *shs, int mem) {
     if (!c) return GS_ERR_INVALID;
@@ -162,27 +158,9 @@ int gs_set_model(gs_ctx *c, int64_t n, int sh_degree, const float *means, const 
     if (sh_degree < 0 || sh_degree > 3) return fail(c, GS_ERR_UNSUPPORTED, "gs_set_model: sh_degree must be 0..3");
     if (n > 0 && (!means || !scales || !quats || !opacities || !shs)) return fail(c, GS_ERR_INVALID, "gs_set_model: NULL array");
     if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(c, GS_ERR_INVALID, "gs_set_model: bad mem");
-    if (bind_device(c)) return GS_ERR_HIP;
     const int K = (sh_degree + 1) * (sh_degree + 1);
     const float *src[5] = {means, scales, quats, opacities, shs};
-    const size_t width[5] = {3, 3, 4, 1, (size_t)3 * K};
-    const float *dst[5];
-    if (mem == GS_MEM_HOST) {
-        for (int i = 0; i < 5; ++i) {
-            const size_t bytes = sizeof(float) * width[i] * (size_t)n;
-            HIPCHK(c, c->model[i].ensure(bytes ? bytes : 4));
-            if (bytes) HIPCHK(c, hipMemcpyAsync(c->model[i].p, src[i], bytes, hipMemcpyHostToDevice, c->stream));
-            dst[i] = c->model[i].as<float>();
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));            // caller may free its host arrays on return
-    } else {
-        for (int i = 0; i < 5; ++i) dst[i] = src[i];
-    }
-    c->n = n; c->sh_degree = sh_degree; c->kind = 0;
-    for (int i = 0; i < 5; ++i) c->width[i] = width[i];
-    c->means = dst[0]; c->scales = dst[1]; c->quats = dst[2]; c->opac = dst[3]; c->shs = dst[4];
-    c->did_pre = c->did_bin = c->did_fwd = c->did_bwd = false;
-    return GS_OK;
+    return adopt_model(c, n, sh_degree, 0, src, {3, 3, 4, 1, (size_t)3 * K}, mem);
 }
 
 int gs_set_model_2d(gs_ctx *c, int64_t n, const float *means, const float *scales, const float *rotations,
@@ -191,26 +169,8 @@ int gs_set_model_2d(gs_ctx *c, int64_t n, const float *means, const float *scale
     if (n < 0 || n > 0x7FFFFFF0LL) return fail(c, GS_ERR_INVALID, "gs_set_model_2d: n out of range");
     if (n > 0 && (!means || !scales || !rotations || !opacities || !colors)) return fail(c, GS_ERR_INVALID, "gs_set_model_2d: NULL array");
     if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(c, GS_ERR_INVALID, "gs_set_model_2d: bad mem");
-    if (bind_device(c)) return GS_ERR_HIP;
     const float *src[5] = {means, scales, rotations, opacities, colors};
-    const size_t width[5] = {2, 2, 1, 1, 3};
-    const float *dst[5];
-    if (mem == GS_MEM_HOST) {
-        for (int i = 0; i < 5; ++i) {
-            const size_t bytes = sizeof(float) * width[i] * (size_t)n;
-            HIPCHK(c, c->model[i].ensure(bytes ? bytes : 4));
-            if (bytes) HIPCHK(c, hipMemcpyAsync(c->model[i].p, src[i], bytes, hipMemcpyHostToDevice, c->stream));
-            dst[i] = c->model[i].as<float>();
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else {
-        for (int i = 0; i < 5; ++i) dst[i] = src[i];
-    }
-    c->n = n; c->sh_degree = 0; c->kind = 1;
-    for (int i = 0; i < 5; ++i) c->width[i] = width[i];
-    c->means = dst[0]; c->scales = dst[1]; c->quats = dst[2]; c->opac = dst[3]; c->shs = dst[4];
-    c->did_pre = c->did_bin = c->did_fwd = c->did_bwd = false;
-    return GS_OK;
+    return adopt_model(c, n, 0, 1, src, {2, 2, 1, 1, 3}, mem);
 }
 
 int gs_set_image_size(gs_ctx *c, int32_t W, int32_t H) {
@@ -222,7 +182,7 @@ int gs_set_image_size(gs_ctx *c, int32_t W, int32_t H) {
     }
     c->cam.W = W; c->cam.H = H;
     c->have_cam = true;
-    c->did_pre = c->did_bin = c->did_fwd = c->did_bwd = false;
+    c->inputs_changed();
     return GS_OK;
 }
 
@@ -237,7 +197,7 @@ int gs_set_camera(gs_ctx *c, const float T[16], const float P[16], float fx, flo
     for (int i = 0; i < 3; ++i) { c->cam.eye[i] = eye[i]; c->cam.lookAt[i] = lookAt[i]; }
     c->cam.W = W; c->cam.H = H;
     c->have_cam = true;
-    c->did_pre = c->did_bin = c->did_fwd = c->did_bwd = false;
+    c->inputs_changed();
     return GS_OK;
 }
 
@@ -267,11 +227,9 @@ int gs_preprocess(gs_ctx *c) {
             a2.dbg.mu = c->dbg[2].as<float>(); a2.dbg.cov2d = c->dbg[4].as<float>(); a2.dbg.invcov = c->dbg[5].as<float>();
             a2.dbg.bbs = c->dbg[6].as<float>();
         }
-        {
-            StageTimer t(c, GS_STAGE_PREPROCESS);
-            HIPCHK(c, gs_launch_preprocess2d(a2, c->stream));
-        }
-        c->did_pre = true; c->did_bin = c->did_fwd = c->did_bwd = false;
+        StageTimer t(c, GS_STAGE_PREPROCESS);
+        HIPCHK(c, gs_launch_preprocess2d(a2, c->stream));
+        c->reach(gs_ctx::Stage::PREPROCESSED);
         return GS_OK;
     }
     GsPreprocessArgs a{};
@@ -301,11 +259,9 @@ int gs_preprocess(gs_ctx *c) {
         a.dbg.cov3d = c->dbg[3].as<float>(); a.dbg.cov2d = c->dbg[4].as<float>(); a.dbg.invcov = c->dbg[5].as<float>();
         a.dbg.bbs = c->dbg[6].as<float>();
     }
-    {
-        StageTimer t(c, GS_STAGE_PREPROCESS);
-        HIPCHK(c, gs_launch_preprocess(a, c->cam, c->stream));
-    }
-    c->did_pre = true; c->did_bin = c->did_fwd = c->did_bwd = false;
+    StageTimer t(c, GS_STAGE_PREPROCESS);
+    HIPCHK(c, gs_launch_preprocess(a, c->cam, c->stream));
+    c->reach(gs_ctx::Stage::PREPROCESSED);
     return GS_OK;
 }
 
@@ -354,12 +310,9 @@ int gs_sgd_step(gs_ctx *c, float lr, const gs_grads *g) {
     if (!c || !g) return GS_ERR_INVALID;
     if (bind_device(c)) return GS_ERR_HIP;
     const size_t n = (size_t)c->n;
-    float *p[5] = {const_cast<float *>(c->means), const_cast<float *>(c->scales), const_cast<float *>(c->quats),
-                   const_cast<float *>(c->opac), const_cast<float *>(c->shs)};
-    const float *gr[5] = {g->d_means, g->d_scales, g->d_quats, g->d_opacities, g->d_shs};
-    const size_t *w = c->width;
-    for (int i = 0; i < 5; ++i) HIPCHK(c, gs_launch_sgd(p[i], gr[i], lr, w[i] * n, c->stream));
-    c->did_pre = c->did_bin = c->did_fwd = c->did_bwd = false;       // the model changed
+    const Five<float> p = c->model5_mut(), gr = five(*g);
+    for (int i = 0; i < 5; ++i) HIPCHK(c, gs_launch_sgd(p[i], gr[i], lr, c->width[i] * n, c->stream));
+    c->inputs_changed();
     return GS_OK;
 }
 
@@ -367,7 +320,7 @@ int gs_reset_grads(gs_ctx *c, const gs_grads *g) {
     if (!c || !g) return GS_ERR_INVALID;
     if (bind_device(c)) return GS_ERR_HIP;
     const size_t n = (size_t)c->n;
-    float *p[5] = {g->d_means, g->d_scales, g->d_quats, g->d_opacities, g->d_shs};
+    const Five<float> p = five(*g);
     for (int i = 0; i < 5; ++i)
         if (p[i] && n) HIPCHK(c, hipMemsetAsync(p[i], 0, sizeof(float) * c->width[i] * n, c->stream));
     return GS_OK;
@@ -391,11 +344,10 @@ int gs_grads_read(gs_ctx *c, const gs_grads *g, float *h_means, float *h_scales,
     if (!c || !g) return GS_ERR_INVALID;
     if (bind_device(c)) return GS_ERR_HIP;
     const size_t n = (size_t)c->n;
-    const float *src[5] = {g->d_means, g->d_scales, g->d_quats, g->d_opacities, g->d_shs};
+    const Five<float> src = five(*g);
     float *dst[5] = {h_means, h_scales, h_quats, h_opacities, h_shs};
-    const size_t *w = c->width;
     for (int i = 0; i < 5; ++i)
-        if (dst[i] && src[i] && n) HIPCHK(c, hipMemcpyAsync(dst[i], src[i], sizeof(float) * w[i] * n, hipMemcpyDeviceToHost, c->stream));
+        if (dst[i] && src[i] && n) HIPCHK(c, hipMemcpyAsync(dst[i], src[i], sizeof(float) * c->width[i] * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return GS_OK;
 }

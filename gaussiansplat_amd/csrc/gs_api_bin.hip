@@ -291,7 +291,7 @@ int settle_totals(gs_ctx *c, bool *redo, bool may_relist) {
     if (!c->spec_lists) return GS_OK;
     c->spec_lists = false;
     if ((size_t)coarse <= c->spec_cap_coarse && (size_t)fine_slab <= c->spec_cap_fine) return GS_OK;
-    if (!may_relist) { c->did_bin = false; return GS_OK; }                  // the frame is being abandoned (a new gs_preprocess / gs_bin follows)
+    if (!may_relist) { c->fall_back(gs_ctx::Stage::PREPROCESSED); return GS_OK; }                  // the frame is being abandoned (a new gs_preprocess / gs_bin follows)
     // a list outgrew its buffer: nothing was listed (all ranges empty).  Grow and list again with the real totals -- in FULL: the caps'
     // source is the slot's walked array, and the forward that just ran on the empty lists has overwritten it with zeros (rare frame:
     // a model that outgrew its buffers; full lists are the fast choice there)
@@ -474,13 +474,13 @@ static int bin_frame(gs_ctx *c) {
     HIPCHK(c, c->counters.ensure(GS_COUNTER_BYTES));
     if (path != Path::SMALL) HIPCHK(c, c->block_sums.ensure(sizeof(uint32_t) * 3 * ((size_t)c->n / 2048 + 2)));
     if (int rc = path == Path::SMALL ? bin_small(c) : path == Path::TWO_LEVEL ? bin_two_level(c) : bin_radix(c)) return rc;
-    c->did_bin = true; c->did_fwd = c->did_bwd = false;
+    c->reach(gs_ctx::Stage::BINNED);
     return GS_OK;
 }
 
 extern "C" int gs_bin(gs_ctx *c, int32_t gx, int32_t gy) {
     if (!c) return GS_ERR_INVALID;
-    if (!c->did_pre) return fail(c, GS_ERR_INVALID, "gs_bin: gs_preprocess first");
+    if (c->stage < gs_ctx::Stage::PREPROCESSED) return fail(c, GS_ERR_INVALID, "gs_bin: gs_preprocess first");
     if ((gx != 0 || gy != 0) && (gx != c->gx || gy != c->gy))
         return fail(c, GS_ERR_UNSUPPORTED, "gs_bin: blocks must equal ceil(W/16) x ceil(H/16)");
     if (bind_device(c)) return GS_ERR_HIP;

@@ -69,7 +69,7 @@ int gs_allreduce_grads(gs_ctx *c, const gs_grads *g) {
     if (!c->comm) return fail(c, GS_ERR_INVALID, "gs_allreduce_grads: gs_comm_init first");
     if (bind_device(c)) return GS_ERR_HIP;
     const size_t n = (size_t)c->n;
-    float *p[5] = {g->d_means, g->d_scales, g->d_quats, g->d_opacities, g->d_shs};
+    const Five<float> p = five(*g);
     const size_t w[5] = {c->width[0] * n, c->width[1] * n, c->width[2] * n, c->width[3] * n, c->width[4] * n};
     bool flat = p[0] != nullptr;
     for (int i = 0; i + 1 < 5 && flat; ++i) flat = p[i + 1] == p[i] + w[i];

@@ -3,6 +3,9 @@
 #include "gs_ctx.h"
 
 using Snap = gs_ctx::FramePlan::Snap;
+using Stage = gs_ctx::Stage;
+using BackwardPlan = gs_ctx::BackwardPlan;
+using Update = BackwardPlan::Update;
 
 // Launch order of the frame's forward (gs_config.schedule 3 / 4): what the last forward under the same view slot measured, else
 // (schedule 4) what this ctx's previous slot-less forward measured; null = no history: tile order.  *split: the order's split-count word.
@@ -149,7 +152,7 @@ int gs_bind_outputs(gs_ctx *c, float *image, float *transmittance) {
     if (!c) return GS_ERR_INVALID;
     if ((image == nullptr) != (transmittance == nullptr)) return fail(c, GS_ERR_INVALID, "gs_bind_outputs: bind both buffers or neither");
     c->bound_image = image; c->bound_trans = transmittance;
-    c->did_fwd = c->did_bwd = false;                                      // the forward's result lives in the buffers bound at its time
+    c->fall_back(Stage::BINNED);                                          // the forward's result lives in the buffers bound at its time
     return GS_OK;
 }
 
@@ -184,7 +187,7 @@ static int enqueue_forward_round(gs_ctx *c, int r) {
 
 int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
     if (!c) return GS_ERR_INVALID;
-    if (!c->did_bin) return fail(c, GS_ERR_INVALID, "gs_forward: gs_bin first");
+    if (c->stage < Stage::BINNED) return fail(c, GS_ERR_INVALID, "gs_forward: gs_bin first");
     if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(c, GS_ERR_INVALID, "gs_forward: bad mem");
     if (bind_device(c)) return GS_ERR_HIP;
     const size_t px = (size_t)c->cam.W * c->cam.H;
@@ -223,10 +226,10 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
     // composite backward.  Plain stores: the backward's atomics must find the rows where the in-line fill leaves them.
     // Why the rows may be cleared HERE: nothing reads a frame's g2d after the next gs_forward of the ctx.  Its readers are the composite
     // backward and the per-gaussian kernels of gs_backward (both renderers), gs_color_grads_pack and gs_get_array(GS_ARR_GRAD2D); all of
-    // them ask for did_bwd or did_bwd_composite (GS_BWD_PARAMS_ONLY), which this call resets below (and gs_bin before it), and all of them
-    // run on c->stream, in front of this launch.  Only when the buffer stands as the coming backward will want it (same n, same mode:
-    // DevBuf never shrinks, so its ensure() will not move it) and is not clean already; a ctx's first frame, a ctx that only renders and a
-    // model that grew keep the fill command in backward_impl.
+    // them ask for Stage::COMPOSITE_ADJOINT, which this call takes back below (reach(RENDERED); gs_bin, gs_preprocess and gs_bind_outputs
+    // fall back further), and all of them run on c->stream, in front of this launch.  Only when the buffer stands as the coming backward
+    // will want it (same n, same mode: DevBuf never shrinks, so its ensure() will not move it) and is not clean already; a ctx's first
+    // frame, a ctx that only renders and a model that grew keep the fill command in run_backward.
     c->fwd_fills_g2d = c->tail_fill() && !c->g2d_clean && c->g2d.p && c->g2d.cap >= c->g2d_bytes() &&
                        gs_composite_fill_blocks(c->g2d.p, c->g2d_bytes()) > 0;
     for (int r = 0; r < R; ++r) {
@@ -246,95 +249,66 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
     if (image && image != c->img()) HIPCHK(c, hipMemcpyAsync(image, c->img(), sizeof(float) * 3 * px, kind, c->stream));
     if (transmittance && transmittance != c->tr()) HIPCHK(c, hipMemcpyAsync(transmittance, c->tr(), sizeof(float) * px, kind, c->stream));
     if (mem == GS_MEM_HOST && (image || transmittance)) HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->did_fwd = true; c->did_bwd = false; c->did_bwd_composite = false;
+    c->reach(Stage::RENDERED);
     c->prev_counters_valid = true; c->prev_n_inst = c->n_inst;
     return GS_OK;
 }
 
-int gs_backward(gs_ctx *c, const float *dC, int mem, const gs_grads *grads) { return gs_backward_ex(c, dC, mem, grads, 0); }
-
-static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *grads, int flags, float sgd_scale,
-                         const GsAdamFused *adam = nullptr, int adam_mode = 0);
-int gs_backward_ex(gs_ctx *c, const float *dC, int mem, const gs_grads *grads, int flags) { return backward_impl(c, dC, mem, grads, flags, 0.0f); }
-
-// backward + SGD in one pass: the per-gaussian kernels apply param = fma(-lr, gradient, param) to the resident model instead
-// of storing the gradient (the same fma gs_sgd_step applies to the stored float): one read-modify-write of the parameters
-// instead of gradient write + gradient read + parameter read-modify-write.  Single-view steps only (nothing is accumulated).
-int gs_backward_sgd(gs_ctx *c, const float *dC, int mem, float lr) {
+// What this call of the backward family runs: decided HERE, once, from the flags, the update its entry point names in `p` (none: by
+// GS_BWD_OVERWRITE), the renderer and how far the frame has come.  Every refusal of the family is made here, and nothing is enqueued or
+// allocated: a refused call leaves the frame and every buffer as they were.  grads null with a fused update: the targets are the model.
+static int plan_backward(gs_ctx *c, const float *dC, int mem, const gs_grads *grads, int flags, BackwardPlan &p) {
     if (!c) return GS_ERR_INVALID;
-    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_backward_sgd: 3-D renderer only");
-    if (!(lr != 0.0f)) return fail(c, GS_ERR_INVALID, "gs_backward_sgd: lr must be non-zero");
-    gs_grads g{const_cast<float *>(c->means), const_cast<float *>(c->scales), const_cast<float *>(c->quats),
-               const_cast<float *>(c->opac), const_cast<float *>(c->shs)};
-    const int rc = backward_impl(c, dC, mem, &g, 0, -lr);
-    if (rc == GS_OK) c->did_pre = c->did_bin = c->did_fwd = c->did_bwd = false;       // the model changed
-    return rc;
-}
-
-// backward + Adam in one pass (gs_sh_bwd_kernel<.., ADAM>): the OVERWRITE backward whose per-gaussian kernel steps p, m and v with each
-// gradient float instead of storing it -- bit-identical to gs_backward_ex(GS_BWD_OVERWRITE) + gs_adam_step, without the gradient's store
-// and re-read.  The checks come first: a refused call enqueues nothing.
-int gs_backward_adam(gs_ctx *c, const float *dC, int mem, const gs_grads *exp_avg, const gs_grads *exp_avg_sq, const float lr[GS_ADAM_GROUPS],
-                     float beta1, float beta2, float eps, int64_t step, int flags) {
-    if (!c) return GS_ERR_INVALID;
-    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_backward_adam: 3-D renderer only");
-    if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_backward: gs_forward first");
-    if (!dC || !exp_avg || !exp_avg_sq) return fail(c, GS_ERR_INVALID, "gs_backward_adam: NULL argument");
-    GsAdamFused ad{};
-    float *m[5] = {exp_avg->d_means, exp_avg->d_scales, exp_avg->d_quats, exp_avg->d_opacities, exp_avg->d_shs};
-    float *v[5] = {exp_avg_sq->d_means, exp_avg_sq->d_scales, exp_avg_sq->d_quats, exp_avg_sq->d_opacities, exp_avg_sq->d_shs};
-    for (int i = 0; i < 5; ++i) {
-        if (!m[i] || !v[i]) return fail(c, GS_ERR_INVALID, "gs_backward_adam: all ten moment arrays must be non-NULL");
-        ad.m[i] = m[i]; ad.v[i] = v[i];
-    }
-    const float *p[5] = {c->means, c->scales, c->quats, c->opac, c->shs};
-    const int rc0 = gs_adam_prepare(c, "gs_backward_adam", p, nullptr, m, v, lr, beta1, beta2, eps, step, flags, &ad.h);
-    if (rc0 != GS_OK) return rc0;
-    gs_grads g{const_cast<float *>(c->means), const_cast<float *>(c->scales), const_cast<float *>(c->quats),
-               const_cast<float *>(c->opac), const_cast<float *>(c->shs)};
-    const int rc = backward_impl(c, dC, mem, &g, GS_BWD_OVERWRITE, 0.0f, &ad, (flags & GS_ADAM_SELECTIVE) ? 2 : 1);
-    if (rc == GS_OK) c->did_pre = c->did_bin = c->did_fwd = c->did_bwd = false;       // the model changed
-    return rc;
-}
-
-static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *grads, int flags, float sgd_scale, const GsAdamFused *adam,
-                         int adam_mode) {
-    if (!c) return GS_ERR_INVALID;
-    if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_backward: gs_forward first");
+    if (p.fused() && c->kind != 0)
+        return fail(c, GS_ERR_UNSUPPORTED, p.update == Update::SGD ? "gs_backward_sgd: 3-D renderer only" : "gs_backward_adam: 3-D renderer only");
+    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_backward: gs_forward first");
     const bool params_only = (flags & GS_BWD_PARAMS_ONLY) != 0, composite_only = (flags & GS_BWD_COMPOSITE_ONLY) != 0;
     if (params_only && composite_only) return fail(c, GS_ERR_INVALID, "gs_backward: COMPOSITE_ONLY and PARAMS_ONLY exclude each other");
     const int chain = (flags & (GS_BWD_PARAMS_SH | GS_BWD_PARAMS_GEOM)) >> 3;             // bit 0: SH kernel, bit 1: geometry chain; 0 = both
     if (chain && !params_only) return fail(c, GS_ERR_INVALID, "gs_backward: GS_BWD_PARAMS_SH / _GEOM need GS_BWD_PARAMS_ONLY");
     if (chain && c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_backward: GS_BWD_PARAMS_SH / _GEOM: 3-D renderer only");
-    if (params_only && !c->did_bwd_composite) return fail(c, GS_ERR_INVALID, "gs_backward: GS_BWD_PARAMS_ONLY needs a GS_BWD_COMPOSITE_ONLY call on this frame");
-    if ((!dC && !params_only) || (!grads && !composite_only)) return fail(c, GS_ERR_INVALID, "gs_backward: NULL argument");
+    if (params_only && c->stage < Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_backward: GS_BWD_PARAMS_ONLY needs a GS_BWD_COMPOSITE_ONLY call on this frame");
+    if ((!dC && !params_only) || (!grads && !p.fused() && !composite_only)) return fail(c, GS_ERR_INVALID, "gs_backward: NULL argument");
     if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(c, GS_ERR_INVALID, "gs_backward: bad mem");
-    if (bind_device(c)) return GS_ERR_HIP;
-    const size_t px = (size_t)c->cam.W * c->cam.H, n1 = c->n ? (size_t)c->n : 1;
-    const float *dC_dev = dC;
-    if (mem == GS_MEM_HOST && !params_only) {
-        HIPCHK(c, c->stage_in.ensure(sizeof(float) * 3 * px));
-        HIPCHK(c, hipMemcpyAsync(c->stage_in.p, dC, sizeof(float) * 3 * px, hipMemcpyHostToDevice, c->stream));
-        dC_dev = c->stage_in.as<float>();
-    }
-    const bool det = c->cfg.deterministic != 0;
-    HIPCHK(c, c->g2d.ensure((det ? sizeof(long long) : sizeof(float)) * GS_G2D_STRIDE * n1));
-    HIPCHK(c, c->ensure_bwd_counters());
-    GsCompositeArgs a = composite_args(c, true, 0);                        // order, parts, list segments: as the frame's plan says
-    a.dC = dC_dev;
-    // the segments of a tile ADD to these words, which only the frame's forward zeroed: a second backward launch of the frame inflates them
-    a.tile_walked = c->tile_walked_b.as<uint32_t>(); a.tile_work = c->tile_work_b.as<uint32_t>();
+    p.composite = !params_only;
+    p.chain = composite_only ? 0 : chain ? chain : 3;
+    if (!p.fused() && (flags & GS_BWD_OVERWRITE)) p.update = Update::OVERWRITE;
+    if (p.fused()) p.target = c->model5_mut(); else if (grads) p.target = five(*grads);
+    p.dC = dC;
+    p.stage_dC = mem == GS_MEM_HOST && p.composite;
+    p.host_sync = mem == GS_MEM_HOST;
+    p.fill_g2d = p.composite && !c->g2d_clean;                             // (the fill command itself, and why it is in line: run_backward)
     // An overwriting backward of the 3-D renderer, both phases in this call, no fused optimiser: the zeros of the SH gradient rows no pixel
     // touched (63 % of the gaussians at C3, 90 % at C5; 192 B each at degree 3) depend on nothing -- the fill workgroups at the end of the
     // composite backward's grid zero ALL of d_shs, and gs_sh_bwd_kernel then stores the live rows only.  Past the caches, like that kernel's
     // own stores (GS_NT_STORES): the model's SH rows stay in the infinity cache for the next preprocess.  Split phases, GS_BWD_PARAMS_SH /
     // _GEOM, the fused optimisers and accumulating views keep the kernel's own zeros.
-    const size_t shs_bytes = sizeof(float) * c->width[4] * (size_t)(c->n > 0 ? c->n : 0);            // 3K x n floats
-    const bool fill_shs = c->tail_fill() && !params_only && !composite_only && c->kind == 0 && (flags & GS_BWD_OVERWRITE) && sgd_scale == 0.0f &&
-                          !adam && !adam_mode && grads && gs_composite_fill_blocks(grads->d_shs, shs_bytes) > 0;
-    if (fill_shs) { a.fill_dst = grads->d_shs; a.fill_bytes = shs_bytes; a.fill_blocks = gs_composite_fill_blocks(a.fill_dst, a.fill_bytes); a.fill_nt = 1; }
-    if (!params_only) {
-        c->last_dC = dC_dev;
+    p.fill_shs = c->tail_fill() && p.composite && p.chain == 3 && c->kind == 0 && p.update == Update::OVERWRITE &&
+                 gs_composite_fill_blocks(p.target[4], c->shs_bytes()) > 0;
+    return GS_OK;
+}
+
+// The plan, enqueued: staging copy, the composite adjoint with what is the backward's alone, the per-gaussian kernels, the host's wait.
+static int run_backward(gs_ctx *c, const BackwardPlan &p) {
+    if (bind_device(c)) return GS_ERR_HIP;
+    const size_t px = (size_t)c->cam.W * c->cam.H, n1 = c->n ? (size_t)c->n : 1;
+    const float *dC_dev = p.dC;
+    if (p.stage_dC) {
+        HIPCHK(c, c->stage_in.ensure(sizeof(float) * 3 * px));
+        HIPCHK(c, hipMemcpyAsync(c->stage_in.p, p.dC, sizeof(float) * 3 * px, hipMemcpyHostToDevice, c->stream));
+        dC_dev = c->stage_in.as<float>();
+    }
+    const bool det = c->cfg.deterministic != 0;
+    HIPCHK(c, c->g2d.ensure(c->g2d_bytes()));
+    HIPCHK(c, c->ensure_bwd_counters());
+    const float *g2d = det ? nullptr : c->g2d.as<float>();
+    const long long *g2d_fixed = det ? c->g2d.as<long long>() : nullptr;
+    if (p.composite) {
+        GsCompositeArgs a = composite_args(c, true, 0);                    // order, parts, list segments: as the frame's plan says
+        a.dC = c->last_dC = dC_dev;
+        // the segments of a tile ADD to these words, which only the frame's forward zeroed: a second backward launch of the frame inflates them
+        a.tile_walked = c->tile_walked_b.as<uint32_t>(); a.tile_work = c->tile_work_b.as<uint32_t>();
+        if (p.fill_shs) { a.fill_dst = p.target[4]; a.fill_bytes = c->shs_bytes(); a.fill_blocks = gs_composite_fill_blocks(a.fill_dst, a.fill_bytes); a.fill_nt = 1; }
         // zero fill of the gradient rows (64 B per gaussian), in line: on a side stream beside the forward composite it cost more than
         // it hid (C3, same box, interleaved: 1.433 ms with the fill beside the forward, 1.412 ms in line -- its workgroups take wave slots
         // from the forward's tiles, and the two event hand-shakes per frame delay the depth sort's launches)
@@ -342,60 +316,87 @@ static int backward_impl(gs_ctx *c, const float *dC, int mem, const gs_grads *gr
         // find their rows in memory instead of the cache, C3 + 1 %; profiles/r04t_ab_nontemporal.log)
         // (a small frame's gs_bin kernel has cleared them already: gs_bin_small.hip)
         // (... and otherwise the fill workgroups of the frame's forward: gs_forward)
-        if (!c->g2d_clean) HIPCHK(c, hipMemsetAsync(c->g2d.p, 0, (det ? sizeof(long long) : sizeof(float)) * GS_G2D_STRIDE * n1, c->stream));
+        if (p.fill_g2d) HIPCHK(c, hipMemsetAsync(c->g2d.p, 0, c->g2d_bytes(), c->stream));
         c->g2d_clean = false;
         {
-            StageTimer t(c, GS_STAGE_COMPOSITE_BWD);                   // the kernel alone (what rocprof reports for it)
+            StageTimer t(c, GS_STAGE_COMPOSITE_BWD);                       // the kernel alone (what rocprof reports for it)
             HIPCHK(c, gs_launch_composite_bwd(a, c->stream));
         }
         c->fill_blocks_bwd = a.fill_blocks;
-        c->did_bwd_composite = true;
     }
-    if (composite_only) {
-        if (mem == GS_MEM_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->did_bwd = true;                                             // the 2-D gradient sums exist (gs_color_grads_pack, GS_ARR_GRAD2D)
-        return GS_OK;
-    }
-    if (c->kind == 1) {                                  // SplatGrads2D, splat.jl:28-34
+    const int overwrite = p.update == Update::ACCUMULATE || p.update == Update::SGD ? 0 : 1;   // the fused Adam IS the overwriting backward, stepping instead of storing
+    if (p.chain && c->kind == 1) {                       // SplatGrads2D, splat.jl:28-34
         GsPreprocess2DBwdArgs b2{};
         b2.n = c->n; b2.W = c->cam.W; b2.H = c->cam.H;
         b2.scales = c->scales; b2.rots = c->quats; b2.opac = c->opac;
-        b2.g2d = det ? nullptr : c->g2d.as<float>(); b2.g2d_fixed = det ? c->g2d.as<long long>() : nullptr;
-        b2.overwrite = (flags & GS_BWD_OVERWRITE) ? 1 : 0;
-        b2.d_means = grads->d_means; b2.d_scales = grads->d_scales; b2.d_rots = grads->d_quats;
-        b2.d_opac = grads->d_opacities; b2.d_colors = grads->d_shs;
-        {
-            StageTimer t(c, GS_STAGE_PREPROCESS_BWD);
-            HIPCHK(c, gs_launch_preprocess2d_bwd(b2, c->stream));
-        }
-        if (mem == GS_MEM_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->did_bwd = true;
-        return GS_OK;
-    }
-    GsPreprocessBwdArgs b{};
-    b.n = c->n; b.sh_degree = c->sh_degree;
-    b.means = c->means; b.scales = c->scales; b.quats = c->quats; b.opac = c->opac; b.shs = c->shs;
-    b.g2d = det ? nullptr : c->g2d.as<float>(); b.g2d_fixed = det ? c->g2d.as<long long>() : nullptr;
-    HIPCHK(c, c->dpc.ensure(sizeof(float) * 4 * n1));
-    b.dpc = c->dpc.as<float>();
-    b.overwrite = (flags & GS_BWD_OVERWRITE) ? 1 : 0;
-    b.shs_zeroed = fill_shs ? 1 : 0;
-    b.sgd_scale = sgd_scale;
-    b.d_means = grads->d_means; b.d_scales = grads->d_scales; b.d_quats = grads->d_quats;
-    b.d_opac = grads->d_opacities; b.d_shs = grads->d_shs;
-    {
+        b2.g2d = g2d; b2.g2d_fixed = g2d_fixed; b2.overwrite = overwrite;
+        b2.d_means = p.target[0]; b2.d_scales = p.target[1]; b2.d_rots = p.target[2]; b2.d_opac = p.target[3]; b2.d_colors = p.target[4];
         StageTimer t(c, GS_STAGE_PREPROCESS_BWD);
-        HIPCHK(c, gs_launch_preprocess_bwd(b, c->cam, c->stream, chain ? chain : 3, adam, adam_mode));
+        HIPCHK(c, gs_launch_preprocess2d_bwd(b2, c->stream));
+    } else if (p.chain) {
+        GsPreprocessBwdArgs b{};
+        b.n = c->n; b.sh_degree = c->sh_degree;
+        b.means = c->means; b.scales = c->scales; b.quats = c->quats; b.opac = c->opac; b.shs = c->shs;
+        b.g2d = g2d; b.g2d_fixed = g2d_fixed;
+        HIPCHK(c, c->dpc.ensure(sizeof(float) * 4 * n1));
+        b.dpc = c->dpc.as<float>();
+        b.overwrite = overwrite; b.shs_zeroed = p.fill_shs ? 1 : 0;
+        b.sgd_scale = p.update == Update::SGD ? -p.lr : 0.0f;             // with the model as target this IS the SGD step
+        b.d_means = p.target[0]; b.d_scales = p.target[1]; b.d_quats = p.target[2]; b.d_opac = p.target[3]; b.d_shs = p.target[4];
+        const GsPreprocessBwdMode mode{p.chain, p.adam, p.update == Update::ADAM_DENSE ? 1 : p.update == Update::ADAM_SELECTIVE ? 2 : 0};
+        StageTimer t(c, GS_STAGE_PREPROCESS_BWD);
+        HIPCHK(c, gs_launch_preprocess_bwd(b, c->cam, c->stream, mode));
     }
-    if (mem == GS_MEM_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));   // dC host buffer no longer needed
-    c->did_bwd = true;
+    if (p.host_sync) HIPCHK(c, hipStreamSynchronize(c->stream));           // the host's dC buffer is no longer needed
+    if (p.model_changes()) c->inputs_changed();
+    else c->reach(p.chain ? Stage::BACKWARD : Stage::COMPOSITE_ADJOINT);
     return GS_OK;
+}
+
+int gs_backward(gs_ctx *c, const float *dC, int mem, const gs_grads *grads) { return gs_backward_ex(c, dC, mem, grads, 0); }
+
+int gs_backward_ex(gs_ctx *c, const float *dC, int mem, const gs_grads *grads, int flags) {
+    BackwardPlan p;
+    if (const int rc = plan_backward(c, dC, mem, grads, flags, p)) return rc;
+    return run_backward(c, p);
+}
+
+// backward + SGD in one pass: the per-gaussian kernels apply param = fma(-lr, gradient, param) to the resident model instead
+// of storing the gradient (the same fma gs_sgd_step applies to the stored float): one read-modify-write of the parameters
+// instead of gradient write + gradient read + parameter read-modify-write.  Single-view steps only (nothing is accumulated).
+int gs_backward_sgd(gs_ctx *c, const float *dC, int mem, float lr) {
+    if (!c) return GS_ERR_INVALID;
+    if (!(lr != 0.0f)) return fail(c, GS_ERR_INVALID, "gs_backward_sgd: lr must be non-zero");
+    BackwardPlan p;
+    p.update = Update::SGD; p.lr = lr;
+    if (const int rc = plan_backward(c, dC, mem, nullptr, 0, p)) return rc;
+    return run_backward(c, p);
+}
+
+// backward + Adam in one pass (gs_sh_bwd_kernel<.., ADAM>): the OVERWRITE backward whose per-gaussian kernel steps p, m and v with each
+// gradient float instead of storing it -- bit-identical to gs_backward_ex(GS_BWD_OVERWRITE) + gs_adam_step, without the gradient's store
+// and re-read.
+int gs_backward_adam(gs_ctx *c, const float *dC, int mem, const gs_grads *exp_avg, const gs_grads *exp_avg_sq, const float lr[GS_ADAM_GROUPS],
+                     float beta1, float beta2, float eps, int64_t step, int flags) {
+    if (!c) return GS_ERR_INVALID;
+    if (!dC || !exp_avg || !exp_avg_sq) return fail(c, GS_ERR_INVALID, "gs_backward_adam: NULL argument");
+    GsAdamFused ad{};
+    const Five<float> m = five(*exp_avg), v = five(*exp_avg_sq);
+    for (int i = 0; i < 5; ++i) {
+        if (!m[i] || !v[i]) return fail(c, GS_ERR_INVALID, "gs_backward_adam: all ten moment arrays must be non-NULL");
+        ad.m[i] = m[i]; ad.v[i] = v[i];
+    }
+    if (const int rc = gs_adam_prepare(c, "gs_backward_adam", c->model5().p, nullptr, m.p, v.p, lr, beta1, beta2, eps, step, flags, &ad.h)) return rc;
+    BackwardPlan p;
+    p.update = (flags & GS_ADAM_SELECTIVE) ? Update::ADAM_SELECTIVE : Update::ADAM_DENSE; p.adam = &ad;
+    if (const int rc = plan_backward(c, dC, mem, nullptr, 0, p)) return rc;
+    return run_backward(c, p);
 }
 
 int gs_color_grads_pack(gs_ctx *c, float *drgb) {
     if (!c || !drgb) return GS_ERR_INVALID;
     if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_color_grads_pack: 3-D renderer only");
-    if (!c->did_bwd) return fail(c, GS_ERR_INVALID, "gs_color_grads_pack: gs_backward first");
+    if (c->stage < Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_color_grads_pack: gs_backward first");
     if (bind_device(c)) return GS_ERR_HIP;
     const bool det = c->cfg.deterministic != 0;
     HIPCHK(c, gs_launch_pack_drgb(det ? nullptr : c->g2d.as<float>(), det ? c->g2d.as<long long>() : nullptr, drgb, c->n, c->stream));

@@ -2,6 +2,8 @@
 // profiling hooks (per-stage hipEvent timers, work counters, per-tile clocks, isolated composite launches).
 #include "gs_ctx.h"
 
+using Stage = gs_ctx::Stage;
+
 extern "C" {
 
 int64_t gs_num_gaussians(const gs_ctx *c) { return c ? c->n : 0; }
@@ -19,8 +21,8 @@ int gs_get_array(gs_ctx *c, int which, void *dst, int64_t bytes) {
         if (!c->cfg.export_debug) return fail(c, GS_ERR_INVALID, "gs_get_array: needs gs_config.export_debug = 1");
         src = c->dbg[i].p; need = sizeof(float) * w * n; return GS_OK;
     };
-    if (which <= GS_ARR_TILE_RECT && !c->did_pre) return fail(c, GS_ERR_INVALID, "gs_get_array: gs_preprocess first");
-    if (which >= GS_ARR_SORT_IDXS && which <= GS_ARR_SORTED_KEYS && !c->did_bin) return fail(c, GS_ERR_INVALID, "gs_get_array: gs_bin first");
+    if (which <= GS_ARR_TILE_RECT && c->stage < Stage::PREPROCESSED) return fail(c, GS_ERR_INVALID, "gs_get_array: gs_preprocess first");
+    if (which >= GS_ARR_SORT_IDXS && which <= GS_ARR_SORTED_KEYS && c->stage < Stage::BINNED) return fail(c, GS_ERR_INVALID, "gs_get_array: gs_bin first");
     if (which >= GS_ARR_TILE_RANGES && which <= GS_ARR_SORTED_KEYS) { if (int rc = settle_totals(c, nullptr, true)) return rc; }
     if (which >= GS_ARR_TILE_RANGES && which <= GS_ARR_SORTED_KEYS && c->bin.n_rounds > 1)
         return fail(c, GS_ERR_INVALID, "gs_get_array: this frame was binned in depth slabs (lists spread over rounds); use gs_config.slab_mode = 0");
@@ -88,7 +90,7 @@ int gs_get_array(gs_ctx *c, int which, void *dst, int64_t bytes) {
             return GS_OK;
         }
         case GS_ARR_GRAD2D: {
-            if (!c->did_bwd) return fail(c, GS_ERR_INVALID, "gs_get_array: gs_backward first");
+            if (c->stage < Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_get_array: gs_backward first");
             if ((size_t)bytes != sizeof(float) * 10 * n) return fail(c, GS_ERR_INVALID, "gs_get_array: size mismatch");
             float *o = static_cast<float *>(dst);
             if (c->cfg.deterministic) {
@@ -185,8 +187,8 @@ int gs_debug_time_composite(gs_ctx *c, int which, int variant, int reps, float *
     if (!c || !mean_ms || reps == 0) return GS_ERR_INVALID;
     const bool cold = reps < 0;                                               // negative: -reps launches WITHOUT the warm-up launch (tools/cold_fwd.py)
     if (cold) reps = -reps;
-    if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_debug_time_composite: gs_forward first");
-    if (which == 1 && !c->did_bwd) return fail(c, GS_ERR_INVALID, "gs_debug_time_composite: gs_backward first");
+    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_debug_time_composite: gs_forward first");
+    if (which == 1 && c->stage < Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_debug_time_composite: gs_backward first");
     if (bind_device(c)) return GS_ERR_HIP;
     GsCompositeArgs a{};
     if (int rc = debug_composite_args(c, which, variant, a)) return rc;
@@ -207,8 +209,8 @@ int gs_debug_time_composite(gs_ctx *c, int which, int variant, int reps, float *
 
 int gs_debug_tile_clock(gs_ctx *c, int which, int variant, uint64_t *out) {
     if (!c || !out) return GS_ERR_INVALID;
-    if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_debug_tile_clock: gs_forward first");
-    if (which == 1 && !c->did_bwd) return fail(c, GS_ERR_INVALID, "gs_debug_tile_clock: gs_backward first");
+    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_debug_tile_clock: gs_forward first");
+    if (which == 1 && c->stage < Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_debug_tile_clock: gs_backward first");
     if (bind_device(c)) return GS_ERR_HIP;
     GsCompositeArgs a{};
     const bool by_block = variant < 0;                                        // negative variant: records per WORKGROUP (launches with split tiles):
@@ -235,8 +237,8 @@ int gs_debug_tile_clock(gs_ctx *c, int which, int variant, uint64_t *out) {
 
 int gs_debug_tail_fill(gs_ctx *c, int32_t blocks[2]) {
     if (!c || !blocks) return GS_ERR_INVALID;
-    if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_debug_tail_fill: gs_forward first");
-    blocks[0] = c->fill_blocks_fwd; blocks[1] = c->did_bwd_composite ? c->fill_blocks_bwd : 0;
+    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_debug_tail_fill: gs_forward first");
+    blocks[0] = c->fill_blocks_fwd; blocks[1] = c->stage >= Stage::COMPOSITE_ADJOINT ? c->fill_blocks_bwd : 0;
     return GS_OK;
 }
 
@@ -268,7 +270,7 @@ static int sum_work_counters(gs_ctx *c) {
     unsigned long long *w = c->counters.as<unsigned long long>();
     const int nt = c->gx * c->gy;
     HIPCHK(c, gs_launch_sum_tiles(c->last_walked, c->tile_work.as<uint32_t>(), nt, w, c->stream));
-    if (c->did_bwd_composite && c->tile_walked_b.p && c->tile_work_b.p)
+    if (c->stage >= Stage::COMPOSITE_ADJOINT && c->tile_walked_b.p && c->tile_work_b.p)
         HIPCHK(c, gs_launch_sum_tiles(c->tile_walked_b.as<uint32_t>(), c->tile_work_b.as<uint32_t>(), nt, w + 2, c->stream));
     else HIPCHK(c, hipMemsetAsync(w + 2, 0, 16, c->stream));
     return GS_OK;
@@ -276,20 +278,17 @@ static int sum_work_counters(gs_ctx *c) {
 
 int gs_get_work_counters(gs_ctx *c, int64_t *walked_fwd, int64_t *walked_bwd) {
     if (!c) return GS_ERR_INVALID;
-    if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_get_work_counters: gs_forward first");
-    if (bind_device(c)) return GS_ERR_HIP;
-    unsigned long long h[4] = {0, 0, 0, 0};
-    if (int rc = sum_work_counters(c)) return rc;
-    HIPCHK(c, hipMemcpyAsync(h, c->counters.p, 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (walked_fwd) *walked_fwd = (int64_t)h[0];
-    if (walked_bwd) *walked_bwd = (int64_t)h[2];
+    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_get_work_counters: gs_forward first");
+    int64_t o[4];
+    if (int rc = gs_get_work_counters_ex(c, o)) return rc;
+    if (walked_fwd) *walked_fwd = o[0];
+    if (walked_bwd) *walked_bwd = o[1];
     return GS_OK;
 }
 
 int gs_get_list_stats(gs_ctx *c, int64_t out[3]) {
     if (!c || !out) return GS_ERR_INVALID;
-    if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_get_list_stats: gs_forward first");
+    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_get_list_stats: gs_forward first");
     if (bind_device(c)) return GS_ERR_HIP;
     if (int rc = settle_totals(c, nullptr, true)) return rc;
     out[0] = c->n_inst; out[1] = 0; out[2] = 0;
@@ -306,19 +305,19 @@ int gs_get_list_stats(gs_ctx *c, int64_t out[3]) {
 
 int gs_get_tile_parts(gs_ctx *c) {
     if (!c) return GS_ERR_INVALID;
-    if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_get_tile_parts: gs_forward first");
+    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_get_tile_parts: gs_forward first");
     return c->plan.parts;
 }
 
 int gs_get_bin_path(gs_ctx *c) {
     if (!c) return GS_ERR_INVALID;
-    if (!c->did_bin) return fail(c, GS_ERR_INVALID, "gs_get_bin_path: gs_bin first");
+    if (c->stage < Stage::BINNED) return fail(c, GS_ERR_INVALID, "gs_get_bin_path: gs_bin first");
     return (int)c->bin.path;
 }
 
 int gs_get_work_counters_ex(gs_ctx *c, int64_t out[4]) {
     if (!c || !out) return GS_ERR_INVALID;
-    if (!c->did_fwd) return fail(c, GS_ERR_INVALID, "gs_get_work_counters_ex: gs_forward first");
+    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_get_work_counters_ex: gs_forward first");
     if (bind_device(c)) return GS_ERR_HIP;
     unsigned long long h[4] = {0, 0, 0, 0};
     if (int rc = sum_work_counters(c)) return rc;

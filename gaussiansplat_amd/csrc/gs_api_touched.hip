@@ -15,7 +15,7 @@ extern "C" {
 int gs_color_rows_pack(gs_ctx *c, const float *drgb, int64_t n, int32_t *bits, float *rows, int64_t *count) {
     if (!c || !bits || !rows || !count || n < 0) return GS_ERR_INVALID;
     if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_color_rows_pack: 3-D renderer only");
-    if (!drgb && !c->did_bwd) return fail(c, GS_ERR_INVALID, "gs_color_rows_pack: gs_backward first (or pass drgb)");
+    if (!drgb && c->stage < gs_ctx::Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_color_rows_pack: gs_backward first (or pass drgb)");
     if (!drgb && n != c->n) return fail(c, GS_ERR_INVALID, "gs_color_rows_pack: n must be gs_num_gaussians when the ctx's own sums are packed");
     if (bind_device(c)) return GS_ERR_HIP;
     if (n == 0) {

@@ -403,10 +403,12 @@ struct GsPreprocessBwdArgs {
     float sgd_scale;      // != 0 (accumulate mode only): target = fma(sgd_scale, gradient, target) -- with the parameter arrays as
                           // targets and sgd_scale = -lr this IS the SGD step, fused (gs_backward_sgd)
 };
-// phases: bit 0 the SH / colour kernel (d_shs, dpc), bit 1 the geometry chain (reads dpc); 3 = both, in that order.
-// adam_mode 1 (dense) / 2 (selective), with adam and phases = 3 and overwrite = 1: the fused backward + Adam (gs_backward_adam)
-hipError_t gs_launch_preprocess_bwd(const GsPreprocessBwdArgs &a, const GsCamera &cam, hipStream_t s, int phases = 3,
-                                    const GsAdamFused *adam = nullptr, int adam_mode = 0);
+struct GsPreprocessBwdMode {     // the host side of a per-gaussian backward launch: which kernels run, and the optimiser that rides in them
+    int phases;                  // bit 0 the SH / colour kernel (d_shs, dpc), bit 1 the geometry chain (reads dpc); 3 = both, in that order
+    const GsAdamFused *adam;     // the fused backward + Adam (gs_backward_adam), else null ...
+    int adam_mode;               // ... 1 dense / 2 selective (0: none): needs adam, phases = 3 and overwrite = 1
+};
+hipError_t gs_launch_preprocess_bwd(const GsPreprocessBwdArgs &a, const GsCamera &cam, hipStream_t s, const GsPreprocessBwdMode &mode);
 
 // colour-factored gradient exchange (gs_preprocess_bwd.hip)
 hipError_t gs_launch_pack_drgb(const float *g2d, const long long *g2d_fixed, float *out, int64_t n, hipStream_t s);

@@ -3,10 +3,12 @@
 //   gs_api.hip            create / destroy, model, camera, gs_preprocess, gradients buffers, loss, SGD
 //   gs_api_bin.hip        gs_bin: the frame's bin plan (plan_bin), depth order, one function per path (bin_small, bin_two_level, bin_radix), settle_totals
 //   gs_api_composite.hip  gs_forward / gs_backward: the frame's plan (plan_frame), the one builder of the composite launches' arguments
-//                         (composite_args), the launch orders of the view slots
+//                         (composite_args), the launch orders of the view slots; the backward family's plan (plan_backward) and run_backward
 //   gs_api_comm.hip       RCCL below the boundary (gs_comm_*, gs_allreduce_grads)
 //   gs_api_touched.hip    the touched-rows colour exchange (gs_color_rows_pack, gs_sh_grads_from_touched)
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
+// How far the frame has come is ONE ordered value (gs_ctx::Stage): every entry point compares it, reaches a stage or falls back to one.
+// What the ctx holds it owns: DevBuf frees itself, ~gs_ctx releases the communicator, events, streams and pinned blocks -- no list to keep.
 #pragma once
 #include "../../include/gsplat.h"
 #include "gs_common.h"
@@ -23,9 +25,12 @@
 #include <string>
 #include <vector>
 
-struct DevBuf {
+struct DevBuf {                               // grow-only device scratch that frees itself: what a gs_ctx holds of them goes with the ctx
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }   // movable (ViewSlot lives in a std::vector, sized once in gs_create), not copyable
+    ~DevBuf() { if (p) (void)hipFree(p); }
     hipError_t ensure(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
         if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
@@ -34,9 +39,11 @@ struct DevBuf {
         if (e == hipSuccess) cap = want;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
     template <typename T> T *as() const { return static_cast<T *>(p); }
 };
+// five device arrays in the order of gs_ctx::width: a gs_grads (gradients, moments), or the model
+template <typename T> struct Five { T *p[5]; T *operator[](int i) const { return p[i]; } };
+inline Five<float> five(const gs_grads &g) { return {{g.d_means, g.d_scales, g.d_quats, g.d_opacities, g.d_shs}}; }
 
 extern std::string g_create_error;         // message of the last failed gs_create (gs_last_error(NULL))
 
@@ -64,7 +71,18 @@ static_assert(sizeof(CounterBlock) == GS_COUNTER_BYTES && offsetof(CounterBlock,
               offsetof(CounterBlock, scratch) == 160, "counter block layout (the kernels address it by these offsets)");
 static_assert(sizeof(PinnedWords) == 512 && offsetof(PinnedWords, readback) == 0 && offsetof(PinnedWords, walked_prev) == 8 &&
               offsetof(PinnedWords, counters) == 32 && offsetof(PinnedWords, dsort_stat) == 400, "pinned block layout");
+void comm_release(struct gs_ctx *c);         // gs_api_comm.hip: destroys the ctx's RCCL communicator, if any
 struct gs_ctx {
+    // the device is bound; gs_destroy has drained both streams (gs_create giving up has at most its failed probe behind it, which hipStreamDestroy
+    // waits out on its own): the communicator first, the rest in any order, the DevBufs by themselves
+    ~gs_ctx() {
+        comm_release(this);
+        for (auto &pair : ev) for (hipEvent_t e : pair) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {ev_count, ev_main, ev_order}) if (e) (void)hipEventDestroy(e);
+        if (side) (void)hipStreamDestroy(side);
+        for (void *h : {(void *)pinned, (void *)pinned_split}) if (h) (void)hipHostFree(h);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false, borrowed_stream = false;
@@ -78,8 +96,24 @@ struct gs_ctx {
     int order() const { return kind == 1 ? (int)GS_ORDER_INDEX : cfg.order; }    // the 2-D model has no depth
     const float *means = nullptr, *scales = nullptr, *quats = nullptr, *opac = nullptr, *shs = nullptr;
     DevBuf model[5];
+    Five<const float> model5() const { return {{means, scales, quats, opac, shs}}; }
+    // ... to write: the optimiser steps and the fused backwards update the resident model in place (the ctx's copy, or the caller's device arrays)
+    Five<float> model5_mut() const { return {{const_cast<float *>(means), const_cast<float *>(scales), const_cast<float *>(quats), const_cast<float *>(opac), const_cast<float *>(shs)}}; }
+    void set_model5(const float *const a[5]) { means = a[0]; scales = a[1]; quats = a[2]; opac = a[3]; shs = a[4]; }
     GsCamera cam{};
-    bool have_cam = false, did_pre = false, did_bin = false, did_fwd = false, did_bwd = false, did_bwd_composite = false;
+    bool have_cam = false;
+    // ---- how far the frame has come, one linear progress: an entry point asks for the stage it needs, reaches its own once its work is enqueued, or falls back
+    enum class Stage {
+        NOTHING,                             // no frame: the model or the view changed (inputs_changed)
+        PREPROCESSED,                        // gs_preprocess: payload rows, depth keys, tile rectangles
+        BINNED,                              // gs_bin: the tile lists
+        RENDERED,                            // gs_forward: image and transmittance, in the buffers bound at its time
+        COMPOSITE_ADJOINT,                   // the composite backward ran on this forward: the 2-D gradient sums g2d exist (GS_BWD_PARAMS_ONLY, gs_color_grads_pack, GS_ARR_GRAD2D)
+        BACKWARD                             // ... and the per-gaussian kernels behind it
+    } stage = Stage::NOTHING;
+    void reach(Stage s) { stage = s; }
+    void fall_back(Stage s) { if (stage > s) stage = s; }                  // to at most s
+    void inputs_changed() { fall_back(Stage::NOTHING); }   // the model or the view changed: nothing of the frame stands
     int gx = 0, gy = 0;
     int64_t grid_key() const { return ((int64_t)gx << 32) | (int64_t)gy; }        // what per-grid history is tagged with (0: none)
     size_t ntiles1() const { const size_t nt = (size_t)gx * gy; return nt ? nt : 1; }   // tiles, for buffer sizes (never zero)
@@ -161,6 +195,22 @@ struct gs_ctx {
         const uint32_t *seg_hist = nullptr;  // ... their lengths from the walk of the slot's previous forward
         bool bwd_segments = false;           // the backward runs as list segments: the forward LEFT snapshots, and for the order the backward takes
     } plan;
+    // ---- the backward's plan: WHAT one call of the backward family (gs_backward, _ex, _sgd, _adam) runs.  Filled once per call by plan_backward
+    // (gs_api_composite.hip), the one place that decides and refuses -- it enqueues and allocates nothing; run_backward is its one consumer.
+    struct BackwardPlan {
+        bool composite = true;               // phases that run: the composite adjoint (dC -> the 2-D gradient sums g2d) ...
+        int chain = 3;                       // ... and the per-gaussian kernels: bit 0 the SH kernel, bit 1 the geometry chain (0: none, GS_BWD_COMPOSITE_ONLY)
+        // what the per-gaussian kernels do with a gradient float: add it to the target, store it, or step the target with it
+        enum class Update { ACCUMULATE, OVERWRITE, SGD, ADAM_DENSE, ADAM_SELECTIVE } update = Update::ACCUMULATE;
+        float lr = 0.0f; const GsAdamFused *adam = nullptr;   // SGD: target = fma(-lr, gradient, target); ADAM_*: the moments and the step's scalars
+        bool fused() const { return update >= Update::SGD; }
+        Five<float> target{};                // the caller's gs_grads, or (fused) the model's own arrays
+        const float *dC = nullptr; bool stage_dC = false;   // dC is host memory: staged through stage_in ...
+        bool host_sync = false;              // ... and GS_MEM_HOST calls return with the stream drained
+        bool fill_g2d = false;               // the gradient rows need the in-line zero fill (nobody cleared them: g2d_clean)
+        bool fill_shs = false;               // the composite launch carries the zero fill of d_shs: the SH kernel stores live rows only (shs_zeroed)
+        bool model_changes() const { return fused(); }   // the frame falls back to nothing when the call succeeds
+    };
     // ---- heavy tiles: list segments of the backward
     DevBuf snap, snap_walked;                // the forward's snapshots (HEAVY: of the split tiles, ALL: of every tile); HEAVY: their walked lengths, two frame parities
     uint32_t *pinned_split = nullptr;        // coherent pinned host words, two per view slot (one per order buffer): split tiles of that order, as its
@@ -217,6 +267,7 @@ struct gs_ctx {
     bool tail_fill() const { return !(cfg.debug_flags & GS_DEBUG_NO_TAIL_FILL) && (int64_t)gx * gy > 0; }   // the composite launches may carry zero fills
     int fill_blocks_fwd = 0, fill_blocks_bwd = 0;   // fill workgroups the frame's last forward (round 0) / composite backward launch carried (gs_debug_tail_fill)
     size_t g2d_bytes() const { return (cfg.deterministic ? sizeof(long long) : sizeof(float)) * GS_G2D_STRIDE * (n ? (size_t)n : 1); }
+    size_t shs_bytes() const { return sizeof(float) * width[4] * (size_t)(n > 0 ? n : 0); }   // the fifth gradient array: 3K x n floats
     bool small_bin_possible() const {
         if (cfg.bin_path != 0 || cfg.depth_sort != 0 || cfg.list_cap == 2 || cfg.slab_fractions[0] > 0.0f) return false;
         if (cfg.debug_flags & (GS_DEBUG_WIDE_CURSORS | GS_DEBUG_SUPER8 | GS_DEBUG_SUPER16 | GS_DEBUG_TINY_CAPS)) return false;
@@ -323,7 +374,5 @@ inline int order_index(const gs_ctx *c) { return c->view_slot >= 0 ? c->view_slo
 int settle_totals(gs_ctx *c, bool *redo, bool may_relist);
 int bin_round(gs_ctx *c, int r);
 int depth_order(gs_ctx *c, uint32_t **perm_out);
-// gs_api_comm.hip
-void comm_release(gs_ctx *c);                // destroys the ctx's RCCL communicator, if any
 // gs_api_composite.hip: the arguments of a composite launch of the frame, as its plan says (round r of the forward / the backward; debug: an isolated launch)
 GsCompositeArgs composite_args(gs_ctx *c, bool bwd, int r, bool debug = false);

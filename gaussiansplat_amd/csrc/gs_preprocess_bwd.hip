@@ -332,9 +332,10 @@ hipError_t gs_launch_sh_from_views(int64_t n, int sh_degree, const float *means,
 #define GS_SHBWD_THREADS 256
 #endif
 static int sh_bwd_threads() { return GS_SHBWD_THREADS; }
-hipError_t gs_launch_preprocess_bwd(const GsPreprocessBwdArgs &a, const GsCamera &cam, hipStream_t s, int phases, const GsAdamFused *adam,
-                                    int adam_mode) {
+hipError_t gs_launch_preprocess_bwd(const GsPreprocessBwdArgs &a, const GsCamera &cam, hipStream_t s, const GsPreprocessBwdMode &mode) {
     if (a.n <= 0) return hipSuccess;
+    const int phases = mode.phases, adam_mode = mode.adam_mode;
+    const GsAdamFused *adam = mode.adam;
     const int T = sh_bwd_threads();
     dim3 block(T), grid((unsigned)((a.n + T - 1) / T));
     const int K = (a.sh_degree + 1) * (a.sh_degree + 1);

@@ -355,7 +355,7 @@ def _bind_outputs(renderer):
         raise ValueError("renderer.imageData must be a contiguous [3, H, W] tensor matching renderer.transmittance [H, W]")
     key = (img.data_ptr(), tr.data_ptr())
     if getattr(renderer, "_bound_out", None) != key:
-        renderer.ctx.bind_outputs(*key)                         # (invalidates the ctx's forward state: did_fwd = false)
+        renderer.ctx.bind_outputs(*key)                         # (the ctx falls back to the binned frame: a new forward is due)
         renderer._bound_out = key
     return key
 
