@@ -29,16 +29,12 @@
 // 8 x 8 -- l1_scatter 444 us at C5 -- against 135 of 16 x 16, the count of a 1080p frame), while level 2 only tests twice the rows.
 #define GS_BIN3_NS8_MAX 256
 #define L1_THREADS 256
-#ifndef L2_SEG
-#define L2_SEG 2048          // entries of a super-tile list per workgroup
-#endif
 #define L2_THREADS 256
 
 int gs_bin3_sb_shift(int gx, int gy, int force) {
     if (force == 3 || force == 4) return force;
     return ((gx + 7) / 8) * ((gy + 7) / 8) > GS_BIN3_NS8_MAX ? 4 : 3;
 }
-int gs_bin3_seg() { return L2_SEG; }
 int64_t gs_bin3_max_work(int64_t coarse_instances, int ns) { return coarse_instances / L2_SEG + ns; }
 // list positions per level-1 workgroup: the bitmap (ns x G bits), its word prefix (ns x G/32 u16), 2 ns starts and the
 // staging buffer (24 G bytes) share LDS

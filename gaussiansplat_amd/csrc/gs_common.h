@@ -220,7 +220,9 @@ struct GsBin3Args {
 #define GS_CONT_NONE 0xFFFFFFFFu
 // entries kept for a tile whose slot history walked w: a quarter more, and never less than two batches
 __host__ __device__ inline uint32_t gs_list_cap(uint32_t w) { const uint32_t c = w + (w >> 2) + 128u; return c < w ? 0xFFFFFFFFu : c; }
-int gs_bin3_seg();             // L2_SEG: coarse entries per level-2 work item
+#ifndef L2_SEG
+#define L2_SEG 2048            // coarse entries per level-2 work item of gs_bin3.hip (a workgroup's segment of a super-tile list); the composite forward extends capped lists by the same segments
+#endif
 int gs_bin3_sb_shift(int gx, int gy, int force);       // 3 or 4 (force: 3 / 4 = that edge whatever the grid, tests; else by the grid)
 bool gs_bin3_supported(int ns);
 int64_t gs_bin3_max_work(int64_t coarse_instances, int ns);
@@ -382,7 +384,8 @@ __host__ __device__ inline uint32_t gs_seg_len_all(uint32_t w, int seg_n) {
     const uint32_t per = seg_n == 2 ? (w * GS_SEG_ALL_NUM + GS_SEG_ALL_DEN - 1u) / GS_SEG_ALL_DEN : (w + (uint32_t)seg_n - 1u) / (uint32_t)seg_n, sl = ((per + 63u) & ~63u) < (uint32_t)GS_SEG_ALL_MIN_LEN ? (uint32_t)GS_SEG_ALL_MIN_LEN : ((per + 63u) & ~63u);
     return w > sl ? sl : 0u;
 }
-int gs_seg_units(int front);
+// workgroups in front of the order's in a backward launch: list segments 1 .. GS_SEG_MAX - 1 of the tiles that may be split (composite_bwd_kernel)
+__host__ __device__ inline int gs_seg_units(int front) { return 8 * (front / 24) * (GS_SEG_MAX - 1); }
 int gs_composite_grid_blocks(const GsCompositeArgs &a, int bwd);      // workgroups of the launch these arguments describe
 hipError_t gs_launch_composite_fwd(const GsCompositeArgs &a, hipStream_t s);
 hipError_t gs_launch_composite_bwd(const GsCompositeArgs &a, hipStream_t s);

@@ -47,27 +47,14 @@
 #ifndef GS_FWD_MINW
 #define GS_FWD_MINW 5               // __launch_bounds__ waves/SIMD of the forward (89 VGPRs)
 #endif
-#ifndef GS_LIVE_RECT
-#define GS_LIVE_RECT 1              // no-op test against the rectangle of the pixels still taking entries (0: against the whole tile; A/B builds)
-#endif
-#ifndef GS_FWD_PACK
-#define GS_FWD_PACK 1               // forward: pack the live pixels into one or two slots once they fit (0: A/B builds)
-#endif
 #ifndef GS_FWD_NO_PREFETCH
 #define GS_FWD_NO_PREFETCH 0        // 1: measurement build -- no payload rows / ids gathered ahead of the early-out decision (exposes the gather latency)
-#endif
-#ifndef GS_BWD_PAIR
-#define GS_BWD_PAIR 1               // small grids: the backward keeps two entries in flight per wave (0: A/B builds)
 #endif
 #ifndef GS_FWD_UNROLL
 #define GS_FWD_UNROLL 2             // entries interleaved in the forward's per-entry loop
 #endif
 constexpr int kFwdUnroll = GS_FWD_UNROLL;
 #define CB 64                       // splats staged per batch
-#ifndef L2_SEG
-#define L2_SEG 2048                 // gs_bin3.hip: coarse entries per level-2 work item (gs_bin3_seg() on the host side)
-#endif
-__device__ __forceinline__ int gs_bin3_seg_const() { return L2_SEG; }
 #define NEG_HALF_LOG2E (-0.72134752044448170368f)
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -198,15 +185,6 @@ __device__ __forceinline__ void stage_record(const float4 &n0, const float4 &n1,
     }
 }
 
-// The gathered row of the NEXT batch must stay untouched in the registers it was loaded into until the per-entry loop of the current
-// batch is over: any earlier "use" -- even a register copy the allocator inserts to split a live range -- makes the compiler wait for
-// the gather before the loop, i.e. exposes one memory round trip per batch.  Passing the sixteen components through an empty asm
-// AFTER the loop makes that the first use.
-__device__ __forceinline__ void first_use_here(float4 &a, float4 &b, float4 &c, float4 &d) {
-    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w),
-                      "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w), "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));
-}
-
 __device__ __forceinline__ int wave_min_i32(int v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v = min(v, __shfl_xor(v, d));
@@ -221,9 +199,6 @@ __device__ __forceinline__ int wave_max_i32(int v) {
 // The rectangle of the live pixels of a tile whose lanes own FIXED pixels (lane -> column lane & 15, row (lane >> 4) + 4 p of slot p): from the four
 // live masks, on the scalar unit -- the same numbers as four wave-wide min / max reductions (24 cross-lane moves) at a batch boundary where pixels froze.
 // tx0 / ty0: the tile's first pixel column / row (1-based).  No live pixel: (2^20, -1, 2^20, -1), as the reductions over nothing give.
-#ifndef GS_RECT_FROM_MASKS
-#define GS_RECT_FROM_MASKS 1
-#endif
 struct LiveRectAcc {
     uint64_t any = 0; uint32_t rows = 0;
     __device__ __forceinline__ void slot(const int p, const uint64_t m) {   // one slot's live mask at a time (few scalar registers alive)
@@ -253,6 +228,125 @@ __device__ __forceinline__ Entry load_entry(const float4 *sp, const float *syhi,
     return e;
 }
 
+// ---------------------------------------------------------------- the walk both kernels share
+// the rectangle of the live pixels at the start, when every pixel of the wave's strips (`own`) inside the image is live (no reduction needed);
+// ty0: the tile's first pixel row (1-based)
+__device__ __forceinline__ void start_rect(const GsCompositeArgs &a, const int tile, const int ty0, const uint32_t own, int &qx0, int &qx1, int &qy0, int &qy1) {
+    qx0 = (tile % a.gx) * GS_TILE + 1; qx1 = min(qx0 + GS_TILE - 1, a.W);
+    qy0 = ty0 + 4 * (int)__builtin_ctz(own); qy1 = min(ty0 + 4 * (31 - (int)__builtin_clz(own)) + 3, a.H);
+}
+
+// the payload row of gaussian g
+__device__ __forceinline__ void load_row(const float4 *pay4, const size_t g, float4 &n0, float4 &n1, float4 &n2, float4 &n3) {
+    n0 = pay4[4 * g]; n1 = pay4[4 * g + 1]; n2 = pay4[4 * g + 2]; n3 = pay4[4 * g + 3];
+}
+
+// The gathered row of the NEXT batch must stay untouched in the registers it was loaded into until the per-entry loop of the current
+// batch is over: any earlier "use" -- even a register copy the allocator inserts to split a live range -- makes the compiler wait for
+// the gather before the loop, i.e. exposes one memory round trip per batch.  Passing the sixteen components through an empty asm
+// AFTER the loop makes that the first use.
+__device__ __forceinline__ void first_use_here(float4 &a, float4 &b, float4 &c, float4 &d) {
+    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w),
+                      "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w), "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));
+}
+
+// a batch of cnt entries compacted to the ones that can matter (CULL; else all of them): this lane's slot among them, and their number
+struct Kept { bool keep; int slot, nk; };
+template <bool CULL>
+__device__ __forceinline__ Kept compact_batch(const bool keep, const int lane, const int cnt) {
+    if (!CULL) return Kept{true, lane, cnt};
+    const bool k = keep && lane < cnt;
+    const uint64_t m = __ballot(k);
+    return Kept{k, slot_of(m), (int)__popcll(m)};
+}
+
+// a split tile's slot (snapshots, seg_len): 8 x position in its XCD's list + XCD, from the workgroup b of the order that holds its first part
+__device__ __forceinline__ int order_slot(const int b, const int front) { return (b < front ? ((b >> 3) / 3) : ((b - front) >> 3)) * 8 + (b & 7); }
+
+// live strip slots of the first nk staged entries (bit j of mq[p]: strip p of entry j is live)
+__device__ __forceinline__ unsigned long long strip_slots(const uint64_t (&mq)[4], const int nk) {
+    const uint64_t below = nk >= 64 ? ~0ull : ((1ull << nk) - 1ull);
+    return (unsigned long long)(__popcll(mq[0] & below) + __popcll(mq[1] & below) + __popcll(mq[2] & below) + __popcll(mq[3] & below));
+}
+
+// ---------------------------------------------------------------- debug clocks
+// The record of one tile (or workgroup) of a gs_debug_tile_clock launch: GsCompositeArgs.tile_clock says what its GS_TILE_CLOCK_WORDS words mean.
+// The tile functions tell it where they are; only the CLK instantiations carry anything -- the production kernels get the empty form.
+// forward: the record of the forward, which also carries the three packing histograms and word 14.
+template <bool CLK> struct TileClock {
+    __device__ __forceinline__ TileClock(bool) {}
+    __device__ __forceinline__ void start() {}
+    __device__ __forceinline__ void walk_begins() {}
+    __device__ __forceinline__ void batch(bool, uint64_t, uint64_t, uint64_t, uint64_t) {}
+    __device__ __forceinline__ void staged() {}
+    __device__ __forceinline__ void tile_rect(const float4 &, const float4 &, const float4 &, int, int, bool) {}
+    __device__ __forceinline__ void entries_done(int, unsigned long long) {}
+    __device__ __forceinline__ void store(const GsCompositeArgs &, int, uint32_t, uint32_t) {}
+};
+template <> struct TileClock<true> {
+    const bool forward;
+    __device__ __forceinline__ TileClock(const bool fwd) : forward(fwd) {}
+    unsigned long long t0 = 0, t_loop = 0, t_stage = 0, t_mark = 0;     // start (s_memrealtime); shader cycles (s_memtime) inside / outside the per-entry loops, and the last reading
+    // per-entry strip slots executed, the slots live pixels compacted to 64 per slot would need, the strips with any live pixel, and live
+    // pixels, each summed over the evaluated entries (frozen-pixel work inside live strips)
+    unsigned long long exec = 0, ideal = 0, alive = 0, pix = 0;
+    uint32_t live = 0, strips = 0;                                      // live pixels / strips with a live pixel in this batch
+    // ... and (forward), for three ways of packing the live pixels into fewer 64-lane slots, the evaluated entries by the slots K = 1 .. 4 they
+    // would run on: any pixel anywhere (K = ceil(live / 64)); whole pixel ROWS moved (a lane keeps its column: K = ceil(rows with a
+    // live pixel / 4)); pixels moved inside their COLUMN (K = ceil(fullest column / 4))
+    uint32_t hist[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    int k[3] = {4, 4, 4};
+    uint32_t bbkeep = 0;                                                // ... and the entries the no-op test would keep against the whole tile
+    __device__ __forceinline__ void start() { t0 = __builtin_amdgcn_s_memrealtime(); }
+    __device__ __forceinline__ void walk_begins() { t_mark = __builtin_amdgcn_s_memtime(); }
+    // a batch boundary (refresh) with the live masks of the four slots
+    __device__ __forceinline__ void batch(const bool refresh, const uint64_t m0, const uint64_t m1, const uint64_t m2, const uint64_t m3) {
+        if (!refresh) return;
+        const uint64_t lm[4] = {m0, m1, m2, m3};
+        live = 0; strips = 0;
+        uint32_t rows = 0, cmax = 0, colcnt[16] = {};
+#pragma unroll
+        for (int p = 0; p < 4 && forward; ++p) {
+            for (int r4 = 0; r4 < 4; ++r4) rows += ((lm[p] >> (16 * r4)) & 0xFFFFull) ? 1u : 0u;
+            for (int c = 0; c < 16; ++c) colcnt[c] += (uint32_t)__popcll(lm[p] & (0x0001000100010001ull << c));
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) { live += (uint32_t)__popcll(lm[p]); strips += lm[p] ? 1u : 0u; }
+        for (int c = 0; c < 16; ++c) cmax = max(cmax, colcnt[c]);
+        k[0] = (int)((live + 63u) >> 6); k[1] = (int)((rows + 3u) >> 2); k[2] = (int)((cmax + 3u) >> 2);
+    }
+    __device__ __forceinline__ void staged() { const unsigned long long t = __builtin_amdgcn_s_memtime(); t_stage += t - t_mark; t_mark = t; }
+    // forward: would the no-op test keep this lane's entry (`listed`: the lane has one) against the whole tile?
+    __device__ __forceinline__ void tile_rect(const float4 &n0, const float4 &n1, const float4 &n3, const int tx0, const int ty0, const bool listed) {
+        bool k2; uint32_t st2;
+        stage_record<false>(n0, n1, n3, tx0, tx0 + GS_TILE - 1, ty0, ty0 + GS_TILE - 1, ty0, k2, st2);
+        bbkeep += (uint32_t)__popcll(__ballot(k2 && listed));
+    }
+    // the per-entry loop over nk entries is done, `slots` strip slots executed (forward: K per entry; backward: strip_slots())
+    __device__ __forceinline__ void entries_done(const int nk, const unsigned long long slots) {
+        const unsigned long long t = __builtin_amdgcn_s_memtime(); t_loop += t - t_mark; t_mark = t;
+        exec += slots; ideal += (unsigned long long)nk * ((live + 63u) >> 6);
+        alive += (unsigned long long)nk * strips; pix += (unsigned long long)nk * live;
+#pragma unroll
+        for (int i = 0; i < 12 && forward; ++i) hist[i >> 2][i & 3] += k[i >> 2] == (i & 3) + 1 ? (uint32_t)nk : 0u;   // (constant indices: the record stays in registers)
+    }
+    __device__ __forceinline__ void store(const GsCompositeArgs &a, const int tile, const uint32_t walked, const uint32_t evaluated) const {
+        if (!a.tile_clock || threadIdx.x != 0) return;
+        unsigned long long *c = a.tile_clock + GS_TILE_CLOCK_WORDS * (size_t)(a.clock_by_block ? (int)blockIdx.x : tile);
+        c[0] = t0; c[1] = __builtin_amdgcn_s_memrealtime(); c[2] = wave_hw_id();
+        c[3] = ((unsigned long long)walked << 32) | evaluated;
+        c[4] = t_loop; c[5] = t_stage;
+        c[6] = (exec << 32) | (ideal & 0xFFFFFFFFull); c[7] = (alive << 32) | (pix & 0xFFFFFFFFull);
+        if (!forward) return;
+        c[14] = bbkeep;
+#pragma unroll
+        for (int w = 0; w < 3; ++w) {
+            c[8 + 2 * w] = ((unsigned long long)hist[w][0] << 32) | hist[w][1];
+            c[9 + 2 * w] = ((unsigned long long)hist[w][2] << 32) | hist[w][3];
+        }
+    }
+};
+
 // ---------------------------------------------------------------- capped lists: the wave writes the rest of its tile's list itself
 // gs_bin wrote the tile's list only up to the end of a segment of its super-tile's coarse list (GsBin3Args.cap_src: what the view
 // slot's previous forward walked, and a quarter more).  A forward wave that gets to the written end with pixels still taking
@@ -268,8 +362,7 @@ __device__ __forceinline__ uint32_t extend_tile_list(const GsCompositeArgs &a, c
     const int S = (ty >> sbs) * a.sgx + (tx >> sbs);
     const uint32_t lx = (uint32_t)tx & sm, ly = (uint32_t)ty & sm;
     const uint32_t c1 = a.cranges[2 * S + 1];
-    const uint32_t seg = (uint32_t)gs_bin3_seg_const();
-    const uint32_t e_end = min(cont + seg, c1);
+    const uint32_t e_end = min(cont + (uint32_t)L2_SEG, c1);
     for (uint32_t e0 = cont; e0 < e_end; e0 += GS_WAVE) {
         const uint32_t e = e0 + (uint32_t)lane;
         bool hit = false;
@@ -290,6 +383,9 @@ __device__ __forceinline__ uint32_t extend_tile_list(const GsCompositeArgs &a, c
 }
 
 // ---------------------------------------------------------------- forward
+// the column of the pixel in slot p: the lane's own while the tile's pixels are in place (K = 4), else the packed slot's, kept in fy[2], fy[3]
+template <bool PACK>
+__device__ __forceinline__ float slot_column(const int K, const float fx, const float (&fy)[4], const int p) { return (!PACK || K == 4) ? fx : fy[2 + (p & 1)]; }
 template <bool EARLY, bool CULL, bool CLK, bool SLAB, bool SNAP = false>
 // SNAP: the launch order has split tiles whose backward runs as list segments: their forward waves leave snapshots (GsCompositeArgs.snap).
 // An instantiation of its own, chosen by the host from the order kernel's count of split tiles: the snapshot code costs the ordinary
@@ -320,8 +416,8 @@ __device__ __forceinline__ void forward_tile(const GsCompositeArgs &a, const int
     const bool capped = !SLAB && EARLY && a.tile_ext != nullptr;
     if (capped) { const uint2 ex = a.tile_ext[tile]; s1 = s0 + ex.x; cont = ex.y; }
     const int ty0 = py0 - (lane >> 4);                             // first pixel row of the tile (1-based)
-    unsigned long long clk0 = 0;
-    if (CLK) clk0 = __builtin_amdgcn_s_memrealtime();
+    TileClock<CLK> clk(true);
+    clk.start();
 
     // Slab frames (binning in depth slabs): the tile's list arrives in several rounds.  A later round resumes the
     // pixel state the previous one left in image / trans and in tile_dead (four 64-bit lane masks per tile: pixel slot p of
@@ -336,7 +432,7 @@ __device__ __forceinline__ void forward_tile(const GsCompositeArgs &a, const int
     float Cr[4], Cg[4], Cb[4], T[4], fy[4];
     bool dead[4];
     uint32_t walked = 0, evaluated = 0;
-    constexpr bool PACK = GS_FWD_PACK && EARLY && !SLAB;
+    constexpr bool PACK = EARLY && !SLAB;
     const uint32_t own = (EARLY && !SLAB) ? strips_of_part(nparts, part) : 0xFu;   // several waves per tile: the strips this wave composites
     bool first_pack = PACK && nparts > 1;                              // ... packed into K = 2 / 1 slots at the first batch
     int K = 4;                                                          // slots per entry: 4 = the tile's pixels in place; 2 / 1 = live pixels packed
@@ -371,48 +467,32 @@ __device__ __forceinline__ void forward_tile(const GsCompositeArgs &a, const int
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             if (!dead[p]) {
-                const int x = (int)((!PACK || K == 4) ? fx : fy[2 + (p & 1)]), y = (int)fy[p];
+                const int x = (int)slot_column<PACK>(K, fx, fy, p), y = (int)fy[p];
                 lx0 = min(lx0, x); lx1 = max(lx1, x); ly0 = min(ly0, y); ly1 = max(ly1, y);
             }
         }
         qx0 = wave_min_i32(lx0); qx1 = wave_max_i32(lx1); qy0 = wave_min_i32(ly0); qy1 = wave_max_i32(ly1);
-        if (!GS_LIVE_RECT) { qx0 = (tile % a.gx) * GS_TILE + 1; qx1 = qx0 + GS_TILE - 1; qy0 = ty0; qy1 = ty0 + GS_TILE - 1; }
     };
-    {   // at the start every pixel inside the image is live: the tile's rectangle clipped to the image (no reduction needed), unless a
-        // slab round resumes with frozen pixels
-        qx0 = (tile % a.gx) * GS_TILE + 1; qx1 = min(qx0 + GS_TILE - 1, a.W);
-        qy0 = ty0 + 4 * (int)__builtin_ctz(own); qy1 = min(ty0 + 4 * (31 - (int)__builtin_clz(own)) + 3, a.H);
-        if (SLAB && a.resume) live_rect();
-    }
+    start_rect(a, tile, ty0, own, qx0, qx1, qy0, qy1);
+    if (SLAB && a.resume) live_rect();                                  // (... unless a slab round resumes with frozen pixels)
     const float4 *pay4 = reinterpret_cast<const float4 *>(a.payload);
     float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0, n2 = n0, n3 = n0;
     uint32_t pos = s0 + lane;
-    // Gathers run ahead of their use: the payload rows one batch (held in n0..n2 while the previous batch is composited), the
+    // Gathers run ahead of their use: the payload rows one batch (held in n0..n3 while the previous batch is composited), the
     // ids they are addressed by TWO batches (id2), so that the row loads of the next batch are issued from a register instead of
     // behind a second dependent round trip to memory.  A tile whose batches keep few entries (light tiles, the ones that run
-    // when the chip is emptying) is bound by exactly this chain: one exposed load latency per batch instead of two.
+    // when the chip is emptying) is bound by exactly this chain: one exposed load latency per batch instead of two.  Its two steps
+    // (before the first batch; after a batch is staged) are written out here and in backward_tile, three lines each: as shared
+    // functions they changed the register allocation of seventeen kernels.
     uint32_t id2 = 0;
     uint32_t gp = gp0;                                                  // list position of `base` in the tile's whole list
     uint32_t base = s0;
-    unsigned long long t_loop = 0, t_stage = 0, t_mark = 0;             // debug clocks (a.tile_clock): shader cycles inside / outside the per-entry loops
-    // debug (a.tile_clock): per-entry strip slots executed, the slots live pixels compacted to 64 per slot would need, the strips with
-    // any live pixel, and live pixels, each summed over the evaluated entries (frozen-pixel work inside live strips)
-    unsigned long long clk_exec = 0, clk_ideal = 0, clk_alive = 0, clk_pix = 0;
-    uint32_t clk_live = 0, clk_strips = 0;
-    // ... and, for three ways of packing the live pixels into fewer 64-lane slots, the evaluated entries by the slots K = 1 .. 4 they
-    // would run on: any pixel anywhere (K = ceil(live / 64)); whole pixel ROWS moved (a lane keeps its column: K = ceil(rows with a
-    // live pixel / 4)); pixels moved inside their COLUMN (K = ceil(fullest column / 4))
-    uint32_t clk_hist[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-    int clk_k[3] = {4, 4, 4};
-    uint32_t clk_bbkeep = 0;                                            // ... and the entries the no-op test would keep against the whole tile
-    if (CLK) t_mark = __builtin_amdgcn_s_memtime();
+    clk.walk_begins();
     for (;;) {                                                          // (capped lists: once more per segment the wave appends itself)
     bool stopped = false;
-    {
-        const uint32_t pos2 = pos + min((uint32_t)CB - (gp & (CB - 1)), s1 - base);     // first position of the second batch + lane
-        if (pos < s1) { const size_t g = a.ids[pos]; n0 = pay4[4 * g]; n1 = pay4[4 * g + 1]; n2 = pay4[4 * g + 2]; n3 = pay4[4 * g + 3]; }
-        if (pos2 < s1) id2 = a.ids[pos2];
-    }
+    const uint32_t second = pos + min((uint32_t)CB - (gp & (CB - 1)), s1 - base);       // first position of the second batch + lane
+    if (pos < s1) load_row(pay4, a.ids[pos], n0, n1, n2, n3);
+    if (second < s1) id2 = a.ids[second];
     for (; base < s1;) {
         const uint32_t phase = gp & (CB - 1);
         const int cnt = (int)min((uint32_t)CB - phase, s1 - base);      // batches end at multiples of CB of the WHOLE list
@@ -421,7 +501,7 @@ __device__ __forceinline__ void forward_tile(const GsCompositeArgs &a, const int
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 if (!dead[p] && T[p] < a.t_min) {                        // frozen from here on: its transmittance is final
-                    const float x = (!PACK || K == 4) ? fx : fy[2 + (p & 1)];
+                    const float x = slot_column<PACK>(K, fx, fy, p);
                     if (a.trans) a.trans[(uint32_t)((int)x - 1) + (uint32_t)a.W * (uint32_t)((int)fy[p] - 1)] = T[p];
                     if (SNAP && snap_slot >= 0) {                        // ... and every later snapshot says so (NaN: no segment takes this pixel up again)
                         const int nsn = a.seg_hist ? a.seg_n - 1 : GS_SEG_MAX - 1;      // snapshots per tile
@@ -446,7 +526,7 @@ __device__ __forceinline__ void forward_tile(const GsCompositeArgs &a, const int
                     // (1) the pixels that are dropped are final: their colour goes to memory now (their transmittance went when they froze)
 #pragma unroll
                     for (int p = 0; p < 4; ++p) {
-                        const float x = K == 4 ? fx : fy[2 + (p & 1)];
+                        const float x = slot_column<PACK>(K, fx, fy, p);
                         const bool mine = K == 4 ? (px <= a.W && py0 + 4 * p <= a.H && ((own >> p) & 1u)) : (p < 2 && x > 0.5f);
                         if (mine && dead[p] && a.image) {
                             const uint32_t o = (uint32_t)((int)x - 1) + (uint32_t)a.W * (uint32_t)((int)fy[p] - 1);
@@ -462,7 +542,7 @@ __device__ __forceinline__ void forward_tile(const GsCompositeArgs &a, const int
                     for (int p = 0; p < 4; ++p) {
                         if (!dead[p]) {
                             const uint32_t r = rb + (uint32_t)slot_of(lm[p]);
-                            buf[r] = K == 4 ? fx : fy[2 + (p & 1)]; buf[128 + r] = fy[p];
+                            buf[r] = slot_column<PACK>(K, fx, fy, p); buf[128 + r] = fy[p];
                             buf[256 + r] = Cr[p]; buf[384 + r] = Cg[p]; buf[512 + r] = Cb[p]; buf[640 + r] = T[p];
                         }
                         rb += (uint32_t)__popcll(lm[p]);
@@ -491,7 +571,7 @@ __device__ __forceinline__ void forward_tile(const GsCompositeArgs &a, const int
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     if (!dead[p]) {
-                        const float x = (!PACK || K == 4) ? fx : fy[2 + (p & 1)];
+                        const float x = slot_column<PACK>(K, fx, fy, p);
                         const int idx = ((int)fy[p] - ty0) * GS_TILE + ((int)x - (px - (lane & 15)));
                         sn[idx] = Cr[p]; sn[256 + idx] = Cg[p]; sn[512 + idx] = Cb[p]; sn[768 + idx] = T[p];
                     }
@@ -499,40 +579,16 @@ __device__ __forceinline__ void forward_tile(const GsCompositeArgs &a, const int
             }
             next_snap += seg_len;
         }
-        if (CLK && (phase == 0 || base == s0)) {                         // debug: live pixels / strips with a live pixel in this batch
-            clk_live = 0; clk_strips = 0;
-            uint32_t rows = 0, colcnt[16];
-            for (int cidx = 0; cidx < 16; ++cidx) colcnt[cidx] = 0;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const uint64_t m = __ballot(!dead[p]); clk_live += (uint32_t)__popcll(m); clk_strips += m ? 1u : 0u;
-                for (int r4 = 0; r4 < 4; ++r4) rows += ((m >> (16 * r4)) & 0xFFFFull) ? 1u : 0u;
-                for (int cidx = 0; cidx < 16; ++cidx) colcnt[cidx] += (uint32_t)__popcll(m & (0x0001000100010001ull << cidx));
-            }
-            uint32_t cmax = 0;
-            for (int cidx = 0; cidx < 16; ++cidx) cmax = max(cmax, colcnt[cidx]);
-            clk_k[0] = (int)((clk_live + 63u) >> 6); clk_k[1] = (int)((rows + 3u) >> 2); clk_k[2] = (int)((cmax + 3u) >> 2);
-        }
+        clk.batch(phase == 0 || base == s0, __ballot(!dead[0]), __ballot(!dead[1]), __ballot(!dead[2]), __ballot(!dead[3]));
 #if GS_FWD_NO_PREFETCH                                                  // measurement build (tools/fwd_traffic_split.sh): the rows of a batch are gathered
-        if (base > s0 && pos < s1) {                                    // only once the tile is known to go on: nothing is fetched for nobody
-            const size_t g = a.ids[pos]; n0 = pay4[4 * g]; n1 = pay4[4 * g + 1]; n2 = pay4[4 * g + 2]; n3 = pay4[4 * g + 3];
-        }
+        if (base > s0 && pos < s1) load_row(pay4, a.ids[pos], n0, n1, n2, n3);   // only once the tile is known to go on: nothing is fetched for nobody
 #endif
         uint32_t strips;
         bool keep;
         stage_record<false>(n0, n1, n3, qx0, qx1, qy0, qy1, ty0, keep, strips);
-        int slot = lane, nk = cnt;
-        if (!CULL) keep = true;
-        if (CULL) {                                                     // compact the batch to the entries that can matter
-            keep = keep && lane < cnt;
-            const uint64_t m = __ballot(keep);
-            slot = slot_of(m); nk = __popcll(m);
-        }
-        if (CLK && CULL) {                                              // debug: what the tile's own rectangle would have kept
-            bool k2; uint32_t st2;
-            stage_record<false>(n0, n1, n3, px - (lane & 15), px - (lane & 15) + GS_TILE - 1, ty0, ty0 + GS_TILE - 1, ty0, k2, st2);
-            clk_bbkeep += (uint32_t)__popcll(__ballot(k2 && lane < cnt));
-        }
+        const Kept kb = compact_batch<CULL>(keep, lane, cnt);
+        const int slot = kb.slot, nk = kb.nk; keep = kb.keep;
+        if (CULL) clk.tile_rect(n0, n1, n3, px - (lane & 15), ty0, lane < cnt);
         __syncthreads();                                                // one wave: orders LDS reads/writes only
         if (keep) {
             sp[3 * slot] = n0; sp[3 * slot + 1] = n1; sp[3 * slot + 2] = n2;
@@ -542,13 +598,11 @@ __device__ __forceinline__ void forward_tile(const GsCompositeArgs &a, const int
         base += (uint32_t)cnt; gp += (uint32_t)cnt;
         pos = base + lane;
 #if !GS_FWD_NO_PREFETCH
-        {
-            if (pos < s1) { const size_t g = id2; n0 = pay4[4 * g]; n1 = pay4[4 * g + 1]; n2 = pay4[4 * g + 2]; n3 = pay4[4 * g + 3]; }
-            const uint32_t pos2 = pos + min((uint32_t)CB, s1 - base);                   // (batches after the first start at multiples of CB)
-            if (base < s1 && pos2 < s1) id2 = a.ids[pos2];
-        }
+        if (pos < s1) load_row(pay4, id2, n0, n1, n2, n3);
+        const uint32_t pos2 = pos + min((uint32_t)CB, s1 - base);                       // (batches after the first start at multiples of CB)
+        if (base < s1 && pos2 < s1) id2 = a.ids[pos2];
 #endif
-        if (CLK) { const unsigned long long t = __builtin_amdgcn_s_memtime(); t_stage += t - t_mark; t_mark = t; }
+        clk.staged();
 // one pixel slot p of one entry (A0, B0: the column terms of the slot's x)
 #define GS_FWD_PIXEL(e, A0, B0, p) do {                                               \
             const float dY = fy[p] - (e).q0.y;                                              \
@@ -593,12 +647,7 @@ __device__ __forceinline__ void forward_tile(const GsCompositeArgs &a, const int
 #undef GS_FWD_COLUMN
         walked += (uint32_t)cnt; evaluated += (uint32_t)nk;
         first_use_here(n0, n1, n2, n3);
-        if (CLK) {
-            const unsigned long long t = __builtin_amdgcn_s_memtime(); t_loop += t - t_mark; t_mark = t;
-            clk_exec += (unsigned long long)K * (uint32_t)nk; clk_ideal += (unsigned long long)nk * ((clk_live + 63u) >> 6);
-            clk_alive += (unsigned long long)nk * clk_strips; clk_pix += (unsigned long long)nk * clk_live;
-            for (int w = 0; w < 3; ++w) if (clk_k[w] >= 1 && clk_k[w] <= 4) clk_hist[w][clk_k[w] - 1] += (uint32_t)nk;
-        }
+        clk.entries_done(nk, (unsigned long long)K * (uint32_t)nk);
     }
     if (!capped || stopped || cont == GS_CONT_NONE) break;
     // the written list is used up, its pixels still take entries and the super-tile's list goes on: append the next segment's hits
@@ -648,18 +697,7 @@ __device__ __forceinline__ void forward_tile(const GsCompositeArgs &a, const int
             }
         }
     }
-    if (CLK && a.tile_clock && lane == 0) {
-        unsigned long long *c = a.tile_clock + GS_TILE_CLOCK_WORDS * (size_t)(a.clock_by_block ? (int)blockIdx.x : tile);
-        c[0] = clk0; c[1] = __builtin_amdgcn_s_memrealtime(); c[2] = wave_hw_id();
-        c[3] = ((unsigned long long)walked << 32) | evaluated;
-        c[4] = t_loop; c[5] = t_stage;
-        c[6] = (clk_exec << 32) | (clk_ideal & 0xFFFFFFFFull); c[7] = (clk_alive << 32) | (clk_pix & 0xFFFFFFFFull);
-        c[14] = clk_bbkeep;
-        for (int w = 0; w < 3; ++w) {
-            c[8 + 2 * w] = ((unsigned long long)clk_hist[w][0] << 32) | clk_hist[w][1];
-            c[9 + 2 * w] = ((unsigned long long)clk_hist[w][2] << 32) | clk_hist[w][3];
-        }
-    }
+    clk.store(a, tile, walked, evaluated);
 }
 
 template <bool EARLY, int MINW, bool CULL, bool CLK = false, bool SLAB = false, bool SNAP = false>
@@ -681,7 +719,7 @@ __global__ __launch_bounds__(64, MINW) void composite_fwd_kernel(GsCompositeArgs
         sl = gs_seg_len_all(a.seg_hist[tile], a.seg_n);
         if (sl) snap_slot = tile;
     } else if (SNAP && EARLY && !SLAB && a.snap && nparts > 1 && a.parts <= 1) {  // a split tile of the order: its slot = 8 x position in the XCD's list + XCD
-        const int b = (int)blockIdx.x, slot = (b < a.front ? ((b >> 3) / 3) : ((b - a.front) >> 3)) * 8 + (b & 7);
+        const int slot = order_slot((int)blockIdx.x, a.front);
         sl = a.seg_len[slot];
         if (sl) snap_slot = slot;
     }
@@ -776,8 +814,8 @@ __device__ __forceinline__ void backward_tile(const GsCompositeArgs &a, const in
     const float fx = (float)px;
     const size_t plane = (size_t)a.W * a.H;
     const int ty0 = py0 - (lane >> 4);
-    unsigned long long clk0 = 0;
-    if (CLK) clk0 = __builtin_amdgcn_s_memrealtime();
+    TileClock<CLK> clk(false);
+    clk.start();
     // transposed reduction: lane (c, s) = (rl >> 2, rl & 3) sums quarter s of component c; lanes >= 36 mirror lanes 0..27
     // (same addresses: broadcasts, no bank conflicts), their sums are not used
     const int rl = lane < 36 ? lane : lane - 36;
@@ -818,23 +856,12 @@ __device__ __forceinline__ void backward_tile(const GsCompositeArgs &a, const in
     // the same batch boundaries, so the same entries are evaluated)
     int qx0, qx1, qy0, qy1;
     auto live_rect = [&]() {
-        if (GS_RECT_FROM_MASKS && GS_LIVE_RECT) {
-            LiveRectAcc acc;
+        LiveRectAcc acc;
 #pragma unroll
-            for (int p = 0; p < 4; ++p) acc.slot(p, __ballot(!dead[p]));
-            acc.rect(px - (lane & 15), ty0, qx0, qx1, qy0, qy1);
-            return;
-        }
-        int lx0 = 1 << 20, lx1 = -1, ly0 = 1 << 20, ly1 = -1;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            if (!dead[p]) { const int x = (int)fx, y = (int)fy[p]; lx0 = min(lx0, x); lx1 = max(lx1, x); ly0 = min(ly0, y); ly1 = max(ly1, y); }
-        }
-        qx0 = wave_min_i32(lx0); qx1 = wave_max_i32(lx1); qy0 = wave_min_i32(ly0); qy1 = wave_max_i32(ly1);
-        if (!GS_LIVE_RECT) { qx0 = (tile % a.gx) * GS_TILE + 1; qx1 = qx0 + GS_TILE - 1; qy0 = ty0; qy1 = ty0 + GS_TILE - 1; }
+        for (int p = 0; p < 4; ++p) acc.slot(p, __ballot(!dead[p]));
+        acc.rect(px - (lane & 15), ty0, qx0, qx1, qy0, qy1);
     };
-    qx0 = (tile % a.gx) * GS_TILE + 1; qx1 = min(qx0 + GS_TILE - 1, a.W);   // every pixel of the part's strips inside the image is live
-    qy0 = ty0 + 4 * (int)__builtin_ctz(own); qy1 = min(ty0 + 4 * (31 - (int)__builtin_clz(own)) + 3, a.H);
+    start_rect(a, tile, ty0, own, qx0, qx1, qy0, qy1);
     if (snap_in) live_rect();                                               // (... except those the snapshot says were frozen by then)
     const float4 *pay4 = reinterpret_cast<const float4 *>(a.payload);
     float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0, n2 = n0, n3 = n0;
@@ -854,10 +881,7 @@ __device__ __forceinline__ void backward_tile(const GsCompositeArgs &a, const in
     uint32_t gp = seg_start;                                              // (a multiple of CB)
     uint32_t alive = own;                                                 // strips with a live pixel (refreshed at every batch boundary)
     bool stop = false;
-    unsigned long long t_loop = 0, t_stage = 0, t_mark = 0;               // debug clocks (a.tile_clock)
-    unsigned long long clk_exec = 0, clk_ideal = 0, clk_alive = 0, clk_pix = 0;   // (see the forward)
-    uint32_t clk_live = 0, clk_strips = 0;
-    if (CLK) t_mark = __builtin_amdgcn_s_memtime();
+    clk.walk_begins();
     for (int sg = 0; sg < a.nseg && !stop; ++sg) {
     const uint32_t *ids = a.seg_ids[sg];
     const uint32_t r0s = a.seg_ranges[sg][2 * tile];
@@ -867,11 +891,9 @@ __device__ __forceinline__ void backward_tile(const GsCompositeArgs &a, const in
     const uint32_t s0 = min(r1s, r0s + seg_start), s1 = seg_end < r1s - r0s ? r0s + seg_end : r1s;
     uint32_t pos = s0 + lane;
     uint32_t id2 = 0;                                                     // ids run two batches ahead, payload rows one (see the forward)
-    {
-        const uint32_t pos2 = pos + min((uint32_t)CB - (gp & (CB - 1)), s1 - s0);
-        if (pos < s1) { nid = ids[pos]; n0 = pay4[4 * (size_t)nid]; n1 = pay4[4 * (size_t)nid + 1]; n2 = pay4[4 * (size_t)nid + 2]; n3 = pay4[4 * (size_t)nid + 3]; }
-        if (pos2 < s1) id2 = ids[pos2];
-    }
+    const uint32_t second = pos + min((uint32_t)CB - (gp & (CB - 1)), s1 - s0);
+    if (pos < s1) { nid = ids[pos]; load_row(pay4, nid, n0, n1, n2, n3); }
+    if (second < s1) id2 = ids[second];
     for (uint32_t base = s0; base < s1;) {
         const uint32_t phase = gp & (CB - 1);
         const int cnt = (int)min((uint32_t)CB - phase, s1 - base);
@@ -887,23 +909,14 @@ __device__ __forceinline__ void backward_tile(const GsCompositeArgs &a, const in
             if (alive == 0u) { stop = true; break; }
             if (__ballot(froze) != 0ull) live_rect();
         }
-        if (CLK && (phase == 0 || gp == 0)) {
-            clk_live = 0; clk_strips = 0;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) { const uint64_t m = __ballot(!dead[p]); clk_live += (uint32_t)__popcll(m); clk_strips += m ? 1u : 0u; }
-        }
+        clk.batch(phase == 0 || gp == 0, __ballot(!dead[0]), __ballot(!dead[1]), __ballot(!dead[2]), __ballot(!dead[3]));
         uint32_t strips;
         bool keep;
         stage_record<CULL>(n0, n1, n3, qx0, qx1, qy0, qy1, ty0, keep, strips);
         if (CULL && EARLY) strips &= alive;                                 // a strip of frozen pixels (T = S = 0) adds exact zeros
-        int slot = lane, nk = cnt;
-        if (!CULL) keep = true;
+        const Kept kb = compact_batch<CULL>(keep, lane, cnt);
+        const int slot = kb.slot, nk = kb.nk; keep = kb.keep;
         uint64_t mq[4] = {~0ull, ~0ull, ~0ull, ~0ull};                    // bit k: strip p of the k-th staged entry is live
-        if (CULL) {
-            keep = keep && lane < cnt;
-            const uint64_t m = __ballot(keep);
-            slot = slot_of(m); nk = __popcll(m);
-        }
         __syncthreads();
         if (keep) {
             sp[3 * slot] = n0; sp[3 * slot + 1] = n1; sp[3 * slot + 2] = n2;
@@ -923,12 +936,10 @@ __device__ __forceinline__ void backward_tile(const GsCompositeArgs &a, const in
         };
         base += (uint32_t)cnt; gp += (uint32_t)cnt;
         pos = base + lane;
-        if (pos < s1) { nid = id2; n0 = pay4[4 * (size_t)nid]; n1 = pay4[4 * (size_t)nid + 1]; n2 = pay4[4 * (size_t)nid + 2]; n3 = pay4[4 * (size_t)nid + 3]; }
-        {
-            const uint32_t pos2 = pos + min((uint32_t)CB, s1 - base);
-            if (base < s1 && pos2 < s1) id2 = ids[pos2];
-        }
-        if (CLK) { const unsigned long long t = __builtin_amdgcn_s_memtime(); t_stage += t - t_mark; t_mark = t; }
+        if (pos < s1) { nid = id2; load_row(pay4, nid, n0, n1, n2, n3); }
+        const uint32_t pos2 = pos + min((uint32_t)CB, s1 - base);
+        if (base < s1 && pos2 < s1) id2 = ids[pos2];
+        clk.staged();
         int k = 0;
         if (PAIR) {
             float *wrow2 = wrow + RED_FLOATS;
@@ -963,13 +974,7 @@ __device__ __forceinline__ void backward_tile(const GsCompositeArgs &a, const in
         }
         walked += (uint32_t)cnt; evaluated += (uint32_t)nk;
         first_use_here(n0, n1, n2, n3);
-        if (CLK) {
-            const unsigned long long t = __builtin_amdgcn_s_memtime(); t_loop += t - t_mark; t_mark = t;
-            const uint64_t below = nk >= 64 ? ~0ull : ((1ull << nk) - 1ull);
-            clk_exec += CULL ? (unsigned long long)(__popcll(mq[0] & below) + __popcll(mq[1] & below) + __popcll(mq[2] & below) + __popcll(mq[3] & below)) : 4ull * (uint32_t)nk;
-            clk_ideal += (unsigned long long)nk * ((clk_live + 63u) >> 6);
-            clk_alive += (unsigned long long)nk * clk_strips; clk_pix += (unsigned long long)nk * clk_live;
-        }
+        clk.entries_done(nk, strip_slots(mq, nk));
     }
     }
     if (lane == 0 && part == 0) {                                         // (tile_parts > 1: the counters of a tile are those of its first part)
@@ -982,13 +987,7 @@ __device__ __forceinline__ void backward_tile(const GsCompositeArgs &a, const in
             if (a.tile_work) a.tile_work[tile] = evaluated;
         }
     }
-    if (CLK && a.tile_clock && lane == 0) {
-        unsigned long long *c = a.tile_clock + GS_TILE_CLOCK_WORDS * (size_t)(a.clock_by_block ? (int)blockIdx.x : tile);
-        c[0] = clk0; c[1] = __builtin_amdgcn_s_memrealtime(); c[2] = wave_hw_id();
-        c[3] = ((unsigned long long)walked << 32) | evaluated;
-        c[4] = t_loop; c[5] = t_stage;
-        c[6] = (clk_exec << 32) | (clk_ideal & 0xFFFFFFFFull); c[7] = (clk_alive << 32) | (clk_pix & 0xFFFFFFFFull);
-    }
+    clk.store(a, tile, walked, evaluated);
 }
 
 template <bool EARLY, int MINW, bool DET, bool CULL, bool CLK = false, bool PAIR = false>
@@ -1008,7 +1007,7 @@ __global__ __launch_bounds__(64, MINW) void composite_bwd_kernel(GsCompositeArgs
     const float *snap_in = nullptr;
     uint32_t seg_start = 0, seg_end = 0xFFFFFFFFu;
     bool seg_tile = false;
-    const int segunits = (EARLY && a.snap && !a.seg_hist) ? 8 * (a.front / 24) * (GS_SEG_MAX - 1) : 0;   // workgroups in front of the order: segments 1 .. of the heavy tiles
+    const int segunits = (EARLY && a.snap && !a.seg_hist) ? gs_seg_units(a.front) : 0;   // workgroups in front of the order: segments 1 .. of the heavy tiles
     if (EARLY && a.snap && a.seg_hist) {                                      // small grid: block b = unit b / len of tile b % len; unit = segment x parts + pixel part
         const int len = ((ntiles + 7) / 8) * 8, unit = (int)blockIdx.x / len;
         tile = (int)blockIdx.x - unit * len;
@@ -1036,7 +1035,7 @@ __global__ __launch_bounds__(64, MINW) void composite_bwd_kernel(GsCompositeArgs
         tile = tile_of_block(a, ntiles, part, nparts, segunits);
         if (tile < 0) return;
         if (segunits && nparts > 1) {                                         // a split tile: with segments its first entry is segment 0, its other parts do nothing
-            const int b = (int)blockIdx.x - segunits, slot = (b < a.front ? ((b >> 3) / 3) : ((b - a.front) >> 3)) * 8 + (b & 7);
+            const int b = (int)blockIdx.x - segunits, slot = order_slot(b, a.front);
             const uint32_t sl = a.seg_len[slot];
             if (sl) {
                 if (part) return;
@@ -1294,8 +1293,6 @@ hipError_t gs_launch_clock_probe(unsigned long long *out, hipStream_t s) {
     return hipGetLastError();
 }
 
-// workgroups in front of the order's in a backward launch: list segments 1 .. GS_SEG_MAX - 1 of the tiles that may be split (composite_bwd_kernel)
-int gs_seg_units(int front) { return 8 * (front / 24) * (GS_SEG_MAX - 1); }
 static int composite_tile_blocks(const GsCompositeArgs &a, int ntiles, bool bwd) {   // (tile_of_block computes the same length of one part)
     const int len = (a.tile_order && a.order_len > 0) ? a.order_len : ((ntiles + 7) / 8) * 8;
     if (bwd && a.snap && a.seg_hist && a.t_min > 0.0f) return len * a.seg_n * (a.parts > 1 ? a.parts : 1);   // small grid: segments x pixel parts per tile
@@ -1336,7 +1333,7 @@ hipError_t gs_launch_composite_fwd(const GsCompositeArgs &a0, hipStream_t s) {
     if (a.split_ok && (!early || a.tile_ext || a.tile_pos || a.parts > 1)) return hipErrorInvalidValue;   // split entries: frames with the early-out, full lists, one round
     if (a.snap && !a.seg_hist && (!a.split_ok || !a.seg_len || !a.snap_walked || !a.tile_order || a.front <= 0)) return hipErrorInvalidValue;
     if (a.snap && a.seg_hist && (a.tile_order || a.seg_n < 2 || a.seg_n > GS_SEG_MAX || !early || a.tile_ext || a.tile_pos)) return hipErrorInvalidValue;
-    if (a.tile_ext && (gs_bin3_seg() != L2_SEG || !early || !a.cranges || !a.cids || !a.clr || !a.ids_w || a.tile_pos)) return hipErrorInvalidValue;
+    if (a.tile_ext && (!early || !a.cranges || !a.cids || !a.clr || !a.ids_w || a.tile_pos)) return hipErrorInvalidValue;
     if (a.tile_pos) {                                                     // a round of a slab frame (t_min > 0 by construction: plan_rounds)
         if (!early || a.tile_clock) return hipErrorInvalidValue;
         // built for FOUR waves per SIMD: the resume / tile_pos / tile_done / tile_dead state needs ~120 VGPRs, and at five (96) it spilled 12-14 of them
@@ -1384,7 +1381,7 @@ hipError_t gs_launch_composite_bwd(const GsCompositeArgs &a0, hipStream_t s) {
         return hipGetLastError();
     }
     // small grids (several waves per tile: every wave alone on its SIMD): two entries in flight per wave, registers to spare (two waves per SIMD)
-    if (GS_BWD_PAIR && early && a.cull && !a.tile_order && (a.parts > 1 || a.seg_hist)) {
+    if (early && a.cull && !a.tile_order && (a.parts > 1 || a.seg_hist)) {
         if (a.g2d_fixed) hipLaunchKernelGGL((composite_bwd_kernel<true, 2, true, true, false, true>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((composite_bwd_kernel<true, 2, false, true, false, true>), grid, block, 0, s, a);
         return hipGetLastError();

@@ -7,10 +7,11 @@
   tools/compare_libs.py frames                  three frames each of C1, C3 and a forced-slab bin_path 2 frame (to run under rocprofv3 --kernel-trace)
   tools/compare_libs.py kernels DIR             digest of the ordered kernel names of the kernel trace (csv) below DIR
 
-Fixed seeds; every ctx deterministic (fixed-point gradient sums), so every array must be EQUAL.  Arrays above 4096 elements are kept as a
+Fixed seeds; every ctx whose gradients are recorded is deterministic (fixed-point gradient sums), and the two cases with float atomics
+record no gradients (C1_small_float_atomics; tile_clock: counts only), so every array must be EQUAL.  Arrays above 4096 elements are kept as a
 blake2b digest of their bytes.  A call the library refuses is recorded with its message: the refusal must be alike on both sides.
 Per frame: image, T, the five gradient arrays, tile ranges, sorted ids, sortIdxs, num_instances / _coarse_instances / _rounds,
-bin_path_of_frame, list_stats, work_counters_ex."""
+bin_path_of_frame, list_stats, work_counters_ex; and the counting words of the composite kernels' debug record on one small frame."""
 import csv, glob, hashlib, os, subprocess, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -167,6 +168,25 @@ def case_empty(R):
     R.call("empty", run)
 
 
+def case_tile_clock(R):
+    """The run-to-run stable words of the debug record (GsCompositeArgs.tile_clock): counts, not clocks.  One small frame, one wave per tile,
+    float atomics (the backward's clock kernels have no fixed-point form); records by tile in tile order (10) and in the frame's launch order (30)"""
+    from gaussiansplat_amd import backend as B, synthetic
+    sc, n, W, H, deg = scene("C1")
+    ctx = B.Context(deterministic=False, tile_parts=1, slab_mode=0)
+    set_model(ctx, sc, n, deg)
+    set_cam(ctx, W, H, 0)
+    ctx.preprocess(); ctx.bin()
+    ctx.forward_host()
+    ctx.backward(synthetic.make_dC(W, H, 1), ctx.grads_alloc(), overwrite=True)
+    for v in (10, 30):                                                  # (put, not call: a refusal here ends the record, it is not a result)
+        fwd, bwd = ctx.tile_clock(0, v), ctx.tile_clock(1, v)
+        assert (fwd[:, 3] & np.uint64(0xFFFFFFFF)).sum() > 0 and np.array_equal(fwd[:, 3], bwd[:, 3]), "tile_clock: an empty record"
+        R.put("tile_clock/fwd_variant_%d_words_3_6to14" % v, fwd[:, [3] + list(range(6, 15))])
+        R.put("tile_clock/bwd_variant_%d_words_3_6_7" % v, bwd[:, [3, 6, 7]])
+    ctx.close()
+
+
 def record(path):
     from gaussiansplat_amd import backend as B
     R = Recorder()
@@ -192,6 +212,7 @@ def record(path):
     case_3d(R, "C2_wide_cursors", "C2", frames=2, debug_flags=B.GS_DEBUG_WIDE_CURSORS)
     case_2d(R)
     case_empty(R)
+    case_tile_clock(R)
     np.savez(path, **R.out)
     print("recorded %d arrays -> %s" % (len(R.out), path))
 
