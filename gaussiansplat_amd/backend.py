@@ -30,7 +30,8 @@ SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs
            "gs_get_stage_times", "gs_get_stage_stats", "gs_get_work_counters", "gs_get_work_counters_ex", "gs_debug_time_composite",
            "gs_debug_tile_clock", "gs_debug_clock_mhz", "gs_rank_probe_result", "gs_num_rounds", "gs_set_view_slot", "gs_num_coarse_instances",
            "gs_get_list_stats", "gs_get_tile_parts", "gs_get_bin_path", "gs_debug_set_window", "gs_debug_tile_clock_rows", "gs_debug_tail_fill",
-           "gs_adam_step", "gs_backward_adam")
+           "gs_adam_step", "gs_backward_adam",
+           "gs_density_accumulate", "gs_density_decide", "gs_density_plan", "gs_density_restructure", "gs_opacity_reset")
 
 GS_ABI_VERSION = 3          # include/gsplat.h; load() refuses a library that reports another version
 GS_DEBUG_WIDE_CURSORS = 1
@@ -57,6 +58,17 @@ class GsConfig(C.Structure):
 class GsGrads(C.Structure):
     _fields_ = [("d_means", C.c_void_p), ("d_scales", C.c_void_p), ("d_quats", C.c_void_p),
                 ("d_opacities", C.c_void_p), ("d_shs", C.c_void_p)]
+
+
+class GsDensityStats(C.Structure):
+    """gs_density_stats: three caller-owned device arrays of n elements (float32, int32, int32)."""
+    _fields_ = [("grad_sum", C.c_void_p), ("count", C.c_void_p), ("max_extent", C.c_void_p)]
+
+
+class GsDensityParams(C.Structure):
+    """gs_density_params: the thresholds of gs_density_decide, already in log / logit space."""
+    _fields_ = [("struct_size", C.c_int32), ("grad_threshold", C.c_float), ("log_split_scale", C.c_float), ("log_shrink", C.c_float),
+                ("min_opacity_logit", C.c_float), ("log_max_world_scale", C.c_float), ("max_extent_px", C.c_int32)]
 
 
 class GsError(RuntimeError):
@@ -138,6 +150,11 @@ def load():
     L.gs_get_bin_path.argtypes = [vp]
     L.gs_debug_set_window.argtypes = [vp, C.c_int32, C.c_int32]
     L.gs_debug_tile_clock_rows.argtypes = [vp]
+    L.gs_density_accumulate.argtypes = [vp, C.POINTER(GsDensityStats)]
+    L.gs_density_decide.argtypes = [vp, C.POINTER(GsDensityStats), C.POINTER(GsDensityParams), vp]
+    L.gs_density_plan.argtypes = [vp, vp, C.POINTER(C.c_int64)]
+    L.gs_density_restructure.argtypes = [vp, vp, vp, G, C.c_int32, G, G, C.c_int64]
+    L.gs_opacity_reset.argtypes = [vp, C.c_float, vp, vp]
     if L.gs_abi_version() != GS_ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH} has ABI version {L.gs_abi_version()}, this binding is written for {GS_ABI_VERSION}: "
                            "rebuild with `python -m gaussiansplat_amd.build --force`")
@@ -395,6 +412,37 @@ class Context:
         f = (GS_ADAM_SELECTIVE if selective else 0) if flags is None else int(flags)
         self._chk(self.L.gs_backward_adam(self.h, C.c_void_p(int(dC_ptr)), GS_MEM_DEVICE, C.byref(exp_avg), C.byref(exp_avg_sq), lr6,
                                           beta1, beta2, eps, int(step), f))
+
+    # -- density control (3-D renderer): statistics, clone / split / prune, opacity reset
+    def density_accumulate(self, stats: GsDensityStats):
+        """gs_density_accumulate: after a non-fused backward of the frame, stats += this view (|d L / d mu'| in NDC units, visibility,
+        pixel extent).  No sync."""
+        self._chk(self.L.gs_density_accumulate(self.h, C.byref(stats)))
+
+    def density_decide(self, stats: GsDensityStats, params: GsDensityParams, action_ptr: int):
+        """gs_density_decide: action[g] = 0 keep, 1 clone, 2 split, 3 prune (int32 device array of n words).  No sync."""
+        self._chk(self.L.gs_density_decide(self.h, C.byref(stats), C.byref(params), C.c_void_p(int(action_ptr or 0))))
+
+    def density_plan(self, action_ptr: int):
+        """gs_density_plan: (survivors, clones, splits, pruned); n_out = survivors + clones + 2 * splits.  The one call that synchronises."""
+        o = (C.c_int64 * 4)()
+        self._chk(self.L.gs_density_plan(self.h, C.c_void_p(int(action_ptr or 0)), o))
+        return int(o[0]), int(o[1]), int(o[2]), int(o[3])
+
+    def density_restructure(self, action_ptr: int, noise_ptr: "int | None", dst_model: GsGrads, src_sets, dst_sets, n_out: int):
+        """gs_density_restructure: the planned model into dst_model (five device arrays of n_out rows) and the gradient-shaped
+        src_sets into dst_sets (sequences of GsGrads, up to four).  The ctx's model is not switched.  No sync."""
+        src_sets, dst_sets = list(src_sets), list(dst_sets)
+        if len(src_sets) != len(dst_sets):
+            raise ValueError("density_restructure: one destination per source set")
+        k = len(src_sets)
+        sa, da = (GsGrads * max(k, 1))(*src_sets), (GsGrads * max(k, 1))(*dst_sets)
+        self._chk(self.L.gs_density_restructure(self.h, C.c_void_p(int(action_ptr or 0)), C.c_void_p(int(noise_ptr or 0)), C.byref(dst_model), k,
+                                                sa, da, int(n_out)))
+
+    def opacity_reset(self, max_logit: float, m_opac_ptr: int = 0, v_opac_ptr: int = 0):
+        """gs_opacity_reset: opacity = min(opacity, max_logit) on the resident model (NaN stays), +0 into the two moment arrays."""
+        self._chk(self.L.gs_opacity_reset(self.h, C.c_float(max_logit), C.c_void_p(int(m_opac_ptr or 0)), C.c_void_p(int(v_opac_ptr or 0))))
 
     def reset_grads(self, grads: GsGrads):
         self._chk(self.L.gs_reset_grads(self.h, C.byref(grads)))

@@ -43,6 +43,9 @@ SOURCES = {
     "gs_loss.hip": ["-fno-slp-vectorize"],
     # Adam: the per-float update must round exactly as documented in include/gsplat.h (and as gs_sh_bwd_kernel's fused form does)
     "gs_adam.hip": ["-ffp-contract=off"],
+    # density control: statistics, decisions and the children of a split are specified operation by operation (tests/density_ref.py matches bit for bit)
+    "gs_density.hip": ["-ffp-contract=off"],
+    "gs_api_density.hip": ["-ffp-contract=off"],
     "gs_api.hip": [],
     "gs_api_bin.hip": [],
     "gs_api_composite.hip": [],

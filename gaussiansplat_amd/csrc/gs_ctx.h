@@ -6,6 +6,7 @@
 //                         (composite_args), the launch orders of the view slots; the backward family's plan (plan_backward) and run_backward
 //   gs_api_comm.hip       RCCL below the boundary (gs_comm_*, gs_allreduce_grads)
 //   gs_api_touched.hip    the touched-rows colour exchange (gs_color_rows_pack, gs_sh_grads_from_touched)
+//   gs_api_density.hip    density control (gs_density_accumulate / _decide / _plan / _restructure, gs_opacity_reset)
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
 // How far the frame has come is ONE ordered value (gs_ctx::Stage): every entry point compares it, reaches a stage or falls back to one.
 // What the ctx holds it owns: DevBuf frees itself, ~gs_ctx releases the communicator, events, streams and pinned blocks -- no list to keep.
@@ -113,7 +114,7 @@ struct gs_ctx {
     } stage = Stage::NOTHING;
     void reach(Stage s) { stage = s; }
     void fall_back(Stage s) { if (stage > s) stage = s; }                  // to at most s
-    void inputs_changed() { fall_back(Stage::NOTHING); }   // the model or the view changed: nothing of the frame stands
+    void inputs_changed() { fall_back(Stage::NOTHING); density.planned = false; }   // the model or the view changed: nothing of the frame stands, nor a density plan
     int gx = 0, gy = 0;
     int64_t grid_key() const { return ((int64_t)gx << 32) | (int64_t)gy; }        // what per-grid history is tagged with (0: none)
     size_t ntiles1() const { const size_t nt = (size_t)gx * gy; return nt ? nt : 1; }   // tiles, for buffer sizes (never zero)
@@ -285,6 +286,16 @@ struct gs_ctx {
     DevBuf dpc;                              // 4 x n scratch between the two backward kernels
     DevBuf loss_maps, loss_acc, loss_in[2], loss_dc, view_cams;
     DevBuf touched_cnt, touched_off, touched_zero;   // touched-rows exchange: per (view, chunk) counts and exclusive row offsets; three +0 floats (gs_api_touched.hip)
+    // ---- density control (gs_api_density.hip): per chunk of GS_DENSITY_CHUNK gaussians the counts of the three output classes (survivors,
+    // clones, split sources), their exclusive offsets, and {three totals, bad-action flag}; the plan gs_density_plan leaves for gs_density_restructure
+    DevBuf density_cnt, density_off, density_tot;
+    struct DensityPlan {
+        bool planned = false;                // dropped by inputs_changed()
+        const int32_t *action = nullptr;     // the tag: the action array and n the offsets were made from
+        int64_t n = 0, survivors = 0, clones = 0, splits = 0;
+        int64_t n_out() const { return survivors + clones + 2 * splits; }
+    } density;
+    float density_log_shrink = 0.4700036292457356f;   // (float)log(1.6) until a gs_density_decide says otherwise: what the children of a split shrink by
     ncclComm_t comm = nullptr;
     int comm_ranks = 0;
 };

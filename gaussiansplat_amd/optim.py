@@ -159,6 +159,19 @@ class Adam:
         r._end()
         self.step_count = t
 
+    def _rebind(self, exp_avg, exp_avg_sq):
+        """The number of gaussians changed (density.densify_and_prune): take the restructured moment buffers and re-read the
+        layout from the renderer's new gradient buffer.  step_count stays: the bias corrections are a property of the run."""
+        flat = self.renderer._splatGrads.flat
+        for t in (exp_avg, exp_avg_sq):
+            if t.numel() != flat.numel() or t.dtype != flat.dtype or t.device != flat.device or not t.is_contiguous():
+                raise ValueError("Adam._rebind: the moment buffers must match the renderer's flat gradient buffer")
+        g = self.renderer._splatGrads
+        views = (g.Δmeans, g.Δscales, g.Δquaternions, g.Δopacities, g.Δshs)
+        self._offsets = tuple((v.data_ptr() - flat.data_ptr()) // 4 for v in views)
+        self._numel = flat.numel()
+        self.exp_avg, self.exp_avg_sq = exp_avg, exp_avg_sq
+
     # -- checkpoints
     def state_dict(self) -> dict:
         return dict(step=self.step_count, lr=dict(self.lr), betas=tuple(self.betas), eps=self.eps, selective=self.selective,

@@ -111,6 +111,7 @@ class GaussianRenderer3D:               # renderer.jl:205-219
         import torch
         self.splatData = splatData
         self._splatGrads = share_grads_with._splatGrads if share_grads_with is not None else initGrads(splatData)
+        self._shares_grads = share_grads_with is not None   # (density.densify_and_prune replaces the buffer: only its owner may)
         self._grads_lazy_zero = False       # resetGrads() pending: the next backward overwrites
         W, H = int(imgSize[0]), int(imgSize[1])
         dev = splatData.means.device

@@ -8,7 +8,8 @@ backward/SGD lines are commented out, train.jl:39-46); what it intends is implem
 
 with the loss, its image gradient and the SGD update running on the GPU (csrc/gs_loss.hip) so the
 step has no host round trip.  `optimizer=optim.Adam(...)` replaces the SGD update by Adam with per-group rates
-(csrc/gs_adam.hip; fused with the backward when the optimiser was made with fused=True).
+(csrc/gs_adam.hip; fused with the backward when the optimiser was made with fused=True).  `density=density.DensityController(...)`
+adds the other half of the 3DGS recipe: statistics after every backward, clone / split / prune and the opacity reset on schedule.
 """
 from __future__ import annotations
 
@@ -68,14 +69,20 @@ def getLossFunction(imSize, windowSize: int, nChannels: int, renderer=None, λ: 
 
 
 def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, want_loss: bool = True, fused_sgd: bool = False,
-              optimizer=None):
+              optimizer=None, density=None):
     """One iteration of train.jl:33-56 as intended (see module docstring).
     fused_sgd (3-D renderer): backward and the parameter update in one pass (gs_backward_sgd) -- the same parameters bit for
     bit (deterministic mode), but renderer.splatGrads is not filled.
     optimizer (optim.Adam): it does the parameter update instead of SGD and `lr` is ignored -- optimizer.backward_step when it
-    was made with fused=True (renderer.splatGrads then is not filled), else backward, optimizer.step() and resetGrads."""
+    was made with fused=True (renderer.splatGrads then is not filled), else backward, optimizer.step() and resetGrads.
+    density (density.DensityController): its statistics are accumulated between the backward and the update (the update drops the
+    frame, so this is the only place), and after the update it clones / splits / prunes and resets opacities when its schedule says so.
+    The fused forms leave no frame to accumulate from: a fused optimiser or fused_sgd with `density` is a ValueError."""
     if optimizer is not None and fused_sgd:
         raise ValueError("trainStep: fused_sgd and optimizer exclude each other (make the optimiser with fused=True instead)")
+    if density is not None and (fused_sgd or (optimizer is not None and optimizer.fused)):
+        raise ValueError("trainStep: density control needs the unfused backward (no fused_sgd, no Adam(fused=True)): "
+                         "the fused forms leave no frame to accumulate statistics from")
     tps = R.preprocess(renderer, camera)
     R.compactIdxs(renderer)
     R.forward(renderer, tps)
@@ -85,8 +92,12 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
             optimizer.backward_step(ΔC)
             return loss
         R.backward(renderer, ΔC)
+        if density is not None:
+            density.accumulate(renderer)
         optimizer.step()
         R.resetGrads(renderer)
+        if density is not None:
+            density.after_step(renderer, optimizer)
         return loss
     if fused_sgd:
         renderer._dC_keepalive = ΔC
@@ -95,19 +106,24 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
         renderer._end()
         return loss
     R.backward(renderer, ΔC)
+    if density is not None:
+        density.accumulate(renderer)
     renderer._begin()
     renderer.ctx.sgd_step(float(lr), renderer._grads)        # param .-= lr * Δparam (train.jl:42-46)
     renderer._end()
     R.resetGrads(renderer)                                   # train.jl:55
+    if density is not None:
+        density.after_step(renderer, None)
     return loss
 
 
-def train(renderer, gtimg, lr: float, lossFunc: LossFunction, iterations: int = 100, camera=None, log_every: int = 0, optimizer=None):
+def train(renderer, gtimg, lr: float, lossFunc: LossFunction, iterations: int = 100, camera=None, log_every: int = 0, optimizer=None,
+          density=None):
     """train.jl:16-59 without the GUI; the reference loops `while score < 0.99` on a score it never updates.
-    optimizer: an optim.Adam that replaces the SGD update (lr is then ignored)."""
+    optimizer: an optim.Adam that replaces the SGD update (lr is then ignored); density: a density.DensityController (trainStep)."""
     losses = []
     for it in range(iterations):
-        l = trainStep(renderer, gtimg, lr, lossFunc, camera, want_loss=True, optimizer=optimizer)
+        l = trainStep(renderer, gtimg, lr, lossFunc, camera, want_loss=True, optimizer=optimizer, density=density)
         losses.append(l)
         if log_every and it % log_every == 0:
             print(f"loss : {l}")                             # loss.jl:69

@@ -387,6 +387,70 @@ int gs_adam_step(gs_ctx *ctx, const gs_grads *grads, const gs_grads *exp_avg, co
 int gs_backward_adam(gs_ctx *ctx, const float *dC, int mem, const gs_grads *exp_avg, const gs_grads *exp_avg_sq,
                      const float lr[GS_ADAM_GROUPS], float beta1, float beta2, float eps, int64_t step, int flags);
 
+/* ---- density control: statistics, clone / split / prune, opacity reset (3-D renderer) ---------- */
+
+/* The other half of the 3DGS recipe (Kerbl et al. 2023) whose rates gs_adam_step takes: the number of gaussians changes on the
+ * device.  Five calls, every one a pure function of its inputs (random numbers stay with the caller), every decision a comparison
+ * of stored floats and integers -- the host passes its thresholds already in log / logit space:
+ *   per view:    gs_backward_ex (any non-fused backward), gs_density_accumulate
+ *   per window:  gs_density_decide -> gs_density_plan (the one synchronise) -> gs_density_restructure into new arrays ->
+ *                gs_set_model on them; zero the statistics
+ *   now and then: gs_opacity_reset
+ * The 2-D renderer gets GS_ERR_UNSUPPORTED.  Not covered: accumulation inside the fused backwards (gs_backward_sgd / _adam leave
+ * no frame to accumulate from), multi-GPU restructuring (deterministic given equal noise, so replicated ranks may each run it). */
+typedef struct {            /* caller-owned DEVICE arrays of N elements; zero them to start a window */
+    float   *grad_sum;      /* sum over accumulated views of |d L / d mu'| in NDC units                */
+    int32_t *count;         /* views in which the gaussian was visible                                 */
+    int32_t *max_extent;    /* largest pixel extent seen                                               */
+} gs_density_stats;
+
+typedef struct {
+    int32_t struct_size;        /* = sizeof(gs_density_params)                                         */
+    float grad_threshold;       /* densify when grad_sum >= grad_threshold * count and count > 0       */
+    float log_split_scale;      /* densified: split when max_j scale_j > this (log space), else clone  */
+    float log_shrink;           /* children of a split: scale_j - log_shrink (3DGS: log 1.6)           */
+    float min_opacity_logit;    /* prune when opacity < this                                           */
+    float log_max_world_scale;  /* prune when the scale that would remain > this; +Inf = off           */
+    int32_t max_extent_px;      /* prune when max_extent > this; 0 = off                               */
+} gs_density_params;
+
+/* After a backward of the frame (GS_ERR_INVALID before one; the fused backwards drop the frame), per gaussian, with row = the
+ * gaussian's GS_ARR_GRAD2D row (d L / d mu' in pixels at [4], [5]), every operation rounded on its own, sqrt correctly rounded:
+ *   grad_sum += sqrt(((0.5f*W)*row[4])^2 + ((0.5f*H)*row[5])^2);   visible = the view's pixel box is not empty;
+ *   count += visible;   max_extent = max(max_extent, visible ? max(xmax - xmin, ymax - ymin) + 1 : 0).   No synchronise. */
+int gs_density_accumulate(gs_ctx *ctx, const gs_density_stats *stats);
+
+/* action[g] (DEVICE, N words) = 0 keep, 1 clone, 2 split, 3 prune.  With smax = max_j scales[g][j]:
+ *   dens   = count > 0 && grad_sum >= grad_threshold * (float)count;     split = dens && smax > log_split_scale;
+ *   remain = split ? smax - log_shrink : smax;
+ *   prune  = opacity < min_opacity_logit || (max_extent_px > 0 && max_extent > max_extent_px) || remain > log_max_world_scale;
+ *   action = prune ? 3 : split ? 2 : dens ? 1 : 0        (a NaN compares false everywhere: a NaN gaussian is kept)
+ * GS_ERR_INVALID: struct_size, a NaN grad_threshold or log_shrink.  No synchronise. */
+int gs_density_decide(gs_ctx *ctx, const gs_density_stats *stats, const gs_density_params *params, int32_t *action);
+
+/* counts (HOST) = {survivors (actions 0 and 1), clones, splits, pruned}; n_out = survivors + clones + 2 * splits (a split source is
+ * replaced by its two children).  Leaves the output offsets in ctx scratch, tagged with (action, N); the one call of the five that
+ * synchronises.  An action outside 0..3: GS_ERR_INVALID, no plan. */
+int gs_density_plan(gs_ctx *ctx, const int32_t *action, int64_t counts[4]);
+
+/* Writes the restructured model into dst_model (five DEVICE arrays of n_out rows, the model's layouts) and up to four gradient-shaped
+ * companion sets (Adam's moments) from src_sets into dst_sets (nsets 0..4; an array that is NULL on either side is skipped).  Rows:
+ * the survivors in ascending source order, then the clones in ascending source order, then for every split source in ascending
+ * order its child 0 and its child 1.  Survivors and clones are copied bit for bit.  Child c of source g copies quaternion, opacity and
+ * SH row; scale_j - log_shrink;  mean_i + w_i with e_j = exp(scale_j) * noise[(2g + c) * 3 + j] (the preprocess's exp),
+ * w_i = (R[i][0]*e_0 + R[i][1]*e_1) + R[i][2]*e_2 and R the rotation the preprocess forms from the raw quaternion.  Companion rows of
+ * survivors are copied, those of clones and children are +0.  noise: DEVICE [N][2][3] standard normals, read for split sources only
+ * (NULL is fine when the plan has no split).  log_shrink is the one of the ctx's last successful gs_density_decide (the call that
+ * produces split actions); before any, 3DGS's (float)log(1.6).
+ * GS_ERR_INVALID, nothing enqueued: no plan for (action, N) -- gs_set_model, a step of the optimiser or a new camera drop it --, n_out
+ * differs from the plan's, or a destination overlaps the model, a source set or another destination.  The ctx's model is NOT
+ * switched: call gs_set_model on the new arrays.  No synchronise. */
+int gs_density_restructure(gs_ctx *ctx, const int32_t *action, const float *noise, const gs_grads *dst_model, int32_t nsets, const gs_grads *src_sets, const gs_grads *dst_sets, int64_t n_out);
+
+/* opacity = opacity > max_logit ? max_logit : opacity on the resident model (a NaN stays); +0 into the gaussians' words of the two
+ * moment arrays (DEVICE, N floats; either may be NULL).  The frame is dropped, as after an optimiser step.  No synchronise. */
+int gs_opacity_reset(gs_ctx *ctx, float max_logit, float *m_opac, float *v_opac);
+
 /* ---- introspection (parity tests, profiling) ------------------------------------------- */
 
 typedef enum {

@@ -260,6 +260,55 @@ function hip_backward_adam!(r::HipRenderer, ΔC::Array{Float32, 3}, expAvg::GsGr
                    r.ctx, ΔC, GS_MEM_HOST, expAvg, expAvgSq, lr, beta1, beta2, eps, Int64(step), selective ? GS_ADAM_SELECTIVE : Cint(0)))
 end
 
+# ---- density control (include/gsplat.h: statistics, clone / split / prune, opacity reset; 3-D renderer) ---------------
+# The two structs travel as Ptr{Cvoid} (a Ref kept alive around the call).  Every array is a DEVICE pointer.
+struct GsDensityStats
+    grad_sum::Ptr{Float32}
+    count::Ptr{Int32}
+    max_extent::Ptr{Int32}
+end
+struct GsDensityParams
+    struct_size::Int32
+    grad_threshold::Float32
+    log_split_scale::Float32
+    log_shrink::Float32
+    min_opacity_logit::Float32
+    log_max_world_scale::Float32
+    max_extent_px::Int32
+end
+# thresholds already in log / logit space (3DGS: split above percent_dense * extent, children shrink by 1.6, prune below opacity 0.005)
+densityParams(gradThreshold, logSplitScale; logShrink = Float32(log(1.6)), minOpacityLogit = Float32(log(0.005 / 0.995)),
+              logMaxWorldScale = Inf32, maxExtentPx = 0) =
+    GsDensityParams(Int32(sizeof(GsDensityParams)), gradThreshold, logSplitScale, logShrink, minOpacityLogit, logMaxWorldScale, Int32(maxExtentPx))
+# after a (non-fused) backward of the frame: stats += this view
+function hip_densityAccumulate!(r::HipRenderer, stats::GsDensityStats)
+    s = Ref(stats)
+    GC.@preserve s check(r, ccall((:gs_density_accumulate, libgs), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), r.ctx, Base.unsafe_convert(Ptr{Cvoid}, s)))
+end
+# action[g] = 0 keep, 1 clone, 2 split, 3 prune
+function hip_densityDecide!(r::HipRenderer, stats::GsDensityStats, params::GsDensityParams, action::Ptr{Int32})
+    s = Ref(stats); p = Ref(params)
+    GC.@preserve s p check(r, ccall((:gs_density_decide, libgs), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}),
+                                    r.ctx, Base.unsafe_convert(Ptr{Cvoid}, s), Base.unsafe_convert(Ptr{Cvoid}, p), action))
+end
+# (survivors, clones, splits, pruned); the new model has survivors + clones + 2 splits rows.  Synchronises.
+function hip_densityPlan(r::HipRenderer, action::Ptr{Int32})
+    counts = zeros(Int64, 4)
+    check(r, ccall((:gs_density_plan, libgs), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int64}), r.ctx, action, counts))
+    return (survivors = counts[1], clones = counts[2], splits = counts[3], pruned = counts[4])
+end
+# the model (and gradient-shaped companions such as Adam's moments) into new arrays of nOut rows; then hip-side gs_set_model on them
+function hip_densityRestructure!(r::HipRenderer, action::Ptr{Int32}, noise::Ptr{Float32}, dstModel::GsGrads, srcSets::Vector{GsGrads},
+                                 dstSets::Vector{GsGrads}, nOut::Integer)
+    length(srcSets) == length(dstSets) || throw(ArgumentError("srcSets and dstSets: one destination per source set"))
+    check(r, ccall((:gs_density_restructure, libgs), Cint,
+                   (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float32}, Ref{GsGrads}, Int32, Ptr{GsGrads}, Ptr{GsGrads}, Int64),
+                   r.ctx, action, noise, dstModel, Int32(length(srcSets)), srcSets, dstSets, Int64(nOut)))
+end
+# opacity = min(opacity, maxLogit) on the resident model; +0 into the opacities' Adam moments (C_NULL: none)
+hip_opacityReset!(r::HipRenderer, maxLogit::Real, mOpac::Ptr{Float32} = Ptr{Float32}(C_NULL), vOpac::Ptr{Float32} = Ptr{Float32}(C_NULL)) =
+    check(r, ccall((:gs_opacity_reset, libgs), Cint, (Ptr{Cvoid}, Cfloat, Ptr{Float32}, Ptr{Float32}), r.ctx, maxLogit, mOpac, vOpac))
+
 # ---- plumbing and introspection -----------------------------------------------------------------------------------
 
 # enqueue on an existing hipStream_t (C_NULL: the ctx's own stream)

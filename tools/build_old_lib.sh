@@ -12,6 +12,13 @@ grep -q gs_adam_step "$W/include/gsplat.h" || cat >> "$W/gaussiansplat_amd/csrc/
 extern "C" int gs_adam_step(gs_ctx *, const gs_grads *, const gs_grads *, const gs_grads *, const float *, float, float, float, int64_t, int) { return GS_ERR_UNSUPPORTED; }
 extern "C" int gs_backward_adam(gs_ctx *, const float *, int, const gs_grads *, const gs_grads *, const float *, float, float, float, int64_t, int) { return GS_ERR_UNSUPPORTED; }
 STUB
+grep -q gs_density_plan "$W/include/gsplat.h" || cat >> "$W/gaussiansplat_amd/csrc/gs_api_debug.hip" <<'STUB'
+extern "C" int gs_density_accumulate(gs_ctx *, const void *) { return GS_ERR_UNSUPPORTED; }
+extern "C" int gs_density_decide(gs_ctx *, const void *, const void *, int32_t *) { return GS_ERR_UNSUPPORTED; }
+extern "C" int gs_density_plan(gs_ctx *, const int32_t *, int64_t *) { return GS_ERR_UNSUPPORTED; }
+extern "C" int gs_density_restructure(gs_ctx *, const int32_t *, const float *, const gs_grads *, int32_t, const gs_grads *, const gs_grads *, int64_t) { return GS_ERR_UNSUPPORTED; }
+extern "C" int gs_opacity_reset(gs_ctx *, float, float *, float *) { return GS_ERR_UNSUPPORTED; }
+STUB
 objs=()
 for s in "$W"/gaussiansplat_amd/csrc/*.hip; do
   b=$(basename "$s" .hip); extra=""
