@@ -1,4 +1,5 @@
-// gs_bin2.hip -- low-traffic tile binning for gfx950 (default path of gs_bin).
+// gs_bin2.hip -- low-traffic tile binning for gfx950 (gs_config.bin_path = 2; what gs_bin falls back to on grids the two-level
+// path of gs_bin3.hip refuses).
 //
 // Same result as the reference's compactIdxs (src/forward.jl:118-161: hitBinning, scan!, compactHits)
 // with the per-tile lists in (tile, list order) -- bit-identical to the 64-bit key sort of
@@ -18,13 +19,7 @@
 // HBM traffic per instance: 4 B written + 4 B read (hist) + 4 B read + 4 B written = 16 B, against
 // 8 + 2 x 24 + 8 = 64 B for emit + two 64-bit passes + ranges.  Integer/byte work: coalesced 4-byte
 // streams, LDS histograms, LDS-staged scatter; no MFMA.
-#include "gs_common.h"
-
-#define RS_THREADS 256
-#define RS_ITEMS 16
-#define RS_CHUNK (RS_THREADS * RS_ITEMS)
-#define RS_RADIX 256
-#define RS_WAVES (RS_THREADS / GS_WAVE)
+#include "gs_radix.h"
 
 // ---------------------------------------------------------------- tile counts -> ranges
 // Per-tile list lengths = number of rectangles covering each tile.  Each rectangle is four +-1
@@ -70,7 +65,7 @@ __global__ __launch_bounds__(1024) void ranges_from_diff_kernel(const int *__res
     extern __shared__ int ld[];
     __shared__ uint32_t sm[16];
     __shared__ uint32_t carry;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     const int cells = pitch * (gy + 1);
     for (int i = tid; i < cells; i += 1024) ld[i] = diff[i];
     __syncthreads();
@@ -90,17 +85,10 @@ __global__ __launch_bounds__(1024) void ranges_from_diff_kernel(const int *__res
         const int t = b0 + tid;
         uint32_t v = t < ntiles ? (uint32_t)ld[(t / gx) * pitch + (t % gx)] : 0u;
         if (done && t < ntiles && done[t]) v = 0u;                     // completed tiles take no instances in this round
-        uint32_t incl = v;
-#pragma unroll
-        for (int d = 1; d < GS_WAVE; d <<= 1) { const uint32_t u = __shfl_up(incl, d); if (lane >= d) incl += u; }
-        if (lane == 63) sm[w] = incl;
+        const uint32_t pre = block_excl_prefix<1024>(v, sm), c = carry;
+        if (t < ntiles) { ranges[2 * t] = c + pre; ranges[2 * t + 1] = c + pre + v; }
         __syncthreads();
-        uint32_t woff = 0;
-        for (int k = 0; k < w; ++k) woff += sm[k];
-        const uint32_t c = carry;
-        if (t < ntiles) { ranges[2 * t] = c + woff + incl - v; ranges[2 * t + 1] = c + woff + incl; }
-        __syncthreads();
-        if (tid == 1023) carry = c + woff + incl;
+        if (tid == 1023) carry = c + pre + v;
         __syncthreads();
     }
 }
@@ -246,65 +234,15 @@ __global__ __launch_bounds__(RS_THREADS) void gen_hist_kernel(ExpandArgs a, uint
     block_hist[(size_t)tid * a.nchunks + blockIdx.x] = h[tid];
 }
 
-// stable ranking shared by both scatter kernels: wave w owns items [w*1024, (w+1)*1024) in 16
-// wave-striped rounds; order = (wave, round, lane)
-// Two ways to get a key's stable rank among the wave's earlier same-digit keys:
-//  * ballots (portable): 8 wave64 ballots build the set of same-digit lanes, a running LDS counter adds
-//    the earlier rounds;
-//  * LDS atomic (default): ONE ds_add_rtn_u32 on the wave's counter row.  When several lanes of one wave
-//    instruction hit the same LDS address, gfx950 hands out the pre-values in ascending lane order
-//    (tools/lds_atomic_order.hip: 0 mismatches in 1.7e8 lane-ops) -- exactly the stable rank.  Measured
-//    behaviour, not an architectural guarantee: gs_config.rank_mode = 1 selects the ballot form, and the
-//    GPU tests compare every list bit-for-bit against the oracle with both.
-__device__ __forceinline__ void rank_round_atomic(uint32_t dg, bool valid, uint32_t *wc, uint32_t &rank) {
-    rank = 0;
-    if (valid) rank = atomicAdd(&wc[dg], 1u);
-}
-
-__device__ __forceinline__ void rank_round(uint32_t dg, bool valid, int lane, volatile uint32_t *wc, uint32_t &rank) {
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    unsigned long long peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const unsigned long long bal = __ballot((dg >> b) & 1u);
-        peers &= ((dg >> b) & 1u) ? bal : ~bal;
-    }
-    const uint32_t before = wc[dg];
-    rank = before + (uint32_t)__popcll(peers & lt_mask);
-    __builtin_amdgcn_wave_barrier();
-    if (valid && (peers & lt_mask) == 0ull) wc[dg] = before + (uint32_t)__popcll(peers);
-    __builtin_amdgcn_wave_barrier();
-}
-
-// per-wave exclusive offsets (wcnt), chunk digit prefix (lpre); call with all 256 threads
-// returns the number of ranked keys of the chunk (== the chunk's key count unless instances were dropped)
-__device__ __forceinline__ uint32_t digit_prefixes(uint32_t (*wcnt)[RS_RADIX], uint32_t *lpre, uint32_t *sm) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    uint32_t tot = 0;
-#pragma unroll
-    for (int k = 0; k < RS_WAVES; ++k) { const uint32_t c = wcnt[k][tid]; wcnt[k][tid] = tot; tot += c; }
-    uint32_t incl = tot;
-#pragma unroll
-    for (int d = 1; d < GS_WAVE; d <<= 1) { const uint32_t u = __shfl_up(incl, d); if (lane >= d) incl += u; }
-    if (lane == 63) sm[w] = incl;
-    __syncthreads();
-    uint32_t woff = 0, all = 0;
-    for (int k = 0; k < RS_WAVES; ++k) { if (k < w) woff += sm[k]; all += sm[k]; }
-    lpre[tid] = woff + incl - tot;
-    __syncthreads();
-    return all;
-}
-
+// Ranking as in every scatter kernel (gs_radix.h): wave w owns items [w*1024, (w+1)*1024) in 16 wave-striped rounds; order =
+// (wave, round, lane).  Instances of completed tiles are not ranked, so the chunk places fewer keys than it expands (nlive).
 template <bool ATOMIC_RANK>
 __global__ __launch_bounds__(RS_THREADS) void gen_scatter_kernel(ExpandArgs a, const uint32_t *__restrict__ block_hist,
                                                                   uint32_t *__restrict__ out) {
     __shared__ uint32_t own[RS_CHUNK];                   // owners, then reused as the reorder buffer
     __shared__ uint4 rec[EXP_RCAP];                      // gaussian records, then reused for the digit bytes
     uint8_t *sdg = reinterpret_cast<uint8_t *>(rec);
-    __shared__ uint32_t wcnt[RS_WAVES][RS_RADIX];
-    __shared__ uint32_t lpre[RS_RADIX];
-    __shared__ uint32_t gbase[RS_RADIX];
-    __shared__ uint32_t sm[RS_WAVES];
+    __shared__ uint32_t wcnt[RS_WAVES][RS_RADIX], lpre[RS_RADIX], gbase[RS_RADIX], sm[RS_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int64_t base = (int64_t)blockIdx.x * RS_CHUNK;
     const int cnt = (int)min((int64_t)RS_CHUNK, a.n_inst - base);
@@ -319,7 +257,7 @@ __global__ __launch_bounds__(RS_THREADS) void gen_scatter_kernel(ExpandArgs a, c
     uint32_t vmask = 0;                                  // bit r: item r is a live instance (inside the chunk, tile not completed)
 #pragma unroll
     for (int r = 0; r < RS_ITEMS; ++r) {
-        const int li = w * (GS_WAVE * RS_ITEMS) + r * GS_WAVE + lane;
+        const int li = RS_LI(w, r, lane, GS_WAVE * RS_ITEMS);
         bool valid = li < cnt;
         uint32_t tile = 0, gid = 0;
         if (valid) expand_item(a, own, rec, staged, base, li, s_lo, tile, gid);
@@ -327,15 +265,16 @@ __global__ __launch_bounds__(RS_THREADS) void gen_scatter_kernel(ExpandArgs a, c
         if (valid) vmask |= 1u << r;
         dgs[r] = valid ? (tile & mask) : (RS_RADIX - 1);
         val[r] = ((tile >> a.lo_bits) << a.gid_bits) | gid;
-        if (ATOMIC_RANK) rank_round_atomic(dgs[r], valid, wcnt[w], rank[r]);
-        else rank_round(dgs[r], valid, lane, wcnt[w], rank[r]);
+        rank[r] = ATOMIC_RANK ? rank_round_atomic(dgs[r], valid, wcnt[w]) : rank_round(dgs[r], valid, lane, wcnt[w]);
     }
     __syncthreads();                                     // every wave is done reading own[] and rec[]
-    const int nlive = (int)digit_prefixes(wcnt, lpre, sm);
+    digit_prefixes<RS_WAVES>(wcnt, lpre, sm);
+    const int nlive = (int)ranked_keys(sm);
+    __syncthreads();
 #pragma unroll
     for (int r = 0; r < RS_ITEMS; ++r) {
         if (vmask & (1u << r)) {
-            const uint32_t p = lpre[dgs[r]] + wcnt[w][dgs[r]] + rank[r];
+            const uint32_t p = radix_slot(lpre, wcnt[w], dgs[r], rank[r]);
             own[p] = val[r];
             sdg[p] = (uint8_t)dgs[r];
         }
@@ -344,10 +283,7 @@ __global__ __launch_bounds__(RS_THREADS) void gen_scatter_kernel(ExpandArgs a, c
 #pragma unroll
     for (int r = 0; r < RS_ITEMS; ++r) {
         const int li = r * RS_THREADS + tid;
-        if (li < nlive) {
-            const uint32_t dg = sdg[li];
-            out[(size_t)gbase[dg] + (uint32_t)(li - (int)lpre[dg])] = own[li];
-        }
+        if (li < nlive) out[radix_dest(gbase, lpre, sdg[li], li)] = own[li];
     }
 }
 
@@ -375,12 +311,8 @@ __global__ __launch_bounds__(RS_THREADS) void rs32_scatter_kernel(const uint32_t
                                                                    int shift, uint32_t mask, uint32_t out_mask,
                                                                    const uint32_t *__restrict__ block_hist, int nblocks,
                                                                    const uint32_t *__restrict__ n_dev) {
-    __shared__ uint32_t skeys[RS_CHUNK];
+    __shared__ uint32_t skeys[RS_CHUNK], wcnt[RS_WAVES][RS_RADIX], lpre[RS_RADIX], gbase[RS_RADIX], sm[RS_WAVES];
     if (n_dev) n = (int64_t)*n_dev;
-    __shared__ uint32_t wcnt[RS_WAVES][RS_RADIX];
-    __shared__ uint32_t lpre[RS_RADIX];
-    __shared__ uint32_t gbase[RS_RADIX];
-    __shared__ uint32_t sm[RS_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int64_t base = (int64_t)blockIdx.x * RS_CHUNK;
     const int cnt = (int)max((int64_t)0, min((int64_t)RS_CHUNK, n - base));
@@ -388,36 +320,11 @@ __global__ __launch_bounds__(RS_THREADS) void rs32_scatter_kernel(const uint32_t
     for (int k = 0; k < RS_WAVES; ++k) wcnt[k][tid] = 0;
     gbase[tid] = block_hist[(size_t)tid * nblocks + blockIdx.x];
     __syncthreads();
-    uint32_t key[RS_ITEMS], rank[RS_ITEMS];
+    uint32_t key[RS_ITEMS];
 #pragma unroll
-    for (int r = 0; r < RS_ITEMS; ++r) {
-        const int li = w * (GS_WAVE * RS_ITEMS) + r * GS_WAVE + lane;
-        const bool valid = li < cnt;
-        key[r] = valid ? in[base + li] : 0xFFFFFFFFu;
-        const uint32_t dg = valid ? ((key[r] >> shift) & mask) : (RS_RADIX - 1);
-        if (ATOMIC_RANK) rank_round_atomic(dg, valid, wcnt[w], rank[r]);
-        else rank_round(dg, valid, lane, wcnt[w], rank[r]);
-    }
-    __syncthreads();
-    digit_prefixes(wcnt, lpre, sm);
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; ++r) {
-        const int li = w * (GS_WAVE * RS_ITEMS) + r * GS_WAVE + lane;
-        if (li < cnt) {
-            const uint32_t dg = (key[r] >> shift) & mask;
-            skeys[lpre[dg] + wcnt[w][dg] + rank[r]] = key[r];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; ++r) {
-        const int li = r * RS_THREADS + tid;
-        if (li < cnt) {
-            const uint32_t k = skeys[li];
-            const uint32_t dg = (k >> shift) & mask;
-            out[(size_t)gbase[dg] + (uint32_t)(li - (int)lpre[dg])] = k & out_mask;
-        }
-    }
+    for (int r = 0; r < RS_ITEMS; ++r) { const int li = RS_LI(w, r, lane, GS_WAVE * RS_ITEMS); key[r] = li < cnt ? in[base + li] : 0xFFFFFFFFu; }
+    radix_scatter_chunk<RS_THREADS, ATOMIC_RANK>(key, cnt, [=](uint32_t k) { return (k >> shift) & mask; },
+                                                 [=](size_t o, uint32_t k) { out[o] = k & out_mask; }, skeys, wcnt, lpre, gbase, sm);
 }
 
 // live instances of a round = sum of the first pass's digit totals (instances of completed tiles were never counted)
@@ -442,20 +349,15 @@ hipError_t gs_bin2_build_lists(const GsBin2Args &b, hipStream_t s) {
     if (e != hipSuccess) return e;
     if (b.live_total) hipLaunchKernelGGL(sum_digit_totals_kernel, dim3(1), dim3(64), 0, s, b.digit_total, b.live_total);
     uint32_t *first_out = b.hi_bits > 0 ? b.buf_a : b.ids_out;
-    if (b.ballot_ranks) hipLaunchKernelGGL(gen_scatter_kernel<false>, dim3(nchunks), dim3(RS_THREADS), 0, s, a, b.block_hist, first_out);
-    else hipLaunchKernelGGL(gen_scatter_kernel<true>, dim3(nchunks), dim3(RS_THREADS), 0, s, a, b.block_hist, first_out);
+    rs_launch_ranked(b.ballot_ranks, gen_scatter_kernel<false>, gen_scatter_kernel<true>, dim3(nchunks), dim3(RS_THREADS), s, a, b.block_hist, first_out);
     if (b.hi_bits > 0) {
         const uint32_t hmask = (1u << b.hi_bits) - 1u, gmask = b.gid_bits >= 32 ? 0xFFFFFFFFu : ((1u << b.gid_bits) - 1u);
         hipLaunchKernelGGL(rs32_hist_kernel, dim3(nchunks), dim3(RS_THREADS), 0, s, b.buf_a, b.n_inst, b.gid_bits, hmask, b.block_hist, nchunks,
                            (const uint32_t *)b.live_total);
         e = gs_launch_radix_scan(b.block_hist, nchunks, b.digit_total, s);
         if (e != hipSuccess) return e;
-        if (b.ballot_ranks)
-            hipLaunchKernelGGL(rs32_scatter_kernel<false>, dim3(nchunks), dim3(RS_THREADS), 0, s, b.buf_a, b.ids_out, b.n_inst, b.gid_bits, hmask,
-                               gmask, b.block_hist, nchunks, (const uint32_t *)b.live_total);
-        else
-            hipLaunchKernelGGL(rs32_scatter_kernel<true>, dim3(nchunks), dim3(RS_THREADS), 0, s, b.buf_a, b.ids_out, b.n_inst, b.gid_bits, hmask,
-                               gmask, b.block_hist, nchunks, (const uint32_t *)b.live_total);
+        rs_launch_ranked(b.ballot_ranks, rs32_scatter_kernel<false>, rs32_scatter_kernel<true>, dim3(nchunks), dim3(RS_THREADS), s,
+                         b.buf_a, b.ids_out, b.n_inst, b.gid_bits, hmask, gmask, b.block_hist, nchunks, (const uint32_t *)b.live_total);
     }
     return hipGetLastError();
 }

@@ -22,7 +22,7 @@
 //
 // HBM traffic per instance: the 4-byte id written once (+ 6 B per COARSE instance written and read twice), against
 // 16 B per instance for gs_bin2.hip.  The tile ranges are the exclusive scan of the level-2 hit counts.
-#include "gs_common.h"
+#include "gs_radix.h"
 
 // Super-tile edge: 8 tiles (SBS = 3), or 16 tiles (SBS = 4) on grids whose 8 x 8 super-tiles would be more than GS_BIN3_NS8_MAX:
 // level 1 works per (chunk of positions, super-tile) and its cost per position grows with the number of super-tiles (4K: 510 of
@@ -46,14 +46,6 @@ int gs_bin3_group(int ns) {
 }
 bool gs_bin3_supported(int ns) { return l1_lds_bytes(ns, 256) <= 140 * 1024 && ns < (1 << 16); }     // (l1_scatter packs S << 16 | clipped rectangle)
 
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < GS_WAVE; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
 __device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t *sm, int nwaves) {
 #pragma unroll
     for (int d = GS_WAVE / 2; d > 0; d >>= 1) v += __shfl_down(v, d);
@@ -245,7 +237,7 @@ __global__ __launch_bounds__(256) void l1_rowscan_kernel(L1Args a) {
     for (int base = 0; base < a.nwg; base += 256) {
         const int i = base + tid;
         const uint32_t v = i < a.nwg ? row[i] : 0u;
-        const uint32_t incl = wave_incl_scan_u32(v, lane);
+        const uint32_t incl = wave_incl_scan(v, lane);
         __syncthreads();
         if (lane == 63) sm[wv] = incl;
         __syncthreads();
@@ -296,7 +288,7 @@ __global__ __launch_bounds__(1024) void l1_scatter_kernel(L1Args a) {
         const uint32_t lc = S < a.ns ? lstart[S] : 0u;
         uint32_t v = v_first, tb = tb_first;
         if (b0 > 0) { v = S < a.ns ? a.row_total[S] : 0u; tb = S < a.ns ? a.table[(size_t)S * a.nwg + chunk] : 0u; }
-        const uint32_t incl = wave_incl_scan_u32(v, lane), lincl = wave_incl_scan_u32(lc, lane);
+        const uint32_t incl = wave_incl_scan(v, lane), lincl = wave_incl_scan(lc, lane);
         __syncthreads();
         if (lane == 63) { sm[wv] = incl; sm[16 + wv] = lincl; }
         __syncthreads();
@@ -360,7 +352,7 @@ __device__ bool find_work(const GsBin3Args &a, uint32_t *sh, int &S, uint32_t &e
         const int s = base + tid;
         uint32_t nseg = 0, c0 = 0, c1 = 0;
         if (s < a.ns) { const uint2 cr = reinterpret_cast<const uint2 *>(a.cranges)[s]; c0 = cr.x; c1 = cr.y; nseg = (c1 - c0 + (L2_SEG - 1)) / L2_SEG; }
-        const uint32_t incl = wave_incl_scan_u32(nseg, lane);
+        const uint32_t incl = wave_incl_scan(nseg, lane);
         __syncthreads();                                   // sh[0 .. R) free again (and the initial sh[R] visible)
         if (lane == 63) sh[wv] = incl;
         __syncthreads();
@@ -483,7 +475,7 @@ __global__ __launch_bounds__(1024) void l2_ranges_kernel(const uint32_t *__restr
             v[k] = t < ntiles && !(done && done[t]) ? tilecnt[t] : 0u;
             tot += v[k];
         }
-        const uint32_t incl = wave_incl_scan_u32(tot, lane);
+        const uint32_t incl = wave_incl_scan(tot, lane);
         __syncthreads();
         if (lane == 63) sm[wv] = incl;
         __syncthreads();

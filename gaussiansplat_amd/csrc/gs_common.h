@@ -95,10 +95,6 @@ struct GsPreprocess2DBwdArgs {
 hipError_t gs_launch_preprocess2d(const GsPreprocess2DArgs &a, hipStream_t stream);
 hipError_t gs_launch_preprocess2d_bwd(const GsPreprocess2DBwdArgs &a, hipStream_t stream);
 
-struct GsSortScratch {     // sized by gs_sort_scratch_bytes
-    uint32_t *block_hist;  // [256][nblocks]
-    uint32_t *digit_total; // [256]
-};
 size_t gs_sort_table_entries(int64_t n_max);
 // Stable LSD radix sort of n 64-bit keys on bits [bit_lo, bit_hi); result ends in *out_is_b.  final_low32 != null: the
 // last pass writes only the low 32 bits of every key (the id of a (key | id) pair) to final_low32, not the 64-bit keys.
@@ -120,8 +116,6 @@ hipError_t gs_depth_sort_buckets(const uint32_t *keys32, uint64_t *pairs_a, uint
 
 // checks on the current device that one ds_add_rtn_u32 hands same-address lanes their pre-values in ascending lane order
 hipError_t gs_probe_lds_atomic_order(hipStream_t s, int *mismatches);
-hipError_t gs_launch_depth_pairs(const uint32_t *depth_key, uint64_t *pairs, int64_t n, hipStream_t s);
-hipError_t gs_launch_unpack_perm(const uint64_t *pairs, uint32_t *perm, int64_t n, hipStream_t s);
 // counts[s] = tiles of gaussian perm[s] (perm may be null = identity), then exclusive scan
 // into offsets[0..n]; offsets[n] = total instances.
 hipError_t gs_launch_count_scan(const uint16_t *rect, const uint32_t *perm, uint32_t *offsets,
@@ -422,6 +416,9 @@ hipError_t gs_launch_sh_from_views(int64_t n, int sh_degree, const float *means,
 // (dense null) the composite backward's sums g2d / g2d_fixed as gs_launch_pack_drgb takes them.
 #define GS_TOUCHED_CHUNK 256
 inline int64_t gs_touched_chunks(int64_t n) { return (n + GS_TOUCHED_CHUNK - 1) / GS_TOUCHED_CHUNK; }
+// exclusive prefix sums of `rows` rows of nchunks per-chunk counts, one workgroup per row (the views of a touched-rows rebuild, the
+// classes of a density plan); totals (may be null): the rows' sums
+hipError_t gs_launch_chunk_scan(const uint32_t *chunk_cnt, int64_t *chunk_off, int64_t nchunks, int rows, int64_t *totals, hipStream_t s);
 hipError_t gs_launch_touched_pack(const float *dense, const float *g2d, const long long *g2d_fixed, int64_t n, int32_t *bits, float *rows,
                                   int64_t *count, uint32_t *chunk_cnt, int64_t *chunk_off, hipStream_t s);
 hipError_t gs_launch_sh_from_touched(int64_t n, int sh_degree, const float *means, int nviews, const float *cams, const int32_t *bits,

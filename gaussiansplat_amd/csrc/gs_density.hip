@@ -7,8 +7,8 @@
 //                                  the 64-byte row, 12 B of statistics; writes 12 B.
 //   gs_density_decide_kernel       element-wise: 0 keep, 1 clone, 2 split, 3 prune -- comparisons of stored floats and integers only.
 //   PLAN: ordered compaction of three output classes WITHOUT any workgroup waiting for another, the shape of the touched-rows pack
-//   (gs_touched.hip): gs_density_class_kernel (per chunk of 256 gaussians: ballots -> three counts), gs_density_scan_kernel (one
-//   workgroup per class: exclusive offsets and the class total).
+//   (gs_touched.hip): gs_density_class_kernel (per chunk of 256 gaussians: ballots -> three counts), then that pack's own chunk scan
+//   (gs_launch_chunk_scan, one workgroup per class: exclusive offsets and the class total).
 //   gs_density_restructure_kernel  per chunk: every thread re-derives its rank inside the chunk from the same ballots and copies its row to
 //                                  the survivors' block, the clones' block and / or writes its two children into the splits' block; the
 //                                  gradient-shaped companion sets (Adam's moments) ride along: survivors copied, new rows +0.
@@ -99,33 +99,6 @@ __global__ __launch_bounds__(GS_DENSITY_CHUNK) void gs_density_class_kernel(cons
         for (int w = 0; w < GS_DENSITY_WAVES; ++w) s += wave_cnt[threadIdx.x][w];
         chunk_cnt[(int64_t)threadIdx.x * nchunks + blockIdx.x] = (uint32_t)s;
     }
-}
-
-// One workgroup per class (row of `nchunks` counts): exclusive prefix sums and the row's total.  Every thread sums a contiguous span,
-// the 1024 span sums are scanned in LDS -- gs_touched_scan_kernel's shape.
-__global__ __launch_bounds__(1024) void gs_density_scan_kernel(const uint32_t *__restrict__ chunk_cnt, int64_t *__restrict__ chunk_off,
-                                                                int64_t nchunks, int64_t *__restrict__ totals) {
-    __shared__ long long s[2][1024];
-    const uint32_t *c = chunk_cnt + (int64_t)blockIdx.x * nchunks;
-    int64_t *o = chunk_off + (int64_t)blockIdx.x * nchunks;
-    const int t = threadIdx.x;
-    const int64_t per = (nchunks + 1023) / 1024;
-    const int64_t lo = min((int64_t)t * per, nchunks), hi = min(lo + per, nchunks);
-    long long sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += c[i];
-    s[0][t] = sum;
-    __syncthreads();
-    int cur = 0;
-    for (int d = 1; d < 1024; d <<= 1) {                                   // reads s[cur], writes s[cur ^ 1]: one barrier per step
-        long long v = s[cur][t];
-        if (t >= d) v += s[cur][t - d];
-        s[cur ^ 1][t] = v;
-        __syncthreads();
-        cur ^= 1;
-    }
-    long long run = s[cur][t] - sum;
-    for (int64_t i = lo; i < hi; ++i) { o[i] = run; run += c[i]; }
-    if (t == 1023) totals[blockIdx.x] = s[cur][1023];
 }
 
 // w floats of row `srow` of src to row `drow` of dst, bit for bit (src null: +0).  16-byte accesses when the rows are 16-byte aligned.
@@ -261,8 +234,7 @@ hipError_t gs_launch_density_plan(const int32_t *action, int64_t n, uint32_t *ch
     if (!density_grid(n, &blocks)) return hipErrorInvalidValue;
     const int64_t nchunks = gs_density_chunks(n);
     hipLaunchKernelGGL(gs_density_class_kernel, dim3(blocks), dim3(GS_DENSITY_CHUNK), 0, s, action, n, chunk_cnt, nchunks, totals);
-    hipLaunchKernelGGL(gs_density_scan_kernel, dim3(GS_DENSITY_CLASSES), dim3(1024), 0, s, (const uint32_t *)chunk_cnt, chunk_off, nchunks, totals);
-    return hipGetLastError();
+    return gs_launch_chunk_scan(chunk_cnt, chunk_off, nchunks, GS_DENSITY_CLASSES, totals, s);
 }
 
 hipError_t gs_launch_density_restructure(const GsDensityRestructureArgs &a, hipStream_t s) {

@@ -13,13 +13,7 @@
 // pass is stable, so the result is bit-identical to a stable sort of the full 64-bit keys
 // with ties in gaussian-index order.  All of this is HBM-bound integer work: coalesced 8-byte
 // streams, LDS histograms and an LDS-staged scatter; no MFMA.
-#include "gs_common.h"
-
-#define RS_THREADS 256
-#define RS_ITEMS 16
-#define RS_CHUNK (RS_THREADS * RS_ITEMS)   // 4096 keys per workgroup
-#define RS_RADIX 256
-#define RS_WAVES (RS_THREADS / GS_WAVE)
+#include "gs_radix.h"
 
 size_t gs_sort_table_entries(int64_t n_max) {
     const int64_t nb = (n_max + RS_CHUNK - 1) / RS_CHUNK;
@@ -108,15 +102,6 @@ __global__ __launch_bounds__(NT) void rs_hist_kernel(const uint64_t *__restrict_
 // One workgroup per digit: exclusive scan of its row of per-block counts, offset by the total
 // of all smaller digits (each workgroup re-reduces the rows below it -- nblocks*256 dwords from
 // L2, negligible next to the key traffic).
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < GS_WAVE; d <<= 1) {
-        uint32_t t = __shfl_up(v, d);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
 __device__ uint32_t block_reduce_u32(uint32_t v, uint32_t *sm) {
 #pragma unroll
     for (int d = GS_WAVE / 2; d > 0; d >>= 1) v += __shfl_down(v, d);
@@ -179,27 +164,20 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scan_kernel(uint32_t *__restric
 }
 
 // ---------------------------------------------------------------- radix pass: stable scatter
-// Wave w owns keys [w*1024, (w+1)*1024) of the chunk in 16 rounds of 64 (wave-striped), so
-// the stable rank order is (wave, round, lane).  Ranks come from wave64 ballots (8 per round:
-// the set of lanes holding the same digit) and a per-wave running LDS counter; keys are then
-// placed digit-contiguously in LDS and written out in runs.
+// The chunk's keys are requested, the table entry is fetched, and radix_scatter_chunk (gs_radix.h) does the rest.
 // out32 != null (last pass of a (key | id) pair sort): only the low word -- the id -- is written, as 32 bits.
 // NT threads per 4096-key chunk: 256 (sixteen rounds per wave) for the big instance sorts, 1024 (four rounds, sixteen waves)
 // for the depth sort, whose 244 workgroups at 1 M gaussians would otherwise leave one wave per SIMD to hide every latency.
 template <int NT, bool ATOMIC_RANK, bool BUCKETS = false>
-__global__ __launch_bounds__(NT) void rs_scatter_kernel(const uint64_t *__restrict__ in, const uint32_t *__restrict__ in32,
-                                                         uint64_t *__restrict__ out,
-                                                         int64_t n, int shift, uint32_t mask,
-                                                         const uint32_t *__restrict__ block_hist, int nblocks,
+__global__ __launch_bounds__(NT) void rs_scatter_kernel(const uint64_t *__restrict__ in, const uint32_t *__restrict__ in32, uint64_t *__restrict__ out,
+                                                         int64_t n, int shift, uint32_t mask, const uint32_t *__restrict__ block_hist, int nblocks,
                                                          uint32_t *__restrict__ out32, const uint32_t *__restrict__ row_total,
                                                          const uint32_t *__restrict__ range_acc = nullptr) {
     constexpr int NW = NT / GS_WAVE, ITEMS = RS_CHUNK / NT;
     __shared__ uint64_t skeys[RS_CHUNK];                 // 32 KiB
     __shared__ uint32_t wcnt[NW][RS_RADIX];              // running count per (wave, digit)
-    __shared__ uint32_t lpre[RS_RADIX];                  // exclusive prefix over digits in this chunk
-    __shared__ uint32_t gbase[RS_RADIX];
-    __shared__ uint32_t sm[RS_RADIX / GS_WAVE];
-    __shared__ uint32_t sh2[2];
+    __shared__ uint32_t lpre[RS_RADIX], gbase[RS_RADIX];  // the chunk's exclusive prefix over the digits; its first output position per digit
+    __shared__ uint32_t sm[RS_RADIX / GS_WAVE], sh2[2];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int64_t base = (int64_t)blockIdx.x * RS_CHUNK;
     const int64_t remain = n - base;
@@ -207,9 +185,8 @@ __global__ __launch_bounds__(NT) void rs_scatter_kernel(const uint64_t *__restri
     uint64_t key[ITEMS];                                 // requested first: the prologue below (range, table entry, totals) hides their latency
 #pragma unroll
     for (int r = 0; r < ITEMS; ++r) {
-        const int li = w * (GS_WAVE * ITEMS) + r * GS_WAVE + lane;      // index inside the chunk
-        const bool valid = li < cnt;
-        key[r] = !valid ? ~0ull : in32 ? (((uint64_t)in32[base + li] << 32) | (uint32_t)(base + li)) : in[base + li];
+        const int li = RS_LI(w, r, lane, GS_WAVE * ITEMS);                        // index inside the chunk
+        key[r] = li >= cnt ? ~0ull : in32 ? (((uint64_t)in32[base + li] << 32) | (uint32_t)(base + li)) : in[base + li];
     }
     DsMap map{};
     if (BUCKETS) map = ds_load_map(range_acc, sh2);
@@ -218,8 +195,8 @@ __global__ __launch_bounds__(NT) void rs_scatter_kernel(const uint64_t *__restri
     {   // table entry (+ in relative mode the totals of the smaller digits: exclusive scan of the 256 row totals)
         uint32_t g = 0, t = 0;
         if (tid < RS_RADIX) { g = block_hist[(size_t)tid * nblocks + blockIdx.x]; if (row_total) t = row_total[tid]; }
-        if (row_total) {
-            const uint32_t incl = wave_incl_scan(t, lane);
+        if (row_total) {                                                // (written out, not digits_excl_prefix: g takes the sums first, and every
+            const uint32_t incl = wave_incl_scan(t, lane);              // spelling through the helper changed this kernel's vector code)
             if (tid < RS_RADIX && lane == 63) sm[w] = incl;
             __syncthreads();
             if (tid < RS_RADIX) { for (int k = 0; k < w; ++k) g += sm[k]; g += incl - t; }
@@ -228,90 +205,31 @@ __global__ __launch_bounds__(NT) void rs_scatter_kernel(const uint64_t *__restri
         if (tid < RS_RADIX) gbase[tid] = g;
     }
     __syncthreads();
-
-    uint32_t rank[ITEMS];
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int r = 0; r < ITEMS; ++r) {
-        const int li = w * (GS_WAVE * ITEMS) + r * GS_WAVE + lane;
-        const bool valid = li < cnt;
-        const uint32_t dg = valid ? digit_of(key[r]) : (RS_RADIX - 1);
-        if (ATOMIC_RANK) {                                              // see gs_bin2.hip rank_round_atomic
-            rank[r] = 0;
-            if (valid) rank[r] = atomicAdd(&wcnt[w][dg], 1u);
-        } else {
-            unsigned long long peers = __ballot(valid);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                const unsigned long long bal = __ballot((dg >> b) & 1u);
-                peers &= ((dg >> b) & 1u) ? bal : ~bal;
-            }
-            const uint32_t before = wcnt[w][dg];                        // same-digit keys of earlier rounds
-            rank[r] = before + (uint32_t)__popcll(peers & lt_mask);
-            __builtin_amdgcn_wave_barrier();
-            if (valid && (peers & lt_mask) == 0ull) wcnt[w][dg] = before + (uint32_t)__popcll(peers);   // group leader
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-    __syncthreads();
-    // thread `tid` == digit: per-wave exclusive offsets and the chunk's digit prefix
-    uint32_t tot = 0;
-    if (tid < RS_RADIX) {
-#pragma unroll
-        for (int k = 0; k < NW; ++k) { const uint32_t c = wcnt[k][tid]; wcnt[k][tid] = tot; tot += c; }
-    }
-    const uint32_t incl = wave_incl_scan(tot, lane);
-    if (tid < RS_RADIX && lane == 63) sm[w] = incl;
-    __syncthreads();
-    if (tid < RS_RADIX) {
-        uint32_t woff = 0;
-        for (int k = 0; k < w; ++k) woff += sm[k];
-        lpre[tid] = woff + incl - tot;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < ITEMS; ++r) {
-        const int li = w * (GS_WAVE * ITEMS) + r * GS_WAVE + lane;
-        if (li < cnt) {
-            const uint32_t dg = digit_of(key[r]);
-            skeys[lpre[dg] + wcnt[w][dg] + rank[r]] = key[r];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < ITEMS; ++r) {
-        const int li = r * NT + tid;
-        if (li < cnt) {
-            const uint64_t k = skeys[li];
-            const uint32_t dg = digit_of(k);
-            const size_t o = (size_t)gbase[dg] + (uint32_t)(li - (int)lpre[dg]);
-            if (out32) out32[o] = (uint32_t)k; else out[o] = k;
-        }
-    }
+    radix_scatter_chunk<NT, ATOMIC_RANK>(key, cnt, digit_of, [=](size_t o, uint64_t k) { if (out32) out32[o] = (uint32_t)k; else out[o] = k; },
+                                         skeys, wcnt, lpre, gbase, sm);
 }
 
 // ---------------------------------------------------------------- lane-order probe of the LDS atomic rank
 // 256 workgroups x 32 rounds: every wave draws digits from a hash (all-distinct, few-valued, constant and 32-valued
-// patterns, ~6 % inactive lanes), takes atomicAdd-return on an LDS counter row and compares the value with the ballot
-// rank (number of lower active lanes with the same digit).  Any mismatch makes gs_create fall back to ballot ranks.
+// patterns, ~6 % inactive lanes) and ranks them with both forms the scatter kernels use, one after the other on the wave's
+// zeroed counter row: rank_round_atomic must return what rank_round does (the number of lower active lanes with the same
+// digit).  Any mismatch makes gs_create fall back to ballot ranks.
 __global__ __launch_bounds__(256) void lds_atomic_order_probe_kernel(unsigned *__restrict__ bad) {
-    __shared__ unsigned cnt[4][RS_RADIX];
+    __shared__ uint32_t cnt[4][RS_RADIX];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    auto zero_row = [=] { for (int i = lane; i < RS_RADIX; i += 64) cnt[w][i] = 0; __builtin_amdgcn_wave_barrier(); };
     unsigned nbad = 0;
     for (int r = 0; r < 32; ++r) {
-        for (int i = lane; i < RS_RADIX; i += 64) cnt[w][i] = 0;
-        __builtin_amdgcn_wave_barrier();
+        zero_row();
         unsigned h = (unsigned)(((blockIdx.x * 4 + w) * 32 + r) * 64 + lane) * 2654435761u;
         h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
         const int mode = (r + w) & 3;
         const unsigned d = mode == 0 ? (h >> 24) : mode == 1 ? ((h >> 24) & 7u) : mode == 2 ? 5u : ((h >> 24) & 31u);
         const bool active = ((h >> 8) & 15u) != 0u;
-        unsigned got = 0;
-        if (active) got = atomicAdd(&cnt[w][d], 1u);
-        unsigned long long peers = __ballot(active);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) { const unsigned long long bal = __ballot((d >> b) & 1u); peers &= ((d >> b) & 1u) ? bal : ~bal; }
-        const unsigned want = (unsigned)__popcll(peers & ((1ull << lane) - 1ull));
+        const uint32_t got = rank_round_atomic(d, active, cnt[w]);
+        __builtin_amdgcn_wave_barrier();
+        zero_row();
+        const uint32_t want = rank_round(d, active, lane, cnt[w]);
         if (active && got != want) ++nbad;
         __builtin_amdgcn_wave_barrier();
     }
@@ -364,14 +282,14 @@ hipError_t gs_radix_sort_u64(uint64_t *a, uint64_t *b, int64_t n, int bit_lo, in
             uint32_t *tot = digit_total + pass * RS_RADIX;
             hipLaunchKernelGGL(rs_hist_kernel<1024>, dim3(nblocks), dim3(1024), 0, stream, src, k32, n, shift, mask, block_hist, nblocks, (uint32_t *)nullptr);
             hipLaunchKernelGGL(rs_scan_kernel, dim3(RS_RADIX), dim3(RS_THREADS), 0, stream, block_hist, nblocks, (const uint32_t *)nullptr, tot);
-            if (ballot_ranks) hipLaunchKernelGGL((rs_scatter_kernel<1024, false>), dim3(nblocks), dim3(1024), 0, stream, src, k32, dst, n, shift, mask, block_hist, nblocks, o32, tot);
-            else hipLaunchKernelGGL((rs_scatter_kernel<1024, true>), dim3(nblocks), dim3(1024), 0, stream, src, k32, dst, n, shift, mask, block_hist, nblocks, o32, tot);
+            rs_launch_ranked(ballot_ranks, rs_scatter_kernel<1024, false>, rs_scatter_kernel<1024, true>, dim3(nblocks), dim3(1024), stream,
+                             src, k32, dst, n, shift, mask, block_hist, nblocks, o32, tot, (const uint32_t *)nullptr);
         } else {
             hipLaunchKernelGGL(rs_hist_kernel<RS_THREADS>, dim3(nblocks), dim3(RS_THREADS), 0, stream, src, k32, n, shift, mask, block_hist, nblocks, (uint32_t *)nullptr);
             hipLaunchKernelGGL(rs_digit_totals_kernel, dim3(RS_RADIX), dim3(RS_THREADS), 0, stream, block_hist, nblocks, digit_total);
             hipLaunchKernelGGL(rs_scan_kernel, dim3(RS_RADIX), dim3(RS_THREADS), 0, stream, block_hist, nblocks, digit_total, (uint32_t *)nullptr);
-            if (ballot_ranks) hipLaunchKernelGGL((rs_scatter_kernel<RS_THREADS, false>), dim3(nblocks), dim3(RS_THREADS), 0, stream, src, k32, dst, n, shift, mask, block_hist, nblocks, o32, (const uint32_t *)nullptr);
-            else hipLaunchKernelGGL((rs_scatter_kernel<RS_THREADS, true>), dim3(nblocks), dim3(RS_THREADS), 0, stream, src, k32, dst, n, shift, mask, block_hist, nblocks, o32, (const uint32_t *)nullptr);
+            rs_launch_ranked(ballot_ranks, rs_scatter_kernel<RS_THREADS, false>, rs_scatter_kernel<RS_THREADS, true>, dim3(nblocks), dim3(RS_THREADS), stream,
+                             src, k32, dst, n, shift, mask, block_hist, nblocks, o32, (const uint32_t *)nullptr, (const uint32_t *)nullptr);
         }
         uint64_t *t = src; src = dst; dst = t;
         *result_in_b ^= 1;
@@ -392,14 +310,12 @@ hipError_t gs_radix_sort_u64(uint64_t *a, uint64_t *b, int64_t n, int bit_lo, in
 #define DS_PATHOLOGICAL 8
 #define DS_CAP_OF(NT) ((NT) * DS_ITEMS)
 
-// Element `li` of the (at most NT * 8) elements a workgroup holds in registers: wave w owns the `per` consecutive elements from
-// w * per on, round r of the wave the 64 from r * 64 on (per = a multiple of 64 sized to the element count, so that every wave
-// has work and a short bucket costs few rounds).  (wave, round, lane) ascending == li ascending: the stable order.
-#define DS_LI(w, r, lane, per) ((w) * (per) + (r) * GS_WAVE + (lane))
+// The (at most NT * 8) elements of a bucket are held as RS_LI(w, r, lane, per) with per = a multiple of 64 sized to the element
+// count, so that every wave has work and a short bucket costs few rounds.
 
 // One stable counting-sort step on digit (sub >> shift) & 255 of the elements held in registers (valid if li < cnt; `rounds`
 // rounds per wave): afterwards skey / sid hold them digit-contiguously, lpre[d] is the first slot of digit d and ltot[d] their
-// number.  Ranks from wave ballots (as rs_scatter_kernel).
+// number.  Ranks from wave ballots (rank_round).
 template <int NT>
 __device__ __forceinline__ void ds_stage(const uint32_t (&sub)[DS_ITEMS], const uint32_t (&id)[DS_ITEMS], const int cnt, const int per, const int rounds,
                                          const int shift, uint32_t *skey, uint32_t *sid, uint32_t (*wcnt)[RS_RADIX], uint32_t *lpre, uint32_t *ltot,
@@ -409,49 +325,23 @@ __device__ __forceinline__ void ds_stage(const uint32_t (&sub)[DS_ITEMS], const 
     for (int i = tid; i < NW * RS_RADIX; i += NT) (&wcnt[0][0])[i] = 0;
     __syncthreads();                                                    // (also: every reader of skey / sid of the previous step is done)
     uint32_t rank[DS_ITEMS];
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
 #pragma unroll
     for (int r = 0; r < DS_ITEMS; ++r) {
         rank[r] = 0;
-        if (r < rounds && DS_LI(w, r, 0, per) < cnt) {                  // wave-uniform
-            const int li = DS_LI(w, r, lane, per);
-            const bool valid = li < cnt;
-            const uint32_t dg = valid ? ((sub[r] >> shift) & 255u) : 255u;
-            unsigned long long peers = __ballot(valid);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                const unsigned long long bal = __ballot((dg >> b) & 1u);
-                peers &= ((dg >> b) & 1u) ? bal : ~bal;
-            }
-            const uint32_t before = wcnt[w][dg];
-            rank[r] = before + (uint32_t)__popcll(peers & lt_mask);
-            __builtin_amdgcn_wave_barrier();
-            if (valid && (peers & lt_mask) == 0ull) wcnt[w][dg] = before + (uint32_t)__popcll(peers);
-            __builtin_amdgcn_wave_barrier();
+        if (r < rounds && RS_LI(w, r, 0, per) < cnt) {                  // wave-uniform
+            const bool valid = RS_LI(w, r, lane, per) < cnt;
+            rank[r] = rank_round(valid ? ((sub[r] >> shift) & 255u) : 255u, valid, lane, wcnt[w]);
         }
     }
     __syncthreads();
-    uint32_t tot = 0;
-    if (tid < RS_RADIX) {
-#pragma unroll
-        for (int k = 0; k < NW; ++k) { const uint32_t c = wcnt[k][tid]; wcnt[k][tid] = tot; tot += c; }
-    }
-    const uint32_t incl = wave_incl_scan(tot, lane);
-    if (tid < RS_RADIX && lane == 63) sm[w] = incl;
-    __syncthreads();
-    if (tid < RS_RADIX) {
-        uint32_t woff = 0;
-        for (int k = 0; k < w; ++k) woff += sm[k];
-        lpre[tid] = woff + incl - tot;
-        ltot[tid] = tot;
-    }
+    const uint32_t tot = digit_prefixes<NW>(wcnt, lpre, sm);
+    if (tid < RS_RADIX) ltot[tid] = tot;
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < DS_ITEMS; ++r) {
-        const int li = DS_LI(w, r, lane, per);
+        const int li = RS_LI(w, r, lane, per);
         if (r < rounds && li < cnt) {
-            const uint32_t dg = (sub[r] >> shift) & 255u;
-            const uint32_t o = lpre[dg] + wcnt[w][dg] + rank[r];
+            const uint32_t o = radix_slot(lpre, wcnt[w], (sub[r] >> shift) & 255u, rank[r]);
             skey[o] = sub[r]; sid[o] = id[r];
         }
     }
@@ -510,7 +400,7 @@ __global__ __launch_bounds__(NT) void ds_local_kernel(uint64_t *__restrict__ pai
         uint32_t mn = 0xFFFFFFFFu, mx = 0u;
 #pragma unroll
         for (int r = 0; r < DS_ITEMS; ++r) {
-            const int li = DS_LI(w, r, lane, per);
+            const int li = RS_LI(w, r, lane, per);
             sub[r] = 0; id[r] = 0;
             if (r < rounds && li < (int)cnt) { const uint64_t p = pairs[(size_t)start + li]; sub[r] = (uint32_t)(p >> 32); id[r] = (uint32_t)p; mn = min(mn, sub[r]); mx = max(mx, sub[r]); }
         }
@@ -519,7 +409,7 @@ __global__ __launch_bounds__(NT) void ds_local_kernel(uint64_t *__restrict__ pai
         const int bits = spread ? 32 - __builtin_clz(spread) : 0, passes = (bits + 7) >> 3;
         if (passes == 0) {                                              // one key value: index order is the order
 #pragma unroll
-            for (int r = 0; r < DS_ITEMS; ++r) { const int li = DS_LI(w, r, lane, per); if (r < rounds && li < (int)cnt) perm[(size_t)start + li] = id[r]; }
+            for (int r = 0; r < DS_ITEMS; ++r) { const int li = RS_LI(w, r, lane, per); if (r < rounds && li < (int)cnt) perm[(size_t)start + li] = id[r]; }
             return;
         }
 #pragma unroll
@@ -529,7 +419,7 @@ __global__ __launch_bounds__(NT) void ds_local_kernel(uint64_t *__restrict__ pai
             if (p + 1 < passes) {
 #pragma unroll
                 for (int r = 0; r < DS_ITEMS; ++r) {
-                    const int li = DS_LI(w, r, lane, per);
+                    const int li = RS_LI(w, r, lane, per);
                     if (r < rounds && li < (int)cnt) { sub[r] = skey[li]; id[r] = sid[li]; }
                 }
             }
@@ -558,11 +448,7 @@ __global__ __launch_bounds__(NT) void ds_local_kernel(uint64_t *__restrict__ pai
         for (uint32_t i = tid; i < cnt; i += NT) atomicAdd(&gbase[(((uint32_t)(src[i] >> 32) - mn) >> shift) & 255u], 1u);
         __syncthreads();
         {                                                               // exclusive prefix over the digits
-            const uint32_t t = tid < RS_RADIX ? gbase[tid] : 0u;
-            const uint32_t incl = wave_incl_scan(t, lane);
-            if (tid < RS_RADIX && lane == 63) sm[w] = incl;
-            __syncthreads();
-            if (tid < RS_RADIX) { uint32_t woff = 0; for (int k = 0; k < w; ++k) woff += sm[k]; gbase[tid] = woff + incl - t; }
+            digits_excl_prefix(tid < RS_RADIX ? gbase[tid] : 0u, sm, [=](uint32_t pre) { gbase[tid] = pre; });
             __syncthreads();
         }
         for (uint32_t c0 = 0; c0 < cnt; c0 += CAP) {
@@ -570,14 +456,14 @@ __global__ __launch_bounds__(NT) void ds_local_kernel(uint64_t *__restrict__ pai
             const int per = ((nc + NT - 1) / NT) * GS_WAVE, rounds = per / GS_WAVE;
 #pragma unroll
             for (int r = 0; r < DS_ITEMS; ++r) {
-                const int li = DS_LI(w, r, lane, per);
+                const int li = RS_LI(w, r, lane, per);
                 sub[r] = 0; id[r] = 0;
                 if (r < rounds && li < nc) { const uint64_t pr = src[(size_t)c0 + li]; sub[r] = (uint32_t)(pr >> 32) - mn; id[r] = (uint32_t)pr; }
             }
             ds_stage<NT>(sub, id, nc, per, rounds, shift, skey, sid, wcnt, lpre, ltot, sm);
             for (int li = tid; li < nc; li += NT) {
-                const uint32_t k = skey[li], dg = (k >> shift) & 255u;
-                const size_t o = (size_t)gbase[dg] + (uint32_t)(li - (int)lpre[dg]);
+                const uint32_t k = skey[li];
+                const size_t o = radix_dest(gbase, lpre, (k >> shift) & 255u, li);
                 if (p + 1 < passes) dst[o] = ((uint64_t)(k + mn) << 32) | sid[li];
                 else perm[(size_t)start + o] = sid[li];
             }
@@ -611,33 +497,11 @@ hipError_t gs_depth_sort_buckets(const uint32_t *keys32, uint64_t *pairs_a, uint
     hipLaunchKernelGGL((rs_hist_kernel<1024, true>), dim3(nblocks), dim3(1024), 0, stream, (const uint64_t *)nullptr, keys32, n, 0, 0u, block_hist, nblocks,
                        (uint32_t *)nullptr, range_acc);
     hipLaunchKernelGGL(rs_scan_kernel, dim3(RS_RADIX), dim3(RS_THREADS), 0, stream, block_hist, nblocks, (const uint32_t *)nullptr, digit_total);
-    if (ballot_ranks) hipLaunchKernelGGL((rs_scatter_kernel<1024, false, true>), dim3(nblocks), dim3(1024), 0, stream, (const uint64_t *)nullptr, keys32, pairs_b, n, 0, 0u,
-                                         block_hist, nblocks, (uint32_t *)nullptr, digit_total, range_acc);
-    else hipLaunchKernelGGL((rs_scatter_kernel<1024, true, true>), dim3(nblocks), dim3(1024), 0, stream, (const uint64_t *)nullptr, keys32, pairs_b, n, 0, 0u,
-                            block_hist, nblocks, (uint32_t *)nullptr, digit_total, range_acc);
+    rs_launch_ranked(ballot_ranks, rs_scatter_kernel<1024, false, true>, rs_scatter_kernel<1024, true, true>, dim3(nblocks), dim3(1024), stream,
+                     (const uint64_t *)nullptr, keys32, pairs_b, n, 0, 0u, block_hist, nblocks, (uint32_t *)nullptr, digit_total, range_acc);
     // small models: four waves per bucket (capacity 2048: eight times the mean bucket at 64 K gaussians)
     if (n <= 65536) hipLaunchKernelGGL(ds_local_kernel<256>, dim3(DS_BUCKETS), dim3(256), 0, stream, pairs_b, pairs_a, digit_total, perm, reset_acc, host_stat);
     else hipLaunchKernelGGL(ds_local_kernel<1024>, dim3(DS_BUCKETS), dim3(1024), 0, stream, pairs_b, pairs_a, digit_total, perm, reset_acc, host_stat);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------- depth pairs
-__global__ void depth_pairs_kernel(const uint32_t *__restrict__ key, uint64_t *__restrict__ pairs, int64_t n) {
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < n) pairs[g] = ((uint64_t)key[g] << 32) | (uint32_t)g;
-}
-__global__ void unpack_perm_kernel(const uint64_t *__restrict__ pairs, uint32_t *__restrict__ perm, int64_t n) {
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < n) perm[g] = (uint32_t)pairs[g];
-}
-hipError_t gs_launch_depth_pairs(const uint32_t *depth_key, uint64_t *pairs, int64_t n, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(depth_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, depth_key, pairs, n);
-    return hipGetLastError();
-}
-hipError_t gs_launch_unpack_perm(const uint64_t *pairs, uint32_t *perm, int64_t n, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(unpack_perm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pairs, perm, n);
     return hipGetLastError();
 }
 
@@ -681,15 +545,10 @@ __global__ __launch_bounds__(1024) void scan_block_sums_kernel(uint32_t *__restr
         const int i = base + threadIdx.x;
         const uint32_t v = (i < nb) ? block_sums[i] : 0u;
         t64 += v;
-        const uint32_t incl = wave_incl_scan(v, lane);
-        if (lane == 63) sm[w] = incl;
+        const uint32_t pre = block_excl_prefix<1024>(v, sm), c = carry;
+        if (i < nb) block_sums[i] = c + pre;
         __syncthreads();
-        uint32_t woff = 0;
-        for (int k = 0; k < w; ++k) woff += sm[k];
-        const uint32_t c = carry;
-        if (i < nb) block_sums[i] = c + woff + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = c + woff + incl;
+        if (threadIdx.x == 1023) carry = c + pre + v;
         __syncthreads();
     }
 #pragma unroll
@@ -707,7 +566,6 @@ __global__ __launch_bounds__(1024) void scan_block_sums_kernel(uint32_t *__restr
 __global__ __launch_bounds__(SC_THREADS) void count_scan_kernel(int64_t n, const uint32_t *__restrict__ block_sums,
                                                                  uint32_t *__restrict__ offsets) {
     __shared__ uint32_t sm[SC_THREADS / GS_WAVE];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t base = (int64_t)blockIdx.x * SC_CHUNK + (int64_t)threadIdx.x * SC_ITEMS;
     uint32_t c[SC_ITEMS], s = 0;
 #pragma unroll
@@ -716,11 +574,7 @@ __global__ __launch_bounds__(SC_THREADS) void count_scan_kernel(int64_t n, const
         c[i] = (idx < n) ? offsets[idx] : 0u;                            // the count parked by pass 1
         s += c[i];
     }
-    const uint32_t incl = wave_incl_scan(s, lane);
-    if (lane == 63) sm[w] = incl;
-    __syncthreads();
-    uint32_t off = block_sums[blockIdx.x] + incl - s;
-    for (int k = 0; k < w; ++k) off += sm[k];
+    uint32_t off = block_sums[blockIdx.x] + block_excl_prefix<SC_THREADS>(s, sm);
 #pragma unroll
     for (int i = 0; i < SC_ITEMS; ++i) {
         const int64_t idx = base + i;

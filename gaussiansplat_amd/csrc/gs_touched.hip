@@ -103,8 +103,9 @@ __global__ __launch_bounds__(256) void gs_touched_count_kernel(const int32_t *__
     if ((threadIdx.x & (GS_TOUCHED_WORDS - 1)) == 0 && chunk < nchunks) chunk_cnt[(int64_t)blockIdx.y * nchunks + chunk] = (uint32_t)p;
 }
 
-// One workgroup per row of `nchunks` counts (blockIdx.x: the pack has one row, the rebuild one per view): exclusive prefix sums,
-// and the row's total when `total` is not null.  Every thread sums a contiguous span, the 1024 span sums are scanned in LDS.
+// One workgroup per row of `nchunks` counts (blockIdx.x: the pack has one row, the rebuild one per view, a density plan one per
+// class): exclusive prefix sums, and the row's total when `total` is not null.  Every thread sums a contiguous span, the 1024 span
+// sums are scanned in LDS.
 __global__ __launch_bounds__(1024) void gs_touched_scan_kernel(const uint32_t *__restrict__ chunk_cnt, int64_t *__restrict__ chunk_off,
                                                                 int64_t nchunks, int64_t *__restrict__ total) {
     __shared__ long long s[2][1024];
@@ -128,6 +129,11 @@ __global__ __launch_bounds__(1024) void gs_touched_scan_kernel(const uint32_t *_
     long long run = s[cur][t] - sum;
     for (int64_t i = lo; i < hi; ++i) { o[i] = run; run += c[i]; }
     if (t == 1023 && total) total[blockIdx.x] = s[cur][1023];
+}
+
+hipError_t gs_launch_chunk_scan(const uint32_t *chunk_cnt, int64_t *chunk_off, int64_t nchunks, int rows, int64_t *totals, hipStream_t s) {
+    hipLaunchKernelGGL(gs_touched_scan_kernel, dim3((unsigned)rows), dim3(1024), 0, s, chunk_cnt, chunk_off, nchunks, totals);
+    return hipGetLastError();
 }
 
 template <int SRC>
@@ -184,7 +190,8 @@ hipError_t gs_launch_touched_pack(const float *dense, const float *g2d, const lo
                            else if (g2d_fixed) hipLaunchKernelGGL(K<2>, grid, block, 0, s, __VA_ARGS__); \
                            else hipLaunchKernelGGL(K<1>, grid, block, 0, s, __VA_ARGS__); } while (0)
     GS_TP(gs_touched_mark_kernel, src, n, bits, words, chunk_cnt);
-    hipLaunchKernelGGL(gs_touched_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)chunk_cnt, chunk_off, nchunks, count);
+    const hipError_t e = gs_launch_chunk_scan(chunk_cnt, chunk_off, nchunks, 1, count, s);   // (also reports the mark launch)
+    if (e != hipSuccess) return e;
     GS_TP(gs_touched_scatter_kernel, src, n, (const int32_t *)bits, words, (const int64_t *)chunk_off, rows);
 #undef GS_TP
     return hipGetLastError();
@@ -197,7 +204,8 @@ hipError_t gs_launch_sh_from_touched(int64_t n, int sh_degree, const float *mean
     const int64_t nchunks = gs_touched_chunks(n), words = (n + 31) / 32;
     if (nchunks > 0x7fffffffLL || nviews <= 0 || nviews > 65535 || sh_degree < 0 || sh_degree > 3) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gs_touched_count_kernel, dim3((unsigned)((words + 255) / 256), (unsigned)nviews), dim3(256), 0, s, bits, words, n, chunk_cnt, nchunks);
-    hipLaunchKernelGGL(gs_touched_scan_kernel, dim3((unsigned)nviews), dim3(1024), 0, s, (const uint32_t *)chunk_cnt, chunk_off, nchunks, (int64_t *)nullptr);
+    const hipError_t e = gs_launch_chunk_scan(chunk_cnt, chunk_off, nchunks, nviews, nullptr, s);   // (also reports the count launch)
+    if (e != hipSuccess) return e;
     const GsTouchedColorSrc src{bits, rows, chunk_off, zero3, words, nchunks, rows_cap};
     const dim3 grid((unsigned)nchunks), block(GS_TOUCHED_CHUNK);
     const int K = (sh_degree + 1) * (sh_degree + 1);

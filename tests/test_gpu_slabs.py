@@ -30,23 +30,36 @@ def _frame(ctx, dC, deg):
     return rounds, img, tr, grads, ctx.work_counters_ex()
 
 
-@pytest.mark.parametrize("fractions,rounds", [((0.3,), 2), ((0.15, 0.5), 3), ((0.1, 0.2, 0.4), 4), ((0.999,), 2), ((0.0005, 0.6), 3)])
+# radix32 = (bin_path, rank_mode): the same frames on the 32-bit radix path (gs_bin2.hip), whose slab rounds drop the instances of
+# completed tiles while ranking (ExpandArgs.done) and hand the second pass its key count on the device (live_total).  The second
+# pass runs on grids of more than 256 tiles and a round has several chunks from 4096 instances on, so these cases take a larger image.
+_SLAB_CASES = [((0.3,), 2), ((0.15, 0.5), 3), ((0.1, 0.2, 0.4), 4), ((0.999,), 2), ((0.0005, 0.6), 3)]
+@pytest.mark.parametrize("fractions,rounds,radix32",
+                         [pytest.param(f, r, None, id="fractions%d-%d" % (i, r)) for i, (f, r) in enumerate(_SLAB_CASES)] +      # (the ids these cases always had)
+                         [pytest.param((0.15, 0.5), 3, (2, rm), id="bin2-rank%d" % rm) for rm in (0, 1)])
 @pytest.mark.parametrize("t_min", [1e-3, 1e-5])
-def test_forced_slabs_bit_identical_to_classic(oracle, fractions, rounds, t_min):
+def test_forced_slabs_bit_identical_to_classic(oracle, fractions, rounds, radix32, t_min):
     from gaussiansplat_amd import synthetic
     O = oracle
     n, W, H, deg = 5000, 112, 72, 2                                          # ragged: 7 x 4.5 tiles
+    path = {}
+    if radix32:
+        W, H = 280, 248                                                      # ragged: 17.5 x 15.5 tiles, 288 > 256
+        path = dict(bin_path=radix32[0], rank_mode=radix32[1])
     sc, cam, T, P, ocam = scene_and_cameras(n, W, H, deg, 17)
     sc["scales"] = sc["scales"] + np.float32(1.2)                           # dense: several hundred entries per tile, pixels freeze
     dC = synthetic.make_dC(W, H, 17)
     res = {}
     for det in (True, False):
-        c0 = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=t_min, deterministic=det, slab_mode=0)
+        c0 = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=t_min, deterministic=det, slab_mode=0, **path)
         r0 = _frame(c0, dC, deg); c0.close()
         assert r0[0] == 1
-        c1 = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=t_min, deterministic=det, slab_mode=1, slab_fractions=fractions)
+        c1 = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=t_min, deterministic=det, slab_mode=1, slab_fractions=fractions, **path)
         r1 = _frame(c1, dC, deg)
         assert r1[0] == rounds, r1[0]
+        if radix32:                                                          # not by falling back: several rounds, on the radix path, two passes, several chunks
+            assert c1.num_rounds > 1 and c1.bin_path_of_frame() == 2, (c1.num_rounds, c1.bin_path_of_frame())
+            assert ((W + 15) // 16) * ((H + 15) // 16) > 256 and c1.num_instances > 4096, c1.num_instances
         with pytest.raises(Exception):
             c1.get_array(13)                                                # lists are spread over the rounds
         c1.close()
@@ -60,6 +73,8 @@ def test_forced_slabs_bit_identical_to_classic(oracle, fractions, rounds, t_min)
             else:
                 assert rel_l2(r1[3][k].reshape(-1), r0[3][k].reshape(-1)) <= 1e-5, k
         res[det] = r1
+    if radix32:
+        return                                                              # (the oracle bars below are this scene's on the small image: held by the cases above)
     ref = O.render(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"], deg, ocam, order=1, t_min=t_min)
     gref = O.backward(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"], deg, ocam, ref["ranges"], ref["ids"], dC, t_min=t_min)
     img, tr = res[False][1], res[False][2]
