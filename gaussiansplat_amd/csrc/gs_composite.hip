@@ -243,11 +243,27 @@ __device__ __forceinline__ void load_row(const float4 *pay4, const size_t g, flo
 
 // The gathered row of the NEXT batch must stay untouched in the registers it was loaded into until the per-entry loop of the current
 // batch is over: any earlier "use" -- even a register copy the allocator inserts to split a live range -- makes the compiler wait for
-// the gather before the loop, i.e. exposes one memory round trip per batch.  Passing the sixteen components through an empty asm
-// AFTER the loop makes that the first use.
+// the gather before the loop, i.e. exposes one memory round trip per batch.  Passing the row through an empty asm AFTER the loop
+// makes that the first use.
+// QUADS (the forward): the row passes as four 128-bit operands.  A 4-float vector operand is one register tuple, so each quad is
+// carried across the loop in the four consecutive VGPRs a global_load_dwordx4 writes, and the conditional gather loads under EXEC
+// straight into them.  With sixteen scalar operands the allocator is free to home the components apart; at the forward's 96 VGPRs it
+// did, in the CULL instantiations: the rows landed in temporary tuples and were copied out one component at a time behind
+// s_waitcnt vmcnt(3) .. vmcnt(0), before the loop (tools/gather_wait.py counts exactly that; profiles/forward_gather_isa.log).
+// !QUADS (the backward): sixteen scalars.  At its 80 VGPRs the production backward keeps the quads together by itself (no wait, no
+// copy: same log); the tuple form reorders its code for nothing, so every backward instantiation keeps the parent's instructions.
+template <bool QUADS>
 __device__ __forceinline__ void first_use_here(float4 &a, float4 &b, float4 &c, float4 &d) {
-    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w),
-                      "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w), "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));
+    if (QUADS) {
+        typedef float quad __attribute__((ext_vector_type(4)));
+        quad qa = {a.x, a.y, a.z, a.w}, qb = {b.x, b.y, b.z, b.w}, qc = {c.x, c.y, c.z, c.w}, qd = {d.x, d.y, d.z, d.w};
+        asm volatile("" : "+v"(qa), "+v"(qb), "+v"(qc), "+v"(qd));
+        a = make_float4(qa.x, qa.y, qa.z, qa.w); b = make_float4(qb.x, qb.y, qb.z, qb.w);
+        c = make_float4(qc.x, qc.y, qc.z, qc.w); d = make_float4(qd.x, qd.y, qd.z, qd.w);
+    } else {
+        asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w),
+                          "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w), "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));
+    }
 }
 
 // a batch of cnt entries compacted to the ones that can matter (CULL; else all of them): this lane's slot among them, and their number
@@ -646,7 +662,7 @@ __device__ __forceinline__ void forward_tile(const GsCompositeArgs &a, const int
 #undef GS_FWD_PIXEL
 #undef GS_FWD_COLUMN
         walked += (uint32_t)cnt; evaluated += (uint32_t)nk;
-        first_use_here(n0, n1, n2, n3);
+        first_use_here<true>(n0, n1, n2, n3);
         clk.entries_done(nk, (unsigned long long)K * (uint32_t)nk);
     }
     if (!capped || stopped || cont == GS_CONT_NONE) break;
@@ -973,7 +989,7 @@ __device__ __forceinline__ void backward_tile(const GsCompositeArgs &a, const in
             finish();
         }
         walked += (uint32_t)cnt; evaluated += (uint32_t)nk;
-        first_use_here(n0, n1, n2, n3);
+        first_use_here<false>(n0, n1, n2, n3);
         clk.entries_done(nk, strip_slots(mq, nk));
     }
     }

@@ -9,8 +9,11 @@ rm -rf $D; mkdir -p $D/x/y/csrc $D/x/include gaussiansplat_amd/lib_ref
 for f in $(git ls-tree --name-only $REV gaussiansplat_amd/csrc/); do git show $REV:$f > $D/x/y/csrc/$(basename $f); done
 git show $REV:include/gsplat.h > $D/x/include/gsplat.h
 cd $D/x/y/csrc
-for f in gs_preprocess gs_preprocess2d; do /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -ffp-contract=off -c $f.hip -o $f.o & done
-for f in $(ls *.hip | sed 's/\.hip$//' | grep -v '^gs_preprocess$\|^gs_preprocess2d$'); do /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -c $f.hip -o $f.o & done
+for f in $(ls *.hip | sed 's/\.hip$//'); do
+  extra=""                                                             # the per-file flags of gaussiansplat_amd/build.py
+  case $f in gs_preprocess|gs_preprocess2d|gs_adam|gs_density|gs_api_density) extra="-ffp-contract=off";; gs_composite|gs_loss) extra="-fno-slp-vectorize";; esac
+  /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wno-unused-function $extra -c $f.hip -o $f.o &
+done
 wait
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../../../../../../gaussiansplat_amd/lib_ref/libgsplat_hip.so *.o -ldl
 echo built gaussiansplat_amd/lib_ref/libgsplat_hip.so from $REV
