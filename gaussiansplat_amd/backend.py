@@ -24,7 +24,7 @@ STAGES = ("preprocess", "depth_sort", "count_scan", "emit", "tile_sort", "ranges
 
 # every symbol include/gsplat.h declares (tests/test_abi.py checks the header against this)
 SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs_last_error", "gs_set_stream",
-           "gs_synchronize", "gs_set_model", "gs_set_model_2d", "gs_set_image_size", "gs_set_camera", "gs_preprocess", "gs_bin", "gs_bind_outputs", "gs_forward", "gs_backward_sgd",
+           "gs_synchronize", "gs_set_model", "gs_set_model_2d", "gs_set_active_sh_degree", "gs_get_active_sh_degree", "gs_set_image_size", "gs_set_camera", "gs_preprocess", "gs_bin", "gs_bind_outputs", "gs_forward", "gs_backward_sgd",
            "gs_backward", "gs_backward_ex", "gs_reset_grads", "gs_loss_l1_dssim", "gs_sgd_step", "gs_comm_unique_id",
            "gs_comm_init", "gs_allreduce_grads", "gs_comm_destroy", "gs_color_grads_pack", "gs_sh_grads_from_views", "gs_color_rows_pack", "gs_sh_grads_from_touched", "gs_grads_alloc", "gs_grads_read", "gs_num_gaussians", "gs_num_instances", "gs_get_array",
            "gs_get_stage_times", "gs_get_stage_stats", "gs_get_work_counters", "gs_get_work_counters_ex", "gs_debug_time_composite",
@@ -133,6 +133,8 @@ def load():
     L.gs_get_work_counters.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gs_set_model_2d.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int]
     L.gs_set_image_size.argtypes = [vp, C.c_int32, C.c_int32]
+    L.gs_set_active_sh_degree.argtypes = [vp, C.c_int]
+    L.gs_get_active_sh_degree.argtypes = [vp]
     L.gs_color_grads_pack.argtypes = [vp, vp]
     L.gs_sh_grads_from_views.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int]
     L.gs_color_rows_pack.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
@@ -254,6 +256,19 @@ class Context:
 
     def set_model_2d_device(self, n: int, ptrs):
         self._chk(self.L.gs_set_model_2d(self.h, n, *(C.c_void_p(int(p)) for p in ptrs), GS_MEM_DEVICE))
+
+    def set_active_sh_degree(self, degree: int = -1):
+        """gs_set_active_sh_degree: evaluate the SH bands 0 .. degree only, on rows that keep the model's stride (-1: the model's own
+        degree).  The request is the ctx's: it survives set_model_*; a change of the effective degree drops the frame."""
+        self._chk(self.L.gs_set_active_sh_degree(self.h, int(degree)))
+
+    @property
+    def active_sh_degree(self) -> int:
+        """gs_get_active_sh_degree: the effective degree, min(requested, the model's)."""
+        rc = self.L.gs_get_active_sh_degree(self.h)
+        if rc < 0:
+            self._chk(rc)
+        return int(rc)
 
     def set_image_size(self, W: int, H: int):
         self._chk(self.L.gs_set_image_size(self.h, int(W), int(H)))

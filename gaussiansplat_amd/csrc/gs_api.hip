@@ -173,6 +173,24 @@ int gs_set_model_2d(gs_ctx *c, int64_t n, const float *means, const float *scale
     return adopt_model(c, n, 0, 1, src, {2, 2, 1, 1, 3}, mem);
 }
 
+// The active degree: the kernels that touch SH evaluate bands 0 .. active only; rows keep the model's stride.  A change of the EFFECTIVE value is a
+// change of the model as far as the frame is concerned (an optimiser step does the same); the value in force costs nothing.
+int gs_set_active_sh_degree(gs_ctx *c, int degree) {
+    if (!c) return GS_ERR_INVALID;
+    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_set_active_sh_degree: 3-D renderer only");
+    if (degree < -1 || degree > 3) return fail(c, GS_ERR_INVALID, "gs_set_active_sh_degree: degree must be -1 (the model's own) or 0..3");
+    const int before = c->active_sh_degree();
+    c->sh_active_request = degree;
+    if (c->active_sh_degree() != before) c->inputs_changed();
+    return GS_OK;
+}
+
+int gs_get_active_sh_degree(const gs_ctx *c) {
+    if (!c) return GS_ERR_INVALID;
+    if (c->kind != 0) return GS_ERR_UNSUPPORTED;
+    return c->active_sh_degree();
+}
+
 int gs_set_image_size(gs_ctx *c, int32_t W, int32_t H) {
     if (!c) return GS_ERR_INVALID;
     if (W <= 0 || H <= 0 || W > 32767 || H > 32767) return fail(c, GS_ERR_INVALID, "gs_set_image_size: image size must be in 1..32767");
@@ -233,7 +251,7 @@ int gs_preprocess(gs_ctx *c) {
         return GS_OK;
     }
     GsPreprocessArgs a{};
-    a.n = c->n; a.sh_degree = c->sh_degree; a.order = c->cfg.order;
+    a.n = c->n; a.sh_degree = c->active_sh_degree(); a.order = c->cfg.order;
     a.gx = c->gx; a.gy = c->gy;
     a.means = c->means; a.scales = c->scales; a.quats = c->quats; a.opac = c->opac; a.shs = c->shs;
     a.payload = c->payload.as<GsPayload>();
@@ -260,7 +278,7 @@ int gs_preprocess(gs_ctx *c) {
         a.dbg.bbs = c->dbg[6].as<float>();
     }
     StageTimer t(c, GS_STAGE_PREPROCESS);
-    HIPCHK(c, gs_launch_preprocess(a, c->cam, c->stream));
+    HIPCHK(c, gs_launch_preprocess(a, c->cam, c->sh_row_floats(), c->stream));
     c->reach(gs_ctx::Stage::PREPROCESSED);
     return GS_OK;
 }

@@ -335,7 +335,7 @@ static int run_backward(gs_ctx *c, const BackwardPlan &p) {
         HIPCHK(c, gs_launch_preprocess2d_bwd(b2, c->stream));
     } else if (p.chain) {
         GsPreprocessBwdArgs b{};
-        b.n = c->n; b.sh_degree = c->sh_degree;
+        b.n = c->n; b.sh_degree = c->active_sh_degree(); b.sh_stride = c->sh_row_floats();
         b.means = c->means; b.scales = c->scales; b.quats = c->quats; b.opac = c->opac; b.shs = c->shs;
         b.g2d = g2d; b.g2d_fixed = g2d_fixed;
         HIPCHK(c, c->dpc.ensure(sizeof(float) * 4 * n1));
@@ -410,7 +410,7 @@ int gs_sh_grads_from_views(gs_ctx *c, int32_t nviews, const float *cams, const f
     const size_t bytes = sizeof(float) * GS_VIEW_RECORD_FLOATS * (size_t)nviews;
     HIPCHK(c, c->view_cams.ensure(bytes));
     HIPCHK(c, hipMemcpyAsync(c->view_cams.p, cams, bytes, hipMemcpyHostToDevice, c->stream));   // pageable source: staged before return
-    HIPCHK(c, gs_launch_sh_from_views(c->n, c->sh_degree, c->means, nviews, c->view_cams.as<float>(), drgb, d_shs,
+    HIPCHK(c, gs_launch_sh_from_views(c->n, c->active_sh_degree(), c->sh_row_floats(), c->means, nviews, c->view_cams.as<float>(), drgb, d_shs,
                                       (flags & GS_BWD_OVERWRITE) ? 1 : 0, c->stream));
     return GS_OK;
 }

@@ -43,7 +43,7 @@ int gs_sh_grads_from_touched(gs_ctx *c, int32_t nviews, const float *cams, const
         HIPCHK(c, hipMemset(c->touched_zero.p, 0, c->touched_zero.cap));
     }
     HIPCHK(c, hipMemcpyAsync(c->view_cams.p, cams, bytes, hipMemcpyHostToDevice, c->stream));   // pageable source: staged before return
-    HIPCHK(c, gs_launch_sh_from_touched(c->n, c->sh_degree, c->means, nviews, c->view_cams.as<float>(), bits, rows, rows_cap,
+    HIPCHK(c, gs_launch_sh_from_touched(c->n, c->active_sh_degree(), c->sh_row_floats(), c->means, nviews, c->view_cams.as<float>(), bits, rows, rows_cap,
                                         c->touched_cnt.as<uint32_t>(), c->touched_off.as<int64_t>(), c->touched_zero.as<float>(), d_shs,
                                         (flags & GS_BWD_OVERWRITE) ? 1 : 0, c->stream));
     return GS_OK;

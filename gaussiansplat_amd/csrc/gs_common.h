@@ -55,7 +55,7 @@ struct GsDebugArrays {
 
 struct GsPreprocessArgs {
     int64_t n;
-    int sh_degree;
+    int sh_degree;        // the ACTIVE degree: the bands evaluated (gs_launch_preprocess takes the stored row stride beside it)
     int order;
     int gx, gy;
     const float *means, *scales, *quats, *opac, *shs;
@@ -70,7 +70,9 @@ struct GsPreprocessArgs {
 #define GS_KEY_RANGE_SLOTS 64
 #define GS_KEY_RANGE_STRIDE 64
 // launchers (each enqueues on `stream`, returns hipGetLastError())
-hipError_t gs_launch_preprocess(const GsPreprocessArgs &a, const GsCamera &cam, hipStream_t stream);
+// sh_stride: floats per stored row of a.shs, 3 (stored degree + 1)^2 >= 3 (a.sh_degree + 1)^2.  (A launch argument of its own, not a field: the
+// struct keeps its size, and the kernels of the default path their argument layout.)
+hipError_t gs_launch_preprocess(const GsPreprocessArgs &a, const GsCamera &cam, int sh_stride, hipStream_t stream);
 
 // 2-D image-fitting renderer (gs_preprocess2d.hip): SplatData2D, reference src/splat.jl:20-26
 struct GsPreprocess2DArgs {
@@ -388,7 +390,8 @@ hipError_t gs_launch_composite_bwd(const GsCompositeArgs &a, hipStream_t s);
 
 struct GsPreprocessBwdArgs {
     int64_t n;
-    int sh_degree;
+    int sh_degree;        // the ACTIVE degree: bands evaluated, width of the LDS tile ...
+    int sh_stride;        // ... and the floats per stored row of shs, d_shs and the SH moments: 3 (stored degree + 1)^2 >= 3 K
     const float *means, *scales, *quats, *opac, *shs;
     const float *g2d;
     const long long *g2d_fixed;   // non-null: read the 2-D gradients from the fixed-point buffer
@@ -409,7 +412,7 @@ hipError_t gs_launch_preprocess_bwd(const GsPreprocessBwdArgs &a, const GsCamera
 
 // colour-factored gradient exchange (gs_preprocess_bwd.hip)
 hipError_t gs_launch_pack_drgb(const float *g2d, const long long *g2d_fixed, float *out, int64_t n, hipStream_t s);
-hipError_t gs_launch_sh_from_views(int64_t n, int sh_degree, const float *means, int nviews, const float *cams, const float *drgb,
+hipError_t gs_launch_sh_from_views(int64_t n, int sh_degree, int sh_stride, const float *means, int nviews, const float *cams, const float *drgb,
                                    float *d_shs, int overwrite, hipStream_t s);
 // touched-rows exchange (gs_touched.hip): a view as a bitmap plus the colour-gradient rows of the gaussians it touched.  chunk_cnt /
 // chunk_off: scratch of gs_touched_chunks(n) words per view (the pack has one view).  Source of the pack: `dense` [n][3], or
@@ -421,7 +424,7 @@ inline int64_t gs_touched_chunks(int64_t n) { return (n + GS_TOUCHED_CHUNK - 1) 
 hipError_t gs_launch_chunk_scan(const uint32_t *chunk_cnt, int64_t *chunk_off, int64_t nchunks, int rows, int64_t *totals, hipStream_t s);
 hipError_t gs_launch_touched_pack(const float *dense, const float *g2d, const long long *g2d_fixed, int64_t n, int32_t *bits, float *rows,
                                   int64_t *count, uint32_t *chunk_cnt, int64_t *chunk_off, hipStream_t s);
-hipError_t gs_launch_sh_from_touched(int64_t n, int sh_degree, const float *means, int nviews, const float *cams, const int32_t *bits,
+hipError_t gs_launch_sh_from_touched(int64_t n, int sh_degree, int sh_stride, const float *means, int nviews, const float *cams, const int32_t *bits,
                                      const float *rows, int64_t rows_cap, uint32_t *chunk_cnt, int64_t *chunk_off, const float *zero3,
                                      float *d_shs, int overwrite, hipStream_t s);   // zero3: three +0 floats in device memory
 

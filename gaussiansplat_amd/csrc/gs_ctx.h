@@ -92,6 +92,11 @@ struct gs_ctx {
 
     int64_t n = 0;
     int sh_degree = 0;
+    // the active SH degree (gs_set_active_sh_degree): the REQUEST is the ctx's and outlives gs_set_model (densification re-adopts the model every
+    // window); what the kernels evaluate is the effective value -- bands below it, on rows that keep the stored stride 3 (sh_degree + 1)^2
+    int sh_active_request = -1;              // -1: the model's own degree
+    int active_sh_degree() const { return sh_active_request < 0 || sh_active_request > sh_degree ? sh_degree : sh_active_request; }
+    int sh_row_floats() const { return 3 * (sh_degree + 1) * (sh_degree + 1); }   // the stored row stride of shs, d_shs and their moments
     int kind = 0;                            // 0: 3-D renderer (SplatData3D), 1: 2-D image-fitting renderer (SplatData2D)
     size_t width[5] = {3, 3, 4, 1, 3};       // floats per gaussian of the five parameter / gradient arrays
     int order() const { return kind == 1 ? (int)GS_ORDER_INDEX : cfg.order; }    // the 2-D model has no depth

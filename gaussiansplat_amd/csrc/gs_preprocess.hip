@@ -35,8 +35,10 @@ __device__ __forceinline__ uint32_t gs_pack_i16(float lo, float hi) {
     return ((uint32_t)a & 0xFFFFu) | ((uint32_t)b << 16);
 }
 
-template <int DEG>
-__global__ __launch_bounds__(256) void gs_preprocess_kernel(GsPreprocessArgs a, GsCamera cam) {
+// DEG is the ACTIVE degree: the bands evaluated.  STRIDED: the model stores more bands than that (gs_set_active_sh_degree below the model's
+// degree) -- a row is sh_stride floats apart and its first 3 K are read, in the same order: the colour is what the model truncated to DEG gives.
+template <int DEG, bool STRIDED = false>
+__global__ __launch_bounds__(256) void gs_preprocess_kernel(GsPreprocessArgs a, GsCamera cam, int sh_stride) {
     constexpr int K = (DEG + 1) * (DEG + 1);
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= a.n) return;
@@ -181,7 +183,7 @@ __global__ __launch_bounds__(256) void gs_preprocess_kernel(GsPreprocessArgs a, 
             bs[15] = (kC3[6] * x) * (xx - 3.0f * yy);
         }
     }
-    const float *sh = a.shs + (int64_t)3 * K * g;
+    const float *sh = a.shs + (STRIDED ? (int64_t)sh_stride : (int64_t)3 * K) * g;
     float rgb[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -267,14 +269,25 @@ __global__ __launch_bounds__(256) void gs_preprocess_kernel(GsPreprocessArgs a, 
     }
 }
 
-hipError_t gs_launch_preprocess(const GsPreprocessArgs &a, const GsCamera &cam, hipStream_t stream) {
+hipError_t gs_launch_preprocess(const GsPreprocessArgs &a, const GsCamera &cam, int sh_stride, hipStream_t stream) {
     if (a.n <= 0) return hipSuccess;
     const dim3 block(256), grid((unsigned)((a.n + 255) / 256));
+    const int K3 = 3 * (a.sh_degree + 1) * (a.sh_degree + 1);
+    if (sh_stride > K3) {                                              // an active degree below the stored one: 0..2
+        switch (a.sh_degree) {
+            case 0: hipLaunchKernelGGL((gs_preprocess_kernel<0, true>), grid, block, 0, stream, a, cam, sh_stride); break;
+            case 1: hipLaunchKernelGGL((gs_preprocess_kernel<1, true>), grid, block, 0, stream, a, cam, sh_stride); break;
+            case 2: hipLaunchKernelGGL((gs_preprocess_kernel<2, true>), grid, block, 0, stream, a, cam, sh_stride); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
+    if (sh_stride != K3) return hipErrorInvalidValue;
     switch (a.sh_degree) {
-        case 0: hipLaunchKernelGGL(gs_preprocess_kernel<0>, grid, block, 0, stream, a, cam); break;
-        case 1: hipLaunchKernelGGL(gs_preprocess_kernel<1>, grid, block, 0, stream, a, cam); break;
-        case 2: hipLaunchKernelGGL(gs_preprocess_kernel<2>, grid, block, 0, stream, a, cam); break;
-        case 3: hipLaunchKernelGGL(gs_preprocess_kernel<3>, grid, block, 0, stream, a, cam); break;
+        case 0: hipLaunchKernelGGL(gs_preprocess_kernel<0>, grid, block, 0, stream, a, cam, sh_stride); break;
+        case 1: hipLaunchKernelGGL(gs_preprocess_kernel<1>, grid, block, 0, stream, a, cam, sh_stride); break;
+        case 2: hipLaunchKernelGGL(gs_preprocess_kernel<2>, grid, block, 0, stream, a, cam, sh_stride); break;
+        case 3: hipLaunchKernelGGL(gs_preprocess_kernel<3>, grid, block, 0, stream, a, cam, sh_stride); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -60,11 +60,16 @@ __device__ __forceinline__ float acc_or_step(float old, float v, float sgd_scale
 // same float steps p, m and v instead (gs_adam_update): the geometry rows in the thread, the SH rows in the coalesced loop behind the
 // LDS tile.  Every row is visited (dense Adam moves untouched rows too: the moments decay); selective mode decides liveness per
 // gaussian on all 11 + 3K gradient floats, as gs_adam_step does.
-template <int DEG, bool OVERWRITE, bool FUSED, int ADAM = 0>
+// DEG is the ACTIVE degree: basis, bs / cs, the ladders, the tile's width.  STRIDED (an active degree below the stored one, gs_set_active_sh_degree):
+// the rows of shs, d_shs and the SH moments are RS = a.sh_stride floats apart and their first 3 K are this kernel's -- the same floats the model
+// truncated to DEG gets.  The floats behind them: overwriting, + 0 (unless the fill workgroups wrote it, a.shs_zeroed); Adam, stepped with a
+// gradient of + 0 in every row that is stepped (what gs_adam_step does with the stored + 0); accumulating or SGD, neither read nor written.
+template <int DEG, bool OVERWRITE, bool FUSED, int ADAM = 0, bool STRIDED = false>
 __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, GsCamera cam, GsAdamFused ad) {
 #pragma clang fp contract(off)   // the fused and the two-kernel form must produce the same bits: no context-dependent fma formation
     constexpr int K = (DEG + 1) * (DEG + 1);
     constexpr int ROW = 3 * K + 1;
+    const int RS = STRIDED ? a.sh_stride : 3 * K;                       // floats between two rows in global memory
     extern __shared__ __attribute__((aligned(16))) float tile[];       // [256][ROW]
     // Untouched gaussians.  With the transmittance early-out most gaussians of a dense view are never composited (C3: 63 %, C5: 90 %,
     // tools/touched_rows.py): their colour gradient d rgb is exactly zero, hence d shs = basis * 0 and the colour -> direction term are
@@ -86,8 +91,10 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
         __syncthreads();
     }
     // 3K is a multiple of 4 only for K = 4, 16 ... : use 16-byte global accesses when it is
+    // (strided: the rows must start on 16 bytes too -- active 1 in stored 3 only; everything else one float per lane)
     constexpr bool VEC = (3 * K) % 4 == 0;
-    const bool vec_out = VEC && (reinterpret_cast<uintptr_t>(a.d_shs) & 15) == 0;   // e.g. a flat buffer slice at 44 n bytes
+    const bool vec_rows = VEC && (!STRIDED || RS % 4 == 0);
+    const bool vec_out = vec_rows && (reinterpret_cast<uintptr_t>(a.d_shs) & 15) == 0;   // e.g. a flat buffer slice at 44 n bytes
     const int64_t g = gb + threadIdx.x;
     if (g < a.n) {
         if (!SKIP) load_g2(a, g, g2);
@@ -135,14 +142,14 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
             // derivative polynomials of the basis.  (Until round 4 every row came in through the LDS tile, touched or not: 192 of the
             // kernel's 476 bytes per gaussian.  A 3 x 3 Jacobian d rgb / d dir written by the preprocess instead was measured too: the
             // backward 10 us faster than this, the preprocess 30 us slower -- 131 VGPRs, three waves per SIMD; profiles/r04s_ab_lazy_sh.log.)
-            const float4 *row = reinterpret_cast<const float4 *>(a.shs + (int64_t)3 * K * g);
+            const float4 *row = reinterpret_cast<const float4 *>(a.shs + (int64_t)RS * g);
             float shv[3 * K];
-            if constexpr ((3 * K) % 4 == 0) {
+            if (vec_rows) {                                             // (a constant unless STRIDED: then the first 3 K floats of a row that starts on 16 bytes)
 #pragma unroll
                 for (int q = 0; q < 3 * K / 4; ++q) { const float4 t4 = row[q]; shv[4 * q] = t4.x; shv[4 * q + 1] = t4.y; shv[4 * q + 2] = t4.z; shv[4 * q + 3] = t4.w; }
             } else {
 #pragma unroll
-                for (int q = 0; q < 3 * K; ++q) shv[q] = a.shs[(int64_t)3 * K * g + q];
+                for (int q = 0; q < 3 * K; ++q) shv[q] = a.shs[(int64_t)RS * g + q];
             }
             float cs[K];
 #pragma unroll
@@ -180,9 +187,9 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
     __syncthreads();
     if constexpr (ADAM != 0) {
         // p, m, v of the SH rows: group 4 for the first three floats of a row, 5 for the rest
-        const int64_t o = gb * 3 * K;
+        const int64_t o = gb * RS;
         float *ps = const_cast<float *>(a.shs) + o, *ms = ad.m[4] + o, *vs = ad.v[4] + o;
-        const bool vec = VEC && ((reinterpret_cast<uintptr_t>(a.shs) | reinterpret_cast<uintptr_t>(ad.m[4]) | reinterpret_cast<uintptr_t>(ad.v[4])) & 15) == 0;
+        const bool vec = vec_rows && ((reinterpret_cast<uintptr_t>(a.shs) | reinterpret_cast<uintptr_t>(ad.m[4]) | reinterpret_cast<uintptr_t>(ad.v[4])) & 15) == 0;
         const float ss4 = ad.h.step_size[4], ss5 = ad.h.step_size[5];
         // selective: the live rows compacted (a ballot per wave), so that every lane of the loops below steps a live float -- the
         // correctly rounded update is ~55 VALU operations per float, which the masked lanes of a mixed wave would pay as well
@@ -204,7 +211,7 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
             for (int c4 = threadIdx.x; c4 < nrow * (3 * K / 4); c4 += blockDim.x) {
                 const int ri = (c4 * 4) / (3 * K), j = (c4 * 4) % (3 * K);
                 const int row = ADAM == 2 ? srow_order[ri] : ri;
-                const int i4 = (row * 3 * K + j) / 4;
+                const int i4 = (row * RS + j) / 4;
                 const float *t = tile + row * ROW + j;
                 float4 p = reinterpret_cast<float4 *>(ps)[i4], m = reinterpret_cast<float4 *>(ms)[i4], v = reinterpret_cast<float4 *>(vs)[i4];
                 gs_adam_update(p.x, m.x, v.x, t[0], ad.h, j < 3 ? ss4 : ss5);
@@ -217,20 +224,33 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
             for (int c = threadIdx.x; c < nrow * 3 * K; c += blockDim.x) {
                 const int ri = c / (3 * K), j = c % (3 * K);
                 const int row = ADAM == 2 ? srow_order[ri] : ri;
-                const int idx = row * 3 * K + j;
+                const int idx = row * RS + j;
                 float p = ps[idx], m = ms[idx], v = vs[idx];
                 gs_adam_update(p, m, v, tile[row * ROW + j], ad.h, j < 3 ? ss4 : ss5);
                 ps[idx] = p; ms[idx] = m; vs[idx] = v;
             }
         }
+        if constexpr (STRIDED) {
+            // the inactive floats of the rows stepped above: a gradient of + 0 -- the moments decay, p moves where old moments are non-zero
+            const int hi = RS - 3 * K;
+            for (int c = threadIdx.x; c < nrow * hi; c += blockDim.x) {
+                const int ri = c / hi, j = 3 * K + c % hi;
+                const int row = ADAM == 2 ? srow_order[ri] : ri;
+                const int idx = row * RS + j;
+                float p = ps[idx], m = ms[idx], v = vs[idx];
+                gs_adam_update(p, m, v, 0.0f, ad.h, ss5);
+                ps[idx] = p; ms[idx] = m; vs[idx] = v;
+            }
+        }
     } else if (a.d_shs) {
         if (vec_out) {
-            float4 *dst = reinterpret_cast<float4 *>(a.d_shs + gb * 3 * K);
-            for (int i4 = threadIdx.x; i4 < nb * (3 * K / 4); i4 += blockDim.x) {
-                const int row = (i4 * 4) / (3 * K);
+            float4 *dst = reinterpret_cast<float4 *>(a.d_shs + gb * RS);
+            for (int t4 = threadIdx.x; t4 < nb * (3 * K / 4); t4 += blockDim.x) {
+                const int row = (t4 * 4) / (3 * K);
+                const int i4 = STRIDED ? (row * RS + (t4 * 4) % (3 * K)) / 4 : t4;   // where the four floats sit in global memory
                 const bool lv = srow_live[row] != 0;
                 if ((!OVERWRITE || a.shs_zeroed) && !lv) continue;       // + 0 (or a step of 0): the row stays as it is; overwriting: it holds its zeros already
-                const float *t = tile + row * ROW + (i4 * 4) % (3 * K);
+                const float *t = tile + row * ROW + (t4 * 4) % (3 * K);
                 float4 v = make_float4(t[0], t[1], t[2], t[3]);
                 if (OVERWRITE && !lv) v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (!OVERWRITE) {
@@ -253,9 +273,17 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
                 const bool lv = srow_live[idx / (3 * K)] != 0;
                 if ((!OVERWRITE || a.shs_zeroed) && !lv) continue;
                 const float v = (OVERWRITE && !lv) ? 0.0f : tile[(idx / (3 * K)) * ROW + idx % (3 * K)];
-                if (OVERWRITE) a.d_shs[gb * 3 * K + idx] = v;
-                else if (a.sgd_scale != 0.0f) a.d_shs[gb * 3 * K + idx] = fmaf(a.sgd_scale, v, a.d_shs[gb * 3 * K + idx]);
-                else a.d_shs[gb * 3 * K + idx] += v;
+                const int64_t gi = STRIDED ? gb * RS + (int64_t)(idx / (3 * K)) * RS + idx % (3 * K) : gb * 3 * K + idx;
+                if (OVERWRITE) a.d_shs[gi] = v;
+                else if (a.sgd_scale != 0.0f) a.d_shs[gi] = fmaf(a.sgd_scale, v, a.d_shs[gi]);
+                else a.d_shs[gi] += v;
+            }
+        }
+        if constexpr (STRIDED && OVERWRITE) {
+            // the inactive floats of EVERY row, touched or not, end as + 0 (a.shs_zeroed: the fill workgroups wrote all of d_shs already)
+            if (!a.shs_zeroed) {
+                const int hi = RS - 3 * K;
+                for (int c = threadIdx.x; c < nb * hi; c += blockDim.x) a.d_shs[gb * RS + (int64_t)(c / hi) * RS + 3 * K + c % hi] = 0.0f;
             }
         }
     }
@@ -290,10 +318,10 @@ __global__ __launch_bounds__(256) void gs_pack_drgb_kernel(const float *__restri
 // cams: nviews records of 38 floats {T[16], P[16], eye[3], lookAt[3]}; drgb: [nviews][3n]; the direction and the
 // basis are computed exactly as in gs_sh_bwd_kernel.  The body (gs_sh_views_body.inc) is shared with the kernel that reads the
 // views' colour gradients from bitmaps and compacted rows (gs_touched.hip).
-template <int DEG, bool OVERWRITE>
+template <int DEG, bool OVERWRITE, bool STRIDED = false>
 __global__ __launch_bounds__(256) void gs_sh_from_views_kernel(int64_t n, const float *__restrict__ means, int nviews,
                                                                 const float *__restrict__ cams, const float *__restrict__ drgb,
-                                                                float *__restrict__ d_shs) {
+                                                                float *__restrict__ d_shs, int sh_stride) {
 #define GS_SH_VIEWS_BEGIN
 #define GS_SH_VIEWS_DRGB const float *gr = drgb + (size_t)v * 3 * (size_t)n + 3 * g; const float g0 = gr[0], g1 = gr[1], g2 = gr[2];
 #include "gs_sh_views_body.inc"
@@ -307,14 +335,24 @@ hipError_t gs_launch_pack_drgb(const float *g2d, const long long *g2d_fixed, flo
     return hipGetLastError();
 }
 
-hipError_t gs_launch_sh_from_views(int64_t n, int sh_degree, const float *means, int nviews, const float *cams, const float *drgb,
+// sh_degree: the ACTIVE degree; sh_stride: floats per stored row of d_shs (3 K, or more: the strided instantiations, degrees 0..2)
+hipError_t gs_launch_sh_from_views(int64_t n, int sh_degree, int sh_stride, const float *means, int nviews, const float *cams, const float *drgb,
                                    float *d_shs, int overwrite, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     const dim3 block(256), grid((unsigned)((n + 255) / 256));
     const int K = (sh_degree + 1) * (sh_degree + 1);
     const size_t lds = sizeof(float) * 256 * (3 * K + 1);
-#define GS_SV(D) do { if (overwrite) hipLaunchKernelGGL((gs_sh_from_views_kernel<D, true>), grid, block, lds, s, n, means, nviews, cams, drgb, d_shs); \
-                      else hipLaunchKernelGGL((gs_sh_from_views_kernel<D, false>), grid, block, lds, s, n, means, nviews, cams, drgb, d_shs); } while (0)
+    if (sh_degree < 0 || sh_degree > 3 || sh_stride < 3 * K) return hipErrorInvalidValue;
+#define GS_SV(D, ...) do { if (overwrite) hipLaunchKernelGGL((gs_sh_from_views_kernel<D, true, ##__VA_ARGS__>), grid, block, lds, s, n, means, nviews, cams, drgb, d_shs, sh_stride); \
+                      else hipLaunchKernelGGL((gs_sh_from_views_kernel<D, false, ##__VA_ARGS__>), grid, block, lds, s, n, means, nviews, cams, drgb, d_shs, sh_stride); } while (0)
+    if (sh_stride > 3 * K)
+    switch (sh_degree) {
+        case 0: GS_SV(0, true); break;
+        case 1: GS_SV(1, true); break;
+        case 2: GS_SV(2, true); break;
+        default: return hipErrorInvalidValue;
+    }
+    else
     switch (sh_degree) {
         case 0: GS_SV(0); break;
         case 1: GS_SV(1); break;
@@ -338,33 +376,50 @@ hipError_t gs_launch_preprocess_bwd(const GsPreprocessBwdArgs &a, const GsCamera
     const GsAdamFused *adam = mode.adam;
     const int T = sh_bwd_threads();
     dim3 block(T), grid((unsigned)((a.n + T - 1) / T));
-    const int K = (a.sh_degree + 1) * (a.sh_degree + 1);
+    const int K = (a.sh_degree + 1) * (a.sh_degree + 1);                 // of the ACTIVE degree: the tile holds the bands evaluated
     const size_t lds = sizeof(float) * T * (3 * K + 1);
+    if (a.sh_degree < 0 || a.sh_degree > 3 || a.sh_stride < 3 * K) return hipErrorInvalidValue;
+    const bool strided = a.sh_stride > 3 * K;                            // an active degree below the stored one (0..2): rows a.sh_stride floats apart
     const GsAdamFused ad = adam ? *adam : GsAdamFused{};
     if (adam_mode) {                                                   // fused backward + Adam: one launch, both phases
         if (!adam || !a.overwrite || (phases & 3) != 3 || (adam_mode != 1 && adam_mode != 2)) return hipErrorInvalidValue;
-#define GS_SHA(D) do { if (adam_mode == 2) hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, true, 2>), grid, block, lds, s, a, cam, ad); \
-                       else hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, true, 1>), grid, block, lds, s, a, cam, ad); } while (0)
+#define GS_SHA(D, S) do { if (adam_mode == 2) hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, true, 2, S>), grid, block, lds, s, a, cam, ad); \
+                          else hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, true, 1, S>), grid, block, lds, s, a, cam, ad); } while (0)
+        if (strided)
         switch (a.sh_degree) {
-            case 0: GS_SHA(0); break;
-            case 1: GS_SHA(1); break;
-            case 2: GS_SHA(2); break;
-            case 3: GS_SHA(3); break;
+            case 0: GS_SHA(0, true); break;
+            case 1: GS_SHA(1, true); break;
+            case 2: GS_SHA(2, true); break;
+            default: return hipErrorInvalidValue;
+        }
+        else
+        switch (a.sh_degree) {
+            case 0: GS_SHA(0, false); break;
+            case 1: GS_SHA(1, false); break;
+            case 2: GS_SHA(2, false); break;
+            case 3: GS_SHA(3, false); break;
             default: return hipErrorInvalidValue;
         }
 #undef GS_SHA
         return hipGetLastError();
     }
-#define GS_SH2(D, F) do { if (a.overwrite) hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, F>), grid, block, lds, s, a, cam, ad); \
-                         else hipLaunchKernelGGL((gs_sh_bwd_kernel<D, false, F>), grid, block, lds, s, a, cam, ad); } while (0)
-#define GS_SH(D) do { if (fused) GS_SH2(D, true); else GS_SH2(D, false); } while (0)
+#define GS_SH2(D, F, S) do { if (a.overwrite) hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, F, 0, S>), grid, block, lds, s, a, cam, ad); \
+                            else hipLaunchKernelGGL((gs_sh_bwd_kernel<D, false, F, 0, S>), grid, block, lds, s, a, cam, ad); } while (0)
+#define GS_SH(D, S) do { if (fused) GS_SH2(D, true, S); else GS_SH2(D, false, S); } while (0)
     const bool fused = (phases & 3) == 3;
-    if (phases & 1)
+    if ((phases & 1) && strided)
     switch (a.sh_degree) {
-        case 0: GS_SH(0); break;
-        case 1: GS_SH(1); break;
-        case 2: GS_SH(2); break;
-        case 3: GS_SH(3); break;
+        case 0: GS_SH(0, true); break;
+        case 1: GS_SH(1, true); break;
+        case 2: GS_SH(2, true); break;
+        default: return hipErrorInvalidValue;
+    }
+    else if (phases & 1)
+    switch (a.sh_degree) {
+        case 0: GS_SH(0, false); break;
+        case 1: GS_SH(1, false); break;
+        case 2: GS_SH(2, false); break;
+        case 3: GS_SH(3, false); break;
         default: return hipErrorInvalidValue;
     }
     block = dim3(256); grid = dim3((unsigned)((a.n + 255) / 256));

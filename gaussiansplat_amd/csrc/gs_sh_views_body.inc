@@ -3,7 +3,9 @@
 // [views][3n] slots) and by gs_sh_from_touched_kernel (gs_touched.hip: from bitmaps plus compacted rows).  ONE text, so that both
 // compute the direction, the basis and the sums alike; they differ in two macros only: GS_SH_VIEWS_BEGIN (first thing in the loop over the views:
 // whatever the source needs before the arithmetic; may be empty) and GS_SH_VIEWS_DRGB, which declares the three floats g0, g1, g2
-// of (view v, gaussian g) as plain loads.  Expects n, means, nviews, cams, d_shs and the template parameters DEG, OVERWRITE in scope.
+// of (view v, gaussian g) as plain loads.  Expects n, means, nviews, cams, d_shs, sh_stride and the template parameters DEG, OVERWRITE,
+// STRIDED in scope.  DEG is the ACTIVE degree; STRIDED: the rows of d_shs are sh_stride > 3 K floats apart (an active degree below the
+// stored one): their first 3 K floats are rebuilt, the rest become + 0 when overwriting and are left alone when accumulating.
     constexpr int K = (DEG + 1) * (DEG + 1);
     constexpr int ROW = 3 * K + 1;
     extern __shared__ __attribute__((aligned(16))) float tile[];       // [256][ROW] accumulators
@@ -46,7 +48,13 @@
         }
     }
     __syncthreads();
+    const int RS = STRIDED ? sh_stride : 3 * K;
     for (int idx = threadIdx.x; idx < nb * 3 * K; idx += blockDim.x) {     // coalesced rows
         const float v = tile[(idx / (3 * K)) * ROW + idx % (3 * K)];
-        if (OVERWRITE) d_shs[gb * 3 * K + idx] = v; else d_shs[gb * 3 * K + idx] += v;
+        const int64_t gi = STRIDED ? gb * RS + (int64_t)(idx / (3 * K)) * RS + idx % (3 * K) : gb * 3 * K + idx;
+        if (OVERWRITE) d_shs[gi] = v; else d_shs[gi] += v;
+    }
+    if constexpr (STRIDED && OVERWRITE) {
+        const int hi = RS - 3 * K;
+        for (int c = threadIdx.x; c < nb * hi; c += blockDim.x) d_shs[gb * RS + (int64_t)(c / hi) * RS + 3 * K + c % hi] = 0.0f;
     }

@@ -168,10 +168,10 @@ struct GsTouchedColorSrc {
     }
 };
 
-template <int DEG, bool OVERWRITE>
+template <int DEG, bool OVERWRITE, bool STRIDED = false>
 __global__ __launch_bounds__(GS_TOUCHED_CHUNK) void gs_sh_from_touched_kernel(int64_t n, const float *__restrict__ means, int nviews,
                                                                                const float *__restrict__ cams, GsTouchedColorSrc src,
-                                                                               float *__restrict__ d_shs) {
+                                                                               float *__restrict__ d_shs, int sh_stride) {
 #define GS_SH_VIEWS_BEGIN const float *gr = src.row(v);      // the integer work first: the arithmetic behind it is then laid out as in the dense kernel
 #define GS_SH_VIEWS_DRGB const float g0 = gr[0], g1 = gr[1], g2 = gr[2];
 #include "gs_sh_views_body.inc"
@@ -197,21 +197,28 @@ hipError_t gs_launch_touched_pack(const float *dense, const float *g2d, const lo
     return hipGetLastError();
 }
 
-hipError_t gs_launch_sh_from_touched(int64_t n, int sh_degree, const float *means, int nviews, const float *cams, const int32_t *bits,
+hipError_t gs_launch_sh_from_touched(int64_t n, int sh_degree, int sh_stride, const float *means, int nviews, const float *cams, const int32_t *bits,
                                      const float *rows, int64_t rows_cap, uint32_t *chunk_cnt, int64_t *chunk_off, const float *zero3,
                                      float *d_shs, int overwrite, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     const int64_t nchunks = gs_touched_chunks(n), words = (n + 31) / 32;
-    if (nchunks > 0x7fffffffLL || nviews <= 0 || nviews > 65535 || sh_degree < 0 || sh_degree > 3) return hipErrorInvalidValue;
+    const int K = (sh_degree + 1) * (sh_degree + 1);                      // of the ACTIVE degree; sh_stride: floats per stored row of d_shs
+    if (nchunks > 0x7fffffffLL || nviews <= 0 || nviews > 65535 || sh_degree < 0 || sh_degree > 3 || sh_stride < 3 * K) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gs_touched_count_kernel, dim3((unsigned)((words + 255) / 256), (unsigned)nviews), dim3(256), 0, s, bits, words, n, chunk_cnt, nchunks);
     const hipError_t e = gs_launch_chunk_scan(chunk_cnt, chunk_off, nchunks, nviews, nullptr, s);   // (also reports the count launch)
     if (e != hipSuccess) return e;
     const GsTouchedColorSrc src{bits, rows, chunk_off, zero3, words, nchunks, rows_cap};
     const dim3 grid((unsigned)nchunks), block(GS_TOUCHED_CHUNK);
-    const int K = (sh_degree + 1) * (sh_degree + 1);
     const size_t lds = sizeof(float) * GS_TOUCHED_CHUNK * (3 * K + 1);
-#define GS_ST(D) do { if (overwrite) hipLaunchKernelGGL((gs_sh_from_touched_kernel<D, true>), grid, block, lds, s, n, means, nviews, cams, src, d_shs); \
-                      else hipLaunchKernelGGL((gs_sh_from_touched_kernel<D, false>), grid, block, lds, s, n, means, nviews, cams, src, d_shs); } while (0)
+#define GS_ST(D, ...) do { if (overwrite) hipLaunchKernelGGL((gs_sh_from_touched_kernel<D, true, ##__VA_ARGS__>), grid, block, lds, s, n, means, nviews, cams, src, d_shs, sh_stride); \
+                      else hipLaunchKernelGGL((gs_sh_from_touched_kernel<D, false, ##__VA_ARGS__>), grid, block, lds, s, n, means, nviews, cams, src, d_shs, sh_stride); } while (0)
+    if (sh_stride > 3 * K)                                                // an active degree below the stored one: 0..2
+    switch (sh_degree) {
+        case 0: GS_ST(0, true); break;
+        case 1: GS_ST(1, true); break;
+        default: GS_ST(2, true); break;
+    }
+    else
     switch (sh_degree) {
         case 0: GS_ST(0); break;
         case 1: GS_ST(1); break;

@@ -308,6 +308,10 @@ class HipViewRenderer:
         start = torch.cuda.Event(); start.record(cur)
         overwrite = r._grads_lazy_zero
         prev_chain = None
+        active = r.active_sh_degree                                        # the twins are ctxs of their own: they follow the rank's renderer
+        for t, _ in self._twins():
+            if t is not r and getattr(t, "_active_sh_sent", None) != active:
+                t.active_sh_degree = t._active_sh_sent = active
         for i, (cam, dC) in enumerate(zip(cameras, dCs)):
             t, st = self._twins()[i % self.pipeline_depth]
             with torch.cuda.stream(st):

@@ -143,6 +143,17 @@ class GaussianRenderer3D:               # renderer.jl:205-219
             self._grads_lazy_zero = False
         return self._splatGrads
 
+    @property
+    def active_sh_degree(self) -> int:
+        """The SH degree the kernels evaluate: the model's own unless a lower one was set (the degree schedule of a training run,
+        train.SHDegreeSchedule; a viewer drawing a degree-3 model at degree 0).  Setting it (-1: the model's own again) changes
+        neither splatData.shs nor the gradients' layout: the inactive bands get zero gradients."""
+        return self.ctx.active_sh_degree
+
+    @active_sh_degree.setter
+    def active_sh_degree(self, degree: int):
+        self.ctx.set_active_sh_degree(int(degree))
+
     def _begin(self):
         """Bind the ctx to torch's current stream (handle 0 = the legacy default stream = GS_STREAM_LEGACY)."""
         h = _current_stream_handle(self.imageData.device) or 1

@@ -10,6 +10,7 @@ with the loss, its image gradient and the SGD update running on the GPU (csrc/gs
 step has no host round trip.  `optimizer=optim.Adam(...)` replaces the SGD update by Adam with per-group rates
 (csrc/gs_adam.hip; fused with the backward when the optimiser was made with fused=True).  `density=density.DensityController(...)`
 adds the other half of the 3DGS recipe: statistics after every backward, clone / split / prune and the opacity reset on schedule.
+`sh_schedule=SHDegreeSchedule(...)` is the recipe's SH degree schedule: band 0 first, one more band every `every` iterations.
 """
 from __future__ import annotations
 
@@ -68,8 +69,41 @@ def getLossFunction(imSize, windowSize: int, nChannels: int, renderer=None, λ: 
     return LossFunction(renderer, imSize, windowSize, nChannels, λ)
 
 
+class SHDegreeSchedule:
+    """The SH degree schedule of 3DGS training: iteration `it` (counted from 0) runs at the active degree
+    min(max_degree, start + it // every) -- band 0 only at first, one more band every `every` iterations.  The model keeps all its
+    bands; the kernels evaluate the active ones and the others get zero gradients (renderer.active_sh_degree).
+    max_degree None: the model's own degree.  The object counts the iterations it was applied to (`iteration`), as
+    density.DensityController does, so one schedule serves one training run."""
+
+    def __init__(self, every: int = 1000, start: int = 0, max_degree: "int | None" = None):
+        if int(every) != every or every < 1:
+            raise ValueError(f"SHDegreeSchedule: every must be a positive integer, not {every!r}")
+        if int(start) != start or not 0 <= start <= 3:
+            raise ValueError(f"SHDegreeSchedule: start must be in 0..3, not {start!r}")
+        if max_degree is not None and (int(max_degree) != max_degree or not 0 <= max_degree <= 3):
+            raise ValueError(f"SHDegreeSchedule: max_degree must be None or in 0..3, not {max_degree!r}")
+        self.every, self.start = int(every), int(start)
+        self.max_degree = None if max_degree is None else int(max_degree)
+        self.iteration = 0                                      # iterations the schedule was applied to
+
+    def degree_at(self, iteration: int) -> int:
+        """The active degree of iteration `iteration` (from 0); without max_degree capped at 3, and by the model when applied."""
+        if iteration < 0:
+            raise ValueError("SHDegreeSchedule.degree_at: iteration must be >= 0")
+        return min(3 if self.max_degree is None else self.max_degree, self.start + int(iteration) // self.every)
+
+    def apply(self, renderer) -> int:
+        """Set the renderer's active degree for the iteration about to run and count it.  Returns the effective degree."""
+        if not isinstance(renderer, R.GaussianRenderer3D):
+            raise ValueError("SHDegreeSchedule: the SH degree schedule needs a GaussianRenderer3D (the 2-D renderer has colours, not SH)")
+        renderer.active_sh_degree = self.degree_at(self.iteration)
+        self.iteration += 1
+        return renderer.active_sh_degree
+
+
 def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, want_loss: bool = True, fused_sgd: bool = False,
-              optimizer=None, density=None):
+              optimizer=None, density=None, sh_schedule=None):
     """One iteration of train.jl:33-56 as intended (see module docstring).
     fused_sgd (3-D renderer): backward and the parameter update in one pass (gs_backward_sgd) -- the same parameters bit for
     bit (deterministic mode), but renderer.splatGrads is not filled.
@@ -77,12 +111,16 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
     was made with fused=True (renderer.splatGrads then is not filled), else backward, optimizer.step() and resetGrads.
     density (density.DensityController): its statistics are accumulated between the backward and the update (the update drops the
     frame, so this is the only place), and after the update it clones / splits / prunes and resets opacities when its schedule says so.
-    The fused forms leave no frame to accumulate from: a fused optimiser or fused_sgd with `density` is a ValueError."""
+    The fused forms leave no frame to accumulate from: a fused optimiser or fused_sgd with `density` is a ValueError.
+    sh_schedule (SHDegreeSchedule, 3-D renderer): sets the active SH degree of this iteration before preprocess; every optimiser form,
+    the fused ones included, and density control run under it unchanged (the request survives a restructured model)."""
     if optimizer is not None and fused_sgd:
         raise ValueError("trainStep: fused_sgd and optimizer exclude each other (make the optimiser with fused=True instead)")
     if density is not None and (fused_sgd or (optimizer is not None and optimizer.fused)):
         raise ValueError("trainStep: density control needs the unfused backward (no fused_sgd, no Adam(fused=True)): "
                          "the fused forms leave no frame to accumulate statistics from")
+    if sh_schedule is not None:
+        sh_schedule.apply(renderer)
     tps = R.preprocess(renderer, camera)
     R.compactIdxs(renderer)
     R.forward(renderer, tps)
@@ -118,12 +156,13 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
 
 
 def train(renderer, gtimg, lr: float, lossFunc: LossFunction, iterations: int = 100, camera=None, log_every: int = 0, optimizer=None,
-          density=None):
+          density=None, sh_schedule=None):
     """train.jl:16-59 without the GUI; the reference loops `while score < 0.99` on a score it never updates.
-    optimizer: an optim.Adam that replaces the SGD update (lr is then ignored); density: a density.DensityController (trainStep)."""
+    optimizer: an optim.Adam that replaces the SGD update (lr is then ignored); density: a density.DensityController,
+    sh_schedule: an SHDegreeSchedule (trainStep)."""
     losses = []
     for it in range(iterations):
-        l = trainStep(renderer, gtimg, lr, lossFunc, camera, want_loss=True, optimizer=optimizer, density=density)
+        l = trainStep(renderer, gtimg, lr, lossFunc, camera, want_loss=True, optimizer=optimizer, density=density, sh_schedule=sh_schedule)
         losses.append(l)
         if log_every and it % log_every == 0:
             print(f"loss : {l}")                             # loss.jl:69

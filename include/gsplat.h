@@ -217,6 +217,23 @@ int gs_set_model(gs_ctx *ctx, int64_t n, int sh_degree,
  * Needs gs_set_image_size (or gs_set_camera, of which only W and H are used). */
 int gs_set_model_2d(gs_ctx *ctx, int64_t n, const float *means, const float *scales, const float *rotations,
                     const float *opacities, const float *colors, int mem);
+
+/* The ACTIVE SH degree (3-D renderer; after gs_set_model_2d both calls return GS_ERR_UNSUPPORTED): render and train a model below the
+ * degree it stores -- the SH degree schedule of a training run, or a viewer drawing a degree-3 model at degree 0.
+ * degree: -1 (the default: the model's own degree) or 0..3, anything else GS_ERR_INVALID.  The effective degree is
+ * requested < 0 ? model degree : min(requested, model degree); gs_get_active_sh_degree returns it (negative: an error).  The request is
+ * the ctx's: it survives gs_set_model, also onto a model of another size or degree.  With Ka = (active+1)^2, Ks = (stored+1)^2:
+ *   forward   the colour is the sum over the bands k < Ka in the usual order; the rows of `shs` stay 3Ks floats apart.  Payload, lists, image
+ *             and gradients are bit for bit those of the model truncated to its first 3Ka floats per row.
+ *   backward  floats j < 3Ka of a d_shs row: the truncated model's; the colour -> direction term uses k < Ka.  Floats j >= 3Ka: +0.0 under
+ *             GS_BWD_OVERWRITE, neither read nor written when accumulating and in gs_backward_sgd.  gs_backward_adam keeps its contract:
+ *             it steps the inactive floats of every row it steps with a gradient of +0 (the moments decay), as gs_adam_step does with the
+ *             stored zeros.  gs_sh_grads_from_views / _from_touched: bands < Ka rebuilt, the rest +0 (overwrite) or untouched (accumulate).
+ * A call that changes the effective degree drops the frame to before gs_preprocess (as an optimiser step does); one that does not
+ * returns at once and keeps the frame. */
+int gs_set_active_sh_degree(gs_ctx *ctx, int degree);
+int gs_get_active_sh_degree(const gs_ctx *ctx);
+
 int gs_set_image_size(gs_ctx *ctx, int32_t W, int32_t H);
 
 /* Camera + image size (forward.jl:41,53-62).  T, P: 16 floats each, column-major. */

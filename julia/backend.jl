@@ -309,6 +309,17 @@ end
 hip_opacityReset!(r::HipRenderer, maxLogit::Real, mOpac::Ptr{Float32} = Ptr{Float32}(C_NULL), vOpac::Ptr{Float32} = Ptr{Float32}(C_NULL)) =
     check(r, ccall((:gs_opacity_reset, libgs), Cint, (Ptr{Cvoid}, Cfloat, Ptr{Float32}, Ptr{Float32}), r.ctx, maxLogit, mOpac, vOpac))
 
+# the active SH degree (3-D renderer): evaluate bands 0 .. degree on rows that keep the model's stride; -1 = the model's own degree.
+# The request is the ctx's (it survives a later gs_set_model); a change of the effective degree drops the frame.
+hip_setActiveShDegree!(r::HipRenderer, degree::Integer = -1) =
+    check(r, ccall((:gs_set_active_sh_degree, libgs), Cint, (Ptr{Cvoid}, Cint), r.ctx, degree))
+# the effective degree: min(requested, the model's)
+function hip_activeShDegree(r::HipRenderer)
+    rc = ccall((:gs_get_active_sh_degree, libgs), Cint, (Ptr{Cvoid},), r.ctx)
+    rc < 0 && check(r, rc)
+    return Int(rc)
+end
+
 # ---- plumbing and introspection -----------------------------------------------------------------------------------
 
 # enqueue on an existing hipStream_t (C_NULL: the ctx's own stream)
