@@ -30,7 +30,8 @@ SOURCES = {
     "gs_preprocess.hip": ["-ffp-contract=off"],
     "gs_preprocess2d.hip": ["-ffp-contract=off"],
     "gs_preprocess_bwd.hip": [],
-    # same flags as gs_preprocess_bwd.hip: the two kernels that rebuild SH gradients from views share one body (gs_sh_views_body.inc) and must round alike
+    # same flags as gs_preprocess_bwd.hip: the two kernels that rebuild SH gradients from views share one body (gs_sh_views_body.inc, with the
+    # basis text gs_sh_basis.inc inside it) and must round alike -- the text is contracted as the including translation unit is built
     "gs_touched.hip": [],
     "gs_sort.hip": [],
     "gs_bin2.hip": [],

@@ -13,15 +13,9 @@
 // 60 B written per gaussian; no LDS, no MFMA.
 #include "gs_common.h"
 #include "gs_detmath.h"
+#include "gs_sh.h"
 
 #pragma clang fp contract(off)
-
-#define SH_C0 0.28209479177387814f
-#define SH_C1 0.48860251190291990f
-__constant__ float kC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                             -1.0925484305920792f, 0.5462742152960396f};
-__constant__ float kC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
-                             -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
 
 __device__ __forceinline__ int gs_tile_div(float v) {
     // Julia div(v, 16f0) + saturation (see oracle gso_tile_rect): v is integer valued.
@@ -163,26 +157,8 @@ __global__ __launch_bounds__(256) void gs_preprocess_kernel(GsPreprocessArgs a, 
     const float nrm = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
     const float ninv = 1.0f / nrm;
     const float x = ninv * d0, y = ninv * d1, z = ninv * d2;
-    float bs[K];
-    bs[0] = SH_C0;
-    if constexpr (DEG >= 1) { bs[1] = -y * SH_C1; bs[2] = z * SH_C1; bs[3] = -x * SH_C1; }
-    if constexpr (DEG >= 2) {
-        const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-        bs[4] = kC2[0] * xy;
-        bs[5] = kC2[1] * yz;
-        bs[6] = kC2[2] * ((2.0f * zz - xx) - yy);
-        bs[7] = kC2[3] * xz;
-        bs[8] = kC2[4] * (xx - yy);
-        if constexpr (DEG >= 3) {
-            bs[9]  = (kC3[0] * y) * (3.0f * xx - yy);
-            bs[10] = (kC3[1] * xy) * z;
-            bs[11] = (kC3[2] * y) * ((4.0f * zz - xx) - yy);
-            bs[12] = (kC3[3] * z) * ((2.0f * zz - 3.0f * xx) - 3.0f * yy);
-            bs[13] = (kC3[4] * x) * ((4.0f * zz - xx) - yy);
-            bs[14] = (kC3[5] * z) * (xx - yy);
-            bs[15] = (kC3[6] * x) * (xx - 3.0f * yy);
-        }
-    }
+    const float X = x, Y = y, Z = z;
+#include "gs_sh_basis.inc"
     const float *sh = a.shs + (STRIDED ? (int64_t)sh_stride : (int64_t)3 * K) * g;
     float rgb[3];
 #pragma unroll
@@ -272,23 +248,8 @@ __global__ __launch_bounds__(256) void gs_preprocess_kernel(GsPreprocessArgs a, 
 hipError_t gs_launch_preprocess(const GsPreprocessArgs &a, const GsCamera &cam, int sh_stride, hipStream_t stream) {
     if (a.n <= 0) return hipSuccess;
     const dim3 block(256), grid((unsigned)((a.n + 255) / 256));
-    const int K3 = 3 * (a.sh_degree + 1) * (a.sh_degree + 1);
-    if (sh_stride > K3) {                                              // an active degree below the stored one: 0..2
-        switch (a.sh_degree) {
-            case 0: hipLaunchKernelGGL((gs_preprocess_kernel<0, true>), grid, block, 0, stream, a, cam, sh_stride); break;
-            case 1: hipLaunchKernelGGL((gs_preprocess_kernel<1, true>), grid, block, 0, stream, a, cam, sh_stride); break;
-            case 2: hipLaunchKernelGGL((gs_preprocess_kernel<2, true>), grid, block, 0, stream, a, cam, sh_stride); break;
-            default: return hipErrorInvalidValue;
-        }
+    return gs_sh_dispatch(a.sh_degree, sh_stride, [&](auto D, auto S) {
+        hipLaunchKernelGGL((gs_preprocess_kernel<decltype(D)::value, decltype(S)::value>), grid, block, 0, stream, a, cam, sh_stride);
         return hipGetLastError();
-    }
-    if (sh_stride != K3) return hipErrorInvalidValue;
-    switch (a.sh_degree) {
-        case 0: hipLaunchKernelGGL(gs_preprocess_kernel<0>, grid, block, 0, stream, a, cam, sh_stride); break;
-        case 1: hipLaunchKernelGGL(gs_preprocess_kernel<1>, grid, block, 0, stream, a, cam, sh_stride); break;
-        case 2: hipLaunchKernelGGL(gs_preprocess_kernel<2>, grid, block, 0, stream, a, cam, sh_stride); break;
-        case 3: hipLaunchKernelGGL(gs_preprocess_kernel<3>, grid, block, 0, stream, a, cam, sh_stride); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    });
 }

@@ -24,7 +24,7 @@
 // `overwrite` stores instead of accumulating: used for the first backward after resetGrads, so
 // the reset needs no 4(11+3K)-byte/gaussian zero fill and this pass no read of the old gradients.
 #include "gs_common.h"
-#include "gs_sh_views.h"      // SH_C0 / SH_C1 / bC2 / bC3
+#include "gs_sh.h"            // SH_C0 / SH_C1 / bC2 / bC3, gs_sh_dispatch, the strided rows
 #include <stdlib.h>
 
 #ifndef GS_NT_STORES
@@ -116,18 +116,7 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
         const float v2 = p[2] - (cam.lookAt[2] - cam.eye[2]);
         const float inrm = live ? rsqrtf(v0 * v0 + v1 * v1 + v2 * v2) : 0.0f;
         const float X = live ? v0 * inrm : 0.0f, Y = live ? v1 * inrm : 0.0f, Z = live ? v2 * inrm : 0.0f;
-        float bs[K];
-        bs[0] = SH_C0;
-        if constexpr (DEG >= 1) { bs[1] = -Y * SH_C1; bs[2] = Z * SH_C1; bs[3] = -X * SH_C1; }
-        if constexpr (DEG >= 2) {
-            const float xx = X * X, yy = Y * Y, zz = Z * Z, xy = X * Y, yz = Y * Z, xz = X * Z;
-            bs[4] = bC2[0] * xy; bs[5] = bC2[1] * yz; bs[6] = bC2[2] * (2 * zz - xx - yy); bs[7] = bC2[3] * xz; bs[8] = bC2[4] * (xx - yy);
-            if constexpr (DEG >= 3) {
-                bs[9] = bC3[0] * Y * (3 * xx - yy); bs[10] = bC3[1] * xy * Z; bs[11] = bC3[2] * Y * (4 * zz - xx - yy);
-                bs[12] = bC3[3] * Z * (2 * zz - 3 * xx - 3 * yy); bs[13] = bC3[4] * X * (4 * zz - xx - yy);
-                bs[14] = bC3[5] * Z * (xx - yy); bs[15] = bC3[6] * X * (xx - 3 * yy);
-            }
-        }
+#include "gs_sh_basis.inc"
         float *sh = tile + threadIdx.x * ROW;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -273,7 +262,7 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
                 const bool lv = srow_live[idx / (3 * K)] != 0;
                 if ((!OVERWRITE || a.shs_zeroed) && !lv) continue;
                 const float v = (OVERWRITE && !lv) ? 0.0f : tile[(idx / (3 * K)) * ROW + idx % (3 * K)];
-                const int64_t gi = STRIDED ? gb * RS + (int64_t)(idx / (3 * K)) * RS + idx % (3 * K) : gb * 3 * K + idx;
+                const int64_t gi = gs_sh_row_index<3 * K, STRIDED>(gb, RS, idx);
                 if (OVERWRITE) a.d_shs[gi] = v;
                 else if (a.sgd_scale != 0.0f) a.d_shs[gi] = fmaf(a.sgd_scale, v, a.d_shs[gi]);
                 else a.d_shs[gi] += v;
@@ -281,10 +270,7 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
         }
         if constexpr (STRIDED && OVERWRITE) {
             // the inactive floats of EVERY row, touched or not, end as + 0 (a.shs_zeroed: the fill workgroups wrote all of d_shs already)
-            if (!a.shs_zeroed) {
-                const int hi = RS - 3 * K;
-                for (int c = threadIdx.x; c < nb * hi; c += blockDim.x) a.d_shs[gb * RS + (int64_t)(c / hi) * RS + 3 * K + c % hi] = 0.0f;
-            }
+            if (!a.shs_zeroed) gs_sh_zero_inactive<3 * K>(a.d_shs, gb, nb, RS);
         }
     }
 }
@@ -316,8 +302,8 @@ __global__ __launch_bounds__(256) void gs_pack_drgb_kernel(const float *__restri
 }
 
 // cams: nviews records of 38 floats {T[16], P[16], eye[3], lookAt[3]}; drgb: [nviews][3n]; the direction and the
-// basis are computed exactly as in gs_sh_bwd_kernel.  The body (gs_sh_views_body.inc) is shared with the kernel that reads the
-// views' colour gradients from bitmaps and compacted rows (gs_touched.hip).
+// basis are those of gs_sh_bwd_kernel (one basis text, gs_sh_basis.inc; this kernel lets the compiler fuse it, that one does not).  The body
+// (gs_sh_views_body.inc) is shared with the kernel that reads the views' colour gradients from bitmaps and compacted rows (gs_touched.hip).
 template <int DEG, bool OVERWRITE, bool STRIDED = false>
 __global__ __launch_bounds__(256) void gs_sh_from_views_kernel(int64_t n, const float *__restrict__ means, int nviews,
                                                                 const float *__restrict__ cams, const float *__restrict__ drgb,
@@ -340,28 +326,14 @@ hipError_t gs_launch_sh_from_views(int64_t n, int sh_degree, int sh_stride, cons
                                    float *d_shs, int overwrite, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     const dim3 block(256), grid((unsigned)((n + 255) / 256));
-    const int K = (sh_degree + 1) * (sh_degree + 1);
-    const size_t lds = sizeof(float) * 256 * (3 * K + 1);
-    if (sh_degree < 0 || sh_degree > 3 || sh_stride < 3 * K) return hipErrorInvalidValue;
-#define GS_SV(D, ...) do { if (overwrite) hipLaunchKernelGGL((gs_sh_from_views_kernel<D, true, ##__VA_ARGS__>), grid, block, lds, s, n, means, nviews, cams, drgb, d_shs, sh_stride); \
-                      else hipLaunchKernelGGL((gs_sh_from_views_kernel<D, false, ##__VA_ARGS__>), grid, block, lds, s, n, means, nviews, cams, drgb, d_shs, sh_stride); } while (0)
-    if (sh_stride > 3 * K)
-    switch (sh_degree) {
-        case 0: GS_SV(0, true); break;
-        case 1: GS_SV(1, true); break;
-        case 2: GS_SV(2, true); break;
-        default: return hipErrorInvalidValue;
-    }
-    else
-    switch (sh_degree) {
-        case 0: GS_SV(0); break;
-        case 1: GS_SV(1); break;
-        case 2: GS_SV(2); break;
-        case 3: GS_SV(3); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GS_SV
-    return hipGetLastError();
+    return gs_sh_dispatch(sh_degree, sh_stride, [&](auto D, auto S) {
+        constexpr int DEG = decltype(D)::value, K = (DEG + 1) * (DEG + 1);
+        constexpr bool STRIDED = decltype(S)::value;
+        const size_t lds = sizeof(float) * 256 * (3 * K + 1);
+        if (overwrite) hipLaunchKernelGGL((gs_sh_from_views_kernel<DEG, true, STRIDED>), grid, block, lds, s, n, means, nviews, cams, drgb, d_shs, sh_stride);
+        else hipLaunchKernelGGL((gs_sh_from_views_kernel<DEG, false, STRIDED>), grid, block, lds, s, n, means, nviews, cams, drgb, d_shs, sh_stride);
+        return hipGetLastError();
+    });
 }
 
 // gaussians per workgroup of the SH kernel: its LDS tile is (3K + 1) floats per gaussian (49 at SH degree 3), so 256 gaussians
@@ -374,56 +346,30 @@ hipError_t gs_launch_preprocess_bwd(const GsPreprocessBwdArgs &a, const GsCamera
     if (a.n <= 0) return hipSuccess;
     const int phases = mode.phases, adam_mode = mode.adam_mode;
     const GsAdamFused *adam = mode.adam;
-    const int T = sh_bwd_threads();
-    dim3 block(T), grid((unsigned)((a.n + T - 1) / T));
-    const int K = (a.sh_degree + 1) * (a.sh_degree + 1);                 // of the ACTIVE degree: the tile holds the bands evaluated
-    const size_t lds = sizeof(float) * T * (3 * K + 1);
-    if (a.sh_degree < 0 || a.sh_degree > 3 || a.sh_stride < 3 * K) return hipErrorInvalidValue;
-    const bool strided = a.sh_stride > 3 * K;                            // an active degree below the stored one (0..2): rows a.sh_stride floats apart
     const GsAdamFused ad = adam ? *adam : GsAdamFused{};
-    if (adam_mode) {                                                   // fused backward + Adam: one launch, both phases
-        if (!adam || !a.overwrite || (phases & 3) != 3 || (adam_mode != 1 && adam_mode != 2)) return hipErrorInvalidValue;
-#define GS_SHA(D, S) do { if (adam_mode == 2) hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, true, 2, S>), grid, block, lds, s, a, cam, ad); \
-                          else hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, true, 1, S>), grid, block, lds, s, a, cam, ad); } while (0)
-        if (strided)
-        switch (a.sh_degree) {
-            case 0: GS_SHA(0, true); break;
-            case 1: GS_SHA(1, true); break;
-            case 2: GS_SHA(2, true); break;
-            default: return hipErrorInvalidValue;
-        }
-        else
-        switch (a.sh_degree) {
-            case 0: GS_SHA(0, false); break;
-            case 1: GS_SHA(1, false); break;
-            case 2: GS_SHA(2, false); break;
-            case 3: GS_SHA(3, false); break;
-            default: return hipErrorInvalidValue;
-        }
-#undef GS_SHA
-        return hipGetLastError();
-    }
-#define GS_SH2(D, F, S) do { if (a.overwrite) hipLaunchKernelGGL((gs_sh_bwd_kernel<D, true, F, 0, S>), grid, block, lds, s, a, cam, ad); \
-                            else hipLaunchKernelGGL((gs_sh_bwd_kernel<D, false, F, 0, S>), grid, block, lds, s, a, cam, ad); } while (0)
-#define GS_SH(D, S) do { if (fused) GS_SH2(D, true, S); else GS_SH2(D, false, S); } while (0)
+    if (adam_mode && (!adam || !a.overwrite || (phases & 3) != 3 || (adam_mode != 1 && adam_mode != 2))) return hipErrorInvalidValue;
     const bool fused = (phases & 3) == 3;
-    if ((phases & 1) && strided)
-    switch (a.sh_degree) {
-        case 0: GS_SH(0, true); break;
-        case 1: GS_SH(1, true); break;
-        case 2: GS_SH(2, true); break;
-        default: return hipErrorInvalidValue;
-    }
-    else if (phases & 1)
-    switch (a.sh_degree) {
-        case 0: GS_SH(0, false); break;
-        case 1: GS_SH(1, false); break;
-        case 2: GS_SH(2, false); break;
-        case 3: GS_SH(3, false); break;
-        default: return hipErrorInvalidValue;
-    }
-    block = dim3(256); grid = dim3((unsigned)((a.n + 255) / 256));
+    // a.sh_degree: the ACTIVE degree (the tile holds the bands evaluated); a.sh_stride above 3 K: an active degree below the stored one
+    const hipError_t e = gs_sh_dispatch(a.sh_degree, a.sh_stride, [&](auto D, auto S) {
+        constexpr int DEG = decltype(D)::value, K = (DEG + 1) * (DEG + 1);
+        constexpr bool STRIDED = decltype(S)::value;
+        const int T = sh_bwd_threads();
+        const dim3 block(T), grid((unsigned)((a.n + T - 1) / T));
+        const size_t lds = sizeof(float) * T * (3 * K + 1);
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, lds, s, a, cam, ad); };
+        if (adam_mode == 2) launch(gs_sh_bwd_kernel<DEG, true, true, 2, STRIDED>);      // fused backward + Adam: one launch, both phases
+        else if (adam_mode) launch(gs_sh_bwd_kernel<DEG, true, true, 1, STRIDED>);
+        else if (phases & 1) {                                          // (not: the geometry chain alone; degree and stride are checked all the same)
+            if (a.overwrite && fused) launch(gs_sh_bwd_kernel<DEG, true, true, 0, STRIDED>);
+            else if (a.overwrite) launch(gs_sh_bwd_kernel<DEG, true, false, 0, STRIDED>);
+            else if (fused) launch(gs_sh_bwd_kernel<DEG, false, true, 0, STRIDED>);
+            else launch(gs_sh_bwd_kernel<DEG, false, false, 0, STRIDED>);
+        }
+        return hipSuccess;
+    });
+    if (e != hipSuccess) return e;
     if ((phases & 2) && !fused) {
+        const dim3 block(256), grid((unsigned)((a.n + 255) / 256));
         if (a.overwrite) hipLaunchKernelGGL(gs_geom_bwd_kernel<true>, grid, block, 0, s, a, cam);
         else hipLaunchKernelGGL(gs_geom_bwd_kernel<false>, grid, block, 0, s, a, cam);
     }

@@ -4,7 +4,7 @@
 // compute the direction, the basis and the sums alike; they differ in two macros only: GS_SH_VIEWS_BEGIN (first thing in the loop over the views:
 // whatever the source needs before the arithmetic; may be empty) and GS_SH_VIEWS_DRGB, which declares the three floats g0, g1, g2
 // of (view v, gaussian g) as plain loads.  Expects n, means, nviews, cams, d_shs, sh_stride and the template parameters DEG, OVERWRITE,
-// STRIDED in scope.  DEG is the ACTIVE degree; STRIDED: the rows of d_shs are sh_stride > 3 K floats apart (an active degree below the
+// STRIDED in scope, and gs_sh.h included (the basis is gs_sh_basis.inc).  DEG is the ACTIVE degree; STRIDED: the rows of d_shs are sh_stride > 3 K floats apart (an active degree below the
 // stored one): their first 3 K floats are rebuilt, the rest become + 0 when overwriting and are left alone when accumulating.
     constexpr int K = (DEG + 1) * (DEG + 1);
     constexpr int ROW = 3 * K + 1;
@@ -30,18 +30,7 @@
             const float v2 = p[2] - (lookAt[2] - eye[2]);
             const float inrm = rsqrtf(v0 * v0 + v1 * v1 + v2 * v2);
             const float X = v0 * inrm, Y = v1 * inrm, Z = v2 * inrm;
-            float bs[K];
-            bs[0] = SH_C0;
-            if constexpr (DEG >= 1) { bs[1] = -Y * SH_C1; bs[2] = Z * SH_C1; bs[3] = -X * SH_C1; }
-            if constexpr (DEG >= 2) {
-                const float xx = X * X, yy = Y * Y, zz = Z * Z, xy = X * Y, yz = Y * Z, xz = X * Z;
-                bs[4] = bC2[0] * xy; bs[5] = bC2[1] * yz; bs[6] = bC2[2] * (2 * zz - xx - yy); bs[7] = bC2[3] * xz; bs[8] = bC2[4] * (xx - yy);
-                if constexpr (DEG >= 3) {
-                    bs[9] = bC3[0] * Y * (3 * xx - yy); bs[10] = bC3[1] * xy * Z; bs[11] = bC3[2] * Y * (4 * zz - xx - yy);
-                    bs[12] = bC3[3] * Z * (2 * zz - 3 * xx - 3 * yy); bs[13] = bC3[4] * X * (4 * zz - xx - yy);
-                    bs[14] = bC3[5] * Z * (xx - yy); bs[15] = bC3[6] * X * (xx - 3 * yy);
-                }
-            }
+#include "gs_sh_basis.inc"
             GS_SH_VIEWS_DRGB
 #pragma unroll
             for (int k = 0; k < K; ++k) { acc[3 * k] += bs[k] * g0; acc[3 * k + 1] += bs[k] * g1; acc[3 * k + 2] += bs[k] * g2; }
@@ -51,10 +40,7 @@
     const int RS = STRIDED ? sh_stride : 3 * K;
     for (int idx = threadIdx.x; idx < nb * 3 * K; idx += blockDim.x) {     // coalesced rows
         const float v = tile[(idx / (3 * K)) * ROW + idx % (3 * K)];
-        const int64_t gi = STRIDED ? gb * RS + (int64_t)(idx / (3 * K)) * RS + idx % (3 * K) : gb * 3 * K + idx;
+        const int64_t gi = gs_sh_row_index<3 * K, STRIDED>(gb, RS, idx);
         if (OVERWRITE) d_shs[gi] = v; else d_shs[gi] += v;
     }
-    if constexpr (STRIDED && OVERWRITE) {
-        const int hi = RS - 3 * K;
-        for (int c = threadIdx.x; c < nb * hi; c += blockDim.x) d_shs[gb * RS + (int64_t)(c / hi) * RS + 3 * K + c % hi] = 0.0f;
-    }
+    if constexpr (STRIDED && OVERWRITE) gs_sh_zero_inactive<3 * K>(d_shs, gb, nb, RS);

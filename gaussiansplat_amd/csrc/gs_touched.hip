@@ -23,8 +23,7 @@
 // Nothing is read outside a view's rows_cap rows whatever the bitmap says: bits at positions >= n belong to no thread, and a
 // rank >= rows_cap (a corrupt or truncated gather) reads as a zero row.
 #include "gs_common.h"
-#define GS_SH_CONSTANTS_NS gs_touched_constants
-#include "gs_sh_views.h"
+#include "gs_sh.h"
 
 static_assert(GS_TOUCHED_CHUNK == 256, "one workgroup of 256 threads (four ballots, eight bitmap words) per chunk");
 #define GS_TOUCHED_WORDS (GS_TOUCHED_CHUNK / 32)
@@ -202,29 +201,19 @@ hipError_t gs_launch_sh_from_touched(int64_t n, int sh_degree, int sh_stride, co
                                      float *d_shs, int overwrite, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     const int64_t nchunks = gs_touched_chunks(n), words = (n + 31) / 32;
-    const int K = (sh_degree + 1) * (sh_degree + 1);                      // of the ACTIVE degree; sh_stride: floats per stored row of d_shs
-    if (nchunks > 0x7fffffffLL || nviews <= 0 || nviews > 65535 || sh_degree < 0 || sh_degree > 3 || sh_stride < 3 * K) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(gs_touched_count_kernel, dim3((unsigned)((words + 255) / 256), (unsigned)nviews), dim3(256), 0, s, bits, words, n, chunk_cnt, nchunks);
-    const hipError_t e = gs_launch_chunk_scan(chunk_cnt, chunk_off, nchunks, nviews, nullptr, s);   // (also reports the count launch)
-    if (e != hipSuccess) return e;
-    const GsTouchedColorSrc src{bits, rows, chunk_off, zero3, words, nchunks, rows_cap};
-    const dim3 grid((unsigned)nchunks), block(GS_TOUCHED_CHUNK);
-    const size_t lds = sizeof(float) * GS_TOUCHED_CHUNK * (3 * K + 1);
-#define GS_ST(D, ...) do { if (overwrite) hipLaunchKernelGGL((gs_sh_from_touched_kernel<D, true, ##__VA_ARGS__>), grid, block, lds, s, n, means, nviews, cams, src, d_shs, sh_stride); \
-                      else hipLaunchKernelGGL((gs_sh_from_touched_kernel<D, false, ##__VA_ARGS__>), grid, block, lds, s, n, means, nviews, cams, src, d_shs, sh_stride); } while (0)
-    if (sh_stride > 3 * K)                                                // an active degree below the stored one: 0..2
-    switch (sh_degree) {
-        case 0: GS_ST(0, true); break;
-        case 1: GS_ST(1, true); break;
-        default: GS_ST(2, true); break;
-    }
-    else
-    switch (sh_degree) {
-        case 0: GS_ST(0); break;
-        case 1: GS_ST(1); break;
-        case 2: GS_ST(2); break;
-        default: GS_ST(3); break;
-    }
-#undef GS_ST
-    return hipGetLastError();
+    if (nchunks > 0x7fffffffLL || nviews <= 0 || nviews > 65535) return hipErrorInvalidValue;
+    // sh_degree: the ACTIVE degree; sh_stride: floats per stored row of d_shs
+    return gs_sh_dispatch(sh_degree, sh_stride, [&](auto D, auto S) {
+        hipLaunchKernelGGL(gs_touched_count_kernel, dim3((unsigned)((words + 255) / 256), (unsigned)nviews), dim3(256), 0, s, bits, words, n, chunk_cnt, nchunks);
+        const hipError_t e = gs_launch_chunk_scan(chunk_cnt, chunk_off, nchunks, nviews, nullptr, s);   // (also reports the count launch)
+        if (e != hipSuccess) return e;
+        constexpr int DEG = decltype(D)::value, K = (DEG + 1) * (DEG + 1);
+        constexpr bool STRIDED = decltype(S)::value;
+        const GsTouchedColorSrc src{bits, rows, chunk_off, zero3, words, nchunks, rows_cap};
+        const dim3 grid((unsigned)nchunks), block(GS_TOUCHED_CHUNK);
+        const size_t lds = sizeof(float) * GS_TOUCHED_CHUNK * (3 * K + 1);
+        if (overwrite) hipLaunchKernelGGL((gs_sh_from_touched_kernel<DEG, true, STRIDED>), grid, block, lds, s, n, means, nviews, cams, src, d_shs, sh_stride);
+        else hipLaunchKernelGGL((gs_sh_from_touched_kernel<DEG, false, STRIDED>), grid, block, lds, s, n, means, nviews, cams, src, d_shs, sh_stride);
+        return hipGetLastError();
+    });
 }
