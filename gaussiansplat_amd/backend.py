@@ -24,7 +24,7 @@ STAGES = ("preprocess", "depth_sort", "count_scan", "emit", "tile_sort", "ranges
 
 # every symbol include/gsplat.h declares (tests/test_abi.py checks the header against this)
 SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs_last_error", "gs_set_stream",
-           "gs_synchronize", "gs_set_model", "gs_set_model_2d", "gs_set_active_sh_degree", "gs_get_active_sh_degree", "gs_set_image_size", "gs_set_camera", "gs_preprocess", "gs_bin", "gs_bind_outputs", "gs_forward", "gs_backward_sgd",
+           "gs_synchronize", "gs_set_model", "gs_set_model_2d", "gs_set_active_sh_degree", "gs_get_active_sh_degree", "gs_set_background", "gs_get_background", "gs_compose_target", "gs_set_image_size", "gs_set_camera", "gs_preprocess", "gs_bin", "gs_bind_outputs", "gs_forward", "gs_backward_sgd",
            "gs_backward", "gs_backward_ex", "gs_reset_grads", "gs_loss_l1_dssim", "gs_sgd_step", "gs_comm_unique_id",
            "gs_comm_init", "gs_allreduce_grads", "gs_comm_destroy", "gs_color_grads_pack", "gs_sh_grads_from_views", "gs_color_rows_pack", "gs_sh_grads_from_touched", "gs_grads_alloc", "gs_grads_read", "gs_num_gaussians", "gs_num_instances", "gs_get_array",
            "gs_get_stage_times", "gs_get_stage_stats", "gs_get_work_counters", "gs_get_work_counters_ex", "gs_debug_time_composite",
@@ -135,6 +135,9 @@ def load():
     L.gs_set_image_size.argtypes = [vp, C.c_int32, C.c_int32]
     L.gs_set_active_sh_degree.argtypes = [vp, C.c_int]
     L.gs_get_active_sh_degree.argtypes = [vp]
+    L.gs_set_background.argtypes = [vp, fp]
+    L.gs_get_background.argtypes = [vp, fp]
+    L.gs_compose_target.argtypes = [vp, vp, C.c_int32, C.c_int32, vp]
     L.gs_color_grads_pack.argtypes = [vp, vp]
     L.gs_sh_grads_from_views.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int]
     L.gs_color_rows_pack.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
@@ -269,6 +272,26 @@ class Context:
         if rc < 0:
             self._chk(rc)
         return int(rc)
+
+    def set_background(self, rgb=(0.0, 0.0, 0.0)):
+        """gs_set_background: the colour behind the last splat, image = C + T * bg (three finite floats; the default is black).  The request
+        is the ctx's: it survives set_model_*; a changed value drops the image (backward wants a new forward), the lists stand."""
+        vals = [float(x) for x in rgb]
+        if len(vals) != 3:
+            raise ValueError("set_background: three components (r, g, b)")
+        self._chk(self.L.gs_set_background(self.h, (C.c_float * 3)(*vals)))
+
+    @property
+    def background(self) -> tuple:
+        """gs_get_background: the current background as three floats."""
+        o = (C.c_float * 3)()
+        self._chk(self.L.gs_get_background(self.h, o))
+        return (float(o[0]), float(o[1]), float(o[2]))
+
+    def compose_target(self, rgba_ptr: int, W: int, H: int, out_ptr: int):
+        """gs_compose_target: a straight-alpha target [4, H, W] over the ctx's background into [3, H, W], device buffers, on the ctx
+        stream: out = rgba[c] * a + bg[c] * (1 - a), four fp32 operations.  No sync."""
+        self._chk(self.L.gs_compose_target(self.h, C.c_void_p(int(rgba_ptr)), int(W), int(H), C.c_void_p(int(out_ptr))))
 
     def set_image_size(self, W: int, H: int):
         self._chk(self.L.gs_set_image_size(self.h, int(W), int(H)))

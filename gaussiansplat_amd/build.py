@@ -47,6 +47,8 @@ SOURCES = {
     # density control: statistics, decisions and the children of a split are specified operation by operation (tests/density_ref.py matches bit for bit)
     "gs_density.hip": ["-ffp-contract=off"],
     "gs_api_density.hip": ["-ffp-contract=off"],
+    # background colour: blend and target compositor are specified as single fp32 operations (NumPy float32 matches bit for bit)
+    "gs_background.hip": ["-ffp-contract=off"],
     "gs_api.hip": [],
     "gs_api_bin.hip": [],
     "gs_api_composite.hip": [],

@@ -191,6 +191,37 @@ int gs_get_active_sh_degree(const gs_ctx *c) {
     return c->active_sh_degree();
 }
 
+// The background colour: what gs_forward adds behind the last splat.  The lists do not depend on it, so a change takes the frame back to
+// Stage::BINNED only -- the image is stale and a backward asks for gs_forward first; the value in force costs nothing.
+int gs_set_background(gs_ctx *c, const float rgb[3]) {
+    if (!c) return GS_ERR_INVALID;
+    if (!rgb) return fail(c, GS_ERR_INVALID, "gs_set_background: NULL argument");
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(rgb[i])) return fail(c, GS_ERR_INVALID, "gs_set_background: the components must be finite");
+    if (rgb[0] == c->background[0] && rgb[1] == c->background[1] && rgb[2] == c->background[2]) return GS_OK;
+    for (int i = 0; i < 3; ++i) c->background[i] = rgb[i];
+    c->fall_back(gs_ctx::Stage::BINNED);
+    return GS_OK;
+}
+
+int gs_get_background(const gs_ctx *c, float rgb[3]) {
+    if (!c || !rgb) return GS_ERR_INVALID;
+    for (int i = 0; i < 3; ++i) rgb[i] = c->background[i];
+    return GS_OK;
+}
+
+// A training target with straight alpha, composited over the ctx's background: what the loss compares the frame against.
+int gs_compose_target(gs_ctx *c, const float *rgba, int32_t W, int32_t H, float *rgb_out) {
+    if (!c) return GS_ERR_INVALID;
+    if (!rgba || !rgb_out) return fail(c, GS_ERR_INVALID, "gs_compose_target: NULL argument");
+    if (W <= 0 || H <= 0 || W > 32767 || H > 32767) return fail(c, GS_ERR_INVALID, "gs_compose_target: image size must be in 1..32767");
+    const size_t px = (size_t)W * H;
+    if (rgb_out < rgba + 4 * px && rgba < rgb_out + 3 * px) return fail(c, GS_ERR_INVALID, "gs_compose_target: rgb_out overlaps rgba");
+    if (bind_device(c)) return GS_ERR_HIP;
+    HIPCHK(c, gs_launch_compose_target(rgba, rgb_out, px, c->background, c->stream));
+    return GS_OK;
+}
+
 int gs_set_image_size(gs_ctx *c, int32_t W, int32_t H) {
     if (!c) return GS_ERR_INVALID;
     if (W <= 0 || H <= 0 || W > 32767 || H > 32767) return fail(c, GS_ERR_INVALID, "gs_set_image_size: image size must be in 1..32767");

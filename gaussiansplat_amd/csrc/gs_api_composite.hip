@@ -146,6 +146,15 @@ static int build_frame_order(gs_ctx *c) {
     return GS_OK;
 }
 
+// The background, blended into the image the frame's forward left: image = C + T bg, in place (gs_background.hip).  Everything that reads the
+// image afterwards -- the copy-out, the loss, the composite backward's seed S = image . dC, whole tiles, strips, list segments and the fused
+// backwards alike -- finds the blended one.  Over black nothing is launched.
+int blend_background(gs_ctx *c) {
+    if (!c->has_background()) return GS_OK;
+    HIPCHK(c, gs_launch_blend_background(c->img(), c->tr(), (size_t)c->cam.W * c->cam.H, c->background, c->stream));
+    return GS_OK;
+}
+
 extern "C" {
 
 int gs_bind_outputs(gs_ctx *c, float *image, float *transmittance) {
@@ -179,8 +188,11 @@ static int enqueue_forward_round(gs_ctx *c, int r) {
     if (r == 0 && c->fwd_fills_g2d) {                                      // the zero fill of the gradient rows, at the end of this launch's grid (gs_forward)
         a.fill_dst = c->g2d.p; a.fill_bytes = c->g2d_bytes(); a.fill_blocks = gs_composite_fill_blocks(a.fill_dst, a.fill_bytes);
     }
-    StageTimer t(c, GS_STAGE_COMPOSITE_FWD);                               // the kernel alone
+    StageTimer t(c, GS_STAGE_COMPOSITE_FWD);                               // the kernel alone ...
     HIPCHK(c, gs_launch_composite_fwd(a, c->stream));
+    // ... and, behind the frame's last round, the background: inside the same pair of events, in front of the order kernel and the copy-out.  A
+    // round 0 that gs_forward enqueues again (settle_totals rebuilt the lists) rewrites every pixel and is blended again
+    if (a.final_round) { if (int rc = blend_background(c)) return rc; }
     if (r == 0) c->fill_blocks_fwd = a.fill_blocks;
     return GS_OK;
 }

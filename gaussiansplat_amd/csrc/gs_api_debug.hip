@@ -169,6 +169,8 @@ static int debug_composite_args(gs_ctx *c, int which, int variant, GsCompositeAr
     a.variant = variant % 100;
     a.cull = (c->cfg.alpha_cull != 0) != (variant >= 1000);                  // +1000: the other cull setting
     if (c->dbg_win_len > 0) {                                                // gs_debug_set_window: a slice of the launch order
+        // (a forward over a slice rewrites the slice's tiles only: the blend behind it would add the background to the others a second time)
+        if (which == 0 && c->has_background()) return fail(c, GS_ERR_UNSUPPORTED, "gs_debug_set_window: forward launches over a window need a black background");
         if (!a.tile_order || a.parts > 1) return fail(c, GS_ERR_INVALID, "gs_debug_set_window: the frame has no launch order (or several waves per tile)");
         if (c->dbg_win_start + c->dbg_win_len > a.order_len) return fail(c, GS_ERR_INVALID, "gs_debug_set_window: beyond the launch order");
         a.tile_order += c->dbg_win_start; a.order_len = c->dbg_win_len;
@@ -199,6 +201,7 @@ int gs_debug_time_composite(gs_ctx *c, int which, int variant, int reps, float *
     HIPCHK(c, hipEventRecord(e0, c->stream));
     for (int i = 0; i < reps; ++i) HIPCHK(c, launch());
     HIPCHK(c, hipEventRecord(e1, c->stream));
+    if (which == 0) { if (int rc = blend_background(c)) return rc; }          // the launches left C in the bound image: the frame stays what gs_forward left
     HIPCHK(c, hipEventSynchronize(e1));
     float ms = 0.0f;
     HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
@@ -230,6 +233,7 @@ int gs_debug_tile_clock(gs_ctx *c, int which, int variant, uint64_t *out) {
     for (int rep = 0; rep < 2; ++rep) {                                       // the second launch (warm) is the one kept
         HIPCHK(c, which == 0 ? gs_launch_composite_fwd(a, c->stream) : gs_launch_composite_bwd(a, c->stream));
     }
+    if (which == 0) { if (int rc = blend_background(c)) return rc; }          // (as gs_debug_time_composite)
     HIPCHK(c, hipMemcpyAsync(out, c->tile_clock.p, sizeof(uint64_t) * GS_TILE_CLOCK_WORDS * rows, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return GS_OK;

@@ -458,3 +458,7 @@ __host__ __device__ inline double gs_fixed_inv(int comp) { return comp >= 6 ? GS
 hipError_t gs_loss_run(int W, int H, int C, const float *img, const float *gt, float *maps, double *acc, float *dC, float lam,
                        const float *win121, hipStream_t s);
 hipError_t gs_launch_sgd(float *p, const float *g, float lr, size_t n, hipStream_t s);
+
+// background colour (gs_background.hip): px pixels per plane, bg three host floats; each operation one fp32 operation, never fused
+hipError_t gs_launch_blend_background(float *image, const float *trans, size_t px, const float bg[3], hipStream_t s);   // image[c][p] += trans[p] * bg[c], in place
+hipError_t gs_launch_compose_target(const float *rgba, float *out, size_t px, const float bg[3], hipStream_t s);        // out[c][p] = rgba[c][p] * a + bg[c] * (1 - a)

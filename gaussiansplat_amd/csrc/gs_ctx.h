@@ -7,6 +7,7 @@
 //   gs_api_comm.hip       RCCL below the boundary (gs_comm_*, gs_allreduce_grads)
 //   gs_api_touched.hip    the touched-rows colour exchange (gs_color_rows_pack, gs_sh_grads_from_touched)
 //   gs_api_density.hip    density control (gs_density_accumulate / _decide / _plan / _restructure, gs_opacity_reset)
+//   gs_background.hip     the background colour's two elementwise kernels (the forward's epilogue, gs_compose_target)
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
 // How far the frame has come is ONE ordered value (gs_ctx::Stage): every entry point compares it, reaches a stage or falls back to one.
 // What the ctx holds it owns: DevBuf frees itself, ~gs_ctx releases the communicator, events, streams and pinned blocks -- no list to keep.
@@ -97,6 +98,10 @@ struct gs_ctx {
     int sh_active_request = -1;              // -1: the model's own degree
     int active_sh_degree() const { return sh_active_request < 0 || sh_active_request > sh_degree ? sh_degree : sh_active_request; }
     int sh_row_floats() const { return 3 * (sh_degree + 1) * (sh_degree + 1); }   // the stored row stride of shs, d_shs and their moments
+    // the background colour (gs_set_background): like the active degree the request is the ctx's and outlives gs_set_model.  gs_forward leaves
+    // C + T bg in the image (gs_background.hip, one launch behind the last composite round); all zeros: no launch, the frame over black
+    float background[3] = {0.0f, 0.0f, 0.0f};
+    bool has_background() const { return background[0] != 0.0f || background[1] != 0.0f || background[2] != 0.0f; }
     int kind = 0;                            // 0: 3-D renderer (SplatData3D), 1: 2-D image-fitting renderer (SplatData2D)
     size_t width[5] = {3, 3, 4, 1, 3};       // floats per gaussian of the five parameter / gradient arrays
     int order() const { return kind == 1 ? (int)GS_ORDER_INDEX : cfg.order; }    // the 2-D model has no depth
@@ -390,5 +395,6 @@ inline int order_index(const gs_ctx *c) { return c->view_slot >= 0 ? c->view_slo
 int settle_totals(gs_ctx *c, bool *redo, bool may_relist);
 int bin_round(gs_ctx *c, int r);
 int depth_order(gs_ctx *c, uint32_t **perm_out);
+int blend_background(gs_ctx *c);              // gs_api_composite.hip: image += T bg over the frame's image, on the stream (no launch over black)
 // gs_api_composite.hip: the arguments of a composite launch of the frame, as its plan says (round r of the forward / the backward; debug: an isolated launch)
 GsCompositeArgs composite_args(gs_ctx *c, bool bwd, int r, bool debug = false);

@@ -312,6 +312,10 @@ class HipViewRenderer:
         for t, _ in self._twins():
             if t is not r and getattr(t, "_active_sh_sent", None) != active:
                 t.active_sh_degree = t._active_sh_sent = active
+        bg = r.background                                                  # ... and its background
+        for t, _ in self._twins():
+            if t is not r and getattr(t, "_background_sent", None) != bg:
+                t.background = t._background_sent = bg
         for i, (cam, dC) in enumerate(zip(cameras, dCs)):
             t, st = self._twins()[i % self.pipeline_depth]
             with torch.cuda.stream(st):

@@ -105,8 +105,10 @@ def initGrads(splatData: SplatData3D) -> SplatGrads3D:
 class GaussianRenderer3D:               # renderer.jl:205-219
     def __init__(self, splatData: SplatData3D, imgSize, sh_degree: int, device: int = 0, order: int = B.ORDER_DEPTH_DESC,
                  t_min: float = 1e-5, export_debug: bool = False, profile_stages: bool = False, deterministic: bool = False,
-                 alpha_cull: bool = True, rank_mode: int = 1, slab_mode: int = 1, schedule: int = 0, share_grads_with=None, **ctx_kw):
-        """share_grads_with: another GaussianRenderer3D over the same splatData whose gradient buffer this one accumulates into
+                 alpha_cull: bool = True, rank_mode: int = 1, slab_mode: int = 1, schedule: int = 0, share_grads_with=None,
+                 background=None, **ctx_kw):
+        """background: (r, g, b) behind the last splat (the `background` property); None: black, the reference's frame.
+        share_grads_with: another GaussianRenderer3D over the same splatData whose gradient buffer this one accumulates into
         (a second view in flight, distributed.HipViewRenderer): no buffer of its own is allocated."""
         import torch
         self.splatData = splatData
@@ -132,6 +134,19 @@ class GaussianRenderer3D:               # renderer.jl:205-219
         g = self._splatGrads
         self._grads = B.GsGrads(g.Δmeans.data_ptr(), g.Δscales.data_ptr(), g.Δquaternions.data_ptr(),
                                 g.Δopacities.data_ptr(), g.Δshs.data_ptr())
+        if background is not None:
+            self.background = background
+
+    @property
+    def background(self) -> tuple:
+        """The colour behind the last splat, three floats (default black): forward() leaves C + T * background in imageData, and
+        backward() differentiates that image -- transparent pixels of a white-background dataset then carry a gradient.  Setting it
+        keeps the tile lists and drops the image: render again before the next backward.  It survives a restructured model."""
+        return self.ctx.background
+
+    @background.setter
+    def background(self, rgb):
+        self.ctx.set_background(rgb)
 
     @property
     def splatGrads(self) -> SplatGrads3D:
@@ -212,7 +227,7 @@ class GaussianRenderer2D:               # renderer.jl:7-18
     (DESIGN.md, 2-D renderer)."""
 
     def __init__(self, splatData: SplatData2D, imgSize, device: int = 0, t_min: float = 1e-5, export_debug: bool = False,
-                 profile_stages: bool = False, deterministic: bool = False, alpha_cull: bool = True):
+                 profile_stages: bool = False, deterministic: bool = False, alpha_cull: bool = True, background=None):
         import torch
         self.splatData = splatData
         self._splatGrads = initGrads2D(splatData)
@@ -232,8 +247,11 @@ class GaussianRenderer2D:               # renderer.jl:7-18
         g = self._splatGrads
         self._grads = B.GsGrads(g.Δmeans.data_ptr(), g.Δscales.data_ptr(), g.Δrotations.data_ptr(), g.Δopacities.data_ptr(),
                                 g.Δcolors.data_ptr())
+        if background is not None:
+            self.background = background
 
     splatGrads = GaussianRenderer3D.splatGrads
+    background = GaussianRenderer3D.background
     _begin = GaussianRenderer3D._begin
     _end = GaussianRenderer3D._end
 

@@ -11,6 +11,7 @@ step has no host round trip.  `optimizer=optim.Adam(...)` replaces the SGD updat
 (csrc/gs_adam.hip; fused with the backward when the optimiser was made with fused=True).  `density=density.DensityController(...)`
 adds the other half of the 3DGS recipe: statistics after every backward, clone / split / prune and the opacity reset on schedule.
 `sh_schedule=SHDegreeSchedule(...)` is the recipe's SH degree schedule: band 0 first, one more band every `every` iterations.
+`background=(r, g, b)` or `background=RandomBackground(...)` renders and trains over that colour; an RGBA target is composited over it.
 """
 from __future__ import annotations
 
@@ -37,6 +38,24 @@ class LossFunction:
         self.r, self.λ = renderer, float(λ)
         self.W, self.H, self.C = int(imSize[0]), int(imSize[1]), int(nChannels)
         self._dC = None
+        self._target = None                 # scratch of compose_target: an RGBA target over the renderer's background
+
+    def compose_target(self, rgba):
+        """A straight-alpha target [4, H, W] over the renderer's current background (gs_compose_target, on the GPU): the [3, H, W]
+        target the loss compares the frame against.  The result is a scratch tensor kept here and overwritten by the next call."""
+        import torch
+        dev = self.r.imageData.device
+        rgba = rgba if isinstance(rgba, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(rgba, np.float32))
+        rgba = rgba.to(dev, torch.float32).contiguous()
+        if tuple(rgba.shape) != (4, self.H, self.W):
+            raise ValueError(f"compose_target: the target must be [4, {self.H}, {self.W}], not {tuple(rgba.shape)}")
+        if self._target is None:
+            self._target = torch.empty((3, self.H, self.W), dtype=torch.float32, device=dev)
+        self.r._begin()
+        self.r.ctx.compose_target(rgba.data_ptr(), self.W, self.H, self._target.data_ptr())
+        self.r._end()
+        self._keep_rgba = rgba
+        return self._target
 
     def _ptrs(self, img, gt):
         import torch
@@ -102,8 +121,40 @@ class SHDegreeSchedule:
         return renderer.active_sh_degree
 
 
+class RandomBackground:
+    """A fresh random background every iteration, the usual remedy against floaters: numpy.random.default_rng(seed) draws three uniform
+    float32 values in [0, 1) per iteration, and the RGBA target is composited over the same colour (trainStep).  The object counts the
+    iterations it was applied to (`iteration`), as SHDegreeSchedule does, so one object serves one training run."""
+
+    def __init__(self, seed: int = 0):
+        self.seed = seed
+        self.rng = np.random.default_rng(seed)
+        self.iteration = 0                                      # iterations a colour was drawn for
+
+    def draw(self) -> tuple:
+        """The colour of the iteration about to run (three floats that are exact float32 values); counts it."""
+        rgb = self.rng.random(3, dtype=np.float32)
+        self.iteration += 1
+        return (float(rgb[0]), float(rgb[1]), float(rgb[2]))
+
+    def apply(self, renderer) -> tuple:
+        """Set the renderer's background for the iteration about to run and count it.  Returns the colour."""
+        if not isinstance(renderer, (R.GaussianRenderer3D, R.GaussianRenderer2D)):
+            raise ValueError("RandomBackground: apply needs a GaussianRenderer3D or GaussianRenderer2D")
+        rgb = self.draw()
+        renderer.background = rgb
+        return rgb
+
+
+def _channels(gtimg) -> int:
+    shape = getattr(gtimg, "shape", None)
+    if shape is None or len(shape) != 3 or int(shape[0]) not in (3, 4):
+        raise ValueError("trainStep: with `background` the target must be a [3, H, W] or [4, H, W] image")
+    return int(shape[0])
+
+
 def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, want_loss: bool = True, fused_sgd: bool = False,
-              optimizer=None, density=None, sh_schedule=None):
+              optimizer=None, density=None, sh_schedule=None, background=None):
     """One iteration of train.jl:33-56 as intended (see module docstring).
     fused_sgd (3-D renderer): backward and the parameter update in one pass (gs_backward_sgd) -- the same parameters bit for
     bit (deterministic mode), but renderer.splatGrads is not filled.
@@ -113,7 +164,14 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
     frame, so this is the only place), and after the update it clones / splits / prunes and resets opacities when its schedule says so.
     The fused forms leave no frame to accumulate from: a fused optimiser or fused_sgd with `density` is a ValueError.
     sh_schedule (SHDegreeSchedule, 3-D renderer): sets the active SH degree of this iteration before preprocess; every optimiser form,
-    the fused ones included, and density control run under it unchanged (the request survives a restructured model)."""
+    the fused ones included, and density control run under it unchanged (the request survives a restructured model).
+    background: None leaves the renderer's background as it is; (r, g, b) sets it; a RandomBackground draws this iteration's colour and
+    sets it, before preprocess.  A [4, H, W] target (straight alpha) is composited over the renderer's current background before the
+    loss (lossFunc.compose_target), a [3, H, W] one is used as it is -- so a RandomBackground with a 3-channel target is a ValueError:
+    the target could not follow the colour.  Every optimiser form, density control and the SH schedule run unchanged under it."""
+    if isinstance(background, RandomBackground) and _channels(gtimg) != 4:
+        raise ValueError("trainStep: a RandomBackground needs a [4, H, W] target (RGBA, straight alpha): a 3-channel target "
+                         "could not follow the colour")
     if optimizer is not None and fused_sgd:
         raise ValueError("trainStep: fused_sgd and optimizer exclude each other (make the optimiser with fused=True instead)")
     if density is not None and (fused_sgd or (optimizer is not None and optimizer.fused)):
@@ -121,9 +179,15 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
                          "the fused forms leave no frame to accumulate statistics from")
     if sh_schedule is not None:
         sh_schedule.apply(renderer)
+    if isinstance(background, RandomBackground):
+        background.apply(renderer)
+    elif background is not None:
+        renderer.background = background
     tps = R.preprocess(renderer, camera)
     R.compactIdxs(renderer)
     R.forward(renderer, tps)
+    if getattr(gtimg, "ndim", 0) == 3 and gtimg.shape[0] == 4:
+        gtimg = lossFunc.compose_target(gtimg)
     loss, ΔC = lossFunc.value_and_grad(renderer.imageData, gtimg, want_loss)
     if optimizer is not None:
         if optimizer.fused:
@@ -156,13 +220,14 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
 
 
 def train(renderer, gtimg, lr: float, lossFunc: LossFunction, iterations: int = 100, camera=None, log_every: int = 0, optimizer=None,
-          density=None, sh_schedule=None):
+          density=None, sh_schedule=None, background=None):
     """train.jl:16-59 without the GUI; the reference loops `while score < 0.99` on a score it never updates.
     optimizer: an optim.Adam that replaces the SGD update (lr is then ignored); density: a density.DensityController,
-    sh_schedule: an SHDegreeSchedule (trainStep)."""
+    sh_schedule: an SHDegreeSchedule, background: a colour or a RandomBackground (trainStep)."""
     losses = []
     for it in range(iterations):
-        l = trainStep(renderer, gtimg, lr, lossFunc, camera, want_loss=True, optimizer=optimizer, density=density, sh_schedule=sh_schedule)
+        l = trainStep(renderer, gtimg, lr, lossFunc, camera, want_loss=True, optimizer=optimizer, density=density, sh_schedule=sh_schedule,
+                      background=background)
         losses.append(l)
         if log_every and it % log_every == 0:
             print(f"loss : {l}")                             # loss.jl:69

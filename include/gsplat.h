@@ -234,6 +234,22 @@ int gs_set_model_2d(gs_ctx *ctx, int64_t n, const float *means, const float *sca
 int gs_set_active_sh_degree(gs_ctx *ctx, int degree);
 int gs_get_active_sh_degree(const gs_ctx *ctx);
 
+/* The BACKGROUND colour (both renderers; default 0, 0, 0: the reference composites over black, splat.jl:224-261).  With C = sum c_i alpha_i T_i
+ * and T = prod (1 - alpha_i) as the composite kernels leave them, gs_forward gives
+ *   image[c][p] = C[c][p] + (T[p] * bg[c])        one fp32 multiply, then one fp32 add, never fused; transmittance unchanged,
+ * in the ctx's or the bound image and in whatever it copies out; with bg = 0 nothing is added and nothing is launched.  The backward needs no
+ * argument: it reads the image the forward left, and its gradients are those of sum (C + T bg) . dC.  No gradient with respect to bg.
+ * rgb: three HOST floats; a non-finite one is GS_ERR_INVALID and changes nothing.  The request is the ctx's: it survives gs_set_model and a
+ * density restructure.  A value that differs from the current one drops the image, not the lists: the frame falls back to after gs_bin, and
+ * a backward asks for gs_forward first.  The same value returns at once and keeps the frame. */
+int gs_set_background(gs_ctx *ctx, const float rgb[3]);
+int gs_get_background(const gs_ctx *ctx, float rgb[3]);
+/* A target with straight (non-premultiplied) alpha over the ctx's background, for the loss of a frame rendered over it: rgba planar
+ * [4, H, W] and rgb_out planar [3, H, W] (the image layout), both DEVICE and not overlapping; with a = rgba[3][p]
+ *   rgb_out[c][p] = (rgba[c][p] * a) + (bg[c] * (1 - a))        four fp32 operations, each rounded on its own, in this order.
+ * Runs on the ctx stream, needs no frame and no model, does not synchronise. */
+int gs_compose_target(gs_ctx *ctx, const float *rgba, int32_t W, int32_t H, float *rgb_out);
+
 int gs_set_image_size(gs_ctx *ctx, int32_t W, int32_t H);
 
 /* Camera + image size (forward.jl:41,53-62).  T, P: 16 floats each, column-major. */

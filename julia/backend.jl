@@ -320,6 +320,21 @@ function hip_activeShDegree(r::HipRenderer)
     return Int(rc)
 end
 
+# the background colour (both renderers; default black): hip_forward! leaves C + T * bg in the image and hip_backward! differentiates that
+# image.  The request is the ctx's (it survives a later gs_set_model); a changed value drops the image, the tile lists stand.
+function hip_setBackground!(r::HipRenderer, rgb)
+    length(rgb) == 3 || throw(ArgumentError("rgb: three components"))
+    check(r, ccall((:gs_set_background, libgs), Cint, (Ptr{Cvoid}, Ptr{Float32}), r.ctx, Float32[rgb[1], rgb[2], rgb[3]]))
+end
+function hip_background(r::HipRenderer)
+    rgb = zeros(Float32, 3)
+    check(r, ccall((:gs_get_background, libgs), Cint, (Ptr{Cvoid}, Ptr{Float32}), r.ctx, rgb))
+    return (rgb[1], rgb[2], rgb[3])
+end
+# a straight-alpha target W x H x 4 over the ctx's background into W x H x 3, DEVICE pointers, on the ctx stream (no synchronise)
+hip_composeTarget!(r::HipRenderer, rgba::Ptr{Float32}, rgbOut::Ptr{Float32}) =
+    check(r, ccall((:gs_compose_target, libgs), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int32, Int32, Ptr{Float32}), r.ctx, rgba, r.W, r.H, rgbOut))
+
 # ---- plumbing and introspection -----------------------------------------------------------------------------------
 
 # enqueue on an existing hipStream_t (C_NULL: the ctx's own stream)

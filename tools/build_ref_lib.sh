@@ -11,7 +11,7 @@ git show $REV:include/gsplat.h > $D/x/include/gsplat.h
 cd $D/x/y/csrc
 for f in $(ls *.hip | sed 's/\.hip$//'); do
   extra=""                                                             # the per-file flags of gaussiansplat_amd/build.py
-  case $f in gs_preprocess|gs_preprocess2d|gs_adam|gs_density|gs_api_density) extra="-ffp-contract=off";; gs_composite|gs_loss) extra="-fno-slp-vectorize";; esac
+  case $f in gs_preprocess|gs_preprocess2d|gs_adam|gs_density|gs_api_density|gs_background) extra="-ffp-contract=off";; gs_composite|gs_loss) extra="-fno-slp-vectorize";; esac
   /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wno-unused-function $extra -c $f.hip -o $f.o &
 done
 wait
