@@ -1,6 +1,7 @@
 // gs_api_debug.hip -- introspection for the parity tests (gs_get_array: the reference's scratch arrays and the tile lists) and the
 // profiling hooks (per-stage hipEvent timers, work counters, per-tile clocks, isolated composite launches).
 #include "gs_ctx.h"
+#include "gs_pergaussian.h"
 
 using Stage = gs_ctx::Stage;
 
@@ -93,28 +94,19 @@ int gs_get_array(gs_ctx *c, int which, void *dst, int64_t bytes) {
             if (c->stage < Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_get_array: gs_backward first");
             if ((size_t)bytes != sizeof(float) * 10 * n) return fail(c, GS_ERR_INVALID, "gs_get_array: size mismatch");
             float *o = static_cast<float *>(dst);
-            if (c->cfg.deterministic) {
-                std::vector<long long> fx((size_t)GS_G2D_STRIDE * (n ? n : 1));
-                if (n) HIPCHK(c, hipMemcpyAsync(fx.data(), c->g2d.p, sizeof(long long) * GS_G2D_STRIDE * n, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                for (size_t g = 0; g < n; ++g)
-                    for (int i = 0; i < 10; ++i) o[10 * g + i] = (float)((double)fx[GS_G2D_STRIDE * g + i] * gs_fixed_inv(i));
-            } else {
-                std::vector<float> fl((size_t)GS_G2D_STRIDE * (n ? n : 1));
-                if (n) HIPCHK(c, hipMemcpyAsync(fl.data(), c->g2d.p, sizeof(float) * GS_G2D_STRIDE * n, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                for (size_t g = 0; g < n; ++g)
-                    for (int i = 0; i < 10; ++i) o[10 * g + i] = fl[GS_G2D_STRIDE * g + i];
-            }
-            // the device rows hold raw moments: apply the per-gaussian factors with the view's payload (sig, conic)
+            // the device rows (float, or fixed point in deterministic mode) hold raw moments: apply the per-gaussian factors with the view's payload (sig, conic)
+            const bool fixed = c->cfg.deterministic;
+            std::vector<long long> fx(fixed ? (size_t)GS_G2D_STRIDE * (n ? n : 1) : 0);
+            std::vector<float> fl(fixed ? 0 : (size_t)GS_G2D_STRIDE * (n ? n : 1));
             std::vector<GsPayload> pay(n ? n : 1);
             std::vector<float> ic(4 * (n ? n : 1));
+            if (n) HIPCHK(c, hipMemcpyAsync(fixed ? (void *)fx.data() : (void *)fl.data(), c->g2d.p, c->g2d_bytes(), hipMemcpyDeviceToHost, c->stream));
             if (n) HIPCHK(c, hipMemcpyAsync(pay.data(), c->payload.p, sizeof(GsPayload) * n, hipMemcpyDeviceToHost, c->stream));
             if (n) HIPCHK(c, hipMemcpyAsync(ic.data(), c->invcov.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             for (size_t g = 0; g < n; ++g) {
                 float row[10];
-                for (int i = 0; i < 10; ++i) row[i] = o[10 * g + i];
+                gs_g2d_row_load(GsG2dRows{fl.data(), fixed ? fx.data() : nullptr}, (int64_t)g, row);
                 gs_g2d_to_grads(row, pay[g].sig, ic[4 * g], 0.5f * (ic[4 * g + 1] + ic[4 * g + 2]), ic[4 * g + 3]);
                 for (int i = 0; i < 10; ++i) o[10 * g + i] = row[i];
             }

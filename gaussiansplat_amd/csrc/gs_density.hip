@@ -21,7 +21,7 @@
 // Built with -ffp-contract=off: every product and sum below is rounded on its own (tests/density_ref.py is the NumPy twin, bit for bit);
 // sqrtf is the correctly rounded form (hipcc's default, see gs_adam.h).  Random numbers are an input: the kernels are pure functions.
 #include "gs_density.h"
-#include "gs_detmath.h"
+#include "gs_pergaussian.h"
 #include <stddef.h>
 
 #pragma clang fp contract(off)
@@ -32,15 +32,8 @@ static_assert(GS_DENSITY_CHUNK == 256, "one workgroup of 256 threads = four wave
 __global__ __launch_bounds__(256) void gs_density_accumulate_kernel(GsDensityAccArgs a) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= a.n) return;
-    float row[10];                                                         // as load_g2 (gs_preprocess_bwd.hip) reads it
-    if (a.g2d_fixed) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) row[i] = (float)((double)a.g2d_fixed[GS_G2D_STRIDE * g + i] * gs_fixed_inv(i));
-    } else {
-        const float4 *r = reinterpret_cast<const float4 *>(a.g2d + GS_G2D_STRIDE * g);
-        const float4 v0 = r[0], v1 = r[1], v2 = r[2];
-        row[0] = v0.x; row[1] = v0.y; row[2] = v0.z; row[3] = v0.w; row[4] = v1.x; row[5] = v1.y; row[6] = v1.z; row[7] = v1.w; row[8] = v2.x; row[9] = v2.y;
-    }
+    float row[10];
+    gs_g2d_row_load(a, g, row);
     const float4 ic = reinterpret_cast<const float4 *>(a.invcov)[g];
     const uint4 q = reinterpret_cast<const uint4 *>(a.payload + g)[GS_PAYLOAD_QUADS - 1];   // {yhi, sig, bbx, bby}
     static_assert(offsetof(GsPayload, sig) == 52 && offsetof(GsPayload, bbx) == 56 && offsetof(GsPayload, bby) == 60, "the payload row's last quad");
@@ -161,17 +154,8 @@ __global__ __launch_bounds__(GS_DENSITY_CHUNK) void gs_density_restructure_kerne
     if (cls[2] && idx[2] < a.splits) {
         const float m[3] = {a.src[0][3 * g], a.src[0][3 * g + 1], a.src[0][3 * g + 2]};
         const float sc[3] = {a.src[1][3 * g], a.src[1][3 * g + 1], a.src[1][3 * g + 2]};
-        const float qw = a.src[2][4 * g], qx = a.src[2][4 * g + 1], qy = a.src[2][4 * g + 2], qz = a.src[2][4 * g + 3];
-        float R[3][3];                                                     // quatToRot as gs_preprocess_kernel writes it: raw quaternion, the reference's signs
-        R[0][0] = 1.0f - 2.0f * (qy * qy + qz * qz);
-        R[1][0] = 2.0f * (qx * qy + qw * qz);
-        R[2][0] = 2.0f * (qx * qz - qw * qy);
-        R[0][1] = 2.0f * (qx * qy - qw * qz);
-        R[1][1] = 1.0f - 2.0f * (qx * qx - qz * qz);
-        R[2][1] = 2.0f * (qy * qz + qw * qx);
-        R[0][2] = 2.0f * (qx * qz + qw * qy);
-        R[1][2] = 2.0f * (qy * qz - qw * qx);
-        R[2][2] = 1.0f - 2.0f * (qx * qx + qy * qy);
+        float R[3][3];                                                     // quatToRot as the forward writes it: raw quaternion, the reference's signs
+        gs_quat_to_rot(a.src[2][4 * g], a.src[2][4 * g + 1], a.src[2][4 * g + 2], a.src[2][4 * g + 3], R);
         const float ex[3] = {gs_expf(sc[0]), gs_expf(sc[1]), gs_expf(sc[2])};
 #pragma unroll
         for (int c = 0; c < 2; ++c) {

@@ -2,20 +2,20 @@
 //
 // The preprocess path decides tile ids and depth keys, which must be bit-identical to the
 // CPU oracle.  Everything here is built only from individually rounded IEEE fp32/fp64
-// operations (the translation unit is compiled with -ffp-contract=off), so gfx950 and any
-// IEEE host produce the same bits.  exp stands in for Julia/libdevice exp
+// operations (contraction is off below, whatever the translation unit's flags), so gfx950 and any
+// IEEE host produce the same bits -- and every function is __host__ __device__:
+// tests/pergaussian_host.cpp runs them on the CPU.  exp stands in for Julia/libdevice exp
 // (reference src/splat.jl:176, src/projection.jl:133-135).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#pragma clang fp contract(off)
-
-__device__ __forceinline__ float gs_u2f(uint32_t u) { return __uint_as_float(u); }
-__device__ __forceinline__ uint32_t gs_f2u(float f) { return __float_as_uint(f); }
+__host__ __device__ __forceinline__ float gs_u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
+__host__ __device__ __forceinline__ uint32_t gs_f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
 
 // Cody-Waite range reduction + Cephes expf polynomial; results below FLT_MIN flush to 0.
-__device__ __forceinline__ float gs_expf(float x) {
+__host__ __device__ __forceinline__ float gs_expf(float x) {
+#pragma clang fp contract(off)
     if (x != x) return x;
     if (x > 88.72283f) return __builtin_huge_valf();
     if (x < -87.33654f) return 0.0f;
@@ -41,13 +41,14 @@ __device__ __forceinline__ float gs_expf(float x) {
 }
 
 // Julia max/min propagate NaN.
-__device__ __forceinline__ double gs_jlmax(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : (a > b ? a : b); }
-__device__ __forceinline__ double gs_jlmin(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : (a < b ? a : b); }
+__host__ __device__ __forceinline__ double gs_jlmax(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : (a > b ? a : b); }
+__host__ __device__ __forceinline__ double gs_jlmin(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : (a < b ? a : b); }
 
 // The spec's sin/cos (2-D renderer, reference src/cov2d.jl:6-8 CUDA.cos / CUDA.sin): k = rint(x*2/pi), three-term
 // Cody-Waite reduction by pi/2, Cephes sinf/cosf polynomials on [-pi/4, pi/4], quadrant fix-up; fp32 mul/add only
 // (the CPU oracle and its NumPy twin use the same sequence of operations).
-__device__ __forceinline__ void gs_sincosf(float x, float &sn, float &cs) {
+__host__ __device__ __forceinline__ void gs_sincosf(float x, float &sn, float &cs) {
+#pragma clang fp contract(off)
     if (!(x - x == 0.0f)) { sn = __builtin_nanf(""); cs = sn; return; }      // NaN or Inf
     const float kf = __builtin_rintf(x * 0.636619772f);
     float r = x - kf * 1.5703125f;

@@ -5,6 +5,8 @@
 // thread's row of SH gradients in the LDS tile), K and srow_live -- ADAM != 0 steps p, m, v with the gradients instead of storing them.
 // Text, not a function: as a __forceinline__ function the same statements took 186 VGPRs instead of 148 (two waves per SIMD instead of three).  Contraction is off: which products the compiler fuses into fma depends on
 // the code around them, and both kernels must produce the same bits (a backward in two steps == a backward in one, tests/test_gpu_multiview.py).
+// The eleven gradients stay written twice, for the fused Adam and for the store: formed once into one array with one sink behind it, the
+// fused accumulating kernels took 156 .. 160 VGPRs instead of 144 (profiles/HISTORY.md); the two share grad_put, the one store line.
 #pragma clang fp contract(off)
     const float *T = cam.T, *P = cam.P;
     if (!OVERWRITE) {   // untouched by the view (see gs_sh_bwd_kernel): a gradient of exactly zero is added to nothing -- the model is not read
@@ -15,7 +17,7 @@
         if (!touched) break;
     }
 
-    // ---- forward recompute (same formulas as gs_preprocess.hip)
+    // ---- forward recompute in fp64: R and the sigmoid are the forward's own functions (gs_pergaussian.h); t and p are text (that header says why)
     const double m1 = a.means[3 * g], m2 = a.means[3 * g + 1], m3 = a.means[3 * g + 2];
     double t[4], p[4];
 #pragma unroll
@@ -37,9 +39,8 @@
     const double itz = 1.0 / tz, itz2 = itz * itz;
     const double J[2][3] = {{fx * itz, 0.0, -fx * tx * itz2}, {0.0, fy * itz, -fy * ty * itz2}};
     const double w = a.quats[4 * g], x = a.quats[4 * g + 1], y = a.quats[4 * g + 2], z = a.quats[4 * g + 3];
-    const double R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)},
-                           {2 * (x * y + w * z), 1 - 2 * (x * x - z * z), 2 * (y * z - w * x)},
-                           {2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)}};
+    double R[3][3];
+    gs_quat_to_rot(w, x, y, z, R);
     const double e[3] = {exp((double)a.scales[3 * g]), exp((double)a.scales[3 * g + 1]), exp((double)a.scales[3 * g + 2])};
     double Wm[3][3], Sg[3][3], A[2][3], ASg[2][3], cov[2][2];
 #pragma unroll
@@ -64,8 +65,7 @@
         for (int j = 0; j < 2; ++j) cov[i][j] = ASg[i][0] * A[j][0] + ASg[i][1] * A[j][1] + ASg[i][2] * A[j][2] + 0.3;
     const double idet = 1.0 / (cov[0][0] * cov[1][1] - cov[0][1] * cov[1][0]);
     const double M[2][2] = {{cov[1][1] * idet, -cov[0][1] * idet}, {-cov[1][0] * idet, cov[0][0] * idet}};
-    const double ez = exp((double)a.opac[g]);
-    const double sg = ez / (1.0 + ez);
+    const double sg = gs_sigmoid_logit<double>(a.opac[g]);
     gs_g2d_to_grads(g2, sg, M[0][0], 0.5 * (M[0][1] + M[1][0]), M[1][1]);
     const double gsig = g2[3], gmx = g2[4], gmy = g2[5];
     const double G[2][2] = {{g2[6], g2[7]}, {g2[8], g2[9]}};           // G[r][c] = dL/dM[r][c]
@@ -185,14 +185,14 @@
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const float v = live ? (float)(T[4 * j] * dt[0] + T[1 + 4 * j] * dt[1] + T[2 + 4 * j] * dt[2] + T[3 + 4 * j] * dt[3]) : 0.0f;
-            if (OVERWRITE) { if (GS_NT_STORES > 1) __builtin_nontemporal_store(v, &a.d_means[3 * g + j]); else a.d_means[3 * g + j] = v; } else a.d_means[3 * g + j] = acc_or_step(a.d_means[3 * g + j], v, a.sgd_scale);
+            grad_put<OVERWRITE>(&a.d_means[3 * g + j], v, a.sgd_scale);
         }
     }
     if (a.d_scales) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const float v = live ? (float)(de[j] * e[j]) : 0.0f;
-            if (OVERWRITE) { if (GS_NT_STORES > 1) __builtin_nontemporal_store(v, &a.d_scales[3 * g + j]); else a.d_scales[3 * g + j] = v; } else a.d_scales[3 * g + j] = acc_or_step(a.d_scales[3 * g + j], v, a.sgd_scale);
+            grad_put<OVERWRITE>(&a.d_scales[3 * g + j], v, a.sgd_scale);
         }
     }
     if (a.d_quats) {
@@ -203,6 +203,6 @@
     }
     if (a.d_opac) {
         const float v = live ? (float)(gsig * sg * (1.0 - sg)) : 0.0f;
-        if (OVERWRITE) { if (GS_NT_STORES > 1) __builtin_nontemporal_store(v, &a.d_opac[g]); else a.d_opac[g] = v; } else a.d_opac[g] = acc_or_step(a.d_opac[g], v, a.sgd_scale);
+        grad_put<OVERWRITE>(&a.d_opac[g], v, a.sgd_scale);
     }
     }

@@ -11,23 +11,10 @@
 // individually rounded in the reference's written order, so tile rectangles and depth keys
 // are bit-identical to the CPU oracle.  HBM-bound: 4*(11+3K) B read +
 // 60 B written per gaussian; no LDS, no MFMA.
-#include "gs_common.h"
-#include "gs_detmath.h"
+#include "gs_pergaussian.h"
 #include "gs_sh.h"
 
 #pragma clang fp contract(off)
-
-__device__ __forceinline__ int gs_tile_div(float v) {
-    // Julia div(v, 16f0) + saturation (see oracle gso_tile_rect): v is integer valued.
-    v = fminf(fmaxf(v, -1073741824.0f), 1073741824.0f);
-    return (int)v / GS_TILE;                       // C integer division truncates like div()
-}
-
-__device__ __forceinline__ uint32_t gs_pack_i16(float lo, float hi) {
-    int a = (int)fminf(fmaxf(lo, -32768.0f), 32767.0f);
-    int b = (int)fminf(fmaxf(hi, -32768.0f), 32767.0f);
-    return ((uint32_t)a & 0xFFFFu) | ((uint32_t)b << 16);
-}
 
 // DEG is the ACTIVE degree: the bands evaluated.  STRIDED: the model stores more bands than that (gs_set_active_sh_degree below the model's
 // degree) -- a row is sh_stride floats apart and its first 3 K are read, in the same order: the colour is what the model truncated to DEG gives.
@@ -36,9 +23,9 @@ __global__ __launch_bounds__(256) void gs_preprocess_kernel(GsPreprocessArgs a, 
     constexpr int K = (DEG + 1) * (DEG + 1);
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= a.n) return;
-    const float *T = cam.T, *P = cam.P;
 
     // ---- frustumCulling, projection.jl:46-93
+    const float *T = cam.T, *P = cam.P;
     const float m1 = a.means[3 * g], m2 = a.means[3 * g + 1], m3 = a.means[3 * g + 2];
     float ts[4], tps[4];
 #pragma unroll
@@ -69,17 +56,8 @@ __global__ __launch_bounds__(256) void gs_preprocess_kernel(GsPreprocessArgs a, 
     J[0][1] = 0.0f;        J[1][1] = cam.fy / tz;
     J[0][2] = -cam.fx * tx / (tz * tz);
     J[1][2] = -cam.fy * ty / (tz * tz);
-    const float qw = a.quats[4 * g], qx = a.quats[4 * g + 1], qy = a.quats[4 * g + 2], qz = a.quats[4 * g + 3];
     float R[3][3];                                                    // quatToRot, projection.jl:1-14
-    R[0][0] = 1.0f - 2.0f * (qy * qy + qz * qz);
-    R[1][0] = 2.0f * (qx * qy + qw * qz);
-    R[2][0] = 2.0f * (qx * qz - qw * qy);
-    R[0][1] = 2.0f * (qx * qy - qw * qz);
-    R[1][1] = 1.0f - 2.0f * (qx * qx - qz * qz);                      // :8 (minus, as written)
-    R[2][1] = 2.0f * (qy * qz + qw * qx);
-    R[0][2] = 2.0f * (qx * qz + qw * qy);
-    R[1][2] = 2.0f * (qy * qz - qw * qx);
-    R[2][2] = 1.0f - 2.0f * (qx * qx + qy * qy);
+    gs_quat_to_rot(a.quats[4 * g], a.quats[4 * g + 1], a.quats[4 * g + 2], a.quats[4 * g + 3], R);
     float S[3][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
     S[0][0] = gs_expf(a.scales[3 * g]);
     S[1][1] = gs_expf(a.scales[3 * g + 1]);
@@ -131,24 +109,10 @@ __global__ __launch_bounds__(256) void gs_preprocess_kernel(GsPreprocessArgs a, 
             s = s + JCR[i][2] * JR[j][2];
             c2[i][j] = (float)((double)s + 0.3);                      // :150 (+0.3 on all four, Float64)
         }
-    const float a0 = c2[0][0], a1 = c2[1][0], a2 = c2[0][1], a3 = c2[1][1];
-
-    // ---- computeInvCov2d, cov2d.jl:30-45
-    const float det = a0 * a3 - a2 * a1;
-    const float idet = 1.0f / det;
-    const float inv0 = a3 * idet, inv1 = -(a1 * idet), inv2 = -(a2 * idet), inv3 = a0 * idet;
-
-    // ---- computeBB, boundingbox.jl:19-27
-    const float halfad = (a0 + a3) / 2.0f;
-    const double disc = (double)(halfad * halfad - det);
-    const double sq = sqrt(gs_jlmax(0.1, disc));
-    const double e1 = (double)halfad - sq;
-    const double e2 = (double)halfad + sq;
-    const double r = ceil(3.0 * sqrt(gs_jlmax(e1, e2)));
-    const float bxmin = (float)gs_jlmax(1.0, floor(-r + (double)mux));
-    const float bxmax = (float)gs_jlmin((double)cam.W, ceil(r + (double)mux));
-    const float bymin = (float)gs_jlmax(1.0, floor(-r + (double)muy));
-    const float bymax = (float)gs_jlmin((double)cam.H, ceil(r + (double)muy));
+    GsSplatView sv;
+    sv.mux = mux; sv.muy = muy;
+    sv.cov[0] = c2[0][0]; sv.cov[1] = c2[1][0]; sv.cov[2] = c2[0][1]; sv.cov[3] = c2[1][1];
+    gs_conic_box(sv.cov, mux, muy, cam.W, cam.H, sv.inv, sv.bb);      // computeInvCov2d, computeBB
 
     // ---- sh2color, splat.jl:180-193 (degrees 2,3: build extension, same accumulation order)
     const float d0 = tps[0] - (cam.lookAt[0] - cam.eye[0]);
@@ -160,61 +124,22 @@ __global__ __launch_bounds__(256) void gs_preprocess_kernel(GsPreprocessArgs a, 
     const float X = x, Y = y, Z = z;
 #include "gs_sh_basis.inc"
     const float *sh = a.shs + (STRIDED ? (int64_t)sh_stride : (int64_t)3 * K) * g;
-    float rgb[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float s = sh[c] * bs[0];
 #pragma unroll
         for (int k = 1; k < K; ++k) s = s + sh[c + 3 * k] * bs[k];
-        rgb[c] = (float)((double)s + 0.5);                            // :192
+        sv.rgb[c] = (float)((double)s + 0.5);                            // :192
     }
-    // ---- cusigmoid, splat.jl:175-178
-    const float ez = gs_expf(a.opac[g]);
-    float sg = ez / (1.0f + ez);
+    sv.sig = gs_sigmoid_logit<float>(a.opac[g]);                      // cusigmoid, splat.jl:175-178
 
-    // ---- tile rectangle, binning.jl:6-27 (non-finite boxes: dropped)
-    const bool finite_bb = isfinite(bxmin) && isfinite(bxmax) && isfinite(bymin) && isfinite(bymax);
-    uint16_t rc[4] = {0, 0, 0, 0};
-    if (finite_bb) {
-        int bminx = gs_tile_div(floorf(bxmin)) + 1, bmaxx = gs_tile_div(ceilf(bxmax)) + 1;
-        int bminy = gs_tile_div(floorf(bymin)) + 1, bmaxy = gs_tile_div(ceilf(bymax)) + 1;
-        if (bminx <= bmaxx && bminy <= bmaxy) {
-            bminx = max(bminx, 1); bminy = max(bminy, 1);
-            bmaxx = min(bmaxx, a.gx); bmaxy = min(bmaxy, a.gy);
-            if (bminx <= bmaxx && bminy <= bmaxy) {
-                rc[0] = (uint16_t)bminx; rc[1] = (uint16_t)bmaxx; rc[2] = (uint16_t)bminy; rc[3] = (uint16_t)bmaxy;
-            }
-        }
-    }
-
-    // ---- depth key for sortperm(-tps[3,:], lt=isless), forward.jl:103
-    uint32_t key = 0u;
-    if (a.order != 0) {
-        const float v = (a.order == 1) ? -tps[2] : tps[2];
-        const uint32_t u = gs_f2u(v);
-        key = (v != v) ? 0xFFFFFFFFu : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-    }
-
-    // ---- payload.  The near/far skip of splat.jl:227 becomes an empty pixel box.  A splat whose
-    // per-view payload is not finite (degenerate covariance, NaN/Inf SH or opacity) is skipped the
-    // same way: the reference would write NaN into its pixel box, and its example scrubs those NaNs
-    // afterwards (examples/main.jl:35); the composite kernels mask arithmetically and could not keep
-    // a NaN inside the box.
-    GsPayload p;
+    // ---- payload, conic, tile rectangle; the near/far skip of splat.jl:227 becomes an empty pixel box
+    // (the rectangle is formed here, not where the box is: there the degree-3 kernel takes 101 VGPRs instead of 118 -- a fifth wave per SIMD --
+    // and the stage 0.073 instead of 0.070 ms at C3, profiles/pergaussian_once_ab.log)
+    gs_tile_rect(sv.bb, a.gx, a.gy, sv.rc);                           // binning.jl:6-27
+    const uint32_t key = gs_depth_key(tps[2], a.order);
     const bool depth_ok = !(tps[2] < cam.near_ || tps[2] > cam.far_);
-    const bool pay_ok = isfinite(rgb[0]) && isfinite(rgb[1]) && isfinite(rgb[2]) && isfinite(sg) && isfinite(mux) && isfinite(muy) &&
-                        isfinite(inv0) && isfinite(inv1) && isfinite(inv2) && isfinite(inv3);
-    p.mx = mux; p.my = muy; p.sig = sg;
-    // what the composite kernels' inner loops consume, formed once per (gaussian, view) instead of once per (tile, splat):
-    // alpha = exp2(ka dX^2 + kb dX dY + kc dY^2 + l2s)   (same single fp32 operations the staging lanes performed in rounds 1-2)
-    p.l2s = fminf(__builtin_amdgcn_logf(sg), GS_L2S_CAP);
-    p.ka = GS_NEG_HALF_LOG2E * inv0; p.kb = GS_NEG_HALF_LOG2E * (inv1 + inv2); p.kc = GS_NEG_HALF_LOG2E * inv3;
-    p.r = rgb[0]; p.g = rgb[1]; p.b = rgb[2];
-    if (finite_bb && depth_ok && pay_ok) { p.bbx = gs_pack_i16(bxmin, bxmax); p.bby = gs_pack_i16(bymin, bymax); }
-    else { p.bbx = 1u; p.bby = 1u; }                                   // min 1, max 0: empty
-    gs_payload_box_edges(p);
-    a.payload[g] = p;
-    reinterpret_cast<float4 *>(a.invcov)[g] = make_float4(inv0, inv1, inv2, inv3);
+    gs_store_splat(sv, g, depth_ok, a.payload, a.invcov, a.rect, a.dbg, a.dbg.ts != nullptr);
     a.depth_key[g] = key;
     if (a.key_range) {                                                  // the frame's key range, for the two-step depth sort (gs_sort.hip)
         uint32_t *lo = a.key_range + (size_t)(blockIdx.x % GS_KEY_RANGE_SLOTS) * GS_KEY_RANGE_STRIDE;
@@ -229,19 +154,13 @@ __global__ __launch_bounds__(256) void gs_preprocess_kernel(GsPreprocessArgs a, 
             if ((threadIdx.x & 63) == 0) { atomicMin(lo, mn); atomicMax(hi, mx); }
         } else if (finite) { atomicMin(lo, key); atomicMax(hi, key); }
     }
-    reinterpret_cast<uint2 *>(a.rect)[g] = make_uint2((uint32_t)rc[0] | ((uint32_t)rc[1] << 16),
-                                                       (uint32_t)rc[2] | ((uint32_t)rc[3] << 16));
     if (a.dbg.ts) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) { a.dbg.ts[4 * g + i] = ts[i]; a.dbg.tps[4 * g + i] = tps[i]; }
-        a.dbg.mu[2 * g] = mux; a.dbg.mu[2 * g + 1] = muy;
 #pragma unroll
         for (int j = 0; j < 3; ++j)
 #pragma unroll
             for (int i = 0; i < 3; ++i) a.dbg.cov3d[9 * g + i + 3 * j] = C3[i][j];
-        a.dbg.cov2d[4 * g] = a0; a.dbg.cov2d[4 * g + 1] = a1; a.dbg.cov2d[4 * g + 2] = a2; a.dbg.cov2d[4 * g + 3] = a3;
-        a.dbg.invcov[4 * g] = inv0; a.dbg.invcov[4 * g + 1] = inv1; a.dbg.invcov[4 * g + 2] = inv2; a.dbg.invcov[4 * g + 3] = inv3;
-        a.dbg.bbs[4 * g] = bxmin; a.dbg.bbs[4 * g + 1] = bymin; a.dbg.bbs[4 * g + 2] = bxmax; a.dbg.bbs[4 * g + 3] = bymax;
     }
 }
 

@@ -15,20 +15,9 @@
 //
 // Compiled with -ffp-contract=off: tile rectangles must be bit-identical to the CPU oracle.
 // HBM-bound: 36 B read + 60 B written per gaussian forward, 76 B read + 36 B written backward.
-#include "gs_common.h"
-#include "gs_detmath.h"
+#include "gs_pergaussian.h"
 
 #pragma clang fp contract(off)
-
-__device__ __forceinline__ int gs2_tile_div(float v) {
-    v = fminf(fmaxf(v, -1073741824.0f), 1073741824.0f);
-    return (int)v / GS_TILE;
-}
-__device__ __forceinline__ uint32_t gs2_pack_i16(float lo, float hi) {
-    const int a = (int)fminf(fmaxf(lo, -32768.0f), 32767.0f);
-    const int b = (int)fminf(fmaxf(hi, -32768.0f), 32767.0f);
-    return ((uint32_t)a & 0xFFFFu) | ((uint32_t)b << 16);
-}
 
 __global__ __launch_bounds__(256) void gs_preprocess2d_kernel(GsPreprocess2DArgs a) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -55,64 +44,24 @@ __global__ __launch_bounds__(256) void gs_preprocess2d_kernel(GsPreprocess2DArgs
             s = s + Wm[i][1] * Wm[j][1];
             Jm[i][j] = s;                                              // :19 J = W*W'
         }
-    const float a0 = (float)((double)Jm[0][0] + 0.3);                  // :25 (Float64 literal, diagonal only)
-    const float a1 = Jm[1][0], a2 = Jm[0][1];
-    const float a3 = (float)((double)Jm[1][1] + 0.3);                  // :26
-    // ---- computeInvCov2d, cov2d.jl:30-45
-    const float det = a0 * a3 - a2 * a1;
-    const float idet = 1.0f / det;
-    const float inv0 = a3 * idet, inv1 = -(a1 * idet), inv2 = -(a2 * idet), inv3 = a0 * idet;
+    GsSplatView sv;
+    sv.cov[0] = (float)((double)Jm[0][0] + 0.3);                       // :25 (Float64 literal, diagonal only)
+    sv.cov[1] = Jm[1][0]; sv.cov[2] = Jm[0][1];
+    sv.cov[3] = (float)((double)Jm[1][1] + 0.3);                       // :26
     // ---- pixel position, splat.jl:337-339
-    const float mux = (float)a.W * a.means[2 * g], muy = (float)a.H * a.means[2 * g + 1];
-    // ---- computeBB, boundingbox.jl:19-27
-    const float halfad = (a0 + a3) / 2.0f;
-    const double disc = (double)(halfad * halfad - det);
-    const double sq = sqrt(gs_jlmax(0.1, disc));
-    const double e1 = (double)halfad - sq, e2 = (double)halfad + sq;
-    const double r = ceil(3.0 * sqrt(gs_jlmax(e1, e2)));
-    const float bxmin = (float)gs_jlmax(1.0, floor(-r + (double)mux));
-    const float bxmax = (float)gs_jlmin((double)a.W, ceil(r + (double)mux));
-    const float bymin = (float)gs_jlmax(1.0, floor(-r + (double)muy));
-    const float bymax = (float)gs_jlmin((double)a.H, ceil(r + (double)muy));
-    // ---- tile rectangle, binning.jl:6-27 (non-finite boxes: dropped, as in the 3-D path)
-    const bool finite_bb = isfinite(bxmin) && isfinite(bxmax) && isfinite(bymin) && isfinite(bymax);
-    uint16_t rc[4] = {0, 0, 0, 0};
-    if (finite_bb) {
-        int bminx = gs2_tile_div(floorf(bxmin)) + 1, bmaxx = gs2_tile_div(ceilf(bxmax)) + 1;
-        int bminy = gs2_tile_div(floorf(bymin)) + 1, bmaxy = gs2_tile_div(ceilf(bymax)) + 1;
-        if (bminx <= bmaxx && bminy <= bmaxy) {
-            bminx = max(bminx, 1); bminy = max(bminy, 1);
-            bmaxx = min(bmaxx, a.gx); bmaxy = min(bmaxy, a.gy);
-            if (bminx <= bmaxx && bminy <= bmaxy) {
-                rc[0] = (uint16_t)bminx; rc[1] = (uint16_t)bmaxx; rc[2] = (uint16_t)bminy; rc[3] = (uint16_t)bmaxy;
-            }
-        }
-    }
+    sv.mux = (float)a.W * a.means[2 * g]; sv.muy = (float)a.H * a.means[2 * g + 1];
+    gs_conic_box(sv.cov, sv.mux, sv.muy, a.W, a.H, sv.inv, sv.bb);     // computeInvCov2d, computeBB
+    gs_tile_rect(sv.bb, a.gx, a.gy, sv.rc);                            // binning.jl:6-27
     // raw opacity (splat.jl:341) clamped to [0, 1): alpha must stay below 1 for the adjoint's 1/(1-alpha); NaN -> 0
-    const float sg = fminf(fmaxf(a.opac[g], 0.0f), 0.99999994f);
-    const float cr = a.colors[3 * g], cg = a.colors[3 * g + 1], cb = a.colors[3 * g + 2];
-    GsPayload p;
-    const bool pay_ok = isfinite(cr) && isfinite(cg) && isfinite(cb) && isfinite(sg) && isfinite(mux) && isfinite(muy) &&
-                        isfinite(inv0) && isfinite(inv1) && isfinite(inv2) && isfinite(inv3);
-    p.mx = mux; p.my = muy; p.sig = sg;
-    p.l2s = fminf(__builtin_amdgcn_logf(sg), GS_L2S_CAP);             // log2; sg == 0 gives -inf: alpha = exp2(-inf) = 0
-    p.ka = GS_NEG_HALF_LOG2E * inv0; p.kb = GS_NEG_HALF_LOG2E * (inv1 + inv2); p.kc = GS_NEG_HALF_LOG2E * inv3;
-    p.r = cr; p.g = cg; p.b = cb;
-    if (finite_bb && pay_ok) { p.bbx = gs2_pack_i16(bxmin, bxmax); p.bby = gs2_pack_i16(bymin, bymax); }
-    else { p.bbx = 1u; p.bby = 1u; }                                   // min 1, max 0: empty
-    gs_payload_box_edges(p);
-    a.payload[g] = p;
-    reinterpret_cast<float4 *>(a.invcov)[g] = make_float4(inv0, inv1, inv2, inv3);
+    sv.sig = fminf(fmaxf(a.opac[g], 0.0f), 0.99999994f);
+    sv.rgb[0] = a.colors[3 * g]; sv.rgb[1] = a.colors[3 * g + 1]; sv.rgb[2] = a.colors[3 * g + 2];
+    gs_store_splat(sv, g, true, a.payload, a.invcov, a.rect, a.dbg, a.dbg.mu != nullptr);
     a.depth_key[g] = 0u;                                               // no depth: lists are in gaussian-index order
-    reinterpret_cast<uint2 *>(a.rect)[g] = make_uint2((uint32_t)rc[0] | ((uint32_t)rc[1] << 16),
-                                                       (uint32_t)rc[2] | ((uint32_t)rc[3] << 16));
-    if (a.dbg.mu) {
-        a.dbg.mu[2 * g] = mux; a.dbg.mu[2 * g + 1] = muy;
-        a.dbg.cov2d[4 * g] = a0; a.dbg.cov2d[4 * g + 1] = a1; a.dbg.cov2d[4 * g + 2] = a2; a.dbg.cov2d[4 * g + 3] = a3;
-        a.dbg.invcov[4 * g] = inv0; a.dbg.invcov[4 * g + 1] = inv1; a.dbg.invcov[4 * g + 2] = inv2; a.dbg.invcov[4 * g + 3] = inv3;
-        a.dbg.bbs[4 * g] = bxmin; a.dbg.bbs[4 * g + 1] = bymin; a.dbg.bbs[4 * g + 2] = bxmax; a.dbg.bbs[4 * g + 3] = bymax;
-    }
 }
+
+// accumulate (+=) or overwrite
+template <bool OVERWRITE>
+__device__ __forceinline__ void put(float *p, float v) { if (OVERWRITE) *p = v; else *p += v; }
 
 // d{rgb3, sig, mu2, inv4} -> d{means2, scales2, rotation, opacity, colors3}; accumulate (+=) or overwrite.
 template <bool OVERWRITE>
@@ -120,13 +69,7 @@ __global__ __launch_bounds__(256) void gs_preprocess2d_bwd_kernel(GsPreprocess2D
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= a.n) return;
     float g2[10];
-    if (a.g2d_fixed) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) g2[i] = (float)((double)a.g2d_fixed[GS_G2D_STRIDE * g + i] * gs_fixed_inv(i));
-    } else {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) g2[i] = a.g2d[GS_G2D_STRIDE * g + i];
-    }
+    gs_g2d_row_load(a, g, g2);
     // forward pieces again (cheaper than storing them): Sigma = Wm Wm' + 0.3 I, M = Sigma^-1
     float sn, cs;
     gs_sincosf(a.rots[g], sn, cs);
@@ -167,20 +110,14 @@ __global__ __launch_bounds__(256) void gs_preprocess2d_bwd_kernel(GsPreprocess2D
         ds[j] = de * e[j];
     }
     const float dm0 = (float)a.W * g2[4], dm1 = (float)a.H * g2[5];
-    if (a.d_means) {
-        if (OVERWRITE) { a.d_means[2 * g] = dm0; a.d_means[2 * g + 1] = dm1; }
-        else { a.d_means[2 * g] += dm0; a.d_means[2 * g + 1] += dm1; }
-    }
-    if (a.d_scales) {
-        if (OVERWRITE) { a.d_scales[2 * g] = ds[0]; a.d_scales[2 * g + 1] = ds[1]; }
-        else { a.d_scales[2 * g] += ds[0]; a.d_scales[2 * g + 1] += ds[1]; }
-    }
-    if (a.d_rots) { if (OVERWRITE) a.d_rots[g] = dth; else a.d_rots[g] += dth; }
+    if (a.d_means) { put<OVERWRITE>(a.d_means + 2 * g, dm0); put<OVERWRITE>(a.d_means + 2 * g + 1, dm1); }
+    if (a.d_scales) { put<OVERWRITE>(a.d_scales + 2 * g, ds[0]); put<OVERWRITE>(a.d_scales + 2 * g + 1, ds[1]); }
+    if (a.d_rots) put<OVERWRITE>(a.d_rots + g, dth);
     const float dop = (op > 0.0f && op < 0.99999994f) ? g2[3] : 0.0f;       // the clamp of the forward has zero slope outside
-    if (a.d_opac) { if (OVERWRITE) a.d_opac[g] = dop; else a.d_opac[g] += dop; }
+    if (a.d_opac) put<OVERWRITE>(a.d_opac + g, dop);
     if (a.d_colors) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { if (OVERWRITE) a.d_colors[3 * g + k] = g2[k]; else a.d_colors[3 * g + k] += g2[k]; }
+        for (int k = 0; k < 3; ++k) put<OVERWRITE>(a.d_colors + 3 * g + k, g2[k]);
     }
 }
 

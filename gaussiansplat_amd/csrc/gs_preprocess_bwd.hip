@@ -23,25 +23,13 @@
 // Splitting keeps both under 128 VGPRs (the fused version needed 168 + spills).
 // `overwrite` stores instead of accumulating: used for the first backward after resetGrads, so
 // the reset needs no 4(11+3K)-byte/gaussian zero fill and this pass no read of the old gradients.
-#include "gs_common.h"
+#include "gs_pergaussian.h"  // quatToRot and the sigmoid as the forward has them, the row of 2-D gradient sums (gs_g2d_row_load)
 #include "gs_sh.h"            // SH_C0 / SH_C1 / bC2 / bC3, gs_sh_dispatch, the strided rows
 #include <stdlib.h>
 
 #ifndef GS_NT_STORES
 #define GS_NT_STORES 2               // overwrite-mode gradient stores bypass the caches: 1 the SH gradients, 2 the geometry chain's too (0: A/B builds)
 #endif
-// 2-D gradient row of gaussian g: float atomics buffer, or the deterministic fixed-point buffer
-__device__ __forceinline__ void load_g2(const GsPreprocessBwdArgs &a, int64_t g, float (&o)[10]) {
-    if (a.g2d_fixed) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) o[i] = (float)((double)a.g2d_fixed[GS_G2D_STRIDE * g + i] * gs_fixed_inv(i));
-    } else {                                                           // one 64-byte row: three 16-byte loads
-        const float4 *r = reinterpret_cast<const float4 *>(a.g2d + GS_G2D_STRIDE * g);
-        const float4 v0 = r[0], v1 = r[1], v2 = r[2];
-        o[0] = v0.x; o[1] = v0.y; o[2] = v0.z; o[3] = v0.w; o[4] = v1.x; o[5] = v1.y; o[6] = v1.z; o[7] = v1.w; o[8] = v2.x; o[9] = v2.y;
-    }
-}
-
 // old + v as one rounded add that the compiler may not fuse with the products v came from: the accumulating and the
 // overwriting instantiation must produce the SAME v (accumulating eight views == the sum of eight single-view gradients)
 __device__ __forceinline__ float add_exact(float old, float v) {
@@ -51,6 +39,12 @@ __device__ __forceinline__ float add_exact(float old, float v) {
 // accumulate, or (sgd_scale != 0) apply the step: the same fma gs_sgd_step would do on the stored float gradient
 __device__ __forceinline__ float acc_or_step(float old, float v, float sgd_scale) {
     return sgd_scale != 0.0f ? fmaf(sgd_scale, v, old) : add_exact(old, v);
+}
+// one geometry gradient to its place: stored past the caches (overwriting), or accumulated / stepped
+template <bool OVERWRITE>
+__device__ __forceinline__ void grad_put(float *dst, float v, float sgd_scale) {
+    if (OVERWRITE) { if (GS_NT_STORES > 1) __builtin_nontemporal_store(v, dst); else *dst = v; }
+    else *dst = acc_or_step(*dst, v, sgd_scale);
 }
 
 // FUSED: the geometry chain of the gaussian follows in the same thread (gs_backward's usual case: both phases) -- its row of 2-D gradients
@@ -86,7 +80,7 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
     if (SKIP) {
         const int64_t g0 = gb + threadIdx.x;
         bool lv = false;
-        if (g0 < a.n) { load_g2(a, g0, g2); lv = g2[0] != 0.0f || g2[1] != 0.0f || g2[2] != 0.0f; }
+        if (g0 < a.n) { gs_g2d_row_load(a, g0, g2); lv = g2[0] != 0.0f || g2[1] != 0.0f || g2[2] != 0.0f; }
         srow_live[threadIdx.x] = lv ? 1 : 0;
         __syncthreads();
     }
@@ -97,7 +91,7 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
     const bool vec_out = vec_rows && (reinterpret_cast<uintptr_t>(a.d_shs) & 15) == 0;   // e.g. a flat buffer slice at 44 n bytes
     const int64_t g = gb + threadIdx.x;
     if (g < a.n) {
-        if (!SKIP) load_g2(a, g, g2);
+        if (!SKIP) gs_g2d_row_load(a, g, g2);
         // a gaussian no pixel touched (off screen, or skipped by the composite because its per-view payload is not finite:
         // tz == 0, exp(scale) overflow, singular covariance) has an all-zero row: its gradient is exactly zero, and the
         // recomputed direction may be NaN, so zeros are substituted for the basis instead of forming 0 * NaN
@@ -105,7 +99,7 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
         const float grgb[3] = {g2[0], g2[1], g2[2]};
         const float *T = cam.T, *P = cam.P;
         const float m1 = a.means[3 * g], m2 = a.means[3 * g + 1], m3 = a.means[3 * g + 2];
-        float t[4], p[4];
+        float t[4], p[4];                                               // (text, not a function: gs_pergaussian.h says why)
 #pragma unroll
         for (int i = 0; i < 4; ++i) t[i] = T[i] * m1 + T[i + 4] * m2 + T[i + 8] * m3 + T[i + 12];
 #pragma unroll
@@ -280,7 +274,7 @@ __global__ __launch_bounds__(256) void gs_geom_bwd_kernel(GsPreprocessBwdArgs a,
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= a.n) return;
     float g2f[10];
-    load_g2(a, g, g2f);                                  // colour gradient + raw moments (gs_common.h: gs_g2d_to_grads)
+    gs_g2d_row_load(a, g, g2f);         // colour gradient + raw moments (gs_common.h: gs_g2d_to_grads)
 #define GS_GEOM_DPC (reinterpret_cast<const float4 *>(a.dpc)[g])
     do {
 #include "gs_geom_bwd_body.inc"
@@ -298,7 +292,8 @@ __global__ __launch_bounds__(256) void gs_pack_drgb_kernel(const float *__restri
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // over 3n
     if (i >= 3 * n) return;
     const int64_t g = i / 3; const int c = (int)(i - 3 * g);
-    out[i] = g2d_fixed ? (float)((double)g2d_fixed[GS_G2D_STRIDE * g + c] * GS_FIXED_INV) : g2d[GS_G2D_STRIDE * g + c];
+    __builtin_assume(c < 3);                                               // (one fixed-point scale for the three: no select)
+    out[i] = gs_g2d_load(GsG2dRows{g2d, g2d_fixed}, g, c);
 }
 
 // cams: nviews records of 38 floats {T[16], P[16], eye[3], lookAt[3]}; drgb: [nviews][3n]; the direction and the

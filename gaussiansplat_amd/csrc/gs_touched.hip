@@ -22,7 +22,7 @@
 // (gs_touched_count_kernel: popcounts per (view, chunk); gs_touched_scan_kernel, one workgroup per view) makes the offsets.
 // Nothing is read outside a view's rows_cap rows whatever the bitmap says: bits at positions >= n belong to no thread, and a
 // rank >= rows_cap (a corrupt or truncated gather) reads as a zero row.
-#include "gs_common.h"
+#include "gs_pergaussian.h"   // gs_g2d_rgb_load; gs_sh_views_body.inc keeps its own t and p (this unit contracts, and both kernels share that body)
 #include "gs_sh.h"
 
 static_assert(GS_TOUCHED_CHUNK == 256, "one workgroup of 256 threads (four ballots, eight bitmap words) per chunk");
@@ -36,10 +36,9 @@ struct GsColorRowSrc {
 template <int SRC>
 __device__ __forceinline__ void load_row(const GsColorRowSrc &s, int64_t g, float &a, float &b, float &c) {
     if constexpr (SRC == 0) { const float *p = s.dense + 3 * g; a = p[0]; b = p[1]; c = p[2]; }
-    else if constexpr (SRC == 1) { const float *p = s.g2d + GS_G2D_STRIDE * g; a = p[0]; b = p[1]; c = p[2]; }
     else {
-        const long long *p = s.g2d_fixed + GS_G2D_STRIDE * g;
-        a = (float)((double)p[0] * GS_FIXED_INV); b = (float)((double)p[1] * GS_FIXED_INV); c = (float)((double)p[2] * GS_FIXED_INV);
+        __builtin_assume(SRC != 2 || s.g2d_fixed != nullptr);              // (SRC is the launcher's reading of these pointers)
+        gs_g2d_rgb_load(GsG2dRows{s.g2d, SRC == 2 ? s.g2d_fixed : nullptr}, g, a, b, c);
     }
 }
 __device__ __forceinline__ bool touched3(float a, float b, float c) {

@@ -8,7 +8,7 @@ for rep in 1 2 3; do
     lib=$PWD/gaussiansplat_amd/$d/libgsplat_hip.so
     for c in $CFGS; do
       GSPLAT_HIP_LIB=$lib timeout -k 10 200 python3 bench.py --full --config $c --steps 20 --warmup 5 --no-cpu-baseline --no-literal --no-train-iteration --no-c4-anchor $AB_FLAGS 2>/dev/null | tail -1 | \
-        python3 -c "import json,sys; d=json.loads(sys.stdin.read()); s=d['stage_ms']; print('%-10s' % '$d', '$c', 'ms/frame %.4f' % d['ms_per_step'], 'fwd %.4f bwd %.4f depth_sort %.4f lists %.4f' % (s['composite_fwd'], s['composite_bwd'], s['depth_sort'], s['tile_sort']))"
+        python3 -c "import json,sys; d=json.loads(sys.stdin.read()); s=d['stage_ms']; print('%-10s' % '$d', '$c', 'ms/frame %.4f' % d['ms_per_step'], 'fwd %.4f bwd %.4f depth_sort %.4f lists %.4f preprocess %.4f preprocess_bwd %.4f' % (s['composite_fwd'], s['composite_bwd'], s['depth_sort'], s['tile_sort'], s.get('preprocess', 0.0), s.get('preprocess_bwd', 0.0)))"
     done
   done
 done

@@ -1,11 +1,11 @@
 #!/bin/bash
 # Same-box A/B against an earlier commit's kernels:  tools/build_old_lib.sh COMMIT [TAG=old]  ->  gaussiansplat_amd/lib_TAG/libgsplat_hip.so
-# built from that commit's csrc/ + include/ with the flags of gaussiansplat_amd/build.py; ABI functions added since (the ctypes binding
+# built from that commit's csrc/ + include/, every file with the flags that commit's own gaussiansplat_amd/build.py gives it (SOURCES); ABI functions added since (the ctypes binding
 # refuses a library without them) get a stub.  Then: GSPLAT_HIP_LIB=$PWD/gaussiansplat_amd/lib_TAG/libgsplat_hip.so python3 bench.py ...
 set -e -o pipefail
 C=$1; TAG=${2:-old}
 W=$(mktemp -d)
-git archive "$C" gaussiansplat_amd/csrc include | tar -x -C "$W"
+git archive "$C" gaussiansplat_amd/csrc gaussiansplat_amd/build.py include | tar -x -C "$W"
 OUT=$PWD/gaussiansplat_amd/lib_$TAG; mkdir -p "$OUT"
 grep -q gs_get_bin_path "$W/include/gsplat.h" || echo 'extern "C" int gs_get_bin_path(gs_ctx *c) { return c ? 0 : -1; }' >> "$W/gaussiansplat_amd/csrc/gs_api_debug.hip"
 grep -q gs_adam_step "$W/include/gsplat.h" || cat >> "$W/gaussiansplat_amd/csrc/gs_api_debug.hip" <<'STUB'
@@ -21,8 +21,8 @@ extern "C" int gs_opacity_reset(gs_ctx *, float, float *, float *) { return GS_E
 STUB
 objs=()
 for s in "$W"/gaussiansplat_amd/csrc/*.hip; do
-  b=$(basename "$s" .hip); extra=""
-  case $b in gs_preprocess|gs_preprocess2d|gs_adam) extra="-ffp-contract=off";; gs_composite|gs_loss) extra="-fno-slp-vectorize";; esac
+  b=$(basename "$s" .hip)
+  extra=$(python3 -c 'import importlib.util as u, sys; s = u.spec_from_file_location("b", sys.argv[1]); m = u.module_from_spec(s); s.loader.exec_module(m); print(" ".join(m.SOURCES[sys.argv[2]]))' "$W/gaussiansplat_amd/build.py" "$b.hip")
   /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wno-unused-function $extra -c "$s" -o "$OUT/$b.o" &
   objs+=("$OUT/$b.o")
 done

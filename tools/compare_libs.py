@@ -11,7 +11,10 @@ Fixed seeds; every ctx whose gradients are recorded is deterministic (fixed-poin
 record no gradients (C1_small_float_atomics; tile_clock: counts only), so every array must be EQUAL.  Arrays above 4096 elements are kept as a
 blake2b digest of their bytes.  A call the library refuses is recorded with its message: the refusal must be alike on both sides.
 Per frame: image, T, the five gradient arrays, tile ranges, sorted ids, sortIdxs, num_instances / _coarse_instances / _rounds,
-bin_path_of_frame, list_stats, work_counters_ex; and the counting words of the composite kernels' debug record on one small frame."""
+bin_path_of_frame, list_stats, work_counters_ex; and the counting words of the composite kernels' debug record on one small frame.
+The per-gaussian kernels beyond a frame: a density cycle (statistics, actions, plan, the restructured model and one moment set), the
+touched-rows pack of two views and the SH gradients rebuilt from them, one fused backward + Adam step dense and selective (parameters
+and moments), and a frame at active SH degree 1 of a stored degree 3."""
 import csv, glob, hashlib, os, subprocess, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -187,6 +190,139 @@ def case_tile_clock(R):
     ctx.close()
 
 
+def small_scene(n, deg, seed):
+    """n gaussians of SH degree `deg` on a C1-sized image, the model in caller-owned device arrays (so that a step or a restructure can be read back)"""
+    import torch
+    from gaussiansplat_amd import synthetic
+    W = H = 256
+    sc = synthetic.make_scene(n, W, H, deg, seed=seed)
+    model = [torch.as_tensor(np.ascontiguousarray(sc[k], np.float32).reshape(n, -1)).cuda() for k in ("means", "scales", "quats", "opacities", "shs")]
+    return model, W, H
+
+
+def device_ctx(model, n, deg, W, H, view=0, **kw):
+    from gaussiansplat_amd import backend as B
+    ctx = B.Context(deterministic=True, **kw)
+    ctx.set_model_device(n, deg, [t.data_ptr() for t in model])
+    set_cam(ctx, W, H, view)
+    return ctx
+
+
+def host(ts):
+    import torch
+    torch.cuda.synchronize()
+    return {("means", "scales", "quats", "opacities", "shs")[i]: t.cpu().numpy() for i, t in enumerate(ts)}
+
+
+def case_density(R):
+    """One density cycle at n = 1000: accumulate, decide, plan, restructure with clones and splits, one moment set"""
+    import torch
+    from gaussiansplat_amd import backend as B, synthetic
+    from gaussiansplat_amd.density import density_params
+    n, deg = 1000, 1
+    model, W, H = small_scene(n, deg, 501)
+    ctx = device_ctx(model, n, deg, W, H)
+    ctx.preprocess(); ctx.bin(); ctx.forward_host()
+    ctx.backward(synthetic.make_dC(W, H, 502), ctx.grads_alloc(), overwrite=True)
+    gs, cnt, ext = torch.zeros(n, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda")
+    st = B.GsDensityStats(gs.data_ptr(), cnt.data_ptr(), ext.data_ptr())
+    ctx.density_accumulate(st)
+    action = torch.zeros(n, dtype=torch.int32, device="cuda")
+    gsum = np.sort(gs.cpu().numpy())
+    # thresholds from the recorded statistics themselves: the upper half densifies, and the median scale parts clones from splits
+    smax = float(np.median(model[1].cpu().numpy().max(axis=1)))
+    par = density_params(scene_extent=float(np.exp(smax)) / 0.01, grad_threshold=float(gsum[n // 2]), percent_dense=0.01, min_opacity=0.2,
+                         max_world_fraction=None)
+    ctx.density_decide(st, par, action.data_ptr())
+    plan = ctx.density_plan(action.data_ptr())
+    assert plan[1] > 0 and plan[2] > 0 and plan[3] > 0, ("density: the cycle needs clones, splits and pruned rows", plan)
+    no = plan[0] + plan[1] + 2 * plan[2]
+    g = torch.Generator("cuda").manual_seed(503)
+    noise = torch.randn((n, 2, 3), device="cuda", generator=g)
+    moments = [torch.randn(t.shape, device="cuda", generator=g) for t in model]
+    dst = [torch.full((no, t.shape[1]), 7.0, device="cuda") for t in model]
+    dst_m = [torch.full((no, t.shape[1]), 7.0, device="cuda") for t in model]
+    G = lambda ts: B.GsGrads(*[t.data_ptr() for t in ts])
+    ctx.density_restructure(action.data_ptr(), noise.data_ptr(), G(dst), [G(moments)], [G(dst_m)], no)
+    ctx.synchronize()
+    R.put("density/grad_sum", gs.cpu().numpy()); R.put("density/count", cnt.cpu().numpy()); R.put("density/max_extent", ext.cpu().numpy())
+    R.put("density/action", action.cpu().numpy()); R.put("density/plan", plan)
+    for k, v in host(dst).items():
+        R.put("density/model." + k, v)
+    for k, v in host(dst_m).items():
+        R.put("density/moments." + k, v)
+    ctx.close()
+
+
+def case_touched(R):
+    """color_rows_pack of two views' own gradient sums, then sh_grads_from_touched on the gathered pair, n = 1000"""
+    import torch
+    from gaussiansplat_amd import camera as gcam, synthetic
+    n, deg, V = 1000, 3, 2
+    model, W, H = small_scene(n, deg, 511)
+    words = (n + 31) // 32
+    bits = torch.zeros((V, words), dtype=torch.int32, device="cuda")
+    rows = torch.zeros((V, n, 3), device="cuda")
+    count = torch.zeros(V, dtype=torch.int64, device="cuda")
+    recs = []
+    for v in range(V):
+        ctx = device_ctx(model, n, deg, W, H, view=v)
+        ctx.preprocess(); ctx.bin(); ctx.forward_host()
+        ctx.backward(synthetic.make_dC(W, H, 512 + v), ctx.grads_alloc(), overwrite=True)
+        ctx.color_rows_pack(None, n, bits[v].data_ptr(), rows[v].data_ptr(), count[v:].data_ptr())
+        ctx.synchronize()
+        cam = synthetic.scene_camera(W, view=v)
+        recs.append(np.concatenate([gcam.compute_transform(cam), gcam.compute_projection(cam, W, H), cam.eye, cam.lookAt]).astype(np.float32))
+        if v + 1 < V:
+            ctx.close()
+    assert 0 < int(count.min()) and int(count.max()) < n, ("touched: both views must touch some rows and not all", count)
+    d_shs = torch.full((n, 3 * (deg + 1) ** 2), 7.0, device="cuda")
+    ctx.sh_grads_from_touched(np.stack(recs), bits.data_ptr(), rows.data_ptr(), n, d_shs.data_ptr(), overwrite=True)
+    ctx.synchronize()
+    R.put("touched/bits", bits.cpu().numpy()); R.put("touched/count", count.cpu().numpy())
+    R.put("touched/rows", rows.cpu().numpy()); R.put("touched/d_shs", d_shs.cpu().numpy())
+    ctx.close()
+
+
+def case_adam(R):
+    """One backward_adam step, dense and selective, n = 1000 at SH degree 3: parameters and both moments afterwards"""
+    import torch
+    from gaussiansplat_amd import backend as B, synthetic
+    n, deg = 1000, 3
+    for selective in (False, True):
+        model, W, H = small_scene(n, deg, 521)
+        before = host(model)
+        g = torch.Generator("cuda").manual_seed(522)
+        m = [0.01 * torch.randn(t.shape, device="cuda", generator=g) for t in model]
+        v = [1e-4 * torch.rand(t.shape, device="cuda", generator=g) for t in model]
+        dC = torch.as_tensor(synthetic.make_dC(W, H, 523)).cuda()
+        ctx = device_ctx(model, n, deg, W, H)
+        ctx.preprocess(); ctx.bin(); ctx.forward_host()
+        G = lambda ts: B.GsGrads(*[t.data_ptr() for t in ts])
+        ctx.backward_adam(dC.data_ptr(), G(m), G(v), [1.6e-4, 5e-3, 1e-3, 5e-2, 2.5e-3, 1.25e-4], 0.9, 0.999, 1e-15, 3, selective=selective)
+        ctx.synchronize()
+        tag = "adam_selective" if selective else "adam_dense"
+        after = host(model)
+        assert any(not np.array_equal(after[k], before[k]) for k in after), "adam: the step moved nothing"
+        for name, ts in (("p", model), ("m", m), ("v", v)):
+            for k, a in host(ts).items():
+                R.put("%s/%s.%s" % (tag, name, k), a)
+        ctx.close()
+
+
+def case_active_degree(R):
+    """One frame at active degree 1 of a stored degree 3 (the strided instantiations): image, T, gradients"""
+    from gaussiansplat_amd import backend as B, synthetic
+    sc, n, W, H, deg = scene("C2", 20000)
+    ctx = B.Context(deterministic=True)
+    set_model(ctx, sc, n, deg)
+    ctx.set_active_sh_degree(1)
+    set_cam(ctx, W, H, 0)
+    g = ctx.grads_alloc()
+    frame(R, "active_degree_1_of_3/f0", ctx, synthetic.make_dC(W, H, 1), g, lambda gg: ctx.grads_read(gg, deg))
+    ctx.close()
+
+
 def record(path):
     from gaussiansplat_amd import backend as B
     R = Recorder()
@@ -213,6 +349,10 @@ def record(path):
     case_2d(R)
     case_empty(R)
     case_tile_clock(R)
+    case_density(R)
+    case_touched(R)
+    case_adam(R)
+    case_active_degree(R)
     np.savez(path, **R.out)
     print("recorded %d arrays -> %s" % (len(R.out), path))
 
