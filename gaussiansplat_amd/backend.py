@@ -31,7 +31,8 @@ SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs
            "gs_debug_tile_clock", "gs_debug_clock_mhz", "gs_rank_probe_result", "gs_num_rounds", "gs_set_view_slot", "gs_num_coarse_instances",
            "gs_get_list_stats", "gs_get_tile_parts", "gs_get_bin_path", "gs_debug_set_window", "gs_debug_tile_clock_rows", "gs_debug_tail_fill",
            "gs_adam_step", "gs_backward_adam",
-           "gs_density_accumulate", "gs_density_decide", "gs_density_plan", "gs_density_restructure", "gs_opacity_reset")
+           "gs_density_accumulate", "gs_density_decide", "gs_density_plan", "gs_density_restructure", "gs_opacity_reset",
+           "gs_knn_mean_dist2", "gs_init_from_points")
 
 GS_ABI_VERSION = 3          # include/gsplat.h; load() refuses a library that reports another version
 GS_DEBUG_WIDE_CURSORS = 1
@@ -44,6 +45,7 @@ GS_MAX_VIEW_SLOTS = 4096
 GS_ADAM_GROUPS = 6            # lr[0] means, [1] scales, [2] quaternions, [3] opacities, [4] SH band 0, [5] SH bands >= 1
 GS_ADAM_SELECTIVE = 1         # step only the gaussians with a non-zero gradient float ("selective Adam")
 GS_ERR_INVALID, GS_ERR_UNSUPPORTED = -1, -5
+KNN_BOX = 64                  # points per box of the 3-NN search (GS_KNN_BOX in csrc/gs_knn.h; tests pick their sizes around it)
 TOUCHED_CHUNK = 256           # gaussians per workgroup of the touched-rows pack (GS_TOUCHED_CHUNK in csrc/gs_common.h; tests pick their sizes around it)
 
 
@@ -160,6 +162,8 @@ def load():
     L.gs_density_plan.argtypes = [vp, vp, C.POINTER(C.c_int64)]
     L.gs_density_restructure.argtypes = [vp, vp, vp, G, C.c_int32, G, G, C.c_int64]
     L.gs_opacity_reset.argtypes = [vp, C.c_float, vp, vp]
+    L.gs_knn_mean_dist2.argtypes = [vp, vp, C.c_int64, vp]
+    L.gs_init_from_points.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int, C.c_float, G]
     if L.gs_abi_version() != GS_ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH} has ABI version {L.gs_abi_version()}, this binding is written for {GS_ABI_VERSION}: "
                            "rebuild with `python -m gaussiansplat_amd.build --force`")
@@ -481,6 +485,19 @@ class Context:
     def opacity_reset(self, max_logit: float, m_opac_ptr: int = 0, v_opac_ptr: int = 0):
         """gs_opacity_reset: opacity = min(opacity, max_logit) on the resident model (NaN stays), +0 into the two moment arrays."""
         self._chk(self.L.gs_opacity_reset(self.h, C.c_float(max_logit), C.c_void_p(int(m_opac_ptr or 0)), C.c_void_p(int(v_opac_ptr or 0))))
+
+    # -- point-cloud initialisation: needs no model, camera or frame, and leaves the ctx's frame as it is
+    def knn_mean_dist2(self, points_ptr: int, n: int, dist2_ptr: int):
+        """gs_knn_mean_dist2: dist2[i] = the mean of the three smallest squared distances from point i to the other finite points (exact:
+        bit for bit a brute force).  points: 3 x n device floats, dist2: n device floats.  No sync."""
+        self._chk(self.L.gs_knn_mean_dist2(self.h, C.c_void_p(int(points_ptr or 0)), C.c_int64(int(n)), C.c_void_p(int(dist2_ptr or 0))))
+
+    def init_from_points(self, points_ptr: int, colors_ptr: "int | None", dist2_ptr: int, n: int, sh_degree: int, opacity_logit: float,
+                         dst_model: GsGrads):
+        """gs_init_from_points: the model a training run starts from, into dst_model (five device arrays of n rows).  colors_ptr None / 0:
+        grey.  The ctx's model is not switched.  No sync."""
+        self._chk(self.L.gs_init_from_points(self.h, C.c_void_p(int(points_ptr or 0)), C.c_void_p(int(colors_ptr or 0)), C.c_void_p(int(dist2_ptr or 0)),
+                                             C.c_int64(int(n)), C.c_int(int(sh_degree)), C.c_float(opacity_logit), C.byref(dst_model)))
 
     def reset_grads(self, grads: GsGrads):
         self._chk(self.L.gs_reset_grads(self.h, C.byref(grads)))

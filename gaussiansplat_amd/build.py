@@ -49,6 +49,9 @@ SOURCES = {
     "gs_api_density.hip": ["-ffp-contract=off"],
     # background colour: blend and target compositor are specified as single fp32 operations (NumPy float32 matches bit for bit)
     "gs_background.hip": ["-ffp-contract=off"],
+    # point-cloud initialisation: d2, the box bound and the mean are specified operation by operation (tests/knn_ref.py matches bit for bit)
+    "gs_knn.hip": ["-ffp-contract=off"],
+    "gs_api_knn.hip": ["-ffp-contract=off"],
     "gs_api.hip": [],
     "gs_api_bin.hip": [],
     "gs_api_composite.hip": [],

@@ -75,6 +75,15 @@ def compute_projection(camera: Camera, w: int, h: int) -> np.ndarray:
     return P.flatten(order="F")
 
 
+def scene_extent(cameras) -> float:
+    """The camera extent of a scene as 3DGS defines it: 1.1 x the largest distance of a camera eye from the mean of the eyes, in
+    float64 -- the value density.density_params(scene_extent=...) expects."""
+    eyes = np.stack([np.asarray(c.eye, np.float64).reshape(3) for c in cameras])
+    if not np.isfinite(eyes).all():
+        raise ValueError("scene_extent: a camera eye is not finite")
+    return float(1.1 * np.max(np.linalg.norm(eyes - eyes.mean(axis=0), axis=1)))
+
+
 def get_camera(path: str, idx: int) -> Camera:
     """cameras.json loader (camera.jl:113-151); `idx` is 1-based like the reference."""
     with open(path) as fh:

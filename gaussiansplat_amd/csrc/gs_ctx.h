@@ -7,6 +7,7 @@
 //   gs_api_comm.hip       RCCL below the boundary (gs_comm_*, gs_allreduce_grads)
 //   gs_api_touched.hip    the touched-rows colour exchange (gs_color_rows_pack, gs_sh_grads_from_touched)
 //   gs_api_density.hip    density control (gs_density_accumulate / _decide / _plan / _restructure, gs_opacity_reset)
+//   gs_api_knn.hip        point-cloud initialisation (gs_knn_mean_dist2, gs_init_from_points)
 //   gs_background.hip     the background colour's two elementwise kernels (the forward's epilogue, gs_compose_target)
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
 // How far the frame has come is ONE ordered value (gs_ctx::Stage): every entry point compares it, reaches a stage or falls back to one.
@@ -306,6 +307,9 @@ struct gs_ctx {
         int64_t n_out() const { return survivors + clones + 2 * splits; }
     } density;
     float density_log_shrink = 0.4700036292457356f;   // (float)log(1.6) until a gs_density_decide says otherwise: what the children of a split shrink by
+    // ---- point-cloud initialisation (gs_api_knn.hip): scratch of its own, so that gs_knn_mean_dist2 is legal in the middle of a frame --
+    // (key | index) pairs and the sort's table, the sorted points, box and super-box bounds, {bounding box, count of finite points}
+    DevBuf knn_pairs_a, knn_pairs_b, knn_table, knn_digit_total, knn_sorted, knn_boxes, knn_supers, knn_stats;
     ncclComm_t comm = nullptr;
     int comm_ranks = 0;
 };

@@ -67,6 +67,22 @@ def load_ply(path: str, sh_degree: int = 1) -> dict:
                 shs=shs.reshape(n, K, 3))
 
 
+def load_points(path: str, sh_degree: int = 3, opacity: float = 0.1):
+    """An SfM point cloud (`points3D.ply`: x, y, z and, when present, uchar red / green / blue -> [0, 1] by / 255) as a
+    pointcloud.PointCloud -- what a training run starts from.  Colours are taken only when all three are there."""
+    from .pointcloud import PointCloud
+    v = _read_vertex_table(path)
+    names = v.dtype.names or ()
+    for k in "xyz":
+        if k not in names:
+            raise ValueError(f"{path}: no vertex property {k!r}")
+    points = np.stack([np.asarray(v[k], np.float32) for k in "xyz"], axis=1)
+    colors = None
+    if all(k in names for k in ("red", "green", "blue")):
+        colors = np.stack([np.asarray(v[k], np.float32) for k in ("red", "green", "blue")], axis=1) / np.float32(255.0)
+    return PointCloud(points, colors, sh_degree=sh_degree, opacity=opacity)
+
+
 def save_ply(path: str, scene: dict) -> None:
     """Write a scene in the 3DGS layout (45 f_rest columns, zero padded) -- used by tests/tools."""
     n = scene["means"].shape[0]

@@ -304,7 +304,8 @@ def initData(nGaussians: int, seed: int = 0) -> dict:
 
 def getRenderer(rendererType, imgSize, threads, blocks, source=None, *, device: int = 0, **kw):
     """renderer.jl:164-186.  `source`: a PLY path (splat.jl:106-119), an int nGaussians
-    (splat.jl:90-104) or a dict of arrays (means, scales, quats, opacities, shs[n,K,3])."""
+    (splat.jl:90-104), a dict of arrays (means, scales, quats, opacities, shs[n,K,3]) or a pointcloud.PointCloud (an SfM point
+    cloud: the model a training run starts from, pointcloud.from_points)."""
     import torch
     if isinstance(rendererType, str):
         rendererType = RendererType[rendererType.lstrip(":")]
@@ -327,6 +328,9 @@ def getRenderer(rendererType, imgSize, threads, blocks, source=None, *, device: 
             raise TypeError("GAUSSIAN_2D: source must be an int (nGaussians) or a dict of arrays (means, scales, rots, opacities, colors)")
         kw.pop("order", None)
         return GaussianRenderer2D(_to_device_data_2d(scene, torch.device("cuda", device)), (W, H), device=device, **kw)
+    from .pointcloud import PointCloud, from_points
+    if isinstance(source, PointCloud):                   # the start of a training run: 3-NN scales and the model built on the device
+        return GaussianRenderer3D(from_points(source, device=device), (W, H), source.sh_degree, device=device, **kw)
     if isinstance(source, str):
         from .ply import load_ply
         scene = load_ply(source)
@@ -335,7 +339,7 @@ def getRenderer(rendererType, imgSize, threads, blocks, source=None, *, device: 
     elif isinstance(source, dict):
         scene = source
     else:
-        raise TypeError("source must be a PLY path, an int or a dict of arrays")
+        raise TypeError("source must be a PLY path, an int, a dict of arrays or a pointcloud.PointCloud")
     shs = np.asarray(scene["shs"])
     K = shs.reshape(shs.shape[0], -1).shape[1] // 3
     deg = {1: 0, 4: 1, 9: 2, 16: 3}[K]

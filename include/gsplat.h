@@ -484,6 +484,36 @@ int gs_density_restructure(gs_ctx *ctx, const int32_t *action, const float *nois
  * moment arrays (DEVICE, N floats; either may be NULL).  The frame is dropped, as after an optimiser step.  No synchronise. */
 int gs_opacity_reset(gs_ctx *ctx, float max_logit, float *m_opac, float *v_opac);
 
+/* ---- point-cloud initialisation: exact 3-NN scales, a model on the device ---------- */
+
+/* The FIRST step of the 3DGS recipe: a model from an SfM point cloud.  Means are the points, SH band 0 the point colours, quaternions the
+ * identity, and every scale the mean distance to the three nearest neighbours (distCUDA2 in the original).  Both calls run on the ctx
+ * stream, need no model, camera or frame and leave the ctx's frame, its plans and every frame buffer exactly as they were (their scratch
+ * is the ctx's own, grow-only): they are legal between gs_forward and gs_backward.  Neither synchronises.  All pointers are DEVICE pointers.
+ *
+ * gs_knn_mean_dist2.  points: 3 x N, the component fastest; dist2: N floats, not overlapping points.  A point is finite if its three
+ * coordinates are; m = the number of finite points.  With every operation a single fp32 operation rounded on its own, no contraction:
+ *   dx = xi - xj (dy, dz likewise);   d2(i, j) = ((dx*dx + dy*dy) + dz*dz)        (an overflowed square is +Inf and takes part as such)
+ * For a finite point i and m >= 4, with b0 <= b1 <= b2 the three smallest values of the multiset { d2(i, j) : j != i, j finite } --
+ * j != i by INDEX: a duplicate of i counts, with distance 0 --
+ *   dist2[i] = ((b0 + b1) + b2) / 3.0f
+ * A function of a multiset of individually rounded values: it does not depend on the search order and equals a brute-force evaluation
+ * bit for bit.  m >= 4, point i not finite: dist2[i] = NaN (any NaN).  m < 4: every dist2[i] = NaN.
+ * N == 0: GS_OK, nothing enqueued.  GS_ERR_INVALID, nothing written: a NULL pointer, N < 0, dist2 overlapping points.
+ * GS_ERR_UNSUPPORTED: N > 2^31 - 1. */
+int gs_knn_mean_dist2(gs_ctx *ctx, const float *points, int64_t n, float *dist2);
+
+/* colors: 3 x N rgb in [0, 1], or NULL for grey 0.5; dist2: what gs_knn_mean_dist2 left; dst_model: five arrays of N rows in the model's
+ * layouts, passed as gs_density_restructure takes them (d_shs: 3 (sh_degree + 1)^2 floats per row).  Per point, bit for bit but the scales:
+ *   means = the point;   v = dist2 > 1e-7f ? dist2 : 1e-7f  (a NaN gives 1e-7f);   scales[0..2] = (float)(0.5 * log((double)v)), within
+ *   1 float ulp of the correctly rounded value;   quats = (1, 0, 0, 0);   opacities = opacity_logit (the host passes the logit, as the
+ *   density calls take theirs);   shs[c] = (rgb[c] - 0.5f) / SH_C0 for c < 3, one subtract and one correctly rounded divide by
+ *   SH_C0 = 0.28209479177387814f -- the inverse of the + 0.5 of the preprocess -- or +0.0 with NULL colours;   shs[3 ..] = +0.0.
+ * GS_ERR_INVALID, nothing written: sh_degree outside 0..3, N < 0, a NULL points, dist2 or destination, any overlap between destinations
+ * or of one with a source.  The ctx's model is NOT switched: call gs_set_model on the new arrays. */
+int gs_init_from_points(gs_ctx *ctx, const float *points, const float *colors, const float *dist2, int64_t n,
+                        int sh_degree, float opacity_logit, const gs_grads *dst_model);
+
 /* ---- introspection (parity tests, profiling) ------------------------------------------- */
 
 typedef enum {

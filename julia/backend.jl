@@ -309,6 +309,17 @@ end
 hip_opacityReset!(r::HipRenderer, maxLogit::Real, mOpac::Ptr{Float32} = Ptr{Float32}(C_NULL), vOpac::Ptr{Float32} = Ptr{Float32}(C_NULL)) =
     check(r, ccall((:gs_opacity_reset, libgs), Cint, (Ptr{Cvoid}, Cfloat, Ptr{Float32}, Ptr{Float32}), r.ctx, maxLogit, mOpac, vOpac))
 
+# point-cloud initialisation (device pointers; no model, camera or frame needed, the ctx's frame is left as it is; no synchronise)
+# dist2[i] = the mean of the three smallest squared distances from point i to the other finite points: exact, bit for bit a brute force
+hip_knnMeanDist2!(r::HipRenderer, points::Ptr{Float32}, n::Integer, dist2::Ptr{Float32}) =
+    check(r, ccall((:gs_knn_mean_dist2, libgs), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int64, Ptr{Float32}), r.ctx, points, Int64(n), dist2))
+# the model a training run starts from, into dstModel (five arrays of n rows); colors C_NULL: grey.  Then hip-side gs_set_model on them
+hip_initFromPoints!(r::HipRenderer, points::Ptr{Float32}, colors::Ptr{Float32}, dist2::Ptr{Float32}, n::Integer, shDegree::Integer,
+                    opacityLogit::Real, dstModel::GsGrads) =
+    check(r, ccall((:gs_init_from_points, libgs), Cint,
+                   (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64, Cint, Cfloat, Ref{GsGrads}),
+                   r.ctx, points, colors, dist2, Int64(n), shDegree, opacityLogit, dstModel))
+
 # the active SH degree (3-D renderer): evaluate bands 0 .. degree on rows that keep the model's stride; -1 = the model's own degree.
 # The request is the ctx's (it survives a later gs_set_model); a change of the effective degree drops the frame.
 hip_setActiveShDegree!(r::HipRenderer, degree::Integer = -1) =
