@@ -32,7 +32,8 @@ SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs
            "gs_get_list_stats", "gs_get_tile_parts", "gs_get_bin_path", "gs_debug_set_window", "gs_debug_tile_clock_rows", "gs_debug_tail_fill",
            "gs_adam_step", "gs_backward_adam",
            "gs_density_accumulate", "gs_density_decide", "gs_density_plan", "gs_density_restructure", "gs_opacity_reset",
-           "gs_knn_mean_dist2", "gs_init_from_points")
+           "gs_knn_mean_dist2", "gs_init_from_points",
+           "gs_view_depth", "gs_view_depth_backward", "gs_render_features", "gs_backward_features")
 
 GS_ABI_VERSION = 3          # include/gsplat.h; load() refuses a library that reports another version
 GS_DEBUG_WIDE_CURSORS = 1
@@ -164,6 +165,10 @@ def load():
     L.gs_opacity_reset.argtypes = [vp, C.c_float, vp, vp]
     L.gs_knn_mean_dist2.argtypes = [vp, vp, C.c_int64, vp]
     L.gs_init_from_points.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int, C.c_float, G]
+    L.gs_view_depth.argtypes = [vp, vp]
+    L.gs_view_depth_backward.argtypes = [vp, vp, vp]
+    L.gs_render_features.argtypes = [vp, vp, vp, vp]
+    L.gs_backward_features.argtypes = [vp, vp, vp, vp, vp, G]
     if L.gs_abi_version() != GS_ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH} has ABI version {L.gs_abi_version()}, this binding is written for {GS_ABI_VERSION}: "
                            "rebuild with `python -m gaussiansplat_amd.build --force`")
@@ -498,6 +503,27 @@ class Context:
         grey.  The ctx's model is not switched.  No sync."""
         self._chk(self.L.gs_init_from_points(self.h, C.c_void_p(int(points_ptr or 0)), C.c_void_p(int(colors_ptr or 0)), C.c_void_p(int(dist2_ptr or 0)),
                                              C.c_int64(int(n)), C.c_int(int(sh_degree)), C.c_float(opacity_logit), C.byref(dst_model)))
+
+    # -- feature maps (3-D renderer): depth, opacity and per-gaussian features through the frame's own composite launches
+    def view_depth(self, z_ptr: int):
+        """gs_view_depth: z[g] = the view-space depth ts[2] of gaussian g (n device floats; GS_ARR_TS row 2 bit for bit).  Needs a model and
+        a camera, no frame.  No sync."""
+        self._chk(self.L.gs_view_depth(self.h, C.c_void_p(int(z_ptr or 0))))
+
+    def view_depth_backward(self, dz_ptr: int, d_means_ptr: int):
+        """gs_view_depth_backward: d_means[g][j] += T[2 + 4 j] * dz[g]; rows whose dz compares == 0 are left unread.  No sync."""
+        self._chk(self.L.gs_view_depth_backward(self.h, C.c_void_p(int(dz_ptr or 0)), C.c_void_p(int(d_means_ptr or 0))))
+
+    def render_features(self, feat_ptr: int, out_ptr: int, trans_ptr: int = 0):
+        """gs_render_features: out [3, H, W] = sum feat[g] * alpha * T over the finished frame's own walk (feat [n, 3] device floats); no
+        background; trans_ptr 0: the transmittance is not wanted.  The frame stays as forward left it.  No sync."""
+        self._chk(self.L.gs_render_features(self.h, C.c_void_p(int(feat_ptr or 0)), C.c_void_p(int(out_ptr or 0)), C.c_void_p(int(trans_ptr or 0))))
+
+    def backward_features(self, feat_ptr: int, image_f_ptr: int, dF_ptr: int, d_feat_ptr: int, grads: "GsGrads | None"):
+        """gs_backward_features: the gradients of sum out . dF -- d_feat [n, 3] overwritten, the alpha path accumulated into the means,
+        scales, quaternions and opacities of `grads` (None: d_feat only; d_shs is not touched).  No sync."""
+        self._chk(self.L.gs_backward_features(self.h, C.c_void_p(int(feat_ptr or 0)), C.c_void_p(int(image_f_ptr or 0)), C.c_void_p(int(dF_ptr or 0)),
+                                              C.c_void_p(int(d_feat_ptr or 0)), C.byref(grads) if grads is not None else None))
 
     def reset_grads(self, grads: GsGrads):
         self._chk(self.L.gs_reset_grads(self.h, C.byref(grads)))

@@ -52,6 +52,9 @@ SOURCES = {
     # point-cloud initialisation: d2, the box bound and the mean are specified operation by operation (tests/knn_ref.py matches bit for bit)
     "gs_knn.hip": ["-ffp-contract=off"],
     "gs_api_knn.hip": ["-ffp-contract=off"],
+    # feature maps: the view-space depth is the preprocess's own statement (GS_ARR_TS row 2, bit for bit), its adjoint one multiply and one add
+    "gs_features.hip": ["-ffp-contract=off"],
+    "gs_api_features.hip": [],
     "gs_api.hip": [],
     "gs_api_bin.hip": [],
     "gs_api_composite.hip": [],

@@ -8,6 +8,7 @@
 //   gs_api_touched.hip    the touched-rows colour exchange (gs_color_rows_pack, gs_sh_grads_from_touched)
 //   gs_api_density.hip    density control (gs_density_accumulate / _decide / _plan / _restructure, gs_opacity_reset)
 //   gs_api_knn.hip        point-cloud initialisation (gs_knn_mean_dist2, gs_init_from_points)
+//   gs_api_features.hip   feature maps (gs_view_depth, gs_render_features, gs_backward_features, gs_view_depth_backward)
 //   gs_background.hip     the background colour's two elementwise kernels (the forward's epilogue, gs_compose_target)
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
 // How far the frame has come is ONE ordered value (gs_ctx::Stage): every entry point compares it, reaches a stage or falls back to one.
@@ -310,6 +311,12 @@ struct gs_ctx {
     // ---- point-cloud initialisation (gs_api_knn.hip): scratch of its own, so that gs_knn_mean_dist2 is legal in the middle of a frame --
     // (key | index) pairs and the sort's table, the sorted points, box and super-box bounds, {bounding box, count of finite points}
     DevBuf knn_pairs_a, knn_pairs_b, knn_table, knn_digit_total, knn_sorted, knn_boxes, knn_supers, knn_stats;
+    // ---- feature maps (gs_api_features.hip): the frame's composite launches over a SECOND payload whose three colour floats are the caller's.
+    // Buffers of their own, so that the frame's image, transmittance, g2d and dpc stay what gs_forward / gs_backward left: the payload copy, the
+    // transmittance of a render without trans_out, the auxiliary rows of 2-D gradient sums and the geometry chain's colour-path input, which
+    // nothing ever writes but the zero fill behind its allocation (feat_dpc_zeroed: the capacity that fill covered)
+    DevBuf feat_payload, feat_trans, feat_g2d, feat_dpc;
+    size_t feat_dpc_zeroed = 0;
     ncclComm_t comm = nullptr;
     int comm_ranks = 0;
 };

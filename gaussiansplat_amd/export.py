@@ -22,6 +22,23 @@ def to_rgb8(image_chw, rotate: bool = True) -> np.ndarray:
     return np.ascontiguousarray(julia)
 
 
+def depth_to_gray8(depth_hw, near: "float | None" = None, far: "float | None" = None, rotate: bool = True) -> np.ndarray:
+    """A depth map [H, W] (renderer.renderDepth(mode="expected"): 0 where nothing was hit) as 8-bit grey, near = white, far = dark,
+    empty and non-finite pixels black; near / far default to the smallest and largest depth hit.  Orientation as to_rgb8; [.., 3] so that
+    save_ppm takes it."""
+    d = np.asarray(depth_hw.detach().cpu().numpy() if hasattr(depth_hw, "detach") else depth_hw, np.float32)
+    hit = np.isfinite(d) & (d > 0)
+    lo = float(near) if near is not None else (float(d[hit].min()) if hit.any() else 0.0)
+    hi = float(far) if far is not None else (float(d[hit].max()) if hit.any() else 1.0)
+    span = hi - lo if hi > lo else 1.0
+    g = np.where(hit, 1.0 - np.clip((np.where(hit, d, lo) - lo) / span, 0.0, 1.0) * (254.0 / 255.0), 0.0).astype(np.float32)
+    u8 = np.floor(g * 255.0 + 0.5).astype(np.uint8)
+    julia = np.repeat(np.transpose(u8, (1, 0))[:, :, None], 3, axis=2)  # [W, H, 3]
+    if rotate:
+        julia = np.rot90(julia, k=1, axes=(0, 1))
+    return np.ascontiguousarray(julia)
+
+
 def save_ppm(path: str, rgb8: np.ndarray) -> None:
     """Minimal dependency-free writer (binary PPM) for the exported image."""
     h, w, _ = rgb8.shape

@@ -425,6 +425,95 @@ def backward(renderer, ΔC, skip_shs: bool = False, phase: str = "all"):
         renderer._grads_lazy_zero = False
 
 
+# ---------------------------------------------------------------- feature maps (3-D renderer): depth, opacity, per-gaussian features
+
+def _feature_tensor(renderer, t, shape, what):
+    import torch
+    t = t if isinstance(t, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(t, np.float32))
+    t = t.to(renderer.imageData.device, torch.float32).contiguous()
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def renderFeatures(renderer, feat):
+    """Composite three per-gaussian floats over the frame forward() rendered: feat [n, 3] -> (F [3, H, W], T [H, W]) with
+    F[c] = sum feat[:, c] * alpha * T over the same entries, in the same order, under the same early-out as the colour image; no
+    background is added, T is the frame's transmittance.  New tensors; renderer.imageData / transmittance and the frame stay as they are
+    (a frame binned in depth slabs is refused: pass slab_mode=0 to getRenderer).  Wider features are rendered in triples."""
+    import torch
+    H, W = renderer.transmittance.shape
+    f = _feature_tensor(renderer, feat, (renderer.nGaussians, 3), "feat")
+    F = torch.empty((3, H, W), dtype=torch.float32, device=f.device)
+    T = torch.empty((H, W), dtype=torch.float32, device=f.device)
+    renderer._begin()
+    _bind_outputs(renderer)
+    renderer.ctx.render_features(f.data_ptr(), F.data_ptr(), T.data_ptr())
+    return F, T
+
+
+def backwardFeatures(renderer, feat, F, dF):
+    """The adjoint of renderFeatures for the loss sum F * dF: returns d_feat [n, 3] and ACCUMULATES the alpha-path gradients into
+    renderer.splatGrads (means, scales, quaternions, opacities; the SH gradients are not touched: the features do not depend on the model
+    here).  F is what renderFeatures returned for this feat on this frame.  Legal before, between or after backward()."""
+    import torch
+    H, W = renderer.transmittance.shape
+    n = renderer.nGaussians
+    f = _feature_tensor(renderer, feat, (n, 3), "feat")
+    F = _feature_tensor(renderer, F, (3, H, W), "F")
+    dF = _feature_tensor(renderer, dF, (3, H, W), "dF")
+    d_feat = torch.empty((n, 3), dtype=torch.float32, device=f.device)
+    renderer.splatGrads                                         # a pending lazy reset becomes zeros now: this call accumulates
+    renderer._begin()
+    _bind_outputs(renderer)
+    g = renderer._grads
+    renderer.ctx.backward_features(f.data_ptr(), F.data_ptr(), dF.data_ptr(), d_feat.data_ptr(),
+                                   B.GsGrads(g.d_means, g.d_scales, g.d_quats, g.d_opacities, None))
+    return d_feat
+
+
+def viewDepth(renderer):
+    """z [n]: the view-space depth of every gaussian under the renderer's current camera (preprocess() sets it), as the preprocess
+    computes it (ts[3, :] of the reference's tValues)."""
+    import torch
+    z = torch.empty((renderer.nGaussians,), dtype=torch.float32, device=renderer.imageData.device)
+    renderer._begin()
+    renderer.ctx.view_depth(z.data_ptr())
+    return z
+
+
+def renderDepth(renderer, mode: str = "accumulated"):
+    """Depth of the frame forward() rendered, from the features (z, z^2, 1): planes [3, H, W] = (sum z w, sum z^2 w, sum w) with
+    w = alpha * T -- accumulated depth, its second moment (a variance: planes[1] / planes[2] - expected^2) and the opacity 1 - T.
+    mode "accumulated": returns planes.  mode "expected": returns (planes, depth [H, W]) with depth = planes[0] / planes[2] where
+    planes[2] > 1e-8, else 0.  backwardDepth differentiates the three planes."""
+    import torch
+    if mode not in ("accumulated", "expected"):
+        raise ValueError('renderDepth: mode must be "accumulated" or "expected"')
+    z = viewDepth(renderer)
+    feat = torch.stack((z, z * z, torch.ones_like(z)), 1).contiguous()
+    planes, _ = renderFeatures(renderer, feat)
+    renderer._depth_state = (feat, planes, z)
+    if mode == "accumulated":
+        return planes
+    return planes, torch.where(planes[2] > 1e-8, planes[0] / planes[2], torch.zeros_like(planes[0]))
+
+
+def backwardDepth(renderer, dD):
+    """The adjoint of renderDepth's three planes for the loss sum planes * dD (dD [3, H, W]; for the expected depth the caller chains
+    d depth -> d planes first: d planes[0] = g / planes[2], d planes[2] = -g * depth / planes[2]).  Accumulates into
+    renderer.splatGrads: the alpha path through backwardFeatures, and the value path z(means) -- dz = d_feat[:, 0] + 2 z d_feat[:, 1] --
+    into the means."""
+    st = getattr(renderer, "_depth_state", None)
+    if st is None:
+        raise RuntimeError("backwardDepth: renderDepth first")
+    feat, planes, z = st
+    d_feat = backwardFeatures(renderer, feat, planes, dD)
+    dz = (d_feat[:, 0] + 2.0 * z * d_feat[:, 1]).contiguous()
+    renderer.ctx.view_depth_backward(dz.data_ptr(), renderer._grads.d_means)
+    return d_feat
+
+
 def resetGrads(renderer_or_grads):
     """splat.jl:158-173."""
     import torch

@@ -514,6 +514,47 @@ int gs_knn_mean_dist2(gs_ctx *ctx, const float *points, int64_t n, float *dist2)
 int gs_init_from_points(gs_ctx *ctx, const float *points, const float *colors, const float *dist2, int64_t n,
                         int sh_degree, float opacity_logit, const gs_grads *dst_model);
 
+/* ---- feature maps: depth, opacity and per-gaussian features, with gradients (3-D renderer) ---------- */
+
+/* The composite forward computes C = sum c_g alpha T for three per-gaussian floats; that they are colours is the preprocess's business.
+ * These calls run a FINISHED frame's composite launches over a second, ctx-owned payload whose three colour floats are the caller's: the
+ * same tile lists, entries, order, early-out (t_min) and no-op rule (alpha_cull) as the frame's forward, so a depth or opacity map is
+ * consistent with the colour image pixel by pixel.  Features wider than three are rendered in triples.  All four calls: 3-D renderer only
+ * (GS_ERR_UNSUPPORTED after gs_set_model_2d), every pointer a DEVICE pointer, work enqueued on the ctx stream, no synchronise.
+ *
+ * gs_view_depth.  z: N floats; z[g] = ts[2], the view-space depth of gaussian g, as the preprocess states it -- with m the mean and T
+ * column major, every step a single fp32 operation:
+ *   s = T[2]*m1;  s = s + T[6]*m2;  s = s + T[10]*m3;  s = s + T[14]*1.0f
+ * equal to row 2 of GS_ARR_TS bit for bit (non-finite means pass through as IEEE gives them).  Needs a model and a camera, no frame, and
+ * leaves the frame alone.  gs_view_depth_backward is its adjoint: d_means[3g+j] = d_means[3g+j] + (T[2+4j] * dz[g]), one multiply and one
+ * add; a dz[g] that compares == 0 leaves row g unread (the "untouched" rule of the per-gaussian chain). */
+int gs_view_depth(gs_ctx *ctx, float *z);
+int gs_view_depth_backward(gs_ctx *ctx, const float *dz, float *d_means);
+
+/* gs_render_features.  feat: 3 x N, component fastest; out: [3, H, W] planar (the image layout); trans_out: [H, W] or NULL.
+ *   out[c][p] = sum over the frame's entries of feat[c][g] * alpha * T        no background is added; trans_out = the frame's transmittance
+ * Needs a frame at gs_forward or later (GS_ERR_INVALID otherwise) and is legal before, between and after its backward calls.  With
+ * feat = GS_ARR_RGB and one wave per tile (gs_config.tile_parts = 1) out and trans_out equal the frame's image (over black) and
+ * transmittance bit for bit; with tiles shared between waves, within the no-op rule of tile_parts.  The features should be finite: the
+ * composite kernels mask arithmetically, so a NaN or Inf feature of a LISTED gaussian reaches the pixels of the tiles that list it.
+ * The frame is left exactly as gs_forward left it: image, transmittance, work counters, the view slot's history, launch orders,
+ * snapshots and gradient sums; the ctx pays one payload copy (64 B per gaussian) of scratch.
+ * GS_ERR_UNSUPPORTED, nothing enqueued: a frame binned in depth slabs (gs_num_rounds > 1) -- a caller that renders feature maps sets
+ * gs_config.slab_mode = 0.  GS_ERR_INVALID, nothing enqueued: a NULL feat or out; out or trans_out overlapping the frame's image or
+ * transmittance (the ctx's own or the bound ones) or each other. */
+int gs_render_features(gs_ctx *ctx, const float *feat, float *out, float *trans_out);
+
+/* gs_backward_features.  The gradients of sum out . dF for the `out` gs_render_features wrote for this `feat` on this frame (image_f; dF:
+ * [3, H, W]).  d_feat (3 x N) is OVERWRITTEN with d / d feat; the alpha-path gradients ACCUMULATE (+=) into grads->d_means, d_scales,
+ * d_quats and d_opacities (any may be NULL, as may grads); d_shs is neither read nor written -- the features do not depend on the model
+ * here: a caller whose features do (depth) chains d_feat itself (gs_view_depth_backward).  The composite adjoint runs over whole tiles into
+ * auxiliary gradient sums of the frame's mode, then the geometry chain alone runs over them; the call is legal before, between or after
+ * the frame's colour backward calls (also between GS_BWD_PARAMS_SH and GS_BWD_PARAMS_GEOM) and changes nothing they read or write apart
+ * from the accumulation into `grads`.  gs_config.deterministic: bitwise reproducible run to run; the fixed-point sums hold +-8.4e6 in the
+ * first six words of a row (d feat, and the moments of order 0 and 1), and what they hold scales with |feat| * |dF| -- a depth feature
+ * in scene units of thousands wants dF scaled down accordingly.  Refusals as gs_render_features (a NULL feat, image_f, dF or d_feat). */
+int gs_backward_features(gs_ctx *ctx, const float *feat, const float *image_f, const float *dF, float *d_feat, const gs_grads *grads);
+
 /* ---- introspection (parity tests, profiling) ------------------------------------------- */
 
 typedef enum {

@@ -320,6 +320,24 @@ hip_initFromPoints!(r::HipRenderer, points::Ptr{Float32}, colors::Ptr{Float32}, 
                    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64, Cint, Cfloat, Ref{GsGrads}),
                    r.ctx, points, colors, dist2, Int64(n), shDegree, opacityLogit, dstModel))
 
+# feature maps (3-D renderer; device pointers, on the ctx stream, no synchronise): the finished frame's composite launches over a second
+# payload whose three colour floats are the caller's.  The frame stays exactly as hip_forward! left it.
+# z[g] = the view-space depth of gaussian g (ts[3, g] of the reference's tValues, bit for bit); needs a model and a camera, no frame
+hip_viewDepth!(r::HipRenderer, z::Ptr{Float32}) =
+    check(r, ccall((:gs_view_depth, libgs), Cint, (Ptr{Cvoid}, Ptr{Float32}), r.ctx, z))
+# its adjoint: dMeans[j, g] += T[3, j] * dz[g]; rows whose dz is zero are left unread
+hip_viewDepthBackward!(r::HipRenderer, dz::Ptr{Float32}, dMeans::Ptr{Float32}) =
+    check(r, ccall((:gs_view_depth_backward, libgs), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), r.ctx, dz, dMeans))
+# out (W x H x 3) = sum feat[:, g] * alpha * T over the frame's own walk, feat 3 x N; no background; transOut (W x H) may be C_NULL
+hip_renderFeatures!(r::HipRenderer, feat::Ptr{Float32}, out::Ptr{Float32}, transOut::Ptr{Float32} = Ptr{Float32}(C_NULL)) =
+    check(r, ccall((:gs_render_features, libgs), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), r.ctx, feat, out, transOut))
+# the gradients of sum out .* dF: dFeat (3 x N) overwritten, the alpha path accumulated into the means, scales, quaternions and opacities
+# of grads (a C_NULL array is skipped; d_shs is not touched)
+hip_backwardFeatures!(r::HipRenderer, feat::Ptr{Float32}, imageF::Ptr{Float32}, dF::Ptr{Float32}, dFeat::Ptr{Float32}, grads::GsGrads) =
+    check(r, ccall((:gs_backward_features, libgs), Cint,
+                   (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ref{GsGrads}),
+                   r.ctx, feat, imageF, dF, dFeat, grads))
+
 # the active SH degree (3-D renderer): evaluate bands 0 .. degree on rows that keep the model's stride; -1 = the model's own degree.
 # The request is the ctx's (it survives a later gs_set_model); a change of the effective degree drops the frame.
 hip_setActiveShDegree!(r::HipRenderer, degree::Integer = -1) =
