@@ -1,6 +1,10 @@
 """Loss + SGD step on the GPU against the loss.jl restatement and torch autograd."""
+import os
+
 import numpy as np
 import pytest
+
+import loss_ref as LR
 
 pytestmark = pytest.mark.gpu
 
@@ -167,3 +171,149 @@ def test_three_iteration_trajectory_against_an_oracle_side_loop(oracle, fused):
         assert rep[k]["param_rel_l2"] <= 1e-4, (k, rep[k])
         assert rep[k]["displacement_over_param"] > 0.0, k
         assert rep[k]["displacement_rel_l2"] <= 1e-2, (k, rep[k])
+
+
+# ---------------------------------------------------------------- the loss kernels on flat, smooth and tiny images (tests/loss_ref.py)
+def _dev(a):
+    import torch
+    return torch.as_tensor(np.array(a, np.float32)).cuda()                  # a copy: the shared cases are read-only
+
+
+def _loss_device(ctx, img, gt, lam, want_dC=True, want_loss=True):
+    """(loss, dC) through the device path: images and dC resident, dC filled with NaN first"""
+    import torch
+    Cn, H, W = img.shape
+    x, y = _dev(img), _dev(gt)
+    d = torch.full((Cn, H, W), float("nan"), device="cuda")
+    loss = ctx.loss_device(x.data_ptr(), y.data_ptr(), d.data_ptr() if want_dC else 0, W, H, Cn, lam, want_loss)
+    torch.cuda.synchronize()
+    return loss, d.cpu().numpy()
+
+
+@pytest.mark.parametrize("name", LR.FAMILIES)
+def test_loss_family_within_the_float32_restatements_error(name):
+    """Nine image families x lam in {0.1, 0.2, 1} x thirteen shapes (tests/loss_ref.py: below the window, one pixel wide, W % 4 == 3,
+    either side of the 64 x 16 tile, exactly 8 tiles, other channel counts).  The kernel is compared with the float64 restatement
+    and allowed 4 x the float32 restatement's own error on the same input: gradient max, gradient L2, loss, and the L2 of each
+    border strip (the outer 6 rows / columns, the 6 columns either side of x = 64); loss_ref.RAISED names the parts of a family
+    that are allowed up to 16 and why.  The measured ratios, kernel error over float32 error, go to the parity report of
+    test_gpu_sizes._report (parity_sizes.json) under "loss_families"."""
+    import json
+    from gaussiansplat_amd import backend as B
+    import test_gpu_sizes as TS
+    ctx = B.Context()
+    rep, bad = {}, []
+    for lam in LR.LAMS:
+        for shape in LR.SHAPES:
+            img, gt, b = LR.case(name, shape, lam)
+            loss, dC = ctx.loss_host(img, gt, lam)
+            r = LR.ratios(dC, loss, b)
+            rep["lam%g_%dx%dx%d" % ((lam,) + shape)] = r
+            if not (np.isfinite(dC).all() and all(v <= LR.factor(name, shape, k) for k, v in r.items())):
+                bad.append((lam, shape, r))
+    ctx.close()
+    rep["worst"] = {k: max(v[k] for v in rep.values()) for k in ("max", "l2", "loss", "strips")}
+    print(name, json.dumps(rep["worst"]))
+    prev = {}
+    if os.path.exists(TS._REPORT):
+        try:
+            with open(TS._REPORT) as fh:
+                prev = json.load(fh).get("loss_families", {})
+        except Exception:
+            prev = {}
+    prev[name] = rep
+    TS._report("loss_families", prev)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("name", ["uniform", "range"])
+def test_loss_gradient_at_lambda_zero_is_the_l1_term_exactly(name):
+    """lam = 0: the SSIM term is multiplied by -0.0, so dC = sign(img - gt) * (1 / (2 n)) in float32, element for element, and 0 at
+    the planted ties"""
+    from gaussiansplat_amd import backend as B
+    ctx = B.Context()
+    for shape in ((3, 17, 65), (5, 16, 67), (3, 2, 3)):
+        img, gt, _ = LR.case(name, shape, 1.0)
+        loss, dC = ctx.loss_host(img, gt, 0.0)
+        want = np.sign(img - gt) * (np.float32(1.0) / (np.float32(2.0) * np.float32(img.size)))
+        assert want.dtype == np.float32 and np.array_equal(dC, want), shape
+        assert not dC[0, :3, :5].any()
+        assert abs(loss - np.abs(img.astype(np.float64) - gt).sum() / (2.0 * img.size)) <= 1e-6 * loss
+    ctx.close()
+
+
+@pytest.mark.parametrize("name", ["uniform", "smooth_near"])
+def test_loss_paths_agree_bit_for_bit(name):
+    """dC has one writer per element and no atomics: bitwise equal across two runs, between the host and the device path, and with
+    and without the loss read back.  With dC == NULL on the device path the loss is the one with a dC buffer to 1e-12 relative
+    (the slotted double atomics may reorder)."""
+    from gaussiansplat_amd import backend as B
+    lam = 0.2
+    img, gt, _ = LR.case(name, (3, 49, 193), lam)
+    ctx = B.Context()
+    loss_h, dC_h = ctx.loss_host(img, gt, lam)
+    loss_h2, dC_h2 = ctx.loss_host(img, gt, lam)
+    assert np.array_equal(dC_h, dC_h2) and abs(loss_h - loss_h2) <= 1e-12 * abs(loss_h)
+    loss_d, dC_d = _loss_device(ctx, img, gt, lam)
+    assert np.array_equal(dC_d, dC_h) and abs(loss_d - loss_h) <= 1e-12 * abs(loss_h)
+    none, dC_q = _loss_device(ctx, img, gt, lam, want_loss=False)
+    assert none is None and np.array_equal(dC_q, dC_h)
+    loss_n, untouched = _loss_device(ctx, img, gt, lam, want_dC=False)
+    assert abs(loss_n - loss_h) <= 1e-12 * abs(loss_h) and np.isnan(untouched).all()
+    ctx.close()
+
+
+@pytest.mark.parametrize("name", ["uniform", "smooth_near"])
+@pytest.mark.parametrize("shape", [(3, 17, 65), (2, 33, 129)], ids=lambda s: "%dx%dx%d" % s)
+def test_loss_symmetries(name, shape):
+    """The loss is symmetric in its arguments, and the window under both reflections -- the tiling is not (tiles start at the top
+    left, the ragged end is at the bottom right): dC of the flipped images is the flipped dC.  Every run is held to the bars of
+    the unflipped case, against the float64 restatement of the unflipped case."""
+    from gaussiansplat_amd import backend as B
+    lam = 1.0
+    img, gt, b = LR.case(name, shape, lam)
+    ctx = B.Context()
+    loss_swapped, _ = ctx.loss_host(gt, img, lam)
+    assert abs(loss_swapped - b.loss) <= LR.factor(name, shape, "loss") * b.e_loss
+    for flip in (np.s_[:, :, ::-1], np.s_[:, ::-1, :], np.s_[:, ::-1, ::-1]):
+        loss, dC = ctx.loss_host(np.ascontiguousarray(img[flip]), np.ascontiguousarray(gt[flip]), lam)
+        r = LR.ratios(dC[flip], loss, b)
+        assert all(v <= LR.factor(name, shape, k) for k, v in r.items()), (flip, r)
+    ctx.close()
+
+
+def test_loss_context_reused_across_image_sizes():
+    """One context runs a large image, a tiny one, another, and the large one again: its map planes still hold the larger
+    image's maps.  Every dC equals a fresh context's bit for bit, the losses to 1e-12 relative."""
+    from gaussiansplat_amd import backend as B
+    lam = 0.2
+    ctx = B.Context()
+    for shape in ((3, 49, 193), (3, 2, 3), (1, 16, 64), (3, 49, 193)):
+        img, gt, _ = LR.case("uniform", shape, lam)
+        loss, dC = ctx.loss_host(img, gt, lam)
+        fresh = B.Context()
+        loss_f, dC_f = fresh.loss_host(img, gt, lam)
+        fresh.close()
+        assert np.array_equal(dC, dC_f), shape
+        assert abs(loss - loss_f) <= 1e-12 * abs(loss_f), shape
+    ctx.close()
+
+
+def test_loss_refusals_leave_dC_untouched():
+    """W, H or C <= 0, a bad mem, a NULL img or gt: GS_ERR_INVALID, and a sentinel-filled dC comes back as it went in"""
+    import ctypes as C
+    from gaussiansplat_amd import backend as B
+    ctx = B.Context()
+    img = np.full((3, 4, 5), 0.5, np.float32); gt = np.full((3, 4, 5), 0.25, np.float32)
+    dC = np.full((3, 4, 5), -7.0, np.float32)
+    out = C.c_double(-7.0)
+    ip, gp = img.ctypes.data, gt.ctypes.data
+    for ip_, gp_, W, H, Cn, mem in ((ip, gp, 0, 4, 3, B.GS_MEM_HOST), (ip, gp, 5, 0, 3, B.GS_MEM_HOST), (ip, gp, 5, 4, 0, B.GS_MEM_HOST),
+                                    (ip, gp, -5, 4, 3, B.GS_MEM_HOST), (ip, gp, 5, -4, 3, B.GS_MEM_HOST), (ip, gp, 5, 4, -3, B.GS_MEM_HOST),
+                                    (ip, gp, 5, 4, 3, 2), (ip, gp, 5, 4, 3, -1), (None, gp, 5, 4, 3, B.GS_MEM_HOST), (ip, None, 5, 4, 3, B.GS_MEM_HOST)):
+        rc = ctx.L.gs_loss_l1_dssim(ctx.h, C.c_void_p(ip_), C.c_void_p(gp_), W, H, Cn, 0.2, C.c_void_p(dC.ctypes.data), C.byref(out), mem)
+        assert rc == B.GS_ERR_INVALID, (W, H, Cn, mem, rc)
+        assert np.all(dC == -7.0) and out.value == -7.0
+    loss, got = ctx.loss_host(img, gt, 0.2)                                  # the context still works
+    assert np.isfinite(loss) and np.isfinite(got).all()
+    ctx.close()

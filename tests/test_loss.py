@@ -1,7 +1,9 @@
 """src/loss.jl restatement (oracle/loss_oracle_np.py): known answers + fp64 torch autograd of the gradient."""
 import numpy as np
+import pytest
 import torch
 
+import loss_ref as LR
 from oracle import loss_oracle_np as LO
 
 
@@ -45,6 +47,55 @@ def test_loss_identical_images_and_against_torch():
     # interior pixel of a constant image: mu = value, variance 0 -> ssim map = 1 there
     c = np.full((1, 32, 32), 0.3, np.float32)
     assert abs(float(LO.ssim_score(c, c, k)) - 1.0) < 1e-6
+
+
+def test_restatement_of_the_loss_families_equals_torch_loss():
+    rng = np.random.default_rng(11)
+    img, gt = rng.random((3, 23, 31), dtype=np.float32), rng.random((3, 23, 31), dtype=np.float32)
+    for lam in (0.1, 1.0):
+        x = torch.tensor(img, dtype=torch.float64, requires_grad=True)
+        l = torch_loss(x, torch.tensor(gt, dtype=torch.float64), LO.kernel_window(), lam=lam)
+        l.backward()
+        loss, grad, smap = LR.restate(img, gt, lam, torch.float64)
+        assert abs(loss - float(l.detach())) <= 1e-13 and np.abs(grad - x.grad.numpy()).max() <= 1e-13
+        assert smap.shape == img.shape and abs((1 - lam) * np.abs(img - gt).mean(dtype=np.float64) / 2 + lam * (1 - smap.mean()) / 2 - loss) <= 1e-13
+    assert LR.restate(img, gt, 0.1, torch.float32)[1].dtype == np.float32
+
+
+def test_loss_family_inputs_are_what_they_are_named():
+    for name in LR.FAMILIES:
+        for shape in ((3, 17, 65), (3, 2, 3), (1, 1, 1)):
+            img, gt = LR.family(name, *shape, np.random.default_rng(3))
+            assert img.shape == gt.shape == shape and img.dtype == gt.dtype == np.float32
+            assert img.flags.c_contiguous and gt.flags.c_contiguous
+            if name == "two_consts":
+                assert not np.any(img == gt)
+            elif name != "impulse":                                          # the planted ties: sign(0) = 0
+                assert np.array_equal(img[0, :3, :5], gt[0, :3, :5]) and np.array_equal(img[-1, -7:, -9:], gt[-1, -7:, -9:])
+    img, gt = LR.family("impulse", 3, 49, 193, np.random.default_rng(3))
+    assert not gt.any() and sorted(zip(*np.nonzero(img[1]))) == [(0, 0), (15, 63), (16, 64), (48, 192)]
+    img, gt = LR.family("range", 3, 49, 193, np.random.default_rng(3))
+    assert img.min() < 0 and img.max() > 1 and np.array_equal(img[0, :3, :5], gt[0, :3, :5]) and np.array_equal(img[2, -7:, -9:], gt[2, -7:, -9:])
+    img, gt = LR.family("step", 1, 16, 67, np.random.default_rng(3))
+    assert np.array_equal(np.nonzero(img[0, 5] != gt[0, 5])[0], [64])      # the edges at x = 64 and x = 65
+
+
+@pytest.mark.parametrize("name", LR.FAMILIES)
+def test_loss_family_bars_cannot_hide_a_lost_tap(name):
+    """The GPU tests allow a kernel FACTOR x the float32 restatement's own error (tests/loss_ref.py).  That allowance itself is
+    capped here over the whole matrix: for the sharp families below the window's folded corner weight (four taps of 1.4e-4,
+    5.5e-4 in all; with that weight zeroed, or the halo one column short, the kernel was 100 to 10 000 x over its bars on every
+    family), for the cancelling ones at 2e-2.  Measured worst: sharp 5.2e-6 (checker,
+    lam = 1, 3x1x1), cancelling 2.2e-3 (two_consts, lam = 1)."""
+    cap = LR.CAP_SHARP if name in LR.SHARP else LR.CAP_CANCELLING
+    assert all(LR.FACTOR < f <= 16.0 for f in LR.RAISED.values()) and LR.FACTOR == 4.0
+    for lam in LR.LAMS:
+        for shape in LR.SHAPES:
+            img, gt, b = LR.case(name, shape, lam)
+            assert np.abs(b.grad).max() > 0.0 and np.isfinite(b.grad).all(), (name, lam, shape)
+            assert LR.FACTOR * b.e_max <= cap and LR.FACTOR * b.e_l2 <= cap, (name, lam, shape, b.e_max, b.e_l2)
+            assert LR.factor(name, shape, "max") * max(b.e_max, b.e_l2) <= cap                  # a raised factor stays under it too
+            assert b.e_loss > 0.0 and np.isfinite(b.loss)
 
 
 def test_fft_form_of_the_torch_reference_equals_the_direct_one():
