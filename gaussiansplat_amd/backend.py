@@ -33,8 +33,9 @@ SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs
            "gs_adam_step", "gs_backward_adam",
            "gs_density_accumulate", "gs_density_decide", "gs_density_plan", "gs_density_restructure", "gs_opacity_reset",
            "gs_knn_mean_dist2", "gs_init_from_points",
-           "gs_view_depth", "gs_view_depth_backward", "gs_render_features", "gs_backward_features")
+           "gs_view_depth", "gs_view_depth_backward", "gs_render_features", "gs_backward_features", "gs_backward_camera")
 
+GS_CAMERA_GRAD_FLOATS = 40  # include/gsplat.h: gs_backward_camera
 GS_ABI_VERSION = 3          # include/gsplat.h; load() refuses a library that reports another version
 GS_DEBUG_WIDE_CURSORS = 1
 GS_DEBUG_ALWAYS_ORDER = 2     # launch orders + side stream also on small frames (tests)
@@ -169,6 +170,7 @@ def load():
     L.gs_view_depth_backward.argtypes = [vp, vp, vp]
     L.gs_render_features.argtypes = [vp, vp, vp, vp]
     L.gs_backward_features.argtypes = [vp, vp, vp, vp, vp, G]
+    L.gs_backward_camera.argtypes = [vp, vp, C.c_int]
     if L.gs_abi_version() != GS_ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH} has ABI version {L.gs_abi_version()}, this binding is written for {GS_ABI_VERSION}: "
                            "rebuild with `python -m gaussiansplat_amd.build --force`")
@@ -524,6 +526,17 @@ class Context:
         scales, quaternions and opacities of `grads` (None: d_feat only; d_shs is not touched).  No sync."""
         self._chk(self.L.gs_backward_features(self.h, C.c_void_p(int(feat_ptr or 0)), C.c_void_p(int(image_f_ptr or 0)), C.c_void_p(int(dF_ptr or 0)),
                                               C.c_void_p(int(d_feat_ptr or 0)), C.byref(grads) if grads is not None else None))
+
+    def backward_camera(self, out_ptr: "int | None" = None):
+        """gs_backward_camera: the frame's gradient into the arguments of set_camera, GS_CAMERA_GRAD_FLOATS floats {d_T[16], d_P[16], d_eye[3],
+        d_lookAt[3], d_fx, d_fy} (overwritten).  Needs the frame's colour backward and must precede anything that steps the model.
+        out_ptr None: returned as a float32 array (synchronises); else a device pointer that is filled on the stream (no sync)."""
+        if out_ptr is None:
+            out = np.empty(GS_CAMERA_GRAD_FLOATS, np.float32)
+            self._chk(self.L.gs_backward_camera(self.h, C.c_void_p(out.ctypes.data), GS_MEM_HOST))
+            return out
+        self._chk(self.L.gs_backward_camera(self.h, C.c_void_p(int(out_ptr)), GS_MEM_DEVICE))
+        return None
 
     def reset_grads(self, grads: GsGrads):
         self._chk(self.L.gs_reset_grads(self.h, C.byref(grads)))

@@ -55,6 +55,9 @@ SOURCES = {
     # feature maps: the view-space depth is the preprocess's own statement (GS_ARR_TS row 2, bit for bit), its adjoint one multiply and one add
     "gs_features.hip": ["-ffp-contract=off"],
     "gs_api_features.hip": [],
+    # camera gradient: the statement (gs_camera_grad.h) and the two reduction kernels round operation by operation, as tests/camera_grad_host.cpp does on the CPU
+    "gs_camera.hip": ["-ffp-contract=off"],
+    "gs_api_camera.hip": [],
     "gs_api.hip": [],
     "gs_api_bin.hip": [],
     "gs_api_composite.hip": [],

@@ -75,6 +75,44 @@ def compute_projection(camera: Camera, w: int, h: int) -> np.ndarray:
     return P.flatten(order="F")
 
 
+def camera_param_grads(camera: Camera, w: int, h: int, grads) -> dict:
+    """The chain from the 40 raw partials of renderer.backwardCamera (a CameraGrads, or the 40 floats {d_T[16], d_P[16], d_eye[3],
+    d_lookAt[3], d_fx, d_fy}) to the fields of `camera`: dict(eye, lookAt, up, fx, fy) in float64.  The analytic adjoint of
+    compute_transform (w = unit(lookAt - eye), u = unit(up x w), v = w x u, rows u, v, w, fourth column -axis . eye, fourth row zero) and
+    compute_projection (P[0,0] = 2 fx / w, P[1,1] = 2 fy / h; the other entries depend on near and far only), evaluated in float64 at
+    the camera's float32 fields, plus the direct eye, lookAt, fx, fy terms.  `up` is returned and nobody steps it (optim.CameraAdam)."""
+    f64 = np.float64
+    if hasattr(grads, "T") and hasattr(grads, "lookAt"):
+        gT, gP, g_eye, g_look, g_fx, g_fy = (np.asarray(a, f64).reshape(-1) for a in (grads.T, grads.P, grads.eye, grads.lookAt, grads.fx, grads.fy))
+    else:
+        g = np.asarray(grads, f64).reshape(-1)
+        if g.shape != (40,):
+            raise ValueError(f"camera_param_grads: 40 raw partials expected, got {g.shape}")
+        gT, gP, g_eye, g_look, g_fx, g_fy = g[0:16], g[16:32], g[32:35], g[35:38], g[38:39], g[39:40]
+    G = gT.reshape(4, 4, order="F")                     # G[i, j] = d L / d T[i, j]
+    GP = gP.reshape(4, 4, order="F")
+    eye, look, up = (np.asarray(a, _f32).astype(f64).reshape(3) for a in (camera.eye, camera.lookAt, camera.up))
+    d = look - eye
+    nd = np.sqrt(d @ d)
+    wv = d / nd
+    c = np.cross(up, wv)
+    nc = np.sqrt(c @ c)
+    u = c / nc
+    v = np.cross(wv, u)
+    # T[r, :3] = axis_r, T[r, 3] = -axis_r . eye
+    d_axis = [G[r, :3] - G[r, 3] * eye for r in range(3)]
+    d_eye = -(G[0, 3] * u + G[1, 3] * v + G[2, 3] * wv)
+    d_u, d_v, d_w = d_axis
+    d_w = d_w + np.cross(u, d_v)                        # v = w x u
+    d_u = d_u + np.cross(d_v, wv)
+    d_c = (d_u - u * (u @ d_u)) / nc                    # u = c / |c|
+    d_up = np.cross(wv, d_c)                            # c = up x w
+    d_w = d_w + np.cross(d_c, up)
+    d_d = (d_w - wv * (wv @ d_w)) / nd                  # w = d / |d|, d = lookAt - eye
+    return dict(eye=d_eye - d_d + g_eye, lookAt=d_d + g_look, up=d_up,
+                fx=f64(GP[0, 0] * 2.0 / f64(w) + g_fx[0]), fy=f64(GP[1, 1] * 2.0 / f64(h) + g_fy[0]))
+
+
 def scene_extent(cameras) -> float:
     """The camera extent of a scene as 3DGS defines it: 1.1 x the largest distance of a camera eye from the mean of the eyes, in
     float64 -- the value density.density_params(scene_extent=...) expects."""

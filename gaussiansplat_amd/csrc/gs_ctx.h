@@ -9,6 +9,7 @@
 //   gs_api_density.hip    density control (gs_density_accumulate / _decide / _plan / _restructure, gs_opacity_reset)
 //   gs_api_knn.hip        point-cloud initialisation (gs_knn_mean_dist2, gs_init_from_points)
 //   gs_api_features.hip   feature maps (gs_view_depth, gs_render_features, gs_backward_features, gs_view_depth_backward)
+//   gs_api_camera.hip     the camera gradient (gs_backward_camera)
 //   gs_background.hip     the background colour's two elementwise kernels (the forward's epilogue, gs_compose_target)
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
 // How far the frame has come is ONE ordered value (gs_ctx::Stage): every entry point compares it, reaches a stage or falls back to one.
@@ -317,6 +318,8 @@ struct gs_ctx {
     // nothing ever writes but the zero fill behind its allocation (feat_dpc_zeroed: the capacity that fill covered)
     DevBuf feat_payload, feat_trans, feat_g2d, feat_dpc;
     size_t feat_dpc_zeroed = 0;
+    // ---- camera gradient (gs_api_camera.hip): the staged 40 floats of a GS_MEM_HOST call, then one row of 40 doubles per workgroup of gs_camera_grad_kernel
+    DevBuf camera_partials;
     ncclComm_t comm = nullptr;
     int comm_ranks = 0;
 };

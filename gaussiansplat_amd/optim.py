@@ -197,3 +197,63 @@ class Adam:
         self.exp_avg_sq.copy_(state["exp_avg_sq"].reshape(-1))
         self.step_count, self.lr, self.betas, self.eps = step, lr, (b1, b2), eps
         self.selective = bool(state.get("selective", self.selective))
+
+
+class CameraAdam:
+    """CameraAdam(camera, lr_eye, lr_lookat, lr_focal=0.0, betas=(0.9, 0.999), eps=1e-8): Adam on a view's eye, lookAt and (lr_focal != 0)
+    fx, fy -- pose refinement against a trained model, or beside its training (train.trainStep(..., pose=...)).  Nine numbers do not need a
+    kernel: the state is float64 on the host.  `.camera` is the current Camera (float32 fields; up, near, far, id as given: they are not
+    optimised); `.step(param_grads)` takes what camera.camera_param_grads returns."""
+
+    def __init__(self, camera, lr_eye: float, lr_lookat: float, lr_focal: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8):
+        import numpy as np
+        self.lr = dict(eye=_check_rate("eye", lr_eye), lookAt=_check_rate("lookAt", lr_lookat), focal=_check_rate("focal", lr_focal))
+        b1, b2 = (float(b) for b in betas)
+        for b in (b1, b2):
+            if not (0.0 <= b < 1.0):
+                raise ValueError(f"CameraAdam: betas must lie in [0, 1), got {tuple(betas)}")
+        eps = float(eps)
+        if not math.isfinite(eps) or eps <= 0.0:
+            raise ValueError(f"CameraAdam: eps must be finite and > 0, got {eps}")
+        self.betas, self.eps = (b1, b2), eps
+        self._template = camera
+        # the parameter vector: eye[3], lookAt[3], fx, fy
+        self.x = np.concatenate([np.asarray(camera.eye, np.float64).reshape(3), np.asarray(camera.lookAt, np.float64).reshape(3),
+                                 np.array([camera.fx, camera.fy], np.float64)])
+        if not np.isfinite(self.x).all():
+            raise ValueError("CameraAdam: the camera's eye, lookAt, fx and fy must be finite")
+        self.m = np.zeros(8, np.float64)
+        self.v = np.zeros(8, np.float64)
+        self.step_count = 0
+        self._camera = None
+
+    def _rates(self):
+        import numpy as np
+        return np.array([self.lr["eye"]] * 3 + [self.lr["lookAt"]] * 3 + [self.lr["focal"]] * 2, np.float64)
+
+    @property
+    def camera(self):
+        """The current Camera: float32 eye and lookAt, fx and fy rounded to float32; one object until the next step."""
+        if self._camera is None:
+            import dataclasses
+            import numpy as np
+            self._camera = dataclasses.replace(self._template, eye=self.x[0:3].astype(np.float32), lookAt=self.x[3:6].astype(np.float32),
+                                               fx=float(np.float32(self.x[6])), fy=float(np.float32(self.x[7])))
+        return self._camera
+
+    def step(self, param_grads: dict):
+        """One Adam step from dict(eye, lookAt, fx, fy) (camera.camera_param_grads; `up` is ignored)."""
+        import numpy as np
+        g = np.concatenate([np.asarray(param_grads["eye"], np.float64).reshape(3), np.asarray(param_grads["lookAt"], np.float64).reshape(3),
+                            np.array([param_grads["fx"], param_grads["fy"]], np.float64).reshape(2)])
+        if not np.isfinite(g).all():
+            raise ValueError("CameraAdam.step: a gradient is not finite")
+        b1, b2 = self.betas
+        t = self.step_count + 1
+        self.m = b1 * self.m + (1.0 - b1) * g
+        self.v = b2 * self.v + (1.0 - b2) * (g * g)
+        mhat = self.m / (1.0 - b1 ** t)
+        vhat = self.v / (1.0 - b2 ** t)
+        self.x = self.x - self._rates() * (mhat / (np.sqrt(vhat) + self.eps))
+        self.step_count = t
+        self._camera = None

@@ -514,6 +514,38 @@ def backwardDepth(renderer, dD):
     return d_feat
 
 
+# ---------------------------------------------------------------- camera gradient (3-D renderer): pose refinement
+
+@dataclass
+class CameraGrads:
+    """What backwardCamera returns: the frame's gradient into the arguments of gs_set_camera, taken as independent inputs, float32.
+    T and P are flat column-major like compute_transform / compute_projection; camera.camera_param_grads chains them to Camera fields."""
+    T: np.ndarray
+    P: np.ndarray
+    eye: np.ndarray
+    lookAt: np.ndarray
+    fx: np.ndarray
+    fy: np.ndarray
+
+    @classmethod
+    def from_flat(cls, v) -> "CameraGrads":
+        v = np.ascontiguousarray(v, np.float32).reshape(-1)
+        if v.shape != (B.GS_CAMERA_GRAD_FLOATS,):
+            raise ValueError(f"CameraGrads: {B.GS_CAMERA_GRAD_FLOATS} floats expected, got {v.shape}")
+        return cls(v[0:16].copy(), v[16:32].copy(), v[32:35].copy(), v[35:38].copy(), v[38:39].copy().reshape(()), v[39:40].copy().reshape(()))
+
+    def flat(self) -> np.ndarray:
+        return np.concatenate([np.asarray(a, np.float32).reshape(-1) for a in (self.T, self.P, self.eye, self.lookAt, self.fx, self.fy)])
+
+
+def backwardCamera(renderer) -> CameraGrads:
+    """The gradient of the frame's loss with respect to the view (gs_backward_camera): call it after backward() on the frame and BEFORE
+    anything steps the model -- the chain is recomputed from the resident parameters.  The frame and renderer.splatGrads stay as they
+    are.  The 2-D renderer has no camera: the library's error (GS_ERR_UNSUPPORTED) is raised."""
+    renderer._begin()
+    return CameraGrads.from_flat(renderer.ctx.backward_camera())
+
+
 def resetGrads(renderer_or_grads):
     """splat.jl:158-173."""
     import torch

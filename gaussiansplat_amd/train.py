@@ -153,8 +153,15 @@ def _channels(gtimg) -> int:
     return int(shape[0])
 
 
+def _pose_step(renderer, pose):
+    """backwardCamera on the frame at hand -> the camera's fields -> one step of the pose optimiser."""
+    from .camera import camera_param_grads
+    H, W = renderer.transmittance.shape
+    pose.step(camera_param_grads(pose.camera, W, H, R.backwardCamera(renderer)))
+
+
 def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, want_loss: bool = True, fused_sgd: bool = False,
-              optimizer=None, density=None, sh_schedule=None, background=None):
+              optimizer=None, density=None, sh_schedule=None, background=None, pose=None, freeze_model: bool = False):
     """One iteration of train.jl:33-56 as intended (see module docstring).
     fused_sgd (3-D renderer): backward and the parameter update in one pass (gs_backward_sgd) -- the same parameters bit for
     bit (deterministic mode), but renderer.splatGrads is not filled.
@@ -168,7 +175,22 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
     background: None leaves the renderer's background as it is; (r, g, b) sets it; a RandomBackground draws this iteration's colour and
     sets it, before preprocess.  A [4, H, W] target (straight alpha) is composited over the renderer's current background before the
     loss (lossFunc.compose_target), a [3, H, W] one is used as it is -- so a RandomBackground with a 3-channel target is a ValueError:
-    the target could not follow the colour.  Every optimiser form, density control and the SH schedule run unchanged under it."""
+    the target could not follow the colour.  Every optimiser form, density control and the SH schedule run unchanged under it.
+    pose (optim.CameraAdam, 3-D renderer): the iteration renders under pose.camera; after the unfused backward and before the parameter
+    update (the camera gradient is recomputed from the resident model, so this is the only place) it takes renderer.backwardCamera,
+    chains it to the camera's fields (camera.camera_param_grads) and steps the pose.  The fused forms leave no frame: a ValueError, as
+    with density control; so is an explicit `camera` beside it.  None: the same calls in the same order as without the argument.
+    freeze_model: no parameter update (the gradients are still reset) -- with `pose`, registering a view against a trained model."""
+    if pose is not None and camera is not None:
+        raise ValueError("trainStep: camera and pose exclude each other (the iteration renders under pose.camera)")
+    if pose is not None and (fused_sgd or (optimizer is not None and optimizer.fused)):
+        raise ValueError("trainStep: pose refinement needs the unfused backward (no fused_sgd, no Adam(fused=True)): "
+                         "the fused forms leave no frame to take the camera gradient from")
+    if freeze_model and (fused_sgd or (optimizer is not None and optimizer.fused)):
+        raise ValueError("trainStep: freeze_model needs the unfused backward (no fused_sgd, no Adam(fused=True)): "
+                         "the fused forms step the model inside the backward")
+    if pose is not None:
+        camera = pose.camera
     if isinstance(background, RandomBackground) and _channels(gtimg) != 4:
         raise ValueError("trainStep: a RandomBackground needs a [4, H, W] target (RGBA, straight alpha): a 3-channel target "
                          "could not follow the colour")
@@ -194,9 +216,12 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
             optimizer.backward_step(ΔC)
             return loss
         R.backward(renderer, ΔC)
+        if pose is not None:
+            _pose_step(renderer, pose)
         if density is not None:
             density.accumulate(renderer)
-        optimizer.step()
+        if not freeze_model:
+            optimizer.step()
         R.resetGrads(renderer)
         if density is not None:
             density.after_step(renderer, optimizer)
@@ -208,11 +233,14 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
         renderer._end()
         return loss
     R.backward(renderer, ΔC)
+    if pose is not None:
+        _pose_step(renderer, pose)
     if density is not None:
         density.accumulate(renderer)
-    renderer._begin()
-    renderer.ctx.sgd_step(float(lr), renderer._grads)        # param .-= lr * Δparam (train.jl:42-46)
-    renderer._end()
+    if not freeze_model:
+        renderer._begin()
+        renderer.ctx.sgd_step(float(lr), renderer._grads)    # param .-= lr * Δparam (train.jl:42-46)
+        renderer._end()
     R.resetGrads(renderer)                                   # train.jl:55
     if density is not None:
         density.after_step(renderer, None)
@@ -220,14 +248,15 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
 
 
 def train(renderer, gtimg, lr: float, lossFunc: LossFunction, iterations: int = 100, camera=None, log_every: int = 0, optimizer=None,
-          density=None, sh_schedule=None, background=None):
+          density=None, sh_schedule=None, background=None, pose=None, freeze_model: bool = False):
     """train.jl:16-59 without the GUI; the reference loops `while score < 0.99` on a score it never updates.
     optimizer: an optim.Adam that replaces the SGD update (lr is then ignored); density: a density.DensityController,
-    sh_schedule: an SHDegreeSchedule, background: a colour or a RandomBackground (trainStep)."""
+    sh_schedule: an SHDegreeSchedule, background: a colour or a RandomBackground, pose: an optim.CameraAdam that refines the view,
+    freeze_model: no parameter update -- with `pose`, pose refinement against a trained model (trainStep)."""
     losses = []
     for it in range(iterations):
         l = trainStep(renderer, gtimg, lr, lossFunc, camera, want_loss=True, optimizer=optimizer, density=density, sh_schedule=sh_schedule,
-                      background=background)
+                      background=background, pose=pose, freeze_model=freeze_model)
         losses.append(l)
         if log_every and it % log_every == 0:
             print(f"loss : {l}")                             # loss.jl:69

@@ -16,6 +16,7 @@
  *   gs_forward                forward(renderer,tps,threads,blocks) src/forward.jl:163-198
  *   gs_backward               backward(renderer, dC)              src/backward.jl:3-38
  *   gs_reset_grads            resetGrads(renderer.splatGrads)     src/splat.jl:158-173
+ *   gs_backward_camera        (none: the reference's camera is a constant) the frame's gradient into T, P, eye, lookAt, fx, fy
  *
  * Conventions
  *   - plain C: pointers + sizes, no exceptions; every function returns 0 (GS_OK) or a
@@ -554,6 +555,24 @@ int gs_render_features(gs_ctx *ctx, const float *feat, float *out, float *trans_
  * first six words of a row (d feat, and the moments of order 0 and 1), and what they hold scales with |feat| * |dF| -- a depth feature
  * in scene units of thousands wants dF scaled down accordingly.  Refusals as gs_render_features (a NULL feat, image_f, dF or d_feat). */
 int gs_backward_features(gs_ctx *ctx, const float *feat, const float *image_f, const float *dF, float *d_feat, const gs_grads *grads);
+
+/* gs_backward_camera.  The gradient of the frame's loss with respect to the arguments of gs_set_camera, taken as independent inputs: pose
+ * refinement, registering a new photograph against a trained model.  out: GS_CAMERA_GRAD_FLOATS floats, OVERWRITTEN (a camera gradient
+ * belongs to one view), in the order of a view record and two more:
+ *   [0..15] d_T   [16..31] d_P  (column major, like T and P)   [32..34] d_eye   [35..37] d_lookAt   [38] d_fx   [39] d_fy
+ * each the sum over the gaussians of the statement in csrc/gs_camera_grad.h (d_T[i + 4 j] = sum dt[i] * [m; 1][j], d_P[i + 4 j] = sum dp[i] * t[j],
+ * d_eye = - d_lookAt = the colour path's direction term), evaluated in fp64 from the fp32 inputs at the ACTIVE SH degree, summed in fp64
+ * in a fixed tree without atomics and rounded to float once: the 40 floats are a pure function of the frame's rows of 2-D gradient sums,
+ * the model and the camera, bitwise reproducible call to call (and run to run with gs_config.deterministic).  The fourth row of T is zero
+ * in the reference's cameras; its gradient row is still the formal one.  near and far have no gradient (they only cull).
+ * Needs the frame's colour backward: a gs_backward / gs_backward_ex on this frame that ran the composite adjoint (GS_BWD_COMPOSITE_ONLY is
+ * enough) -- else GS_ERR_INVALID "gs_backward first".  MUST be called before anything steps the model: the chain is recomputed from the
+ * RESIDENT parameters (gs_sgd_step and gs_adam_step on the ctx's own arrays change them under the frame; the fused gs_backward_sgd and
+ * gs_backward_adam drop the frame, so after them the call is refused).  3-D renderer only (GS_ERR_UNSUPPORTED).  Every refusal is made before
+ * anything is enqueued or allocated.  The call reads the frame and writes `out` and scratch of its own: image, transmittance, gradient
+ * sums, stage, view-slot history and stage timers stay as they were.  GS_MEM_HOST synchronises, GS_MEM_DEVICE does not.  N = 0: 40 x +0. */
+#define GS_CAMERA_GRAD_FLOATS 40
+int gs_backward_camera(gs_ctx *ctx, float *out, int mem);
 
 /* ---- introspection (parity tests, profiling) ------------------------------------------- */
 

@@ -338,6 +338,15 @@ hip_backwardFeatures!(r::HipRenderer, feat::Ptr{Float32}, imageF::Ptr{Float32}, 
                    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ref{GsGrads}),
                    r.ctx, feat, imageF, dF, dFeat, grads))
 
+# the frame's gradient into the arguments of gs_set_camera (pose refinement): 40 floats {d_T[16], d_P[16], d_eye[3], d_lookAt[3], d_fx, d_fy},
+# overwritten.  After hip_backward on the frame and before anything steps the model (the chain is recomputed from the resident parameters).
+const GS_CAMERA_GRAD_FLOATS = 40
+function hip_backward_camera(r::HipRenderer)
+    out = Vector{Float32}(undef, GS_CAMERA_GRAD_FLOATS)
+    check(r, ccall((:gs_backward_camera, libgs), Cint, (Ptr{Cvoid}, Ptr{Float32}, Cint), r.ctx, out, GS_MEM_HOST))
+    return out
+end
+
 # the active SH degree (3-D renderer): evaluate bands 0 .. degree on rows that keep the model's stride; -1 = the model's own degree.
 # The request is the ctx's (it survives a later gs_set_model); a change of the effective degree drops the frame.
 hip_setActiveShDegree!(r::HipRenderer, degree::Integer = -1) =
