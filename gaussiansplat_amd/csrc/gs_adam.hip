@@ -148,8 +148,6 @@ __global__ __launch_bounds__(256) void gs_adam_selective_kernel(AdamArgs a) {
     }
 }
 
-bool overlaps(uintptr_t a0, size_t an, uintptr_t b0, size_t bn) { return an && bn && a0 < b0 + bn && b0 < a0 + an; }
-
 }  // namespace
 
 int gs_adam_prepare(gs_ctx *c, const char *who, const float *const p[5], const float *const g[5], float *const m[5], float *const v[5],
@@ -163,8 +161,7 @@ int gs_adam_prepare(gs_ctx *c, const char *who, const float *const p[5], const f
         if (!std::isfinite(lr[i]) || lr[i] < 0.0f) return fail(c, GS_ERR_INVALID, w + ": every lr must be finite and >= 0");
     if (flags & ~GS_ADAM_SELECTIVE) return fail(c, GS_ERR_INVALID, w + ": unknown flag bits");
     // the arrays the step touches must not overlap: p, g, m, v of every group that is stepped
-    uintptr_t lo[20];
-    size_t nb[20];
+    ByteRange r[20];
     int nr = 0;
     for (int i = 0; i < 5; ++i) {
         if (g && !g[i]) continue;                                          // frozen group: nothing of it is touched
@@ -173,11 +170,11 @@ int gs_adam_prepare(gs_ctx *c, const char *who, const float *const p[5], const f
         if (bytes && !p[i]) return fail(c, GS_ERR_INVALID, w + ": no model (gs_set_model first)");
         const void *arr[4] = {p[i], g ? g[i] : nullptr, m[i], v[i]};
         for (const void *q : arr)
-            if (q) { lo[nr] = reinterpret_cast<uintptr_t>(q); nb[nr] = bytes; ++nr; }
+            if (q) r[nr++] = {q, bytes};
     }
     for (int i = 0; i < nr; ++i)
         for (int j = i + 1; j < nr; ++j)
-            if (overlaps(lo[i], nb[i], lo[j], nb[j])) return fail(c, GS_ERR_INVALID, w + ": parameter, gradient and moment arrays overlap");
+            if (overlaps(r[i], r[j])) return fail(c, GS_ERR_INVALID, w + ": parameter, gradient and moment arrays overlap");
     // the scalars: each in double, rounded to float once
     const double t = (double)step;
     h->beta1 = beta1; h->beta2 = beta2; h->eps = eps;

@@ -13,6 +13,18 @@
 
 std::string g_create_error;
 
+// What the preprocess kernels of the two renderers share: the grid, the four outputs and, with export_debug, the debug arrays (2-D: no ts, tps, cov3d)
+template <typename A> static int preprocess_outputs(gs_ctx *c, A &a) {
+    a.gx = c->gx; a.gy = c->gy;
+    a.payload = c->payload.as<GsPayload>(); a.invcov = c->invcov.as<float>(); a.depth_key = c->depth_key.as<uint32_t>(); a.rect = c->rect.as<uint16_t>();
+    if (!c->cfg.export_debug) return GS_OK;
+    for (int i = 0; i < gs_ctx::DBG_COUNT; ++i) HIPCHK(c, c->dbg[i].ensure(sizeof(float) * gs_ctx::DBG_WIDTH[i] * c->n1()));
+    auto arr = [c](gs_ctx::Dbg i) { return c->dbg[i].as<float>(); };
+    a.dbg.mu = arr(gs_ctx::DBG_MU); a.dbg.cov2d = arr(gs_ctx::DBG_COV2D); a.dbg.invcov = arr(gs_ctx::DBG_INVCOV); a.dbg.bbs = arr(gs_ctx::DBG_BBS);
+    if (c->kind == 0) { a.dbg.ts = arr(gs_ctx::DBG_TS); a.dbg.tps = arr(gs_ctx::DBG_TPS); a.dbg.cov3d = arr(gs_ctx::DBG_COV3D); }
+    return GS_OK;
+}
+
 extern "C" {
 
 void gs_default_config(gs_config *cfg) {
@@ -157,7 +169,7 @@ int gs_set_model(gs_ctx *c, int64_t n, int sh_degree, const float *means, const 
     if (n < 0 || n > 0x7FFFFFF0LL) return fail(c, GS_ERR_INVALID, "gs_set_model: n out of range");
     if (sh_degree < 0 || sh_degree > 3) return fail(c, GS_ERR_UNSUPPORTED, "gs_set_model: sh_degree must be 0..3");
     if (n > 0 && (!means || !scales || !quats || !opacities || !shs)) return fail(c, GS_ERR_INVALID, "gs_set_model: NULL array");
-    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(c, GS_ERR_INVALID, "gs_set_model: bad mem");
+    if (const int rc = need_mem(c, "gs_set_model", mem)) return rc;
     const int K = (sh_degree + 1) * (sh_degree + 1);
     const float *src[5] = {means, scales, quats, opacities, shs};
     return adopt_model(c, n, sh_degree, 0, src, {3, 3, 4, 1, (size_t)3 * K}, mem);
@@ -168,7 +180,7 @@ int gs_set_model_2d(gs_ctx *c, int64_t n, const float *means, const float *scale
     if (!c) return GS_ERR_INVALID;
     if (n < 0 || n > 0x7FFFFFF0LL) return fail(c, GS_ERR_INVALID, "gs_set_model_2d: n out of range");
     if (n > 0 && (!means || !scales || !rotations || !opacities || !colors)) return fail(c, GS_ERR_INVALID, "gs_set_model_2d: NULL array");
-    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(c, GS_ERR_INVALID, "gs_set_model_2d: bad mem");
+    if (const int rc = need_mem(c, "gs_set_model_2d", mem)) return rc;
     const float *src[5] = {means, scales, rotations, opacities, colors};
     return adopt_model(c, n, 0, 1, src, {2, 2, 1, 1, 3}, mem);
 }
@@ -177,7 +189,7 @@ int gs_set_model_2d(gs_ctx *c, int64_t n, const float *means, const float *scale
 // change of the model as far as the frame is concerned (an optimiser step does the same); the value in force costs nothing.
 int gs_set_active_sh_degree(gs_ctx *c, int degree) {
     if (!c) return GS_ERR_INVALID;
-    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_set_active_sh_degree: 3-D renderer only");
+    if (const int rc = need_3d(c, "gs_set_active_sh_degree")) return rc;
     if (degree < -1 || degree > 3) return fail(c, GS_ERR_INVALID, "gs_set_active_sh_degree: degree must be -1 (the model's own) or 0..3");
     const int before = c->active_sh_degree();
     c->sh_active_request = degree;
@@ -214,9 +226,9 @@ int gs_get_background(const gs_ctx *c, float rgb[3]) {
 int gs_compose_target(gs_ctx *c, const float *rgba, int32_t W, int32_t H, float *rgb_out) {
     if (!c) return GS_ERR_INVALID;
     if (!rgba || !rgb_out) return fail(c, GS_ERR_INVALID, "gs_compose_target: NULL argument");
-    if (W <= 0 || H <= 0 || W > 32767 || H > 32767) return fail(c, GS_ERR_INVALID, "gs_compose_target: image size must be in 1..32767");
+    if (const int rc = need_image_size(c, "gs_compose_target", W, H)) return rc;
     const size_t px = (size_t)W * H;
-    if (rgb_out < rgba + 4 * px && rgba < rgb_out + 3 * px) return fail(c, GS_ERR_INVALID, "gs_compose_target: rgb_out overlaps rgba");
+    if (overlaps({rgb_out, sizeof(float) * 3 * px}, {rgba, sizeof(float) * 4 * px})) return fail(c, GS_ERR_INVALID, "gs_compose_target: rgb_out overlaps rgba");
     if (bind_device(c)) return GS_ERR_HIP;
     HIPCHK(c, gs_launch_compose_target(rgba, rgb_out, px, c->background, c->stream));
     return GS_OK;
@@ -224,7 +236,7 @@ int gs_compose_target(gs_ctx *c, const float *rgba, int32_t W, int32_t H, float 
 
 int gs_set_image_size(gs_ctx *c, int32_t W, int32_t H) {
     if (!c) return GS_ERR_INVALID;
-    if (W <= 0 || H <= 0 || W > 32767 || H > 32767) return fail(c, GS_ERR_INVALID, "gs_set_image_size: image size must be in 1..32767");
+    if (const int rc = need_image_size(c, "gs_set_image_size", W, H)) return rc;
     if (!c->have_cam) {                                  // a harmless camera, so the shared paths have one
         std::memset(&c->cam, 0, sizeof(c->cam));
         c->cam.near_ = -1.0f; c->cam.far_ = 1.0f;
@@ -239,7 +251,7 @@ int gs_set_camera(gs_ctx *c, const float T[16], const float P[16], float fx, flo
                   const float eye[3], const float lookAt[3], int32_t W, int32_t H) {
     if (!c) return GS_ERR_INVALID;
     if (!T || !P || !eye || !lookAt) return fail(c, GS_ERR_INVALID, "gs_set_camera: NULL argument");
-    if (W <= 0 || H <= 0 || W > 32767 || H > 32767) return fail(c, GS_ERR_INVALID, "gs_set_camera: image size must be in 1..32767");
+    if (const int rc = need_image_size(c, "gs_set_camera", W, H)) return rc;
     std::memcpy(c->cam.T, T, sizeof(float) * 16);
     std::memcpy(c->cam.P, P, sizeof(float) * 16);
     c->cam.fx = fx; c->cam.fy = fy; c->cam.near_ = near_; c->cam.far_ = far_;
@@ -256,60 +268,38 @@ int gs_preprocess(gs_ctx *c) {
     if (bind_device(c)) return GS_ERR_HIP;
     if (int rc = settle_totals(c, nullptr, false)) return rc;               // totals of a frame that was binned but never rendered
     c->frame_id += 1;
-    const size_t n = (size_t)c->n, n1 = n ? n : 1;
-    HIPCHK(c, c->payload.ensure(sizeof(GsPayload) * n1));
-    HIPCHK(c, c->invcov.ensure(sizeof(float) * 4 * n1));
-    HIPCHK(c, c->depth_key.ensure(sizeof(uint32_t) * n1));
-    HIPCHK(c, c->rect.ensure(sizeof(uint16_t) * 4 * n1));
+    HIPCHK(c, c->payload.ensure(sizeof(GsPayload) * c->n1()));
+    HIPCHK(c, c->invcov.ensure(sizeof(float) * 4 * c->n1()));
+    HIPCHK(c, c->depth_key.ensure(sizeof(uint32_t) * c->n1()));
+    HIPCHK(c, c->rect.ensure(sizeof(uint16_t) * 4 * c->n1()));
     // the tile grid is fixed by the image: the reference passes blocks = size/threads (main.jl:9-11)
     c->gx = (c->cam.W + GS_TILE - 1) / GS_TILE;
     c->gy = (c->cam.H + GS_TILE - 1) / GS_TILE;
-    if (c->kind == 1) {                                  // preprocess(::GaussianRenderer2D), forward.jl:9-33
-        c->range_valid = false;
-        GsPreprocess2DArgs a2{};
-        a2.n = c->n; a2.W = c->cam.W; a2.H = c->cam.H; a2.gx = c->gx; a2.gy = c->gy;
-        a2.means = c->means; a2.scales = c->scales; a2.rots = c->quats; a2.opac = c->opac; a2.colors = c->shs;
-        a2.payload = c->payload.as<GsPayload>(); a2.invcov = c->invcov.as<float>(); a2.depth_key = c->depth_key.as<uint32_t>(); a2.rect = c->rect.as<uint16_t>();
-        if (c->cfg.export_debug) {
-            const size_t w[7] = {4, 4, 2, 9, 4, 4, 4};
-            for (int i = 0; i < 7; ++i) HIPCHK(c, c->dbg[i].ensure(sizeof(float) * w[i] * n1));
-            a2.dbg.mu = c->dbg[2].as<float>(); a2.dbg.cov2d = c->dbg[4].as<float>(); a2.dbg.invcov = c->dbg[5].as<float>();
-            a2.dbg.bbs = c->dbg[6].as<float>();
-        }
-        StageTimer t(c, GS_STAGE_PREPROCESS);
-        HIPCHK(c, gs_launch_preprocess2d(a2, c->stream));
-        c->reach(gs_ctx::Stage::PREPROCESSED);
-        return GS_OK;
-    }
-    GsPreprocessArgs a{};
-    a.n = c->n; a.sh_degree = c->active_sh_degree(); a.order = c->cfg.order;
-    a.gx = c->gx; a.gy = c->gy;
-    a.means = c->means; a.scales = c->scales; a.quats = c->quats; a.opac = c->opac; a.shs = c->shs;
-    a.payload = c->payload.as<GsPayload>();
-    a.invcov = c->invcov.as<float>();
-    a.depth_key = c->depth_key.as<uint32_t>();
-    a.rect = c->rect.as<uint16_t>();
     c->range_valid = false;
-    // the key range is folded only when this frame's depth sort can take the bucket path: while the classic sort runs (the 64-frame
-    // fallback, N beyond the bucket path's limit) nothing would reset the accumulators and the atomics would be wasted
-    if (c->dsort_can_bucket() && c->order() != GS_ORDER_INDEX && c->n > 0 && !c->small_bin_possible()) {
-        if (!c->key_range.p) {
-            HIPCHK(c, c->key_range.ensure(sizeof(uint32_t) * gs_depth_range_words()));
-            HIPCHK(c, gs_depth_range_reset(c->key_range.as<uint32_t>(), c->stream));
+    GsPreprocessArgs a{};
+    GsPreprocess2DArgs a2{};
+    if (c->kind == 1) {                                  // preprocess(::GaussianRenderer2D), forward.jl:9-33
+        a2.n = c->n; a2.W = c->cam.W; a2.H = c->cam.H;
+        a2.means = c->means; a2.scales = c->scales; a2.rots = c->quats; a2.opac = c->opac; a2.colors = c->shs;
+        if (int rc = preprocess_outputs(c, a2)) return rc;
+    } else {
+        model_head(c, a);
+        a.order = c->cfg.order;
+        // the key range is folded only when this frame's depth sort can take the bucket path: while the classic sort runs (the 64-frame
+        // fallback, N beyond the bucket path's limit) nothing would reset the accumulators and the atomics would be wasted
+        if (c->dsort_can_bucket() && c->order() != GS_ORDER_INDEX && c->n > 0 && !c->small_bin_possible()) {
+            if (!c->key_range.p) {
+                HIPCHK(c, c->key_range.ensure(sizeof(uint32_t) * gs_depth_range_words()));
+                HIPCHK(c, gs_depth_range_reset(c->key_range.as<uint32_t>(), c->stream));
+            }
+            c->range_parity ^= 1;
+            a.key_range = key_range_of(c, c->range_parity);
+            c->range_valid = true;
         }
-        c->range_parity ^= 1;
-        a.key_range = key_range_of(c, c->range_parity);
-        c->range_valid = true;
-    }
-    if (c->cfg.export_debug) {
-        const size_t w[7] = {4, 4, 2, 9, 4, 4, 4};
-        for (int i = 0; i < 7; ++i) HIPCHK(c, c->dbg[i].ensure(sizeof(float) * w[i] * n1));
-        a.dbg.ts = c->dbg[0].as<float>(); a.dbg.tps = c->dbg[1].as<float>(); a.dbg.mu = c->dbg[2].as<float>();
-        a.dbg.cov3d = c->dbg[3].as<float>(); a.dbg.cov2d = c->dbg[4].as<float>(); a.dbg.invcov = c->dbg[5].as<float>();
-        a.dbg.bbs = c->dbg[6].as<float>();
+        if (int rc = preprocess_outputs(c, a)) return rc;
     }
     StageTimer t(c, GS_STAGE_PREPROCESS);
-    HIPCHK(c, gs_launch_preprocess(a, c->cam, c->sh_row_floats(), c->stream));
+    HIPCHK(c, c->kind == 1 ? gs_launch_preprocess2d(a2, c->stream) : gs_launch_preprocess(a, c->cam, c->sh_row_floats(), c->stream));
     c->reach(gs_ctx::Stage::PREPROCESSED);
     return GS_OK;
 }
@@ -318,7 +308,7 @@ int gs_loss_l1_dssim(gs_ctx *c, const float *img, const float *gt, int32_t W, in
                      double *loss_out, int mem) {
     if (!c || !img || !gt) return GS_ERR_INVALID;
     if (W <= 0 || H <= 0 || C <= 0) return fail(c, GS_ERR_INVALID, "gs_loss_l1_dssim: bad image size");
-    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(c, GS_ERR_INVALID, "gs_loss_l1_dssim: bad mem");
+    if (const int rc = need_mem(c, "gs_loss_l1_dssim", mem)) return rc;
     if (bind_device(c)) return GS_ERR_HIP;
     const size_t n = (size_t)W * H * C;
     HIPCHK(c, c->loss_maps.ensure(sizeof(float) * 3 * n));

@@ -51,7 +51,7 @@ static void plan_rounds(const gs_ctx *c, gs_ctx::BinPlan &p) {
 // frame uses the share known so far (one frame of lag; only speed depends on it).
 static void plan_bin(gs_ctx *c) {
     gs_ctx::BinPlan p{};
-    const int64_t ntiles = (int64_t)c->gx * c->gy;
+    const int64_t ntiles = c->ntiles();
     p.tile_bits = 1;
     while ((1LL << p.tile_bits) < ntiles) ++p.tile_bits;
     p.gid_bits = 1;
@@ -81,7 +81,7 @@ static GsBin3L1 two_level_args(gs_ctx *c, const uint32_t *perm_slab, int64_t n_a
     b.rect_sorted = c->rect_sorted.as<uint32_t>(); b.table = c->l1_table.as<uint32_t>(); b.row_total = c->l1_rows.as<uint32_t>();
     b.partials = c->l1_partials.as<uint32_t>(); b.totals = c->bin_totals(); b.cranges = c->cranges.as<uint32_t>();
     b.cids = c->cids.as<uint32_t>(); b.clr = c->clr.as<uint16_t>();
-    b.tilecnt = c->tilecnt.as<uint32_t>(); b.ntiles = c->gx * c->gy;
+    b.tilecnt = c->tilecnt.as<uint32_t>(); b.ntiles = (int)c->ntiles();
     b.cap_coarse = (uint32_t)std::min<size_t>(cap_coarse, 0xFFFFFFFEu); b.cap_fine = (uint32_t)std::min<size_t>(cap_fine, 0xFFFFFFFEu);
     return b;
 }
@@ -93,24 +93,27 @@ static int two_level_count(gs_ctx *c, const uint32_t *perm_slab, int64_t n_all, 
     HIPCHK(c, c->l1_partials.ensure(sizeof(uint32_t) * gs_bin3_partial_words(n_all, ns)));
     HIPCHK(c, c->counters.ensure(GS_COUNTER_BYTES));
     HIPCHK(c, c->cranges.ensure(sizeof(uint32_t) * 2 * (size_t)ns));
-    HIPCHK(c, c->tilecnt.ensure(sizeof(uint32_t) * (size_t)c->gx * c->gy));
+    HIPCHK(c, c->tilecnt.ensure(sizeof(uint32_t) * c->ntiles()));
     GsBin3L1 b = two_level_args(c, perm_slab, n_all, nr, sdone, 0, 0);
     if (to_host) {                                                          // where settle_totals reads them: the pinned copy of the counter block
         b.host_totals = c->pinned->counters.totals; b.host_walked = c->pinned->counters.work; b.walked_src = c->counters.as<uint32_t>();
         // the previous forward's walked entries, per tile (valid only if that forward ran on this grid: prev_counters_valid)
         if (!c->counters_here()) c->prev_counters_valid = false;
-        b.tile_walked = c->prev_counters_valid ? c->last_walked : nullptr; b.n_tile_walked = c->gx * c->gy;
+        b.tile_walked = c->prev_counters_valid ? c->last_walked : nullptr; b.n_tile_walked = (int)c->ntiles();
     }
     HIPCHK(c, gs_bin3_l1_count(b, c->stream));
     return GS_OK;
 }
-// PRECONDITION of a call with done == nullptr (round 0): the caller has cleared frame_capped and have_l2 (gs_bin's reset, settle_totals' relist); this call only sets them.
+// Round 0 (done == nullptr) writes the frame's list state in c->live and only ever SETS its flags: gs_bin's fresh FrameLive or relist_in_full() comes first.
 // cap_src (round 0 of a one-round frame only): per-tile walked counts of the view slot's previous forward -> capped lists
 static int two_level_lists(gs_ctx *c, const uint32_t *perm_slab, int64_t n_all, int64_t nr, size_t coarse, size_t fine, uint32_t *ranges, uint32_t *ids_out,
                            const uint8_t *done, const uint8_t *sdone, const uint32_t *cap_src = nullptr) {
     const int ns = c->bin.ns();
+    gs_ctx::FrameLive &live = c->live;
+    assert(done || (!live.frame_capped && !live.have_l2));
+    if (!done) live.cap_src = cap_src;
     if (coarse == 0) {                                      // nothing listed: every tile range of the round is empty
-        HIPCHK(c, hipMemsetAsync(ranges, 0, sizeof(uint32_t) * 2 * (size_t)c->gx * c->gy, c->stream));
+        HIPCHK(c, hipMemsetAsync(ranges, 0, sizeof(uint32_t) * 2 * c->ntiles(), c->stream));
         return GS_OK;
     }
     const int64_t max_work = gs_bin3_max_work((int64_t)coarse, ns);
@@ -125,16 +128,16 @@ static int two_level_lists(gs_ctx *c, const uint32_t *perm_slab, int64_t n_all, 
     a.wide = (uint64_t)fine * 4ull >= (1ull << 32) || (c->cfg.debug_flags & GS_DEBUG_WIDE_CURSORS) != 0;
     a.totals = c->bin_totals(); a.cap_coarse = (uint32_t)std::min<size_t>(coarse, 0xFFFFFFFEu); a.cap_fine = (uint32_t)std::min<size_t>(fine, 0xFFFFFFFEu);
     if (cap_src && !done) {
-        const size_t nt = (size_t)c->gx * c->gy;
+        const size_t nt = (size_t)c->ntiles();
         HIPCHK(c, c->tile_nopen.ensure(sizeof(uint32_t) * nt));
         HIPCHK(c, c->smax.ensure(sizeof(uint32_t) * (size_t)ns));
         HIPCHK(c, c->tile_ext.ensure(sizeof(uint2) * nt));
         a.cap_src = cap_src; a.tile_nopen = c->tile_nopen.as<uint32_t>(); a.smax = c->smax.as<uint32_t>(); a.tile_ext = c->tile_ext.as<uint2>();
         a.ext_count = c->ext_count();
-        c->frame_capped = true;
+        live.frame_capped = true;
     }
     HIPCHK(c, gs_bin3_build_lists(a, c->stream));
-    if (!done) { c->last_l2 = a; c->have_l2 = true; }
+    if (!done) { live.last_l2 = a; live.have_l2 = true; }
     return GS_OK;
 }
 
@@ -145,7 +148,7 @@ static int two_level_lists(gs_ctx *c, const uint32_t *perm_slab, int64_t n_all, 
 #define GS_LIST_CAP_MAX_RATIO 0.15
 static int list_cap_source(gs_ctx *c, const uint32_t **out) {
     *out = nullptr;
-    const int64_t ntiles = (int64_t)c->gx * c->gy, grid = c->grid_key();
+    const int64_t ntiles = c->ntiles(), grid = c->grid_key();
     if (c->bin.path != Path::TWO_LEVEL || c->bin.n_rounds != 1 || c->cfg.list_cap == 1 || !(c->cfg.t_min > 0.0f) || ntiles <= 0) return GS_OK;
     if (c->cfg.debug_flags & GS_DEBUG_TINY_CAPS) {          // tests: every tile capped at the minimum, whatever it walked
         if (c->zero_tiles.cap < sizeof(uint32_t) * (size_t)ntiles) {
@@ -170,7 +173,7 @@ static GsBin2Args bin2_args(gs_ctx *c, int r) {
     const gs_ctx::BinPlan &p = c->bin;
     GsBin2Args b{};
     b.n = p.slab_lo[r + 1] - p.slab_lo[r]; b.n_inst = c->round_gen[r]; b.gx = c->gx; b.lo_bits = p.lo_bits; b.hi_bits = p.hi_bits; b.gid_bits = p.gid_bits;
-    b.offsets = (r ? c->offsets_r : c->offsets).as<uint32_t>(); b.perm = c->perm_ptr ? c->perm_ptr + p.slab_lo[r] : nullptr;
+    b.offsets = (r ? c->offsets_r : c->offsets).as<uint32_t>(); b.perm = c->live.perm_ptr ? c->live.perm_ptr + p.slab_lo[r] : nullptr;
     b.rect = (r ? c->rect_r : c->rect).as<uint16_t>();
     b.cs = c->cs.as<uint32_t>(); b.block_hist = c->table.as<uint32_t>(); b.digit_total = c->digit_total.as<uint32_t>();
     b.buf_a = c->words.as<uint32_t>(); b.ids_out = c->ids.as<uint32_t>() + c->round_ids_off[r]; b.ballot_ranks = c->cfg.rank_mode != 0;
@@ -182,9 +185,8 @@ static GsBin2Args bin2_args(gs_ctx *c, int r) {
 static int bin_round_two_level(gs_ctx *c, int r) {
     const gs_ctx::BinPlan &p = c->bin;
     const int64_t lo = p.slab_lo[r], nr = p.slab_lo[r + 1] - lo;
-    const int64_t ntiles = (int64_t)c->gx * c->gy;
-    const uint32_t *perm = c->perm_ptr + lo;
-    HIPCHK(c, c->ranges_r[r].ensure(sizeof(uint32_t) * 2 * (size_t)ntiles));
+    const uint32_t *perm = c->live.perm_ptr + lo;
+    HIPCHK(c, c->ranges_r[r].ensure(sizeof(uint32_t) * 2 * c->ntiles()));
     HIPCHK(c, c->sdone.ensure((size_t)p.ns()));
     {
         StageTimer t(c, GS_STAGE_COUNT_SCAN);
@@ -211,13 +213,12 @@ static int bin_round_two_level(gs_ctx *c, int r) {
 int bin_round(gs_ctx *c, int r) {
     if (c->bin.path == Path::TWO_LEVEL) return bin_round_two_level(c, r);
     const int64_t lo = c->bin.slab_lo[r], nr = c->bin.slab_lo[r + 1] - lo;
-    const int64_t ntiles = (int64_t)c->gx * c->gy;
-    const uint32_t *perm = c->perm_ptr + lo;
+    const uint32_t *perm = c->live.perm_ptr + lo;
     HIPCHK(c, c->live2d.ensure(sizeof(uint32_t) * 2 * (size_t)(c->gx + 1) * (c->gy + 1)));      // the table + the row-pass scratch
-    HIPCHK(c, c->rect_r.ensure(sizeof(uint16_t) * 4 * (size_t)(c->n ? c->n : 1)));
+    HIPCHK(c, c->rect_r.ensure(sizeof(uint16_t) * 4 * c->n1()));
     HIPCHK(c, c->offsets_r.ensure(sizeof(uint32_t) * ((size_t)nr + 1)));
     HIPCHK(c, c->live_total.ensure(sizeof(uint32_t) * GS_MAX_ROUNDS));
-    HIPCHK(c, c->ranges_r[r].ensure(sizeof(uint32_t) * 2 * (size_t)ntiles));
+    HIPCHK(c, c->ranges_r[r].ensure(sizeof(uint32_t) * 2 * c->ntiles()));
     {
         StageTimer t(c, GS_STAGE_COUNT_SCAN);
         HIPCHK(c, gs_launch_live_prefix(c->tile_done.as<uint8_t>(), c->gx, c->gy, c->live2d.as<uint32_t>(),
@@ -288,18 +289,16 @@ int settle_totals(gs_ctx *c, bool *redo, bool may_relist) {
     const CounterBlock &h = c->pinned->counters;
     const uint32_t coarse = h.totals[0], fine_slab = h.totals[1];
     if (int rc = totals_arrived(c, coarse, fine_slab, h.totals[2], h.work)) return rc;
-    if (!c->spec_lists) return GS_OK;
-    c->spec_lists = false;
-    if ((size_t)coarse <= c->spec_cap_coarse && (size_t)fine_slab <= c->spec_cap_fine) return GS_OK;
+    if (!c->live.spec_lists || c->live.speculation_held(coarse, fine_slab)) return GS_OK;
     if (!may_relist) { c->fall_back(gs_ctx::Stage::PREPROCESSED); return GS_OK; }                  // the frame is being abandoned (a new gs_preprocess / gs_bin follows)
     // a list outgrew its buffer: nothing was listed (all ranges empty).  Grow and list again with the real totals -- in FULL: the caps'
     // source is the slot's walked array, and the forward that just ran on the empty lists has overwritten it with zeros (rare frame:
     // a model that outgrew its buffers; full lists are the fast choice there)
     HIPCHK(c, c->ids.ensure(sizeof(uint32_t) * (size_t)(c->n_inst ? c->n_inst : 1)));
-    c->cap_src = nullptr; c->frame_capped = false; c->have_l2 = false;
+    c->live.relist_in_full();
     {
         StageTimer t(c, GS_STAGE_TILE_SORT);
-        if (int rc = two_level_lists(c, c->perm_ptr, c->n, c->bin.slab_lo[1], (size_t)coarse, (size_t)fine_slab, c->ranges.as<uint32_t>(), c->ids.as<uint32_t>(), nullptr, nullptr,
+        if (int rc = two_level_lists(c, c->live.perm_ptr, c->n, c->bin.slab_lo[1], (size_t)coarse, (size_t)fine_slab, c->ranges.as<uint32_t>(), c->ids.as<uint32_t>(), nullptr, nullptr,
                                      nullptr)) return rc;
     }
     if (redo) *redo = true;
@@ -308,8 +307,8 @@ int settle_totals(gs_ctx *c, bool *redo, bool may_relist) {
 
 // The depth order of the frame (CUDA.sortperm, forward.jl:103) -> c->perm.  Also called by gs_get_array for a frame binned by the small
 // path, which needs no global order.
-int depth_order(gs_ctx *c, uint32_t **perm_out) {
-    const size_t n1 = c->n ? (size_t)c->n : 1;
+int depth_order(gs_ctx *c) {
+    const size_t n1 = c->n1();
     StageTimer t(c, GS_STAGE_DEPTH_SORT);
     HIPCHK(c, c->pairs_a.ensure(sizeof(uint64_t) * n1));
     HIPCHK(c, c->pairs_b.ensure(sizeof(uint64_t) * n1));
@@ -336,14 +335,14 @@ int depth_order(gs_ctx *c, uint32_t **perm_out) {
         HIPCHK(c, gs_radix_sort_u64(c->pairs_a.as<uint64_t>(), c->pairs_b.as<uint64_t>(), c->n, 32, 64, c->table.as<uint32_t>(),
                                     c->digit_total.as<uint32_t>(), &in_b, c->stream, c->cfg.rank_mode != 0, perm, c->depth_key.as<uint32_t>()));
     }
-    *perm_out = perm;
+    c->live.perm_ptr = perm;
     return GS_OK;
 }
 
 // Small frames (gs_bin_small.hip): the whole of gs_bin in one launch, one workgroup per tile.  The ids buffer holds every (gaussian, tile)
 // pair the path admits, so nothing is speculative; the totals travel to the host as on the two-level path.
 static int bin_small(gs_ctx *c) {
-    const size_t n = (size_t)c->n, nt = (size_t)c->gx * c->gy;
+    const size_t n = (size_t)c->n, nt = (size_t)c->ntiles();
     HIPCHK(c, c->ids.ensure(sizeof(uint32_t) * n * nt));
     if (c->range_valid)                                                     // (gs_preprocess judged otherwise and folded the key range: nobody will consume it)
         HIPCHK(c, gs_depth_range_reset(key_range_of(c, c->range_parity), c->stream, 1));
@@ -355,15 +354,14 @@ static int bin_small(gs_ctx *c) {
     if (!c->counters_here()) c->prev_counters_valid = false;
     a.tile_walked = c->prev_counters_valid ? c->last_walked : nullptr; a.n_tile_walked = (int)nt;
     {   // the rows the composite backward accumulates into (64 B per gaussian; nothing touches them between here and that kernel)
-        const size_t bytes = (c->cfg.deterministic ? sizeof(long long) : sizeof(float)) * GS_G2D_STRIDE * n;
-        HIPCHK(c, c->g2d.ensure(bytes));
-        a.zero = c->g2d.as<uint4>(); a.zero_words16 = bytes / sizeof(uint4);
+        HIPCHK(c, c->g2d.ensure(c->g2d_bytes()));                          // (this path has n >= 1: every row of the model, no more)
+        a.zero = c->g2d.as<uint4>(); a.zero_words16 = c->g2d_bytes() / sizeof(uint4);
     }
     {
         StageTimer t(c, GS_STAGE_TILE_SORT);
         HIPCHK(c, gs_bin_small(a, c->stream));
     }
-    c->g2d_clean = true;
+    c->live.g2d_clean = true;
     HIPCHK(c, hipEventRecord(c->ev_count, c->stream));
     c->pending_totals = true;
     return GS_OK;
@@ -371,7 +369,7 @@ static int bin_small(gs_ctx *c) {
 
 // Two-level path (gs_bin3.hip): count, totals on their way to the host, then the lists -- speculatively when there is one round and buffers to launch against
 static int bin_two_level(gs_ctx *c) {
-    uint32_t *perm = c->perm_ptr;
+    uint32_t *perm = c->live.perm_ptr;
     const int64_t n0 = c->bin.slab_lo[1];                                   // list positions of round 0
     {
         StageTimer t(c, GS_STAGE_COUNT_SCAN);
@@ -383,17 +381,18 @@ static int bin_two_level(gs_ctx *c) {
     HIPCHK(c, hipEventRecord(c->ev_count, c->stream));
     c->pending_totals = true;
     const size_t cap_coarse = std::min(c->cids.cap / sizeof(uint32_t), c->clr.cap / sizeof(uint16_t)), cap_fine = c->ids.cap / sizeof(uint32_t);
-    if (int rc = list_cap_source(c, &c->cap_src)) return rc;
+    const uint32_t *cap_src = nullptr;
+    if (int rc = list_cap_source(c, &cap_src)) return rc;
     if (c->bin.n_rounds == 1 && cap_coarse > 0 && cap_fine > 0) {
-        c->spec_lists = true; c->spec_cap_coarse = cap_coarse; c->spec_cap_fine = cap_fine;
+        c->live.speculate(cap_coarse, cap_fine);
         StageTimer t(c, GS_STAGE_TILE_SORT);
-        return two_level_lists(c, perm, c->n, n0, cap_coarse, cap_fine, c->ranges.as<uint32_t>(), c->ids.as<uint32_t>(), nullptr, nullptr, c->cap_src);
+        return two_level_lists(c, perm, c->n, n0, cap_coarse, cap_fine, c->ranges.as<uint32_t>(), c->ids.as<uint32_t>(), nullptr, nullptr, cap_src);
     }
     // first frame of a ctx, or a slab frame: the host needs the totals now
     if (int rc = settle_totals(c, nullptr, true)) return rc;
     HIPCHK(c, c->ids.ensure(sizeof(uint32_t) * (size_t)(c->n_inst ? c->n_inst : 1)));
     StageTimer t(c, GS_STAGE_TILE_SORT);
-    return two_level_lists(c, perm, c->n, n0, (size_t)c->n_coarse, (size_t)c->round_gen[0], c->ranges.as<uint32_t>(), c->ids.as<uint32_t>(), nullptr, nullptr, c->cap_src);
+    return two_level_lists(c, perm, c->n, n0, (size_t)c->n_coarse, (size_t)c->round_gen[0], c->ranges.as<uint32_t>(), c->ids.as<uint32_t>(), nullptr, nullptr, cap_src);
 }
 
 // RADIX64: explicit 64-bit tile|id instances, two radix passes (fallback; identical lists)
@@ -403,7 +402,7 @@ static int radix64_lists(gs_ctx *c) {
     HIPCHK(c, c->inst_b.ensure(sizeof(uint64_t) * ni1));
     {
         StageTimer t(c, GS_STAGE_EMIT);
-        HIPCHK(c, gs_launch_emit(c->rect.as<uint16_t>(), c->perm_ptr, c->offsets.as<uint32_t>(), c->inst_a.as<uint64_t>(), c->n, c->gx, c->stream));
+        HIPCHK(c, gs_launch_emit(c->rect.as<uint16_t>(), c->live.perm_ptr, c->offsets.as<uint32_t>(), c->inst_a.as<uint64_t>(), c->n, c->gx, c->stream));
     }
     uint64_t *sorted = nullptr;
     {
@@ -414,7 +413,7 @@ static int radix64_lists(gs_ctx *c) {
         sorted = in_b ? c->inst_b.as<uint64_t>() : c->inst_a.as<uint64_t>();
     }
     StageTimer t(c, GS_STAGE_RANGES);
-    HIPCHK(c, gs_launch_ranges(sorted, c->n_inst, c->ranges.as<uint32_t>(), (int64_t)c->gx * c->gy, c->stream));
+    HIPCHK(c, gs_launch_ranges(sorted, c->n_inst, c->ranges.as<uint32_t>(), c->ntiles(), c->stream));
     HIPCHK(c, gs_launch_split_ids(sorted, c->ids.as<uint32_t>(), c->n_inst, c->stream));
     return GS_OK;
 }
@@ -424,7 +423,7 @@ static int bin_radix(gs_ctx *c) {
     const size_t n = (size_t)c->n;
     const bool fast = c->bin.path == Path::RADIX32, slabs = c->bin.n_rounds > 1;
     const int64_t n0 = c->bin.slab_lo[1];                                   // list positions of round 0
-    uint32_t *perm = c->perm_ptr;
+    uint32_t *perm = c->live.perm_ptr;
     PinnedWords *h = c->pinned;
     {
         StageTimer t(c, GS_STAGE_COUNT_SCAN);
@@ -438,7 +437,7 @@ static int bin_radix(gs_ctx *c) {
     HIPCHK(c, hipMemcpyAsync(&h->readback[1], c->offsets.as<uint32_t>() + n0, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (!c->counters_here()) c->prev_counters_valid = false;
     if (c->prev_counters_valid) {
-        HIPCHK(c, gs_launch_sum_tiles(c->last_walked, c->tile_work.as<uint32_t>(), c->gx * c->gy, c->counters.as<unsigned long long>(), c->stream));
+        HIPCHK(c, gs_launch_sum_tiles(c->last_walked, c->tile_work.as<uint32_t>(), (int)c->ntiles(), c->counters.as<unsigned long long>(), c->stream));
         HIPCHK(c, hipMemcpyAsync(h->walked_prev, c->counters.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipEventRecord(c->ev_count, c->stream));
@@ -469,7 +468,7 @@ static int bin_radix(gs_ctx *c) {
 // The frame as its plan says: the depth order (unless the path needs none), the buffers every path writes, the path
 static int bin_frame(gs_ctx *c) {
     const Path path = c->bin.path;
-    if (c->order() != GS_ORDER_INDEX && path != Path::SMALL) { if (int rc = depth_order(c, &c->perm_ptr)) return rc; }
+    if (c->order() != GS_ORDER_INDEX && path != Path::SMALL) { if (int rc = depth_order(c)) return rc; }
     HIPCHK(c, c->ranges.ensure(sizeof(uint32_t) * 2 * c->ntiles1()));
     HIPCHK(c, c->counters.ensure(GS_COUNTER_BYTES));
     if (path != Path::SMALL) HIPCHK(c, c->block_sums.ensure(sizeof(uint32_t) * 3 * ((size_t)c->n / 2048 + 2)));
@@ -480,13 +479,13 @@ static int bin_frame(gs_ctx *c) {
 
 extern "C" int gs_bin(gs_ctx *c, int32_t gx, int32_t gy) {
     if (!c) return GS_ERR_INVALID;
-    if (c->stage < gs_ctx::Stage::PREPROCESSED) return fail(c, GS_ERR_INVALID, "gs_bin: gs_preprocess first");
+    if (const int rc = need_stage(c, gs_ctx::Stage::PREPROCESSED, "gs_bin: gs_preprocess first")) return rc;
     if ((gx != 0 || gy != 0) && (gx != c->gx || gy != c->gy))
         return fail(c, GS_ERR_UNSUPPORTED, "gs_bin: blocks must equal ceil(W/16) x ceil(H/16)");
     if (bind_device(c)) return GS_ERR_HIP;
     if (int rc = settle_totals(c, nullptr, false)) return rc;               // a frame that was binned but never rendered
     // the frame's live state starts here, whatever its path; the plan is fixed from here to the next gs_bin
-    c->frame_capped = false; c->have_l2 = false; c->cap_src = nullptr; c->spec_lists = false; c->g2d_clean = false; c->perm_ptr = nullptr;
+    c->live = gs_ctx::FrameLive{};
     plan_bin(c);
     return bin_frame(c);
 }

@@ -15,21 +15,18 @@ extern "C" {
 
 int gs_backward_camera(gs_ctx *c, float *out, int mem) {
     if (!c) return GS_ERR_INVALID;
-    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_backward_camera: 3-D renderer only");
+    if (const int rc = need_3d(c, "gs_backward_camera")) return rc;
     if (!out) return fail(c, GS_ERR_INVALID, "gs_backward_camera: NULL argument");
-    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(c, GS_ERR_INVALID, "gs_backward_camera: bad mem");
-    if (c->stage < Stage::COMPOSITE_ADJOINT)
-        return fail(c, GS_ERR_INVALID, "gs_backward_camera: gs_backward first (the frame's colour backward leaves the rows this call reads; a call that steps the model drops them)");
+    if (const int rc = need_mem(c, "gs_backward_camera", mem)) return rc;
+    if (const int rc = need_stage(c, Stage::COMPOSITE_ADJOINT,
+                                  "gs_backward_camera: gs_backward first (the frame's colour backward leaves the rows this call reads; a call that steps the model drops them)")) return rc;
     if (bind_device(c)) return GS_ERR_HIP;
-    const bool det = c->cfg.deterministic != 0;
     const int64_t rows = gs_camera_grad_rows(c->n);
     HIPCHK(c, c->camera_partials.ensure(GS_CAMERA_OUT_BYTES + sizeof(double) * GS_CAMERA_GRAD_VALUES * (size_t)rows));
     float *stage = c->camera_partials.as<float>();
     GsCameraGradArgs a{};
-    a.n = c->n; a.sh_degree = c->active_sh_degree(); a.sh_stride = c->sh_row_floats();     // the active degree on the stored rows, as the backward has it
-    a.means = c->means; a.scales = c->scales; a.quats = c->quats; a.opac = c->opac; a.shs = c->shs;
-    a.g2d = det ? nullptr : c->g2d.as<float>();
-    a.g2d_fixed = det ? c->g2d.as<long long>() : nullptr;
+    model_head(c, a);                                                      // the active degree on the stored rows, as the backward has it
+    c->rows(c->g2d).into(a);
     a.partials = reinterpret_cast<double *>(c->camera_partials.as<char>() + GS_CAMERA_OUT_BYTES);
     HIPCHK(c, gs_launch_camera_grad(a, c->cam, mem == GS_MEM_HOST ? stage : out, c->stream));
     if (mem == GS_MEM_HOST) {

@@ -10,7 +10,7 @@ using Update = BackwardPlan::Update;
 // Launch order of the frame's forward (gs_config.schedule 3 / 4): what the last forward under the same view slot measured, else
 // (schedule 4) what this ctx's previous slot-less forward measured; null = no history: tile order.  *split: the order's split-count word.
 static const uint32_t *forward_order(gs_ctx *c, const uint32_t **split) {
-    const int64_t ntiles = (int64_t)c->gx * c->gy;
+    const int64_t ntiles = c->ntiles();
     if (!lpt_schedule(c) || ntiles <= 0 || ntiles > GS_LPT_MAX_TILES) return nullptr;
     const int k = order_index(c);
     if (k == GS_MAX_VIEW_SLOTS && c->cfg.schedule != 4) return nullptr;
@@ -26,7 +26,7 @@ static const uint32_t *forward_order(gs_ctx *c, const uint32_t **split) {
 
 // pixel parts (waves per tile, each owning 4 / parts of its pixel strips) that fit the wave slots when a tile runs as `units` waves already
 static int parts_that_fit(const gs_ctx *c, int units) {
-    const long long w = (long long)units * c->gx * c->gy;
+    const long long w = (long long)units * c->ntiles();
     return 4 * w <= c->wave_slots ? 4 : 2 * w <= c->wave_slots ? 2 : 1;
 }
 
@@ -37,7 +37,7 @@ static void plan_frame(gs_ctx *c, const uint32_t *order, const uint32_t *order_s
     gs_ctx::FramePlan p;
     const int want = c->cfg.tile_parts;
     // launches that composite whole tiles, one wave each: no early-out, slab rounds, capped lists
-    const bool whole = !(c->cfg.t_min > 0.0f) || c->bin.n_rounds > 1 || c->frame_capped;
+    const bool whole = !(c->cfg.t_min > 0.0f) || c->bin.n_rounds > 1 || c->live.frame_capped;
     p.parts = p.bwd_parts = want == 1 || whole ? 1 : (want == 2 || want == 4) ? want : parts_that_fit(c, 1);
     p.order = p.bwd_order = order;
     // The backward runs in the forward's order while the order kernel works beside it, on the side stream, for the slot's next frame; else
@@ -50,7 +50,7 @@ static void plan_frame(gs_ctx *c, const uint32_t *order, const uint32_t *order_s
     if (order && p.split && c->snap_walked.p && may_split) {
         p.snap = Snap::HEAVY;                                              // ... and leave snapshots for the list segments of their backward
         p.snap_walked = c->snap_walked.as<uint32_t>() + (size_t)c->snap_parity * GS_SEG_SLOTS;
-    } else if (hist && want == 0 && p.parts > 1 && !lpt_schedule(c) && c->kind == 0 && (int64_t)c->gx * c->gy > 0) {
+    } else if (hist && want == 0 && p.parts > 1 && !lpt_schedule(c) && c->kind == 0 && c->ntiles() > 0) {
         // small grids (the automatic choice gave pixel parts: full lists, one round, at most half as many tiles as wave slots; no launch order):
         // with the slot's previous walk at hand EVERY tile's backward runs as list segments instead, the forward's waves leave the
         // snapshots.  Two segments, and as many pixel parts on top as still fit the wave slots (C1: 4 x 2 waves per tile; C2: 1 x 2)
@@ -81,11 +81,11 @@ GsCompositeArgs composite_args(gs_ctx *c, bool bwd, int r, bool debug) {
         ++a.nseg;
     }
     a.ranges = r == 0 ? c->ranges.as<uint32_t>() : c->ranges_r[r].as<uint32_t>(); a.ids = c->ids.as<uint32_t>() + c->round_ids_off[r];
-    if (bwd) { a.g2d = c->cfg.deterministic ? nullptr : c->g2d.as<float>(); a.g2d_fixed = c->cfg.deterministic ? c->g2d.as<long long>() : nullptr; }
+    if (bwd) c->rows_mut(c->g2d).into(a);
     a.tile_order = bwd || debug ? p.bwd_order : p.order; a.order_len = a.tile_order ? lpt_order_entries(c) : 0;
     a.parts = bwd ? p.bwd_parts : p.parts;
-    a.split_ok = a.tile_order && p.split && !c->frame_capped;
-    if (c->frame_capped && c->bin.n_rounds == 1) {
+    a.split_ok = a.tile_order && p.split && !c->live.frame_capped;
+    if (c->live.frame_capped && c->bin.n_rounds == 1) {
         a.tile_ext = c->tile_ext.as<uint2>();                              // the lists end where gs_bin / the forward stopped writing them
         if (!bwd) {                                                        // the forward's wave extends its tile's list when it must
             a.cranges = c->cranges.as<uint32_t>(); a.cids = c->cids.as<uint32_t>(); a.clr = c->clr.as<uint16_t>();
@@ -107,7 +107,7 @@ GsCompositeArgs composite_args(gs_ctx *c, bool bwd, int r, bool debug) {
 // the backward waits for it: it is its only source of a longest-first order.
 static int build_frame_order(gs_ctx *c) {
     gs_ctx::FramePlan &p = c->plan;
-    const int64_t ntiles = (int64_t)c->gx * c->gy;
+    const int64_t ntiles = c->ntiles();
     if (!lpt_schedule(c) || ntiles <= 0 || ntiles > GS_LPT_MAX_TILES) return GS_OK;
     const int k = order_index(c);
     gs_ctx::ViewSlot &vs = c->slots[k];
@@ -151,7 +151,7 @@ static int build_frame_order(gs_ctx *c) {
 // backwards alike -- finds the blended one.  Over black nothing is launched.
 int blend_background(gs_ctx *c) {
     if (!c->has_background()) return GS_OK;
-    HIPCHK(c, gs_launch_blend_background(c->img(), c->tr(), (size_t)c->cam.W * c->cam.H, c->background, c->stream));
+    HIPCHK(c, gs_launch_blend_background(c->img(), c->tr(), c->pixels(), c->background, c->stream));
     return GS_OK;
 }
 
@@ -175,8 +175,8 @@ int gs_set_view_slot(gs_ctx *c, int32_t slot) {
 // the composite launch of round r of the frame (r = 0 unless the frame is binned in depth slabs)
 static int enqueue_forward_round(gs_ctx *c, int r) {
     gs_ctx::FramePlan &p = c->plan;
-    if (p.snap != Snap::NONE && !c->frame_capped) {                         // this launch leaves snapshots (composite_args)
-        HIPCHK(c, c->snap.ensure(sizeof(float) * (p.snap == Snap::ALL ? (size_t)c->gx * c->gy * (size_t)(p.seg_n - 1) * 4 * 256 : (size_t)GS_SEG_SLOTS * GS_SEG_SNAP_FLOATS)));
+    if (p.snap != Snap::NONE && !c->live.frame_capped) {                         // this launch leaves snapshots (composite_args)
+        HIPCHK(c, c->snap.ensure(sizeof(float) * (p.snap == Snap::ALL ? (size_t)c->ntiles() * (size_t)(p.seg_n - 1) * 4 * 256 : (size_t)GS_SEG_SLOTS * GS_SEG_SNAP_FLOATS)));
         HIPCHK(c, c->ensure_bwd_counters());
     }
     GsCompositeArgs a = composite_args(c, false, r);
@@ -199,11 +199,10 @@ static int enqueue_forward_round(gs_ctx *c, int r) {
 
 int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
     if (!c) return GS_ERR_INVALID;
-    if (c->stage < Stage::BINNED) return fail(c, GS_ERR_INVALID, "gs_forward: gs_bin first");
-    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(c, GS_ERR_INVALID, "gs_forward: bad mem");
+    if (const int rc = need_stage(c, Stage::BINNED, "gs_forward: gs_bin first")) return rc;
+    if (const int rc = need_mem(c, "gs_forward", mem)) return rc;
     if (bind_device(c)) return GS_ERR_HIP;
-    const size_t px = (size_t)c->cam.W * c->cam.H;
-    const size_t ntiles = (size_t)c->gx * c->gy, nt1 = c->ntiles1();
+    const size_t px = c->pixels(), ntiles = (size_t)c->ntiles(), nt1 = c->ntiles1();
     if (!c->bound_image) {
         HIPCHK(c, c->image.ensure(sizeof(float) * 3 * px));
         HIPCHK(c, c->trans.ensure(sizeof(float) * px));
@@ -242,7 +241,7 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
     // fall back further), and all of them run on c->stream, in front of this launch.  Only when the buffer stands as the coming backward
     // will want it (same n, same mode: DevBuf never shrinks, so its ensure() will not move it) and is not clean already; a ctx's first
     // frame, a ctx that only renders and a model that grew keep the fill command in run_backward.
-    c->fwd_fills_g2d = c->tail_fill() && !c->g2d_clean && c->g2d.p && c->g2d.cap >= c->g2d_bytes() &&
+    c->fwd_fills_g2d = c->tail_fill() && !c->live.g2d_clean && c->g2d.p && c->g2d.cap >= c->g2d_bytes() &&
                        gs_composite_fill_blocks(c->g2d.p, c->g2d_bytes()) > 0;
     for (int r = 0; r < R; ++r) {
         if (r > 0) { if (int rc = bin_round(c, r)) return rc; }
@@ -254,7 +253,7 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
             if (redo) { if (int rc = enqueue_forward_round(c, 0)) return rc; }     // the lists outgrew a buffer and were rebuilt: composite again, same plan
         }
     }
-    if (c->fwd_fills_g2d) c->g2d_clean = true;                             // (a forward enqueued again after settle_totals filled again: idempotent)
+    if (c->fwd_fills_g2d) c->live.g2d_clean = true;                             // (a forward enqueued again after settle_totals filled again: idempotent)
     if (vs) vs->walk_written(c->counters_grid);
     if (int rc = build_frame_order(c)) return rc;
     const hipMemcpyKind kind = mem == GS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
@@ -271,17 +270,16 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
 // allocated: a refused call leaves the frame and every buffer as they were.  grads null with a fused update: the targets are the model.
 static int plan_backward(gs_ctx *c, const float *dC, int mem, const gs_grads *grads, int flags, BackwardPlan &p) {
     if (!c) return GS_ERR_INVALID;
-    if (p.fused() && c->kind != 0)
-        return fail(c, GS_ERR_UNSUPPORTED, p.update == Update::SGD ? "gs_backward_sgd: 3-D renderer only" : "gs_backward_adam: 3-D renderer only");
-    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_backward: gs_forward first");
+    if (p.fused()) { if (const int rc = need_3d(c, p.update == Update::SGD ? "gs_backward_sgd" : "gs_backward_adam")) return rc; }
+    if (const int rc = need_stage(c, Stage::RENDERED, "gs_backward: gs_forward first")) return rc;
     const bool params_only = (flags & GS_BWD_PARAMS_ONLY) != 0, composite_only = (flags & GS_BWD_COMPOSITE_ONLY) != 0;
     if (params_only && composite_only) return fail(c, GS_ERR_INVALID, "gs_backward: COMPOSITE_ONLY and PARAMS_ONLY exclude each other");
     const int chain = (flags & (GS_BWD_PARAMS_SH | GS_BWD_PARAMS_GEOM)) >> 3;             // bit 0: SH kernel, bit 1: geometry chain; 0 = both
     if (chain && !params_only) return fail(c, GS_ERR_INVALID, "gs_backward: GS_BWD_PARAMS_SH / _GEOM need GS_BWD_PARAMS_ONLY");
-    if (chain && c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_backward: GS_BWD_PARAMS_SH / _GEOM: 3-D renderer only");
-    if (params_only && c->stage < Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_backward: GS_BWD_PARAMS_ONLY needs a GS_BWD_COMPOSITE_ONLY call on this frame");
+    if (chain) { if (const int rc = need_3d(c, "gs_backward: GS_BWD_PARAMS_SH / _GEOM")) return rc; }
+    if (params_only) { if (const int rc = need_stage(c, Stage::COMPOSITE_ADJOINT, "gs_backward: GS_BWD_PARAMS_ONLY needs a GS_BWD_COMPOSITE_ONLY call on this frame")) return rc; }
     if ((!dC && !params_only) || (!grads && !p.fused() && !composite_only)) return fail(c, GS_ERR_INVALID, "gs_backward: NULL argument");
-    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(c, GS_ERR_INVALID, "gs_backward: bad mem");
+    if (const int rc = need_mem(c, "gs_backward", mem)) return rc;
     p.composite = !params_only;
     p.chain = composite_only ? 0 : chain ? chain : 3;
     if (!p.fused() && (flags & GS_BWD_OVERWRITE)) p.update = Update::OVERWRITE;
@@ -289,7 +287,7 @@ static int plan_backward(gs_ctx *c, const float *dC, int mem, const gs_grads *gr
     p.dC = dC;
     p.stage_dC = mem == GS_MEM_HOST && p.composite;
     p.host_sync = mem == GS_MEM_HOST;
-    p.fill_g2d = p.composite && !c->g2d_clean;                             // (the fill command itself, and why it is in line: run_backward)
+    p.fill_g2d = p.composite && !c->live.g2d_clean;                             // (the fill command itself, and why it is in line: run_backward)
     // An overwriting backward of the 3-D renderer, both phases in this call, no fused optimiser: the zeros of the SH gradient rows no pixel
     // touched (63 % of the gaussians at C3, 90 % at C5; 192 B each at degree 3) depend on nothing -- the fill workgroups at the end of the
     // composite backward's grid zero ALL of d_shs, and gs_sh_bwd_kernel then stores the live rows only.  Past the caches, like that kernel's
@@ -303,18 +301,15 @@ static int plan_backward(gs_ctx *c, const float *dC, int mem, const gs_grads *gr
 // The plan, enqueued: staging copy, the composite adjoint with what is the backward's alone, the per-gaussian kernels, the host's wait.
 static int run_backward(gs_ctx *c, const BackwardPlan &p) {
     if (bind_device(c)) return GS_ERR_HIP;
-    const size_t px = (size_t)c->cam.W * c->cam.H, n1 = c->n ? (size_t)c->n : 1;
+    const size_t px = c->pixels();
     const float *dC_dev = p.dC;
     if (p.stage_dC) {
         HIPCHK(c, c->stage_in.ensure(sizeof(float) * 3 * px));
         HIPCHK(c, hipMemcpyAsync(c->stage_in.p, p.dC, sizeof(float) * 3 * px, hipMemcpyHostToDevice, c->stream));
         dC_dev = c->stage_in.as<float>();
     }
-    const bool det = c->cfg.deterministic != 0;
     HIPCHK(c, c->g2d.ensure(c->g2d_bytes()));
     HIPCHK(c, c->ensure_bwd_counters());
-    const float *g2d = det ? nullptr : c->g2d.as<float>();
-    const long long *g2d_fixed = det ? c->g2d.as<long long>() : nullptr;
     if (p.composite) {
         GsCompositeArgs a = composite_args(c, true, 0);                    // order, parts, list segments: as the frame's plan says
         a.dC = c->last_dC = dC_dev;
@@ -329,7 +324,7 @@ static int run_backward(gs_ctx *c, const BackwardPlan &p) {
         // (a small frame's gs_bin kernel has cleared them already: gs_bin_small.hip)
         // (... and otherwise the fill workgroups of the frame's forward: gs_forward)
         if (p.fill_g2d) HIPCHK(c, hipMemsetAsync(c->g2d.p, 0, c->g2d_bytes(), c->stream));
-        c->g2d_clean = false;
+        c->live.rows_dirtied();
         {
             StageTimer t(c, GS_STAGE_COMPOSITE_BWD);                       // the kernel alone (what rocprof reports for it)
             HIPCHK(c, gs_launch_composite_bwd(a, c->stream));
@@ -341,20 +336,14 @@ static int run_backward(gs_ctx *c, const BackwardPlan &p) {
         GsPreprocess2DBwdArgs b2{};
         b2.n = c->n; b2.W = c->cam.W; b2.H = c->cam.H;
         b2.scales = c->scales; b2.rots = c->quats; b2.opac = c->opac;
-        b2.g2d = g2d; b2.g2d_fixed = g2d_fixed; b2.overwrite = overwrite;
+        c->rows(c->g2d).into(b2); b2.overwrite = overwrite;
         b2.d_means = p.target[0]; b2.d_scales = p.target[1]; b2.d_rots = p.target[2]; b2.d_opac = p.target[3]; b2.d_colors = p.target[4];
         StageTimer t(c, GS_STAGE_PREPROCESS_BWD);
         HIPCHK(c, gs_launch_preprocess2d_bwd(b2, c->stream));
     } else if (p.chain) {
-        GsPreprocessBwdArgs b{};
-        b.n = c->n; b.sh_degree = c->active_sh_degree(); b.sh_stride = c->sh_row_floats();
-        b.means = c->means; b.scales = c->scales; b.quats = c->quats; b.opac = c->opac; b.shs = c->shs;
-        b.g2d = g2d; b.g2d_fixed = g2d_fixed;
-        HIPCHK(c, c->dpc.ensure(sizeof(float) * 4 * n1));
-        b.dpc = c->dpc.as<float>();
-        b.overwrite = overwrite; b.shs_zeroed = p.fill_shs ? 1 : 0;
-        b.sgd_scale = p.update == Update::SGD ? -p.lr : 0.0f;             // with the model as target this IS the SGD step
-        b.d_means = p.target[0]; b.d_scales = p.target[1]; b.d_quats = p.target[2]; b.d_opac = p.target[3]; b.d_shs = p.target[4];
+        HIPCHK(c, c->dpc.ensure(sizeof(float) * 4 * c->n1()));
+        const GsPreprocessBwdArgs b = chain_args(c, c->rows(c->g2d), c->dpc.as<float>(), p.target, overwrite, p.fill_shs ? 1 : 0,
+                                                 p.update == Update::SGD ? -p.lr : 0.0f);   // with the model as target this IS the SGD step
         const GsPreprocessBwdMode mode{p.chain, p.adam, p.update == Update::ADAM_DENSE ? 1 : p.update == Update::ADAM_SELECTIVE ? 2 : 0};
         StageTimer t(c, GS_STAGE_PREPROCESS_BWD);
         HIPCHK(c, gs_launch_preprocess_bwd(b, c->cam, c->stream, mode));
@@ -407,17 +396,17 @@ int gs_backward_adam(gs_ctx *c, const float *dC, int mem, const gs_grads *exp_av
 
 int gs_color_grads_pack(gs_ctx *c, float *drgb) {
     if (!c || !drgb) return GS_ERR_INVALID;
-    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_color_grads_pack: 3-D renderer only");
-    if (c->stage < Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_color_grads_pack: gs_backward first");
+    if (const int rc = need_3d(c, "gs_color_grads_pack")) return rc;
+    if (const int rc = need_stage(c, Stage::COMPOSITE_ADJOINT, "gs_color_grads_pack: gs_backward first")) return rc;
     if (bind_device(c)) return GS_ERR_HIP;
-    const bool det = c->cfg.deterministic != 0;
-    HIPCHK(c, gs_launch_pack_drgb(det ? nullptr : c->g2d.as<float>(), det ? c->g2d.as<long long>() : nullptr, drgb, c->n, c->stream));
+    const gs_ctx::Rows rows = c->rows(c->g2d);
+    HIPCHK(c, gs_launch_pack_drgb(rows.g2d, rows.g2d_fixed, drgb, c->n, c->stream));
     return GS_OK;
 }
 
 int gs_sh_grads_from_views(gs_ctx *c, int32_t nviews, const float *cams, const float *drgb, float *d_shs, int flags) {
     if (!c || !cams || !drgb || !d_shs || nviews <= 0) return GS_ERR_INVALID;
-    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_sh_grads_from_views: 3-D renderer only");
+    if (const int rc = need_3d(c, "gs_sh_grads_from_views")) return rc;
     if (bind_device(c)) return GS_ERR_HIP;
     const size_t bytes = sizeof(float) * GS_VIEW_RECORD_FLOATS * (size_t)nviews;
     HIPCHK(c, c->view_cams.ensure(bytes));

@@ -18,34 +18,35 @@ int gs_get_array(gs_ctx *c, int which, void *dst, int64_t bytes) {
     const size_t n = (size_t)c->n;
     const void *src = nullptr;
     size_t need = 0;
-    auto need_dbg = [&](int i, size_t w) -> int {
+    auto need_dbg = [&](gs_ctx::Dbg i) -> int {
         if (!c->cfg.export_debug) return fail(c, GS_ERR_INVALID, "gs_get_array: needs gs_config.export_debug = 1");
-        src = c->dbg[i].p; need = sizeof(float) * w * n; return GS_OK;
+        src = c->dbg[i].p; need = sizeof(float) * gs_ctx::DBG_WIDTH[i] * n; return GS_OK;
     };
-    if (which <= GS_ARR_TILE_RECT && c->stage < Stage::PREPROCESSED) return fail(c, GS_ERR_INVALID, "gs_get_array: gs_preprocess first");
-    if (which >= GS_ARR_SORT_IDXS && which <= GS_ARR_SORTED_KEYS && c->stage < Stage::BINNED) return fail(c, GS_ERR_INVALID, "gs_get_array: gs_bin first");
-    if (which >= GS_ARR_TILE_RANGES && which <= GS_ARR_SORTED_KEYS) { if (int rc = settle_totals(c, nullptr, true)) return rc; }
+    int rc = GS_OK;
+    if (which <= GS_ARR_TILE_RECT && (rc = need_stage(c, Stage::PREPROCESSED, "gs_get_array: gs_preprocess first"))) return rc;
+    if (which >= GS_ARR_SORT_IDXS && which <= GS_ARR_SORTED_KEYS && (rc = need_stage(c, Stage::BINNED, "gs_get_array: gs_bin first"))) return rc;
+    if (which >= GS_ARR_TILE_RANGES && which <= GS_ARR_SORTED_KEYS && (rc = settle_totals(c, nullptr, true))) return rc;
     if (which >= GS_ARR_TILE_RANGES && which <= GS_ARR_SORTED_KEYS && c->bin.n_rounds > 1)
         return fail(c, GS_ERR_INVALID, "gs_get_array: this frame was binned in depth slabs (lists spread over rounds); use gs_config.slab_mode = 0");
-    if ((which == GS_ARR_SORTED_IDS || which == GS_ARR_SORTED_KEYS) && c->frame_capped && c->have_l2) {
+    if ((which == GS_ARR_SORTED_IDS || which == GS_ARR_SORTED_KEYS) && c->live.frame_capped && c->live.have_l2) {
         // capped lists: only the part of every list the view slot's history says is walked has been written.  Write the rest now (the
         // same kernel with the caps off: same positions, same order); from here on the frame's lists are complete.
-        GsBin3Args a = c->last_l2;
+        GsBin3Args a = c->live.last_l2;
         a.cap_src = nullptr; a.tile_nopen = nullptr; a.smax = nullptr; a.tile_ext = nullptr;
         HIPCHK(c, gs_bin3_write_lists(a, c->stream));
-        c->frame_capped = false;
+        c->live.frame_capped = false;
     }
     switch (which) {
-        case GS_ARR_TS: if (int r = need_dbg(0, 4)) return r; break;
-        case GS_ARR_TPS: if (int r = need_dbg(1, 4)) return r; break;
-        case GS_ARR_COV3D: if (int r = need_dbg(3, 9)) return r; break;
-        case GS_ARR_COV2D: if (int r = need_dbg(4, 4)) return r; break;
-        case GS_ARR_BBS: if (int r = need_dbg(6, 4)) return r; break;
+        case GS_ARR_TS: if ((rc = need_dbg(gs_ctx::DBG_TS))) return rc; break;
+        case GS_ARR_TPS: if ((rc = need_dbg(gs_ctx::DBG_TPS))) return rc; break;
+        case GS_ARR_COV3D: if ((rc = need_dbg(gs_ctx::DBG_COV3D))) return rc; break;
+        case GS_ARR_COV2D: if ((rc = need_dbg(gs_ctx::DBG_COV2D))) return rc; break;
+        case GS_ARR_BBS: if ((rc = need_dbg(gs_ctx::DBG_BBS))) return rc; break;
         case GS_ARR_INVCOV: src = c->invcov.p; need = sizeof(float) * 4 * n; break;
         case GS_ARR_MU: case GS_ARR_RGB: case GS_ARR_SIG: {
             const size_t w = which == GS_ARR_MU ? 2 : which == GS_ARR_RGB ? 3 : 1;
             if ((size_t)bytes != sizeof(float) * w * n) return fail(c, GS_ERR_INVALID, "gs_get_array: size mismatch");
-            std::vector<GsPayload> h(n ? n : 1);
+            std::vector<GsPayload> h(c->n1());
             HIPCHK(c, hipMemcpyAsync(h.data(), c->payload.p, sizeof(GsPayload) * n, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             float *o = static_cast<float *>(dst);
@@ -61,20 +62,19 @@ int gs_get_array(gs_ctx *c, int which, void *dst, int64_t bytes) {
         case GS_ARR_TILE_RECT: src = c->rect.p; need = sizeof(uint16_t) * 4 * n; break;
         case GS_ARR_SORT_IDXS: {
             if ((size_t)bytes != sizeof(uint32_t) * n) return fail(c, GS_ERR_INVALID, "gs_get_array: size mismatch");
-            if (c->bin.perm_on_demand && !c->perm_ptr) {            // a frame binned by the small path (gs_bin_small.hip) sorted nothing globally
-                if (int rc = depth_order(c, &c->perm_ptr)) return rc;
-            }
-            if (c->perm_ptr) { src = c->perm_ptr; need = sizeof(uint32_t) * n; break; }
+            // a frame binned by the small path (gs_bin_small.hip) sorted nothing globally
+            if (c->bin.perm_on_demand && !c->live.perm_ptr && (rc = depth_order(c))) return rc;
+            if (c->live.perm_ptr) { src = c->live.perm_ptr; need = sizeof(uint32_t) * n; break; }
             uint32_t *o = static_cast<uint32_t *>(dst);
             for (size_t g = 0; g < n; ++g) o[g] = (uint32_t)g;
             return GS_OK;
         }
-        case GS_ARR_TILE_RANGES: src = c->ranges.p; need = sizeof(uint32_t) * 2 * (size_t)c->gx * c->gy; break;
+        case GS_ARR_TILE_RANGES: src = c->ranges.p; need = sizeof(uint32_t) * 2 * c->ntiles(); break;
         case GS_ARR_SORTED_IDS: case GS_ARR_SORTED_KEYS: {
-            const size_t ni = (size_t)c->n_inst, nt = (size_t)c->gx * c->gy;
+            const size_t ni = (size_t)c->n_inst, nt = (size_t)c->ntiles();
             const size_t w = which == GS_ARR_SORTED_IDS ? sizeof(uint32_t) : sizeof(uint64_t);
             if ((size_t)bytes != w * ni) return fail(c, GS_ERR_INVALID, "gs_get_array: size mismatch");
-            std::vector<uint32_t> h(ni ? ni : 1), dk(n ? n : 1), rg(2 * c->ntiles1());
+            std::vector<uint32_t> h(ni ? ni : 1), dk(c->n1()), rg(2 * c->ntiles1());
             HIPCHK(c, hipMemcpyAsync(h.data(), c->ids.p, sizeof(uint32_t) * ni, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemcpyAsync(dk.data(), c->depth_key.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemcpyAsync(rg.data(), c->ranges.p, sizeof(uint32_t) * 2 * nt, hipMemcpyDeviceToHost, c->stream));
@@ -91,15 +91,15 @@ int gs_get_array(gs_ctx *c, int which, void *dst, int64_t bytes) {
             return GS_OK;
         }
         case GS_ARR_GRAD2D: {
-            if (c->stage < Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_get_array: gs_backward first");
+            if ((rc = need_stage(c, Stage::COMPOSITE_ADJOINT, "gs_get_array: gs_backward first"))) return rc;
             if ((size_t)bytes != sizeof(float) * 10 * n) return fail(c, GS_ERR_INVALID, "gs_get_array: size mismatch");
             float *o = static_cast<float *>(dst);
             // the device rows (float, or fixed point in deterministic mode) hold raw moments: apply the per-gaussian factors with the view's payload (sig, conic)
             const bool fixed = c->cfg.deterministic;
-            std::vector<long long> fx(fixed ? (size_t)GS_G2D_STRIDE * (n ? n : 1) : 0);
-            std::vector<float> fl(fixed ? 0 : (size_t)GS_G2D_STRIDE * (n ? n : 1));
-            std::vector<GsPayload> pay(n ? n : 1);
-            std::vector<float> ic(4 * (n ? n : 1));
+            std::vector<long long> fx(fixed ? GS_G2D_STRIDE * c->n1() : 0);
+            std::vector<float> fl(fixed ? 0 : GS_G2D_STRIDE * c->n1());
+            std::vector<GsPayload> pay(c->n1());
+            std::vector<float> ic(4 * c->n1());
             if (n) HIPCHK(c, hipMemcpyAsync(fixed ? (void *)fx.data() : (void *)fl.data(), c->g2d.p, c->g2d_bytes(), hipMemcpyDeviceToHost, c->stream));
             if (n) HIPCHK(c, hipMemcpyAsync(pay.data(), c->payload.p, sizeof(GsPayload) * n, hipMemcpyDeviceToHost, c->stream));
             if (n) HIPCHK(c, hipMemcpyAsync(ic.data(), c->invcov.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, c->stream));
@@ -157,7 +157,7 @@ static int debug_composite_args(gs_ctx *c, int which, int variant, GsCompositeAr
         a.walked = c->counters.as<CounterBlock>()->scratch;
     }
     a.final_round = 1;
-    c->g2d_clean = false;
+    c->live.rows_dirtied();
     a.variant = variant % 100;
     a.cull = (c->cfg.alpha_cull != 0) != (variant >= 1000);                  // +1000: the other cull setting
     if (c->dbg_win_len > 0) {                                                // gs_debug_set_window: a slice of the launch order
@@ -181,8 +181,8 @@ int gs_debug_time_composite(gs_ctx *c, int which, int variant, int reps, float *
     if (!c || !mean_ms || reps == 0) return GS_ERR_INVALID;
     const bool cold = reps < 0;                                               // negative: -reps launches WITHOUT the warm-up launch (tools/cold_fwd.py)
     if (cold) reps = -reps;
-    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_debug_time_composite: gs_forward first");
-    if (which == 1 && c->stage < Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_debug_time_composite: gs_backward first");
+    int rc = need_stage(c, Stage::RENDERED, "gs_debug_time_composite: gs_forward first");
+    if (rc || (which == 1 && (rc = need_stage(c, Stage::COMPOSITE_ADJOINT, "gs_debug_time_composite: gs_backward first")))) return rc;
     if (bind_device(c)) return GS_ERR_HIP;
     GsCompositeArgs a{};
     if (int rc = debug_composite_args(c, which, variant, a)) return rc;
@@ -204,8 +204,8 @@ int gs_debug_time_composite(gs_ctx *c, int which, int variant, int reps, float *
 
 int gs_debug_tile_clock(gs_ctx *c, int which, int variant, uint64_t *out) {
     if (!c || !out) return GS_ERR_INVALID;
-    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_debug_tile_clock: gs_forward first");
-    if (which == 1 && c->stage < Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_debug_tile_clock: gs_backward first");
+    int rc = need_stage(c, Stage::RENDERED, "gs_debug_tile_clock: gs_forward first");
+    if (rc || (which == 1 && (rc = need_stage(c, Stage::COMPOSITE_ADJOINT, "gs_debug_tile_clock: gs_backward first")))) return rc;
     if (bind_device(c)) return GS_ERR_HIP;
     GsCompositeArgs a{};
     const bool by_block = variant < 0;                                        // negative variant: records per WORKGROUP (launches with split tiles):
@@ -217,7 +217,7 @@ int gs_debug_tile_clock(gs_ctx *c, int which, int variant, uint64_t *out) {
             return fail(c, GS_ERR_INVALID, "gs_debug_tile_clock: records by workgroup need the frame's launch order (or a small grid's tile parts)");
         a.clock_by_block = 1;
     } else { a.split_ok = 0; a.snap = nullptr; }                              // records by tile: whole tiles only
-    const size_t rows = a.clock_by_block ? (size_t)gs_debug_tile_clock_rows(c) : (size_t)c->gx * c->gy;
+    const size_t rows = a.clock_by_block ? (size_t)gs_debug_tile_clock_rows(c) : (size_t)c->ntiles();
     if (a.clock_by_block && (size_t)gs_composite_grid_blocks(a, which) > rows) return fail(c, GS_ERR_INVALID, "gs_debug_tile_clock: launch larger than its record");
     HIPCHK(c, c->tile_clock.ensure(sizeof(uint64_t) * GS_TILE_CLOCK_WORDS * (rows ? rows : 1)));
     HIPCHK(c, hipMemsetAsync(c->tile_clock.p, 0, sizeof(uint64_t) * GS_TILE_CLOCK_WORDS * rows, c->stream));
@@ -233,7 +233,7 @@ int gs_debug_tile_clock(gs_ctx *c, int which, int variant, uint64_t *out) {
 
 int gs_debug_tail_fill(gs_ctx *c, int32_t blocks[2]) {
     if (!c || !blocks) return GS_ERR_INVALID;
-    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_debug_tail_fill: gs_forward first");
+    if (const int rc = need_stage(c, Stage::RENDERED, "gs_debug_tail_fill: gs_forward first")) return rc;
     blocks[0] = c->fill_blocks_fwd; blocks[1] = c->stage >= Stage::COMPOSITE_ADJOINT ? c->fill_blocks_bwd : 0;
     return GS_OK;
 }
@@ -242,7 +242,7 @@ int gs_debug_tile_clock_rows(gs_ctx *c) {
     if (!c) return GS_ERR_INVALID;
     if (lpt_schedule(c)) return lpt_order_entries(c) + gs_seg_units(lpt_front(c));
     // small grids: blocks of one part x the most waves a tile is given (pixel parts x list segments of the backward); 0: one wave per tile
-    const int len = ((c->gx * c->gy + 7) / 8) * 8;
+    const int len = (((int)c->ntiles() + 7) / 8) * 8;
     const int units = c->plan.parts * (c->plan.snap == gs_ctx::FramePlan::Snap::ALL ? 4 * c->plan.seg_n : 1);   // (an upper bound: at most four parts on top of the segments)
     return units > 1 ? len * units : 0;
 }
@@ -264,7 +264,7 @@ int gs_rank_probe_result(const gs_ctx *c) { return c ? c->rank_probe : -1; }
 // counters[0..3] = {walked, evaluated} of the last forward and of the last composite backward, summed from the per-tile arrays
 static int sum_work_counters(gs_ctx *c) {
     unsigned long long *w = c->counters.as<unsigned long long>();
-    const int nt = c->gx * c->gy;
+    const int nt = (int)c->ntiles();
     HIPCHK(c, gs_launch_sum_tiles(c->last_walked, c->tile_work.as<uint32_t>(), nt, w, c->stream));
     if (c->stage >= Stage::COMPOSITE_ADJOINT && c->tile_walked_b.p && c->tile_work_b.p)
         HIPCHK(c, gs_launch_sum_tiles(c->tile_walked_b.as<uint32_t>(), c->tile_work_b.as<uint32_t>(), nt, w + 2, c->stream));
@@ -274,7 +274,7 @@ static int sum_work_counters(gs_ctx *c) {
 
 int gs_get_work_counters(gs_ctx *c, int64_t *walked_fwd, int64_t *walked_bwd) {
     if (!c) return GS_ERR_INVALID;
-    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_get_work_counters: gs_forward first");
+    if (const int rc = need_stage(c, Stage::RENDERED, "gs_get_work_counters: gs_forward first")) return rc;
     int64_t o[4];
     if (int rc = gs_get_work_counters_ex(c, o)) return rc;
     if (walked_fwd) *walked_fwd = o[0];
@@ -284,14 +284,14 @@ int gs_get_work_counters(gs_ctx *c, int64_t *walked_fwd, int64_t *walked_bwd) {
 
 int gs_get_list_stats(gs_ctx *c, int64_t out[3]) {
     if (!c || !out) return GS_ERR_INVALID;
-    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_get_list_stats: gs_forward first");
+    if (const int rc = need_stage(c, Stage::RENDERED, "gs_get_list_stats: gs_forward first")) return rc;
     if (bind_device(c)) return GS_ERR_HIP;
     if (int rc = settle_totals(c, nullptr, true)) return rc;
     out[0] = c->n_inst; out[1] = 0; out[2] = 0;
-    if (!c->frame_capped || c->bin.n_rounds != 1) return GS_OK;
+    if (!c->live.frame_capped || c->bin.n_rounds != 1) return GS_OK;
     unsigned long long *d = c->counters.as<CounterBlock>()->scratch, h = 0;
     uint32_t e = 0;
-    HIPCHK(c, gs_launch_sum_listed(c->tile_ext.as<uint2>(), c->gx * c->gy, d, c->stream));
+    HIPCHK(c, gs_launch_sum_listed(c->tile_ext.as<uint2>(), (int)c->ntiles(), d, c->stream));
     HIPCHK(c, hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&e, c->ext_count(), sizeof(e), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -301,19 +301,19 @@ int gs_get_list_stats(gs_ctx *c, int64_t out[3]) {
 
 int gs_get_tile_parts(gs_ctx *c) {
     if (!c) return GS_ERR_INVALID;
-    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_get_tile_parts: gs_forward first");
+    if (const int rc = need_stage(c, Stage::RENDERED, "gs_get_tile_parts: gs_forward first")) return rc;
     return c->plan.parts;
 }
 
 int gs_get_bin_path(gs_ctx *c) {
     if (!c) return GS_ERR_INVALID;
-    if (c->stage < Stage::BINNED) return fail(c, GS_ERR_INVALID, "gs_get_bin_path: gs_bin first");
+    if (const int rc = need_stage(c, Stage::BINNED, "gs_get_bin_path: gs_bin first")) return rc;
     return (int)c->bin.path;
 }
 
 int gs_get_work_counters_ex(gs_ctx *c, int64_t out[4]) {
     if (!c || !out) return GS_ERR_INVALID;
-    if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, "gs_get_work_counters_ex: gs_forward first");
+    if (const int rc = need_stage(c, Stage::RENDERED, "gs_get_work_counters_ex: gs_forward first")) return rc;
     if (bind_device(c)) return GS_ERR_HIP;
     unsigned long long h[4] = {0, 0, 0, 0};
     if (int rc = sum_work_counters(c)) return rc;

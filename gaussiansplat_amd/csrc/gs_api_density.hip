@@ -5,31 +5,20 @@
 #include "gs_ctx.h"
 #include "gs_density.h"
 
-namespace {
-
-int density_3d(gs_ctx *c, const char *who) {
-    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, std::string(who) + ": 3-D renderer only");
-    return GS_OK;
-}
-
-struct Range { uintptr_t lo; size_t bytes; };
-bool ranges_overlap(const Range &a, const Range &b) { return a.bytes && b.bytes && a.lo < b.lo + b.bytes && b.lo < a.lo + a.bytes; }
-
-}  // namespace
 
 extern "C" {
 
 int gs_density_accumulate(gs_ctx *c, const gs_density_stats *st) {
     if (!c) return GS_ERR_INVALID;
     if (!st) return fail(c, GS_ERR_INVALID, "gs_density_accumulate: NULL stats");
-    if (const int rc = density_3d(c, "gs_density_accumulate")) return rc;
-    if (c->stage < gs_ctx::Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_density_accumulate: gs_backward first (a non-fused backward of the frame)");
+    if (const int rc = need_3d(c, "gs_density_accumulate")) return rc;
+    if (const int rc = need_stage(c, gs_ctx::Stage::COMPOSITE_ADJOINT, "gs_density_accumulate: gs_backward first (a non-fused backward of the frame)")) return rc;
     if (c->n > 0 && (!st->grad_sum || !st->count || !st->max_extent)) return fail(c, GS_ERR_INVALID, "gs_density_accumulate: NULL statistics array");
     if (bind_device(c)) return GS_ERR_HIP;
     GsDensityAccArgs a{};
     a.n = c->n;
     a.payload = c->payload.as<GsPayload>(); a.invcov = c->invcov.as<float>();
-    if (c->cfg.deterministic) a.g2d_fixed = c->g2d.as<long long>(); else a.g2d = c->g2d.as<float>();
+    c->rows(c->g2d).into(a);
     a.half_w = 0.5f * (float)c->cam.W; a.half_h = 0.5f * (float)c->cam.H;
     a.grad_sum = st->grad_sum; a.count = st->count; a.max_extent = st->max_extent;
     HIPCHK(c, gs_launch_density_accumulate(a, c->stream));
@@ -39,7 +28,7 @@ int gs_density_accumulate(gs_ctx *c, const gs_density_stats *st) {
 int gs_density_decide(gs_ctx *c, const gs_density_stats *st, const gs_density_params *p, int32_t *action) {
     if (!c) return GS_ERR_INVALID;
     if (!st || !p) return fail(c, GS_ERR_INVALID, "gs_density_decide: NULL argument");
-    if (const int rc = density_3d(c, "gs_density_decide")) return rc;
+    if (const int rc = need_3d(c, "gs_density_decide")) return rc;
     if (p->struct_size != (int32_t)sizeof(gs_density_params)) return fail(c, GS_ERR_INVALID, "gs_density_decide: gs_density_params.struct_size mismatch");
     if (std::isnan(p->grad_threshold) || std::isnan(p->log_shrink)) return fail(c, GS_ERR_INVALID, "gs_density_decide: grad_threshold and log_shrink must not be NaN");
     if (c->n > 0 && (!st->grad_sum || !st->count || !st->max_extent || !action)) return fail(c, GS_ERR_INVALID, "gs_density_decide: NULL array");
@@ -58,7 +47,7 @@ int gs_density_decide(gs_ctx *c, const gs_density_stats *st, const gs_density_pa
 int gs_density_plan(gs_ctx *c, const int32_t *action, int64_t counts[4]) {
     if (!c) return GS_ERR_INVALID;
     if (!counts) return fail(c, GS_ERR_INVALID, "gs_density_plan: NULL counts");
-    if (const int rc = density_3d(c, "gs_density_plan")) return rc;
+    if (const int rc = need_3d(c, "gs_density_plan")) return rc;
     if (c->n > 0 && !action) return fail(c, GS_ERR_INVALID, "gs_density_plan: NULL action");
     if (bind_device(c)) return GS_ERR_HIP;
     c->density.planned = false;
@@ -82,7 +71,7 @@ int gs_density_plan(gs_ctx *c, const int32_t *action, int64_t counts[4]) {
 int gs_density_restructure(gs_ctx *c, const int32_t *action, const float *noise, const gs_grads *dst_model, int32_t nsets,
                            const gs_grads *src_sets, const gs_grads *dst_sets, int64_t n_out) {
     if (!c) return GS_ERR_INVALID;
-    if (const int rc = density_3d(c, "gs_density_restructure")) return rc;
+    if (const int rc = need_3d(c, "gs_density_restructure")) return rc;
     const gs_ctx::DensityPlan &d = c->density;
     if (!d.planned || d.action != action || d.n != c->n)
         return fail(c, GS_ERR_INVALID, "gs_density_restructure: no plan for this action array and model (gs_density_plan first; a model or camera change drops it)");
@@ -96,29 +85,29 @@ int gs_density_restructure(gs_ctx *c, const int32_t *action, const float *noise,
     const Five<const float> src = c->model5();
     const Five<float> dst = five(*dst_model);
     // every destination against the model, the source sets and the other destinations (gs_adam_prepare's rule)
-    Range rd[5 + 5 * GS_DENSITY_MAX_SETS], rs[5 + 5 * GS_DENSITY_MAX_SETS];
+    ByteRange rd[5 + 5 * GS_DENSITY_MAX_SETS], rs[5 + 5 * GS_DENSITY_MAX_SETS];
     int nd = 0, ns = 0;
     for (int i = 0; i < 5; ++i) {
         if (no && !dst[i]) return fail(c, GS_ERR_INVALID, "gs_density_restructure: NULL array in dst_model");
         if (n && !src[i]) return fail(c, GS_ERR_INVALID, "gs_density_restructure: no model (gs_set_model first)");
         a.src[i] = src[i]; a.dst[i] = dst[i];
-        rd[nd++] = {reinterpret_cast<uintptr_t>(dst[i]), sizeof(float) * c->width[i] * no};
-        rs[ns++] = {reinterpret_cast<uintptr_t>(src[i]), sizeof(float) * c->width[i] * n};
+        rd[nd++] = {dst[i], sizeof(float) * c->width[i] * no};
+        rs[ns++] = {src[i], sizeof(float) * c->width[i] * n};
     }
     for (int t = 0; t < nsets; ++t) {
         const Five<float> ss = five(src_sets[t]), sd = five(dst_sets[t]);
         for (int i = 0; i < 5; ++i) {
             if (!ss[i] || !sd[i]) continue;                                // skipped (the kernel tests the same pair)
             a.set_src[t][i] = ss[i]; a.set_dst[t][i] = sd[i];
-            rd[nd++] = {reinterpret_cast<uintptr_t>(sd[i]), sizeof(float) * c->width[i] * no};
-            rs[ns++] = {reinterpret_cast<uintptr_t>(ss[i]), sizeof(float) * c->width[i] * n};
+            rd[nd++] = {sd[i], sizeof(float) * c->width[i] * no};
+            rs[ns++] = {ss[i], sizeof(float) * c->width[i] * n};
         }
     }
     for (int i = 0; i < nd; ++i) {
         for (int j = 0; j < ns; ++j)
-            if (ranges_overlap(rd[i], rs[j])) return fail(c, GS_ERR_INVALID, "gs_density_restructure: a destination overlaps the model or a source set");
+            if (overlaps(rd[i], rs[j])) return fail(c, GS_ERR_INVALID, "gs_density_restructure: a destination overlaps the model or a source set");
         for (int j = i + 1; j < nd; ++j)
-            if (ranges_overlap(rd[i], rd[j])) return fail(c, GS_ERR_INVALID, "gs_density_restructure: destinations overlap");
+            if (overlaps(rd[i], rd[j])) return fail(c, GS_ERR_INVALID, "gs_density_restructure: destinations overlap");
     }
     if (bind_device(c)) return GS_ERR_HIP;
     if (!n || !no) return GS_OK;                                           // nothing to read, or nothing to write (every gaussian pruned)
@@ -133,7 +122,7 @@ int gs_density_restructure(gs_ctx *c, const int32_t *action, const float *noise,
 
 int gs_opacity_reset(gs_ctx *c, float max_logit, float *m_opac, float *v_opac) {
     if (!c) return GS_ERR_INVALID;
-    if (const int rc = density_3d(c, "gs_opacity_reset")) return rc;
+    if (const int rc = need_3d(c, "gs_opacity_reset")) return rc;
     if (c->n > 0 && !c->opac) return fail(c, GS_ERR_INVALID, "gs_opacity_reset: no model (gs_set_model first)");
     if (bind_device(c)) return GS_ERR_HIP;
     HIPCHK(c, gs_launch_opacity_reset(const_cast<float *>(c->opac), max_logit, m_opac, v_opac, c->n, c->stream));

@@ -10,15 +10,9 @@
 
 using Stage = gs_ctx::Stage;
 
-static bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + nb && y < x + na;
-}
-
-// what the three frame calls share: the 3-D renderer, a frame that has its image, lists of one round
+// what the two frame calls share: the 3-D renderer, a frame that has its image, lists of one round
 static int feature_frame_ok(gs_ctx *c, const char *who) {
-    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, std::string(who) + ": 3-D renderer only");
+    if (const int rc = need_3d(c, who)) return rc;
     if (c->stage < Stage::RENDERED) return fail(c, GS_ERR_INVALID, std::string(who) + ": gs_forward first");
     if (c->bin.n_rounds > 1)
         return fail(c, GS_ERR_UNSUPPORTED, std::string(who) + ": this frame was binned in depth slabs (lists spread over rounds); use gs_config.slab_mode = 0");
@@ -27,8 +21,7 @@ static int feature_frame_ok(gs_ctx *c, const char *who) {
 
 // the feature payload: the frame's rows with r, g, b = feat
 static int build_feature_payload(gs_ctx *c, const float *feat) {
-    const size_t n1 = c->n ? (size_t)c->n : 1;
-    HIPCHK(c, c->feat_payload.ensure(sizeof(GsPayload) * n1));
+    HIPCHK(c, c->feat_payload.ensure(sizeof(GsPayload) * c->n1()));
     HIPCHK(c, gs_launch_feature_payload(c->payload.as<GsPayload>(), feat, c->n, c->feat_payload.as<GsPayload>(), c->stream));
     return GS_OK;
 }
@@ -37,7 +30,7 @@ extern "C" {
 
 int gs_view_depth(gs_ctx *c, float *z) {
     if (!c) return GS_ERR_INVALID;
-    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_view_depth: 3-D renderer only");
+    if (const int rc = need_3d(c, "gs_view_depth")) return rc;
     if (!z) return fail(c, GS_ERR_INVALID, "gs_view_depth: NULL argument");
     if (!c->have_cam || (c->n > 0 && !c->means)) return fail(c, GS_ERR_INVALID, "gs_view_depth: gs_set_model and gs_set_camera first");
     if (bind_device(c)) return GS_ERR_HIP;
@@ -47,7 +40,7 @@ int gs_view_depth(gs_ctx *c, float *z) {
 
 int gs_view_depth_backward(gs_ctx *c, const float *dz, float *d_means) {
     if (!c) return GS_ERR_INVALID;
-    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_view_depth_backward: 3-D renderer only");
+    if (const int rc = need_3d(c, "gs_view_depth_backward")) return rc;
     if (!dz || !d_means) return fail(c, GS_ERR_INVALID, "gs_view_depth_backward: NULL argument");
     if (!c->have_cam) return fail(c, GS_ERR_INVALID, "gs_view_depth_backward: gs_set_camera first");
     if (bind_device(c)) return GS_ERR_HIP;
@@ -59,10 +52,9 @@ int gs_render_features(gs_ctx *c, const float *feat, float *out, float *trans_ou
     if (!c) return GS_ERR_INVALID;
     if (const int rc = feature_frame_ok(c, "gs_render_features")) return rc;
     if (!feat || !out) return fail(c, GS_ERR_INVALID, "gs_render_features: NULL argument");
-    const size_t px = (size_t)c->cam.W * c->cam.H, fb = sizeof(float);
-    if (overlaps(out, 3 * px * fb, c->img(), 3 * px * fb) || overlaps(out, 3 * px * fb, c->tr(), px * fb) ||
-        overlaps(trans_out, px * fb, c->img(), 3 * px * fb) || overlaps(trans_out, px * fb, c->tr(), px * fb) ||
-        overlaps(out, 3 * px * fb, trans_out, px * fb))
+    const size_t px = c->pixels(), fb = sizeof(float);
+    const ByteRange o{out, 3 * px * fb}, t{trans_out, px * fb}, image{c->img(), 3 * px * fb}, trans{c->tr(), px * fb};
+    if (overlaps(o, image) || overlaps(o, trans) || overlaps(t, image) || overlaps(t, trans) || overlaps(o, t))
         return fail(c, GS_ERR_INVALID, "gs_render_features: out / trans_out overlap the frame's image or transmittance, or each other");
     if (bind_device(c)) return GS_ERR_HIP;
     if (!trans_out) HIPCHK(c, c->feat_trans.ensure(fb * (px ? px : 1)));
@@ -83,14 +75,12 @@ int gs_backward_features(gs_ctx *c, const float *feat, const float *image_f, con
     if (const int rc = feature_frame_ok(c, "gs_backward_features")) return rc;
     if (!feat || !image_f || !dF || !d_feat) return fail(c, GS_ERR_INVALID, "gs_backward_features: NULL argument");
     if (bind_device(c)) return GS_ERR_HIP;
-    const bool det = c->cfg.deterministic != 0;
-    const size_t n1 = c->n ? (size_t)c->n : 1;
     // auxiliary rows of 2-D gradient sums, of the frame's mode, zeroed: c->g2d is the colour backward's
     HIPCHK(c, c->feat_g2d.ensure(c->g2d_bytes()));
     const bool chain = grads && (grads->d_means || grads->d_scales || grads->d_quats || grads->d_opacities);
     if (chain) {
         // the geometry chain's colour-path input: zeros that nothing writes again (not c->dpc: a caller may stand between GS_BWD_PARAMS_SH and _GEOM)
-        HIPCHK(c, c->feat_dpc.ensure(sizeof(float) * 4 * n1));
+        HIPCHK(c, c->feat_dpc.ensure(sizeof(float) * 4 * c->n1()));
         if (c->feat_dpc_zeroed != c->feat_dpc.cap) {
             HIPCHK(c, hipMemsetAsync(c->feat_dpc.p, 0, c->feat_dpc.cap, c->stream));
             c->feat_dpc_zeroed = c->feat_dpc.cap;
@@ -106,21 +96,13 @@ int gs_backward_features(gs_ctx *c, const float *feat, const float *image_f, con
     a.image = const_cast<float *>(image_f);                                // (read only by the backward: S = image . dC)
     a.trans = c->tr();
     a.dC = dF;
-    a.g2d = det ? nullptr : c->feat_g2d.as<float>();
-    a.g2d_fixed = det ? c->feat_g2d.as<long long>() : nullptr;
+    c->rows_mut(c->feat_g2d).into(a);
     HIPCHK(c, gs_launch_composite_bwd(a, c->stream));
-    const float *g2d = det ? nullptr : c->feat_g2d.as<float>();
-    const long long *g2d_fixed = det ? c->feat_g2d.as<long long>() : nullptr;
-    HIPCHK(c, gs_launch_pack_drgb(g2d, g2d_fixed, d_feat, c->n, c->stream));
+    const gs_ctx::Rows rows = c->rows(c->feat_g2d);
+    HIPCHK(c, gs_launch_pack_drgb(rows.g2d, rows.g2d_fixed, d_feat, c->n, c->stream));
     if (chain) {
         // the alpha path alone: the moments of the auxiliary rows through the geometry chain, accumulated into the caller's arrays
-        GsPreprocessBwdArgs b{};
-        b.n = c->n; b.sh_degree = c->active_sh_degree(); b.sh_stride = c->sh_row_floats();
-        b.means = c->means; b.scales = c->scales; b.quats = c->quats; b.opac = c->opac; b.shs = c->shs;
-        b.g2d = g2d; b.g2d_fixed = g2d_fixed;
-        b.dpc = c->feat_dpc.as<float>();
-        b.overwrite = 0; b.shs_zeroed = 0; b.sgd_scale = 0.0f;
-        b.d_means = grads->d_means; b.d_scales = grads->d_scales; b.d_quats = grads->d_quats; b.d_opac = grads->d_opacities; b.d_shs = nullptr;
+        const GsPreprocessBwdArgs b = chain_args(c, rows, c->feat_dpc.as<float>(), {{grads->d_means, grads->d_scales, grads->d_quats, grads->d_opacities, nullptr}}, 0, 0, 0.0f);
         const GsPreprocessBwdMode mode{2, nullptr, 0};
         HIPCHK(c, gs_launch_preprocess_bwd(b, c->cam, c->stream, mode));
     }

@@ -5,13 +5,7 @@
 #include "gs_ctx.h"
 #include "gs_knn.h"
 
-namespace {
-
-struct Range { uintptr_t lo; size_t bytes; };
-bool ranges_overlap(const Range &a, const Range &b) { return a.bytes && b.bytes && a.lo < b.lo + b.bytes && b.lo < a.lo + a.bytes; }
-Range range_of(const void *p, size_t floats) { return {reinterpret_cast<uintptr_t>(p), sizeof(float) * floats}; }
-
-}  // namespace
+static ByteRange range_of(const void *p, size_t floats) { return {p, sizeof(float) * floats}; }
 
 extern "C" {
 
@@ -21,7 +15,7 @@ int gs_knn_mean_dist2(gs_ctx *c, const float *points, int64_t n, float *dist2) {
     if (n == 0) return GS_OK;
     if (!points || !dist2) return fail(c, GS_ERR_INVALID, "gs_knn_mean_dist2: NULL array");
     if (n > (int64_t)INT32_MAX) return fail(c, GS_ERR_UNSUPPORTED, "gs_knn_mean_dist2: more than 2^31 - 1 points");
-    if (ranges_overlap(range_of(points, 3 * (size_t)n), range_of(dist2, (size_t)n))) return fail(c, GS_ERR_INVALID, "gs_knn_mean_dist2: dist2 overlaps points");
+    if (overlaps(range_of(points, 3 * (size_t)n), range_of(dist2, (size_t)n))) return fail(c, GS_ERR_INVALID, "gs_knn_mean_dist2: dist2 overlaps points");
     if (bind_device(c)) return GS_ERR_HIP;
     const size_t nb = (size_t)gs_knn_boxes(n), ns = (size_t)gs_knn_supers(n);
     HIPCHK(c, c->knn_pairs_a.ensure(sizeof(uint64_t) * (size_t)n));
@@ -52,17 +46,17 @@ int gs_init_from_points(gs_ctx *c, const float *points, const float *colors, con
     const Five<float> dst = five(*dst_model);
     const size_t k3 = 3 * (size_t)(sh_degree + 1) * (size_t)(sh_degree + 1), un = (size_t)n;
     const size_t width[5] = {3, 3, 4, 1, k3};
-    Range rd[5];
-    const Range rs[3] = {range_of(points, 3 * un), range_of(colors, colors ? 3 * un : 0), range_of(dist2, un)};
+    ByteRange rd[5];
+    const ByteRange rs[3] = {range_of(points, 3 * un), range_of(colors, colors ? 3 * un : 0), range_of(dist2, un)};
     for (int i = 0; i < 5; ++i) {
         if (!dst[i]) return fail(c, GS_ERR_INVALID, "gs_init_from_points: NULL array in dst_model");
         rd[i] = range_of(dst[i], width[i] * un);
     }
     for (int i = 0; i < 5; ++i) {
-        for (const Range &s : rs)
-            if (ranges_overlap(rd[i], s)) return fail(c, GS_ERR_INVALID, "gs_init_from_points: a destination overlaps a source");
+        for (const ByteRange &s : rs)
+            if (overlaps(rd[i], s)) return fail(c, GS_ERR_INVALID, "gs_init_from_points: a destination overlaps a source");
         for (int j = i + 1; j < 5; ++j)
-            if (ranges_overlap(rd[i], rd[j])) return fail(c, GS_ERR_INVALID, "gs_init_from_points: destinations overlap");
+            if (overlaps(rd[i], rd[j])) return fail(c, GS_ERR_INVALID, "gs_init_from_points: destinations overlap");
     }
     if (n == 0) return GS_OK;
     if (bind_device(c)) return GS_ERR_HIP;

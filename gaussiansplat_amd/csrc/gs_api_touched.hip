@@ -14,25 +14,24 @@ extern "C" {
 
 int gs_color_rows_pack(gs_ctx *c, const float *drgb, int64_t n, int32_t *bits, float *rows, int64_t *count) {
     if (!c || !bits || !rows || !count || n < 0) return GS_ERR_INVALID;
-    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_color_rows_pack: 3-D renderer only");
-    if (!drgb && c->stage < gs_ctx::Stage::COMPOSITE_ADJOINT) return fail(c, GS_ERR_INVALID, "gs_color_rows_pack: gs_backward first (or pass drgb)");
+    int rc = need_3d(c, "gs_color_rows_pack");
+    if (rc || (!drgb && (rc = need_stage(c, gs_ctx::Stage::COMPOSITE_ADJOINT, "gs_color_rows_pack: gs_backward first (or pass drgb)")))) return rc;
     if (!drgb && n != c->n) return fail(c, GS_ERR_INVALID, "gs_color_rows_pack: n must be gs_num_gaussians when the ctx's own sums are packed");
     if (bind_device(c)) return GS_ERR_HIP;
     if (n == 0) {
         HIPCHK(c, hipMemsetAsync(count, 0, sizeof(int64_t), c->stream));
         return GS_OK;
     }
-    if (const int rc = touched_scratch(c, 1, n)) return rc;
-    const bool det = c->cfg.deterministic != 0;
-    HIPCHK(c, gs_launch_touched_pack(drgb, (drgb || det) ? nullptr : c->g2d.as<float>(), (!drgb && det) ? c->g2d.as<long long>() : nullptr, n,
-                                     bits, rows, count, c->touched_cnt.as<uint32_t>(), c->touched_off.as<int64_t>(), c->stream));
+    if ((rc = touched_scratch(c, 1, n))) return rc;
+    const gs_ctx::Rows own = drgb ? gs_ctx::Rows{nullptr, nullptr} : c->rows(c->g2d);    // the ctx's own sums, unless the caller brings dense ones
+    HIPCHK(c, gs_launch_touched_pack(drgb, own.g2d, own.g2d_fixed, n, bits, rows, count, c->touched_cnt.as<uint32_t>(), c->touched_off.as<int64_t>(), c->stream));
     return GS_OK;
 }
 
 int gs_sh_grads_from_touched(gs_ctx *c, int32_t nviews, const float *cams, const int32_t *bits, const float *rows, int64_t rows_cap,
                              float *d_shs, int flags) {
     if (!c || !cams || !bits || !rows || !d_shs || nviews <= 0 || rows_cap < 1) return GS_ERR_INVALID;
-    if (c->kind != 0) return fail(c, GS_ERR_UNSUPPORTED, "gs_sh_grads_from_touched: 3-D renderer only");
+    if (const int rc = need_3d(c, "gs_sh_grads_from_touched")) return rc;
     if (bind_device(c)) return GS_ERR_HIP;
     if (c->n <= 0) return GS_OK;
     const size_t bytes = sizeof(float) * GS_VIEW_RECORD_FLOATS * (size_t)nviews;

@@ -1,6 +1,6 @@
 // gs_ctx.h -- the renderer context behind the C ABI (include/gsplat.h) and the host-side helpers its translation units share.
 // Internal: nothing here is part of the ABI.  The entry points live in
-//   gs_api.hip            create / destroy, model, camera, gs_preprocess, gradients buffers, loss, SGD
+//   gs_api.hip            create / destroy, model, camera, gs_preprocess (what both renderers share: preprocess_outputs), gradients buffers, loss, SGD
 //   gs_api_bin.hip        gs_bin: the frame's bin plan (plan_bin), depth order, one function per path (bin_small, bin_two_level, bin_radix), settle_totals
 //   gs_api_composite.hip  gs_forward / gs_backward: the frame's plan (plan_frame), the one builder of the composite launches' arguments
 //                         (composite_args), the launch orders of the view slots; the backward family's plan (plan_backward) and run_backward
@@ -14,6 +14,9 @@
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
 // How far the frame has come is ONE ordered value (gs_ctx::Stage): every entry point compares it, reaches a stage or falls back to one.
 // What the ctx holds it owns: DevBuf frees itself, ~gs_ctx releases the communicator, events, streams and pinned blocks -- no list to keep.
+// What every entry point needs is written ONCE, here: the refusals they share (need_3d, need_mem, need_image_size, need_stage, overlaps), the sizes
+// (n1, ntiles, pixels), a buffer of gradient rows in the ctx's mode (gs_ctx::rows), the model head of an argument struct (model_head), the per-gaussian
+// chain's arguments (chain_args), the export_debug arrays (gs_ctx::Dbg, DBG_WIDTH); what changes behind a frame's plans is one value (gs_ctx::FrameLive).
 #pragma once
 #include "../../include/gsplat.h"
 #include "gs_common.h"
@@ -21,6 +24,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -130,14 +134,19 @@ struct gs_ctx {
     void inputs_changed() { fall_back(Stage::NOTHING); density.planned = false; }   // the model or the view changed: nothing of the frame stands, nor a density plan
     int gx = 0, gy = 0;
     int64_t grid_key() const { return ((int64_t)gx << 32) | (int64_t)gy; }        // what per-grid history is tagged with (0: none)
-    size_t ntiles1() const { const size_t nt = (size_t)gx * gy; return nt ? nt : 1; }   // tiles, for buffer sizes (never zero)
+    int64_t ntiles() const { return (int64_t)gx * gy; }                           // tiles of the grid (at most 2048 x 2048: fits an int) ...
+    size_t ntiles1() const { const size_t nt = (size_t)ntiles(); return nt ? nt : 1; }   // ... and for buffer sizes (never zero)
+    size_t n1() const { return n ? (size_t)n : 1; }                               // gaussians, for buffer sizes (never zero)
+    size_t pixels() const { return (size_t)cam.W * cam.H; }
 
     DevBuf invcov;                           // 4 x n raw conic (introspection; the payload rows carry it scaled)
     DevBuf payload, depth_key, rect, pairs_a, pairs_b, perm, offsets, block_sums;
     DevBuf inst_a, inst_b, table, digit_total, ranges, image, trans, g2d, stage_in;
-    DevBuf dbg[7];
+    // the export_debug arrays and their floats per gaussian: what gs_preprocess fills (the 2-D renderer: mu, cov2d, invcov, bbs) and gs_get_array hands out
+    enum Dbg { DBG_TS, DBG_TPS, DBG_MU, DBG_COV3D, DBG_COV2D, DBG_INVCOV, DBG_BBS, DBG_COUNT };
+    static constexpr size_t DBG_WIDTH[DBG_COUNT] = {4, 4, 2, 9, 4, 4, 4};
+    DevBuf dbg[DBG_COUNT];
     DevBuf ids, words, cs, diff;             // sorted gaussian ids; pass-1 words; chunk owners; 2-D difference array
-    uint32_t *perm_ptr = nullptr;
     int64_t n_inst = 0;
     PinnedWords *pinned = nullptr;
     const float *last_dC = nullptr;          // device dC of the last gs_backward (debug timing)
@@ -173,15 +182,30 @@ struct gs_ctx {
     };
     std::vector<ViewSlot> slots;             // GS_MAX_VIEW_SLOTS + 1 (allocated at gs_create; device buffers on first use)
     const uint32_t *last_walked = nullptr;   // per-tile walked counts of the most recent forward (the slot's array, or tile_walked)
-    // ---- capped lists (gs_config.list_cap): this frame's tile lists were written only as far as the slot's history says they are walked
-    bool frame_capped = false;               // LIVE state, not plan: gs_get_array(GS_ARR_SORTED_IDS / _KEYS) completes the lists and clears it
     int wave_slots = 5120;                   // CUs x 4 SIMDs x 5 BY DEFINITION (gs_create): the unit of every threshold; the backward holds six waves per SIMD by now
-    const uint32_t *cap_src = nullptr;       // the history the caps of this frame come from (null: none)
-    DevBuf tile_nopen, smax, tile_ext, zero_tiles;
-    GsBin3Args last_l2{};                    // the level-2 arguments of the frame's lists (gs_get_array writes the capped rest with them)
-    bool have_l2 = false;
+    DevBuf tile_nopen, smax, tile_ext, zero_tiles;   // capped lists (gs_config.list_cap; FrameLive::frame_capped)
+    // ---- the frame's LIVE state: what calls behind the plans change.  gs_bin starts every frame with a fresh value, so a member added here cannot be
+    // forgotten in a reset.  Written by two_level_lists (capped lists), bin_small / gs_forward (g2d_clean), depth_order, gs_get_array's list completion, and
+    // the member functions.  What outlives a gs_bin is NOT here: n_inst, n_coarse, round_gen, round_ids_off, pending_totals, fwd_fills_g2d, the fill-block
+    // counts, last_walked, counters_grid, the depth sort's feedback words, the view slots' history.
+    struct FrameLive {
+        bool frame_capped = false;           // capped lists (gs_config.list_cap): the tile lists were written only as far as the slot's history says they
+                                             // are walked; gs_get_array(GS_ARR_SORTED_IDS / _KEYS) completes them and clears it
+        const uint32_t *cap_src = nullptr;   // the history the caps of this frame come from (null: none)
+        bool have_l2 = false;                // the frame has level-2 lists, built with ...
+        GsBin3Args last_l2{};                // ... these arguments (read under have_l2 only: gs_get_array writes the capped rest with them)
+        bool spec_lists = false;             // speculative binning: the lists of this frame were enqueued before the totals were known ...
+        size_t spec_cap_coarse = 0, spec_cap_fine = 0;   // ... against these capacities (entries; read under spec_lists only)
+        bool g2d_clean = false;              // the gradient rows are cleared (enqueued: by the small path's kernel, or by the fill workgroups of the frame's
+                                             // forward): the frame's first composite backward needs no fill
+        uint32_t *perm_ptr = nullptr;        // the frame's depth order (null: index order, or BinPlan::perm_on_demand and nobody has asked yet)
+        void speculate(size_t cap_coarse, size_t cap_fine) { spec_lists = true; spec_cap_coarse = cap_coarse; spec_cap_fine = cap_fine; }
+        bool speculation_held(size_t coarse, size_t fine) { spec_lists = false; return coarse <= spec_cap_coarse && fine <= spec_cap_fine; }   // the totals are here: over
+        void relist_in_full() { cap_src = nullptr; frame_capped = false; have_l2 = false; }   // what two_level_lists(round 0) expects of its caller
+        void rows_dirtied() { g2d_clean = false; }                                            // a composite backward is about to accumulate into them
+    } live;
     // ---- the frame's bin plan: HOW gs_bin builds its lists.  Filled once per frame by plan_bin (gs_api_bin.hip), the one place that decides.  What later calls
-    // change is LIVE state and stays outside: frame_capped, have_l2 / last_l2, cap_src, pending_totals, spec_lists, perm_ptr, n_inst, n_coarse, round_gen, round_ids_off.
+    // change is live state (FrameLive, or a ctx member with a longer lifetime) and stays outside.
     struct BinPlan {
         enum class Path { TWO_LEVEL = 0, RADIX64 = 1, RADIX32 = 2, SMALL = 3 } path = Path::RADIX64;   // the values: what gs_get_bin_path reports
         int tile_bits = 0, gid_bits = 0, lo_bits = 0, hi_bits = 0;                        // bits of a tile index (low / high radix pass) and of a gaussian id
@@ -237,9 +261,7 @@ struct gs_ctx {
     hipEvent_t ev_main = nullptr, ev_order = nullptr;
     bool order_pending = false;              // an order kernel is in flight on the side stream (ev_order)
     // ---- speculative binning: the lists are enqueued with the capacities of the buffers at hand while the frame's totals travel
-    bool pending_totals = false;             // ev_count recorded, pinned totals not read yet
-    bool spec_lists = false;                 // the lists of this frame were enqueued before the totals were known ...
-    size_t spec_cap_coarse = 0, spec_cap_fine = 0;   // ... against these capacities (entries)
+    bool pending_totals = false;             // ev_count recorded, pinned totals not read yet (the speculation itself: FrameLive::spec_lists)
     int64_t n_coarse = 0;                    // coarse instances listed by the frame (two-level and small paths; 0 on the radix paths)
     DevBuf tile_dead;                        // slab frames: 4 lane masks per tile (frozen pixels between rounds)
     int dbg_win_start = 0, dbg_win_len = 0;  // gs_debug_set_window: the part of the launch order the debug launches cover (len 0: all)
@@ -275,18 +297,25 @@ struct gs_ctx {
     }
     // ---- small frames (gs_bin_small.hip): the whole of gs_bin in one launch.  Same predicate in gs_preprocess (which then folds no key
     // range: nothing is sorted globally) and in gs_bin.  bin_path 0 only (3 = the two-level path whatever the size; tests, A/B)
-    bool g2d_clean = false;                  // the gradient rows are cleared (enqueued: by the small path's kernel, or by the fill workgroups of the frame's
-                                             // forward): the frame's first composite backward needs no fill
-    bool fwd_fills_g2d = false;              // this frame's forward (round 0) carries the zero fill of g2d: decided once, in gs_forward
-    bool tail_fill() const { return !(cfg.debug_flags & GS_DEBUG_NO_TAIL_FILL) && (int64_t)gx * gy > 0; }   // the composite launches may carry zero fills
-    int fill_blocks_fwd = 0, fill_blocks_bwd = 0;   // fill workgroups the frame's last forward (round 0) / composite backward launch carried (gs_debug_tail_fill)
-    size_t g2d_bytes() const { return (cfg.deterministic ? sizeof(long long) : sizeof(float)) * GS_G2D_STRIDE * (n ? (size_t)n : 1); }
-    size_t shs_bytes() const { return sizeof(float) * width[4] * (size_t)(n > 0 ? n : 0); }   // the fifth gradient array: 3K x n floats
     bool small_bin_possible() const {
         if (cfg.bin_path != 0 || cfg.depth_sort != 0 || cfg.list_cap == 2 || cfg.slab_fractions[0] > 0.0f) return false;
         if (cfg.debug_flags & (GS_DEBUG_WIDE_CURSORS | GS_DEBUG_SUPER8 | GS_DEBUG_SUPER16 | GS_DEBUG_TINY_CAPS)) return false;
         return gs_bin_small_supported(n, gx, gy);
     }
+    // ---- the rows of 2-D gradient sums (g2d, feat_g2d): float, or fixed point in deterministic mode -- the ONE place that chooses.  A kernel takes a
+    // buffer of them as a pair of pointers of which exactly one is set: const for the readers, mutable for the composite backward (GsCompositeArgs)
+    template <typename F, typename L> struct RowsOf {
+        F *g2d; L *g2d_fixed;
+        template <typename A> void into(A &a) const { a.g2d = g2d; a.g2d_fixed = g2d_fixed; }   // the two members of an argument struct
+    };
+    using Rows = RowsOf<const float, const long long>; using RowsMut = RowsOf<float, long long>;
+    RowsMut rows_mut(const DevBuf &b) const { return cfg.deterministic ? RowsMut{nullptr, b.as<long long>()} : RowsMut{b.as<float>(), nullptr}; }
+    Rows rows(const DevBuf &b) const { const RowsMut m = rows_mut(b); return {m.g2d, m.g2d_fixed}; }
+    size_t g2d_bytes() const { return (cfg.deterministic ? sizeof(long long) : sizeof(float)) * GS_G2D_STRIDE * n1(); }
+    size_t shs_bytes() const { return sizeof(float) * width[4] * (size_t)(n > 0 ? n : 0); }   // the fifth gradient array: 3K x n floats
+    bool fwd_fills_g2d = false;              // this frame's forward (round 0) carries the zero fill of g2d: decided once, in gs_forward
+    bool tail_fill() const { return !(cfg.debug_flags & GS_DEBUG_NO_TAIL_FILL) && ntiles() > 0; }   // the composite launches may carry zero fills
+    int fill_blocks_fwd = 0, fill_blocks_bwd = 0;   // fill workgroups the frame's last forward (round 0) / composite backward launch carried (gs_debug_tail_fill)
     float *bound_image = nullptr, *bound_trans = nullptr;   // gs_bind_outputs: caller-owned device buffers the forward writes directly
     float *img() { return bound_image ? bound_image : image.as<float>(); }
     float *tr() { return bound_trans ? bound_trans : trans.as<float>(); }
@@ -339,6 +368,37 @@ inline int hipfail(gs_ctx *c, hipError_t e, const char *what) {
         if (e__ != hipSuccess) return hipfail((c), e__, #call);      \
     } while (0)
 
+// ---- the refusals entry points share: GS_OK, or the code with "<who>: ..." left for gs_last_error (built only when the call is refused)
+inline int need_3d(gs_ctx *c, const char *who) { return c->kind == 0 ? GS_OK : fail(c, GS_ERR_UNSUPPORTED, std::string(who) + ": 3-D renderer only"); }
+inline int need_mem(gs_ctx *c, const char *who, int mem) { return mem == GS_MEM_HOST || mem == GS_MEM_DEVICE ? GS_OK : fail(c, GS_ERR_INVALID, std::string(who) + ": bad mem"); }
+inline int need_image_size(gs_ctx *c, const char *who, int W, int H) {
+    return W > 0 && H > 0 && W <= 32767 && H <= 32767 ? GS_OK : fail(c, GS_ERR_INVALID, std::string(who) + ": image size must be in 1..32767");
+}
+// the frame has come at least as far as s, else GS_ERR_INVALID with this message (whole: the calls word what they need in their own way)
+inline int need_stage(gs_ctx *c, gs_ctx::Stage s, const char *msg) { return c->stage >= s ? GS_OK : fail(c, GS_ERR_INVALID, msg); }
+// two byte ranges share a byte (an empty or null one shares none)
+struct ByteRange { const void *p; size_t bytes; };
+inline bool overlaps(const ByteRange &a, const ByteRange &b) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
+    return a.p && b.p && a.bytes && b.bytes && x < y + b.bytes && y < x + a.bytes;
+}
+
+// ---- the model head of an argument struct: n, the five arrays, the ACTIVE degree and, where the struct carries it, the stored row stride
+template <typename A> auto model_head_stride(A &a, int stride, int) -> decltype((void)a.sh_stride) { a.sh_stride = stride; }
+template <typename A> void model_head_stride(A &, int, long) {}
+template <typename A> void model_head(const gs_ctx *c, A &a) {
+    a.n = c->n; a.sh_degree = c->active_sh_degree(); model_head_stride(a, c->sh_row_floats(), 0);
+    a.means = c->means; a.scales = c->scales; a.quats = c->quats; a.opac = c->opac; a.shs = c->shs;
+}
+// the per-gaussian chain behind a composite backward: the rows it reads, the colour path's scratch, the targets and what is done with a gradient float
+inline GsPreprocessBwdArgs chain_args(const gs_ctx *c, gs_ctx::Rows rows, float *dpc, const Five<float> &target, int overwrite, int shs_zeroed, float sgd_scale) {
+    GsPreprocessBwdArgs b{};
+    model_head(c, b); rows.into(b);
+    b.dpc = dpc; b.overwrite = overwrite; b.shs_zeroed = shs_zeroed; b.sgd_scale = sgd_scale;
+    b.d_means = target[0]; b.d_scales = target[1]; b.d_quats = target[2]; b.d_opac = target[3]; b.d_shs = target[4];
+    return b;
+}
+
 // One recorded pair of a stage -> the accumulators; false when the pair has not completed yet (it stays `fresh`).
 inline bool harvest_stage(gs_ctx *c, int s) {
     if (!c->ev_fresh[s]) return true;
@@ -384,14 +444,14 @@ inline int bind_device(gs_ctx *c) {
 // balance, and the order kernel is one more launch in a frame that is bound by launches (C2 0.382 -> 0.400 ms, C1 0.183 -> 0.205 ms
 // with it, same box; 0.393 / 0.197 with the kernel on the side stream).
 inline bool lpt_schedule(const gs_ctx *c) {
-    return (c->cfg.schedule == 3 || c->cfg.schedule == 4) && ((int64_t)c->gx * c->gy > c->wave_slots || (c->cfg.debug_flags & GS_DEBUG_ALWAYS_ORDER));
+    return (c->cfg.schedule == 3 || c->cfg.schedule == 4) && (c->ntiles() > c->wave_slots || (c->cfg.debug_flags & GS_DEBUG_ALWAYS_ORDER));
 }
 // Heavy tiles (round 5): the launch orders reserve a front region for the extra parts of split tiles (tile_lpt_order_kernel) when the
 // ctx may use them at all: automatic tile_parts, the early-out on, and a grid on which the frame-wide 2 / 4 waves per tile cannot engage.
 // A property of the ctx and the grid, so every order of a slot has one layout; whether a LAUNCH honours the split entries is decided
 // per frame (plan_frame: FramePlan::split).
 inline int lpt_front(const gs_ctx *c) {
-    const int64_t ntiles = (int64_t)c->gx * c->gy;
+    const int64_t ntiles = c->ntiles();
     return (lpt_schedule(c) && c->cfg.tile_parts == 0 && c->cfg.t_min > 0.0f && 2 * ntiles > c->wave_slots && ntiles <= GS_LPT_MAX_TILES) ? GS_LPT_FRONT : 0;
 }
 // the words behind an order's entries: list entries per backward segment of the split tiles (GS_SEG_SLOTS of them)
@@ -408,7 +468,7 @@ inline int order_index(const gs_ctx *c) { return c->view_slot >= 0 ? c->view_slo
 // gs_api_bin.hip
 int settle_totals(gs_ctx *c, bool *redo, bool may_relist);
 int bin_round(gs_ctx *c, int r);
-int depth_order(gs_ctx *c, uint32_t **perm_out);
+int depth_order(gs_ctx *c);                   // the frame's depth order -> c->perm, c->live.perm_ptr
 int blend_background(gs_ctx *c);              // gs_api_composite.hip: image += T bg over the frame's image, on the stream (no launch over black)
 // gs_api_composite.hip: the arguments of a composite launch of the frame, as its plan says (round r of the forward / the backward; debug: an isolated launch)
 GsCompositeArgs composite_args(gs_ctx *c, bool bwd, int r, bool debug = false);
