@@ -33,9 +33,12 @@ SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs
            "gs_adam_step", "gs_backward_adam",
            "gs_density_accumulate", "gs_density_decide", "gs_density_plan", "gs_density_restructure", "gs_opacity_reset",
            "gs_knn_mean_dist2", "gs_init_from_points",
-           "gs_view_depth", "gs_view_depth_backward", "gs_render_features", "gs_backward_features", "gs_backward_camera")
+           "gs_view_depth", "gs_view_depth_backward", "gs_render_features", "gs_backward_features", "gs_backward_camera",
+           "gs_image_metrics", "gs_metrics_finish")
 
 GS_CAMERA_GRAD_FLOATS = 40  # include/gsplat.h: gs_backward_camera
+GS_METRIC_SUMS = 4          # include/gsplat.h: gs_image_metrics
+(METRIC_MSE, METRIC_MAE, METRIC_SSIM, METRIC_PSNR, GS_METRIC_COUNT) = range(5)
 GS_ABI_VERSION = 3          # include/gsplat.h; load() refuses a library that reports another version
 GS_DEBUG_WIDE_CURSORS = 1
 GS_DEBUG_ALWAYS_ORDER = 2     # launch orders + side stream also on small frames (tests)
@@ -171,6 +174,8 @@ def load():
     L.gs_render_features.argtypes = [vp, vp, vp, vp]
     L.gs_backward_features.argtypes = [vp, vp, vp, vp, vp, G]
     L.gs_backward_camera.argtypes = [vp, vp, C.c_int]
+    L.gs_image_metrics.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int]
+    L.gs_metrics_finish.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if L.gs_abi_version() != GS_ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH} has ABI version {L.gs_abi_version()}, this binding is written for {GS_ABI_VERSION}: "
                            "rebuild with `python -m gaussiansplat_amd.build --force`")
@@ -182,6 +187,20 @@ def default_config() -> GsConfig:
     cfg = GsConfig()
     load().gs_default_config(C.byref(cfg))
     return cfg
+
+
+def metrics_finish(sums) -> np.ndarray:
+    """gs_metrics_finish: the four sums of gs_image_metrics -> float64 [mse, mae, ssim, psnr] (METRIC_*).  Pure host arithmetic: data range 1,
+    psnr = +inf at mse == 0, four NaNs when sum w is not > 0.  Needs the library, not a GPU."""
+    s = np.ascontiguousarray(sums, np.float64).reshape(-1)
+    if s.shape != (GS_METRIC_SUMS,):
+        raise ValueError(f"metrics_finish: {GS_METRIC_SUMS} sums expected, got {s.shape}")
+    out = np.empty(GS_METRIC_COUNT, np.float64)
+    dp = C.POINTER(C.c_double)
+    rc = load().gs_metrics_finish(s.ctypes.data_as(dp), out.ctypes.data_as(dp))
+    if rc != 0:
+        raise GsError(rc, "gs_metrics_finish")
+    return out
 
 
 class Context:
@@ -537,6 +556,30 @@ class Context:
             return out
         self._chk(self.L.gs_backward_camera(self.h, C.c_void_p(int(out_ptr)), GS_MEM_DEVICE))
         return None
+
+    # -- evaluation metrics: needs no model, camera or frame, and leaves the ctx's frame as it is
+    def image_metrics_host(self, img: np.ndarray, gt: np.ndarray, weight: "np.ndarray | None" = None, want_map: bool = False):
+        """gs_image_metrics on host images [C, H, W] (weight [H, W] or None): (sums, ssim_map) with sums the four float64 values
+        {sum w (x - y)^2, sum w |x - y|, sum w S, sum w} and ssim_map float32 [C, H, W] or None.  Synchronises."""
+        img = np.ascontiguousarray(img, np.float32); gt = np.ascontiguousarray(gt, np.float32)
+        if img.ndim != 3 or img.shape != gt.shape:
+            raise ValueError("image_metrics: img and gt must be [C, H, W] arrays of one shape")
+        Cn, H, W = img.shape
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, np.float32)
+            if weight.shape != (H, W):
+                raise ValueError(f"image_metrics: the weight must be [{H}, {W}], not {weight.shape}")
+        sums = np.empty(GS_METRIC_SUMS, np.float64)
+        smap = np.empty_like(img) if want_map else None
+        self._chk(self.L.gs_image_metrics(self.h, C.c_void_p(img.ctypes.data), C.c_void_p(gt.ctypes.data),
+                                          C.c_void_p(weight.ctypes.data) if weight is not None else None, W, H, Cn,
+                                          C.c_void_p(smap.ctypes.data) if smap is not None else None, C.c_void_p(sums.ctypes.data), GS_MEM_HOST))
+        return sums, smap
+
+    def image_metrics_device(self, img_ptr: int, gt_ptr: int, weight_ptr: int, W: int, H: int, Cn: int, map_ptr: int, sums_ptr: int):
+        """gs_image_metrics with device pointers (weight_ptr / map_ptr 0: none); sums_ptr: four device float64.  On the ctx stream, no sync."""
+        self._chk(self.L.gs_image_metrics(self.h, C.c_void_p(int(img_ptr or 0)), C.c_void_p(int(gt_ptr or 0)), C.c_void_p(int(weight_ptr or 0)),
+                                          int(W), int(H), int(Cn), C.c_void_p(int(map_ptr or 0)), C.c_void_p(int(sums_ptr or 0)), GS_MEM_DEVICE))
 
     def reset_grads(self, grads: GsGrads):
         self._chk(self.L.gs_reset_grads(self.h, C.byref(grads)))

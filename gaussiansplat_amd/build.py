@@ -58,6 +58,9 @@ SOURCES = {
     # camera gradient: the statement (gs_camera_grad.h) and the two reduction kernels round operation by operation, as tests/camera_grad_host.cpp does on the CPU
     "gs_camera.hip": ["-ffp-contract=off"],
     "gs_api_camera.hip": [],
+    # evaluation metrics: double arithmetic throughout, held to 1e-10 against a float64 restatement, not bit for bit: contraction stays on
+    "gs_metrics.hip": [],
+    "gs_api_metrics.hip": [],
     "gs_api.hip": [],
     "gs_api_bin.hip": [],
     "gs_api_composite.hip": [],

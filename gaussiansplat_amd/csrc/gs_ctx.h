@@ -10,6 +10,7 @@
 //   gs_api_knn.hip        point-cloud initialisation (gs_knn_mean_dist2, gs_init_from_points)
 //   gs_api_features.hip   feature maps (gs_view_depth, gs_render_features, gs_backward_features, gs_view_depth_backward)
 //   gs_api_camera.hip     the camera gradient (gs_backward_camera)
+//   gs_api_metrics.hip    evaluation metrics (gs_image_metrics, gs_metrics_finish)
 //   gs_background.hip     the background colour's two elementwise kernels (the forward's epilogue, gs_compose_target)
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
 // How far the frame has come is ONE ordered value (gs_ctx::Stage): every entry point compares it, reaches a stage or falls back to one.
@@ -349,6 +350,10 @@ struct gs_ctx {
     size_t feat_dpc_zeroed = 0;
     // ---- camera gradient (gs_api_camera.hip): the staged 40 floats of a GS_MEM_HOST call, then one row of 40 doubles per workgroup of gs_camera_grad_kernel
     DevBuf camera_partials;
+    // ---- evaluation metrics (gs_api_metrics.hip): the staged four sums of a GS_MEM_HOST call, then one row of four doubles per tile of
+    // gs_metrics.hip's kernel; the staged images and weight, and the staged map, of a GS_MEM_HOST call.  Buffers of their own: the call is legal in
+    // the middle of a frame and beside the loss
+    DevBuf metrics_partials, metrics_in[3], metrics_map;
     ncclComm_t comm = nullptr;
     int comm_ranks = 0;
 };

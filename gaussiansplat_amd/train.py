@@ -12,6 +12,8 @@ step has no host round trip.  `optimizer=optim.Adam(...)` replaces the SGD updat
 adds the other half of the 3DGS recipe: statistics after every backward, clone / split / prune and the opacity reset on schedule.
 `sh_schedule=SHDegreeSchedule(...)` is the recipe's SH degree schedule: band 0 first, one more band every `every` iterations.
 `background=(r, g, b)` or `background=RandomBackground(...)` renders and trains over that colour; an RGBA target is composited over it.
+`evaluator=Evaluator(cameras, targets, every)` (train) measures held-out views every `every` iterations: PSNR, MAE and the standard SSIM
+(metrics.evaluate, csrc/gs_metrics.hip), without changing what the iterations compute.
 """
 from __future__ import annotations
 
@@ -247,12 +249,48 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
     return loss
 
 
+class Evaluator:
+    """Held-out views evaluated during a training run: every `every` iterations train() renders `cameras` and compares them with
+    `targets` (metrics.evaluate: PSNR, MAE and the standard SSIM in double on the GPU) and appends (iteration, mean Metrics) to
+    `history`.  cameras: one Camera per target (None for the 2-D renderer); targets: [3, H, W] or RGBA [4, H, W] images; weights:
+    None or one [H, W] array or None per view; background: the colour to evaluate over (None: the renderer's current one).  Give the
+    evaluation cameras ids of their own: the id names the view slot, and the training views keep their launch-order history."""
+
+    def __init__(self, cameras, targets, every: int, weights=None, background=None):
+        if isinstance(every, bool) or int(every) != every or every < 1:
+            raise ValueError(f"Evaluator: every must be a positive integer, not {every!r}")
+        self.targets = list(targets)
+        V = len(self.targets)
+        self.cameras = [None] * V if cameras is None else list(cameras)
+        self.weights = None if weights is None else list(weights)
+        if len(self.cameras) != V:
+            raise ValueError(f"Evaluator: {len(self.cameras)} cameras for {V} targets")
+        if self.weights is not None and len(self.weights) != V:
+            raise ValueError(f"Evaluator: {len(self.weights)} weights for {V} targets")
+        self.every, self.background = int(every), background
+        self.history = []                                       # (iteration, metrics.Metrics: the mean over the views)
+
+    def due(self, iteration: int) -> bool:
+        """After iteration `iteration` (from 0): every `every`-th one."""
+        return (int(iteration) + 1) % self.every == 0
+
+    def run(self, renderer, iteration: int):
+        """Evaluate now and record the mean under `iteration`.  Returns the metrics.EvalResult."""
+        from .metrics import evaluate
+        res = evaluate(renderer, self.cameras, self.targets, self.weights, self.background)
+        self.history.append((int(iteration), res.mean))
+        return res
+
+
 def train(renderer, gtimg, lr: float, lossFunc: LossFunction, iterations: int = 100, camera=None, log_every: int = 0, optimizer=None,
-          density=None, sh_schedule=None, background=None, pose=None, freeze_model: bool = False):
+          density=None, sh_schedule=None, background=None, pose=None, freeze_model: bool = False, evaluator=None):
     """train.jl:16-59 without the GUI; the reference loops `while score < 0.99` on a score it never updates.
     optimizer: an optim.Adam that replaces the SGD update (lr is then ignored); density: a density.DensityController,
     sh_schedule: an SHDegreeSchedule, background: a colour or a RandomBackground, pose: an optim.CameraAdam that refines the view,
-    freeze_model: no parameter update -- with `pose`, pose refinement against a trained model (trainStep)."""
+    freeze_model: no parameter update -- with `pose`, pose refinement against a trained model (trainStep).
+    evaluator: an Evaluator; after iteration `it` with (it + 1) % evaluator.every == 0 its views are rendered and measured
+    (evaluator.history).  The evaluation leaves the renderer's camera, background and active SH degree as they were; None: the same
+    calls in the same order as without the argument."""
     losses = []
     for it in range(iterations):
         l = trainStep(renderer, gtimg, lr, lossFunc, camera, want_loss=True, optimizer=optimizer, density=density, sh_schedule=sh_schedule,
@@ -260,4 +298,6 @@ def train(renderer, gtimg, lr: float, lossFunc: LossFunction, iterations: int = 
         losses.append(l)
         if log_every and it % log_every == 0:
             print(f"loss : {l}")                             # loss.jl:69
+        if evaluator is not None and evaluator.due(it):
+            evaluator.run(renderer, it)
     return losses

@@ -574,6 +574,33 @@ int gs_backward_features(gs_ctx *ctx, const float *feat, const float *image_f, c
 #define GS_CAMERA_GRAD_FLOATS 40
 int gs_backward_camera(gs_ctx *ctx, float *out, int mem);
 
+/* ---- evaluation metrics: PSNR, MAE and the standard SSIM of a rendered image against its target ---- */
+
+/* gs_image_metrics.  img, gt: [C, H, W] float32 (x fastest, channel planes: the layout of the loss); weight: [H, W] float32 shared by all
+ * channels, or NULL (w = 1).  sums, OVERWRITTEN, over the C H W pixel-channels:
+ *   sums[0] = sum w (x - y)^2    sums[1] = sum w |x - y|    sums[2] = sum w S    sums[3] = sum w
+ * S is the standard SSIM map: window g_i = exp(-(i - 5)^2 / (2 1.5^2)), i = 0..10, normalised to sum 1 in double, the 2-D window its outer
+ * product; zero padding of 5 (samples outside the image contribute 0 to all five window sums); C1 = 0.01^2, C2 = 0.03^2;
+ *   S = (2 mu_x mu_y + C1)(2 s_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(s_x^2 + s_y^2 + C2)).
+ * The map is always that of the whole unweighted images: the weight enters only the four sums.  ssim_map ([C, H, W] float32, may be NULL)
+ * receives the map, one rounding from the double value.  Arithmetic: the float32 samples are widened to double, and the products, the five
+ * window sums, the map formula and (x - y) are evaluated in double -- a float32 SSIM is off by more than 1e-3 per pixel on nearly flat images,
+ * the size of the differences models are compared by.  The sums are added without atomics in a fixed order: bitwise reproducible call to call,
+ * the same through GS_MEM_HOST and GS_MEM_DEVICE, and independent of what the ctx did before.
+ * GS_MEM_HOST: every pointer is a host pointer, the data is staged through the ctx and the call synchronises.  GS_MEM_DEVICE: every pointer,
+ * sums included, is a device pointer; the work is enqueued on the ctx stream, no synchronise.  Needs no model, camera or frame and works
+ * under both renderers; image, transmittance, gradient sums, stage, view-slot history and stage timers stay as they were.
+ * GS_ERR_INVALID, nothing written, enqueued or allocated: a NULL ctx, img, gt or sums; W, H or C <= 0; C * H * W >= 2^31; a bad mem. */
+#define GS_METRIC_SUMS 4
+enum { GS_METRIC_MSE = 0, GS_METRIC_MAE, GS_METRIC_SSIM, GS_METRIC_PSNR, GS_METRIC_COUNT };
+int gs_image_metrics(gs_ctx *ctx, const float *img, const float *gt, const float *weight, int32_t W, int32_t H, int32_t C,
+                     float *ssim_map, double *sums, int mem);
+
+/* gs_metrics_finish.  Pure host arithmetic on the four sums (no ctx, no GPU): out[GS_METRIC_MSE] = s0 / s3, out[GS_METRIC_MAE] = s1 / s3,
+ * out[GS_METRIC_SSIM] = s2 / s3, out[GS_METRIC_PSNR] = -10 log10(mse) (data range 1; +inf when mse == 0).  All four are NaN when s3 is not
+ * > 0.  GS_OK for non-NULL arguments, else GS_ERR_INVALID. */
+int gs_metrics_finish(const double sums[GS_METRIC_SUMS], double out[GS_METRIC_COUNT]);
+
 /* ---- introspection (parity tests, profiling) ------------------------------------------- */
 
 typedef enum {

@@ -347,6 +347,32 @@ function hip_backward_camera(r::HipRenderer)
     return out
 end
 
+# evaluation metrics (gs_image_metrics): host arrays W x H x C like the loss; weight: W x H or nothing.  Returns the four double sums
+# {sum w (x - y)^2, sum w |x - y|, sum w S, sum w} (S: the standard SSIM map, evaluated in double on the GPU) and, with wantMap, the map.
+# hip_metricsFinish turns sums into (mse, mae, ssim, psnr): pure host arithmetic, data range 1, psnr = Inf at mse == 0, NaN when sum w is not > 0.
+const GS_METRIC_SUMS = 4
+const GS_METRIC_COUNT = 4
+function hip_imageMetrics(r::HipRenderer, img::Array{Float32, 3}, gt::Array{Float32, 3}; weight::Union{Nothing, Array{Float32, 2}} = nothing,
+                          wantMap::Bool = false)
+    size(img) == size(gt) || throw(ArgumentError("img and gt differ in size"))
+    weight === nothing || size(weight) == size(img)[1:2] || throw(ArgumentError("weight: one value per pixel"))
+    sums = Vector{Float64}(undef, GS_METRIC_SUMS)
+    ssimMap = wantMap ? similar(img) : nothing
+    w = weight === nothing ? Ptr{Float32}(C_NULL) : pointer(weight)
+    m = ssimMap === nothing ? Ptr{Float32}(C_NULL) : pointer(ssimMap)
+    GC.@preserve weight ssimMap check(r, ccall((:gs_image_metrics, libgs), Cint,
+                   (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Int32, Ptr{Float32}, Ptr{Float64}, Cint),
+                   r.ctx, img, gt, w, size(img, 1), size(img, 2), size(img, 3), m, sums, GS_MEM_HOST))
+    return sums, ssimMap
+end
+function hip_metricsFinish(sums::Vector{Float64})
+    length(sums) == GS_METRIC_SUMS || throw(ArgumentError("sums: $GS_METRIC_SUMS values"))
+    out = Vector{Float64}(undef, GS_METRIC_COUNT)
+    rc = ccall((:gs_metrics_finish, libgs), Cint, (Ptr{Float64}, Ptr{Float64}), sums, out)
+    rc == 0 || error("gs_metrics_finish: $rc")
+    return (mse = out[1], mae = out[2], ssim = out[3], psnr = out[4])
+end
+
 # the active SH degree (3-D renderer): evaluate bands 0 .. degree on rows that keep the model's stride; -1 = the model's own degree.
 # The request is the ctx's (it survives a later gs_set_model); a change of the effective degree drops the frame.
 hip_setActiveShDegree!(r::HipRenderer, degree::Integer = -1) =
