@@ -1,0 +1,196 @@
+"""Per-view appearance: a learned 3 x 4 colour affine per training view ("exposure compensation") and per-view pixel weights (masks).
+
+A real capture has auto-exposure and white balance that change from photograph to photograph, and regions that are not to be explained
+(sky, people, the rig).  The 3DGS recipe answers with one 3 x 4 affine per training image, learned by Adam beside the model, and with a
+mask multiplied into both images before the loss.  Both are one image-space stage between the frame and the loss,
+
+    out = w * (M rgb + b),        E = [M | b], 12 floats per view, starting at [I | 0]
+
+run on the device (csrc/gs_exposure.hip: gs_exposure_apply / gs_exposure_backward / gs_exposure_adam), bitwise reproducible.
+
+    exp = Exposure(renderer, n_views, weights=masks)         # masks: None, or one [H, W] array or None per view
+    train.trainStep(renderer, gt, lr, loss, camera, exposure=exp, view=v)
+    exp.set_lr(optim.ExponentialLR(0.01, 0.001, 30000)(it))  # the recipe's decay
+
+A view is an independent Adam problem: it has its own step count and is stepped when it is rendered, so a row never drifts on momentum
+while other views train.  Held-out views are measured without exposure (train.Evaluator), as the recipe does.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+
+def _check_lr(lr) -> float:
+    try:
+        v = float(lr)
+    except (TypeError, ValueError):
+        raise ValueError(f"Exposure: lr must be a number, got {lr!r}") from None
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError(f"Exposure: lr must be finite and >= 0, got {v}")
+    return v
+
+
+class Exposure:
+    """Exposure(renderer, n_views, weights=None, lr=0.01, betas=(0.9, 0.999), eps=1e-15).
+
+    Holds three device [V, 3, 4] float32 tensors -- the table (row v = view v's E, [I | 0] at the start), exp_avg and exp_avg_sq -- and
+    one Adam step count per view on the host.  weights: None, or a sequence of n_views entries, each None or an [H, W] array (uploaded
+    once).  Argument errors are ValueErrors raised before any GPU call."""
+
+    def __init__(self, renderer, n_views: int, weights=None, lr: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-15):
+        if isinstance(n_views, bool) or int(n_views) != n_views or n_views < 1:
+            raise ValueError(f"Exposure: n_views must be a positive integer, not {n_views!r}")
+        self.n_views = int(n_views)
+        self.lr = _check_lr(lr)
+        b1, b2 = (float(b) for b in betas)
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"Exposure: betas must lie in [0, 1), got {tuple(betas)}")
+        eps = float(eps)
+        if not math.isfinite(eps) or eps <= 0.0:
+            raise ValueError(f"Exposure: eps must be finite and > 0, got {eps}")
+        self.betas, self.eps = (b1, b2), eps
+        shape = tuple(int(s) for s in renderer.imageData.shape)
+        if len(shape) != 3 or shape[0] != 3:
+            raise ValueError(f"Exposure: the renderer's image must be [3, H, W], not {shape}")
+        self.H, self.W = shape[1], shape[2]
+        host_w = [None] * self.n_views
+        if weights is not None:
+            weights = list(weights)
+            if len(weights) != self.n_views:
+                raise ValueError(f"Exposure: {len(weights)} weights for {self.n_views} views")
+            for v, w in enumerate(weights):
+                if w is None:
+                    continue
+                a = np.ascontiguousarray(w.detach().cpu().numpy() if hasattr(w, "detach") else w, np.float32)
+                if a.shape != (self.H, self.W):
+                    raise ValueError(f"Exposure: the weight of view {v} must be [{self.H}, {self.W}], not {a.shape}")
+                host_w[v] = a
+        # -- everything above needs no device
+        import torch
+        self.renderer = renderer
+        dev = renderer.imageData.device
+        ident = torch.tensor([[1.0, 0.0, 0.0, 0.0], [0.0, 1.0, 0.0, 0.0], [0.0, 0.0, 1.0, 0.0]], dtype=torch.float32, device=dev)
+        self.table = ident.repeat(self.n_views, 1, 1).contiguous()
+        self.exp_avg = torch.zeros_like(self.table)
+        self.exp_avg_sq = torch.zeros_like(self.table)
+        self.step_counts = [0] * self.n_views
+        self.weights = [None if a is None else torch.tensor(a, dtype=torch.float32, device=dev) for a in host_w]
+        self._identity = ident                                  # the resident row of mask_target
+        self._grad = torch.zeros(12, dtype=torch.float32, device=dev)
+        self._out = None                                        # scratch of apply
+        self._masked = None                                     # scratch of mask_target
+        self._x = None                                          # the image of the last apply: what backward's d_exposure is taken at
+        self._x_view = -1
+        self._have_grad = -1                                    # the view whose gradient _grad holds (-1: none)
+
+    # -- arguments
+    def _view(self, view) -> int:
+        if isinstance(view, bool) or view is None or int(view) != view or not 0 <= int(view) < self.n_views:
+            raise ValueError(f"Exposure: view must be in 0..{self.n_views - 1}, not {view!r}")
+        return int(view)
+
+    def _image(self, img, what: str):
+        import torch
+        dev = self.table.device
+        t = img if isinstance(img, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(img, np.float32))
+        if tuple(t.shape) != (3, self.H, self.W):
+            raise ValueError(f"Exposure.{what}: the image must be [3, {self.H}, {self.W}], not {tuple(t.shape)}")
+        return t.to(dev, torch.float32).contiguous()
+
+    def _wptr(self, v: int) -> int:
+        w = self.weights[v]
+        return 0 if w is None else w.data_ptr()
+
+    def set_lr(self, lr):
+        """The rate of every later step, e.g. optim.ExponentialLR(0.01, 0.001, max_steps)(iteration)."""
+        self.lr = _check_lr(lr)
+
+    # -- the stage
+    def apply(self, view, img):
+        """w * (M img + b) under view `view`'s row and weight: a scratch tensor kept here and overwritten by the next call.  `img` (the
+        renderer's imageData in a training step) is what the next backward takes d_exposure at."""
+        import torch
+        v = self._view(view)
+        x = self._image(img, "apply")
+        if self._out is None:
+            self._out = torch.empty((3, self.H, self.W), dtype=torch.float32, device=self.table.device)
+        r = self.renderer
+        r._begin()
+        r.ctx.exposure_apply(x.data_ptr(), self.table[v].data_ptr(), self._wptr(v), self.W, self.H, self._out.data_ptr())
+        r._end()
+        self._x, self._x_view = x, v
+        return self._out
+
+    def backward(self, view, d_out, want_grad: bool = True):
+        """The adjoint of the last apply(view, img): returns d_img, written in place into d_out, and (want_grad) keeps the 12-float
+        gradient of the row for step()."""
+        v = self._view(view)
+        if self._x is None or self._x_view != v:
+            raise ValueError(f"Exposure.backward: apply(view={v}, img) first")
+        d = self._image(d_out, "backward")
+        r = self.renderer
+        r._begin()
+        r.ctx.exposure_backward(self._x.data_ptr(), d.data_ptr(), self.table[v].data_ptr(), self._wptr(v), self.W, self.H, d.data_ptr(),
+                                self._grad.data_ptr() if want_grad else 0)
+        r._end()
+        if want_grad:
+            self._have_grad = v
+        return d
+
+    def step(self, view):
+        """One Adam step of view `view`'s row from the gradient the last backward kept; the view's own step count advances."""
+        v = self._view(view)
+        if self._have_grad != v:
+            raise ValueError(f"Exposure.step: backward(view={v}, ...) with want_grad first")
+        t = self.step_counts[v] + 1
+        r = self.renderer
+        r._begin()
+        r.ctx.exposure_adam(self.table[v].data_ptr(), self._grad.data_ptr(), self.exp_avg[v].data_ptr(), self.exp_avg_sq[v].data_ptr(),
+                            self.lr, self.betas[0], self.betas[1], self.eps, t)
+        r._end()
+        self.step_counts[v] = t
+        self._have_grad = -1
+
+    def mask_target(self, view, gt):
+        """w * gt for view `view` (gs_exposure_apply with a resident identity row: exact), a scratch tensor overwritten by the next call;
+        `gt` itself when the view has no weight."""
+        import torch
+        v = self._view(view)
+        if self.weights[v] is None:
+            return gt
+        g = self._image(gt, "mask_target")
+        if self._masked is None:
+            self._masked = torch.empty((3, self.H, self.W), dtype=torch.float32, device=self.table.device)
+        r = self.renderer
+        r._begin()
+        r.ctx.exposure_apply(g.data_ptr(), self._identity.data_ptr(), self._wptr(v), self.W, self.H, self._masked.data_ptr())
+        r._end()
+        self._keep_gt = g
+        return self._masked
+
+    def exposure(self, view) -> np.ndarray:
+        """View `view`'s row as a 3 x 4 float32 array (one read-back)."""
+        return self.table[self._view(view)].detach().cpu().numpy()
+
+    # -- checkpoints
+    def state_dict(self) -> dict:
+        return dict(table=self.table.detach().clone(), exp_avg=self.exp_avg.detach().clone(), exp_avg_sq=self.exp_avg_sq.detach().clone(),
+                    steps=list(self.step_counts), lr=self.lr)
+
+    def load_state_dict(self, state: dict):
+        import torch
+        shape = (self.n_views, 3, 4)
+        for k in ("table", "exp_avg", "exp_avg_sq"):
+            t = state[k]
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+                raise ValueError(f"Exposure.load_state_dict: {k} must be a tensor of shape {shape}")
+        steps = [int(s) for s in state["steps"]]
+        if len(steps) != self.n_views or min(steps) < 0:
+            raise ValueError(f"Exposure.load_state_dict: {self.n_views} step counts >= 0 expected")
+        lr = _check_lr(state["lr"])
+        for k in ("table", "exp_avg", "exp_avg_sq"):
+            getattr(self, k).copy_(state[k])
+        self.step_counts, self.lr = steps, lr
+        self._have_grad = -1

@@ -34,10 +34,12 @@ SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs
            "gs_density_accumulate", "gs_density_decide", "gs_density_plan", "gs_density_restructure", "gs_opacity_reset",
            "gs_knn_mean_dist2", "gs_init_from_points",
            "gs_view_depth", "gs_view_depth_backward", "gs_render_features", "gs_backward_features", "gs_backward_camera",
-           "gs_image_metrics", "gs_metrics_finish")
+           "gs_image_metrics", "gs_metrics_finish",
+           "gs_exposure_apply", "gs_exposure_backward", "gs_exposure_adam")
 
 GS_CAMERA_GRAD_FLOATS = 40  # include/gsplat.h: gs_backward_camera
 GS_METRIC_SUMS = 4          # include/gsplat.h: gs_image_metrics
+GS_EXPOSURE_FLOATS = 12     # include/gsplat.h: a row of the exposure table, 3 x 4 row-major
 (METRIC_MSE, METRIC_MAE, METRIC_SSIM, METRIC_PSNR, GS_METRIC_COUNT) = range(5)
 GS_ABI_VERSION = 3          # include/gsplat.h; load() refuses a library that reports another version
 GS_DEBUG_WIDE_CURSORS = 1
@@ -176,6 +178,9 @@ def load():
     L.gs_backward_camera.argtypes = [vp, vp, C.c_int]
     L.gs_image_metrics.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int]
     L.gs_metrics_finish.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.gs_exposure_apply.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, vp]
+    L.gs_exposure_backward.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp]
+    L.gs_exposure_adam.argtypes = [vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64]
     if L.gs_abi_version() != GS_ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH} has ABI version {L.gs_abi_version()}, this binding is written for {GS_ABI_VERSION}: "
                            "rebuild with `python -m gaussiansplat_amd.build --force`")
@@ -580,6 +585,25 @@ class Context:
         """gs_image_metrics with device pointers (weight_ptr / map_ptr 0: none); sums_ptr: four device float64.  On the ctx stream, no sync."""
         self._chk(self.L.gs_image_metrics(self.h, C.c_void_p(int(img_ptr or 0)), C.c_void_p(int(gt_ptr or 0)), C.c_void_p(int(weight_ptr or 0)),
                                           int(W), int(H), int(Cn), C.c_void_p(int(map_ptr or 0)), C.c_void_p(int(sums_ptr or 0)), GS_MEM_DEVICE))
+
+    # -- per-view exposure: needs no model, camera or frame, and leaves the ctx's frame as it is.  Device pointers, no sync
+    def exposure_apply(self, img_ptr: int, exposure_ptr: int, weight_ptr: int, W: int, H: int, out_ptr: int):
+        """gs_exposure_apply: out [3, H, W] = w * (M img + b) per pixel, E = [M | b] 12 device floats (row-major 3 x 4), weight_ptr 0: none."""
+        self._chk(self.L.gs_exposure_apply(self.h, C.c_void_p(int(img_ptr or 0)), C.c_void_p(int(exposure_ptr or 0)), C.c_void_p(int(weight_ptr or 0)),
+                                           int(W), int(H), C.c_void_p(int(out_ptr or 0))))
+
+    def exposure_backward(self, img_ptr: int, d_out_ptr: int, exposure_ptr: int, weight_ptr: int, W: int, H: int, d_img_ptr: int,
+                          d_exposure_ptr: int = 0):
+        """gs_exposure_backward: d_img (may be d_out itself) and, unless d_exposure_ptr is 0, the 12 floats of d_exposure (overwritten)."""
+        self._chk(self.L.gs_exposure_backward(self.h, C.c_void_p(int(img_ptr or 0)), C.c_void_p(int(d_out_ptr or 0)), C.c_void_p(int(exposure_ptr or 0)),
+                                              C.c_void_p(int(weight_ptr or 0)), int(W), int(H), C.c_void_p(int(d_img_ptr or 0)),
+                                              C.c_void_p(int(d_exposure_ptr or 0))))
+
+    def exposure_adam(self, exposure_ptr: int, d_exposure_ptr: int, exp_avg_ptr: int, exp_avg_sq_ptr: int, lr: float, beta1: float, beta2: float,
+                      eps: float, step: int):
+        """gs_exposure_adam: one Adam step of a row of 12 floats (gs_adam_step's update); step counts from 1 and is the row's own."""
+        self._chk(self.L.gs_exposure_adam(self.h, C.c_void_p(int(exposure_ptr or 0)), C.c_void_p(int(d_exposure_ptr or 0)), C.c_void_p(int(exp_avg_ptr or 0)),
+                                          C.c_void_p(int(exp_avg_sq_ptr or 0)), float(lr), float(beta1), float(beta2), float(eps), int(step)))
 
     def reset_grads(self, grads: GsGrads):
         self._chk(self.L.gs_reset_grads(self.h, C.byref(grads)))

@@ -61,6 +61,9 @@ SOURCES = {
     # evaluation metrics: double arithmetic throughout, held to 1e-10 against a float64 restatement, not bit for bit: contraction stays on
     "gs_metrics.hip": [],
     "gs_api_metrics.hip": [],
+    # per-view exposure: the affine, its adjoints and the row's Adam step are specified operation by operation (tests/exposure_ref.py matches bit for bit)
+    "gs_exposure.hip": ["-ffp-contract=off"],
+    "gs_api_exposure.hip": [],
     "gs_api.hip": [],
     "gs_api_bin.hip": [],
     "gs_api_composite.hip": [],

@@ -42,5 +42,8 @@ __device__ __forceinline__ void gs_adam_update(float &p, float &m, float &v, flo
 // host (gs_adam.hip): the checks shared by gs_adam_step and gs_backward_adam, and the step's scalars.  g == NULL: the fused form
 // (every group stepped, no gradient arrays).  On failure nothing has been enqueued.
 struct gs_ctx;
+// ... and the part of it that every Adam step shares, gs_exposure_adam included: the refusals of step, betas, eps and the nlr rates, then
+// the scalars, each in double and rounded to float once (step_size[i] from lr[i], i < nlr; the rest 0)
+int gs_adam_scalars(struct gs_ctx *c, const char *who, const float *lr, int nlr, float beta1, float beta2, float eps, int64_t step, GsAdamHyper *h);
 int gs_adam_prepare(struct gs_ctx *c, const char *who, const float *const p[5], const float *const g[5], float *const m[5], float *const v[5],
                     const float *lr, float beta1, float beta2, float eps, int64_t step, int flags, GsAdamHyper *h);

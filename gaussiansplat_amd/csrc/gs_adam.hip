@@ -150,15 +150,29 @@ __global__ __launch_bounds__(256) void gs_adam_selective_kernel(AdamArgs a) {
 
 }  // namespace
 
-int gs_adam_prepare(gs_ctx *c, const char *who, const float *const p[5], const float *const g[5], float *const m[5], float *const v[5],
-                    const float *lr, float beta1, float beta2, float eps, int64_t step, int flags, GsAdamHyper *h) {
+int gs_adam_scalars(gs_ctx *c, const char *who, const float *lr, int nlr, float beta1, float beta2, float eps, int64_t step, GsAdamHyper *h) {
     const std::string w(who);
     if (step < 1) return fail(c, GS_ERR_INVALID, w + ": step counts from 1");
     if (!(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f)) return fail(c, GS_ERR_INVALID, w + ": betas must lie in [0, 1)");
     if (!std::isfinite(eps) || !(eps > 0.0f)) return fail(c, GS_ERR_INVALID, w + ": eps must be finite and > 0");
     if (!lr) return fail(c, GS_ERR_INVALID, w + ": NULL lr");
-    for (int i = 0; i < GS_ADAM_GROUPS; ++i)
+    for (int i = 0; i < nlr; ++i)
         if (!std::isfinite(lr[i]) || lr[i] < 0.0f) return fail(c, GS_ERR_INVALID, w + ": every lr must be finite and >= 0");
+    // the scalars: each in double, rounded to float once
+    const double t = (double)step;
+    h->beta1 = beta1; h->beta2 = beta2; h->eps = eps;
+    h->omb1 = (float)(1.0 - (double)beta1);
+    h->omb2 = (float)(1.0 - (double)beta2);
+    const double bc1 = 1.0 - std::pow((double)beta1, t);
+    for (int i = 0; i < GS_ADAM_NGROUPS; ++i) h->step_size[i] = i < nlr ? (float)((double)lr[i] / bc1) : 0.0f;
+    h->sqrt_bc2 = (float)std::sqrt(1.0 - std::pow((double)beta2, t));
+    return GS_OK;
+}
+
+int gs_adam_prepare(gs_ctx *c, const char *who, const float *const p[5], const float *const g[5], float *const m[5], float *const v[5],
+                    const float *lr, float beta1, float beta2, float eps, int64_t step, int flags, GsAdamHyper *h) {
+    const std::string w(who);
+    if (const int rc = gs_adam_scalars(c, who, lr, GS_ADAM_GROUPS, beta1, beta2, eps, step, h)) return rc;
     if (flags & ~GS_ADAM_SELECTIVE) return fail(c, GS_ERR_INVALID, w + ": unknown flag bits");
     // the arrays the step touches must not overlap: p, g, m, v of every group that is stepped
     ByteRange r[20];
@@ -175,14 +189,6 @@ int gs_adam_prepare(gs_ctx *c, const char *who, const float *const p[5], const f
     for (int i = 0; i < nr; ++i)
         for (int j = i + 1; j < nr; ++j)
             if (overlaps(r[i], r[j])) return fail(c, GS_ERR_INVALID, w + ": parameter, gradient and moment arrays overlap");
-    // the scalars: each in double, rounded to float once
-    const double t = (double)step;
-    h->beta1 = beta1; h->beta2 = beta2; h->eps = eps;
-    h->omb1 = (float)(1.0 - (double)beta1);
-    h->omb2 = (float)(1.0 - (double)beta2);
-    const double bc1 = 1.0 - std::pow((double)beta1, t);
-    for (int i = 0; i < GS_ADAM_NGROUPS; ++i) h->step_size[i] = (float)((double)lr[i] / bc1);
-    h->sqrt_bc2 = (float)std::sqrt(1.0 - std::pow((double)beta2, t));
     return GS_OK;
 }
 

@@ -11,29 +11,9 @@
 // Built with -ffp-contract=off (gaussiansplat_amd/build.py); the statement turns contraction off itself.
 #include "gs_camera_grad.h"
 #include "gs_sh.h"             // gs_sh_dispatch: the instantiation from (active degree, row stride)
+#include "gs_wave_sum.h"       // gs_wave_sum: the fixed tree over the wave
 
 #pragma clang fp contract(off)
-
-// a double moved across lanes by a DPP control, as its two 32-bit halves
-template <int CTRL>
-__device__ __forceinline__ double gs_dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-// The sum over the wave's 64 lanes in a fixed tree; every lane returns it.  Inside a row of 16 lanes the partner comes by DPP (two moves on
-// the vector unit): lane ^ 1, lane ^ 2 (quad_perm), then the mirror image inside 8 and inside 16 lanes -- after the first two steps the
-// four lanes of a quad hold the same sum, so the mirror pairs quad with quad, and then half with half.  Across rows: __shfl_xor by 16
-// and 32 (ds_bpermute_b32 of the two halves).  Both partners of a pair form a + b and b + a: the same bits.
-__device__ __forceinline__ double gs_wave_sum(double v) {
-    v = v + gs_dpp_f64<0xB1>(v);           // quad_perm [1, 0, 3, 2]
-    v = v + gs_dpp_f64<0x4E>(v);           // quad_perm [2, 3, 0, 1]
-    v = v + gs_dpp_f64<0x141>(v);          // row_half_mirror
-    v = v + gs_dpp_f64<0x140>(v);          // row_mirror
-    v = v + __shfl_xor(v, 16, 64);
-    v = v + __shfl_xor(v, 32, 64);
-    return v;
-}
 
 template <int DEG>
 __global__ __launch_bounds__(256) void gs_camera_grad_kernel(GsCameraGradArgs a, GsCamera cam) {

@@ -11,6 +11,7 @@
 //   gs_api_features.hip   feature maps (gs_view_depth, gs_render_features, gs_backward_features, gs_view_depth_backward)
 //   gs_api_camera.hip     the camera gradient (gs_backward_camera)
 //   gs_api_metrics.hip    evaluation metrics (gs_image_metrics, gs_metrics_finish)
+//   gs_api_exposure.hip   the per-view exposure stage (gs_exposure_apply, gs_exposure_backward, gs_exposure_adam)
 //   gs_background.hip     the background colour's two elementwise kernels (the forward's epilogue, gs_compose_target)
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
 // How far the frame has come is ONE ordered value (gs_ctx::Stage): every entry point compares it, reaches a stage or falls back to one.
@@ -354,6 +355,8 @@ struct gs_ctx {
     // gs_metrics.hip's kernel; the staged images and weight, and the staged map, of a GS_MEM_HOST call.  Buffers of their own: the call is legal in
     // the middle of a frame and beside the loss
     DevBuf metrics_partials, metrics_in[3], metrics_map;
+    // ---- per-view exposure (gs_api_exposure.hip): one row of 12 doubles per workgroup of exposure_bwd_kernel, as many as (W, H) says
+    DevBuf exposure_partials;
     ncclComm_t comm = nullptr;
     int comm_ranks = 0;
 };

@@ -36,6 +36,38 @@ def _check_rate(name: str, value) -> float:
     return v
 
 
+class ExponentialLR:
+    """ExponentialLR(lr_init, lr_final, max_steps, delay_steps=0, delay_mult=1.0): the 3DGS recipe's log-linear decay, callable as lr(step).
+
+        t = clip(step / max_steps, 0, 1);   lr = exp((1 - t) log lr_init + t log lr_final)
+        times  delay_mult + (1 - delay_mult) sin(pi / 2 clip(step / delay_steps, 0, 1))  when delay_steps > 0
+
+    0 for a negative step, or when both rates are 0.  Pure host arithmetic in double: for Adam.set_lr(means=lr(it)) -- the decay of the
+    position rate -- and appearance.Exposure.set_lr(lr(it)) alike."""
+
+    def __init__(self, lr_init: float, lr_final: float, max_steps: int, delay_steps: int = 0, delay_mult: float = 1.0):
+        self.lr_init, self.lr_final = _check_rate("lr_init", lr_init), _check_rate("lr_final", lr_final)
+        if (self.lr_init == 0.0) != (self.lr_final == 0.0):
+            raise ValueError("ExponentialLR: lr_init and lr_final must both be > 0, or both 0 (a log-linear decay cannot reach or leave 0)")
+        if isinstance(max_steps, bool) or int(max_steps) != max_steps or max_steps < 1:
+            raise ValueError(f"ExponentialLR: max_steps must be a positive integer, not {max_steps!r}")
+        if isinstance(delay_steps, bool) or int(delay_steps) != delay_steps or delay_steps < 0:
+            raise ValueError(f"ExponentialLR: delay_steps must be an integer >= 0, not {delay_steps!r}")
+        self.max_steps, self.delay_steps = int(max_steps), int(delay_steps)
+        self.delay_mult = float(delay_mult)
+        if not math.isfinite(self.delay_mult) or self.delay_mult < 0.0:
+            raise ValueError(f"ExponentialLR: delay_mult must be finite and >= 0, got {delay_mult!r}")
+
+    def __call__(self, step) -> float:
+        if step < 0 or (self.lr_init == 0.0 and self.lr_final == 0.0):
+            return 0.0
+        t = min(max(step / self.max_steps, 0.0), 1.0)
+        lr = math.exp((1.0 - t) * math.log(self.lr_init) + t * math.log(self.lr_final))
+        if self.delay_steps > 0:
+            lr *= self.delay_mult + (1.0 - self.delay_mult) * math.sin(0.5 * math.pi * min(max(step / self.delay_steps, 0.0), 1.0))
+        return lr
+
+
 class Adam:
     """Adam(renderer, lr, betas=(0.9, 0.999), eps=1e-8, selective=False, fused=False).
 

@@ -14,6 +14,8 @@ adds the other half of the 3DGS recipe: statistics after every backward, clone /
 `background=(r, g, b)` or `background=RandomBackground(...)` renders and trains over that colour; an RGBA target is composited over it.
 `evaluator=Evaluator(cameras, targets, every)` (train) measures held-out views every `every` iterations: PSNR, MAE and the standard SSIM
 (metrics.evaluate, csrc/gs_metrics.hip), without changing what the iterations compute.
+`exposure=appearance.Exposure(...)` with `view=v` puts the per-view exposure stage between the frame and the loss: a learned 3 x 4 colour
+affine per training view and per-view pixel weights (csrc/gs_exposure.hip); the optimisers see its d_img where they saw the loss's.
 """
 from __future__ import annotations
 
@@ -163,7 +165,8 @@ def _pose_step(renderer, pose):
 
 
 def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, want_loss: bool = True, fused_sgd: bool = False,
-              optimizer=None, density=None, sh_schedule=None, background=None, pose=None, freeze_model: bool = False):
+              optimizer=None, density=None, sh_schedule=None, background=None, pose=None, freeze_model: bool = False, exposure=None,
+              view=None):
     """One iteration of train.jl:33-56 as intended (see module docstring).
     fused_sgd (3-D renderer): backward and the parameter update in one pass (gs_backward_sgd) -- the same parameters bit for
     bit (deterministic mode), but renderer.splatGrads is not filled.
@@ -182,7 +185,17 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
     update (the camera gradient is recomputed from the resident model, so this is the only place) it takes renderer.backwardCamera,
     chains it to the camera's fields (camera.camera_param_grads) and steps the pose.  The fused forms leave no frame: a ValueError, as
     with density control; so is an explicit `camera` beside it.  None: the same calls in the same order as without the argument.
-    freeze_model: no parameter update (the gradients are still reset) -- with `pose`, registering a view against a trained model."""
+    freeze_model: no parameter update (the gradients are still reset) -- with `pose`, registering a view against a trained model.
+    exposure (appearance.Exposure) with view (its row): after the forward the frame goes through exposure.apply(view, imageData); the
+    target, composed as above, through exposure.mask_target; the loss compares the two; exposure.backward(view, dC) turns the loss's image
+    gradient into the frame's, in place, and keeps the row's gradient; exposure.step(view) steps the row; the rest of the iteration is
+    the one above on that gradient, so every optimiser form, the fused ones included, density control, the SH schedule, the backgrounds,
+    pose and freeze_model run unchanged.  One without the other, or a view out of range, is a ValueError.  None: the same calls in the
+    same order as without the arguments."""
+    if (exposure is None) != (view is None):
+        raise ValueError("trainStep: exposure and view go together (the view names the row of the exposure table)")
+    if exposure is not None:
+        view = exposure._view(view)
     if pose is not None and camera is not None:
         raise ValueError("trainStep: camera and pose exclude each other (the iteration renders under pose.camera)")
     if pose is not None and (fused_sgd or (optimizer is not None and optimizer.fused)):
@@ -212,7 +225,13 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
     R.forward(renderer, tps)
     if getattr(gtimg, "ndim", 0) == 3 and gtimg.shape[0] == 4:
         gtimg = lossFunc.compose_target(gtimg)
-    loss, ΔC = lossFunc.value_and_grad(renderer.imageData, gtimg, want_loss)
+    if exposure is None:
+        loss, ΔC = lossFunc.value_and_grad(renderer.imageData, gtimg, want_loss)
+    else:
+        adjusted = exposure.apply(view, renderer.imageData)
+        loss, ΔC = lossFunc.value_and_grad(adjusted, exposure.mask_target(view, gtimg), want_loss)
+        ΔC = exposure.backward(view, ΔC)
+        exposure.step(view)
     if optimizer is not None:
         if optimizer.fused:
             optimizer.backward_step(ΔC)
@@ -283,18 +302,19 @@ class Evaluator:
 
 
 def train(renderer, gtimg, lr: float, lossFunc: LossFunction, iterations: int = 100, camera=None, log_every: int = 0, optimizer=None,
-          density=None, sh_schedule=None, background=None, pose=None, freeze_model: bool = False, evaluator=None):
+          density=None, sh_schedule=None, background=None, pose=None, freeze_model: bool = False, evaluator=None, exposure=None, view=None):
     """train.jl:16-59 without the GUI; the reference loops `while score < 0.99` on a score it never updates.
     optimizer: an optim.Adam that replaces the SGD update (lr is then ignored); density: a density.DensityController,
     sh_schedule: an SHDegreeSchedule, background: a colour or a RandomBackground, pose: an optim.CameraAdam that refines the view,
     freeze_model: no parameter update -- with `pose`, pose refinement against a trained model (trainStep).
     evaluator: an Evaluator; after iteration `it` with (it + 1) % evaluator.every == 0 its views are rendered and measured
     (evaluator.history).  The evaluation leaves the renderer's camera, background and active SH degree as they were; None: the same
-    calls in the same order as without the argument."""
+    calls in the same order as without the argument.
+    exposure, view: an appearance.Exposure and the row of this target's view (trainStep); the evaluator's views are measured without it."""
     losses = []
     for it in range(iterations):
         l = trainStep(renderer, gtimg, lr, lossFunc, camera, want_loss=True, optimizer=optimizer, density=density, sh_schedule=sh_schedule,
-                      background=background, pose=pose, freeze_model=freeze_model)
+                      background=background, pose=pose, freeze_model=freeze_model, exposure=exposure, view=view)
         losses.append(l)
         if log_every and it % log_every == 0:
             print(f"loss : {l}")                             # loss.jl:69

@@ -17,6 +17,9 @@
  *   gs_backward               backward(renderer, dC)              src/backward.jl:3-38
  *   gs_reset_grads            resetGrads(renderer.splatGrads)     src/splat.jl:158-173
  *   gs_backward_camera        (none: the reference's camera is a constant) the frame's gradient into T, P, eye, lookAt, fx, fy
+ *   gs_exposure_apply         (none: the reference's loss sees the raw frame) out = w (M rgb + b), a 3 x 4 colour affine per view and a mask
+ *   gs_exposure_backward      (none: the reference's loss sees the raw frame) its adjoints into the image and into the 12 floats
+ *   gs_exposure_adam          (none: the reference's loss sees the raw frame) the Adam step of one view's 12 floats
  *
  * Conventions
  *   - plain C: pointers + sizes, no exceptions; every function returns 0 (GS_OK) or a
@@ -600,6 +603,33 @@ int gs_image_metrics(gs_ctx *ctx, const float *img, const float *gt, const float
  * out[GS_METRIC_SSIM] = s2 / s3, out[GS_METRIC_PSNR] = -10 log10(mse) (data range 1; +inf when mse == 0).  All four are NaN when s3 is not
  * > 0.  GS_OK for non-NULL arguments, else GS_ERR_INVALID. */
 int gs_metrics_finish(const double sums[GS_METRIC_SUMS], double out[GS_METRIC_COUNT]);
+
+/* ---- per-view exposure: a learned 3 x 4 colour affine and a mask between gs_forward and the loss ---- */
+
+/* Images are planar [3, H, W] float32 (the layout of the loss); exposure: 12 floats E, row-major 3 x 4 -- E[4 r + 0..2] row r of the matrix,
+ * E[4 r + 3] its offset; weight: [H, W] float32 or NULL.  Float32 throughout, one rounding per operation, no fma contraction, in this order:
+ *   gs_exposure_apply     a_r = ((E[r][0] x0 + E[r][1] x1) + E[r][2] x2) + E[r][3];   out_r = w a_r   (no weight: out_r = a_r)
+ *   gs_exposure_backward  g_r = w d_r   (no weight: g_r = d_r);   d_img_k = (E[0][k] g0 + E[1][k] g1) + E[2][k] g2;   and, unless d_exposure
+ *                         is NULL, d_exposure[4 r + k] = sum over the pixels of (double)g_r * (double)x_k, x_3 = 1: exact products, added
+ *                         in double in a fixed order without atomics and rounded to float once.  OVERWRITTEN, 12 floats.
+ * Identity E ([I | 0]) without a weight returns x for every finite x (the bits but for -0, which becomes +0); identity E with a weight
+ * returns w * x exactly, which is how a target is masked.  d_img may be d_out itself (in place).  Results are bitwise reproducible call to
+ * call and independent of what the ctx did before, of the alignment of the buffers and of d_exposure being asked for.
+ * Every pointer is a DEVICE pointer on the ctx's device (E too: the row of a table that gs_exposure_adam has just stepped); the work is
+ * enqueued on the ctx stream, no synchronise.  Needs no model, camera or frame and works under both renderers; image, transmittance,
+ * gradient sums, stage, view-slot history and stage timers stay as they were.
+ * GS_ERR_INVALID, nothing written, enqueued or allocated: a NULL ctx, img, exposure, out, d_out or d_img; W or H <= 0; 3 * W * H >= 2^31; out
+ * overlapping img, weight or exposure; d_img overlapping img, weight, exposure or d_exposure, or d_out in any way but d_img == d_out. */
+int gs_exposure_apply(gs_ctx *ctx, const float *img, const float *exposure, const float *weight, int32_t W, int32_t H, float *out);
+int gs_exposure_backward(gs_ctx *ctx, const float *img, const float *d_out, const float *exposure, const float *weight, int32_t W, int32_t H,
+                         float *d_img, float *d_exposure);
+/* One Adam step of the 12 floats of a row from d_exposure, with its own moments exp_avg and exp_avg_sq (12 floats each, zero before the
+ * first step): gs_adam_step's update and host scalars exactly (t = step counts from 1 and is the ROW's own count: a view is stepped when it
+ * is rendered).  Device pointers, enqueued on the ctx stream, no synchronise; the ctx's frame stays as it was (no model array is touched).
+ * lr == 0 leaves the row unchanged and still updates the moments.  GS_ERR_INVALID, nothing written: a NULL pointer, step < 1, a beta
+ * outside [0, 1), eps not finite or not > 0, lr negative or not finite, any two of the four rows overlapping. */
+int gs_exposure_adam(gs_ctx *ctx, float *exposure, const float *d_exposure, float *exp_avg, float *exp_avg_sq, float lr, float beta1,
+                     float beta2, float eps, int64_t step);
 
 /* ---- introspection (parity tests, profiling) ------------------------------------------- */
 

@@ -373,6 +373,25 @@ function hip_metricsFinish(sums::Vector{Float64})
     return (mse = out[1], mae = out[2], ssim = out[3], psnr = out[4])
 end
 
+# per-view exposure (gs_exposure_apply / _backward / _adam): a 3 x 4 colour affine E (12 floats, row-major) and an optional W x H weight
+# between hip_forward! and the loss: out = w .* (M * rgb + b).  Every array is a DEVICE pointer (E too: the row of a table the Adam step has
+# just written); enqueued on the ctx stream, no synchronise; the frame stays as it was.  weight and dExposure may be C_NULL; dImg may be dOut.
+const GS_EXPOSURE_FLOATS = 12
+hip_exposureApply!(r::HipRenderer, img::Ptr{Float32}, exposure::Ptr{Float32}, weight::Ptr{Float32}, W::Integer, H::Integer, out::Ptr{Float32}) =
+    check(r, ccall((:gs_exposure_apply, libgs), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Ptr{Float32}),
+                   r.ctx, img, exposure, weight, W, H, out))
+hip_exposureBackward!(r::HipRenderer, img::Ptr{Float32}, dOut::Ptr{Float32}, exposure::Ptr{Float32}, weight::Ptr{Float32}, W::Integer, H::Integer,
+                      dImg::Ptr{Float32}, dExposure::Ptr{Float32} = Ptr{Float32}(C_NULL)) =
+    check(r, ccall((:gs_exposure_backward, libgs), Cint,
+                   (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Ptr{Float32}, Ptr{Float32}),
+                   r.ctx, img, dOut, exposure, weight, W, H, dImg, dExposure))
+# one Adam step of a row (12 floats) with its own moments; `step` counts from 1 and is the row's own (a view is stepped when it is rendered)
+hip_exposureAdam!(r::HipRenderer, exposure::Ptr{Float32}, dExposure::Ptr{Float32}, expAvg::Ptr{Float32}, expAvgSq::Ptr{Float32}, lr::Real, step::Integer;
+                  beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-15) =
+    check(r, ccall((:gs_exposure_adam, libgs), Cint,
+                   (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, Cfloat, Cfloat, Int64),
+                   r.ctx, exposure, dExposure, expAvg, expAvgSq, lr, beta1, beta2, eps, Int64(step)))
+
 # the active SH degree (3-D renderer): evaluate bands 0 .. degree on rows that keep the model's stride; -1 = the model's own degree.
 # The request is the ctx's (it survives a later gs_set_model); a change of the effective degree drops the frame.
 hip_setActiveShDegree!(r::HipRenderer, degree::Integer = -1) =
