@@ -12,6 +12,7 @@
 //              wave would pay too).  A dead row costs its gradient read only.
 #include "gs_ctx.h"
 #include "gs_adam.h"
+#include "gs_wave.h"
 
 #define GS_ADAM_ROWS 64              // gaussians per workgroup pass of the selective kernel (= the wave size: one ballot compacts them)
 #define GS_ADAM_MAX_BLOCKS 2048      // 256 CUs x 8 workgroups: memory-bound, capped grid + grid-stride loops
@@ -121,9 +122,9 @@ __global__ __launch_bounds__(256) void gs_adam_selective_kernel(AdamArgs a) {
         // the live rows, compacted by one wave, so that the lanes of the update loop all do useful work
         if (threadIdx.x < GS_ADAM_ROWS) {
             const bool l = threadIdx.x < rows && live[threadIdx.x];
-            const unsigned long long b = __ballot(l);
-            if (l) order[__popcll(b & ((1ull << threadIdx.x) - 1ull))] = threadIdx.x;
-            if (threadIdx.x == 0) nlive = __popcll(b);
+            const GsWaveRank r = gs_wave_rank(l, threadIdx.x);
+            if (l) order[r.below] = threadIdx.x;
+            if (threadIdx.x == 0) nlive = r.count;
         }
         __syncthreads();
         const int nl = nlive;

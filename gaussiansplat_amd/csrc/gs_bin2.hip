@@ -20,6 +20,7 @@
 // 8 + 2 x 24 + 8 = 64 B for emit + two 64-bit passes + ranges.  Integer/byte work: coalesced 4-byte
 // streams, LDS histograms, LDS-staged scatter; no MFMA.
 #include "gs_radix.h"
+#include "gs_wave.h"
 
 // ---------------------------------------------------------------- tile counts -> ranges
 // Per-tile list lengths = number of rectangles covering each tile.  Each rectangle is four +-1
@@ -331,8 +332,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs32_scatter_kernel(const uint32_t
 __global__ void sum_digit_totals_kernel(const uint32_t *__restrict__ digit_total, uint32_t *__restrict__ out) {
     uint32_t v = 0;
     for (int i = threadIdx.x; i < RS_RADIX; i += 64) v += digit_total[i];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
+    v = gs_wave_sum_down(v);
     if (threadIdx.x == 0) *out = v;
 }
 

@@ -23,6 +23,7 @@
 // HBM traffic per instance: the 4-byte id written once (+ 6 B per COARSE instance written and read twice), against
 // 16 B per instance for gs_bin2.hip.  The tile ranges are the exclusive scan of the level-2 hit counts.
 #include "gs_radix.h"
+#include "gs_wave.h"
 
 // Super-tile edge: 8 tiles (SBS = 3), or 16 tiles (SBS = 4) on grids whose 8 x 8 super-tiles would be more than GS_BIN3_NS8_MAX:
 // level 1 works per (chunk of positions, super-tile) and its cost per position grows with the number of super-tiles (4K: 510 of
@@ -45,17 +46,6 @@ int gs_bin3_group(int ns) {
     return g;
 }
 bool gs_bin3_supported(int ns) { return l1_lds_bytes(ns, 256) <= 140 * 1024 && ns < (1 << 16); }     // (l1_scatter packs S << 16 | clipped rectangle)
-
-__device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t *sm, int nwaves) {
-#pragma unroll
-    for (int d = GS_WAVE / 2; d > 0; d >>= 1) v += __shfl_down(v, d);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t t = 0;
-    for (int i = 0; i < nwaves; ++i) t += sm[i];
-    return t;
-}
 
 // ---------------------------------------------------------------- level 1
 struct L1Args {
@@ -183,9 +173,9 @@ __global__ __launch_bounds__(1024) void l1_hist_kernel(L1Args a) {
         __syncthreads();
         for (int S = tid; S < a.ns; S += nt) a.table[(size_t)S * a.nwg + chunk] = rowcnt[S];
     }
-    coarse = block_sum_u32(coarse, sm, nt >> 6);
-    fs = block_sum_u32(fs, sm, nt >> 6);
-    fa = block_sum_u32(fa, sm, nt >> 6);
+    coarse = gs_block_sum<true>(coarse, sm, nt >> 6);
+    fs = gs_block_sum<true>(fs, sm, nt >> 6);
+    fa = gs_block_sum<true>(fa, sm, nt >> 6);
     if (tid == 0) { a.partials[chunk] = coarse; a.partials[a.nwg_all + chunk] = fs; a.partials[2 * (size_t)a.nwg_all + chunk] = fa; }
 }
 
@@ -212,7 +202,7 @@ __global__ __launch_bounds__(256) void l1_rowscan_kernel(L1Args a) {
             for (int i = tid; i < n4; i += 256) { const uint4 v = v4[i]; wk += (unsigned long long)v.x + v.y + v.z + v.w; }
             for (int i = 4 * n4 + tid; i < a.n_tile_walked; i += 256) wk += a.tile_walked[i];
         }
-#pragma unroll
+#pragma unroll      // (not two gs_wave_sum_down: the two ladders advance step by step together, one after the other they schedule differently)
         for (int d = GS_WAVE / 2; d > 0; d >>= 1) { t += __shfl_down(t, d); wk += __shfl_down(wk, d); }
         if (lane == 0) { wide[wv] = t; wide[4 + wv] = wk; }
         __syncthreads();

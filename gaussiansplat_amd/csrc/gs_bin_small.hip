@@ -56,7 +56,7 @@ __global__ __launch_bounds__(BL_NT) void bin_small_kernel(GsBinSmallArgs a) {
         if (y0 <= ty && ty <= y1 && xb >= x0) c += xb - x0 + 1u;
         before += valid ? c : 0u;
     }
-#pragma unroll
+#pragma unroll      // (gs_wave.h's gs_wave_sum_down, kept in place: through the function, with the cast or without, this kernel's registers and schedule move)
     for (int d = GS_WAVE / 2; d > 0; d >>= 1) before += (uint32_t)__shfl_down((int)before, d);
     if (lane == 0) { cnt[q] = mine; pre[q] = before; }
     __syncthreads();
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(BL_NT) void bin_small_kernel(GsBinSmallArgs a) {
     unsigned long long wk = 0;
     if (a.host_walked && a.tile_walked)
         for (int i = tid; i < a.n_tile_walked; i += BL_NT) wk += a.tile_walked[i];
-#pragma unroll
+#pragma unroll      // (gs_wave_sum_down again, kept in place for the same reason)
     for (int d = GS_WAVE / 2; d > 0; d >>= 1) wk += __shfl_down(wk, d);
     if (lane == 0) wide[q] = wk;
     __syncthreads();

@@ -35,6 +35,7 @@
 // Both kernels are VALU bound, not HBM bound; see DESIGN.md section 5 for the roofline accounting and the measured
 // instruction costs that shaped the inner loops.
 #include "gs_common.h"
+#include "gs_wave.h"
 
 // Only the fmaf() calls written below fuse: with the compiler free to contract, T - alpha*T came out as one fma in one
 // template instantiation and as mul + sub in another, so "cull on" and "cull off" differed in the last bit of T.
@@ -1272,21 +1273,15 @@ __global__ __launch_bounds__(1024) void sum_tiles_kernel(const uint32_t *__restr
     __shared__ unsigned long long sm[2][16];
     unsigned long long sa = 0, sb = 0;
     for (int i = threadIdx.x; i < n; i += 1024) { if (a) sa += a[i]; if (b) sb += b[i]; }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { sa += __shfl_down(sa, d); sb += __shfl_down(sb, d); }
-    if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = sa; sm[1][threadIdx.x >> 6] = sb; }
-    __syncthreads();
-    if (threadIdx.x < 2) { unsigned long long t = 0; for (int k = 0; k < 16; ++k) t += sm[threadIdx.x][k]; out[threadIdx.x] = t; }
+    sa = gs_block_sum(sa, sm[0], 16); sb = gs_block_sum(sb, sm[1], 16);
+    if (threadIdx.x == 0) { out[0] = sa; out[1] = sb; }
 }
 __global__ __launch_bounds__(1024) void sum_listed_kernel(const uint2 *__restrict__ ext, int n, unsigned long long *__restrict__ out) {
     __shared__ unsigned long long sm[16];
     unsigned long long sa = 0;
     for (int i = threadIdx.x; i < n; i += 1024) sa += ext[i].x;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sa += __shfl_down(sa, d);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = sa;
-    __syncthreads();
-    if (threadIdx.x == 0) { unsigned long long t = 0; for (int k = 0; k < 16; ++k) t += sm[k]; out[0] = t; }
+    sa = gs_block_sum(sa, sm, 16);
+    if (threadIdx.x == 0) out[0] = sa;
 }
 hipError_t gs_launch_sum_listed(const uint2 *ext, int n, unsigned long long *out, hipStream_t s) {
     hipLaunchKernelGGL(sum_listed_kernel, dim3(1), dim3(1024), 0, s, ext, n, out);

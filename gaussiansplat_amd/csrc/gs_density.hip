@@ -22,6 +22,7 @@
 // sqrtf is the correctly rounded form (hipcc's default, see gs_adam.h).  Random numbers are an input: the kernels are pure functions.
 #include "gs_density.h"
 #include "gs_pergaussian.h"
+#include "gs_wave.h"
 #include <stddef.h>
 
 #pragma clang fp contract(off)
@@ -80,10 +81,10 @@ __global__ __launch_bounds__(GS_DENSITY_CHUNK) void gs_density_class_kernel(cons
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < GS_DENSITY_CLASSES; ++k) {
-        const unsigned long long bal = __ballot(cls[k]);
-        if (lane == 0) wave_cnt[k][wv] = __popcll(bal);
+        const GsWaveRank r = gs_wave_rank(cls[k], lane);
+        if (lane == 0) wave_cnt[k][wv] = r.count;
     }
-    const unsigned long long bad = __ballot(in && (act < 0 || act > 3));
+    const unsigned long long bad = gs_wave_rank(in && (act < 0 || act > 3), lane).ballot;
     if (lane == 0 && bad) atomicOr(reinterpret_cast<unsigned long long *>(totals + 3), 1ull);
     __syncthreads();
     if (threadIdx.x < GS_DENSITY_CLASSES) {
@@ -118,9 +119,9 @@ __global__ __launch_bounds__(GS_DENSITY_CHUNK) void gs_density_restructure_kerne
     int rank[GS_DENSITY_CLASSES];
 #pragma unroll
     for (int k = 0; k < GS_DENSITY_CLASSES; ++k) {
-        const unsigned long long bal = __ballot(cls[k]);
-        rank[k] = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[k][wv] = __popcll(bal);
+        const GsWaveRank r = gs_wave_rank(cls[k], lane);
+        rank[k] = r.below;
+        if (lane == 0) wave_cnt[k][wv] = r.count;
     }
     __syncthreads();
     int64_t idx[GS_DENSITY_CLASSES];                                       // the row's place inside its class

@@ -10,15 +10,14 @@
 //                            address is uniform, so the 12 floats come through the scalar unit once per wave and stay in registers.
 //   exposure_bwd_kernel      the same mapping: x, d and the weight in, dx out.  A lane reads its own pixels of d before it writes them, so
 //                            d_img == d_out is legal (neither is __restrict__).  WANT_DE: 12 double accumulators per lane over its four
-//                            pixels in ascending order, then ONE AFTER ANOTHER through the fixed tree of the camera gradient -- gs_wave_sum
-//                            over the wave, lane 0 of each of the four waves into LDS, (w0 + w1) + (w2 + w3) -- into one row of 12 doubles per
-//                            workgroup.  Lanes past the image add + 0.  Without WANT_DE the instantiation has no double in it.
-//   exposure_finish_kernel   one workgroup: thread i sums the rows i, i + 256, ... in that order, the same tree, one rounding to float each.
+//                            pixels in ascending order, then through gs_block_tree_row (gs_wave.h) into one row of 12 doubles per workgroup.
+//                            Lanes past the image add + 0.  Without WANT_DE the instantiation has no double in it.
+//   exposure_finish_kernel   one workgroup: gs_tree_finish_rows (gs_wave.h), one rounding to float each.
 //   exposure_adam_kernel     one wave, 12 lanes live: gs_adam_update (gs_adam.h) on a row with the scalars of one step.
 // The pixel -> lane mapping does not depend on VEC: an unaligned base changes the accesses, not a bit of dE.
 // Built with -ffp-contract=off (gaussiansplat_amd/build.py); the statements turn contraction off themselves.
 #include "gs_exposure.h"
-#include "gs_wave_sum.h"
+#include "gs_wave.h"
 
 #include <cstdint>
 #include <initializer_list>
@@ -85,7 +84,6 @@ template <bool VEC, bool HAS_W, bool WANT_DE>
 __global__ __launch_bounds__(GS_EXPOSURE_BLOCK) void exposure_bwd_kernel(const float *__restrict__ img, const float *d_out, const float *__restrict__ E,
                                                                          const float *__restrict__ weight, int px, float *d_img,
                                                                          double *__restrict__ partials) {
-    __shared__ double swave[WANT_DE ? GS_EXPOSURE_FLOATS : 1][GS_EXPOSURE_BLOCK / 64];
     const int p0 = (blockIdx.x * GS_EXPOSURE_BLOCK + threadIdx.x) * GS_EXPOSURE_QUAD;
     const int n = p0 < px ? min(GS_EXPOSURE_QUAD, px - p0) : 0;
     double acc[GS_EXPOSURE_FLOATS];                          // (dead without WANT_DE)
@@ -117,42 +115,13 @@ __global__ __launch_bounds__(GS_EXPOSURE_BLOCK) void exposure_bwd_kernel(const f
         for (int r = 0; r < 3; ++r) store4<VEC>(d_img + r * (size_t)px, p0, n, o[r]);
     }
     if constexpr (WANT_DE) {
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-        for (int c = 0; c < GS_EXPOSURE_FLOATS; ++c) {
-            const double s = gs_wave_sum(acc[c]);
-            if (lane == 0) swave[c][wv] = s;
-        }
-        __syncthreads();
-        if (threadIdx.x < GS_EXPOSURE_FLOATS) {
-            const double *w4 = swave[threadIdx.x];
-            partials[(size_t)blockIdx.x * GS_EXPOSURE_FLOATS + threadIdx.x] = (w4[0] + w4[1]) + (w4[2] + w4[3]);
-        }
+        gs_block_tree_row<GS_EXPOSURE_FLOATS, GS_EXPOSURE_BLOCK / 64>([&](int c) { return acc[c]; },
+                                                                      [&](int c, double s) { partials[(size_t)blockIdx.x * GS_EXPOSURE_FLOATS + c] = s; });
     }
 }
 
 __global__ __launch_bounds__(GS_EXPOSURE_BLOCK) void exposure_finish_kernel(const double *__restrict__ partials, int rows, float *__restrict__ d_exposure) {
-    __shared__ double swave[GS_EXPOSURE_FLOATS][GS_EXPOSURE_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    static_assert(GS_EXPOSURE_FLOATS % 2 == 0, "two columns per 16-byte load");
-    double acc[GS_EXPOSURE_FLOATS];
-#pragma unroll
-    for (int c = 0; c < GS_EXPOSURE_FLOATS; ++c) acc[c] = 0.0;
-    for (int r = threadIdx.x; r < rows; r += GS_EXPOSURE_BLOCK) {
-        const double2 *row = reinterpret_cast<const double2 *>(partials + (size_t)r * GS_EXPOSURE_FLOATS);   // 96 r bytes: 16-byte aligned
-#pragma unroll
-        for (int q = 0; q < GS_EXPOSURE_FLOATS / 2; ++q) { const double2 v = row[q]; acc[2 * q] = acc[2 * q] + v.x; acc[2 * q + 1] = acc[2 * q + 1] + v.y; }
-    }
-#pragma unroll
-    for (int c = 0; c < GS_EXPOSURE_FLOATS; ++c) {
-        const double s = gs_wave_sum(acc[c]);
-        if (lane == 0) swave[c][wv] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < GS_EXPOSURE_FLOATS) {
-        const double *w4 = swave[threadIdx.x];
-        d_exposure[threadIdx.x] = (float)((w4[0] + w4[1]) + (w4[2] + w4[3]));
-    }
+    gs_tree_finish_rows<GS_EXPOSURE_FLOATS, GS_EXPOSURE_BLOCK>(partials, rows, [&](int c, double s) { d_exposure[c] = (float)s; });   // 96 r bytes: 16-byte aligned rows
 }
 
 __global__ __launch_bounds__(64) void exposure_adam_kernel(float *__restrict__ E, const float *__restrict__ dE, float *__restrict__ m_, float *__restrict__ v_,

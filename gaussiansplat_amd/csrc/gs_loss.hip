@@ -11,6 +11,7 @@
 // (pass 1 reads 8 B and writes 12 B per pixel-channel, pass 2 reads 20 B and writes 4 B; no MFMA: the window is a
 // 121-tap non-separable stencil on fp32 data whose symmetric taps are folded first).
 #include "gs_common.h"
+#include "gs_wave.h"              // gs_block_sum, gs_xcd_tile
 
 #define LW 11
 #define LP 5
@@ -39,14 +40,6 @@ struct GsLossArgs {
 // a uniform value the compiler must hold in a VGPR: a v_fmac with an SGPR source issues at 4.4 cycles per wave on gfx950, 2.3 with
 // VGPR sources only (tools/valu_ubench3.hip); left alone the kernarg weights stay in SGPRs (242 of the loop's 630 VALU instructions)
 __device__ __forceinline__ float in_vgpr(float x) { float r; asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "s"(x)); return r; }
-__device__ __forceinline__ float block_sum_256(float v, float *sm) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sm[w] = v;
-    __syncthreads();
-    return sm[0] + sm[1] + sm[2] + sm[3];
-}
 
 // halo tile of one plane: rows y0-5 .. y0+20, columns x0-5 .. x0+68, zero outside the image (loss.jl:29 pads with zeros).
 // Two steps, so that a kernel can put the fetches of ALL its planes in flight before the first LDS store waits for one of them:
@@ -95,20 +88,12 @@ __device__ __forceinline__ void fold_cols(float (&acc)[NO], const float (&F)[NF]
         acc[o] = fmaf(w[LP], F[o + LP], a);
     }
 }
-// Tile of a workgroup.  The dispatcher deals workgroups to the 8 XCDs round-robin (block b runs on XCD b % 8), each XCD with its own
-// L2; in plain grid order the eight tiles around a tile sit on eight different XCDs and every one fetches the shared halo from memory
-// itself.  Here XCD x works through the x-th eighth of the tiles in row-major order, so the tiles in flight on an XCD are neighbours
-// (stats 109 -> 105 us, grad 72 -> 68 us at 1920x1080x3).  (Persistent workgroups that fetch the next tile's halo before the stencil of
-// the current one were measured too, into registers and by LDS-DMA into a second pair of buffers: 111 / 114 us for the stats kernel
-// against 105 -- the kernel is bound by its 2700 VALU instructions per wave, not by the fetch; profiles/r04m_loss_persistent.log,
-// r04n_loss_lds_dma.log.)
+// Tile of a workgroup: gs_xcd_tile's order (gs_wave.h), id = (channel, tile row, tile column) in row-major order.
 struct LossTile { int x0, y0, c; };
 __device__ __forceinline__ bool loss_tile(const GsLossArgs &a, LossTile &t) {
     const int gx = (a.W + LTX - 1) / LTX, gy = (a.H + LTY - 1) / LTY, T = gx * gy * a.C;
-    const int chunk = (T + 7) / 8;
-    const int k = (int)(blockIdx.x >> 3);
-    const int id = (int)(blockIdx.x & 7u) * chunk + k;
-    if (k >= chunk || id >= T) return false;
+    int id;
+    if (!gs_xcd_tile(blockIdx.x, T, id)) return false;
     t.c = id / (gx * gy);
     const int r = id - t.c * (gx * gy);
     t.y0 = (r / gx) * LTY; t.x0 = (r % gx) * LTX;
@@ -213,8 +198,8 @@ __global__ __launch_bounds__(256, 3) void ssim_stats_kernel(GsLossArgs a) {
             }
         }
     }
-    const float t1 = block_sum_256(l1, sm);
-    const float t2 = block_sum_256(St, sm2);
+    const float t1 = gs_block_sum(l1, sm, 4);
+    const float t2 = gs_block_sum(St, sm2, 4);
     // 64 slots, 64 bytes apart (summed by the host): 6120 workgroups x 2 atomics on ONE pair of words drain one after the other
     if (threadIdx.x == 0) {
         double *slot = a.acc + (size_t)(blockIdx.x % GS_LOSS_SLOTS) * GS_LOSS_SLOT_STRIDE;   // (one pair of atomics per workgroup)
@@ -299,7 +284,7 @@ hipError_t gs_launch_loss(const GsLossArgs &a, hipStream_t s) {
     hipError_t e = hipMemsetAsync(a.acc, 0, sizeof(double) * GS_LOSS_SLOTS * GS_LOSS_SLOT_STRIDE, s);
     if (e != hipSuccess) return e;
     const int ntiles = ((a.W + LTX - 1) / LTX) * ((a.H + LTY - 1) / LTY) * a.C;
-    const int grid = 8 * ((ntiles + 7) / 8);                                  // loss_tile: an eighth of the tiles per XCD
+    const int grid = 8 * ((ntiles + 7) / 8);                                  // gs_xcd_tile: an eighth of the tiles per XCD
     hipLaunchKernelGGL(ssim_stats_kernel, dim3(grid), dim3(256), 0, s, a);
     hipLaunchKernelGGL(ssim_grad_kernel<LOSS_GRAD_NO>, dim3(grid), dim3((LTX / LOSS_GRAD_NO) * LTY), 0, s, a);
     return hipGetLastError();

@@ -15,6 +15,7 @@
 // call: nothing to clear, nothing left from an earlier call), and a one-workgroup kernel adds the rows in a fixed order.  The result is bitwise
 // reproducible call to call and independent of what the context did before.
 #include "gs_metrics.h"
+#include "gs_wave.h"              // gs_block_sum, gs_xcd_tile
 
 #include <stdint.h>
 
@@ -58,27 +59,11 @@ __device__ __forceinline__ void metric_halo_store(float (*dst)[MPITCH], const fl
         if (i < MHY * MPITCH) d[i] = v[k];
     }
 }
-__device__ __forceinline__ double metric_wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-    return v;
-}
-// the sum of a value over the 256 threads, in a fixed order (valid in thread 0)
-__device__ __forceinline__ double metric_block_sum(double v, double *sm) {
-    v = metric_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sm[0] + sm[1]) + sm[2]) + sm[3];
-}
-
-// The tile of a workgroup: block b runs on XCD b % 8, so XCD x works through the x-th eighth of the tiles in row-major order and the tiles in
-// flight on an XCD are neighbours that share their halos in its L2 (gs_loss.hip's loss_tile).  id: the tile's row of the partials.
+// The tile of a workgroup: gs_xcd_tile's order (gs_wave.h), so that the tiles in flight on an XCD are neighbours that share their halos in its
+// L2.  id: the tile's row of the partials, (channel, tile row, tile column) in row-major order.
 __device__ __forceinline__ bool metric_tile(const GsMetricArgs &a, int &x0, int &y0, int &c, int &id) {
     const int gx = (a.W + MTX - 1) / MTX, gy = (a.H + MTY - 1) / MTY, T = gx * gy * a.C;
-    const int chunk = (T + 7) / 8;
-    const int k = (int)(blockIdx.x >> 3);
-    id = (int)(blockIdx.x & 7u) * chunk + k;
-    if (k >= chunk || id >= T) return false;
+    if (!gs_xcd_tile(blockIdx.x, T, id)) return false;
     c = id / (gx * gy);
     const int r = id - c * (gx * gy);
     y0 = (r / gx) * MTY; x0 = (r % gx) * MTX;
@@ -183,10 +168,10 @@ __global__ __launch_bounds__(MNT, 3) void metrics_tile_kernel(GsMetricArgs a) {
             if (a.map) a.map[cb + (size_t)py * a.W + px] = (float)S;        // one rounding from the double value
         }
     }
-    const double t0 = metric_block_sum(s_se, red[0]);
-    const double t1 = metric_block_sum(s_ae, red[1]);
-    const double t2 = metric_block_sum(s_ss, red[2]);
-    const double t3 = metric_block_sum(s_w, red[3]);
+    const double t0 = gs_block_sum(s_se, red[0], 4);
+    const double t1 = gs_block_sum(s_ae, red[1], 4);
+    const double t2 = gs_block_sum(s_ss, red[2], 4);
+    const double t3 = gs_block_sum(s_w, red[3], 4);
     if (threadIdx.x == 0) {
         double *row = a.partials + (size_t)id * GS_METRIC_NSUMS;
         row[0] = t0; row[1] = t1; row[2] = t2; row[3] = t3;
@@ -194,7 +179,7 @@ __global__ __launch_bounds__(MNT, 3) void metrics_tile_kernel(GsMetricArgs a) {
 }
 
 // one workgroup: thread t adds the rows t, t + 256, ... in ascending order (four rows' loads in flight at a time; a row past the end counts as
-// four +0), then the fixed tree of metric_block_sum
+// four +0), then gs_block_sum (gs_wave.h)
 __global__ __launch_bounds__(MNT) void metrics_finish_kernel(const double *__restrict__ partials, int tiles, double *__restrict__ sums) {
     __shared__ double red[GS_METRIC_NSUMS][4];
     static_assert(GS_METRIC_NSUMS == 4, "a row is two double2");
@@ -213,7 +198,7 @@ __global__ __launch_bounds__(MNT) void metrics_finish_kernel(const double *__res
     }
 #pragma unroll
     for (int k = 0; k < GS_METRIC_NSUMS; ++k) {
-        const double t = metric_block_sum(s[k], red[k]);
+        const double t = gs_block_sum(s[k], red[k], 4);
         if (threadIdx.x == 0) sums[k] = t;
     }
 }
@@ -226,7 +211,7 @@ hipError_t gs_launch_metrics(const float *img, const float *gt, const float *wei
     a.W = W; a.H = H; a.C = C; a.img = img; a.gt = gt; a.weight = weight; a.map = ssim_map; a.partials = partials;
     gs_metric_window(a.g);
     const int tiles = gs_metric_tiles(W, H, C);
-    const int grid = 8 * ((tiles + 7) / 8);                                   // metric_tile: an eighth of the tiles per XCD
+    const int grid = 8 * ((tiles + 7) / 8);                                   // gs_xcd_tile: an eighth of the tiles per XCD
     hipLaunchKernelGGL(metrics_tile_kernel, dim3(grid), dim3(MNT), 0, s, a);
     hipLaunchKernelGGL(metrics_finish_kernel, dim3(1), dim3(MNT), 0, s, partials, tiles, sums);
     return hipGetLastError();

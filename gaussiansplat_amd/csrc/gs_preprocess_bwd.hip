@@ -25,6 +25,7 @@
 // the reset needs no 4(11+3K)-byte/gaussian zero fill and this pass no read of the old gradients.
 #include "gs_pergaussian.h"  // quatToRot and the sigmoid as the forward has them, the row of 2-D gradient sums (gs_g2d_row_load)
 #include "gs_sh.h"            // SH_C0 / SH_C1 / bC2 / bC3, gs_sh_dispatch, the strided rows
+#include "gs_wave.h"
 #include <stdlib.h>
 
 #ifndef GS_NT_STORES
@@ -181,13 +182,13 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
         if constexpr (ADAM == 2) {
             const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
             const bool l = threadIdx.x < nb && srow_live[threadIdx.x];
-            const unsigned long long b = __ballot(l);
-            if (lane == 0) swave_live[wv] = __popcll(b);
+            const GsWaveRank r = gs_wave_rank(l, lane);
+            if (lane == 0) swave_live[wv] = r.count;
             __syncthreads();
             int off = 0;
             nrow = 0;
             for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { off += w < wv ? swave_live[w] : 0; nrow += swave_live[w]; }
-            if (l) srow_order[off + __popcll(b & ((1ull << lane) - 1ull))] = threadIdx.x;
+            if (l) srow_order[off + r.below] = threadIdx.x;
             __syncthreads();
         }
         if (vec) {

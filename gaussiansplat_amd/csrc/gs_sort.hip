@@ -102,6 +102,7 @@ __global__ __launch_bounds__(NT) void rs_hist_kernel(const uint64_t *__restrict_
 // One workgroup per digit: exclusive scan of its row of per-block counts, offset by the total
 // of all smaller digits (each workgroup re-reduces the rows below it -- nblocks*256 dwords from
 // L2, negligible next to the key traffic).
+// (gs_wave.h's gs_block_sum<true> in its own words, kept: with the shared ladder, or with blockDim.x as an argument, its four kernels schedule differently)
 __device__ uint32_t block_reduce_u32(uint32_t v, uint32_t *sm) {
 #pragma unroll
     for (int d = GS_WAVE / 2; d > 0; d >>= 1) v += __shfl_down(v, d);
@@ -551,7 +552,7 @@ __global__ __launch_bounds__(1024) void scan_block_sums_kernel(uint32_t *__restr
         if (threadIdx.x == 1023) carry = c + pre + v;
         __syncthreads();
     }
-#pragma unroll
+#pragma unroll      // (gs_wave.h's gs_wave_sum_down, kept in place: through the function the kernel's 64-bit adds come out in another order)
     for (int d = GS_WAVE / 2; d > 0; d >>= 1) t64 += __shfl_down(t64, d);
     if (lane == 0) wide[w] = t64;
     __syncthreads();

@@ -24,6 +24,7 @@
 // rank >= rows_cap (a corrupt or truncated gather) reads as a zero row.
 #include "gs_pergaussian.h"   // gs_g2d_rgb_load; gs_sh_views_body.inc keeps its own t and p (this unit contracts, and both kernels share that body)
 #include "gs_sh.h"
+#include "gs_wave.h"
 
 static_assert(GS_TOUCHED_CHUNK == 256, "one workgroup of 256 threads (four ballots, eight bitmap words) per chunk");
 #define GS_TOUCHED_WORDS (GS_TOUCHED_CHUNK / 32)
@@ -74,12 +75,13 @@ __global__ __launch_bounds__(GS_TOUCHED_CHUNK) void gs_touched_mark_kernel(GsCol
         load_row<SRC>(src, g, a, b, c);
         t = touched3(a, b, c);
     }
-    const unsigned long long bal = __ballot(t);                            // wave64: two words, low lanes first
+    const GsWaveRank r = gs_wave_rank(t, threadIdx.x & 63);               // (the vote in front of lane and wv, as it stood: the kernel's schedule follows the order)
+    const unsigned long long bal = r.ballot;                               // wave64: two words, low lanes first
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t wi = (int64_t)blockIdx.x * GS_TOUCHED_WORDS + 2 * wv;
     if (lane == 0 && wi < words) bits[wi] = (int32_t)(uint32_t)bal;
     if (lane == 32 && wi + 1 < words) bits[wi + 1] = (int32_t)(uint32_t)(bal >> 32);
-    if (lane == 0) wave_cnt[wv] = __popcll(bal);
+    if (lane == 0) wave_cnt[wv] = r.count;
     __syncthreads();
     if (threadIdx.x == 0) {
         int s = 0;

@@ -14,10 +14,25 @@ Per frame: image, T, the five gradient arrays, tile ranges, sorted ids, sortIdxs
 bin_path_of_frame, list_stats, work_counters_ex; and the counting words of the composite kernels' debug record on one small frame.
 The per-gaussian kernels beyond a frame: a density cycle (statistics, actions, plan, the restructured model and one moment set), the
 touched-rows pack of two views and the SH gradients rebuilt from them, one fused backward + Adam step dense and selective (parameters
-and moments), and a frame at active SH degree 1 of a stored degree 3."""
+and moments), and a frame at active SH degree 1 of a stored degree 3.
+The stages around a frame whose reductions run through csrc/gs_wave.h, each at the smallest shape that reaches every path: the loss and
+the metrics on a 67 x 35 x 3 pair (two tile columns, three tile rows, ragged both ways: more tiles than XCDs, some XCD chunks short), the
+camera gradient of a 64 x 48 frame at n = 300 and n = 257 (two partial rows; the second workgroup's last wave partly past n / one
+thread), the exposure backward at 129 x 33 (five partial rows, scalar tail, 4-byte accesses) and 64 x 16 (one row, 16-byte accesses),
+with and without a weight.  The loss VALUE alone is no bit-for-bit quantity (double atomics over 64 slots: its last bits depend on the
+dispatch order): its key ends in REL_KEY and is compared to a relative 2^-40."""
 import csv, glob, hashlib, os, subprocess, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+REL_KEY, REL = "~rel_2^-40", 2.0 ** -40
+
+
+def same(k, x, y):
+    if k.endswith(REL_KEY):
+        return x.shape == y.shape and bool(np.all(np.abs(x - y) <= REL * np.maximum(np.abs(x), np.abs(y))))
+    return np.array_equal(x, y)
 
 
 def keep(a):
@@ -323,6 +338,66 @@ def case_active_degree(R):
     ctx.close()
 
 
+def image_pair(W, H, Cn, seed):
+    """a smooth image and a noisy copy of it in [0, 1], and a weight in [0, 1] with zeros in it"""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:H, 0:W].astype(np.float32)
+    gt = np.stack([0.5 + 0.4 * np.sin(0.11 * (c + 1) * x + 0.07 * y) for c in range(Cn)]).astype(np.float32)
+    img = np.clip(gt + 0.1 * rng.standard_normal(gt.shape).astype(np.float32), 0.0, 1.0)
+    w = rng.random((H, W), dtype=np.float32)
+    w[w < 0.2] = 0.0
+    return img, gt, w
+
+
+def case_loss_metrics(R):
+    from gaussiansplat_amd import backend as B
+    W, H, Cn = 67, 35, 3
+    img, gt, w = image_pair(W, H, Cn, 531)
+    ctx = B.Context(deterministic=True)
+    loss, dC = ctx.loss_host(img, gt)
+    assert np.isfinite(loss) and loss > 0 and dC.any(), "loss: nothing computed"
+    R.put("loss/value" + REL_KEY, np.float64(loss)); R.put("loss/dC", dC)
+    for tag, weight in (("metrics", None), ("metrics_weight", w)):
+        sums, smap = ctx.image_metrics_host(img, gt, weight, want_map=True)
+        assert np.isfinite(sums).all() and sums[3] > 0, "metrics: nothing computed"
+        R.put(tag + "/sums", sums); R.put(tag + "/ssim_map", smap)
+    ctx.close()
+
+
+def case_camera_grad(R):
+    from gaussiansplat_amd import backend as B, synthetic
+    W, H, deg = 64, 48, 1
+    for n in (300, 257):
+        sc = synthetic.make_scene(n, W, H, deg, seed=541)
+        ctx = B.Context(deterministic=True)
+        set_model(ctx, sc, n, deg)
+        set_cam(ctx, W, H, 0)
+        ctx.preprocess(); ctx.bin(); ctx.forward_host()
+        ctx.backward(synthetic.make_dC(W, H, 542), ctx.grads_alloc(), overwrite=True)
+        got = ctx.backward_camera()
+        assert np.isfinite(got).all() and got.any(), "camera gradient: nothing computed"
+        R.put("camera_grad_n%d/d_camera" % n, got)
+        ctx.close()
+
+
+def case_exposure(R):
+    import torch
+    from gaussiansplat_amd import backend as B
+    ctx = B.Context(deterministic=True)
+    E = torch.tensor([1.1, 0.05, -0.02, 0.01, 0.03, 0.9, 0.04, -0.02, -0.01, 0.02, 1.05, 0.03], device="cuda")
+    for W, H in ((129, 33), (64, 16)):
+        img, d_out, w = image_pair(W, H, 3, 551 + W)
+        img_t, d_t, w_t = (torch.as_tensor(a).cuda() for a in (img, d_out - 0.5, w))
+        for tag, wp in (("", 0), ("_weight", w_t.data_ptr())):
+            d_img, dE = torch.full_like(img_t, 7.0), torch.full((12,), 7.0, device="cuda")
+            torch.cuda.synchronize()
+            ctx.exposure_backward(img_t.data_ptr(), d_t.data_ptr(), E.data_ptr(), wp, W, H, d_img.data_ptr(), dE.data_ptr())
+            ctx.synchronize()
+            assert bool(torch.isfinite(dE).all()) and bool((dE != 7.0).all()), "exposure: d_exposure not written"
+            R.put("exposure_%dx%d%s/d_img" % (W, H, tag), d_img.cpu().numpy()); R.put("exposure_%dx%d%s/d_exposure" % (W, H, tag), dE.cpu().numpy())
+    ctx.close()
+
+
 def record(path):
     from gaussiansplat_amd import backend as B
     R = Recorder()
@@ -353,6 +428,9 @@ def record(path):
     case_touched(R)
     case_adam(R)
     case_active_degree(R)
+    case_loss_metrics(R)
+    case_camera_grad(R)
+    case_exposure(R)
     np.savez(path, **R.out)
     print("recorded %d arrays -> %s" % (len(R.out), path))
 
@@ -363,7 +441,7 @@ def compare(pa, pb):
     for k in sorted(set(a.files) | set(b.files)):
         c = cases.setdefault(k.split("/")[0].split(".")[0].split("!")[0], dict(n=0, bad=[], refused=set()))
         c["n"] += 1
-        if k not in a.files or k not in b.files or not np.array_equal(a[k], b[k]):
+        if k not in a.files or k not in b.files or not same(k, a[k], b[k]):
             c["bad"].append(k)
         elif "!refused" in k:
             c["refused"].add(bytes(a[k]).decode()[:60])
