@@ -12,17 +12,18 @@
 // the partial derivatives with respect to T, P, eye, lookAt, fx, fy taken as INDEPENDENT inputs (the fourth row of T is zero in the
 // reference's cameras; its gradient row is still the formal one).
 //
-// The whole chain is fp64 from the fp32 inputs, as gs_geom_bwd_body.inc has it: the same forward recompute, gs_quat_to_rot,
-// gs_sigmoid_logit<double>, gs_g2d_to_grads<double>.  The colour -> direction path is fp64 here as well (gs_sh_bwd_kernel has it in fp32):
-// the derivative polynomials of the basis as they stand there, on the constants of gs_sh.h widened to double.  The basis VALUES
-// (gs_sh_basis.inc) enter d_shs only and are not needed.  Contraction is off in the body, so the host build and the kernel round alike.
+// The whole chain is fp64 from the fp32 inputs, and it is the backward's own text: gs_geom_chain_cov.inc (J .. dJ) and gs_geom_chain_tail.inc
+// (J(t), mu(p), p = P t), which gs_geom_bwd_body.inc includes as well.  The colour -> direction path is fp64 here (gs_sh_bwd_kernel has it in
+// fp32): the derivative polynomials of the basis are one text too, gs_sh_ddir.inc, included here with double and with the coefficient lists of
+// gs_sh.h widened.  The basis VALUES (gs_sh_basis.inc) enter d_shs only and are not needed.  Contraction is off in the body, so the host
+// build and the kernel round alike.
 //
 // The `live` rule of gs_geom_bwd_body.inc: a gaussian whose ten row words are all zero (no pixel touched it, or the forward skipped it) has
 // a colour path of zero too; it contributes exactly + 0 in all 40 places and NONE of its model rows is read -- its recomputed chain may be
 // Inf or NaN (tz == 0, exp overflow, singular covariance) and must not reach a sum.
 #pragma once
 #include "gs_pergaussian.h"
-#include "gs_sh.h"             // SH_C1; the values of bC2 / bC3
+#include "gs_sh.h"             // SH_C1, GS_SH_C2_VALUES / GS_SH_C3_VALUES
 
 #define GS_CAMERA_GRAD_VALUES 40          // == GS_CAMERA_GRAD_FLOATS of include/gsplat.h
 
@@ -55,7 +56,7 @@ GS_PG void gs_camera_grad_factors(const float (&g2f)[10], const float *mean, con
         return;
     }
     const float *T = cam.T, *P = cam.P;
-    // ---- forward recompute in fp64 (gs_geom_bwd_body.inc)
+    // ---- forward recompute in fp64: t and p are text in every caller (gs_pergaussian.h says why)
     const double m1 = mean[0], m2 = mean[1], m3 = mean[2];
     double t[4], p[4];
 #pragma unroll
@@ -77,106 +78,21 @@ GS_PG void gs_camera_grad_factors(const float (&g2f)[10], const float *mean, con
         double cs[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) cs[k] = g2[0] * (double)sh[3 * k] + g2[1] * (double)sh[3 * k + 1] + g2[2] * (double)sh[3 * k + 2];
-        // the constants of gs_sh.h (bC2, bC3 are device arrays there, not usable in a constant expression: the same float literals, widened;
-        // tests/test_camera_grad_host.py compares the two texts)
-        constexpr double C1 = (double)SH_C1;
-        constexpr double c2[5] = {(double)1.0925484305920792f, (double)-1.0925484305920792f, (double)0.31539156525252005f,
-                                  (double)-1.0925484305920792f, (double)0.5462742152960396f};
-        constexpr double c3[7] = {(double)-0.5900435899266435f, (double)2.890611442640554f, (double)-0.4570457994644658f, (double)0.3731763325901154f,
-                                  (double)-0.4570457994644658f, (double)1.445305721320277f, (double)-0.5900435899266435f};
+        // the derivative polynomials of gs_sh_bwd_kernel in double: bC2, bC3 are device arrays in gs_sh.h, not usable in a constant expression or
+        // on the host -- here the two names are the same literals, widened
+        constexpr double bC2[5] = {GS_SH_C2_VALUES}, bC3[7] = {GS_SH_C3_VALUES};
         double ddir[3] = {0.0, 0.0, 0.0};
-        ddir[0] += -C1 * cs[3]; ddir[1] += -C1 * cs[1]; ddir[2] += C1 * cs[2];
-        if constexpr (DEG >= 2) {
-            ddir[0] += c2[0] * Y * cs[4] - 2 * c2[2] * X * cs[6] + c2[3] * Z * cs[7] + 2 * c2[4] * X * cs[8];
-            ddir[1] += c2[0] * X * cs[4] + c2[1] * Z * cs[5] - 2 * c2[2] * Y * cs[6] - 2 * c2[4] * Y * cs[8];
-            ddir[2] += c2[1] * Y * cs[5] + 4 * c2[2] * Z * cs[6] + c2[3] * X * cs[7];
-        }
-        if constexpr (DEG >= 3) {
-            const double xx = X * X, yy = Y * Y, zz = Z * Z, xy = X * Y, yz = Y * Z, xz = X * Z;
-            ddir[0] += 6 * c3[0] * xy * cs[9] + c3[1] * yz * cs[10] - 2 * c3[2] * xy * cs[11] - 6 * c3[3] * xz * cs[12]
-                       + c3[4] * (4 * zz - 3 * xx - yy) * cs[13] + 2 * c3[5] * xz * cs[14] + c3[6] * (3 * xx - 3 * yy) * cs[15];
-            ddir[1] += c3[0] * (3 * xx - 3 * yy) * cs[9] + c3[1] * xz * cs[10] + c3[2] * (4 * zz - xx - 3 * yy) * cs[11]
-                       - 6 * c3[3] * yz * cs[12] - 2 * c3[4] * xy * cs[13] - 2 * c3[5] * yz * cs[14] - 6 * c3[6] * xy * cs[15];
-            ddir[2] += c3[1] * xy * cs[10] + 8 * c3[2] * yz * cs[11] + c3[3] * (6 * zz - 3 * xx - 3 * yy) * cs[12]
-                       + 8 * c3[4] * xz * cs[13] + c3[5] * (xx - yy) * cs[14];
-        }
+#define GS_SH_DDIR_T double
+#include "gs_sh_ddir.inc"
+#undef GS_SH_DDIR_T
         const double dd = X * ddir[0] + Y * ddir[1] + Z * ddir[2];
         dpc[0] = (ddir[0] - X * dd) * inrm; dpc[1] = (ddir[1] - Y * dd) * inrm; dpc[2] = (ddir[2] - Z * dd) * inrm;
     }
 
-    // ---- J, R, Sigma, cov, M (gs_geom_bwd_body.inc, statement for statement)
-    double dp[4] = {dpc[0], dpc[1], dpc[2], 0.0};
-    const double tx = t[0], ty = t[1], tz = t[2], fx = cam.fx, fy = cam.fy;
-    const double itz = 1.0 / tz, itz2 = itz * itz;
-    const double J[2][3] = {{fx * itz, 0.0, -fx * tx * itz2}, {0.0, fy * itz, -fy * ty * itz2}};
-    double R[3][3];
-    gs_quat_to_rot((double)quat[0], (double)quat[1], (double)quat[2], (double)quat[3], R);
-    const double e[3] = {exp((double)scale[0]), exp((double)scale[1]), exp((double)scale[2])};
-    double Wm[3][3], Sg[3][3], A[2][3], ASg[2][3], cov[2][2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Wm[i][j] = R[i][j] * e[j];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Sg[i][j] = Wm[i][0] * Wm[j][0] + Wm[i][1] * Wm[j][1] + Wm[i][2] * Wm[j][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) A[i][j] = J[i][0] * R[0][j] + J[i][1] * R[1][j] + J[i][2] * R[2][j];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) ASg[i][j] = A[i][0] * Sg[0][j] + A[i][1] * Sg[1][j] + A[i][2] * Sg[2][j];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cov[i][j] = ASg[i][0] * A[j][0] + ASg[i][1] * A[j][1] + ASg[i][2] * A[j][2] + 0.3;
-    const double idet = 1.0 / (cov[0][0] * cov[1][1] - cov[0][1] * cov[1][0]);
-    const double M[2][2] = {{cov[1][1] * idet, -cov[0][1] * idet}, {-cov[1][0] * idet, cov[0][0] * idet}};
-    const double sg = gs_sigmoid_logit<double>(opac[0]);
-    gs_g2d_to_grads(g2, sg, M[0][0], 0.5 * (M[0][1] + M[1][0]), M[1][1]);
-    const double gmx = g2[4], gmy = g2[5];
-    const double G[2][2] = {{g2[6], g2[7]}, {g2[8], g2[9]}};           // G[r][c] = dL/dM[r][c]
-    // ---- M = cov^-1  =>  dcov = -M^T G M^T ;  cov = A Sg A^T (+0.3): dA = (dcov + dcov^T) A Sg ;  A = J R: dJ = dA R^T
-    double t1[2][2], dcov[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) t1[i][j] = M[0][i] * G[0][j] + M[1][i] * G[1][j];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) dcov[i][j] = -(t1[i][0] * M[j][0] + t1[i][1] * M[j][1]);
-    const double off = dcov[0][1] + dcov[1][0];
-    const double ds2[2][2] = {{2 * dcov[0][0], off}, {off, 2 * dcov[1][1]}};
-    double dA[2][3], dJ[2][3];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) dA[i][j] = ds2[i][0] * ASg[0][j] + ds2[i][1] * ASg[1][j];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) dJ[i][j] = dA[i][0] * R[j][0] + dA[i][1] * R[j][1] + dA[i][2] * R[j][2];
-    // ---- J(t)
-    double dt[4] = {0.0, 0.0, 0.0, 0.0};
-    const double itz3 = itz2 * itz;
-    dt[0] += dJ[0][2] * (-fx * itz2);
-    dt[1] += dJ[1][2] * (-fy * itz2);
-    dt[2] += dJ[0][0] * (-fx * itz2) + dJ[1][1] * (-fy * itz2) + dJ[0][2] * (2 * fx * tx * itz3) + dJ[1][2] * (2 * fy * ty * itz3);
-    // ---- mu(p): mu = (W p0/p3 + 1)/2 + W/2
-    const double ip3 = 1.0 / p[3];
-    const double Wd = (double)cam.W, Hd = (double)cam.H;
-    dp[0] += gmx * 0.5 * Wd * ip3;
-    dp[1] += gmy * 0.5 * Hd * ip3;
-    dp[3] += -(gmx * 0.5 * Wd * p[0] + gmy * 0.5 * Hd * p[1]) * ip3 * ip3;
-    // ---- p = P t
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dt[j] += P[i + 4 * j] * dp[i];
+    // ---- J, R, Sigma, cov, M, dcov, dA, dJ; then J(t), mu(p), p = P t: the backward's own text
+    double dt[4] = {0.0, 0.0, 0.0, 0.0}, dp[4] = {dpc[0], dpc[1], dpc[2], 0.0};
+#include "gs_geom_chain_cov.inc"
+#include "gs_geom_chain_tail.inc"
 
     // ---- the factors of the 40 values
 #pragma unroll

@@ -3,6 +3,8 @@
 // registers).  Expects: a (GsPreprocessBwdArgs), cam (GsCamera), g, g2f (float[10], the gaussian's row of 2-D gradients), OVERWRITE,
 // and the macro GS_GEOM_DPC (a float4 expression); with GS_GEOM_ADAM defined (gs_sh_bwd_kernel) also ADAM, ad (GsAdamFused), sh (the
 // thread's row of SH gradients in the LDS tile), K and srow_live -- ADAM != 0 steps p, m, v with the gradients instead of storing them.
+// What the camera gradient computes as well -- J .. dJ, and J(t), mu(p), p = P t -- is not here but in gs_geom_chain_cov.inc and
+// gs_geom_chain_tail.inc, which gs_camera_grad.h includes too; this file keeps the touched / live tests, dSg, dR, de, the quaternion and the tails.
 // Text, not a function: as a __forceinline__ function the same statements took 186 VGPRs instead of 148 (two waves per SIMD instead of three).  Contraction is off: which products the compiler fuses into fma depends on
 // the code around them, and both kernels must produce the same bits (a backward in two steps == a backward in one, tests/test_gpu_multiview.py).
 // The eleven gradients stay written twice, for the fused Adam and for the store: formed once into one array with one sink behind it, the
@@ -35,69 +37,16 @@
 #pragma unroll
     for (int i = 0; i < 10; ++i) g2[i] = (double)g2f[i];
     double dt[4] = {0, 0, 0, 0}, dp[4] = {dpc.x, dpc.y, dpc.z, 0.0};
-    const double tx = t[0], ty = t[1], tz = t[2], fx = cam.fx, fy = cam.fy;
-    const double itz = 1.0 / tz, itz2 = itz * itz;
-    const double J[2][3] = {{fx * itz, 0.0, -fx * tx * itz2}, {0.0, fy * itz, -fy * ty * itz2}};
-    const double w = a.quats[4 * g], x = a.quats[4 * g + 1], y = a.quats[4 * g + 2], z = a.quats[4 * g + 3];
-    double R[3][3];
-    gs_quat_to_rot(w, x, y, z, R);
-    const double e[3] = {exp((double)a.scales[3 * g]), exp((double)a.scales[3 * g + 1]), exp((double)a.scales[3 * g + 2])};
-    double Wm[3][3], Sg[3][3], A[2][3], ASg[2][3], cov[2][2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Wm[i][j] = R[i][j] * e[j];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Sg[i][j] = Wm[i][0] * Wm[j][0] + Wm[i][1] * Wm[j][1] + Wm[i][2] * Wm[j][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) A[i][j] = J[i][0] * R[0][j] + J[i][1] * R[1][j] + J[i][2] * R[2][j];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) ASg[i][j] = A[i][0] * Sg[0][j] + A[i][1] * Sg[1][j] + A[i][2] * Sg[2][j];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cov[i][j] = ASg[i][0] * A[j][0] + ASg[i][1] * A[j][1] + ASg[i][2] * A[j][2] + 0.3;
-    const double idet = 1.0 / (cov[0][0] * cov[1][1] - cov[0][1] * cov[1][0]);
-    const double M[2][2] = {{cov[1][1] * idet, -cov[0][1] * idet}, {-cov[1][0] * idet, cov[0][0] * idet}};
-    const double sg = gs_sigmoid_logit<double>(a.opac[g]);
-    gs_g2d_to_grads(g2, sg, M[0][0], 0.5 * (M[0][1] + M[1][0]), M[1][1]);
-    const double gsig = g2[3], gmx = g2[4], gmy = g2[5];
-    const double G[2][2] = {{g2[6], g2[7]}, {g2[8], g2[9]}};           // G[r][c] = dL/dM[r][c]
-
-    // ---- M = cov^-1  =>  dcov = -M^T G M^T
-    double t1[2][2], dcov[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) t1[i][j] = M[0][i] * G[0][j] + M[1][i] * G[1][j];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) dcov[i][j] = -(t1[i][0] * M[j][0] + t1[i][1] * M[j][1]);
-    // ---- cov = A Sg A^T (+0.3): dA = (dcov + dcov^T) A Sg ; dSg = A^T dcov A
-    const double off = dcov[0][1] + dcov[1][0];
-    const double ds2[2][2] = {{2 * dcov[0][0], off}, {off, 2 * dcov[1][1]}};
-    double dA[2][3], dSg[3][3], dJ[2][3], dR[3][3], dWm[3][3];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) dA[i][j] = ds2[i][0] * ASg[0][j] + ds2[i][1] * ASg[1][j];
+    const float *quat = a.quats + 4 * g, *scale = a.scales + 3 * g, *opac = a.opac + g;
+#include "gs_geom_chain_cov.inc"
+    const double gsig = g2[3];
+    // ---- dSg = A^T dcov A ;  A = J R: dR = J^T dA
+    double dSg[3][3], dR[3][3], dWm[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j)
             dSg[i][j] = A[0][i] * (dcov[0][0] * A[0][j] + dcov[0][1] * A[1][j]) + A[1][i] * (dcov[1][0] * A[0][j] + dcov[1][1] * A[1][j]);
-    // ---- A = J R
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) dJ[i][j] = dA[i][0] * R[j][0] + dA[i][1] * R[j][1] + dA[i][2] * R[j][2];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -126,22 +75,8 @@
     dx += 2 * z * dR[0][2]; dz += 2 * x * dR[0][2]; dw += 2 * y * dR[0][2]; dy += 2 * w * dR[0][2];
     dy += 2 * z * dR[1][2]; dz += 2 * y * dR[1][2]; dw += -2 * x * dR[1][2]; dx += -2 * w * dR[1][2];
     dx += -4 * x * dR[2][2]; dy += -4 * y * dR[2][2];
-    // ---- J(t)
-    const double itz3 = itz2 * itz;
-    dt[0] += dJ[0][2] * (-fx * itz2);
-    dt[1] += dJ[1][2] * (-fy * itz2);
-    dt[2] += dJ[0][0] * (-fx * itz2) + dJ[1][1] * (-fy * itz2) + dJ[0][2] * (2 * fx * tx * itz3) + dJ[1][2] * (2 * fy * ty * itz3);
-    // ---- mu(p): mu = (W p0/p3 + 1)/2 + W/2
-    const double ip3 = 1.0 / p[3];
-    const double Wd = (double)cam.W, Hd = (double)cam.H;
-    dp[0] += gmx * 0.5 * Wd * ip3;
-    dp[1] += gmy * 0.5 * Hd * ip3;
-    dp[3] += -(gmx * 0.5 * Wd * p[0] + gmy * 0.5 * Hd * p[1]) * ip3 * ip3;
-    // ---- p = P t ; t = T [m;1]
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dt[j] += P[i + 4 * j] * dp[i];
+    // ---- J(t), mu(p), p = P t;  t = T [m; 1] follows where the mean's gradient is formed
+#include "gs_geom_chain_tail.inc"
 #ifdef GS_GEOM_ADAM
     if constexpr (ADAM != 0) {
         // the eleven gradients exactly as the OVERWRITE instantiation below stores them (its quaternion row is 0 + v, added to zeros)

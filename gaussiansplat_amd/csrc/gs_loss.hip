@@ -11,15 +11,10 @@
 // (pass 1 reads 8 B and writes 12 B per pixel-channel, pass 2 reads 20 B and writes 4 B; no MFMA: the window is a
 // 121-tap non-separable stencil on fp32 data whose symmetric taps are folded first).
 #include "gs_common.h"
-#include "gs_wave.h"              // gs_block_sum, gs_xcd_tile
+#include "gs_halo_tile.h"         // the 64 x 16 tile with its halo, the tile of a workgroup, the grid; gs_wave.h (gs_block_sum)
 
 #define LW 11
-#define LP 5
-#define LTX 64                    // tile: 64 x 16 outputs of one channel per workgroup, 4 consecutive pixels per thread
-#define LTY 16
-#define LHX (LTX + 2 * LP)        // 74 halo columns
-#define LHY (LTY + 2 * LP)        // 26 halo rows
-#define LPITCH 76                 // floats per LDS row (16-byte aligned rows for ds_read_b128)
+#define LP GS_HALO_PAD            // the window's half width is the tile's pad
 #define LNF 6                     // folded window rows / columns: w[j][i] = w[10-j][i] = w[j][10-i]
 
 struct GsLossArgs {
@@ -41,38 +36,10 @@ struct GsLossArgs {
 // VGPR sources only (tools/valu_ubench3.hip); left alone the kernarg weights stay in SGPRs (242 of the loop's 630 VALU instructions)
 __device__ __forceinline__ float in_vgpr(float x) { float r; asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "s"(x)); return r; }
 
-// halo tile of one plane: rows y0-5 .. y0+20, columns x0-5 .. x0+68, zero outside the image (loss.jl:29 pads with zeros).
-// Two steps, so that a kernel can put the fetches of ALL its planes in flight before the first LDS store waits for one of them:
-// as one loop (load, wait, store per element) the 8 elements per thread and plane were 16 .. 24 global-load latencies in a row
-// (round 4: ssim_stats 172 -> 145 us, ssim_grad 92 -> 68 us at 1920x1080x3).  The address is clamped instead of predicated
-// (every load is unconditional, the select happens on the value).
-template <int NT> struct HaloIt { static constexpr int n = (LHY * LPITCH + NT - 1) / NT; };     // halo elements per thread and plane
-template <int NT>
-__device__ __forceinline__ void halo_fetch(float (&v)[HaloIt<NT>::n], const float *__restrict__ plane, int W, int H, int x0, int y0) {
-    int hy = (int)threadIdx.x / LPITCH, hx = (int)threadIdx.x - hy * LPITCH;          // element i = thread + NT k: one division, then steps
-#pragma unroll
-    for (int k = 0; k < HaloIt<NT>::n; ++k) {
-        const int gx = x0 + hx - LP, gy = y0 + hy - LP;
-        const bool in = hx < LHX && gx >= 0 && gx < W && gy >= 0 && gy < H;          // (hy >= LHY: gy may still be inside; never stored)
-        const float t = plane[(uint32_t)(min(max(gy, 0), H - 1) * W + min(max(gx, 0), W - 1))];   // uniform base + 32-bit lane offset
-        v[k] = in ? t : 0.0f;
-        hx += NT % LPITCH; hy += NT / LPITCH;
-        if (hx >= LPITCH) { hx -= LPITCH; hy += 1; }
-    }
-}
-template <int NT>
-__device__ __forceinline__ void halo_store(float (*dst)[LPITCH], const float (&v)[HaloIt<NT>::n]) {
-    float *d = &dst[0][0];
-#pragma unroll
-    for (int k = 0; k < HaloIt<NT>::n; ++k) {
-        const int i = (int)threadIdx.x + NT * k;
-        if (i < LHY * LPITCH) d[i] = v[k];
-    }
-}
 // NF (a multiple of 4) consecutive samples of a halo row starting at column col0 (a multiple of 4): a thread with NO outputs needs
 // NO + 10 of them
 template <int NF>
-__device__ __forceinline__ void load_row(float (&v)[NF], const float (*src)[LPITCH], int row, int col0) {
+__device__ __forceinline__ void load_row(float (&v)[NF], const float (*src)[GS_HALO_PITCH], int row, int col0) {
     const float4 *p = reinterpret_cast<const float4 *>(&src[row][col0]);
 #pragma unroll
     for (int q = 0; q < NF / 4; ++q) { const float4 t = p[q]; v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w; }
@@ -87,17 +54,6 @@ __device__ __forceinline__ void fold_cols(float (&acc)[NO], const float (&F)[NF]
         for (int c = 0; c < LP; ++c) a = fmaf(w[c], F[o + c] + F[o + 2 * LP - c], a);
         acc[o] = fmaf(w[LP], F[o + LP], a);
     }
-}
-// Tile of a workgroup: gs_xcd_tile's order (gs_wave.h), id = (channel, tile row, tile column) in row-major order.
-struct LossTile { int x0, y0, c; };
-__device__ __forceinline__ bool loss_tile(const GsLossArgs &a, LossTile &t) {
-    const int gx = (a.W + LTX - 1) / LTX, gy = (a.H + LTY - 1) / LTY, T = gx * gy * a.C;
-    int id;
-    if (!gs_xcd_tile(blockIdx.x, T, id)) return false;
-    t.c = id / (gx * gy);
-    const int r = id - t.c * (gx * gy);
-    t.y0 = (r / gx) * LTY; t.x0 = (r % gx) * LTX;
-    return true;
 }
 // The folded window (6 x 6 weights, rows padded to 8 floats) in LDS: a row is two broadcast reads straight into VGPRs, issued with the
 // sample rows.  (From the kernarg segment a row was an s_load whose wait stood in front of every iteration's LDS reads, and its
@@ -117,14 +73,14 @@ __device__ __forceinline__ void window_row(float (&w)[LNF], const float (*swin)[
 }
 
 __global__ __launch_bounds__(256, 3) void ssim_stats_kernel(GsLossArgs a) {
-    __shared__ __attribute__((aligned(16))) float sx[LHY][LPITCH], sy[LHY][LPITCH];
+    __shared__ __attribute__((aligned(16))) float sx[GS_HALO_HY][GS_HALO_PITCH], sy[GS_HALO_HY][GS_HALO_PITCH];
     __shared__ float sm[4], sm2[4];
     __shared__ __attribute__((aligned(16))) float swin[LNF][8];
     stage_window(swin, a);
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const size_t plane = (size_t)a.W * a.H;
-    LossTile cur;
-    if (!loss_tile(a, cur)) return;
+    GsHaloTile cur;
+    if (!gs_halo_tile(a, cur)) return;
     {
         float hx_[HaloIt<256>::n], hy_[HaloIt<256>::n];
         halo_fetch<256>(hx_, a.img + cur.c * plane, a.W, a.H, cur.x0, cur.y0);
@@ -217,15 +173,15 @@ __global__ __launch_bounds__(256, 3) void ssim_stats_kernel(GsLossArgs a) {
 #define LOSS_GRAD_NO 4
 #endif
 template <int NO>
-__global__ __launch_bounds__((LTX / NO) * LTY, LOSS_GRAD_MINW) void ssim_grad_kernel(GsLossArgs a) {
-    constexpr int NT = (LTX / NO) * LTY, NF = NO + 12;
-    __shared__ __attribute__((aligned(16))) float s0[LHY][LPITCH], s1[LHY][LPITCH], s2[LHY][LPITCH];
+__global__ __launch_bounds__((GS_HALO_TX / NO) * GS_HALO_TY, LOSS_GRAD_MINW) void ssim_grad_kernel(GsLossArgs a) {
+    constexpr int NT = (GS_HALO_TX / NO) * GS_HALO_TY, NF = NO + 12;
+    __shared__ __attribute__((aligned(16))) float s0[GS_HALO_HY][GS_HALO_PITCH], s1[GS_HALO_HY][GS_HALO_PITCH], s2[GS_HALO_HY][GS_HALO_PITCH];
     __shared__ __attribute__((aligned(16))) float swin[LNF][8];
     stage_window(swin, a);
-    const int tx = threadIdx.x % (LTX / NO), ty = threadIdx.x / (LTX / NO);
+    const int tx = threadIdx.x % (GS_HALO_TX / NO), ty = threadIdx.x / (GS_HALO_TX / NO);
     const size_t plane = (size_t)a.W * a.H;
-    LossTile cur;
-    if (!loss_tile(a, cur)) return;
+    GsHaloTile cur;
+    if (!gs_halo_tile(a, cur)) return;
     const size_t cb = cur.c * plane;
     const int py = cur.y0 + ty;
     float xq[NO], yq[NO];                                                     // the outputs' own samples: fetched with the halos, used last
@@ -283,10 +239,9 @@ __global__ __launch_bounds__((LTX / NO) * LTY, LOSS_GRAD_MINW) void ssim_grad_ke
 hipError_t gs_launch_loss(const GsLossArgs &a, hipStream_t s) {
     hipError_t e = hipMemsetAsync(a.acc, 0, sizeof(double) * GS_LOSS_SLOTS * GS_LOSS_SLOT_STRIDE, s);
     if (e != hipSuccess) return e;
-    const int ntiles = ((a.W + LTX - 1) / LTX) * ((a.H + LTY - 1) / LTY) * a.C;
-    const int grid = 8 * ((ntiles + 7) / 8);                                  // gs_xcd_tile: an eighth of the tiles per XCD
+    const int grid = gs_halo_grid(a.W, a.H, a.C).blocks;
     hipLaunchKernelGGL(ssim_stats_kernel, dim3(grid), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(ssim_grad_kernel<LOSS_GRAD_NO>, dim3(grid), dim3((LTX / LOSS_GRAD_NO) * LTY), 0, s, a);
+    hipLaunchKernelGGL(ssim_grad_kernel<LOSS_GRAD_NO>, dim3(grid), dim3((GS_HALO_TX / LOSS_GRAD_NO) * GS_HALO_TY), 0, s, a);
     return hipGetLastError();
 }
 

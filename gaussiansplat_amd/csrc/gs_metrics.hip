@@ -4,7 +4,7 @@
 //
 // One workgroup of 256 threads owns a tile of 64 x 16 outputs of one channel:
 //   1. the halo of both images (26 rows x 74 columns, zero outside the image) goes to LDS as float32, every load in flight before the first
-//      LDS store (the idea of gs_loss.hip's halo_fetch);
+//      LDS store (halo_fetch / halo_store of gs_halo_tile.h, the loss kernels' own);
 //   2. COLUMN pass: a thread takes one halo column and four output rows, widens its 14 sample pairs, forms the three products (exact in double)
 //      and keeps the five 11-tap sums of each row in registers; once every thread has read its samples they go to LDS as double [5][16][74],
 //      over the samples (47 KB per workgroup: three per CU).  Columns first because the tile is wide: the pass runs over 74 / 64 of the tile's
@@ -15,21 +15,16 @@
 // call: nothing to clear, nothing left from an earlier call), and a one-workgroup kernel adds the rows in a fixed order.  The result is bitwise
 // reproducible call to call and independent of what the context did before.
 #include "gs_metrics.h"
-#include "gs_wave.h"              // gs_block_sum, gs_xcd_tile
+#include "gs_halo_tile.h"         // the 64 x 16 tile with its halo, the tile of a workgroup, the grid; gs_wave.h (gs_block_sum)
 
 #include <stdint.h>
 
 #define MP GS_METRIC_PAD
 #define MW GS_METRIC_WIN
 #define MNP GS_METRIC_PLANES
-#define MTX 64                    // tile: 64 x 16 outputs of one channel per workgroup
-#define MTY 16
-#define MHX (MTX + 2 * MP)        // 74 halo columns
-#define MHY (MTY + 2 * MP)        // 26 halo rows
-#define MPITCH 76                 // floats per LDS row of samples
 #define MNT 256                   // threads
 #define MRG 4                     // output rows per thread of the column pass
-#define MHALO ((MHY * MPITCH + MNT - 1) / MNT)   // halo elements per thread and image
+static_assert(GS_HALO_PAD == GS_METRIC_PAD, "the tile's halo is the window's reach");
 
 struct GsMetricArgs {
     int W, H, C;
@@ -39,41 +34,10 @@ struct GsMetricArgs {
     double g[MW];
 };
 
-__device__ __forceinline__ void metric_halo_fetch(float (&v)[MHALO], const float *__restrict__ plane, int W, int H, int x0, int y0) {
-    int hy = (int)threadIdx.x / MPITCH, hx = (int)threadIdx.x - hy * MPITCH;
-#pragma unroll
-    for (int k = 0; k < MHALO; ++k) {
-        const int gx = x0 + hx - MP, gy = y0 + hy - MP;
-        const bool in = hx < MHX && gx >= 0 && gx < W && gy >= 0 && gy < H;
-        const float t = plane[(uint32_t)(min(max(gy, 0), H - 1) * W + min(max(gx, 0), W - 1))];   // the address is clamped, the value selected
-        v[k] = in ? t : 0.0f;
-        hx += MNT % MPITCH; hy += MNT / MPITCH;
-        if (hx >= MPITCH) { hx -= MPITCH; hy += 1; }
-    }
-}
-__device__ __forceinline__ void metric_halo_store(float (*dst)[MPITCH], const float (&v)[MHALO]) {
-    float *d = &dst[0][0];
-#pragma unroll
-    for (int k = 0; k < MHALO; ++k) {
-        const int i = (int)threadIdx.x + MNT * k;
-        if (i < MHY * MPITCH) d[i] = v[k];
-    }
-}
-// The tile of a workgroup: gs_xcd_tile's order (gs_wave.h), so that the tiles in flight on an XCD are neighbours that share their halos in its
-// L2.  id: the tile's row of the partials, (channel, tile row, tile column) in row-major order.
-__device__ __forceinline__ bool metric_tile(const GsMetricArgs &a, int &x0, int &y0, int &c, int &id) {
-    const int gx = (a.W + MTX - 1) / MTX, gy = (a.H + MTY - 1) / MTY, T = gx * gy * a.C;
-    if (!gs_xcd_tile(blockIdx.x, T, id)) return false;
-    c = id / (gx * gy);
-    const int r = id - c * (gx * gy);
-    y0 = (r / gx) * MTY; x0 = (r % gx) * MTX;
-    return true;
-}
-
 // the five 11-tap column sums of NR consecutive output rows r0 .. of halo column hx: output row r0 + o takes the halo rows r0 + o .. + 10, taps in
 // ascending order; the NR + 10 sample pairs are widened and multiplied once
 template <int NR>
-__device__ __forceinline__ void metric_column_sums(double (&acc)[NR][MNP], const float (*sx)[MPITCH], const float (*sy)[MPITCH], const double (&g)[MW], int r0, int hx) {
+__device__ __forceinline__ void metric_column_sums(double (&acc)[NR][MNP], const float (*sx)[GS_HALO_PITCH], const float (*sy)[GS_HALO_PITCH], const double (&g)[MW], int r0, int hx) {
 #pragma unroll
     for (int o = 0; o < NR; ++o)
 #pragma unroll
@@ -93,7 +57,7 @@ __device__ __forceinline__ void metric_column_sums(double (&acc)[NR][MNP], const
     }
 }
 template <int NR>
-__device__ __forceinline__ void metric_column_store(double (*sv)[MTY][MHX], const double (&acc)[NR][MNP], int r0, int hx) {
+__device__ __forceinline__ void metric_column_store(double (*sv)[GS_HALO_TY][GS_HALO_HX], const double (&acc)[NR][MNP], int r0, int hx) {
 #pragma unroll
     for (int o = 0; o < NR; ++o)
 #pragma unroll
@@ -102,19 +66,20 @@ __device__ __forceinline__ void metric_column_store(double (*sv)[MTY][MHX], cons
 
 // The column pass over the 74 halo columns of 16 output rows, dealt so that no wave carries twice another's work: every thread takes MRG = 4
 // rows of one of the first 64 columns (wave w: rows 4 w ..), then the threads below MEDGE take ONE row of one of the last 10 columns
-#define MEDGE ((MHX - MTX) * MTY)        // 160
-static_assert(MTX * (MTY / MRG) == MNT && MEDGE <= MNT, "the column pass is written for one wide unit per thread and at most one edge unit");
-static_assert(2 * MHY * MPITCH * sizeof(float) <= MNP * MTY * MHX * sizeof(double), "the samples fit where the column sums go");
+#define MEDGE ((GS_HALO_HX - GS_HALO_TX) * GS_HALO_TY)        // 160
+static_assert(GS_HALO_TX * (GS_HALO_TY / MRG) == MNT && MEDGE <= MNT, "the column pass is written for one wide unit per thread and at most one edge unit");
+static_assert(2 * GS_HALO_HY * GS_HALO_PITCH * sizeof(float) <= MNP * GS_HALO_TY * GS_HALO_HX * sizeof(double), "the samples fit where the column sums go");
 
 __global__ __launch_bounds__(MNT, 3) void metrics_tile_kernel(GsMetricArgs a) {
     // the column sums (double [5][16][74], 47 KB) take the place of the samples (float 2 x [26][76]) once every thread has read its samples:
     // three workgroups per CU instead of two
-    __shared__ __attribute__((aligned(16))) char smem[MNP * MTY * MHX * sizeof(double)];
+    __shared__ __attribute__((aligned(16))) char smem[MNP * GS_HALO_TY * GS_HALO_HX * sizeof(double)];
     __shared__ double red[GS_METRIC_NSUMS][4];
-    float (*sx)[MPITCH] = reinterpret_cast<float (*)[MPITCH]>(smem), (*sy)[MPITCH] = sx + MHY;
-    double (*sv)[MTY][MHX] = reinterpret_cast<double (*)[MTY][MHX]>(smem);
-    int x0, y0, c, id;
-    if (!metric_tile(a, x0, y0, c, id)) return;                               // (the whole workgroup)
+    float (*sx)[GS_HALO_PITCH] = reinterpret_cast<float (*)[GS_HALO_PITCH]>(smem), (*sy)[GS_HALO_PITCH] = sx + GS_HALO_HY;
+    double (*sv)[GS_HALO_TY][GS_HALO_HX] = reinterpret_cast<double (*)[GS_HALO_TY][GS_HALO_HX]>(smem);
+    GsHaloTile tile;
+    if (!gs_halo_tile(a, tile)) return;                           // (the whole workgroup)
+    const int x0 = tile.x0, y0 = tile.y0, c = tile.c, id = tile.id;           // id: the tile's row of the partials
     const size_t cb = (size_t)c * ((size_t)a.W * a.H);
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int py = y0 + ty;
@@ -123,10 +88,10 @@ __global__ __launch_bounds__(MNT, 3) void metrics_tile_kernel(GsMetricArgs a) {
     for (int o = 0; o < 4; ++o)
         wq[o] = a.weight ? a.weight[(uint32_t)(min(py, a.H - 1) * a.W + min(x0 + 4 * tx + o, a.W - 1))] : 1.0f;
     {
-        float hx_[MHALO], hy_[MHALO];
-        metric_halo_fetch(hx_, a.img + cb, a.W, a.H, x0, y0);
-        metric_halo_fetch(hy_, a.gt + cb, a.W, a.H, x0, y0);
-        metric_halo_store(sx, hx_); metric_halo_store(sy, hy_);
+        float hx_[HaloIt<MNT>::n], hy_[HaloIt<MNT>::n];
+        halo_fetch<MNT>(hx_, a.img + cb, a.W, a.H, x0, y0);
+        halo_fetch<MNT>(hy_, a.gt + cb, a.W, a.H, x0, y0);
+        halo_store<MNT>(sx, hx_); halo_store<MNT>(sy, hy_);
     }
     double g[MW];
 #pragma unroll
@@ -135,7 +100,7 @@ __global__ __launch_bounds__(MNT, 3) void metrics_tile_kernel(GsMetricArgs a) {
     // ---- column pass, results in registers; the outputs' own samples are read before the column sums overwrite them
     const int cr0 = MRG * ((int)threadIdx.x >> 6), chx = (int)threadIdx.x & 63;
     const bool edge = (int)threadIdx.x < MEDGE;
-    const int er0 = (int)threadIdx.x / (MHX - MTX), ehx = MTX + (int)threadIdx.x - er0 * (MHX - MTX);
+    const int er0 = (int)threadIdx.x / (GS_HALO_HX - GS_HALO_TX), ehx = GS_HALO_TX + (int)threadIdx.x - er0 * (GS_HALO_HX - GS_HALO_TX);
     double acc0[MRG][MNP], acc1[1][MNP];
     metric_column_sums<MRG>(acc0, sx, sy, g, cr0, chx);
     if (edge) metric_column_sums<1>(acc1, sx, sy, g, er0, ehx);
@@ -203,16 +168,15 @@ __global__ __launch_bounds__(MNT) void metrics_finish_kernel(const double *__res
     }
 }
 
-int gs_metric_tiles(int W, int H, int C) { return ((W + MTX - 1) / MTX) * ((H + MTY - 1) / MTY) * C; }
+int gs_metric_tiles(int W, int H, int C) { return gs_halo_grid(W, H, C).tiles; }
 
 hipError_t gs_launch_metrics(const float *img, const float *gt, const float *weight, int W, int H, int C, float *ssim_map, double *partials,
                              double *sums, hipStream_t s) {
     GsMetricArgs a{};
     a.W = W; a.H = H; a.C = C; a.img = img; a.gt = gt; a.weight = weight; a.map = ssim_map; a.partials = partials;
     gs_metric_window(a.g);
-    const int tiles = gs_metric_tiles(W, H, C);
-    const int grid = 8 * ((tiles + 7) / 8);                                   // gs_xcd_tile: an eighth of the tiles per XCD
-    hipLaunchKernelGGL(metrics_tile_kernel, dim3(grid), dim3(MNT), 0, s, a);
-    hipLaunchKernelGGL(metrics_finish_kernel, dim3(1), dim3(MNT), 0, s, partials, tiles, sums);
+    const GsHaloGrid grid = gs_halo_grid(W, H, C);
+    hipLaunchKernelGGL(metrics_tile_kernel, dim3(grid.blocks), dim3(MNT), 0, s, a);
+    hipLaunchKernelGGL(metrics_finish_kernel, dim3(1), dim3(MNT), 0, s, partials, grid.tiles, sums);
     return hipGetLastError();
 }

@@ -8,7 +8,8 @@
 // Who takes what: DESIGN.md section 5.2.  Not here: t = T [m; 1], p = P t.  As a function it moved the kernels' camera loads and cost
 // registers in each of its three callers (geometry chain 148 -> 154 VGPRs, forward at degree 1 68 -> 76 SGPRs; profiles/HISTORY.md), so the
 // forward, gs_sh_bwd_kernel and gs_geom_bwd_body.inc keep those two loops as text; gs_sh_views_body.inc has its own as well (its
-// translation units contract on purpose, and both of its kernels already share that one body).
+// translation units contract on purpose, and both of its kernels already share that one body).  The fp64 chain behind t and p is text for
+// the same reason, but one text: gs_geom_chain_cov.inc and gs_geom_chain_tail.inc, for the backward and the camera gradient alike.
 #pragma once
 #include "gs_common.h"
 #include "gs_detmath.h"

@@ -138,21 +138,9 @@ __global__ __launch_bounds__(256) void gs_sh_bwd_kernel(GsPreprocessBwdArgs a, G
             float cs[K];
 #pragma unroll
             for (int k = 0; k < K; ++k) cs[k] = grgb[0] * shv[3 * k] + grgb[1] * shv[3 * k + 1] + grgb[2] * shv[3 * k + 2];
-            if constexpr (DEG >= 1) { ddir[0] += -SH_C1 * cs[3]; ddir[1] += -SH_C1 * cs[1]; ddir[2] += SH_C1 * cs[2]; }
-            if constexpr (DEG >= 2) {
-                ddir[0] += bC2[0] * Y * cs[4] - 2 * bC2[2] * X * cs[6] + bC2[3] * Z * cs[7] + 2 * bC2[4] * X * cs[8];
-                ddir[1] += bC2[0] * X * cs[4] + bC2[1] * Z * cs[5] - 2 * bC2[2] * Y * cs[6] - 2 * bC2[4] * Y * cs[8];
-                ddir[2] += bC2[1] * Y * cs[5] + 4 * bC2[2] * Z * cs[6] + bC2[3] * X * cs[7];
-            }
-            if constexpr (DEG >= 3) {
-                const float xx = X * X, yy = Y * Y, zz = Z * Z, xy = X * Y, yz = Y * Z, xz = X * Z;
-                ddir[0] += 6 * bC3[0] * xy * cs[9] + bC3[1] * yz * cs[10] - 2 * bC3[2] * xy * cs[11] - 6 * bC3[3] * xz * cs[12]
-                           + bC3[4] * (4 * zz - 3 * xx - yy) * cs[13] + 2 * bC3[5] * xz * cs[14] + bC3[6] * (3 * xx - 3 * yy) * cs[15];
-                ddir[1] += bC3[0] * (3 * xx - 3 * yy) * cs[9] + bC3[1] * xz * cs[10] + bC3[2] * (4 * zz - xx - 3 * yy) * cs[11]
-                           - 6 * bC3[3] * yz * cs[12] - 2 * bC3[4] * xy * cs[13] - 2 * bC3[5] * yz * cs[14] - 6 * bC3[6] * xy * cs[15];
-                ddir[2] += bC3[1] * xy * cs[10] + 8 * bC3[2] * yz * cs[11] + bC3[3] * (6 * zz - 3 * xx - 3 * yy) * cs[12]
-                           + 8 * bC3[4] * xz * cs[13] + bC3[5] * (xx - yy) * cs[14];
-            }
+#define GS_SH_DDIR_T float
+#include "gs_sh_ddir.inc"
+#undef GS_SH_DDIR_T
         }
         const float dd = X * ddir[0] + Y * ddir[1] + Z * ddir[2];
         // d L / d tps[1:3] through the colour (dir = normalize(tps[1:3] - (lookAt - eye)))

@@ -1,5 +1,5 @@
 // gs_sh.h -- what the kernels that evaluate spherical harmonics share: the constants, the choice of an instantiation from (active degree,
-// row stride), and the addressing of strided rows.  The basis itself is gs_sh_basis.inc (text: see there).
+// row stride), and the addressing of strided rows.  The basis itself is gs_sh_basis.inc, its derivative gs_sh_ddir.inc (text: see there).
 //
 // The coefficient arrays are `inline __constant__`: ONE definition for every translation unit of the library (no host symbol, nothing
 // registered twice) that the kernels LOAD.  Not `static __constant__`: the compiler then folds the values into the instruction stream and
@@ -12,10 +12,12 @@
 
 #define SH_C0 0.28209479177387814f
 #define SH_C1 0.48860251190291990f
-inline __constant__ float bC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                    -1.0925484305920792f, 0.5462742152960396f};
-inline __constant__ float bC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
-                                    -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
+// each list of literals stands ONCE: the device arrays below, and the constexpr doubles of gs_camera_grad.h (the same floats, widened)
+#define GS_SH_C2_VALUES 1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f, 0.5462742152960396f
+#define GS_SH_C3_VALUES -0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f, \
+                        -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f
+inline __constant__ float bC2[5] = {GS_SH_C2_VALUES};
+inline __constant__ float bC3[7] = {GS_SH_C3_VALUES};
 
 // The instantiation of an SH kernel.  active_degree: the bands evaluated, 0..3; row_stride: floats per stored row, 3 K = 3 (active_degree + 1)^2
 // or more -- more is an active degree below the stored one, hence 0..2 only (the STRIDED instantiations).  Anything else: hipErrorInvalidValue

@@ -145,18 +145,47 @@ def test_the_restatements_are_the_camera_functions(name, cam, w, h):
     assert np.abs(P - P32).max() <= 1e-6 * np.abs(P32).max() and P32[0, 0] > 0 and P32[3, 2] == 1.0
 
 
-def test_sh_constants_are_those_of_gs_sh_h():
-    """gs_camera_grad.h widens the float literals of bC2 / bC3 (device arrays in gs_sh.h, not usable in a constant expression): the same text."""
+def test_shared_device_text_is_written_once():
+    """The geometry chain, the SH direction derivative, the SH coefficient literals and the halo staging each stand in ONE file under csrc/,
+    and every user includes that file: a second copy, typed out or pasted back, fails here."""
     import re
+    text = {f: open(os.path.join(gbuild.CSRC, f)).read() for f in sorted(os.listdir(gbuild.CSRC)) if f.endswith((".h", ".inc", ".hip"))}
 
-    def literals(path, pattern):
-        m = re.search(pattern, open(path).read(), re.S)
-        assert m, (path, pattern)
-        return [x.rstrip("f") for x in re.findall(r"-?\d+\.\d+f", m.group(1))]
-    sh, cg = os.path.join(gbuild.CSRC, "gs_sh.h"), os.path.join(gbuild.CSRC, "gs_camera_grad.h")
-    for n, dev, mine in ((5, r"bC2\[5\] = \{(.*?)\}", r"c2\[5\] = \{(.*?)\}"), (7, r"bC3\[7\] = \{(.*?)\}", r"c3\[7\] = \{(.*?)\}")):
-        a, b = literals(sh, dev), literals(cg, mine)
-        assert len(a) == n and a == b, (a, b)
+    # the coefficient lists: 5 and 7 float literals, once, in gs_sh.h; the device arrays and the camera statement's doubles are made of the two macros
+    sh = text["gs_sh.h"]
+    for name, n in (("GS_SH_C2_VALUES", 5), ("GS_SH_C3_VALUES", 7)):
+        m = re.search(r"#define %s ((?:.*\\\n)*.*)\n" % name, sh)
+        assert m, name
+        lits = re.findall(r"-?\d+\.\d+f", m.group(1))
+        assert len(lits) == n, (name, lits)
+        for digits in {x.lstrip("-").rstrip("f") for x in lits}:
+            where = {f: t.count(digits) for f, t in text.items() if digits in t}
+            assert where == {"gs_sh.h": sum(x.lstrip("-").rstrip("f") == digits for x in lits)}, (name, digits, where)
+    assert re.search(r"bC2\[5\] = \{GS_SH_C2_VALUES\}", sh) and re.search(r"bC3\[7\] = \{GS_SH_C3_VALUES\}", sh)
+    assert re.search(r"constexpr double bC2\[5\] = \{GS_SH_C2_VALUES\}, bC3\[7\] = \{GS_SH_C3_VALUES\}", text["gs_camera_grad.h"])
+
+    # one marker statement of each shared text: in exactly one file, once (whitespace and the coefficient's name aside)
+    markers = {
+        "gs_geom_chain_cov.inc": r"idet\s*=\s*1\.0\s*/\s*\(\s*cov\[0\]\[0\]\s*\*\s*cov\[1\]\[1\]",   # the 2 x 2 inverse
+        "gs_sh_ddir.inc": r"\(\s*4\s*\*\s*zz\s*-\s*3\s*\*\s*xx\s*-\s*yy\s*\)\s*\*\s*cs\[13\]",   # a degree-3 ddir term
+        "gs_halo_tile.h": r"min\(max\(gy, 0\), H - 1\)\s*\*\s*W\s*\+\s*min\(max\(gx, 0\), W - 1\)",   # the clamped halo load
+    }
+    for home, pat in markers.items():
+        where = {f: len(re.findall(pat, t)) for f, t in text.items() if re.search(pat, t)}
+        assert where == {home: 1}, (home, where)
+
+    # every user names the file it takes the text from
+    includers = {
+        "gs_geom_chain_cov.inc": ("gs_geom_bwd_body.inc", "gs_camera_grad.h"),
+        "gs_geom_chain_tail.inc": ("gs_geom_bwd_body.inc", "gs_camera_grad.h"),
+        "gs_sh_ddir.inc": ("gs_preprocess_bwd.hip", "gs_camera_grad.h"),
+        "gs_halo_tile.h": ("gs_loss.hip", "gs_metrics.hip"),
+        "gs_geom_bwd_body.inc": ("gs_preprocess_bwd.hip",),
+    }
+    for frag, users in includers.items():
+        have = sorted(f for f, t in text.items() if '#include "%s"' % frag in t)
+        assert have == sorted(users), (frag, have)
+    assert text["gs_preprocess_bwd.hip"].count('#include "gs_geom_bwd_body.inc"') == 2      # fused in gs_sh_bwd_kernel, alone in gs_geom_bwd_kernel
 
 
 def test_camera_param_grads_sign_and_scale_by_finite_difference():

@@ -14,11 +14,13 @@ Per frame: image, T, the five gradient arrays, tile ranges, sorted ids, sortIdxs
 bin_path_of_frame, list_stats, work_counters_ex; and the counting words of the composite kernels' debug record on one small frame.
 The per-gaussian kernels beyond a frame: a density cycle (statistics, actions, plan, the restructured model and one moment set), the
 touched-rows pack of two views and the SH gradients rebuilt from them, one fused backward + Adam step dense and selective (parameters
-and moments), and a frame at active SH degree 1 of a stored degree 3.
+and moments), a frame at active SH degree 1 of a stored degree 3, and the backward's forms at n = 300 (two workgroups, the second's last wave partly past n):
+stored = active degree 0 .. 3 and active 0 of stored 3, each over two views on one set of gradient buffers (overwriting, then accumulating),
+both phases in one call and the phases apart.
 The stages around a frame whose reductions run through csrc/gs_wave.h, each at the smallest shape that reaches every path: the loss and
 the metrics on a 67 x 35 x 3 pair (two tile columns, three tile rows, ragged both ways: more tiles than XCDs, some XCD chunks short), the
-camera gradient of a 64 x 48 frame at n = 300 and n = 257 (two partial rows; the second workgroup's last wave partly past n / one
-thread), the exposure backward at 129 x 33 (five partial rows, scalar tail, 4-byte accesses) and 64 x 16 (one row, 16-byte accesses),
+camera gradient of a 64 x 48 frame at degree 1 at n = 300 and n = 257 (two partial rows; the second workgroup's last wave partly past n /
+one thread) and at degrees 0, 2, 3 at n = 300, the exposure backward at 129 x 33 (five partial rows, scalar tail, 4-byte accesses) and 64 x 16 (one row, 16-byte accesses),
 with and without a weight.  The loss VALUE alone is no bit-for-bit quantity (double atomics over 64 slots: its last bits depend on the
 dispatch order): its key ends in REL_KEY and is compared to a relative 2^-40."""
 import csv, glob, hashlib, os, subprocess, sys
@@ -338,6 +340,35 @@ def case_active_degree(R):
     ctx.close()
 
 
+def case_backward_forms(R):
+    """The per-gaussian backward's instantiations at n = 300 on a C1-sized image (two workgroups, the second's last wave partly past n): stored =
+    active degree 0 .. 3 and active 0 of stored 3 (strided); per degree two views on ONE set of gradient buffers, the first overwriting, the
+    second accumulating -- both phases in one call (the fused kernels), and the phases apart (gs_sh_bwd_kernel alone, then gs_geom_bwd_kernel)"""
+    from gaussiansplat_amd import backend as B, synthetic
+    n, W, H = 300, 256, 256
+    for stored, active in ((0, 0), (1, 1), (2, 2), (3, 3), (3, 0)):
+        sc = synthetic.make_scene(n, W, H, stored, seed=561 + stored)
+        for form, phases in (("one_call", ("all",)), ("phases_apart", ("composite", "params_sh", "params_geom"))):
+            ctx = B.Context(deterministic=True)
+            set_model(ctx, sc, n, stored)
+            ctx.set_active_sh_degree(active)
+            g = ctx.grads_alloc()
+            got = []
+            for view in (0, 1):
+                ctx.set_view_slot(view)
+                set_cam(ctx, W, H, view)
+                ctx.preprocess(); ctx.bin(); ctx.forward_host()
+                dC = synthetic.make_dC(W, H, 571 + view)
+                for ph in phases:
+                    ctx.backward(dC, g, overwrite=view == 0, phase=ph)
+                got.append(ctx.grads_read(g, stored))
+                for k, v in got[-1].items():
+                    R.put("backward_forms/active_%d_of_%d_%s_view%d.%s" % (active, stored, form, view, k), v)
+            assert all(np.isfinite(v).all() for v in got[1].values()) and all(got[0][k].any() and not np.array_equal(got[0][k], got[1][k]) for k in got[0]), \
+                "backward forms: a view added nothing"
+            ctx.close()
+
+
 def image_pair(W, H, Cn, seed):
     """a smooth image and a noisy copy of it in [0, 1], and a weight in [0, 1] with zeros in it"""
     rng = np.random.default_rng(seed)
@@ -365,9 +396,10 @@ def case_loss_metrics(R):
 
 
 def case_camera_grad(R):
+    """degree 1 at n = 300 and n = 257 (the reduction's ragged ends), the other degrees' instantiations at n = 300"""
     from gaussiansplat_amd import backend as B, synthetic
-    W, H, deg = 64, 48, 1
-    for n in (300, 257):
+    W, H = 64, 48
+    for deg, n in ((1, 300), (1, 257), (0, 300), (2, 300), (3, 300)):
         sc = synthetic.make_scene(n, W, H, deg, seed=541)
         ctx = B.Context(deterministic=True)
         set_model(ctx, sc, n, deg)
@@ -376,7 +408,7 @@ def case_camera_grad(R):
         ctx.backward(synthetic.make_dC(W, H, 542), ctx.grads_alloc(), overwrite=True)
         got = ctx.backward_camera()
         assert np.isfinite(got).all() and got.any(), "camera gradient: nothing computed"
-        R.put("camera_grad_n%d/d_camera" % n, got)
+        R.put(("camera_grad_n%d/d_camera" % n) if deg == 1 else ("camera_grad_degree_%d_n%d/d_camera" % (deg, n)), got)
         ctx.close()
 
 
@@ -428,6 +460,7 @@ def record(path):
     case_touched(R)
     case_adam(R)
     case_active_degree(R)
+    case_backward_forms(R)
     case_loss_metrics(R)
     case_camera_grad(R)
     case_exposure(R)

@@ -4,7 +4,8 @@
 Both files: the gfx950 assembly of one translation unit (hipcc --save-temps, or -S --cuda-device-only) built with build.py's flags.
 One line per kernel.  A kernel is `same` when the sequence of its instruction mnemonics and its .amdhsa_next_free_vgpr,
 .amdhsa_next_free_sgpr, .amdhsa_private_segment_fixed_size and .amdhsa_group_segment_fixed_size equal the parent's: register names,
-block labels and comments may differ.  The composite kernels' debug-clock instantiations (template argument CLK) may reorder: they
+block labels and comments may differ.  A kernel whose mnemonics differ is said to have `moved` when the multiset of its mnemonics is the parent's
+(instructions changed places, none was added or dropped); it still counts as differing.  The composite kernels' debug-clock instantiations (template argument CLK) may reorder: they
 keep their name (which carries the launch bound's waves per SIMD) and their workgroup size, and carry no more scratch than the parent's.
 Exit status 1 if a kernel differs or is missing on either side."""
 import re, sys
@@ -53,7 +54,8 @@ for name in sorted(set(old) | set(new)):
     else:
         d = [k for k in KEYS if o[k] != n[k]] + (["mnemonics"] if o["ops"] != n["ops"] else [])
         ok = not d
-        verdict = ("same" if ok else "DIFFERS: " + ", ".join(d)) + "  ops %d  vgpr %s sgpr %s scratch %s lds %s" % ((len(n["ops"]),) + tuple(n[k] for k in KEYS))
+        moved = d == ["mnemonics"] and sorted(o["ops"]) == sorted(n["ops"])
+        verdict = ("same" if ok else "DIFFERS: " + ("moved, multiset equal" if moved else ", ".join(d))) + "  ops %d  vgpr %s sgpr %s scratch %s lds %s" % ((len(n["ops"]),) + tuple(n[k] for k in KEYS))
     bad += not ok
     print("%-100s %s" % (name[:100], verdict))
 print("%d kernels, %d differ" % (len(set(old) | set(new)), bad))
