@@ -35,7 +35,8 @@ SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs
            "gs_knn_mean_dist2", "gs_init_from_points",
            "gs_view_depth", "gs_view_depth_backward", "gs_render_features", "gs_backward_features", "gs_backward_camera",
            "gs_image_metrics", "gs_metrics_finish",
-           "gs_exposure_apply", "gs_exposure_backward", "gs_exposure_adam")
+           "gs_exposure_apply", "gs_exposure_backward", "gs_exposure_adam",
+           "gs_mcmc_plan", "gs_mcmc_sample", "gs_mcmc_relocate", "gs_mcmc_noise", "gs_mcmc_regularize")
 
 GS_CAMERA_GRAD_FLOATS = 40  # include/gsplat.h: gs_backward_camera
 GS_METRIC_SUMS = 4          # include/gsplat.h: gs_image_metrics
@@ -181,6 +182,11 @@ def load():
     L.gs_exposure_apply.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, vp]
     L.gs_exposure_backward.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp]
     L.gs_exposure_adam.argtypes = [vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64]
+    L.gs_mcmc_plan.argtypes = [vp, C.c_float, vp, vp, C.POINTER(C.c_int64)]
+    L.gs_mcmc_sample.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp]
+    L.gs_mcmc_relocate.argtypes = [vp, vp, vp, C.c_int64, C.c_float, C.c_int32, G]
+    L.gs_mcmc_noise.argtypes = [vp, vp, C.c_float, C.c_float, C.c_float]
+    L.gs_mcmc_regularize.argtypes = [vp, G, C.c_float, C.c_float]
     if L.gs_abi_version() != GS_ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH} has ABI version {L.gs_abi_version()}, this binding is written for {GS_ABI_VERSION}: "
                            "rebuild with `python -m gaussiansplat_amd.build --force`")
@@ -516,6 +522,37 @@ class Context:
     def opacity_reset(self, max_logit: float, m_opac_ptr: int = 0, v_opac_ptr: int = 0):
         """gs_opacity_reset: opacity = min(opacity, max_logit) on the resident model (NaN stays), +0 into the two moment arrays."""
         self._chk(self.L.gs_opacity_reset(self.h, C.c_float(max_logit), C.c_void_p(int(m_opac_ptr or 0)), C.c_void_p(int(v_opac_ptr or 0))))
+
+    # -- MCMC densification (3-D renderer): plan, draws, relocation, noise, regularisers
+    def mcmc_plan(self, min_opacity_logit: float, cdf_ptr: int, dead_ptr: int):
+        """gs_mcmc_plan: the integer weights' inclusive prefix sum into cdf (uint64 device array of n words), the indices of the gaussians
+        that are not alive, ascending, into dead (int32, n words); (alive, dead, total).  The one call of the five that synchronises."""
+        o = (C.c_int64 * 3)()
+        self._chk(self.L.gs_mcmc_plan(self.h, C.c_float(min_opacity_logit), C.c_void_p(int(cdf_ptr or 0)), C.c_void_p(int(dead_ptr or 0)), o))
+        return int(o[0]), int(o[1]), int(o[2])
+
+    def mcmc_sample(self, cdf_ptr: int, n: int, u_ptr: int, m: int, src_ptr: int):
+        """gs_mcmc_sample: src[j] = the gaussian the uniform number u[j] points at on the CDF (int32, m words).  No sync."""
+        self._chk(self.L.gs_mcmc_sample(self.h, C.c_void_p(int(cdf_ptr or 0)), C.c_int64(int(n)), C.c_void_p(int(u_ptr or 0)), C.c_int64(int(m)),
+                                        C.c_void_p(int(src_ptr or 0))))
+
+    def mcmc_relocate(self, src_ptr: int, dst_ptr: "int | None", m: int, min_opacity: float, sets=()):
+        """gs_mcmc_relocate: in place on the resident model, gaussian dst[j] becomes a copy of src[j] and both get the corrected opacity and
+        scales; dst_ptr None / 0: the first m entries of the current plan's dead list.  sets: up to four GsGrads whose rows of sources and
+        destinations become +0 (Adam's moments).  No sync."""
+        sets = list(sets)
+        k = len(sets)
+        sa = (GsGrads * max(k, 1))(*sets)
+        self._chk(self.L.gs_mcmc_relocate(self.h, C.c_void_p(int(src_ptr or 0)), C.c_void_p(int(dst_ptr or 0)), C.c_int64(int(m)), C.c_float(min_opacity),
+                                          k, sa))
+
+    def mcmc_noise(self, z_ptr: int, lr: float, gate_k: float = 100.0, gate_t: float = 0.005):
+        """gs_mcmc_noise: means += lr * gate(opacity) * Sigma z on the resident model, z: [n, 3] standard normals on the device.  No sync."""
+        self._chk(self.L.gs_mcmc_noise(self.h, C.c_void_p(int(z_ptr or 0)), C.c_float(lr), C.c_float(gate_k), C.c_float(gate_t)))
+
+    def mcmc_regularize(self, grads: GsGrads, c_opacity: float, c_scale: float):
+        """gs_mcmc_regularize: d_opacities += c_opacity * sig (1 - sig), d_scales += c_scale * exp(scale) into `grads`.  The frame stands.  No sync."""
+        self._chk(self.L.gs_mcmc_regularize(self.h, C.byref(grads), C.c_float(c_opacity), C.c_float(c_scale)))
 
     # -- point-cloud initialisation: needs no model, camera or frame, and leaves the ctx's frame as it is
     def knn_mean_dist2(self, points_ptr: int, n: int, dist2_ptr: int):

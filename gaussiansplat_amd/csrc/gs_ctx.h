@@ -12,6 +12,7 @@
 //   gs_api_camera.hip     the camera gradient (gs_backward_camera)
 //   gs_api_metrics.hip    evaluation metrics (gs_image_metrics, gs_metrics_finish)
 //   gs_api_exposure.hip   the per-view exposure stage (gs_exposure_apply, gs_exposure_backward, gs_exposure_adam)
+//   gs_api_mcmc.hip       MCMC densification (gs_mcmc_plan / _sample / _relocate / _noise / _regularize)
 //   gs_background.hip     the background colour's two elementwise kernels (the forward's epilogue, gs_compose_target)
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
 // How far the frame has come is ONE ordered value (gs_ctx::Stage): every entry point compares it, reaches a stage or falls back to one.
@@ -133,7 +134,7 @@ struct gs_ctx {
     } stage = Stage::NOTHING;
     void reach(Stage s) { stage = s; }
     void fall_back(Stage s) { if (stage > s) stage = s; }                  // to at most s
-    void inputs_changed() { fall_back(Stage::NOTHING); density.planned = false; }   // the model or the view changed: nothing of the frame stands, nor a density plan
+    void inputs_changed() { fall_back(Stage::NOTHING); density.planned = false; mcmc.planned = false; }   // the model or the view changed: nothing of the frame stands, nor a density or MCMC plan
     int gx = 0, gy = 0;
     int64_t grid_key() const { return ((int64_t)gx << 32) | (int64_t)gy; }        // what per-grid history is tagged with (0: none)
     int64_t ntiles() const { return (int64_t)gx * gy; }                           // tiles of the grid (at most 2048 x 2048: fits an int) ...
@@ -340,6 +341,15 @@ struct gs_ctx {
         int64_t n_out() const { return survivors + clones + 2 * splits; }
     } density;
     float density_log_shrink = 0.4700036292457356f;   // (float)log(1.6) until a gs_density_decide says otherwise: what the children of a split shrink by
+    // ---- MCMC densification (gs_api_mcmc.hip): per chunk of GS_MCMC_CHUNK gaussians {sum of the weights, dead count} and their exclusive offsets, the two
+    // totals, the histogram of a relocation's sources (n int32), the binomial table (uploaded once); the plan gs_mcmc_plan leaves for gs_mcmc_relocate(dst = NULL)
+    DevBuf mcmc_sum, mcmc_off, mcmc_tot, mcmc_hist, mcmc_binom;
+    bool mcmc_binom_ready = false;
+    struct McmcPlan {
+        bool planned = false;                // dropped by inputs_changed()
+        const int32_t *dead = nullptr;       // the caller's dead list, n and the number of entries the plan wrote
+        int64_t n = 0, dead_count = 0;
+    } mcmc;
     // ---- point-cloud initialisation (gs_api_knn.hip): scratch of its own, so that gs_knn_mean_dist2 is legal in the middle of a frame --
     // (key | index) pairs and the sort's table, the sorted points, box and super-box bounds, {bounding box, count of finite points}
     DevBuf knn_pairs_a, knn_pairs_b, knn_table, knn_digit_total, knn_sorted, knn_boxes, knn_supers, knn_stats;

@@ -175,6 +175,9 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
     density (density.DensityController): its statistics are accumulated between the backward and the update (the update drops the
     frame, so this is the only place), and after the update it clones / splits / prunes and resets opacities when its schedule says so.
     The fused forms leave no frame to accumulate from: a fused optimiser or fused_sgd with `density` is a ValueError.
+    density may also be an mcmc.MCMCController, the other strategy, through the same two hooks: between the backward and the update it adds
+    the gradients of its opacity and scale regularisers, after the update it relocates dead gaussians and grows the model when its schedule
+    says so and injects its noise into the means, every iteration (rate: noise_lr times the optimiser's rate of the means; SGD: its means_lr).
     sh_schedule (SHDegreeSchedule, 3-D renderer): sets the active SH degree of this iteration before preprocess; every optimiser form,
     the fused ones included, and density control run under it unchanged (the request survives a restructured model).
     background: None leaves the renderer's background as it is; (r, g, b) sets it; a RandomBackground draws this iteration's colour and

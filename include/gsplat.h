@@ -488,6 +488,62 @@ int gs_density_restructure(gs_ctx *ctx, const int32_t *action, const float *nois
  * moment arrays (DEVICE, N floats; either may be NULL).  The frame is dropped, as after an optimiser step.  No synchronise. */
 int gs_opacity_reset(gs_ctx *ctx, float max_logit, float *m_opac, float *v_opac);
 
+/* ---- MCMC densification: relocate, grow, noise, regularisers (3-D renderer) ---------- */
+
+/* The other densification strategy ("3D Gaussian Splatting as Markov Chain Monte Carlo", Kheradmand et al. 2024): a fixed budget of
+ * gaussians, dead ones relocated onto live ones drawn with probability proportional to opacity, growth by the same draw, noise shaped by
+ * every gaussian's covariance after every step, two L1 regularisers that let unused gaussians die.  Five calls, every one a pure function
+ * of its inputs (random numbers stay with the caller), on the ctx stream, device pointers throughout:
+ *   per iteration:  any non-fused backward, gs_mcmc_regularize into its gradients, the optimiser step, gs_mcmc_noise
+ *   per interval:   gs_mcmc_plan (the one synchronise) -> gs_mcmc_sample -> gs_mcmc_relocate
+ *   growth:         gs_mcmc_sample m sources; arrays of N + m rows, the first N copied, moment rows past N zero; gs_set_model on them;
+ *                   gs_mcmc_relocate with dst = N .. N + m - 1
+ * sig = e / (1 + e) with e = the preprocess's exp of the logit opacity, as everywhere.  The 2-D renderer gets GS_ERR_UNSUPPORTED. */
+
+/* Weights, their prefix sum and the dead list.  alive = opacity > min_opacity_logit (a NaN is not alive);
+ *   w = alive && sig is finite ? (uint32_t)floorf(sig * 16777216.0f) : 0    -- integers: the sums below are exact in any order;
+ *   cdf[i] (N words) = w[0] + ... + w[i];   dead (N words) = the indices of the gaussians that are not alive, ascending; the words past
+ *   their number are left unwritten;   counts (HOST) = {alive, dead, cdf[N-1]}.
+ * The ctx remembers (dead, N, the dead count) as the current plan; gs_set_model, a step of the optimiser, gs_mcmc_noise, a relocation
+ * or a new camera drop it.  The one call of the five that synchronises.  GS_ERR_INVALID: a NaN threshold, a NULL array. */
+int gs_mcmc_plan(gs_ctx *ctx, float min_opacity_logit, uint64_t *cdf, int32_t *dead, int64_t counts[3]);
+
+/* m draws from a CDF of n words (total = cdf[n-1]): with uc = u[j] clamped into [0, 1 - 2^-24] (a NaN: 0),
+ *   t = min((uint64_t)((double)uc * (double)total), total - 1);   src[j] = the smallest i with cdf[i] > t
+ * -- one binary search per draw.  total == 0 (decided on the device), n == 0 or m == 0: GS_OK, nothing written.  No synchronise. */
+int gs_mcmc_sample(gs_ctx *ctx, const uint64_t *cdf, int64_t n, const float *u, int64_t m, int32_t *src);
+
+/* In place on the resident model: gaussian dst[j] becomes a copy of src[j], j < m, and both get the opacity and scales that leave the
+ * rendered result unchanged (the paper's Eq. 9).  With c[s] = the number of j with src[j] == s (counted on the device), for every source
+ * with c >= 1, in DOUBLE, n = min(c + 1, 51):
+ *   o = (double)sig clamped to [0, 1 - 2^-24];   p = -expm1(log1p(-o) / n);
+ *   s = sum_{i=1..n} sum_{k=0..i-1} (C(i-1, k) * ((-1)^k / sqrt(k + 1))) * p^(k+1), in that loop order, p^(k+1) by repeated multiplication;
+ *   pc = min(max(p, min_opacity), 1 - 2^-23);   opacity' = (float)(log(pc) - log1p(-pc));   scale_j' = (float)((double)scale_j + log(o / s)).
+ * Every read sees the model as it was before the call.  Row dst[j]: means, quaternion and SH row of src[j] bit for bit, opacity' and
+ * scale' of src[j].  Every source with c >= 1: opacity' and scale', its other arrays untouched.  Every other row keeps every bit.
+ * dst == NULL: the first m entries of the current plan's dead list, read on the device (GS_ERR_INVALID without a plan, or with m larger
+ * than its dead count).  sets: nsets (0..4) gradient-shaped companion sets (Adam's moments): every non-NULL array gets +0 in the rows of
+ * the sources with c >= 1 and of all destinations, nothing else of them is written.  An entry of src or dst outside [0, N) makes that j
+ * a no-op and is not counted.  Contract, not checked: the dst entries are pairwise distinct and none is a source (the plan's dead list
+ * satisfies it: a dead gaussian has weight 0).  GS_ERR_INVALID, nothing enqueued: m < 0, min_opacity not in (0, 1), nsets out of range,
+ * NULL src with m > 0.  The frame and the plan are dropped, as after an optimiser step (m == 0: nothing changes).  No synchronise. */
+int gs_mcmc_relocate(gs_ctx *ctx, const int32_t *src, const int32_t *dst, int64_t m, float min_opacity, int32_t nsets, const gs_grads *sets);
+
+/* mean += noise shaped by the covariance that is drawn, per gaussian, every operation a single fp32 one; z: [N][3] standard normals:
+ *   gate = 1.0f / (1.0f + exp(gate_k * (sig - gate_t)));   e_j = exp(scale_j);   R = the rotation the preprocess forms from the RAW quaternion;
+ *   a_j = (R[0][j]*z0 + R[1][j]*z1) + R[2][j]*z2;   b_j = (e_j*e_j) * a_j;   d_i = (R[i][0]*b_0 + R[i][1]*b_1) + R[i][2]*b_2;
+ *   mean_i = mean_i + (lr*gate) * d_i      -- all three, or (one of them would not be finite) none.
+ * lr == 0: GS_OK, nothing enqueued.  GS_ERR_INVALID: a non-finite argument, lr < 0, z NULL or overlapping the model.  The frame and
+ * the plans are dropped, as after an optimiser step.  No synchronise. */
+int gs_mcmc_noise(gs_ctx *ctx, const float *z, float lr, float gate_k, float gate_t);
+
+/* The gradients of lambda_o * mean(sig) + lambda_s * mean(exp(scale)) with respect to the stored logit / log parameters, ADDED to the
+ * caller's gradient arrays, fp32:   d_opacities += c_opacity * (sig * (1.0f - sig));   d_scales[j] += c_scale * exp(scale_j)
+ * with c_opacity = (float)(lambda_o / N) and c_scale = (float)(lambda_s / (3 N)) formed by the caller.  Only d_opacities and d_scales of
+ * `grads` are read; a NULL array or a zero coefficient skips that half.  GS_ERR_INVALID: NULL grads, a non-finite coefficient, an array
+ * overlapping the model.  The frame stands (gs_density_accumulate and gs_backward_camera stay legal).  No synchronise. */
+int gs_mcmc_regularize(gs_ctx *ctx, const gs_grads *grads, float c_opacity, float c_scale);
+
 /* ---- point-cloud initialisation: exact 3-NN scales, a model on the device ---------- */
 
 /* The FIRST step of the 3DGS recipe: a model from an SfM point cloud.  Means are the points, SH band 0 the point colours, quaternions the

@@ -309,6 +309,30 @@ end
 hip_opacityReset!(r::HipRenderer, maxLogit::Real, mOpac::Ptr{Float32} = Ptr{Float32}(C_NULL), vOpac::Ptr{Float32} = Ptr{Float32}(C_NULL)) =
     check(r, ccall((:gs_opacity_reset, libgs), Cint, (Ptr{Cvoid}, Cfloat, Ptr{Float32}, Ptr{Float32}), r.ctx, maxLogit, mOpac, vOpac))
 
+# ---- MCMC densification (include/gsplat.h: plan, draws, relocation, noise, regularisers; 3-D renderer; device pointers) ---------------
+# cdf (UInt64, n words) and dead (Int32, n words) are the caller's; (alive, dead, total).  Synchronises.
+function hip_mcmcPlan(r::HipRenderer, minOpacityLogit::Real, cdf::Ptr{UInt64}, dead::Ptr{Int32})
+    counts = zeros(Int64, 3)
+    check(r, ccall((:gs_mcmc_plan, libgs), Cint, (Ptr{Cvoid}, Cfloat, Ptr{UInt64}, Ptr{Int32}, Ptr{Int64}), r.ctx, minOpacityLogit, cdf, dead, counts))
+    return (alive = counts[1], dead = counts[2], total = counts[3])
+end
+# src[j] = the gaussian the uniform number u[j] points at on the CDF of n words (0-based indices, as the library counts)
+hip_mcmcSample!(r::HipRenderer, cdf::Ptr{UInt64}, n::Integer, u::Ptr{Float32}, m::Integer, src::Ptr{Int32}) =
+    check(r, ccall((:gs_mcmc_sample, libgs), Cint, (Ptr{Cvoid}, Ptr{UInt64}, Int64, Ptr{Float32}, Int64, Ptr{Int32}),
+                   r.ctx, cdf, Int64(n), u, Int64(m), src))
+# in place: gaussian dst[j] becomes a copy of src[j], both with the corrected opacity and scales; dst C_NULL: the plan's dead list;
+# sets: gradient-shaped companions (Adam's moments) whose rows of sources and destinations become +0
+function hip_mcmcRelocate!(r::HipRenderer, src::Ptr{Int32}, dst::Ptr{Int32}, m::Integer, minOpacity::Real, sets::Vector{GsGrads} = GsGrads[])
+    check(r, ccall((:gs_mcmc_relocate, libgs), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Int64, Cfloat, Int32, Ptr{GsGrads}),
+                   r.ctx, src, dst, Int64(m), minOpacity, Int32(length(sets)), sets))
+end
+# means += lr * gate(opacity) * Σ z on the resident model; z: [n][3] standard normals
+hip_mcmcNoise!(r::HipRenderer, z::Ptr{Float32}, lr::Real; gateK = 100f0, gateT = 0.005f0) =
+    check(r, ccall((:gs_mcmc_noise, libgs), Cint, (Ptr{Cvoid}, Ptr{Float32}, Cfloat, Cfloat, Cfloat), r.ctx, z, lr, gateK, gateT))
+# the regularisers' gradients added into grads.d_opacities and grads.d_scales; cOpacity = λo / N, cScale = λs / (3 N)
+hip_mcmcRegularize!(r::HipRenderer, grads::GsGrads, cOpacity::Real, cScale::Real) =
+    check(r, ccall((:gs_mcmc_regularize, libgs), Cint, (Ptr{Cvoid}, Ref{GsGrads}, Cfloat, Cfloat), r.ctx, grads, cOpacity, cScale))
+
 # point-cloud initialisation (device pointers; no model, camera or frame needed, the ctx's frame is left as it is; no synchronise)
 # dist2[i] = the mean of the three smallest squared distances from point i to the other finite points: exact, bit for bit a brute force
 hip_knnMeanDist2!(r::HipRenderer, points::Ptr{Float32}, n::Integer, dist2::Ptr{Float32}) =

@@ -19,6 +19,13 @@ extern "C" int gs_density_plan(gs_ctx *, const int32_t *, int64_t *) { return GS
 extern "C" int gs_density_restructure(gs_ctx *, const int32_t *, const float *, const gs_grads *, int32_t, const gs_grads *, const gs_grads *, int64_t) { return GS_ERR_UNSUPPORTED; }
 extern "C" int gs_opacity_reset(gs_ctx *, float, float *, float *) { return GS_ERR_UNSUPPORTED; }
 STUB
+grep -q gs_mcmc_plan "$W/include/gsplat.h" || cat >> "$W/gaussiansplat_amd/csrc/gs_api_debug.hip" <<'STUB'
+extern "C" int gs_mcmc_plan(gs_ctx *, float, uint64_t *, int32_t *, int64_t *) { return GS_ERR_UNSUPPORTED; }
+extern "C" int gs_mcmc_sample(gs_ctx *, const uint64_t *, int64_t, const float *, int64_t, int32_t *) { return GS_ERR_UNSUPPORTED; }
+extern "C" int gs_mcmc_relocate(gs_ctx *, const int32_t *, const int32_t *, int64_t, float, int32_t, const gs_grads *) { return GS_ERR_UNSUPPORTED; }
+extern "C" int gs_mcmc_noise(gs_ctx *, const float *, float, float, float) { return GS_ERR_UNSUPPORTED; }
+extern "C" int gs_mcmc_regularize(gs_ctx *, const gs_grads *, float, float) { return GS_ERR_UNSUPPORTED; }
+STUB
 objs=()
 for s in "$W"/gaussiansplat_amd/csrc/*.hip; do
   b=$(basename "$s" .hip)
