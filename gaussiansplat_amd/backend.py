@@ -54,7 +54,7 @@ GS_ADAM_GROUPS = 6            # lr[0] means, [1] scales, [2] quaternions, [3] op
 GS_ADAM_SELECTIVE = 1         # step only the gaussians with a non-zero gradient float ("selective Adam")
 GS_ERR_INVALID, GS_ERR_UNSUPPORTED = -1, -5
 KNN_BOX = 64                  # points per box of the 3-NN search (GS_KNN_BOX in csrc/gs_knn.h; tests pick their sizes around it)
-TOUCHED_CHUNK = 256           # gaussians per workgroup of the touched-rows pack (GS_TOUCHED_CHUNK in csrc/gs_common.h; tests pick their sizes around it)
+TOUCHED_CHUNK = 256           # gaussians per workgroup of the touched-rows pack (GS_CHUNK in csrc/gs_chunk.h; tests pick their sizes around it)
 
 
 class GsConfig(C.Structure):

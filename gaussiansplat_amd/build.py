@@ -33,6 +33,8 @@ SOURCES = {
     # same flags as gs_preprocess_bwd.hip: the two kernels that rebuild SH gradients from views share one body (gs_sh_views_body.inc, with the
     # basis text gs_sh_basis.inc inside it) and must round alike -- the text is contracted as the including translation unit is built
     "gs_touched.hip": [],
+    # the one scan of the chunk words (touched rows, density plan, MCMC plan): integers only
+    "gs_chunk.hip": [],
     "gs_sort.hip": [],
     "gs_bin2.hip": [],
     "gs_bin3.hip": [],

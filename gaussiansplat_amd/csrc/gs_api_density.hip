@@ -51,7 +51,7 @@ int gs_density_plan(gs_ctx *c, const int32_t *action, int64_t counts[4]) {
     if (c->n > 0 && !action) return fail(c, GS_ERR_INVALID, "gs_density_plan: NULL action");
     if (bind_device(c)) return GS_ERR_HIP;
     c->density.planned = false;
-    const size_t cells = (size_t)GS_DENSITY_CLASSES * (size_t)std::max<int64_t>(gs_density_chunks(c->n), 1);
+    const size_t cells = (size_t)GS_DENSITY_CLASSES * (size_t)std::max<int64_t>(gs_chunks(c->n), 1);
     HIPCHK(c, c->density_cnt.ensure(sizeof(uint32_t) * cells));
     HIPCHK(c, c->density_off.ensure(sizeof(int64_t) * cells));
     HIPCHK(c, c->density_tot.ensure(sizeof(int64_t) * 4));

@@ -7,14 +7,6 @@
 
 typedef unsigned long long u64;
 
-// the model is there (n == 0: nothing to have)
-static int need_model(gs_ctx *c, const char *who) {
-    const Five<const float> m = c->model5();
-    for (int i = 0; i < 5; ++i)
-        if (c->n > 0 && !m[i]) return fail(c, GS_ERR_INVALID, std::string(who) + ": no model (gs_set_model first)");
-    return GS_OK;
-}
-
 extern "C" {
 
 int gs_mcmc_plan(gs_ctx *c, float min_opacity_logit, uint64_t *cdf, int32_t *dead, int64_t counts[3]) {
@@ -27,7 +19,7 @@ int gs_mcmc_plan(gs_ctx *c, float min_opacity_logit, uint64_t *cdf, int32_t *dea
     if (c->n > 0x7fffffffLL) return fail(c, GS_ERR_UNSUPPORTED, "gs_mcmc_plan: more than 2^31 - 1 gaussians");
     if (bind_device(c)) return GS_ERR_HIP;
     c->mcmc.planned = false;
-    const size_t cells = 2 * (size_t)std::max<int64_t>(gs_mcmc_chunks(c->n), 1);
+    const size_t cells = 2 * (size_t)std::max<int64_t>(gs_chunks(c->n), 1);
     HIPCHK(c, c->mcmc_sum.ensure(sizeof(u64) * cells));
     HIPCHK(c, c->mcmc_off.ensure(sizeof(u64) * cells));
     HIPCHK(c, c->mcmc_tot.ensure(sizeof(u64) * 2));

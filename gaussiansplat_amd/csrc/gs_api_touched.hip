@@ -1,10 +1,11 @@
 // gs_api_touched.hip -- the touched-rows colour exchange below the C ABI: gs_color_rows_pack (one view -> bitmap, compacted rows,
 // count) and gs_sh_grads_from_touched (all gathered views -> d_shs).  The kernels are in gs_touched.hip; the per-chunk counts and
 // offsets they pass to each other live in grow-only ctx scratch (touched_cnt, touched_off).  Neither call synchronises.
+#include "gs_chunk.h"
 #include "gs_ctx.h"
 
 static int touched_scratch(gs_ctx *c, int64_t views, int64_t n) {
-    const size_t chunks = (size_t)views * (size_t)gs_touched_chunks(n);
+    const size_t chunks = (size_t)views * (size_t)gs_chunks(n);
     HIPCHK(c, c->touched_cnt.ensure(sizeof(uint32_t) * chunks));
     HIPCHK(c, c->touched_off.ensure(sizeof(int64_t) * chunks));
     return GS_OK;

@@ -6,6 +6,14 @@
 #define GS_TILE 16
 #define GS_WAVE 64
 
+// the grid of a launch of one thread per item in workgroups of 256; false beyond a one-dimensional grid of 2^31 - 1 workgroups
+inline bool gs_grid_256(int64_t n, unsigned *blocks) {
+    const int64_t b = (n + 255) / 256;
+    if (b > 0x7fffffffLL) return false;
+    *blocks = (unsigned)b;
+    return true;
+}
+
 // Per-gaussian, per-view splat payload staged through LDS by the composite kernels: ONE 64-byte row (four quads) per gaussian,
 // so that the random gather of a list entry is a single memory request (48-byte rows were measured: they straddle two 64-byte
 // segments for every second gaussian; tools/ab_traffic.sh at C3, same box, interleaved: 791 vs 628 MB fetched per forward launch at
@@ -415,13 +423,8 @@ hipError_t gs_launch_pack_drgb(const float *g2d, const long long *g2d_fixed, flo
 hipError_t gs_launch_sh_from_views(int64_t n, int sh_degree, int sh_stride, const float *means, int nviews, const float *cams, const float *drgb,
                                    float *d_shs, int overwrite, hipStream_t s);
 // touched-rows exchange (gs_touched.hip): a view as a bitmap plus the colour-gradient rows of the gaussians it touched.  chunk_cnt /
-// chunk_off: scratch of gs_touched_chunks(n) words per view (the pack has one view).  Source of the pack: `dense` [n][3], or
+// chunk_off: scratch of gs_chunks(n) words per view (gs_chunk.h; the pack has one view).  Source of the pack: `dense` [n][3], or
 // (dense null) the composite backward's sums g2d / g2d_fixed as gs_launch_pack_drgb takes them.
-#define GS_TOUCHED_CHUNK 256
-inline int64_t gs_touched_chunks(int64_t n) { return (n + GS_TOUCHED_CHUNK - 1) / GS_TOUCHED_CHUNK; }
-// exclusive prefix sums of `rows` rows of nchunks per-chunk counts, one workgroup per row (the views of a touched-rows rebuild, the
-// classes of a density plan); totals (may be null): the rows' sums
-hipError_t gs_launch_chunk_scan(const uint32_t *chunk_cnt, int64_t *chunk_off, int64_t nchunks, int rows, int64_t *totals, hipStream_t s);
 hipError_t gs_launch_touched_pack(const float *dense, const float *g2d, const long long *g2d_fixed, int64_t n, int32_t *bits, float *rows,
                                   int64_t *count, uint32_t *chunk_cnt, int64_t *chunk_off, hipStream_t s);
 hipError_t gs_launch_sh_from_touched(int64_t n, int sh_degree, int sh_stride, const float *means, int nviews, const float *cams, const int32_t *bits,

@@ -17,7 +17,7 @@
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)
 // How far the frame has come is ONE ordered value (gs_ctx::Stage): every entry point compares it, reaches a stage or falls back to one.
 // What the ctx holds it owns: DevBuf frees itself, ~gs_ctx releases the communicator, events, streams and pinned blocks -- no list to keep.
-// What every entry point needs is written ONCE, here: the refusals they share (need_3d, need_mem, need_image_size, need_stage, overlaps), the sizes
+// What every entry point needs is written ONCE, here: the refusals they share (need_3d, need_mem, need_model, need_image_size, need_stage, overlaps), the sizes
 // (n1, ntiles, pixels), a buffer of gradient rows in the ctx's mode (gs_ctx::rows), the model head of an argument struct (model_head), the per-gaussian
 // chain's arguments (chain_args), the export_debug arrays (gs_ctx::Dbg, DBG_WIDTH); what changes behind a frame's plans is one value (gs_ctx::FrameLive).
 #pragma once
@@ -331,7 +331,7 @@ struct gs_ctx {
     DevBuf dpc;                              // 4 x n scratch between the two backward kernels
     DevBuf loss_maps, loss_acc, loss_in[2], loss_dc, view_cams;
     DevBuf touched_cnt, touched_off, touched_zero;   // touched-rows exchange: per (view, chunk) counts and exclusive row offsets; three +0 floats (gs_api_touched.hip)
-    // ---- density control (gs_api_density.hip): per chunk of GS_DENSITY_CHUNK gaussians the counts of the three output classes (survivors,
+    // ---- density control (gs_api_density.hip): per chunk of GS_CHUNK gaussians the counts of the three output classes (survivors,
     // clones, split sources), their exclusive offsets, and {three totals, bad-action flag}; the plan gs_density_plan leaves for gs_density_restructure
     DevBuf density_cnt, density_off, density_tot;
     struct DensityPlan {
@@ -341,7 +341,7 @@ struct gs_ctx {
         int64_t n_out() const { return survivors + clones + 2 * splits; }
     } density;
     float density_log_shrink = 0.4700036292457356f;   // (float)log(1.6) until a gs_density_decide says otherwise: what the children of a split shrink by
-    // ---- MCMC densification (gs_api_mcmc.hip): per chunk of GS_MCMC_CHUNK gaussians {sum of the weights, dead count} and their exclusive offsets, the two
+    // ---- MCMC densification (gs_api_mcmc.hip): per chunk of GS_CHUNK gaussians {sum of the weights, dead count} and their exclusive offsets, the two
     // totals, the histogram of a relocation's sources (n int32), the binomial table (uploaded once); the plan gs_mcmc_plan leaves for gs_mcmc_relocate(dst = NULL)
     DevBuf mcmc_sum, mcmc_off, mcmc_tot, mcmc_hist, mcmc_binom;
     bool mcmc_binom_ready = false;
@@ -391,6 +391,13 @@ inline int need_3d(gs_ctx *c, const char *who) { return c->kind == 0 ? GS_OK : f
 inline int need_mem(gs_ctx *c, const char *who, int mem) { return mem == GS_MEM_HOST || mem == GS_MEM_DEVICE ? GS_OK : fail(c, GS_ERR_INVALID, std::string(who) + ": bad mem"); }
 inline int need_image_size(gs_ctx *c, const char *who, int W, int H) {
     return W > 0 && H > 0 && W <= 32767 && H <= 32767 ? GS_OK : fail(c, GS_ERR_INVALID, std::string(who) + ": image size must be in 1..32767");
+}
+// the five arrays of the model are there (n == 0: nothing to have)
+inline int need_model(gs_ctx *c, const char *who) {
+    const Five<const float> m = c->model5();
+    for (int i = 0; i < 5; ++i)
+        if (c->n > 0 && !m[i]) return fail(c, GS_ERR_INVALID, std::string(who) + ": no model (gs_set_model first)");
+    return GS_OK;
 }
 // the frame has come at least as far as s, else GS_ERR_INVALID with this message (whole: the calls word what they need in their own way)
 inline int need_stage(gs_ctx *c, gs_ctx::Stage s, const char *msg) { return c->stage >= s ? GS_OK : fail(c, GS_ERR_INVALID, msg); }

@@ -2,12 +2,11 @@
 // screen-space positional gradient, the clone / split / prune decision, the ordered restructuring of the model and of gradient-shaped
 // companion arrays (Adam's moments), and the opacity reset.  Semantics: include/gsplat.h, DESIGN.md 5.8b.
 #pragma once
+#include "gs_chunk.h"
 #include "gs_common.h"
 
-#define GS_DENSITY_CHUNK 256         // gaussians per workgroup of the plan and of the restructure: four wave64 ballots per class
 #define GS_DENSITY_CLASSES 3         // output classes a source row feeds: survivors (actions 0, 1), clones (1), split sources (2)
 #define GS_DENSITY_MAX_SETS 4        // gradient-shaped companion sets a restructure carries along
-inline int64_t gs_density_chunks(int64_t n) { return (n + GS_DENSITY_CHUNK - 1) / GS_DENSITY_CHUNK; }
 
 struct GsDensityAccArgs {
     int64_t n;
@@ -32,7 +31,8 @@ struct GsDensityDecideArgs {
 };
 hipError_t gs_launch_density_decide(const GsDensityDecideArgs &a, hipStream_t s);
 
-// chunk_cnt: [GS_DENSITY_CLASSES][chunks] counts; chunk_off: the same shape, exclusive offsets inside each class; totals: four words
+// The plan and the restructure run one workgroup per chunk of GS_CHUNK gaussians (gs_chunk.h).  chunk_cnt: [GS_DENSITY_CLASSES][gs_chunks(n)]
+// counts; chunk_off: the same shape, exclusive offsets inside each class; totals: four words
 // {survivors, clones, split sources, != 0: an action outside 0..3 was seen}.  Enqueues the zeroing of `totals` as well.
 hipError_t gs_launch_density_plan(const int32_t *action, int64_t n, uint32_t *chunk_cnt, int64_t *chunk_off, int64_t *totals, hipStream_t s);
 
@@ -47,8 +47,8 @@ struct GsDensityRestructureArgs {
     const float *src[5];             // the model
     float *dst[5];
     int nsets;
-    const float *set_src[GS_DENSITY_MAX_SETS][5];   // a null array on either side: skipped
-    float *set_dst[GS_DENSITY_MAX_SETS][5];
+    const float *set_src[GS_DENSITY_MAX_SETS][5];   // a pair with a null array on either side is skipped: the caller leaves BOTH null
+    float *set_dst[GS_DENSITY_MAX_SETS][5];         // (gs_api_density.hip does; the +0 rows of clones and children test set_dst alone)
 };
 hipError_t gs_launch_density_restructure(const GsDensityRestructureArgs &a, hipStream_t s);
 

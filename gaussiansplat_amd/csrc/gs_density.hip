@@ -6,13 +6,12 @@
 //                                  `visible` and the extent.  Reads 16 B of the payload row (its last quad: sig and the box), 16 B conic,
 //                                  the 64-byte row, 12 B of statistics; writes 12 B.
 //   gs_density_decide_kernel       element-wise: 0 keep, 1 clone, 2 split, 3 prune -- comparisons of stored floats and integers only.
-//   PLAN: ordered compaction of three output classes WITHOUT any workgroup waiting for another, the shape of the touched-rows pack
-//   (gs_touched.hip): gs_density_class_kernel (per chunk of 256 gaussians: ballots -> three counts), then that pack's own chunk scan
-//   (gs_launch_chunk_scan, one workgroup per class: exclusive offsets and the class total).
+//   PLAN: the ordered compaction of gs_chunk.h over three output classes: gs_density_class_kernel (per chunk of 256 gaussians: ballots ->
+//   three counts), then gs_launch_chunk_scan (one workgroup per class: exclusive offsets and the class total).
 //   gs_density_restructure_kernel  per chunk: every thread re-derives its rank inside the chunk from the same ballots and copies its row to
 //                                  the survivors' block, the clones' block and / or writes its two children into the splits' block; the
 //                                  gradient-shaped companion sets (Adam's moments) ride along: survivors copied, new rows +0.
-//                                  A row is moved by its own thread, SH rows as 16-byte accesses where 3K % 4 == 0 and the arrays are
+//                                  A row is moved by its own thread (gs_row_put), SH rows as 16-byte accesses where 3K % 4 == 0 and the arrays are
 //                                  16-byte aligned (twelve loads and stores at degree 3).  That is the form that was measured (C3: a quarter
 //                                  of the copy rate); a cooperative copy through the chunk's ranks in LDS was not built: the
 //                                  kernel runs once per hundred iterations.
@@ -26,9 +25,6 @@
 #include <stddef.h>
 
 #pragma clang fp contract(off)
-
-static_assert(GS_DENSITY_CHUNK == 256, "one workgroup of 256 threads = four wave64 ballots per chunk");
-#define GS_DENSITY_WAVES (GS_DENSITY_CHUNK / 64)
 
 __global__ __launch_bounds__(256) void gs_density_accumulate_kernel(GsDensityAccArgs a) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -70,10 +66,10 @@ __device__ __forceinline__ void density_classes(int act, bool in, bool (&cls)[GS
     cls[0] = in && (act == 0 || act == 1); cls[1] = in && act == 1; cls[2] = in && act == 2;
 }
 
-__global__ __launch_bounds__(GS_DENSITY_CHUNK) void gs_density_class_kernel(const int32_t *__restrict__ action, int64_t n, uint32_t *__restrict__ chunk_cnt,
+__global__ __launch_bounds__(GS_CHUNK) void gs_density_class_kernel(const int32_t *__restrict__ action, int64_t n, uint32_t *__restrict__ chunk_cnt,
                                                                              int64_t nchunks, int64_t *__restrict__ totals) {
-    __shared__ int wave_cnt[GS_DENSITY_CLASSES][GS_DENSITY_WAVES];
-    const int64_t g = (int64_t)blockIdx.x * GS_DENSITY_CHUNK + threadIdx.x;
+    __shared__ int wave_cnt[GS_DENSITY_CLASSES][GS_CHUNK_WAVES];
+    const int64_t g = (int64_t)blockIdx.x * GS_CHUNK + threadIdx.x;
     const bool in = g < n;
     const int act = in ? action[g] : 0;
     bool cls[GS_DENSITY_CLASSES];
@@ -87,30 +83,13 @@ __global__ __launch_bounds__(GS_DENSITY_CHUNK) void gs_density_class_kernel(cons
     const unsigned long long bad = gs_wave_rank(in && (act < 0 || act > 3), lane).ballot;
     if (lane == 0 && bad) atomicOr(reinterpret_cast<unsigned long long *>(totals + 3), 1ull);
     __syncthreads();
-    if (threadIdx.x < GS_DENSITY_CLASSES) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < GS_DENSITY_WAVES; ++w) s += wave_cnt[threadIdx.x][w];
-        chunk_cnt[(int64_t)threadIdx.x * nchunks + blockIdx.x] = (uint32_t)s;
-    }
+    if (threadIdx.x < GS_DENSITY_CLASSES)
+        chunk_cnt[(int64_t)threadIdx.x * nchunks + blockIdx.x] = (uint32_t)gs_chunk_count(wave_cnt[threadIdx.x]);
 }
 
-// w floats of row `srow` of src to row `drow` of dst, bit for bit (src null: +0).  16-byte accesses when the rows are 16-byte aligned.
-__device__ __forceinline__ void density_put_row(float *__restrict__ dst, int64_t drow, const float *__restrict__ src, int64_t srow, int w) {
-    float *d = dst + drow * w;
-    const float *s = src ? src + srow * w : nullptr;
-    const bool vec = (w & 3) == 0 && ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15) == 0;
-    if (vec) {
-        for (int j = 0; j < w; j += 4)
-            *reinterpret_cast<float4 *>(d + j) = s ? *reinterpret_cast<const float4 *>(s + j) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    } else {
-        for (int j = 0; j < w; ++j) d[j] = s ? s[j] : 0.0f;
-    }
-}
-
-__global__ __launch_bounds__(GS_DENSITY_CHUNK) void gs_density_restructure_kernel(GsDensityRestructureArgs a, int64_t nchunks) {
-    __shared__ int wave_cnt[GS_DENSITY_CLASSES][GS_DENSITY_WAVES];
-    const int64_t g = (int64_t)blockIdx.x * GS_DENSITY_CHUNK + threadIdx.x;
+__global__ __launch_bounds__(GS_CHUNK) void gs_density_restructure_kernel(GsDensityRestructureArgs a, int64_t nchunks) {
+    __shared__ int wave_cnt[GS_DENSITY_CLASSES][GS_CHUNK_WAVES];
+    const int64_t g = (int64_t)blockIdx.x * GS_CHUNK + threadIdx.x;
     const bool in = g < a.n;
     const int act = in ? a.action[g] : 0;
     bool cls[GS_DENSITY_CLASSES];
@@ -126,31 +105,19 @@ __global__ __launch_bounds__(GS_DENSITY_CHUNK) void gs_density_restructure_kerne
     __syncthreads();
     int64_t idx[GS_DENSITY_CLASSES];                                       // the row's place inside its class
 #pragma unroll
-    for (int k = 0; k < GS_DENSITY_CLASSES; ++k) {
-        int before = 0;
-#pragma unroll
-        for (int w = 0; w < GS_DENSITY_WAVES; ++w) before += w < wv ? wave_cnt[k][w] : 0;
-        idx[k] = a.chunk_off[(int64_t)k * nchunks + blockIdx.x] + before + rank[k];
-    }
-    const int width[5] = {3, 3, 4, 1, a.k3};
+    for (int k = 0; k < GS_DENSITY_CLASSES; ++k) idx[k] = a.chunk_off[(int64_t)k * nchunks + blockIdx.x] + gs_chunk_before(wave_cnt[k], wv) + rank[k];
     // survivors, then clones: copies of the source row; the companions of a survivor are copied, those of a clone are +0.  Every place is
     // checked against the plan's totals: an action array edited since the plan cannot send a row outside the destination
     if (cls[0] && idx[0] < a.survivors) {
 #pragma unroll
-        for (int i = 0; i < 5; ++i) density_put_row(a.dst[i], idx[0], a.src[i], g, width[i]);
-        for (int t = 0; t < a.nsets; ++t)
-#pragma unroll
-            for (int i = 0; i < 5; ++i)
-                if (a.set_dst[t][i] && a.set_src[t][i]) density_put_row(a.set_dst[t][i], idx[0], a.set_src[t][i], g, width[i]);
+        for (int i = 0; i < 5; ++i) gs_row_put(a.dst[i], idx[0], a.src[i], g, gs_row_width(i, a.k3));
+        gs_rows_copy_sets(a.set_dst, a.set_src, a.nsets, idx[0], g, a.k3);
     }
     if (cls[1] && idx[1] < a.clones) {
         const int64_t r = a.survivors + idx[1];
 #pragma unroll
-        for (int i = 0; i < 5; ++i) density_put_row(a.dst[i], r, a.src[i], g, width[i]);
-        for (int t = 0; t < a.nsets; ++t)
-#pragma unroll
-            for (int i = 0; i < 5; ++i)
-                if (a.set_dst[t][i] && a.set_src[t][i]) density_put_row(a.set_dst[t][i], r, nullptr, 0, width[i]);
+        for (int i = 0; i < 5; ++i) gs_row_put(a.dst[i], r, a.src[i], g, gs_row_width(i, a.k3));
+        gs_rows_zero_sets(a.set_dst, a.nsets, r, a.k3);
     }
     if (cls[2] && idx[2] < a.splits) {
         const float m[3] = {a.src[0][3 * g], a.src[0][3 * g + 1], a.src[0][3 * g + 2]};
@@ -170,11 +137,8 @@ __global__ __launch_bounds__(GS_DENSITY_CHUNK) void gs_density_restructure_kerne
                 a.dst[1][3 * r + i] = sc[i] - a.log_shrink;
             }
 #pragma unroll
-            for (int i = 2; i < 5; ++i) density_put_row(a.dst[i], r, a.src[i], g, width[i]);
-            for (int t = 0; t < a.nsets; ++t)
-#pragma unroll
-                for (int i = 0; i < 5; ++i)
-                    if (a.set_dst[t][i] && a.set_src[t][i]) density_put_row(a.set_dst[t][i], r, nullptr, 0, width[i]);
+            for (int i = 2; i < 5; ++i) gs_row_put(a.dst[i], r, a.src[i], g, gs_row_width(i, a.k3));
+            gs_rows_zero_sets(a.set_dst, a.nsets, r, a.k3);
         }
     }
 }
@@ -189,17 +153,10 @@ __global__ __launch_bounds__(256) void gs_opacity_reset_kernel(float *__restrict
     if (v_opac) v_opac[g] = 0.0f;
 }
 
-static bool density_grid(int64_t n, unsigned *blocks) {
-    const int64_t b = (n + 255) / 256;
-    if (b > 0x7fffffffLL) return false;
-    *blocks = (unsigned)b;
-    return true;
-}
-
 hipError_t gs_launch_density_accumulate(const GsDensityAccArgs &a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
     unsigned blocks;
-    if (!density_grid(a.n, &blocks) || (!a.g2d == !a.g2d_fixed)) return hipErrorInvalidValue;
+    if (!gs_grid_256(a.n, &blocks) || (!a.g2d == !a.g2d_fixed)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gs_density_accumulate_kernel, dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }
@@ -207,7 +164,7 @@ hipError_t gs_launch_density_accumulate(const GsDensityAccArgs &a, hipStream_t s
 hipError_t gs_launch_density_decide(const GsDensityDecideArgs &a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
     unsigned blocks;
-    if (!density_grid(a.n, &blocks)) return hipErrorInvalidValue;
+    if (!gs_grid_256(a.n, &blocks)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gs_density_decide_kernel, dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }
@@ -216,24 +173,24 @@ hipError_t gs_launch_density_plan(const int32_t *action, int64_t n, uint32_t *ch
     const hipError_t e = hipMemsetAsync(totals, 0, 4 * sizeof(int64_t), s);
     if (e != hipSuccess || n <= 0) return e;
     unsigned blocks;
-    if (!density_grid(n, &blocks)) return hipErrorInvalidValue;
-    const int64_t nchunks = gs_density_chunks(n);
-    hipLaunchKernelGGL(gs_density_class_kernel, dim3(blocks), dim3(GS_DENSITY_CHUNK), 0, s, action, n, chunk_cnt, nchunks, totals);
+    if (!gs_grid_256(n, &blocks)) return hipErrorInvalidValue;
+    const int64_t nchunks = gs_chunks(n);
+    hipLaunchKernelGGL(gs_density_class_kernel, dim3(blocks), dim3(GS_CHUNK), 0, s, action, n, chunk_cnt, nchunks, totals);
     return gs_launch_chunk_scan(chunk_cnt, chunk_off, nchunks, GS_DENSITY_CLASSES, totals, s);
 }
 
 hipError_t gs_launch_density_restructure(const GsDensityRestructureArgs &a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
     unsigned blocks;
-    if (!density_grid(a.n, &blocks) || a.nsets < 0 || a.nsets > GS_DENSITY_MAX_SETS || a.k3 <= 0 || (a.splits > 0 && !a.noise)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(gs_density_restructure_kernel, dim3(blocks), dim3(GS_DENSITY_CHUNK), 0, s, a, gs_density_chunks(a.n));
+    if (!gs_grid_256(a.n, &blocks) || a.nsets < 0 || a.nsets > GS_DENSITY_MAX_SETS || a.k3 <= 0 || (a.splits > 0 && !a.noise)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gs_density_restructure_kernel, dim3(blocks), dim3(GS_CHUNK), 0, s, a, gs_chunks(a.n));
     return hipGetLastError();
 }
 
 hipError_t gs_launch_opacity_reset(float *opac, float max_logit, float *m_opac, float *v_opac, int64_t n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     unsigned blocks;
-    if (!density_grid(n, &blocks)) return hipErrorInvalidValue;
+    if (!gs_grid_256(n, &blocks)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gs_opacity_reset_kernel, dim3(blocks), dim3(256), 0, s, opac, max_logit, m_opac, v_opac, n);
     return hipGetLastError();
 }

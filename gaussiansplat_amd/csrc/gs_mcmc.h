@@ -116,10 +116,8 @@ GS_PG float gs_mcmc_reg_scale(float d, float c_s, float scale) {
 
 #if defined(__HIPCC__)
 #include "gs_density.h"
-#define GS_MCMC_CHUNK 256                 // gaussians per workgroup of the plan: four wave64 scans
-inline int64_t gs_mcmc_chunks(int64_t n) { return (n + GS_MCMC_CHUNK - 1) / GS_MCMC_CHUNK; }
 // gs_mcmc.hip.  Every pointer is a device pointer.
-// plan: chunk_sum / chunk_off are [2][chunks] words (row 0: the chunks' weight sums, row 1: their dead counts; then the exclusive offsets of both),
+// plan: chunk_sum / chunk_off are [2][gs_chunks(n)] words (row 0: the chunks' weight sums, row 1: their dead counts; then the exclusive offsets of both),
 // totals two words {sum of the weights, dead}.  Three launches, none waits for another workgroup.
 hipError_t gs_launch_mcmc_plan(const float *opac, int64_t n, float min_opacity_logit, unsigned long long *chunk_sum, unsigned long long *chunk_off,
                                unsigned long long *totals, unsigned long long *cdf, int32_t *dead, hipStream_t s);

@@ -1,9 +1,9 @@
 // gs_mcmc.hip -- the MCMC densification strategy on the device: the statements of gs_mcmc.h, per gaussian or per draw.
 //
 //   PLAN: the integer weights, their device-wide inclusive prefix sum (the CDF) and the ordered list of the gaussians that are not alive, WITHOUT any
-//   workgroup waiting for another -- the shape of gs_density_plan: gs_mcmc_weigh_kernel (per chunk of 256 gaussians: the sum of the weights by
-//   gs_block_sum, the dead count by ballots), gs_mcmc_chunk_scan_kernel (one workgroup per row of chunk words: exclusive offsets and the total;
-//   every thread sums a contiguous span, so any number of chunks), gs_mcmc_emit_kernel (per chunk: every thread re-derives its weight, a wave scan
+//   workgroup waiting for another -- the compaction of gs_chunk.h: gs_mcmc_weigh_kernel (per chunk of 256 gaussians: the sum of the weights by
+//   gs_block_sum, the dead count by ballots), gs_launch_chunk_scan on 64-bit words (one workgroup per row of chunk words: exclusive offsets and the
+//   total; every thread sums a contiguous span, so any number of chunks), gs_mcmc_emit_kernel (per chunk: every thread re-derives its weight, a wave scan
 //   and the four wave sums give its inclusive sum inside the chunk, the same ballots its rank among the dead).  Integers: exact in any order.
 //   gs_mcmc_sample_kernel     one thread per draw: the target on the CDF, one binary search (about log2 n dependent 8-byte loads).
 //   RELOCATE, three launches behind the zero fill of the histogram: gs_mcmc_count_kernel (how often every gaussian is a source: int32 atomics),
@@ -22,58 +22,30 @@
 #pragma clang fp contract(off)
 
 typedef unsigned long long u64;
-static_assert(GS_MCMC_CHUNK == 256, "one workgroup of 256 threads = four wave64 scans per chunk");
-#define GS_MCMC_WAVES (GS_MCMC_CHUNK / 64)
 
-__global__ __launch_bounds__(GS_MCMC_CHUNK) void gs_mcmc_weigh_kernel(const float *__restrict__ opac, int64_t n, float min_logit, u64 *__restrict__ chunk_sum,
+__global__ __launch_bounds__(GS_CHUNK) void gs_mcmc_weigh_kernel(const float *__restrict__ opac, int64_t n, float min_logit, u64 *__restrict__ chunk_sum,
                                                                        int64_t nchunks) {
-    __shared__ u64 sm[GS_MCMC_WAVES];
-    __shared__ int dead_cnt[GS_MCMC_WAVES];
-    const int64_t g = (int64_t)blockIdx.x * GS_MCMC_CHUNK + threadIdx.x;
+    __shared__ u64 sm[GS_CHUNK_WAVES];
+    __shared__ int dead_cnt[GS_CHUNK_WAVES];
+    const int64_t g = (int64_t)blockIdx.x * GS_CHUNK + threadIdx.x;
     const bool in = g < n;
     const float o = in ? opac[g] : 0.0f;
     const u64 w = in ? (u64)gs_mcmc_weight(o, min_logit) : 0ull;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const GsWaveRank r = gs_wave_rank(in && !gs_mcmc_alive(o, min_logit), lane);
     if (lane == 0) dead_cnt[wv] = r.count;
-    const u64 total = gs_block_sum(w, sm, GS_MCMC_WAVES);                   // (its barrier covers dead_cnt too)
+    const u64 total = gs_block_sum(w, sm, GS_CHUNK_WAVES);                  // (its barrier covers dead_cnt too)
     if (threadIdx.x == 0) {
         chunk_sum[blockIdx.x] = total;
-        chunk_sum[nchunks + blockIdx.x] = (u64)(dead_cnt[0] + dead_cnt[1] + dead_cnt[2] + dead_cnt[3]);
+        chunk_sum[nchunks + blockIdx.x] = (u64)gs_chunk_count(dead_cnt);
     }
 }
 
-// One workgroup per row of `nchunks` words (blockIdx.x): exclusive prefix sums and the row's total.  gs_touched_scan_kernel's shape on 64-bit words.
-__global__ __launch_bounds__(1024) void gs_mcmc_chunk_scan_kernel(const u64 *__restrict__ chunk_sum, u64 *__restrict__ chunk_off, int64_t nchunks,
-                                                                   u64 *__restrict__ totals) {
-    __shared__ u64 s[2][1024];
-    const u64 *c = chunk_sum + (int64_t)blockIdx.x * nchunks;
-    u64 *o = chunk_off + (int64_t)blockIdx.x * nchunks;
-    const int t = threadIdx.x;
-    const int64_t per = (nchunks + 1023) / 1024;
-    const int64_t lo = min((int64_t)t * per, nchunks), hi = min(lo + per, nchunks);
-    u64 sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += c[i];
-    s[0][t] = sum;
-    __syncthreads();
-    int cur = 0;
-    for (int d = 1; d < 1024; d <<= 1) {                                   // reads s[cur], writes s[cur ^ 1]: one barrier per step
-        u64 v = s[cur][t];
-        if (t >= d) v += s[cur][t - d];
-        s[cur ^ 1][t] = v;
-        __syncthreads();
-        cur ^= 1;
-    }
-    u64 run = s[cur][t] - sum;
-    for (int64_t i = lo; i < hi; ++i) { o[i] = run; run += c[i]; }
-    if (t == 1023) totals[blockIdx.x] = s[cur][1023];
-}
-
-__global__ __launch_bounds__(GS_MCMC_CHUNK) void gs_mcmc_emit_kernel(const float *__restrict__ opac, int64_t n, float min_logit, const u64 *__restrict__ chunk_off,
+__global__ __launch_bounds__(GS_CHUNK) void gs_mcmc_emit_kernel(const float *__restrict__ opac, int64_t n, float min_logit, const u64 *__restrict__ chunk_off,
                                                                       int64_t nchunks, u64 *__restrict__ cdf, int32_t *__restrict__ dead) {
-    __shared__ u64 wave_sum[GS_MCMC_WAVES];
-    __shared__ int dead_cnt[GS_MCMC_WAVES];
-    const int64_t g = (int64_t)blockIdx.x * GS_MCMC_CHUNK + threadIdx.x;
+    __shared__ u64 wave_sum[GS_CHUNK_WAVES];
+    __shared__ int dead_cnt[GS_CHUNK_WAVES];
+    const int64_t g = (int64_t)blockIdx.x * GS_CHUNK + threadIdx.x;
     const bool in = g < n;
     const float o = in ? opac[g] : 0.0f;
     u64 v = in ? (u64)gs_mcmc_weight(o, min_logit) : 0ull;
@@ -88,16 +60,10 @@ __global__ __launch_bounds__(GS_MCMC_CHUNK) void gs_mcmc_emit_kernel(const float
     if (lane == 63) wave_sum[wv] = v;
     if (lane == 0) dead_cnt[wv] = r.count;
     __syncthreads();
-    u64 before = chunk_off[blockIdx.x];
-    int64_t dead_before = (int64_t)chunk_off[nchunks + blockIdx.x];
-#pragma unroll
-    for (int w = 0; w < GS_MCMC_WAVES; ++w) {
-        before += w < wv ? wave_sum[w] : 0ull;
-        dead_before += w < wv ? dead_cnt[w] : 0;
-    }
-    if (in) cdf[g] = before + v;
-    const int64_t place = dead_before + r.below;                           // a rank below the dead total <= n: inside the caller's n words,
-    if (is_dead && place < n) dead[place] = (int32_t)g;                    // even if the opacities were edited between the launches
+    if (in) cdf[g] = chunk_off[blockIdx.x] + gs_chunk_before(wave_sum, wv) + v;
+    // a rank below the dead total <= n: inside the caller's n words, even if the opacities were edited between the launches
+    const int64_t place = (int64_t)chunk_off[nchunks + blockIdx.x] + gs_chunk_before(dead_cnt, wv) + r.below;
+    if (is_dead && place < n) dead[place] = (int32_t)g;
 }
 
 __global__ __launch_bounds__(256) void gs_mcmc_sample_kernel(const u64 *__restrict__ cdf, int64_t n, const float *__restrict__ u, int64_t m, int32_t *__restrict__ src) {
@@ -121,26 +87,6 @@ __global__ __launch_bounds__(256) void gs_mcmc_count_kernel(GsMcmcRelocateArgs a
     if (mcmc_pair(a, j, s, d)) atomicAdd(a.hist + s, 1);
 }
 
-// w floats of row `srow` to row `drow` of one array, bit for bit (src null: +0).  16-byte accesses when the rows are 16-byte aligned.
-__device__ __forceinline__ void mcmc_put_row(float *__restrict__ arr, int64_t drow, bool copy, int64_t srow, int w) {
-    float *d = arr + drow * w;
-    const float *s = arr + srow * w;
-    if ((w & 3) == 0 && (reinterpret_cast<uintptr_t>(arr) & 15) == 0) {
-        for (int j = 0; j < w; j += 4)
-            *reinterpret_cast<float4 *>(d + j) = copy ? *reinterpret_cast<const float4 *>(s + j) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    } else {
-        for (int j = 0; j < w; ++j) d[j] = copy ? s[j] : 0.0f;
-    }
-}
-
-__device__ __forceinline__ void mcmc_zero_sets(const GsMcmcRelocateArgs &a, int64_t row) {
-    const int width[5] = {3, 3, 4, 1, a.k3};
-    for (int t = 0; t < a.nsets; ++t)
-#pragma unroll
-        for (int i = 0; i < 5; ++i)
-            if (a.set[t][i]) mcmc_put_row(a.set[t][i], row, false, 0, width[i]);
-}
-
 __global__ __launch_bounds__(256) void gs_mcmc_move_kernel(GsMcmcRelocateArgs a) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= a.m) return;
@@ -149,12 +95,11 @@ __global__ __launch_bounds__(256) void gs_mcmc_move_kernel(GsMcmcRelocateArgs a)
     const float sc[3] = {a.model[1][3 * s], a.model[1][3 * s + 1], a.model[1][3 * s + 2]};
     float op, so[3];
     gs_mcmc_relocated(a.model[3][s], sc, a.hist[s], a.min_opacity, a.binom, op, so);
-    mcmc_put_row(a.model[0], d, true, s, 3);
-    mcmc_put_row(a.model[2], d, true, s, 4);
-    mcmc_put_row(a.model[4], d, true, s, a.k3);
+#pragma unroll
+    for (int i = 0; i < 5; i += 2) gs_row_put(a.model[i], d, a.model[i], s, gs_row_width(i, a.k3));   // means, quaternion, SH row: inside one array
     a.model[1][3 * d] = so[0]; a.model[1][3 * d + 1] = so[1]; a.model[1][3 * d + 2] = so[2];
     a.model[3][d] = op;
-    mcmc_zero_sets(a, d);
+    gs_rows_zero_sets(a.set, a.nsets, d, a.k3);
 }
 
 __global__ __launch_bounds__(256) void gs_mcmc_source_kernel(GsMcmcRelocateArgs a) {
@@ -167,7 +112,7 @@ __global__ __launch_bounds__(256) void gs_mcmc_source_kernel(GsMcmcRelocateArgs 
     gs_mcmc_relocated(a.model[3][g], sc, c, a.min_opacity, a.binom, op, so);
     a.model[1][3 * g] = so[0]; a.model[1][3 * g + 1] = so[1]; a.model[1][3 * g + 2] = so[2];
     a.model[3][g] = op;
-    mcmc_zero_sets(a, g);
+    gs_rows_zero_sets(a.set, a.nsets, g, a.k3);
 }
 
 __global__ __launch_bounds__(256) void gs_mcmc_noise_kernel(float *__restrict__ means, const float *__restrict__ scales, const float *__restrict__ quats,
@@ -193,30 +138,24 @@ __global__ __launch_bounds__(256) void gs_mcmc_regularize_kernel(const float *__
     }
 }
 
-static bool mcmc_grid(int64_t n, unsigned *blocks) {
-    const int64_t b = (n + 255) / 256;
-    if (b > 0x7fffffffLL) return false;
-    *blocks = (unsigned)b;
-    return true;
-}
-
 hipError_t gs_launch_mcmc_plan(const float *opac, int64_t n, float min_opacity_logit, u64 *chunk_sum, u64 *chunk_off, u64 *totals, u64 *cdf, int32_t *dead,
                                hipStream_t s) {
     const hipError_t e = hipMemsetAsync(totals, 0, 2 * sizeof(u64), s);
     if (e != hipSuccess || n <= 0) return e;
     unsigned blocks;
-    if (!mcmc_grid(n, &blocks)) return hipErrorInvalidValue;
-    const int64_t nchunks = gs_mcmc_chunks(n);
-    hipLaunchKernelGGL(gs_mcmc_weigh_kernel, dim3(blocks), dim3(GS_MCMC_CHUNK), 0, s, opac, n, min_opacity_logit, chunk_sum, nchunks);
-    hipLaunchKernelGGL(gs_mcmc_chunk_scan_kernel, dim3(2), dim3(1024), 0, s, chunk_sum, chunk_off, nchunks, totals);
-    hipLaunchKernelGGL(gs_mcmc_emit_kernel, dim3(blocks), dim3(GS_MCMC_CHUNK), 0, s, opac, n, min_opacity_logit, chunk_off, nchunks, cdf, dead);
+    if (!gs_grid_256(n, &blocks)) return hipErrorInvalidValue;
+    const int64_t nchunks = gs_chunks(n);
+    hipLaunchKernelGGL(gs_mcmc_weigh_kernel, dim3(blocks), dim3(GS_CHUNK), 0, s, opac, n, min_opacity_logit, chunk_sum, nchunks);
+    const hipError_t es = gs_launch_chunk_scan(chunk_sum, chunk_off, nchunks, 2, totals, s);   // (also reports the weigh launch)
+    if (es != hipSuccess) return es;
+    hipLaunchKernelGGL(gs_mcmc_emit_kernel, dim3(blocks), dim3(GS_CHUNK), 0, s, opac, n, min_opacity_logit, chunk_off, nchunks, cdf, dead);
     return hipGetLastError();
 }
 
 hipError_t gs_launch_mcmc_sample(const u64 *cdf, int64_t n, const float *u, int64_t m, int32_t *src, hipStream_t s) {
     if (n <= 0 || m <= 0) return hipSuccess;
     unsigned blocks;
-    if (!mcmc_grid(m, &blocks)) return hipErrorInvalidValue;
+    if (!gs_grid_256(m, &blocks)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gs_mcmc_sample_kernel, dim3(blocks), dim3(256), 0, s, cdf, n, u, m, src);
     return hipGetLastError();
 }
@@ -224,7 +163,7 @@ hipError_t gs_launch_mcmc_sample(const u64 *cdf, int64_t n, const float *u, int6
 hipError_t gs_launch_mcmc_relocate(const GsMcmcRelocateArgs &a, hipStream_t s) {
     if (a.n <= 0 || a.m <= 0) return hipSuccess;
     unsigned bm, bn;
-    if (!mcmc_grid(a.m, &bm) || !mcmc_grid(a.n, &bn) || a.nsets < 0 || a.nsets > GS_DENSITY_MAX_SETS || a.k3 <= 0 || !a.src || !a.dst || !a.hist || !a.binom)
+    if (!gs_grid_256(a.m, &bm) || !gs_grid_256(a.n, &bn) || a.nsets < 0 || a.nsets > GS_DENSITY_MAX_SETS || a.k3 <= 0 || !a.src || !a.dst || !a.hist || !a.binom)
         return hipErrorInvalidValue;
     const hipError_t e = hipMemsetAsync(a.hist, 0, sizeof(int32_t) * (size_t)a.n, s);
     if (e != hipSuccess) return e;
@@ -238,7 +177,7 @@ hipError_t gs_launch_mcmc_noise(float *means, const float *scales, const float *
                                 float gate_t, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     unsigned blocks;
-    if (!mcmc_grid(n, &blocks)) return hipErrorInvalidValue;
+    if (!gs_grid_256(n, &blocks)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gs_mcmc_noise_kernel, dim3(blocks), dim3(256), 0, s, means, scales, quats, opac, z, n, lr, gate_k, gate_t);
     return hipGetLastError();
 }
@@ -247,7 +186,7 @@ hipError_t gs_launch_mcmc_regularize(const float *scales, const float *opac, flo
                                      hipStream_t s) {
     if (n <= 0 || (!d_scales && !d_opac)) return hipSuccess;
     unsigned blocks;
-    if (!mcmc_grid(n, &blocks)) return hipErrorInvalidValue;
+    if (!gs_grid_256(n, &blocks)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gs_mcmc_regularize_kernel, dim3(blocks), dim3(256), 0, s, scales, opac, d_scales, d_opac, n, c_opacity, c_scale);
     return hipGetLastError();
 }

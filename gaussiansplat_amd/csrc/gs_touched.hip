@@ -5,10 +5,10 @@
 // floats has (bit pattern & 0x7fffffff) != 0: +-0 is untouched; denormals, NaN and Inf are touched (the bit pattern is tested, not
 // the float: the denormal mode cannot change the answer).  Bit g % 32 of int32 word g / 32; the bits of the last word beyond n are 0.
 //
-// PACK (one view): ordered compaction WITHOUT any workgroup waiting for another -- three launches over chunks of
-// GS_TOUCHED_CHUNK = 256 gaussians (one workgroup, four wave64 ballots = eight bitmap words):
+// PACK (one view): the ordered compaction of gs_chunk.h -- three launches over chunks of GS_CHUNK = 256 gaussians (one workgroup,
+// four wave64 ballots = eight bitmap words):
 //   gs_touched_mark_kernel     per chunk: ballots -> bitmap words, popcounts -> the chunk's count
-//   gs_touched_scan_kernel     ONE workgroup: exclusive scan of the chunk counts (5 M gaussians = 19.5 k counts, 20 per thread),
+//   gs_launch_chunk_scan       ONE workgroup: exclusive scan of the chunk counts (5 M gaussians = 19.5 k counts, 20 per thread),
 //                              and the total -> *count
 //   gs_touched_scatter_kernel  per chunk: every lane re-derives its rank from the chunk's eight bitmap words and copies its row
 // The source is a caller's dense [n][3] array or the ctx's own 2-D gradient sums (float, or fixed point in deterministic mode,
@@ -19,15 +19,15 @@
 // from three +0 floats otherwise -- the arithmetic of an untouched view is NOT skipped (a non-finite basis times zero must give what the
 // dense path gives), so the result equals gs_sh_from_views_kernel on the unpacked array bit for bit.  Its workgroup covers one
 // chunk, so per view it needs ONE offset and its own eight words, all wave-uniform loads.  A pre-pass of two launches
-// (gs_touched_count_kernel: popcounts per (view, chunk); gs_touched_scan_kernel, one workgroup per view) makes the offsets.
+// (gs_touched_count_kernel: popcounts per (view, chunk); gs_launch_chunk_scan, one workgroup per view) makes the offsets.
 // Nothing is read outside a view's rows_cap rows whatever the bitmap says: bits at positions >= n belong to no thread, and a
 // rank >= rows_cap (a corrupt or truncated gather) reads as a zero row.
 #include "gs_pergaussian.h"   // gs_g2d_rgb_load; gs_sh_views_body.inc keeps its own t and p (this unit contracts, and both kernels share that body)
+#include "gs_chunk.h"
 #include "gs_sh.h"
 #include "gs_wave.h"
 
-static_assert(GS_TOUCHED_CHUNK == 256, "one workgroup of 256 threads (four ballots, eight bitmap words) per chunk");
-#define GS_TOUCHED_WORDS (GS_TOUCHED_CHUNK / 32)
+#define GS_TOUCHED_WORDS (GS_CHUNK / 32)
 
 struct GsColorRowSrc {
     const float *dense;                 // SRC 0: [n][3]
@@ -65,10 +65,10 @@ __device__ __forceinline__ bool touched_rank(const int32_t *__restrict__ bits, i
 }
 
 template <int SRC>
-__global__ __launch_bounds__(GS_TOUCHED_CHUNK) void gs_touched_mark_kernel(GsColorRowSrc src, int64_t n, int32_t *__restrict__ bits, int64_t words,
+__global__ __launch_bounds__(GS_CHUNK) void gs_touched_mark_kernel(GsColorRowSrc src, int64_t n, int32_t *__restrict__ bits, int64_t words,
                                                                             uint32_t *__restrict__ chunk_cnt) {
-    __shared__ int wave_cnt[GS_TOUCHED_CHUNK / 64];
-    const int64_t g = (int64_t)blockIdx.x * GS_TOUCHED_CHUNK + threadIdx.x;
+    __shared__ int wave_cnt[GS_CHUNK_WAVES];
+    const int64_t g = (int64_t)blockIdx.x * GS_CHUNK + threadIdx.x;
     bool t = false;
     if (g < n) {                                                           // lanes past n vote 0: the padding bits of the last word
         float a, b, c;
@@ -83,12 +83,7 @@ __global__ __launch_bounds__(GS_TOUCHED_CHUNK) void gs_touched_mark_kernel(GsCol
     if (lane == 32 && wi + 1 < words) bits[wi + 1] = (int32_t)(uint32_t)(bal >> 32);
     if (lane == 0) wave_cnt[wv] = r.count;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < GS_TOUCHED_CHUNK / 64; ++w) s += wave_cnt[w];
-        chunk_cnt[blockIdx.x] = (uint32_t)s;
-    }
+    if (threadIdx.x == 0) chunk_cnt[blockIdx.x] = (uint32_t)gs_chunk_count(wave_cnt);
 }
 
 // popcounts per (view = blockIdx.y, chunk) of gathered bitmaps [views][words]; bits at positions >= n are ignored
@@ -103,43 +98,10 @@ __global__ __launch_bounds__(256) void gs_touched_count_kernel(const int32_t *__
     if ((threadIdx.x & (GS_TOUCHED_WORDS - 1)) == 0 && chunk < nchunks) chunk_cnt[(int64_t)blockIdx.y * nchunks + chunk] = (uint32_t)p;
 }
 
-// One workgroup per row of `nchunks` counts (blockIdx.x: the pack has one row, the rebuild one per view, a density plan one per
-// class): exclusive prefix sums, and the row's total when `total` is not null.  Every thread sums a contiguous span, the 1024 span
-// sums are scanned in LDS.
-__global__ __launch_bounds__(1024) void gs_touched_scan_kernel(const uint32_t *__restrict__ chunk_cnt, int64_t *__restrict__ chunk_off,
-                                                                int64_t nchunks, int64_t *__restrict__ total) {
-    __shared__ long long s[2][1024];
-    const uint32_t *c = chunk_cnt + (int64_t)blockIdx.x * nchunks;
-    int64_t *o = chunk_off + (int64_t)blockIdx.x * nchunks;
-    const int t = threadIdx.x;
-    const int64_t per = (nchunks + 1023) / 1024;
-    const int64_t lo = min((int64_t)t * per, nchunks), hi = min(lo + per, nchunks);
-    long long sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += c[i];
-    s[0][t] = sum;
-    __syncthreads();
-    int cur = 0;
-    for (int d = 1; d < 1024; d <<= 1) {                                   // reads s[cur], writes s[cur ^ 1]: one barrier per step
-        long long v = s[cur][t];
-        if (t >= d) v += s[cur][t - d];
-        s[cur ^ 1][t] = v;
-        __syncthreads();
-        cur ^= 1;
-    }
-    long long run = s[cur][t] - sum;
-    for (int64_t i = lo; i < hi; ++i) { o[i] = run; run += c[i]; }
-    if (t == 1023 && total) total[blockIdx.x] = s[cur][1023];
-}
-
-hipError_t gs_launch_chunk_scan(const uint32_t *chunk_cnt, int64_t *chunk_off, int64_t nchunks, int rows, int64_t *totals, hipStream_t s) {
-    hipLaunchKernelGGL(gs_touched_scan_kernel, dim3((unsigned)rows), dim3(1024), 0, s, chunk_cnt, chunk_off, nchunks, totals);
-    return hipGetLastError();
-}
-
 template <int SRC>
-__global__ __launch_bounds__(GS_TOUCHED_CHUNK) void gs_touched_scatter_kernel(GsColorRowSrc src, int64_t n, const int32_t *__restrict__ bits, int64_t words,
+__global__ __launch_bounds__(GS_CHUNK) void gs_touched_scatter_kernel(GsColorRowSrc src, int64_t n, const int32_t *__restrict__ bits, int64_t words,
                                                                                const int64_t *__restrict__ chunk_off, float *__restrict__ rows) {
-    const int64_t g = (int64_t)blockIdx.x * GS_TOUCHED_CHUNK + threadIdx.x;
+    const int64_t g = (int64_t)blockIdx.x * GS_CHUNK + threadIdx.x;
     if (g >= n) return;
     uint32_t rank;
     if (!touched_rank(bits, words, blockIdx.x, threadIdx.x, rank)) return;
@@ -169,7 +131,7 @@ struct GsTouchedColorSrc {
 };
 
 template <int DEG, bool OVERWRITE, bool STRIDED = false>
-__global__ __launch_bounds__(GS_TOUCHED_CHUNK) void gs_sh_from_touched_kernel(int64_t n, const float *__restrict__ means, int nviews,
+__global__ __launch_bounds__(GS_CHUNK) void gs_sh_from_touched_kernel(int64_t n, const float *__restrict__ means, int nviews,
                                                                                const float *__restrict__ cams, GsTouchedColorSrc src,
                                                                                float *__restrict__ d_shs, int sh_stride) {
 #define GS_SH_VIEWS_BEGIN const float *gr = src.row(v);      // the integer work first: the arithmetic behind it is then laid out as in the dense kernel
@@ -182,10 +144,10 @@ __global__ __launch_bounds__(GS_TOUCHED_CHUNK) void gs_sh_from_touched_kernel(in
 hipError_t gs_launch_touched_pack(const float *dense, const float *g2d, const long long *g2d_fixed, int64_t n, int32_t *bits, float *rows,
                                   int64_t *count, uint32_t *chunk_cnt, int64_t *chunk_off, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    const int64_t nchunks = gs_touched_chunks(n), words = (n + 31) / 32;
+    const int64_t nchunks = gs_chunks(n), words = (n + 31) / 32;
     if (nchunks > 0x7fffffffLL) return hipErrorInvalidValue;
     const GsColorRowSrc src{dense, g2d, g2d_fixed};
-    const dim3 grid((unsigned)nchunks), block(GS_TOUCHED_CHUNK);
+    const dim3 grid((unsigned)nchunks), block(GS_CHUNK);
 #define GS_TP(K, ...) do { if (dense) hipLaunchKernelGGL(K<0>, grid, block, 0, s, __VA_ARGS__); \
                            else if (g2d_fixed) hipLaunchKernelGGL(K<2>, grid, block, 0, s, __VA_ARGS__); \
                            else hipLaunchKernelGGL(K<1>, grid, block, 0, s, __VA_ARGS__); } while (0)
@@ -201,7 +163,7 @@ hipError_t gs_launch_sh_from_touched(int64_t n, int sh_degree, int sh_stride, co
                                      const float *rows, int64_t rows_cap, uint32_t *chunk_cnt, int64_t *chunk_off, const float *zero3,
                                      float *d_shs, int overwrite, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    const int64_t nchunks = gs_touched_chunks(n), words = (n + 31) / 32;
+    const int64_t nchunks = gs_chunks(n), words = (n + 31) / 32;
     if (nchunks > 0x7fffffffLL || nviews <= 0 || nviews > 65535) return hipErrorInvalidValue;
     // sh_degree: the ACTIVE degree; sh_stride: floats per stored row of d_shs
     return gs_sh_dispatch(sh_degree, sh_stride, [&](auto D, auto S) {
@@ -211,8 +173,8 @@ hipError_t gs_launch_sh_from_touched(int64_t n, int sh_degree, int sh_stride, co
         constexpr int DEG = decltype(D)::value, K = (DEG + 1) * (DEG + 1);
         constexpr bool STRIDED = decltype(S)::value;
         const GsTouchedColorSrc src{bits, rows, chunk_off, zero3, words, nchunks, rows_cap};
-        const dim3 grid((unsigned)nchunks), block(GS_TOUCHED_CHUNK);
-        const size_t lds = sizeof(float) * GS_TOUCHED_CHUNK * (3 * K + 1);
+        const dim3 grid((unsigned)nchunks), block(GS_CHUNK);
+        const size_t lds = sizeof(float) * GS_CHUNK * (3 * K + 1);
         if (overwrite) hipLaunchKernelGGL((gs_sh_from_touched_kernel<DEG, true, STRIDED>), grid, block, lds, s, n, means, nviews, cams, src, d_shs, sh_stride);
         else hipLaunchKernelGGL((gs_sh_from_touched_kernel<DEG, false, STRIDED>), grid, block, lds, s, n, means, nviews, cams, src, d_shs, sh_stride);
         return hipGetLastError();

@@ -109,11 +109,6 @@ class DensityStats:
         r._end()
 
 
-def _flat_struct(flat, offsets) -> B.GsGrads:
-    base = flat.data_ptr()
-    return B.GsGrads(*(base + 4 * o for o in offsets))
-
-
 def densify_and_prune(renderer, stats: DensityStats, optimizer=None, *, scene_extent, grad_threshold=2e-4, percent_dense=0.01,
                       min_opacity=0.005, max_world_fraction=0.1, max_extent_px=0, generator=None, max_gaussians=None) -> dict:
     """Clone, split and prune by the statistics of the window, on the device; returns dict(survivors, clones, splits, pruned, n).
@@ -124,11 +119,7 @@ def densify_and_prune(renderer, stats: DensityStats, optimizer=None, *, scene_ex
     generator: the torch.Generator the normals of the split are drawn from (n x 2 x 3 of them, whatever is split)."""
     import torch
     _require_3d(renderer, "densify_and_prune")
-    if getattr(renderer, "_shares_grads", False):
-        raise ValueError("densify_and_prune: this renderer accumulates into another renderer's gradient buffer (share_grads_with); "
-                         "restructure the renderer that owns it and rebuild this one")
-    if optimizer is not None and optimizer.renderer is not renderer:
-        raise ValueError("densify_and_prune: the optimiser belongs to another renderer")
+    renderer.check_resize(optimizer, "densify_and_prune")
     if max_gaussians is not None and int(max_gaussians) < 1:
         raise ValueError(f"density: max_gaussians must be >= 1 or None, got {max_gaussians}")
     kw = dict(scene_extent=scene_extent, percent_dense=percent_dense, min_opacity=min_opacity, max_world_fraction=max_world_fraction,
@@ -137,8 +128,7 @@ def densify_and_prune(renderer, stats: DensityStats, optimizer=None, *, scene_ex
     n = renderer.nGaussians
     if stats.grad_sum.numel() != n:
         raise ValueError("densify_and_prune: stats do not match the renderer's number of gaussians")
-    d = renderer.splatData
-    dev = d.means.device
+    dev = renderer.splatData.means.device
     ctx = renderer.ctx
     renderer._begin()
     action = torch.empty(n, dtype=torch.int32, device=dev)
@@ -152,28 +142,13 @@ def densify_and_prune(renderer, stats: DensityStats, optimizer=None, *, scene_ex
         n_out = survivors + clones + 2 * splits
     gdev = generator.device if generator is not None else dev
     noise = torch.randn((n, 2, 3), generator=generator, device=gdev, dtype=torch.float32).to(dev).contiguous()
-    k3 = d.shs.shape[1]
-    new = R.SplatData3D(means=torch.empty((n_out, 3), dtype=torch.float32, device=dev), scales=torch.empty((n_out, 3), dtype=torch.float32, device=dev),
-                        shs=torch.empty((n_out, k3), dtype=torch.float32, device=dev), quaternions=torch.empty((n_out, 4), dtype=torch.float32, device=dev),
-                        opacities=torch.empty((n_out, 1), dtype=torch.float32, device=dev), features=d.features)
-    grads = R.initGrads(new)
-    # the flat initGrads layout depends on n: the moments move into new flat buffers, five pointers into each
-    new_off = tuple((v.data_ptr() - grads.flat.data_ptr()) // 4 for v in (grads.Δmeans, grads.Δscales, grads.Δquaternions, grads.Δopacities, grads.Δshs))
+    new = renderer.alloc_model(n_out, zero=False)                # every row is written by the restructure
     src_sets, dst_sets, moments = [], [], ()
-    if optimizer is not None:
-        moments = (torch.empty_like(grads.flat), torch.empty_like(grads.flat))
-        src_sets = [optimizer._struct(optimizer.exp_avg), optimizer._struct(optimizer.exp_avg_sq)]
-        dst_sets = [_flat_struct(m, new_off) for m in moments]
-    ptrs = [t.data_ptr() for t in (new.means, new.scales, new.quaternions, new.opacities, new.shs)]
-    ctx.density_restructure(action.data_ptr(), noise.data_ptr(), B.GsGrads(*ptrs), src_sets, dst_sets, n_out)
-    # the old arrays stay referenced until here; torch frees them in stream order behind the kernel that read them
-    renderer.splatData = new
-    renderer.nGaussians = n_out
-    renderer._splatGrads = grads
-    renderer._grads_lazy_zero = False
-    renderer._grads = B.GsGrads(grads.Δmeans.data_ptr(), grads.Δscales.data_ptr(), grads.Δquaternions.data_ptr(), grads.Δopacities.data_ptr(),
-                                grads.Δshs.data_ptr())
-    ctx.set_model_device(n_out, renderer.sh_degree, ptrs)
+    if optimizer is not None:                                   # the flat layout depends on n: the moments move into new flat buffers
+        *moments, dst_sets = optimizer.resized_moments(n_out, zero=False)
+        src_sets = optimizer.moment_structs()
+    ctx.density_restructure(action.data_ptr(), noise.data_ptr(), B.GsGrads(*(t.data_ptr() for t in R.model_arrays(new))), src_sets, dst_sets, n_out)
+    renderer.adopt_model(new, "densify_and_prune")
     renderer._end()
     if optimizer is not None:
         optimizer._rebind(*moments)
@@ -189,8 +164,7 @@ def reset_opacity(renderer, optimizer=None, opacity: float = 0.01):
     if optimizer is not None:
         if optimizer.renderer is not renderer:
             raise ValueError("reset_opacity: the optimiser belongs to another renderer")
-        m = optimizer.exp_avg.data_ptr() + 4 * optimizer._offsets[3]
-        v = optimizer.exp_avg_sq.data_ptr() + 4 * optimizer._offsets[3]
+        m, v = optimizer.moment_ptrs("opacities")
     renderer._begin()
     renderer.ctx.opacity_reset(logit(p), m, v)
     renderer._end()

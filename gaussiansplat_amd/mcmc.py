@@ -21,9 +21,8 @@ from __future__ import annotations
 
 import math
 
-from . import backend as B
 from . import renderer as R
-from .density import _flat_struct, _positive, _probability, _require_3d, logit
+from .density import _positive, _probability, _require_3d, logit
 
 
 def _plan(renderer, min_opacity: float):
@@ -54,7 +53,7 @@ def _moment_sets(renderer, optimizer, who: str):
         return []
     if optimizer.renderer is not renderer:
         raise ValueError(f"{who}: the optimiser belongs to another renderer")
-    return [optimizer._struct(optimizer.exp_avg), optimizer._struct(optimizer.exp_avg_sq)]
+    return optimizer.moment_structs()
 
 
 def relocate(renderer, optimizer=None, *, min_opacity=0.005, generator=None) -> dict:
@@ -81,11 +80,7 @@ def grow(renderer, optimizer=None, *, cap_max, growth=1.05, min_opacity=0.005, g
     Returns dict(n, added, src)."""
     import torch
     _require_3d(renderer, "grow")
-    if getattr(renderer, "_shares_grads", False):
-        raise ValueError("densify_and_prune: this renderer accumulates into another renderer's gradient buffer (share_grads_with); "
-                         "restructure the renderer that owns it and rebuild this one")
-    if optimizer is not None and optimizer.renderer is not renderer:
-        raise ValueError("densify_and_prune: the optimiser belongs to another renderer")
+    renderer.check_resize(optimizer, "grow")
     if isinstance(cap_max, bool) or not isinstance(cap_max, int) or cap_max < 1:
         raise ValueError(f"mcmc: cap_max must be an integer >= 1, got {cap_max!r}")
     g = _positive("growth", growth)
@@ -98,38 +93,16 @@ def grow(renderer, optimizer=None, *, cap_max, growth=1.05, min_opacity=0.005, g
     if total == 0:                                               # nobody is alive: nothing to draw from
         return dict(n=n, added=0, src=None)
     src = _draw(renderer, cdf, added, generator)
-    d = renderer.splatData
-    dev = d.means.device
-    ctx = renderer.ctx
     n_out = n + added
-
-    def longer(t):                                               # the first n rows copied on the device, the new ones +0 until the relocation fills them
-        out = torch.zeros((n_out,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
-        out[:n].copy_(t)
-        return out
-    new = R.SplatData3D(means=longer(d.means), scales=longer(d.scales), shs=longer(d.shs), quaternions=longer(d.quaternions),
-                        opacities=longer(d.opacities), features=d.features)
-    grads = R.initGrads(new)
-    views = (grads.Δmeans, grads.Δscales, grads.Δquaternions, grads.Δopacities, grads.Δshs)
-    new_off = tuple((v.data_ptr() - grads.flat.data_ptr()) // 4 for v in views)
+    new = renderer.alloc_model(n_out, zero=True)                 # the first n rows copied on the device, the new ones +0 until the relocation fills them
+    for t_new, t_old in zip(R.model_arrays(new), R.model_arrays(renderer.splatData)):
+        t_new[:n].copy_(t_old)
     moments, sets = (), []
     if optimizer is not None:
-        moments = (torch.zeros_like(grads.flat), torch.zeros_like(grads.flat))
-        for old, m in zip((optimizer.exp_avg, optimizer.exp_avg_sq), moments):
-            for o_old, o_new, v in zip(optimizer._offsets, new_off, views):
-                w = v.numel() // n_out
-                m[o_new:o_new + n * w].copy_(old[o_old:o_old + n * w])
-        sets = [_flat_struct(m, new_off) for m in moments]
-    ptrs = [t.data_ptr() for t in (new.means, new.scales, new.quaternions, new.opacities, new.shs)]
-    ctx.set_model_device(n_out, renderer.sh_degree, ptrs)
-    dst = torch.arange(n, n_out, dtype=torch.int32, device=dev)
-    ctx.mcmc_relocate(src.data_ptr(), dst.data_ptr(), added, mo, sets)
-    # the old arrays stay referenced until here; torch frees them in stream order behind the copies that read them
-    renderer.splatData = new
-    renderer.nGaussians = n_out
-    renderer._splatGrads = grads
-    renderer._grads_lazy_zero = False
-    renderer._grads = B.GsGrads(*(v.data_ptr() for v in views))
+        *moments, sets = optimizer.resized_moments(n_out, zero=True, keep_rows=n)
+    renderer.adopt_model(new, "grow")
+    dst = torch.arange(n, n_out, dtype=torch.int32, device=new.means.device)
+    renderer.ctx.mcmc_relocate(src.data_ptr(), dst.data_ptr(), added, mo, sets)
     renderer._end()
     if optimizer is not None:
         optimizer._rebind(*moments)

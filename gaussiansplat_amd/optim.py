@@ -16,14 +16,14 @@ from __future__ import annotations
 import math
 
 from . import backend as B
+from . import renderer as R
 
 GROUPS_3D = ("means", "scales", "quaternions", "opacities", "sh_dc", "sh_rest")
 GROUPS_2D = ("means", "scales", "rotations", "opacities", "colors")     # colors -> lr[4]; lr[5] unused
 
 
 def _is_2d(renderer) -> bool:
-    from .renderer import GaussianRenderer2D
-    return isinstance(renderer, GaussianRenderer2D)
+    return isinstance(renderer, R.GaussianRenderer2D)
 
 
 def _check_rate(name: str, value) -> float:
@@ -97,12 +97,8 @@ class Adam:
         flat = renderer._splatGrads.flat
         self.exp_avg = torch.zeros_like(flat)
         self.exp_avg_sq = torch.zeros_like(flat)
-        g = renderer._splatGrads
-        views = (g.Δmeans, g.Δscales, g.Δrotations, g.Δopacities, g.Δcolors) if self.is_2d else \
-                (g.Δmeans, g.Δscales, g.Δquaternions, g.Δopacities, g.Δshs)
-        # floats from the start of the flat buffer to each of the five arrays (the initGrads layout)
-        self._offsets = tuple((v.data_ptr() - flat.data_ptr()) // 4 for v in views)
-        self._numel = flat.numel()
+        # floats from the start of the flat buffer to each of the five arrays, and its length (the initGrads layout)
+        self._offsets, self._numel = R.layout_of(renderer._splatGrads)
 
     @classmethod
     def for_3dgs(cls, renderer, scene_extent: float, selective: bool = False, fused: bool = False) -> "Adam":
@@ -139,8 +135,16 @@ class Adam:
 
     # -- the buffers of the C ABI
     def _struct(self, flat) -> B.GsGrads:
-        base = flat.data_ptr()
-        return B.GsGrads(*(base + 4 * o for o in self._offsets))
+        return R.grads_struct(flat, self._offsets)
+
+    def moment_structs(self) -> list:
+        """[exp_avg, exp_avg_sq] as the gradient-shaped companion sets of a call that moves rows (density, mcmc)."""
+        return [self._struct(self.exp_avg), self._struct(self.exp_avg_sq)]
+
+    def moment_ptrs(self, group: str) -> tuple:
+        """(exp_avg, exp_avg_sq) device pointers of one parameter group's array (sh_dc and sh_rest share the SH rows)."""
+        o = 4 * self._offsets[min(self.groups.index(group), 4)]
+        return self.exp_avg.data_ptr() + o, self.exp_avg_sq.data_ptr() + o
 
     def _grads_struct(self, grads) -> B.GsGrads:
         import torch
@@ -191,17 +195,29 @@ class Adam:
         r._end()
         self.step_count = t
 
+    # -- the number of gaussians changes (renderer.adopt_model): moment buffers of the new size first, _rebind once the renderer has adopted
+    def resized_moments(self, n_out: int, zero: bool, keep_rows: int = 0) -> tuple:
+        """(exp_avg, exp_avg_sq, structs) for a model of n_out gaussians: two flat buffers in the layout the renderer's gradient buffer
+        will have -- zeros, or uninitialised for a call that writes every row -- and their gs_grads.  keep_rows: that many leading rows
+        of every array are copied from the present moments, on the device."""
+        import torch
+        widths = [v.shape[1] for v in R.grads_views(self.renderer._splatGrads)]
+        offsets, total = R.grads_layout(widths, n_out)
+        make = torch.zeros if zero else torch.empty
+        new = [make(total, dtype=self.exp_avg.dtype, device=self.exp_avg.device) for _ in range(2)]
+        for old, m in zip((self.exp_avg, self.exp_avg_sq), new) if keep_rows else ():
+            for o_old, o_new, w in zip(self._offsets, offsets, widths):
+                m[o_new:o_new + keep_rows * w].copy_(old[o_old:o_old + keep_rows * w])
+        return new[0], new[1], [R.grads_struct(m, offsets) for m in new]
+
     def _rebind(self, exp_avg, exp_avg_sq):
-        """The number of gaussians changed (density.densify_and_prune): take the restructured moment buffers and re-read the
-        layout from the renderer's new gradient buffer.  step_count stays: the bias corrections are a property of the run."""
+        """The renderer adopted a model of another size: take the moment buffers made for it and its gradient buffer's layout.
+        step_count stays: the bias corrections are a property of the run."""
         flat = self.renderer._splatGrads.flat
         for t in (exp_avg, exp_avg_sq):
             if t.numel() != flat.numel() or t.dtype != flat.dtype or t.device != flat.device or not t.is_contiguous():
                 raise ValueError("Adam._rebind: the moment buffers must match the renderer's flat gradient buffer")
-        g = self.renderer._splatGrads
-        views = (g.Δmeans, g.Δscales, g.Δquaternions, g.Δopacities, g.Δshs)
-        self._offsets = tuple((v.data_ptr() - flat.data_ptr()) // 4 for v in views)
-        self._numel = flat.numel()
+        self._offsets, self._numel = R.layout_of(self.renderer._splatGrads)
         self.exp_avg, self.exp_avg_sq = exp_avg, exp_avg_sq
 
     # -- checkpoints

@@ -74,32 +74,58 @@ class SplatGrads2D:                     # splat.jl:28-34 -- views into ONE flat 
     Δcolors: "torch.Tensor"
 
 
+def grads_layout(widths, n: int):
+    """The layout of a flat gradient buffer, in floats: array i holds widths[i] floats per gaussian and starts at offsets[i], the arrays
+    stand behind one another.  Returns (offsets, total).  Pure: everything that needs an offset asks here (initGrads, optim.Adam)."""
+    offsets, o = [], 0
+    for w in widths:
+        offsets.append(o); o += int(w) * int(n)
+    return tuple(offsets), o
+
+
+def grads_views(grads) -> tuple:
+    """The five views of a SplatGrads3D / SplatGrads2D in the order of the C ABI's gs_grads."""
+    if isinstance(grads, SplatGrads2D):
+        return grads.Δmeans, grads.Δscales, grads.Δrotations, grads.Δopacities, grads.Δcolors
+    return grads.Δmeans, grads.Δscales, grads.Δquaternions, grads.Δopacities, grads.Δshs
+
+
+def layout_of(grads):
+    """grads_layout of the buffer a SplatGrads3D / SplatGrads2D views."""
+    views = grads_views(grads)
+    return grads_layout([v.shape[1] for v in views], views[0].shape[0])
+
+
+def grads_struct(flat, offsets) -> B.GsGrads:
+    """Five pointers into a flat buffer of the layout `offsets` (the gradient buffer itself, or Adam's moments)."""
+    base = flat.data_ptr()
+    return B.GsGrads(*(base + 4 * o for o in offsets))
+
+
+def _zero_flat(widths, n, device):
+    import torch
+    offsets, total = grads_layout(widths, n)
+    flat = torch.zeros(total, dtype=torch.float32, device=device)
+    return flat, [flat[o:o + w * n].view(n, w) for o, w in zip(offsets, widths)]
+
+
 def initGrads2D(splatData: SplatData2D) -> SplatGrads2D:
     """initGrads(::SplatData2D), splat.jl:121-135, as one flat buffer [Δmeans 2N | Δscales 2N | Δrot N | Δopac N | Δcolors 3N]."""
-    import torch
-    n = splatData.means.shape[0]
-    sizes = [2 * n, 2 * n, n, n, 3 * n]
-    flat = torch.zeros(sum(sizes), dtype=torch.float32, device=splatData.means.device)
-    parts, o = [], 0
-    for sz in sizes:
-        parts.append(flat[o:o + sz]); o += sz
-    return SplatGrads2D(flat, parts[0].view(n, 2), parts[1].view(n, 2), parts[2].view(n, 1), parts[3].view(n, 1), parts[4].view(n, 3))
+    flat, views = _zero_flat((2, 2, 1, 1, 3), splatData.means.shape[0], splatData.means.device)
+    return SplatGrads2D(flat, *views)
 
 
 def initGrads(splatData: SplatData3D) -> SplatGrads3D:
     """splat.jl:137-156; laid out as one flat fp32 buffer
     [Δmeans 3N | Δscales 3N | Δquats 4N | Δopac N | Δshs 3K·N] so that a multi-view step needs a
     single RCCL all-reduce."""
-    import torch
-    n = splatData.means.shape[0]
-    k3 = splatData.shs.shape[1]
-    sizes = [3 * n, 3 * n, 4 * n, n, k3 * n]
-    flat = torch.zeros(sum(sizes), dtype=torch.float32, device=splatData.means.device)
-    parts, o = [], 0
-    for s in sizes:
-        parts.append(flat[o:o + s]); o += s
-    return SplatGrads3D(flat, parts[0].view(n, 3), parts[1].view(n, 3), parts[2].view(n, 4), parts[3].view(n, 1),
-                        parts[4].view(n, k3))
+    flat, views = _zero_flat((3, 3, 4, 1, splatData.shs.shape[1]), splatData.means.shape[0], splatData.means.device)
+    return SplatGrads3D(flat, *views)
+
+
+def model_arrays(splatData: SplatData3D) -> tuple:
+    """The five arrays of a model in the order of the C ABI (gs_set_model, gs_grads)."""
+    return splatData.means, splatData.scales, splatData.quaternions, splatData.opacities, splatData.shs
 
 
 class GaussianRenderer3D:               # renderer.jl:205-219
@@ -111,15 +137,11 @@ class GaussianRenderer3D:               # renderer.jl:205-219
         share_grads_with: another GaussianRenderer3D over the same splatData whose gradient buffer this one accumulates into
         (a second view in flight, distributed.HipViewRenderer): no buffer of its own is allocated."""
         import torch
-        self.splatData = splatData
-        self._splatGrads = share_grads_with._splatGrads if share_grads_with is not None else initGrads(splatData)
-        self._shares_grads = share_grads_with is not None   # (density.densify_and_prune replaces the buffer: only its owner may)
-        self._grads_lazy_zero = False       # resetGrads() pending: the next backward overwrites
+        self._shares_grads = share_grads_with is not None   # (a resize replaces the buffer: only its owner may, check_resize)
         W, H = int(imgSize[0]), int(imgSize[1])
         dev = splatData.means.device
         self.imageData = torch.zeros((3, H, W), dtype=torch.float32, device=dev)      # CUDA.zeros(imgSize...)
         self.transmittance = torch.ones((H, W), dtype=torch.float32, device=dev)      # CUDA.ones(imgSize[1:2])
-        self.nGaussians = splatData.means.shape[0]
         self.sh_degree = sh_degree
         self.camera: Camera | None = None
         self.ctx = B.Context(device=device, order=order, t_min=t_min, export_debug=export_debug, profile_stages=profile_stages,
@@ -128,14 +150,44 @@ class GaussianRenderer3D:               # renderer.jl:205-219
         # op: no cross-stream fences, so consecutive calls run back to back on the GPU
         self._stream_handle = None
         self._begin()
-        self.ctx.set_model_device(self.nGaussians, sh_degree,
-                                  [t.data_ptr() for t in (splatData.means, splatData.scales, splatData.quaternions,
-                                                          splatData.opacities, splatData.shs)])
-        g = self._splatGrads
-        self._grads = B.GsGrads(g.Δmeans.data_ptr(), g.Δscales.data_ptr(), g.Δquaternions.data_ptr(),
-                                g.Δopacities.data_ptr(), g.Δshs.data_ptr())
+        self._set_model(splatData, share_grads_with._splatGrads if share_grads_with is not None else None)
         if background is not None:
             self.background = background
+
+    # -- the model and its size.  These three methods are the only code that assigns splatData, nGaussians, _splatGrads, _grads_lazy_zero
+    # and _grads: a strategy that changes the number of gaussians allocates with alloc_model, fills the arrays through the
+    # library and hands them to adopt_model; optim.Adam follows with resized_moments / _rebind
+    def _set_model(self, splatData: SplatData3D, shared_grads=None):
+        self.splatData = splatData
+        self.nGaussians = splatData.means.shape[0]
+        self._splatGrads = shared_grads if shared_grads is not None else initGrads(splatData)
+        self._grads_lazy_zero = False       # True: resetGrads() pending, the next backward overwrites
+        self._grads = grads_struct(self._splatGrads.flat, layout_of(self._splatGrads)[0])
+        self.ctx.set_model_device(self.nGaussians, self.sh_degree, [t.data_ptr() for t in model_arrays(splatData)])
+
+    def check_resize(self, optimizer, who: str):
+        """A call that changes the number of gaussians needs the renderer that owns its gradient buffer, and that renderer's optimiser."""
+        if self._shares_grads:
+            raise ValueError(f"{who}: this renderer accumulates into another renderer's gradient buffer (share_grads_with); "
+                             "restructure the renderer that owns it and rebuild this one")
+        if optimizer is not None and optimizer.renderer is not self:
+            raise ValueError(f"{who}: the optimiser belongs to another renderer")
+
+    def alloc_model(self, n_out: int, zero: bool) -> SplatData3D:
+        """Five arrays of n_out rows like the model's own (dtype, device, SH row; `features` carried over): zeros, or uninitialised for a
+        call that writes every row."""
+        import torch
+        make = torch.zeros if zero else torch.empty
+        d = self.splatData
+        new = lambda t: make((int(n_out),) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+        return SplatData3D(means=new(d.means), scales=new(d.scales), shs=new(d.shs), quaternions=new(d.quaternions), opacities=new(d.opacities),
+                           features=d.features)
+
+    def adopt_model(self, new_data: SplatData3D, who: str):
+        """new_data becomes the model: a fresh zero gradient buffer of its size, and gs_set_model on the bound stream.  The arrays replaced
+        stay referenced until here; torch frees them in stream order behind the kernels that read them."""
+        self.check_resize(None, who)
+        self._set_model(new_data)
 
     @property
     def background(self) -> tuple:
@@ -232,6 +284,7 @@ class GaussianRenderer2D:               # renderer.jl:7-18
         self.splatData = splatData
         self._splatGrads = initGrads2D(splatData)
         self._grads_lazy_zero = False
+        self._grads = grads_struct(self._splatGrads.flat, layout_of(self._splatGrads)[0])
         W, H = int(imgSize[0]), int(imgSize[1])
         dev = splatData.means.device
         self.imageData = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
@@ -244,9 +297,6 @@ class GaussianRenderer2D:               # renderer.jl:7-18
         self._begin()
         self.ctx.set_model_2d_device(self.nGaussians, [t.data_ptr() for t in (splatData.means, splatData.scales, splatData.rotations,
                                                                               splatData.opacities, splatData.colors)])
-        g = self._splatGrads
-        self._grads = B.GsGrads(g.Δmeans.data_ptr(), g.Δscales.data_ptr(), g.Δrotations.data_ptr(), g.Δopacities.data_ptr(),
-                                g.Δcolors.data_ptr())
         if background is not None:
             self.background = background
 

@@ -75,7 +75,7 @@ def _opacity_cases(n, seed):
 
 
 # ---------------------------------------------------------------- plan
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 4097, 70001])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 4097, 70001, 262145])   # 262145: 1025 chunks, two words per scan thread, half of the spans empty
 def test_plan_matches_the_reference_bit_for_bit(n):
     r = _renderer(n, 0, seed=n)
     for name, o in _opacity_cases(n, n).items():

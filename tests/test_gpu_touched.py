@@ -20,8 +20,8 @@ W, H = 160, 112
 
 def _chunk():
     from gaussiansplat_amd import backend as B
-    src = open(os.path.join(ROOT, "gaussiansplat_amd", "csrc", "gs_common.h")).read()
-    assert int(re.search(r"#define GS_TOUCHED_CHUNK (\d+)", src).group(1)) == B.TOUCHED_CHUNK
+    src = open(os.path.join(ROOT, "gaussiansplat_amd", "csrc", "gs_chunk.h")).read()
+    assert int(re.search(r"#define GS_CHUNK (\d+)", src).group(1)) == B.TOUCHED_CHUNK
     return B.TOUCHED_CHUNK
 
 

@@ -12,7 +12,8 @@ record no gradients (C1_small_float_atomics; tile_clock: counts only), so every 
 blake2b digest of their bytes.  A call the library refuses is recorded with its message: the refusal must be alike on both sides.
 Per frame: image, T, the five gradient arrays, tile ranges, sorted ids, sortIdxs, num_instances / _coarse_instances / _rounds,
 bin_path_of_frame, list_stats, work_counters_ex; and the counting words of the composite kernels' debug record on one small frame.
-The per-gaussian kernels beyond a frame: a density cycle (statistics, actions, plan, the restructured model and one moment set), the
+The per-gaussian kernels beyond a frame: a density cycle (statistics, actions, plan, the restructured model and one moment set), the five
+MCMC calls (plan at n = 1000 and at 1025 chunks, draws, a relocation from the plan and one onto an explicit dst at degree 3, noise, regularisers), the
 touched-rows pack of two views and the SH gradients rebuilt from them, one fused backward + Adam step dense and selective (parameters
 and moments), a frame at active SH degree 1 of a stored degree 3, and the backward's forms at n = 300 (two workgroups, the second's last wave partly past n):
 stored = active degree 0 .. 3 and active 0 of stored 3, each over two views on one set of gradient buffers (overwriting, then accumulating),
@@ -271,6 +272,83 @@ def case_density(R):
     ctx.close()
 
 
+def case_mcmc(R):
+    """The five MCMC calls.  Plan at n = 1000 (four chunks) and n = 262145 (1025 chunks: two words per scan thread, half of the threads with an empty
+    span), a tenth of the opacities dead; 500 draws; a relocation from the plan with one moment set; one onto an explicit dst at SH degree 3 (16-byte
+    rows); noise and the regularisers at n = 300"""
+    import torch
+    from gaussiansplat_amd import backend as B
+    from gaussiansplat_amd.density import logit
+    G = lambda ts: B.GsGrads(*[t.data_ptr() for t in ts])
+    min_opacity = 0.005
+
+    def planned(n, deg, seed):
+        model, W, H = small_scene(n, deg, seed)
+        g = torch.Generator("cuda").manual_seed(seed + 1)
+        model[3][torch.randperm(n, device="cuda", generator=g)[:max(n // 10, 1)]] = -8.0
+        ctx = device_ctx(model, n, deg, W, H)
+        cdf, dead = torch.zeros(n, dtype=torch.int64, device="cuda"), torch.full((n,), -1, dtype=torch.int32, device="cuda")
+        counts = ctx.mcmc_plan(logit(min_opacity), cdf.data_ptr(), dead.data_ptr())
+        assert counts[1] == max(n // 10, 1) and counts[0] + counts[1] == n and counts[2] > 0, ("mcmc: the plan needs dead and live gaussians", counts)
+        return model, ctx, g, cdf, dead, counts
+
+    def draw(ctx, g, cdf, n, m):
+        u = torch.rand(m, device="cuda", generator=g)
+        src = torch.full((m,), -1, dtype=torch.int32, device="cuda")
+        ctx.mcmc_sample(cdf.data_ptr(), n, u.data_ptr(), m, src.data_ptr())
+        return src
+
+    def put_model(tag, ctx, model, moments):
+        ctx.synchronize()
+        for k, v in host(model).items():
+            R.put(tag + "/model." + k, v)
+        for k, v in host(moments).items():
+            R.put(tag + "/moments." + k, v)
+
+    for n in (1000, 262145):
+        model, ctx, g, cdf, dead, counts = planned(n, 1, 581)
+        ctx.synchronize()
+        tag = "mcmc_n%d" % n
+        R.put(tag + "/counts", counts); R.put(tag + "/cdf", cdf.cpu().numpy()); R.put(tag + "/dead", dead.cpu().numpy()[:counts[1]])
+        if n == 1000:
+            src = draw(ctx, g, cdf, n, 500)
+            ctx.synchronize()
+            R.put(tag + "/sample_500", src.cpu().numpy())
+            src = draw(ctx, g, cdf, n, counts[1])
+            moments = [torch.randn(t.shape, device="cuda", generator=g) for t in model]
+            ctx.mcmc_relocate(src.data_ptr(), None, counts[1], min_opacity, [G(moments)])
+            R.put(tag + "/relocate_src", src.cpu().numpy())
+            put_model(tag + "/relocate", ctx, model, moments)
+        ctx.close()
+    # an explicit dst at degree 3: the last 50 rows take copies of sources drawn from the plan (dead rows among them: a draw never names one)
+    n = 1000
+    model, ctx, g, cdf, dead, counts = planned(n, 3, 583)
+    src = draw(ctx, g, cdf, n, 50)
+    dst = torch.arange(n - 50, n, dtype=torch.int32, device="cuda")
+    keep_rows = ~torch.isin(src.long(), dst.long())              # destinations are no sources by contract: such a draw becomes a no-op (-1)
+    src = torch.where(keep_rows, src, torch.full_like(src, -1))
+    moments = [torch.randn(t.shape, device="cuda", generator=g) for t in model]
+    ctx.mcmc_relocate(src.data_ptr(), dst.data_ptr(), 50, min_opacity, [G(moments)])
+    R.put("mcmc_dst_degree_3/src", src.cpu().numpy())
+    put_model("mcmc_dst_degree_3", ctx, model, moments)
+    ctx.close()
+    n = 300
+    model, W, H = small_scene(n, 1, 585)
+    ctx = device_ctx(model, n, 1, W, H)
+    g = torch.Generator("cuda").manual_seed(586)
+    z = torch.randn((n, 3), device="cuda", generator=g)
+    model[3][:60] = -8.0                                         # the gate opens for transparent gaussians only
+    before = model[0].clone()
+    ctx.mcmc_noise(z.data_ptr(), 80.0, 100.0, 0.005)
+    grads = [torch.randn(t.shape, device="cuda", generator=g) for t in model]
+    ctx.mcmc_regularize(G(grads), 0.01 / n, 0.01 / (3 * n))
+    ctx.synchronize()
+    assert not torch.equal(before, model[0]), "mcmc: the noise moved nothing"
+    R.put("mcmc_noise_n300/means", model[0].cpu().numpy())
+    R.put("mcmc_regularize_n300/d_scales", grads[1].cpu().numpy()); R.put("mcmc_regularize_n300/d_opacities", grads[3].cpu().numpy())
+    ctx.close()
+
+
 def case_touched(R):
     """color_rows_pack of two views' own gradient sums, then sh_grads_from_touched on the gathered pair, n = 1000"""
     import torch
@@ -457,6 +535,7 @@ def record(path):
     case_empty(R)
     case_tile_clock(R)
     case_density(R)
+    case_mcmc(R)
     case_touched(R)
     case_adam(R)
     case_active_degree(R)

@@ -82,7 +82,7 @@ def main():
 
     def restructure():
         r.ctx.density_plan(act.data_ptr())
-        return timed(lambda: r.ctx.density_restructure(act.data_ptr(), noise.data_ptr(), g(dst), [opt._struct(opt.exp_avg), opt._struct(opt.exp_avg_sq)],
+        return timed(lambda: r.ctx.density_restructure(act.data_ptr(), noise.data_ptr(), g(dst), opt.moment_structs(),
                                                        [g(dst_m[0]), g(dst_m[1])], n_out))
 
     variants = [("iter_adam", lambda: iteration(False)), ("iter_adam_accumulate", lambda: iteration(True)), ("accumulate", accumulate),

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Same device code?  tools/isa_same.py PARENT.s NEW.s
+"""Same device code?  tools/isa_same.py PARENT.s NEW.s [PARENT_NAME=NEW_NAME ...]
 
-Both files: the gfx950 assembly of one translation unit (hipcc --save-temps, or -S --cuda-device-only) built with build.py's flags.
+Both files: the gfx950 assembly of one translation unit (hipcc --save-temps, or -S --cuda-device-only) built with build.py's flags, or of several
+behind one another when a kernel moved to another unit; a kernel that changed its (mangled) name is compared under the new one.
 One line per kernel.  A kernel is `same` when the sequence of its instruction mnemonics and its .amdhsa_next_free_vgpr,
 .amdhsa_next_free_sgpr, .amdhsa_private_segment_fixed_size and .amdhsa_group_segment_fixed_size equal the parent's: register names,
 block labels and comments may differ.  A kernel whose mnemonics differ is said to have `moved` when the multiset of its mnemonics is the parent's
@@ -42,7 +43,8 @@ def is_clk(name):                                                   # composite_
     return bool(m) and re.findall(r"L[bi](\d+)E", m.group(2))[3 if m.group(1) == "fwd" else 4] == "1"
 
 
-old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+rename = dict(a.split("=", 1) for a in sys.argv[3:])                # a kernel that became another: further arguments PARENT_NAME=NEW_NAME
+old, new = {rename.get(k, k): v for k, v in kernels(sys.argv[1]).items()}, kernels(sys.argv[2])
 bad = 0
 for name in sorted(set(old) | set(new)):
     o, n = old.get(name), new.get(name)

@@ -94,7 +94,7 @@ def one_size(n, reps):
                 t[dead] = t[src]
             rows = torch.cat([dead, (cnt > 0).nonzero()[:, 0]])
             for m in moments:
-                for off, t in zip(opt._offsets, (d.means, d.scales, d.quaternions, d.opacities, d.shs)):
+                for off, t in zip(R.layout_of(r._splatGrads)[0], (d.means, d.scales, d.quaternions, d.opacities, d.shs)):
                     m[off:off + t.numel()].view(t.shape)[rows] = 0.0
         return timed(go)
 
