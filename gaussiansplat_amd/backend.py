@@ -7,42 +7,29 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSPLAT_HIP_LIB") or os.path.join(_HERE, "lib", "libgsplat_hip.so")   # override: diagnostic builds
 
+# Every integer below states a value of include/gsplat.h (or, where the comment says so, of a csrc/ header); tests/test_abi.py reads the
+# headers and compares each one, and fails on an integer constant of this module that it cannot place.
 GS_MEM_HOST, GS_MEM_DEVICE = 0, 1
-ORDER_INDEX, ORDER_DEPTH_DESC, ORDER_DEPTH_ASC = 0, 1, 2
+ORDER_INDEX, ORDER_DEPTH_DESC, ORDER_DEPTH_ASC = 0, 1, 2          # GS_ORDER_*
 
 (ARR_TS, ARR_TPS, ARR_MU, ARR_COV3D, ARR_COV2D, ARR_INVCOV, ARR_BBS, ARR_RGB, ARR_SIG, ARR_DEPTH_KEY,
- ARR_TILE_RECT, ARR_SORT_IDXS, ARR_TILE_RANGES, ARR_SORTED_IDS, ARR_SORTED_KEYS, ARR_GRAD2D) = range(16)
+ ARR_TILE_RECT, ARR_SORT_IDXS, ARR_TILE_RANGES, ARR_SORTED_IDS, ARR_SORTED_KEYS, ARR_GRAD2D) = range(16)   # GS_ARR_*
 
 STAGES = ("preprocess", "depth_sort", "count_scan", "emit", "tile_sort", "ranges", "composite_fwd",
-          "composite_bwd", "preprocess_bwd")
+          "composite_bwd", "preprocess_bwd")                     # gs_stage, lower case
 
-# every symbol include/gsplat.h declares (tests/test_abi.py checks the header against this)
-SYMBOLS = ("gs_default_config", "gs_abi_version", "gs_create", "gs_destroy", "gs_last_error", "gs_set_stream",
-           "gs_synchronize", "gs_set_model", "gs_set_model_2d", "gs_set_active_sh_degree", "gs_get_active_sh_degree", "gs_set_background", "gs_get_background", "gs_compose_target", "gs_set_image_size", "gs_set_camera", "gs_preprocess", "gs_bin", "gs_bind_outputs", "gs_forward", "gs_backward_sgd",
-           "gs_backward", "gs_backward_ex", "gs_reset_grads", "gs_loss_l1_dssim", "gs_sgd_step", "gs_comm_unique_id",
-           "gs_comm_init", "gs_allreduce_grads", "gs_comm_destroy", "gs_color_grads_pack", "gs_sh_grads_from_views", "gs_color_rows_pack", "gs_sh_grads_from_touched", "gs_grads_alloc", "gs_grads_read", "gs_num_gaussians", "gs_num_instances", "gs_get_array",
-           "gs_get_stage_times", "gs_get_stage_stats", "gs_get_work_counters", "gs_get_work_counters_ex", "gs_debug_time_composite",
-           "gs_debug_tile_clock", "gs_debug_clock_mhz", "gs_rank_probe_result", "gs_num_rounds", "gs_set_view_slot", "gs_num_coarse_instances",
-           "gs_get_list_stats", "gs_get_tile_parts", "gs_get_bin_path", "gs_debug_set_window", "gs_debug_tile_clock_rows", "gs_debug_tail_fill",
-           "gs_adam_step", "gs_backward_adam",
-           "gs_density_accumulate", "gs_density_decide", "gs_density_plan", "gs_density_restructure", "gs_opacity_reset",
-           "gs_knn_mean_dist2", "gs_init_from_points",
-           "gs_view_depth", "gs_view_depth_backward", "gs_render_features", "gs_backward_features", "gs_backward_camera",
-           "gs_image_metrics", "gs_metrics_finish",
-           "gs_exposure_apply", "gs_exposure_backward", "gs_exposure_adam",
-           "gs_mcmc_plan", "gs_mcmc_sample", "gs_mcmc_relocate", "gs_mcmc_noise", "gs_mcmc_regularize")
-
-GS_CAMERA_GRAD_FLOATS = 40  # include/gsplat.h: gs_backward_camera
-GS_METRIC_SUMS = 4          # include/gsplat.h: gs_image_metrics
-GS_EXPOSURE_FLOATS = 12     # include/gsplat.h: a row of the exposure table, 3 x 4 row-major
-(METRIC_MSE, METRIC_MAE, METRIC_SSIM, METRIC_PSNR, GS_METRIC_COUNT) = range(5)
-GS_ABI_VERSION = 3          # include/gsplat.h; load() refuses a library that reports another version
+GS_CAMERA_GRAD_FLOATS = 40  # gs_backward_camera
+GS_METRIC_SUMS = 4          # gs_image_metrics
+GS_EXPOSURE_FLOATS = 12     # csrc/gs_exposure.h: a row of the exposure table, 3 x 4 row-major
+(METRIC_MSE, METRIC_MAE, METRIC_SSIM, METRIC_PSNR, GS_METRIC_COUNT) = range(5)   # GS_METRIC_*
+GS_ABI_VERSION = 3          # load() refuses a library that reports another version
 GS_DEBUG_WIDE_CURSORS = 1
 GS_DEBUG_ALWAYS_ORDER = 2     # launch orders + side stream also on small frames (tests)
 GS_DEBUG_SUPER16 = 8          # two-level binning: super-tiles of 16 x 16 tiles whatever the grid (tests)
@@ -50,6 +37,7 @@ GS_DEBUG_SUPER8 = 16          # ... of 8 x 8 tiles whatever the grid
 GS_DEBUG_NO_TAIL_FILL = 32    # the frame's zero fills in line instead of at the end of the composite launches' grids (A/B runs, tests)
 GS_DEBUG_TINY_CAPS = 4        # capped lists with the minimum cap on every tile (tests: every busy tile extends its list in the composite kernel)
 GS_MAX_VIEW_SLOTS = 4096
+GS_BWD_OVERWRITE, GS_BWD_COMPOSITE_ONLY, GS_BWD_PARAMS_ONLY, GS_BWD_PARAMS_SH, GS_BWD_PARAMS_GEOM = 1, 2, 4, 8, 16   # gs_backward_ex
 GS_ADAM_GROUPS = 6            # lr[0] means, [1] scales, [2] quaternions, [3] opacities, [4] SH band 0, [5] SH bands >= 1
 GS_ADAM_SELECTIVE = 1         # step only the gaussians with a non-zero gradient float ("selective Adam")
 GS_ERR_INVALID, GS_ERR_UNSUPPORTED = -1, -5
@@ -87,6 +75,98 @@ class GsError(RuntimeError):
         self.code = code
 
 
+# one prototype of include/gsplat.h as ctypes states it; optional: load() tolerates a library without the symbol
+Sig = namedtuple("Sig", "restype argtypes optional", defaults=(False,))
+_i, _i32, _i64, _f, _vp = C.c_int, C.c_int32, C.c_int64, C.c_float, C.c_void_p
+_fp, _dp, _i32p, _i64p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+_G, _cfg = C.POINTER(GsGrads), C.POINTER(GsConfig)
+
+# The C ABI, stated once for Python, in the header's order: load() applies it, SYMBOLS is its keys, and tests/test_abi.py checks every entry
+# against the header's prototype (arity, scalar widths, pointees) and that neither side has a function the other lacks.
+ABI = {
+    "gs_default_config": Sig(None, [_cfg]),
+    "gs_abi_version": Sig(_i, []),
+    "gs_create": Sig(_i, [C.POINTER(_vp), _i, _cfg]),
+    "gs_destroy": Sig(_i, [_vp]),
+    "gs_last_error": Sig(C.c_char_p, [_vp]),
+    "gs_set_stream": Sig(_i, [_vp, _vp]),
+    "gs_synchronize": Sig(_i, [_vp]),
+    "gs_set_model": Sig(_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "gs_set_model_2d": Sig(_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i]),
+    "gs_set_active_sh_degree": Sig(_i, [_vp, _i]),
+    "gs_get_active_sh_degree": Sig(_i, [_vp]),
+    "gs_set_background": Sig(_i, [_vp, _fp]),
+    "gs_get_background": Sig(_i, [_vp, _fp]),
+    "gs_compose_target": Sig(_i, [_vp, _vp, _i32, _i32, _vp]),
+    "gs_set_image_size": Sig(_i, [_vp, _i32, _i32]),
+    "gs_set_camera": Sig(_i, [_vp, _fp, _fp, _f, _f, _f, _f, _fp, _fp, _i32, _i32]),
+    "gs_set_view_slot": Sig(_i, [_vp, _i32]),
+    "gs_preprocess": Sig(_i, [_vp]),
+    "gs_bin": Sig(_i, [_vp, _i32, _i32]),
+    "gs_bind_outputs": Sig(_i, [_vp, _vp, _vp]),
+    "gs_forward": Sig(_i, [_vp, _vp, _vp, _i]),
+    "gs_backward": Sig(_i, [_vp, _vp, _i, _G]),
+    "gs_backward_ex": Sig(_i, [_vp, _vp, _i, _G, _i]),
+    "gs_backward_sgd": Sig(_i, [_vp, _vp, _i, _f]),
+    "gs_reset_grads": Sig(_i, [_vp, _G]),
+    "gs_grads_alloc": Sig(_i, [_vp, _G]),
+    "gs_grads_read": Sig(_i, [_vp, _G, _vp, _vp, _vp, _vp, _vp]),
+    "gs_color_grads_pack": Sig(_i, [_vp, _vp]),
+    "gs_sh_grads_from_views": Sig(_i, [_vp, _i32, _vp, _vp, _vp, _i]),
+    "gs_color_rows_pack": Sig(_i, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "gs_sh_grads_from_touched": Sig(_i, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _i]),
+    "gs_comm_unique_id": Sig(_i, [_vp]),
+    "gs_comm_init": Sig(_i, [_vp, _i, _i, _vp]),
+    "gs_allreduce_grads": Sig(_i, [_vp, _G]),
+    "gs_comm_destroy": Sig(_i, [_vp]),
+    "gs_loss_l1_dssim": Sig(_i, [_vp, _vp, _vp, _i32, _i32, _i32, _f, _vp, _dp, _i]),
+    "gs_sgd_step": Sig(_i, [_vp, _f, _G]),
+    "gs_adam_step": Sig(_i, [_vp, _G, _G, _G, _fp, _f, _f, _f, _i64, _i]),
+    "gs_backward_adam": Sig(_i, [_vp, _vp, _i, _G, _G, _fp, _f, _f, _f, _i64, _i]),
+    "gs_density_accumulate": Sig(_i, [_vp, C.POINTER(GsDensityStats)]),
+    "gs_density_decide": Sig(_i, [_vp, C.POINTER(GsDensityStats), C.POINTER(GsDensityParams), _vp]),
+    "gs_density_plan": Sig(_i, [_vp, _vp, _i64p]),
+    "gs_density_restructure": Sig(_i, [_vp, _vp, _vp, _G, _i32, _G, _G, _i64]),
+    "gs_opacity_reset": Sig(_i, [_vp, _f, _vp, _vp]),
+    "gs_mcmc_plan": Sig(_i, [_vp, _f, _vp, _vp, _i64p]),
+    "gs_mcmc_sample": Sig(_i, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "gs_mcmc_relocate": Sig(_i, [_vp, _vp, _vp, _i64, _f, _i32, _G]),
+    "gs_mcmc_noise": Sig(_i, [_vp, _vp, _f, _f, _f]),
+    "gs_mcmc_regularize": Sig(_i, [_vp, _G, _f, _f]),
+    "gs_knn_mean_dist2": Sig(_i, [_vp, _vp, _i64, _vp]),
+    "gs_init_from_points": Sig(_i, [_vp, _vp, _vp, _vp, _i64, _i, _f, _G]),
+    "gs_view_depth": Sig(_i, [_vp, _vp]),
+    "gs_view_depth_backward": Sig(_i, [_vp, _vp, _vp]),
+    "gs_render_features": Sig(_i, [_vp, _vp, _vp, _vp]),
+    "gs_backward_features": Sig(_i, [_vp, _vp, _vp, _vp, _vp, _G]),
+    "gs_backward_camera": Sig(_i, [_vp, _vp, _i]),
+    "gs_image_metrics": Sig(_i, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i]),
+    "gs_metrics_finish": Sig(_i, [_dp, _dp]),
+    "gs_exposure_apply": Sig(_i, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "gs_exposure_backward": Sig(_i, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "gs_exposure_adam": Sig(_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i64]),
+    "gs_num_gaussians": Sig(_i64, [_vp]),
+    "gs_num_instances": Sig(_i64, [_vp]),
+    "gs_num_coarse_instances": Sig(_i64, [_vp]),
+    "gs_num_rounds": Sig(_i, [_vp]),
+    "gs_get_array": Sig(_i, [_vp, _i, _vp, _i64]),
+    "gs_get_stage_times": Sig(_i, [_vp, _fp]),
+    "gs_get_stage_stats": Sig(_i, [_vp, _dp, _i64p, _i]),
+    "gs_get_work_counters": Sig(_i, [_vp, _i64p, _i64p]),
+    "gs_get_list_stats": Sig(_i, [_vp, _i64p]),
+    "gs_get_tile_parts": Sig(_i, [_vp]),
+    "gs_get_bin_path": Sig(_i, [_vp]),
+    "gs_get_work_counters_ex": Sig(_i, [_vp, _i64p]),
+    "gs_debug_time_composite": Sig(_i, [_vp, _i, _i, _i, _fp]),
+    "gs_debug_tile_clock": Sig(_i, [_vp, _i, _i, _vp]),
+    "gs_debug_tile_clock_rows": Sig(_i, [_vp]),
+    "gs_debug_tail_fill": Sig(_i, [_vp, _i32p], optional=True),   # an older library built for an A/B run loads without it; only tail_fill_blocks fails
+    "gs_debug_clock_mhz": Sig(_i, [_vp, _fp]),
+    "gs_debug_set_window": Sig(_i, [_vp, _i32, _i32]),
+    "gs_rank_probe_result": Sig(_i, [_vp]),
+}
+SYMBOLS = tuple(ABI)
+
 _lib = None
 
 
@@ -106,87 +186,14 @@ def load():
         raise FileNotFoundError(f"{LIB_PATH} not found: build it with `python -m gaussiansplat_amd.build` "
                                 "(there is no CPU fallback)")
     L = C.CDLL(LIB_PATH)
-    vp, fp = C.c_void_p, C.POINTER(C.c_float)
-    L.gs_default_config.argtypes = [C.POINTER(GsConfig)]; L.gs_default_config.restype = None
-    L.gs_abi_version.restype = C.c_int
-    L.gs_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(GsConfig)]
-    L.gs_destroy.argtypes = [vp]
-    L.gs_last_error.argtypes = [vp]; L.gs_last_error.restype = C.c_char_p
-    L.gs_set_stream.argtypes = [vp, vp]
-    L.gs_synchronize.argtypes = [vp]
-    L.gs_set_model.argtypes = [vp, C.c_int64, C.c_int, vp, vp, vp, vp, vp, C.c_int]
-    L.gs_set_camera.argtypes = [vp, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, fp, fp, C.c_int32, C.c_int32]
-    L.gs_preprocess.argtypes = [vp]
-    L.gs_bin.argtypes = [vp, C.c_int32, C.c_int32]
-    L.gs_bind_outputs.argtypes = [vp, vp, vp]
-    L.gs_backward_sgd.argtypes = [vp, vp, C.c_int, C.c_float]
-    L.gs_forward.argtypes = [vp, vp, vp, C.c_int]
-    L.gs_backward.argtypes = [vp, vp, C.c_int, C.POINTER(GsGrads)]
-    L.gs_backward_ex.argtypes = [vp, vp, C.c_int, C.POINTER(GsGrads), C.c_int]
-    L.gs_reset_grads.argtypes = [vp, C.POINTER(GsGrads)]
-    L.gs_loss_l1_dssim.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, C.POINTER(C.c_double), C.c_int]
-    L.gs_sgd_step.argtypes = [vp, C.c_float, C.POINTER(GsGrads)]
-    G = C.POINTER(GsGrads)
-    L.gs_adam_step.argtypes = [vp, G, G, G, fp, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_int]
-    L.gs_backward_adam.argtypes = [vp, vp, C.c_int, G, G, fp, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_int]
-    L.gs_comm_unique_id.argtypes = [vp]
-    L.gs_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
-    L.gs_allreduce_grads.argtypes = [vp, C.POINTER(GsGrads)]
-    L.gs_comm_destroy.argtypes = [vp]
-    L.gs_grads_alloc.argtypes = [vp, C.POINTER(GsGrads)]
-    L.gs_grads_read.argtypes = [vp, C.POINTER(GsGrads), vp, vp, vp, vp, vp]
-    L.gs_num_gaussians.argtypes = [vp]; L.gs_num_gaussians.restype = C.c_int64
-    L.gs_num_instances.argtypes = [vp]; L.gs_num_instances.restype = C.c_int64
-    L.gs_get_array.argtypes = [vp, C.c_int, vp, C.c_int64]
-    L.gs_get_stage_times.argtypes = [vp, fp]
-    L.gs_get_stage_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
-    L.gs_get_work_counters.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.gs_set_model_2d.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int]
-    L.gs_set_image_size.argtypes = [vp, C.c_int32, C.c_int32]
-    L.gs_set_active_sh_degree.argtypes = [vp, C.c_int]
-    L.gs_get_active_sh_degree.argtypes = [vp]
-    L.gs_set_background.argtypes = [vp, fp]
-    L.gs_get_background.argtypes = [vp, fp]
-    L.gs_compose_target.argtypes = [vp, vp, C.c_int32, C.c_int32, vp]
-    L.gs_color_grads_pack.argtypes = [vp, vp]
-    L.gs_sh_grads_from_views.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int]
-    L.gs_color_rows_pack.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
-    L.gs_sh_grads_from_touched.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int64, vp, C.c_int]
-    L.gs_get_work_counters_ex.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.gs_debug_time_composite.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
-    L.gs_debug_tile_clock.argtypes = [vp, C.c_int, C.c_int, vp]
-    L.gs_debug_clock_mhz.argtypes = [vp, C.POINTER(C.c_float)]
-    L.gs_rank_probe_result.argtypes = [vp]
-    L.gs_num_rounds.argtypes = [vp]
-    L.gs_set_view_slot.argtypes = [vp, C.c_int32]
-    L.gs_num_coarse_instances.argtypes = [vp]; L.gs_num_coarse_instances.restype = C.c_int64
-    L.gs_get_list_stats.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.gs_get_tile_parts.argtypes = [vp]
-    L.gs_get_bin_path.argtypes = [vp]
-    L.gs_debug_set_window.argtypes = [vp, C.c_int32, C.c_int32]
-    L.gs_debug_tile_clock_rows.argtypes = [vp]
-    L.gs_density_accumulate.argtypes = [vp, C.POINTER(GsDensityStats)]
-    L.gs_density_decide.argtypes = [vp, C.POINTER(GsDensityStats), C.POINTER(GsDensityParams), vp]
-    L.gs_density_plan.argtypes = [vp, vp, C.POINTER(C.c_int64)]
-    L.gs_density_restructure.argtypes = [vp, vp, vp, G, C.c_int32, G, G, C.c_int64]
-    L.gs_opacity_reset.argtypes = [vp, C.c_float, vp, vp]
-    L.gs_knn_mean_dist2.argtypes = [vp, vp, C.c_int64, vp]
-    L.gs_init_from_points.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int, C.c_float, G]
-    L.gs_view_depth.argtypes = [vp, vp]
-    L.gs_view_depth_backward.argtypes = [vp, vp, vp]
-    L.gs_render_features.argtypes = [vp, vp, vp, vp]
-    L.gs_backward_features.argtypes = [vp, vp, vp, vp, vp, G]
-    L.gs_backward_camera.argtypes = [vp, vp, C.c_int]
-    L.gs_image_metrics.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int]
-    L.gs_metrics_finish.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.gs_exposure_apply.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, vp]
-    L.gs_exposure_backward.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp]
-    L.gs_exposure_adam.argtypes = [vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64]
-    L.gs_mcmc_plan.argtypes = [vp, C.c_float, vp, vp, C.POINTER(C.c_int64)]
-    L.gs_mcmc_sample.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp]
-    L.gs_mcmc_relocate.argtypes = [vp, vp, vp, C.c_int64, C.c_float, C.c_int32, G]
-    L.gs_mcmc_noise.argtypes = [vp, vp, C.c_float, C.c_float, C.c_float]
-    L.gs_mcmc_regularize.argtypes = [vp, G, C.c_float, C.c_float]
+    for name, sig in ABI.items():
+        try:
+            f = getattr(L, name)
+        except AttributeError:
+            if sig.optional:
+                continue
+            raise
+        f.restype, f.argtypes = sig.restype, sig.argtypes
     if L.gs_abi_version() != GS_ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH} has ABI version {L.gs_abi_version()}, this binding is written for {GS_ABI_VERSION}: "
                            "rebuild with `python -m gaussiansplat_amd.build --force`")
@@ -207,11 +214,14 @@ def metrics_finish(sums) -> np.ndarray:
     if s.shape != (GS_METRIC_SUMS,):
         raise ValueError(f"metrics_finish: {GS_METRIC_SUMS} sums expected, got {s.shape}")
     out = np.empty(GS_METRIC_COUNT, np.float64)
-    dp = C.POINTER(C.c_double)
-    rc = load().gs_metrics_finish(s.ctypes.data_as(dp), out.ctypes.data_as(dp))
+    rc = load().gs_metrics_finish(s.ctypes.data_as(_dp), out.ctypes.data_as(_dp))
     if rc != 0:
         raise GsError(rc, "gs_metrics_finish")
     return out
+
+
+_BWD_PHASE = {"all": 0, "composite": GS_BWD_COMPOSITE_ONLY, "params": GS_BWD_PARAMS_ONLY, "params_sh": GS_BWD_PARAMS_ONLY | GS_BWD_PARAMS_SH,
+              "params_geom": GS_BWD_PARAMS_ONLY | GS_BWD_PARAMS_GEOM}      # Context.backward(phase=...)
 
 
 class Context:
@@ -228,31 +238,24 @@ class Context:
         cfg: a complete gs_config to copy instead (every field: a second ctx that must take the same code paths as the first)."""
         self.L = load()
         if cfg is not None:
-            twin = GsConfig()
-            C.memmove(C.byref(twin), C.byref(cfg), C.sizeof(GsConfig))
-            self.cfg = twin
-            self.h = C.c_void_p()
-            rc = self.L.gs_create(C.byref(self.h), device, C.byref(twin))
-            if rc != 0:
-                raise GsError(rc, (self.L.gs_last_error(None) or b"").decode())
-            self._keep = []
-            return
-        cfg = default_config()
-        assert cfg.struct_size == C.sizeof(GsConfig) and cfg.abi_version == GS_ABI_VERSION
-        cfg.schedule = int(schedule)
-        cfg.slab_mode = int(slab_mode)
-        cfg.slab_max_ratio = float(slab_max_ratio)
-        for i, f in enumerate(tuple(slab_fractions)[:3]):
-            cfg.slab_fractions[i] = float(f)
-        cfg.debug_flags = int(debug_flags)
-        cfg.depth_sort = int(depth_sort)
-        cfg.list_cap = int(list_cap)
-        # waves per tile on small grids: 0 = automatic; None = GSPLAT_TILE_PARTS (the test suite pins 1 there: its cross-mode tests
-        # assert bit-identical results, which holds under one partition of the pixels only) or automatic
-        cfg.tile_parts = int(os.environ.get("GSPLAT_TILE_PARTS", "0")) if tile_parts is None else int(tile_parts)
-        cfg.order, cfg.t_min = int(order), float(t_min)
-        cfg.export_debug, cfg.profile_stages, cfg.deterministic = int(export_debug), int(profile_stages), int(deterministic)
-        cfg.bin_path, cfg.rank_mode, cfg.alpha_cull = int(bin_path), int(rank_mode), int(alpha_cull)
+            cfg = GsConfig.from_buffer_copy(cfg)
+        else:
+            cfg = default_config()
+            assert cfg.struct_size == C.sizeof(GsConfig) and cfg.abi_version == GS_ABI_VERSION
+            cfg.schedule = int(schedule)
+            cfg.slab_mode = int(slab_mode)
+            cfg.slab_max_ratio = float(slab_max_ratio)
+            for i, f in enumerate(tuple(slab_fractions)[:3]):
+                cfg.slab_fractions[i] = float(f)
+            cfg.debug_flags = int(debug_flags)
+            cfg.depth_sort = int(depth_sort)
+            cfg.list_cap = int(list_cap)
+            # waves per tile on small grids: 0 = automatic; None = GSPLAT_TILE_PARTS (the test suite pins 1 there: its cross-mode tests
+            # assert bit-identical results, which holds under one partition of the pixels only) or automatic
+            cfg.tile_parts = int(os.environ.get("GSPLAT_TILE_PARTS", "0")) if tile_parts is None else int(tile_parts)
+            cfg.order, cfg.t_min = int(order), float(t_min)
+            cfg.export_debug, cfg.profile_stages, cfg.deterministic = int(export_debug), int(profile_stages), int(deterministic)
+            cfg.bin_path, cfg.rank_mode, cfg.alpha_cull = int(bin_path), int(rank_mode), int(alpha_cull)
         self.cfg = cfg
         self.h = C.c_void_p()
         rc = self.L.gs_create(C.byref(self.h), device, C.byref(cfg))
@@ -277,7 +280,7 @@ class Context:
 
     # -- plumbing
     def set_stream(self, hip_stream: int | None):
-        self._chk(self.L.gs_set_stream(self.h, C.c_void_p(hip_stream or 0)))
+        self._chk(self.L.gs_set_stream(self.h, hip_stream or 0))
 
     def synchronize(self):
         self._chk(self.L.gs_synchronize(self.h))
@@ -286,20 +289,20 @@ class Context:
     def set_model_host(self, means, scales, quats, opacities, shs, sh_degree: int):
         arrs = [np.ascontiguousarray(a, np.float32) for a in (means, scales, quats, opacities, shs)]
         n = arrs[0].shape[0]
-        self._chk(self.L.gs_set_model(self.h, n, sh_degree, *(C.c_void_p(a.ctypes.data) for a in arrs), GS_MEM_HOST))
+        self._chk(self.L.gs_set_model(self.h, n, sh_degree, *(a.ctypes.data for a in arrs), GS_MEM_HOST))
 
     def set_model_device(self, n: int, sh_degree: int, ptrs):
         """ptrs: five device pointers (means, scales, quats, opacities, shs); borrowed, not copied."""
-        self._chk(self.L.gs_set_model(self.h, n, sh_degree, *(C.c_void_p(int(p)) for p in ptrs), GS_MEM_DEVICE))
+        self._chk(self.L.gs_set_model(self.h, n, sh_degree, *(int(p) for p in ptrs), GS_MEM_DEVICE))
 
     def set_model_2d_host(self, means, scales, rots, opacities, colors):
         """SplatData2D (splat.jl:20-26): means [n,2], scales [n,2], rotations [n], opacities [n], colors [n,3]."""
         arrs = [np.ascontiguousarray(a, np.float32) for a in (means, scales, rots, opacities, colors)]
         n = arrs[0].shape[0]
-        self._chk(self.L.gs_set_model_2d(self.h, n, *(C.c_void_p(a.ctypes.data) for a in arrs), GS_MEM_HOST))
+        self._chk(self.L.gs_set_model_2d(self.h, n, *(a.ctypes.data for a in arrs), GS_MEM_HOST))
 
     def set_model_2d_device(self, n: int, ptrs):
-        self._chk(self.L.gs_set_model_2d(self.h, n, *(C.c_void_p(int(p)) for p in ptrs), GS_MEM_DEVICE))
+        self._chk(self.L.gs_set_model_2d(self.h, n, *(int(p) for p in ptrs), GS_MEM_DEVICE))
 
     def set_active_sh_degree(self, degree: int = -1):
         """gs_set_active_sh_degree: evaluate the SH bands 0 .. degree only, on rows that keep the model's stride (-1: the model's own
@@ -332,17 +335,16 @@ class Context:
     def compose_target(self, rgba_ptr: int, W: int, H: int, out_ptr: int):
         """gs_compose_target: a straight-alpha target [4, H, W] over the ctx's background into [3, H, W], device buffers, on the ctx
         stream: out = rgba[c] * a + bg[c] * (1 - a), four fp32 operations.  No sync."""
-        self._chk(self.L.gs_compose_target(self.h, C.c_void_p(int(rgba_ptr)), int(W), int(H), C.c_void_p(int(out_ptr))))
+        self._chk(self.L.gs_compose_target(self.h, int(rgba_ptr), int(W), int(H), int(out_ptr)))
 
     def set_image_size(self, W: int, H: int):
         self._chk(self.L.gs_set_image_size(self.h, int(W), int(H)))
         self.W, self.H = int(W), int(H)
 
     def set_camera(self, T, P, fx, fy, near, far, eye, lookAt, W, H):
-        fp = C.POINTER(C.c_float)
         a = [np.ascontiguousarray(v, np.float32).reshape(-1) for v in (T, P, eye, lookAt)]
-        self._chk(self.L.gs_set_camera(self.h, a[0].ctypes.data_as(fp), a[1].ctypes.data_as(fp), fx, fy, near, far,
-                                       a[2].ctypes.data_as(fp), a[3].ctypes.data_as(fp), int(W), int(H)))
+        self._chk(self.L.gs_set_camera(self.h, a[0].ctypes.data_as(_fp), a[1].ctypes.data_as(_fp), fx, fy, near, far,
+                                       a[2].ctypes.data_as(_fp), a[3].ctypes.data_as(_fp), int(W), int(H)))
         self.W, self.H = int(W), int(H)
 
     def camera_record(self, T, P, fx, fy, near, far, eye, lookAt, W, H):
@@ -369,55 +371,53 @@ class Context:
     def forward_host(self):
         img = np.empty((3, self.H, self.W), np.float32)
         tr = np.empty((self.H, self.W), np.float32)
-        self._chk(self.L.gs_forward(self.h, C.c_void_p(img.ctypes.data), C.c_void_p(tr.ctypes.data), GS_MEM_HOST))
+        self._chk(self.L.gs_forward(self.h, img.ctypes.data, tr.ctypes.data, GS_MEM_HOST))
         return img, tr
 
     def bind_outputs(self, image_ptr: int = 0, trans_ptr: int = 0):
         """gs_bind_outputs: the forward writes straight into these device buffers (0, 0 unbinds); they must stay valid and
         unmodified until the frame's last backward."""
-        self._chk(self.L.gs_bind_outputs(self.h, C.c_void_p(image_ptr), C.c_void_p(trans_ptr)))
+        self._chk(self.L.gs_bind_outputs(self.h, image_ptr, trans_ptr))
 
     def forward_device(self, image_ptr: int = 0, trans_ptr: int = 0):
-        self._chk(self.L.gs_forward(self.h, C.c_void_p(image_ptr), C.c_void_p(trans_ptr), GS_MEM_DEVICE))
+        self._chk(self.L.gs_forward(self.h, image_ptr, trans_ptr, GS_MEM_DEVICE))
 
     def backward(self, dC_ptr_or_array, grads: GsGrads, overwrite: bool = False, phase: str = "all"):
         """phase: "all", "composite" (GS_BWD_COMPOSITE_ONLY), "params" (GS_BWD_PARAMS_ONLY), or the chain in two steps:
         "params_sh" (GS_BWD_PARAMS_ONLY | GS_BWD_PARAMS_SH) then "params_geom" (GS_BWD_PARAMS_ONLY | GS_BWD_PARAMS_GEOM)."""
-        flags = (1 if overwrite else 0) | {"all": 0, "composite": 2, "params": 4, "params_sh": 4 | 8, "params_geom": 4 | 16}[phase]   # GS_BWD_*
+        flags = (GS_BWD_OVERWRITE if overwrite else 0) | _BWD_PHASE[phase]
         if isinstance(dC_ptr_or_array, np.ndarray):
             a = np.ascontiguousarray(dC_ptr_or_array, np.float32)
-            self._chk(self.L.gs_backward_ex(self.h, C.c_void_p(a.ctypes.data), GS_MEM_HOST, C.byref(grads), flags))
+            self._chk(self.L.gs_backward_ex(self.h, a.ctypes.data, GS_MEM_HOST, C.byref(grads), flags))
         else:
-            self._chk(self.L.gs_backward_ex(self.h, C.c_void_p(int(dC_ptr_or_array)), GS_MEM_DEVICE, C.byref(grads), flags))
+            self._chk(self.L.gs_backward_ex(self.h, int(dC_ptr_or_array), GS_MEM_DEVICE, C.byref(grads), flags))
 
     def color_grads_pack(self, drgb_ptr: int):
         """d rgb of the last backward, packed [n, 3] into a device buffer (colour-factored exchange)."""
-        self._chk(self.L.gs_color_grads_pack(self.h, C.c_void_p(int(drgb_ptr))))
+        self._chk(self.L.gs_color_grads_pack(self.h, int(drgb_ptr)))
 
     def sh_grads_from_views(self, cam_records: np.ndarray, drgb_ptr: int, d_shs_ptr: int, overwrite: bool = True):
         """cam_records [nviews, 38] host float32 {T16, P16, eye3, lookAt3}; drgb [nviews, n, 3] device."""
         cr = np.ascontiguousarray(cam_records, np.float32)
         assert cr.ndim == 2 and cr.shape[1] == 38
-        self._chk(self.L.gs_sh_grads_from_views(self.h, cr.shape[0], C.c_void_p(cr.ctypes.data), C.c_void_p(int(drgb_ptr)),
-                                                C.c_void_p(int(d_shs_ptr)), 1 if overwrite else 0))
+        self._chk(self.L.gs_sh_grads_from_views(self.h, cr.shape[0], cr.ctypes.data, int(drgb_ptr), int(d_shs_ptr), 1 if overwrite else 0))
 
     def color_rows_pack(self, drgb_ptr: "int | None", n: int, bits_ptr: int, rows_ptr: int, count_ptr: int):
         """gs_color_rows_pack: one view as a bitmap of touched gaussians (int32 words), their d rgb rows in gaussian order and an
         int64 count, all device buffers; drgb_ptr None / 0 = the ctx's own sums of the last backward (n = num_gaussians).  No sync."""
-        self._chk(self.L.gs_color_rows_pack(self.h, C.c_void_p(int(drgb_ptr or 0)), int(n), C.c_void_p(int(bits_ptr)),
-                                            C.c_void_p(int(rows_ptr)), C.c_void_p(int(count_ptr))))
+        self._chk(self.L.gs_color_rows_pack(self.h, int(drgb_ptr or 0), int(n), int(bits_ptr), int(rows_ptr), int(count_ptr)))
 
     def sh_grads_from_touched(self, cam_records: np.ndarray, bits_ptr: int, rows_ptr: int, rows_cap: int, d_shs_ptr: int,
                               overwrite: bool = True):
         """cam_records as sh_grads_from_views; bits [nviews, ceil(n / 32)] int32 and rows [nviews, rows_cap, 3] float32, device."""
         cr = np.ascontiguousarray(cam_records, np.float32)
         assert cr.ndim == 2 and cr.shape[1] == 38
-        self._chk(self.L.gs_sh_grads_from_touched(self.h, cr.shape[0], C.c_void_p(cr.ctypes.data), C.c_void_p(int(bits_ptr)),
-                                                  C.c_void_p(int(rows_ptr)), int(rows_cap), C.c_void_p(int(d_shs_ptr)), 1 if overwrite else 0))
+        self._chk(self.L.gs_sh_grads_from_touched(self.h, cr.shape[0], cr.ctypes.data, int(bits_ptr), int(rows_ptr), int(rows_cap), int(d_shs_ptr),
+                                                  1 if overwrite else 0))
 
     def backward_sgd(self, dC_ptr: int, lr: float):
         """gs_backward_sgd: backward and `param .-= lr * grad` (train.jl:42-46) in one pass on the resident model; dC on the device."""
-        self._chk(self.L.gs_backward_sgd(self.h, C.c_void_p(dC_ptr), GS_MEM_DEVICE, C.c_float(lr)))
+        self._chk(self.L.gs_backward_sgd(self.h, dC_ptr, GS_MEM_DEVICE, lr))
 
     def grads_alloc(self) -> GsGrads:
         """Library-owned flat gradient buffer (for hosts without a device allocator, e.g. plain Julia)."""
@@ -429,7 +429,7 @@ class Context:
         n, k3 = self.num_gaussians, 3 * (sh_degree + 1) ** 2
         out = dict(means=np.empty((n, 3), np.float32), scales=np.empty((n, 3), np.float32), quats=np.empty((n, 4), np.float32),
                    opacities=np.empty((n,), np.float32), shs=np.empty((n, k3), np.float32))
-        self._chk(self.L.gs_grads_read(self.h, C.byref(grads), *(C.c_void_p(out[k].ctypes.data) for k in
+        self._chk(self.L.gs_grads_read(self.h, C.byref(grads), *(out[k].ctypes.data for k in
                                                                    ("means", "scales", "quats", "opacities", "shs"))))
         return out
 
@@ -438,7 +438,7 @@ class Context:
         n = self.num_gaussians
         out = dict(means=np.empty((n, 2), np.float32), scales=np.empty((n, 2), np.float32), rots=np.empty((n,), np.float32),
                    opacities=np.empty((n,), np.float32), colors=np.empty((n, 3), np.float32))
-        self._chk(self.L.gs_grads_read(self.h, C.byref(grads), *(C.c_void_p(out[k].ctypes.data) for k in
+        self._chk(self.L.gs_grads_read(self.h, C.byref(grads), *(out[k].ctypes.data for k in
                                                                    ("means", "scales", "rots", "opacities", "colors"))))
         return out
 
@@ -448,13 +448,12 @@ class Context:
         dC = np.empty_like(img)
         out = C.c_double()
         Cn, H, W = img.shape
-        self._chk(self.L.gs_loss_l1_dssim(self.h, C.c_void_p(img.ctypes.data), C.c_void_p(gt.ctypes.data), W, H, Cn, lam,
-                                          C.c_void_p(dC.ctypes.data), C.byref(out), GS_MEM_HOST))
+        self._chk(self.L.gs_loss_l1_dssim(self.h, img.ctypes.data, gt.ctypes.data, W, H, Cn, lam, dC.ctypes.data, C.byref(out), GS_MEM_HOST))
         return float(out.value), dC
 
     def loss_device(self, img_ptr: int, gt_ptr: int, dC_ptr: int, W: int, H: int, Cn: int, lam: float = 0.1, want_loss: bool = True):
         out = C.c_double()
-        self._chk(self.L.gs_loss_l1_dssim(self.h, C.c_void_p(img_ptr), C.c_void_p(gt_ptr), W, H, Cn, lam, C.c_void_p(dC_ptr),
+        self._chk(self.L.gs_loss_l1_dssim(self.h, img_ptr, gt_ptr, W, H, Cn, lam, dC_ptr,
                                           C.byref(out) if want_loss else None, GS_MEM_DEVICE))
         return float(out.value) if want_loss else None
 
@@ -468,7 +467,7 @@ class Context:
         return buf.raw
 
     def comm_init(self, rank: int, nranks: int, unique_id: bytes):
-        self._chk(self.L.gs_comm_init(self.h, rank, nranks, C.c_char_p(unique_id)))
+        self._chk(self.L.gs_comm_init(self.h, rank, nranks, unique_id))
 
     def allreduce_grads(self, grads: GsGrads):
         self._chk(self.L.gs_allreduce_grads(self.h, C.byref(grads)))
@@ -489,7 +488,7 @@ class Context:
         """gs_backward_adam: backward and gs_adam_step in one pass on the resident model (3-D renderer); dC on the device."""
         lr6 = (C.c_float * GS_ADAM_GROUPS)(*[float(x) for x in lr])
         f = (GS_ADAM_SELECTIVE if selective else 0) if flags is None else int(flags)
-        self._chk(self.L.gs_backward_adam(self.h, C.c_void_p(int(dC_ptr)), GS_MEM_DEVICE, C.byref(exp_avg), C.byref(exp_avg_sq), lr6,
+        self._chk(self.L.gs_backward_adam(self.h, int(dC_ptr), GS_MEM_DEVICE, C.byref(exp_avg), C.byref(exp_avg_sq), lr6,
                                           beta1, beta2, eps, int(step), f))
 
     # -- density control (3-D renderer): statistics, clone / split / prune, opacity reset
@@ -500,12 +499,12 @@ class Context:
 
     def density_decide(self, stats: GsDensityStats, params: GsDensityParams, action_ptr: int):
         """gs_density_decide: action[g] = 0 keep, 1 clone, 2 split, 3 prune (int32 device array of n words).  No sync."""
-        self._chk(self.L.gs_density_decide(self.h, C.byref(stats), C.byref(params), C.c_void_p(int(action_ptr or 0))))
+        self._chk(self.L.gs_density_decide(self.h, C.byref(stats), C.byref(params), int(action_ptr or 0)))
 
     def density_plan(self, action_ptr: int):
         """gs_density_plan: (survivors, clones, splits, pruned); n_out = survivors + clones + 2 * splits.  The one call that synchronises."""
         o = (C.c_int64 * 4)()
-        self._chk(self.L.gs_density_plan(self.h, C.c_void_p(int(action_ptr or 0)), o))
+        self._chk(self.L.gs_density_plan(self.h, int(action_ptr or 0), o))
         return int(o[0]), int(o[1]), int(o[2]), int(o[3])
 
     def density_restructure(self, action_ptr: int, noise_ptr: "int | None", dst_model: GsGrads, src_sets, dst_sets, n_out: int):
@@ -516,25 +515,24 @@ class Context:
             raise ValueError("density_restructure: one destination per source set")
         k = len(src_sets)
         sa, da = (GsGrads * max(k, 1))(*src_sets), (GsGrads * max(k, 1))(*dst_sets)
-        self._chk(self.L.gs_density_restructure(self.h, C.c_void_p(int(action_ptr or 0)), C.c_void_p(int(noise_ptr or 0)), C.byref(dst_model), k,
+        self._chk(self.L.gs_density_restructure(self.h, int(action_ptr or 0), int(noise_ptr or 0), C.byref(dst_model), k,
                                                 sa, da, int(n_out)))
 
     def opacity_reset(self, max_logit: float, m_opac_ptr: int = 0, v_opac_ptr: int = 0):
         """gs_opacity_reset: opacity = min(opacity, max_logit) on the resident model (NaN stays), +0 into the two moment arrays."""
-        self._chk(self.L.gs_opacity_reset(self.h, C.c_float(max_logit), C.c_void_p(int(m_opac_ptr or 0)), C.c_void_p(int(v_opac_ptr or 0))))
+        self._chk(self.L.gs_opacity_reset(self.h, max_logit, int(m_opac_ptr or 0), int(v_opac_ptr or 0)))
 
     # -- MCMC densification (3-D renderer): plan, draws, relocation, noise, regularisers
     def mcmc_plan(self, min_opacity_logit: float, cdf_ptr: int, dead_ptr: int):
         """gs_mcmc_plan: the integer weights' inclusive prefix sum into cdf (uint64 device array of n words), the indices of the gaussians
         that are not alive, ascending, into dead (int32, n words); (alive, dead, total).  The one call of the five that synchronises."""
         o = (C.c_int64 * 3)()
-        self._chk(self.L.gs_mcmc_plan(self.h, C.c_float(min_opacity_logit), C.c_void_p(int(cdf_ptr or 0)), C.c_void_p(int(dead_ptr or 0)), o))
+        self._chk(self.L.gs_mcmc_plan(self.h, min_opacity_logit, int(cdf_ptr or 0), int(dead_ptr or 0), o))
         return int(o[0]), int(o[1]), int(o[2])
 
     def mcmc_sample(self, cdf_ptr: int, n: int, u_ptr: int, m: int, src_ptr: int):
         """gs_mcmc_sample: src[j] = the gaussian the uniform number u[j] points at on the CDF (int32, m words).  No sync."""
-        self._chk(self.L.gs_mcmc_sample(self.h, C.c_void_p(int(cdf_ptr or 0)), C.c_int64(int(n)), C.c_void_p(int(u_ptr or 0)), C.c_int64(int(m)),
-                                        C.c_void_p(int(src_ptr or 0))))
+        self._chk(self.L.gs_mcmc_sample(self.h, int(cdf_ptr or 0), int(n), int(u_ptr or 0), int(m), int(src_ptr or 0)))
 
     def mcmc_relocate(self, src_ptr: int, dst_ptr: "int | None", m: int, min_opacity: float, sets=()):
         """gs_mcmc_relocate: in place on the resident model, gaussian dst[j] becomes a copy of src[j] and both get the corrected opacity and
@@ -543,50 +541,49 @@ class Context:
         sets = list(sets)
         k = len(sets)
         sa = (GsGrads * max(k, 1))(*sets)
-        self._chk(self.L.gs_mcmc_relocate(self.h, C.c_void_p(int(src_ptr or 0)), C.c_void_p(int(dst_ptr or 0)), C.c_int64(int(m)), C.c_float(min_opacity),
-                                          k, sa))
+        self._chk(self.L.gs_mcmc_relocate(self.h, int(src_ptr or 0), int(dst_ptr or 0), int(m), min_opacity, k, sa))
 
     def mcmc_noise(self, z_ptr: int, lr: float, gate_k: float = 100.0, gate_t: float = 0.005):
         """gs_mcmc_noise: means += lr * gate(opacity) * Sigma z on the resident model, z: [n, 3] standard normals on the device.  No sync."""
-        self._chk(self.L.gs_mcmc_noise(self.h, C.c_void_p(int(z_ptr or 0)), C.c_float(lr), C.c_float(gate_k), C.c_float(gate_t)))
+        self._chk(self.L.gs_mcmc_noise(self.h, int(z_ptr or 0), lr, gate_k, gate_t))
 
     def mcmc_regularize(self, grads: GsGrads, c_opacity: float, c_scale: float):
         """gs_mcmc_regularize: d_opacities += c_opacity * sig (1 - sig), d_scales += c_scale * exp(scale) into `grads`.  The frame stands.  No sync."""
-        self._chk(self.L.gs_mcmc_regularize(self.h, C.byref(grads), C.c_float(c_opacity), C.c_float(c_scale)))
+        self._chk(self.L.gs_mcmc_regularize(self.h, C.byref(grads), c_opacity, c_scale))
 
     # -- point-cloud initialisation: needs no model, camera or frame, and leaves the ctx's frame as it is
     def knn_mean_dist2(self, points_ptr: int, n: int, dist2_ptr: int):
         """gs_knn_mean_dist2: dist2[i] = the mean of the three smallest squared distances from point i to the other finite points (exact:
         bit for bit a brute force).  points: 3 x n device floats, dist2: n device floats.  No sync."""
-        self._chk(self.L.gs_knn_mean_dist2(self.h, C.c_void_p(int(points_ptr or 0)), C.c_int64(int(n)), C.c_void_p(int(dist2_ptr or 0))))
+        self._chk(self.L.gs_knn_mean_dist2(self.h, int(points_ptr or 0), int(n), int(dist2_ptr or 0)))
 
     def init_from_points(self, points_ptr: int, colors_ptr: "int | None", dist2_ptr: int, n: int, sh_degree: int, opacity_logit: float,
                          dst_model: GsGrads):
         """gs_init_from_points: the model a training run starts from, into dst_model (five device arrays of n rows).  colors_ptr None / 0:
         grey.  The ctx's model is not switched.  No sync."""
-        self._chk(self.L.gs_init_from_points(self.h, C.c_void_p(int(points_ptr or 0)), C.c_void_p(int(colors_ptr or 0)), C.c_void_p(int(dist2_ptr or 0)),
-                                             C.c_int64(int(n)), C.c_int(int(sh_degree)), C.c_float(opacity_logit), C.byref(dst_model)))
+        self._chk(self.L.gs_init_from_points(self.h, int(points_ptr or 0), int(colors_ptr or 0), int(dist2_ptr or 0), int(n), int(sh_degree),
+                                             opacity_logit, C.byref(dst_model)))
 
     # -- feature maps (3-D renderer): depth, opacity and per-gaussian features through the frame's own composite launches
     def view_depth(self, z_ptr: int):
         """gs_view_depth: z[g] = the view-space depth ts[2] of gaussian g (n device floats; GS_ARR_TS row 2 bit for bit).  Needs a model and
         a camera, no frame.  No sync."""
-        self._chk(self.L.gs_view_depth(self.h, C.c_void_p(int(z_ptr or 0))))
+        self._chk(self.L.gs_view_depth(self.h, int(z_ptr or 0)))
 
     def view_depth_backward(self, dz_ptr: int, d_means_ptr: int):
         """gs_view_depth_backward: d_means[g][j] += T[2 + 4 j] * dz[g]; rows whose dz compares == 0 are left unread.  No sync."""
-        self._chk(self.L.gs_view_depth_backward(self.h, C.c_void_p(int(dz_ptr or 0)), C.c_void_p(int(d_means_ptr or 0))))
+        self._chk(self.L.gs_view_depth_backward(self.h, int(dz_ptr or 0), int(d_means_ptr or 0)))
 
     def render_features(self, feat_ptr: int, out_ptr: int, trans_ptr: int = 0):
         """gs_render_features: out [3, H, W] = sum feat[g] * alpha * T over the finished frame's own walk (feat [n, 3] device floats); no
         background; trans_ptr 0: the transmittance is not wanted.  The frame stays as forward left it.  No sync."""
-        self._chk(self.L.gs_render_features(self.h, C.c_void_p(int(feat_ptr or 0)), C.c_void_p(int(out_ptr or 0)), C.c_void_p(int(trans_ptr or 0))))
+        self._chk(self.L.gs_render_features(self.h, int(feat_ptr or 0), int(out_ptr or 0), int(trans_ptr or 0)))
 
     def backward_features(self, feat_ptr: int, image_f_ptr: int, dF_ptr: int, d_feat_ptr: int, grads: "GsGrads | None"):
         """gs_backward_features: the gradients of sum out . dF -- d_feat [n, 3] overwritten, the alpha path accumulated into the means,
         scales, quaternions and opacities of `grads` (None: d_feat only; d_shs is not touched).  No sync."""
-        self._chk(self.L.gs_backward_features(self.h, C.c_void_p(int(feat_ptr or 0)), C.c_void_p(int(image_f_ptr or 0)), C.c_void_p(int(dF_ptr or 0)),
-                                              C.c_void_p(int(d_feat_ptr or 0)), C.byref(grads) if grads is not None else None))
+        self._chk(self.L.gs_backward_features(self.h, int(feat_ptr or 0), int(image_f_ptr or 0), int(dF_ptr or 0), int(d_feat_ptr or 0),
+                                              C.byref(grads) if grads is not None else None))
 
     def backward_camera(self, out_ptr: "int | None" = None):
         """gs_backward_camera: the frame's gradient into the arguments of set_camera, GS_CAMERA_GRAD_FLOATS floats {d_T[16], d_P[16], d_eye[3],
@@ -594,9 +591,9 @@ class Context:
         out_ptr None: returned as a float32 array (synchronises); else a device pointer that is filled on the stream (no sync)."""
         if out_ptr is None:
             out = np.empty(GS_CAMERA_GRAD_FLOATS, np.float32)
-            self._chk(self.L.gs_backward_camera(self.h, C.c_void_p(out.ctypes.data), GS_MEM_HOST))
+            self._chk(self.L.gs_backward_camera(self.h, out.ctypes.data, GS_MEM_HOST))
             return out
-        self._chk(self.L.gs_backward_camera(self.h, C.c_void_p(int(out_ptr)), GS_MEM_DEVICE))
+        self._chk(self.L.gs_backward_camera(self.h, int(out_ptr), GS_MEM_DEVICE))
         return None
 
     # -- evaluation metrics: needs no model, camera or frame, and leaves the ctx's frame as it is
@@ -613,34 +610,32 @@ class Context:
                 raise ValueError(f"image_metrics: the weight must be [{H}, {W}], not {weight.shape}")
         sums = np.empty(GS_METRIC_SUMS, np.float64)
         smap = np.empty_like(img) if want_map else None
-        self._chk(self.L.gs_image_metrics(self.h, C.c_void_p(img.ctypes.data), C.c_void_p(gt.ctypes.data),
-                                          C.c_void_p(weight.ctypes.data) if weight is not None else None, W, H, Cn,
-                                          C.c_void_p(smap.ctypes.data) if smap is not None else None, C.c_void_p(sums.ctypes.data), GS_MEM_HOST))
+        self._chk(self.L.gs_image_metrics(self.h, img.ctypes.data, gt.ctypes.data, weight.ctypes.data if weight is not None else None, W, H, Cn,
+                                          smap.ctypes.data if smap is not None else None, sums.ctypes.data, GS_MEM_HOST))
         return sums, smap
 
     def image_metrics_device(self, img_ptr: int, gt_ptr: int, weight_ptr: int, W: int, H: int, Cn: int, map_ptr: int, sums_ptr: int):
         """gs_image_metrics with device pointers (weight_ptr / map_ptr 0: none); sums_ptr: four device float64.  On the ctx stream, no sync."""
-        self._chk(self.L.gs_image_metrics(self.h, C.c_void_p(int(img_ptr or 0)), C.c_void_p(int(gt_ptr or 0)), C.c_void_p(int(weight_ptr or 0)),
-                                          int(W), int(H), int(Cn), C.c_void_p(int(map_ptr or 0)), C.c_void_p(int(sums_ptr or 0)), GS_MEM_DEVICE))
+        self._chk(self.L.gs_image_metrics(self.h, int(img_ptr or 0), int(gt_ptr or 0), int(weight_ptr or 0),
+                                          int(W), int(H), int(Cn), int(map_ptr or 0), int(sums_ptr or 0), GS_MEM_DEVICE))
 
     # -- per-view exposure: needs no model, camera or frame, and leaves the ctx's frame as it is.  Device pointers, no sync
     def exposure_apply(self, img_ptr: int, exposure_ptr: int, weight_ptr: int, W: int, H: int, out_ptr: int):
         """gs_exposure_apply: out [3, H, W] = w * (M img + b) per pixel, E = [M | b] 12 device floats (row-major 3 x 4), weight_ptr 0: none."""
-        self._chk(self.L.gs_exposure_apply(self.h, C.c_void_p(int(img_ptr or 0)), C.c_void_p(int(exposure_ptr or 0)), C.c_void_p(int(weight_ptr or 0)),
-                                           int(W), int(H), C.c_void_p(int(out_ptr or 0))))
+        self._chk(self.L.gs_exposure_apply(self.h, int(img_ptr or 0), int(exposure_ptr or 0), int(weight_ptr or 0), int(W), int(H),
+                                           int(out_ptr or 0)))
 
     def exposure_backward(self, img_ptr: int, d_out_ptr: int, exposure_ptr: int, weight_ptr: int, W: int, H: int, d_img_ptr: int,
                           d_exposure_ptr: int = 0):
         """gs_exposure_backward: d_img (may be d_out itself) and, unless d_exposure_ptr is 0, the 12 floats of d_exposure (overwritten)."""
-        self._chk(self.L.gs_exposure_backward(self.h, C.c_void_p(int(img_ptr or 0)), C.c_void_p(int(d_out_ptr or 0)), C.c_void_p(int(exposure_ptr or 0)),
-                                              C.c_void_p(int(weight_ptr or 0)), int(W), int(H), C.c_void_p(int(d_img_ptr or 0)),
-                                              C.c_void_p(int(d_exposure_ptr or 0))))
+        self._chk(self.L.gs_exposure_backward(self.h, int(img_ptr or 0), int(d_out_ptr or 0), int(exposure_ptr or 0), int(weight_ptr or 0),
+                                              int(W), int(H), int(d_img_ptr or 0), int(d_exposure_ptr or 0)))
 
     def exposure_adam(self, exposure_ptr: int, d_exposure_ptr: int, exp_avg_ptr: int, exp_avg_sq_ptr: int, lr: float, beta1: float, beta2: float,
                       eps: float, step: int):
         """gs_exposure_adam: one Adam step of a row of 12 floats (gs_adam_step's update); step counts from 1 and is the row's own."""
-        self._chk(self.L.gs_exposure_adam(self.h, C.c_void_p(int(exposure_ptr or 0)), C.c_void_p(int(d_exposure_ptr or 0)), C.c_void_p(int(exp_avg_ptr or 0)),
-                                          C.c_void_p(int(exp_avg_sq_ptr or 0)), float(lr), float(beta1), float(beta2), float(eps), int(step)))
+        self._chk(self.L.gs_exposure_adam(self.h, int(exposure_ptr or 0), int(d_exposure_ptr or 0), int(exp_avg_ptr or 0),
+                                          int(exp_avg_sq_ptr or 0), float(lr), float(beta1), float(beta2), float(eps), int(step)))
 
     def reset_grads(self, grads: GsGrads):
         self._chk(self.L.gs_reset_grads(self.h, C.byref(grads)))
@@ -677,7 +672,7 @@ class Context:
         else:
             shape, dt = spec[which]
         out = np.empty(shape, dt)
-        self._chk(self.L.gs_get_array(self.h, which, C.c_void_p(out.ctypes.data), out.nbytes))
+        self._chk(self.L.gs_get_array(self.h, which, out.ctypes.data, out.nbytes))
         return out
 
     def stage_stats(self, reset: bool = False) -> dict:
@@ -734,15 +729,13 @@ class Context:
             if rows <= 0:
                 raise GsError(-1, "tile_clock: records by workgroup need a frame with a launch order")
         out = np.zeros((rows, 15), np.uint64)
-        self._chk(self.L.gs_debug_tile_clock(self.h, which, variant, C.c_void_p(out.ctypes.data)))
+        self._chk(self.L.gs_debug_tile_clock(self.h, which, variant, out.ctypes.data))
         return out
 
     def tail_fill_blocks(self):
         """(forward, backward): fill workgroups the last frame's composite launches carried at the end of their grids (0: the in-line form)"""
         o = (C.c_int32 * 2)()
-        f = self.L.gs_debug_tail_fill                       # (bound here: an older library built for an A/B run loads without it)
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-        self._chk(f(self.h, o))
+        self._chk(self.L.gs_debug_tail_fill(self.h, o))
         return int(o[0]), int(o[1])
 
     def tile_clock_rows(self) -> int:

@@ -2,42 +2,12 @@
 
 Every `ccall((:name, libgs), Ret, (Args...), ...)` is parsed and checked against the C prototype of the same name:
 arity, scalar widths, pointer-ness and pointee types; the Julia mirror structs must have the header's fields in the
-header's order (and gs_config must stay 64 bytes); every function the header declares must be bound at least once.
+header's order (and gs_config must stay 96 bytes); every function the header declares must be bound at least once.
 """
 import os
 import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _strip_comments(src):
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-
-
-def _c_prototypes():
-    src = _strip_comments(open(os.path.join(ROOT, "include", "gsplat.h")).read())
-    protos = {}
-    for m in re.finditer(r"(?m)^\s*((?:const\s+)?[A-Za-z_0-9]+\s*\**)\s*(gs_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", src):
-        ret, name, args = m.group(1).strip(), m.group(2), m.group(3).strip()
-        alist = [] if args in ("", "void") else [a.strip() for a in args.split(",")]
-        protos[name] = (ret, alist)
-    return protos
-
-
-def _c_kind(decl):
-    """(kind, pointee) of a C parameter / return declaration."""
-    d = re.sub(r"\bconst\b", "", decl).strip()
-    arr = "[" in d
-    d = re.sub(r"\[.*?\]", "", d).strip()
-    stars = d.count("*")
-    d = d.replace("*", " ").split()
-    base = d[0] if d else ""
-    if len(d) > 1 and d[0] in ("unsigned", "long"):
-        base = " ".join(d[:-1])
-    nptr = stars + (1 if arr else 0)
-    if nptr == 0:
-        return {"int": "i32", "int32_t": "i32", "int64_t": "i64", "float": "f32", "double": "f64", "void": "void"}[base], None
-    return "ptr" * 1, (base, nptr)
+from abi_header import ROOT, _c_kind, _c_prototypes, _c_struct_fields, _split_top
 
 
 _J_SCALAR = {"Cint": "i32", "Int32": "i32", "Int64": "i64", "Cfloat": "f32", "Float32": "f32", "Cdouble": "f64", "Float64": "f64",
@@ -58,22 +28,6 @@ def _j_kind(t):
     if inner.startswith("Ptr{"):
         return "ptr", (_j_kind(inner)[1][0], 2)
     return "ptr", (_J_POINTEE[inner], 1)
-
-
-def _split_top(s):
-    out, depth, cur = [], 0, ""
-    for ch in s:
-        if ch in "({[":
-            depth += 1
-        elif ch in ")}]":
-            depth -= 1
-        if ch == "," and depth == 0:
-            out.append(cur); cur = ""
-        else:
-            cur += ch
-    if cur.strip():
-        out.append(cur)
-    return [x.strip() for x in out]
 
 
 def _julia_ccalls():
@@ -138,20 +92,6 @@ def test_every_exported_function_is_bound():
     assert not missing, f"declared in include/gsplat.h but never ccall'ed in julia/backend.jl: {missing}"
 
 
-def _c_struct_fields(name):
-    src = _strip_comments(open(os.path.join(ROOT, "include", "gsplat.h")).read())
-    m = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*" + name + r"\s*;", src)
-    fields = []
-    for line in m.group(1).split(";"):
-        line = line.strip()
-        if not line:
-            continue
-        fm = re.fullmatch(r"([A-Za-z_0-9]+)\s*(\*?)\s*([A-Za-z_0-9]+)(?:\[(\d+)\])?", line)
-        assert fm, line
-        fields.append((fm.group(3), fm.group(1) + fm.group(2), int(fm.group(4) or 1)))
-    return fields
-
-
 def _julia_struct_fields(name):
     src = open(os.path.join(ROOT, "julia", "backend.jl")).read()
     m = re.search(r"struct\s+" + name + r"\b[^\n]*\n(.*?)\nend", src, flags=re.S)
@@ -176,7 +116,7 @@ def test_config_and_grads_structs_mirror_the_header():
             assert jt == f"NTuple{{{cnt}, {'Int32' if ct == 'int32_t' else 'Float32'}}}", (cn, jt)
         else:
             assert jt == {"int32_t": "Int32", "float": "Float32"}[ct], (cn, jt)
-    assert total == 96, "sizeof(gs_config) is 96 in ABI version 2 (struct_size + abi_version guard)"
+    assert total == 96, "sizeof(gs_config) is 96 in ABI version 3 (struct_size + abi_version guard)"
     src = open(os.path.join(ROOT, "julia", "backend.jl")).read()
     ctor = re.search(r"GsConfig\(([^\n]*)\)\n", src).group(1)
     assert len(_split_top(ctor)) == len(jf), "defaultConfig(): GsConfig constructor arity"
@@ -184,11 +124,6 @@ def test_config_and_grads_structs_mirror_the_header():
     jg = _julia_struct_fields("GsGrads")
     assert [f[0] for f in gf] == [f[0] for f in jg]
     assert all(t == "Ptr{Float32}" for _, t in jg) and all(t == "float*" for _, t, _ in gf)
-    # the Python mirror agrees as well
-    import ctypes as C
-    from gaussiansplat_amd import backend
-    assert [f[0] for f in backend.GsConfig._fields_] == [f[0] for f in cf] and C.sizeof(backend.GsConfig) == 96
-    assert [f[0] for f in backend.GsGrads._fields_] == [f[0] for f in gf]
 
 
 # ---- the reference's own signatures: julia/backend.jl must define METHODS on the reference's types so that

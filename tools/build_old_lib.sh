@@ -1,31 +1,27 @@
 #!/bin/bash
 # Same-box A/B against an earlier commit's kernels:  tools/build_old_lib.sh COMMIT [TAG=old]  ->  gaussiansplat_amd/lib_TAG/libgsplat_hip.so
 # built from that commit's csrc/ + include/, every file with the flags that commit's own gaussiansplat_amd/build.py gives it (SOURCES); ABI functions added since (the ctypes binding
-# refuses a library without them) get a stub.  Then: GSPLAT_HIP_LIB=$PWD/gaussiansplat_amd/lib_TAG/libgsplat_hip.so python3 bench.py ...
+# refuses a library without them) get a generated stub.  Then: GSPLAT_HIP_LIB=$PWD/gaussiansplat_amd/lib_TAG/libgsplat_hip.so python3 bench.py ...
 set -e -o pipefail
 C=$1; TAG=${2:-old}
 W=$(mktemp -d)
 git archive "$C" gaussiansplat_amd/csrc gaussiansplat_amd/build.py include | tar -x -C "$W"
 OUT=$PWD/gaussiansplat_amd/lib_$TAG; mkdir -p "$OUT"
-grep -q gs_get_bin_path "$W/include/gsplat.h" || echo 'extern "C" int gs_get_bin_path(gs_ctx *c) { return c ? 0 : -1; }' >> "$W/gaussiansplat_amd/csrc/gs_api_debug.hip"
-grep -q gs_adam_step "$W/include/gsplat.h" || cat >> "$W/gaussiansplat_amd/csrc/gs_api_debug.hip" <<'STUB'
-extern "C" int gs_adam_step(gs_ctx *, const gs_grads *, const gs_grads *, const gs_grads *, const float *, float, float, float, int64_t, int) { return GS_ERR_UNSUPPORTED; }
-extern "C" int gs_backward_adam(gs_ctx *, const float *, int, const gs_grads *, const gs_grads *, const float *, float, float, float, int64_t, int) { return GS_ERR_UNSUPPORTED; }
-STUB
-grep -q gs_density_plan "$W/include/gsplat.h" || cat >> "$W/gaussiansplat_amd/csrc/gs_api_debug.hip" <<'STUB'
-extern "C" int gs_density_accumulate(gs_ctx *, const void *) { return GS_ERR_UNSUPPORTED; }
-extern "C" int gs_density_decide(gs_ctx *, const void *, const void *, int32_t *) { return GS_ERR_UNSUPPORTED; }
-extern "C" int gs_density_plan(gs_ctx *, const int32_t *, int64_t *) { return GS_ERR_UNSUPPORTED; }
-extern "C" int gs_density_restructure(gs_ctx *, const int32_t *, const float *, const gs_grads *, int32_t, const gs_grads *, const gs_grads *, int64_t) { return GS_ERR_UNSUPPORTED; }
-extern "C" int gs_opacity_reset(gs_ctx *, float, float *, float *) { return GS_ERR_UNSUPPORTED; }
-STUB
-grep -q gs_mcmc_plan "$W/include/gsplat.h" || cat >> "$W/gaussiansplat_amd/csrc/gs_api_debug.hip" <<'STUB'
-extern "C" int gs_mcmc_plan(gs_ctx *, float, uint64_t *, int32_t *, int64_t *) { return GS_ERR_UNSUPPORTED; }
-extern "C" int gs_mcmc_sample(gs_ctx *, const uint64_t *, int64_t, const float *, int64_t, int32_t *) { return GS_ERR_UNSUPPORTED; }
-extern "C" int gs_mcmc_relocate(gs_ctx *, const int32_t *, const int32_t *, int64_t, float, int32_t, const gs_grads *) { return GS_ERR_UNSUPPORTED; }
-extern "C" int gs_mcmc_noise(gs_ctx *, const float *, float, float, float) { return GS_ERR_UNSUPPORTED; }
-extern "C" int gs_mcmc_regularize(gs_ctx *, const gs_grads *, float, float) { return GS_ERR_UNSUPPORTED; }
-STUB
+# a stub for every function today's header declares and that commit's does not, written from today's prototypes (tests/abi_header.py: the
+# header reader of the ABI tests).  Pointers become const void *, which C linkage makes harmless and which needs no type the old header lacks.
+python3 - "$(dirname "$0")/../tests" "$W/include/gsplat.h" >> "$W/gaussiansplat_amd/csrc/gs_api_debug.hip" <<'PY'
+import sys
+sys.path.insert(0, sys.argv[1])
+from abi_header import _c_kind, _c_prototypes
+ctype = {"i32": "int32_t", "i64": "int64_t", "f32": "float", "f64": "double", "ptr": "const void *"}
+old = _c_prototypes(sys.argv[2])
+for name, (ret, args) in _c_prototypes().items():
+    if name not in old:
+        assert ret == "int", name
+        body = "return a0 ? 0 : -1;" if name == "gs_get_bin_path" else "return GS_ERR_UNSUPPORTED;"      # (a ctx of that commit took path 0)
+        params = ", ".join("%s a%d" % (ctype[_c_kind(a)[0]], i) for i, a in enumerate(args))
+        print('extern "C" int %s(%s) { %s }' % (name, params, body))
+PY
 objs=()
 for s in "$W"/gaussiansplat_amd/csrc/*.hip; do
   b=$(basename "$s" .hip)
