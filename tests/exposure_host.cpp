@@ -4,7 +4,7 @@
 // OUT: out [3][H][W] and dx [3][H][W] as float32, then the per-pixel terms of the adjoint into E, [12][H W] as float64 (each term the
 // difference of gs_exposure_dE_add's accumulators around one pixel, from + 0: the term itself).
 // Without arguments: a built-in scene (odd sizes, weights of 0 and 1 among them, the two identity consequences) checked in place; what
-// `make -C tests -f exposure.mk sanitize-exposure` runs under ASan + UBSan.
+// `make -C tests sanitize-exposure` runs under ASan + UBSan.
 #include "gs_exposure.h"
 
 #include <cmath>

@@ -6,18 +6,10 @@ The result is a function of a multiset of individually rounded values, so any ex
 """
 import numpy as np
 
+from common import same_bits
+
 NAN, INF = np.float32("nan"), np.float32("inf")
 BOX = 64                                   # GS_KNN_BOX (tests/test_pointcloud_host.py checks it against csrc/gs_knn.h and backend.KNN_BOX)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32).reshape(-1)
-
-
-def same_bits(got, want):
-    g, w = bits(got), bits(want)
-    nan = np.isnan(g.view(np.float32)) & np.isnan(w.view(np.float32))
-    return bool(g.shape == w.shape and np.all((g == w) | nan))
 
 
 def knn_mean_dist2(points, chunk=512):
@@ -164,7 +156,7 @@ def check_planted(name, pts, ref):
         rows = np.array(NONFINITE_ROWS)
         keep = np.setdiff1d(np.arange(len(pts)), rows)
         assert np.isnan(ref[rows]).all() and np.isfinite(ref[keep]).all()
-        assert same_bits(ref[keep], knn_mean_dist2(pts[keep]))
+        assert same_bits(ref[keep], knn_mean_dist2(pts[keep]), nan_equal=True)
     elif name == "too_few":
         assert np.isnan(ref).all()
     elif name == "overflow":

@@ -1,6 +1,6 @@
 // mcmc_host.cpp -- the statements of gaussiansplat_amd/csrc/gs_mcmc.h in a HOST build: a stand-alone program with its own main.
 //     mcmc_host <mode> <in.bin> <out.bin>     tests/test_mcmc_host.py feeds it cases and compares with tests/mcmc_ref.py
-//     mcmc_host                               a built-in scene that checks itself (what `make -C tests -f mcmc.mk sanitize-mcmc` runs)
+//     mcmc_host                               a built-in scene that checks itself (what `make -C tests sanitize-mcmc` runs)
 // Every file starts with int64 n.  Modes and layouts (little endian, packed):
 //   weight    in: float threshold, float opac[n]                                      out: uint32 w[n]
 //   draw      in: int64 m, uint64 cdf[n], float u[m]                                  out: int32 src[m]

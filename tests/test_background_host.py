@@ -8,11 +8,11 @@ plus a constant.  Its gradients are therefore those of sum (C + T bg) . dC."""
 import numpy as np
 import pytest
 
+from common import GRADS
 from gaussiansplat_amd import train as TR
 
 SH_C0 = 0.28209479177387814
 BG = (1.0, 0.25, 0.6)
-GRADS = ("means", "scales", "quats", "opacities", "shs")
 
 
 def test_random_background_is_a_seeded_float32_sequence():

@@ -10,18 +10,16 @@ The bar, per component c: |host - autograd| <= 1e-9 x max_g |autograd[g, c]|.  B
 cancellation was measured as 1e3 .. 1e4 x epsilon (gs_preprocess_bwd.hip's header: 2e-4 .. 2e-3 in fp32), i.e. 1e-13 .. 1e-12 here --
 the bar stands three orders above it.  `make -C tests sanitize-camera-grad` runs the same program under ASan + UBSan."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import camera_ref
-from common import scene_and_cameras
+from common import host_program, run_host, scene_and_cameras
 from gaussiansplat_amd import build as gbuild
 from gaussiansplat_amd import camera as gcam
 from gaussiansplat_amd import optim, synthetic, train
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, W, H = 300, 64, 48
 # (active degree, stored degree)
 CASES = [(0, 0), (1, 1), (2, 2), (3, 3), (1, 3)]
@@ -29,12 +27,7 @@ CASES = [(0, 0), (1, 1), (2, 2), (3, 3), (1, 3)]
 
 @pytest.fixture(scope="module")
 def host_exe(tmp_path_factory):
-    d = tmp_path_factory.mktemp("camera_grad_host")
-    exe = str(d / "camera_grad_host")
-    subprocess.run([gbuild._hipcc(), "-O2", "-std=c++17", "-x", "hip", "--cuda-host-only", "-Wall", "-I", gbuild.CSRC,
-                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "camera_grad_host.cpp"), "-o", exe],
-                   check=True, capture_output=True, text=True)        # (no -ffp-contract=off: the function turns contraction off itself)
-    return exe, d
+    return host_program("camera_grad", tmp_path_factory.mktemp("camera_grad_host"))
 
 
 def camera_words(cam, T, P, W, H):
@@ -43,18 +36,12 @@ def camera_words(cam, T, P, W, H):
     return np.concatenate([f.view(np.uint32), np.array([W, H], np.int32).view(np.uint32)])
 
 
-def run_host(host_exe, tag, sc, deg, cam, T, P, rows):
-    exe, d = host_exe
+def _run_host(host_exe, sc, deg, cam, T, P, rows):
     n = sc["means"].shape[0]
-    shs = np.ascontiguousarray(sc["shs"], np.float32).reshape(n, -1)
-    fin, fout = str(d / f"in_{tag}.bin"), str(d / f"out_{tag}.bin")
-    parts = [np.array([n, deg, shs.shape[1]], np.uint32), camera_words(cam, T, P, W, H)]
-    parts += [np.ascontiguousarray(a, np.float32).reshape(-1).view(np.uint32) for a in (sc["means"], sc["scales"], sc["quats"], sc["opacities"], shs, rows)]
-    np.concatenate(parts).tofile(fin)
-    subprocess.run([exe, fin, fout], check=True, timeout=60)
-    out = np.fromfile(fout, np.float64)
-    assert out.shape == (40 * (n + 1),)
-    return out[:40 * n].reshape(n, 40), out[40 * n:]
+    shs = np.asarray(sc["shs"], np.float32).reshape(n, -1)
+    arrays = [camera_words(cam, T, P, W, H)] + [np.asarray(a, np.float32) for a in (sc["means"], sc["scales"], sc["quats"], sc["opacities"], shs, rows)]
+    per, total = run_host(host_exe, [], np.array([n, deg, shs.shape[1]], np.uint32).tobytes(), arrays, [(np.float64, 40 * n), (np.float64, 40)])
+    return per.reshape(n, 40), total
 
 
 def make_rows(n, seed):
@@ -76,7 +63,7 @@ def case(request, host_exe):
     scp = {k: np.concatenate([v, v[:3]]) for k, v in sc.items()}
     scp["means"][N] = cam.eye; scp["means"][N + 1] = (np.nan, 0.0, 0.0); scp["scales"][N + 2] = 200.0
     rows_p = np.concatenate([rows, np.zeros((3, 10), np.float32)])
-    per, total = run_host(host_exe, f"{deg}_{stored}", scp, deg, cam, T, P, rows_p)
+    per, total = _run_host(host_exe, scp, deg, cam, T, P, rows_p)
     want = camera_ref.rows_scalar_grads(sc, deg, T, P, float(np.float32(cam.fx)), float(np.float32(cam.fy)), cam.eye, cam.lookAt, W, H, rows)
     return dict(deg=deg, per=per, total=total, want=want, rows=rows)
 

@@ -6,16 +6,13 @@ import numpy as np
 import pytest
 
 import density_ref as D
+from common import same_bits
 
 f32 = np.float32
 
 
 def _model(rng, n, k3):
     return [rng.standard_normal((n, w)).astype(f32) for w in (3, 3, 4, 1, k3)]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, f32).view(np.uint32)
 
 
 @pytest.mark.parametrize("n", [0, 1, 7, 300])
@@ -45,7 +42,7 @@ def test_all_keep_is_the_identity_and_all_prune_is_empty():
     sets = [_model(rng, n, 48)]
     new, new_sets = D.restructure(model, np.zeros(n, np.int32), None, sets=sets)
     for a, b in zip(new + new_sets[0], model + sets[0]):
-        assert np.array_equal(_bits(a), _bits(b))
+        assert same_bits(a, b)
     new, new_sets = D.restructure(model, np.full(n, 3, np.int32), None, sets=sets)
     assert all(a.shape[0] == 0 for a in new + new_sets[0])
 
@@ -61,8 +58,8 @@ def test_rows_are_ordered_survivors_clones_children():
     surv, cl, sp = np.flatnonzero(action <= 1), np.flatnonzero(action == 1), np.flatnonzero(action == 2)
     assert np.array_equal(new[3][:, 0], np.concatenate([surv, cl, np.repeat(sp, 2)]).astype(f32))
     kids = slice(len(surv) + len(cl), None)
-    assert np.array_equal(_bits(new[1][kids]), _bits(np.repeat(model[1][sp] - f32(0.25), 2, axis=0)))
-    assert np.array_equal(_bits(new[2][kids]), _bits(np.repeat(model[2][sp], 2, axis=0)))
+    assert same_bits(new[1][kids], np.repeat(model[1][sp] - f32(0.25), 2, axis=0))
+    assert same_bits(new[2][kids], np.repeat(model[2][sp], 2, axis=0))
     # a child sits at mean + R diag(exp(scale)) z: with z = 0 it sits on its source
     new0, _ = D.restructure(model, action, np.zeros((n, 2, 3), f32))
     assert np.array_equal(new0[0][kids], np.repeat(model[0][sp], 2, axis=0))
@@ -103,7 +100,7 @@ def test_decide_thresholds_are_exact_and_nan_is_kept():
 def test_opacity_reset_reference():
     o = np.array([[-6.0], [5.0], [np.nan], [-4.59512], [np.inf]], f32)
     out, m, v = D.opacity_reset(o, f32(-4.59512), np.ones((5, 1), f32), None)
-    assert np.array_equal(_bits(out), _bits(np.array([[-6.0], [-4.59512], [np.nan], [-4.59512], [-4.59512]], f32)))
+    assert same_bits(out, np.array([[-6.0], [-4.59512], [np.nan], [-4.59512], [-4.59512]], f32))
     assert v is None and not m.any()
 
 
@@ -118,7 +115,7 @@ def test_accumulate_reference_visibility():
     g = np.zeros((6, 10), f32); g[:, 4] = 3e-3; g[:, 5] = -4e-3
     gs, cnt, mx = D.accumulate(np.zeros(6, f32), np.zeros(6, np.int32), np.full(6, 7, np.int32), g, W, H, vis, ext)
     a, b = f32(100.0) * f32(3e-3), f32(68.0) * f32(-4e-3)
-    assert np.array_equal(_bits(gs), _bits(np.full(6, np.sqrt(f32(a * a + b * b)), f32)))
+    assert same_bits(gs, np.full(6, np.sqrt(f32(a * a + b * b)), f32))
     assert cnt.tolist() == [1, 0, 1, 0, 0, 0] and mx.tolist() == [21, 7, 7, 7, 7, 7]
 
 

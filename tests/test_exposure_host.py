@@ -2,47 +2,26 @@
 NumPy restatement (tests/exposure_ref.py), bit for bit; optim.ExponentialLR against its closed form; the argument checks of
 appearance.Exposure and of train.trainStep's exposure / view pair that need no device."""
 import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import exposure_ref as ER
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _same_bits(a, b):
-    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
-
+from common import host_program, run_host, same_bits
 
 @pytest.fixture(scope="module")
 def host_exe(tmp_path_factory):
-    from gaussiansplat_amd import build as gbuild
-    d = tmp_path_factory.mktemp("exposure_host")
-    exe = str(d / "exposure_host")
-    subprocess.run([gbuild._hipcc(), "-O2", "-std=c++17", "-x", "hip", "--cuda-host-only", "-Wall", "-I", gbuild.CSRC,
-                    os.path.join(ROOT, "tests", "exposure_host.cpp"), "-o", exe], check=True, capture_output=True, text=True)
-    return d, exe
+    return host_program("exposure", tmp_path_factory.mktemp("exposure_host"))
 
 
 def _run_host(host_exe, x, d, E, w=None):
-    dirn, exe = host_exe
-    fin, fout = str(dirn / "in.bin"), str(dirn / "out.bin")
     _, H, W = x.shape
-    with open(fin, "wb") as fh:
-        fh.write(np.array([W, H, int(w is not None)], np.int32).tobytes())
-        for a in (E, x, d) + ((w,) if w is not None else ()):
-            fh.write(np.ascontiguousarray(a, np.float32).tobytes())
-    subprocess.run([exe, fin, fout], check=True, timeout=60)
-    raw = open(fout, "rb").read()
     n = 3 * H * W
-    assert len(raw) == 4 * 2 * n + 8 * 12 * H * W
-    out = np.frombuffer(raw, np.float32, n, 0).reshape(3, H, W)
-    dx = np.frombuffer(raw, np.float32, n, 4 * n).reshape(3, H, W)
-    terms = np.frombuffer(raw, np.float64, 12 * H * W, 8 * n).reshape(3, 4, H * W)
-    return out, dx, terms
+    arrays = [np.asarray(a, np.float32) for a in (E, x, d) + ((w,) if w is not None else ())]
+    out, dx, terms = run_host(host_exe, [], np.array([W, H, int(w is not None)], np.int32).tobytes(), arrays,
+                              [(np.float32, n), (np.float32, n), (np.float64, 12 * H * W)])
+    return out.reshape(3, H, W), dx.reshape(3, H, W), terms.reshape(3, 4, H * W)
 
 
 def _weights(W, H):
@@ -56,10 +35,10 @@ def test_header_statements_equal_the_restatement_bit_for_bit(host_exe, W, H):
     x, d, E, _ = ER.case(W, H, False)
     for w in _weights(W, H):
         out, dx, terms = _run_host(host_exe, x, d, E, w)
-        assert _same_bits(out, ER.forward(x, E, w))
-        assert _same_bits(dx, ER.backward_image(d, E, w))
+        assert same_bits(out, ER.forward(x, E, w))
+        assert same_bits(dx, ER.backward_image(d, E, w))
         # float64(g) * float64(x), and g itself in column 3; the program reads a term off an accumulator that started at + 0: -0 comes as +0
-        assert _same_bits(terms, ER.terms(x, d, w) + 0.0)
+        assert same_bits(terms, ER.terms(x, d, w) + 0.0)
 
 
 @pytest.mark.parametrize("W,H", [(5, 7), (129, 33)])
@@ -69,20 +48,20 @@ def test_identity_row_returns_the_image_and_masks_exactly(host_exe, W, H):
     x.reshape(-1)[3:5] = [np.float32(3.4e38), np.float32(-3.4e38)]
     I = ER.identity()
     out, dx, _ = _run_host(host_exe, x, d, I, None)
-    assert np.array_equal(out, x) and _same_bits(out + np.float32(0), x + np.float32(0))     # the bits, but for -0 -> +0
+    assert np.array_equal(out, x) and same_bits(out + np.float32(0), x + np.float32(0))      # the bits, but for -0 -> +0
     assert out.reshape(-1)[0] == 0 and not np.signbit(out.reshape(-1)[0])
     nz = x != 0
-    assert _same_bits(out[nz], x[nz])
+    assert same_bits(out[nz], x[nz])
     assert np.array_equal(dx, d)
     for w in _weights(W, H)[1:]:
         out, dx, _ = _run_host(host_exe, x, d, I, w)
-        assert _same_bits(out, w[None] * (x + np.float32(0)))                # w * x exactly: masking a target needs no kernel of its own
+        assert same_bits(out, w[None] * (x + np.float32(0)))                 # w * x exactly: masking a target needs no kernel of its own
         assert np.array_equal(out, w[None] * x)
 
 
 def test_host_program_checks_itself_without_arguments(host_exe):
-    """what `make -C tests -f exposure.mk sanitize-exposure` runs under ASan + UBSan: the built-in scene"""
-    r = subprocess.run([host_exe[1]], capture_output=True, text=True, timeout=60)
+    """what `make -C tests sanitize-exposure` runs under ASan + UBSan: the built-in scene"""
+    r = subprocess.run([host_exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and "0 mismatches" in r.stdout, r.stdout + r.stderr
 
 

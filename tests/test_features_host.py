@@ -5,29 +5,14 @@ The statement is a __host__ __device__ function with contraction off: tests/feat
 process on the means and the view matrix the oracle gets.  Equality is of bit patterns, NaN matching NaN, no tolerance: every operation
 is individually rounded on both sides.  Non-finite means are planted: they pass through as IEEE gives them.  Beside it, the host-only
 pieces of the feature: the grey export of a depth map."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from common import scene_and_cameras
-from gaussiansplat_amd import build as gbuild
+from common import bits, host_program, run_host, same_bits, scene_and_cameras
 from gaussiansplat_amd import export
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, W, H, DEG, SEED = 4096, 400, 300, 1, 71
 NAN, INF = np.float32("nan"), np.float32("inf")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32).reshape(-1)
-
-
-def same_bits(got, want):
-    g, w = bits(got), bits(want)
-    nan = np.isnan(g.view(np.float32)) & np.isnan(w.view(np.float32))
-    return bool(np.all((g == w) | nan))
 
 
 @pytest.fixture(scope="module")
@@ -43,15 +28,8 @@ def data(oracle):
 
 @pytest.fixture(scope="module")
 def host_z(data, tmp_path_factory):
-    d = tmp_path_factory.mktemp("features_host")
-    exe, fin, fout = str(d / "features_host"), str(d / "in.bin"), str(d / "out.bin")
-    subprocess.run([gbuild._hipcc(), "-O2", "-std=c++17", "-x", "hip", "--cuda-host-only", "-Wall", "-I", gbuild.CSRC,
-                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "features_host.cpp"), "-o", exe],
-                   check=True, capture_output=True, text=True)        # (no -ffp-contract=off: the function turns contraction off itself)
-    np.concatenate([np.array([N], np.uint32), bits(data["T"]), bits(data["means"])]).tofile(fin)
-    subprocess.run([exe, fin, fout], check=True, timeout=60)
-    z = np.fromfile(fout, np.float32)
-    assert z.shape == (N,)
+    exe = host_program("features", tmp_path_factory.mktemp("features_host"))
+    (z,) = run_host(exe, [], np.uint32(N).tobytes(), [data["T"], data["means"]], [(np.float32, N)])
     return z
 
 
@@ -63,7 +41,7 @@ def test_the_oracle_depths_are_real_work(data):
 
 
 def test_view_depth_statement_equals_the_oracle_bit_for_bit(data, host_z):
-    assert same_bits(host_z, data["ts"][:, 2])
+    assert same_bits(host_z, data["ts"][:, 2], nan_equal=True)
     fin = np.isfinite(host_z)
     assert np.array_equal(bits(host_z[fin]), bits(data["ts"][fin, 2]))   # finite values: no NaN allowance hides anything
 
@@ -76,7 +54,7 @@ def test_view_depth_statement_is_the_written_order(data, host_z):
         s = s + T[6] * m[:, 1]
         s = s + T[10] * m[:, 2]
         s = s + T[14] * np.float32(1.0)
-    assert s.dtype == np.float32 and same_bits(host_z, s)
+    assert s.dtype == np.float32 and same_bits(host_z, s, nan_equal=True)
 
 
 def test_depth_to_gray8():

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import adam_ref as A
-from common import rel_l2
+from common import host, perturbed_start, rel_l2, same_bits, synthetic_renderer
 
 pytestmark = pytest.mark.gpu
 
@@ -16,26 +16,9 @@ W, H = 128, 96
 N = 1281                                    # n % 4 == 1 and not a multiple of 256
 
 
-def _renderer(n, deg, seed, W=W, H=H, **kw):
-    from gaussiansplat_amd import renderer as R, synthetic
-    scene = synthetic.make_scene(n, W, H, deg, seed=seed)
-    return R.getRenderer("GAUSSIAN_3D", (W, H, 3), (16, 16), None, scene, **kw)
-
-
 def _params(r):
     sd = r.splatData
     return [sd.means, sd.scales, sd.quaternions, sd.opacities, sd.shs]
-
-
-def _host(ts):
-    import torch
-    torch.cuda.synchronize()
-    return [t.detach().cpu().numpy().reshape(t.shape[0], -1).copy() for t in ts]
-
-
-def _bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def _rand_grads(rng, n, widths):
@@ -87,10 +70,10 @@ def _step(r, buf, t, lr=LR6, null=(), selective=False):
 @pytest.mark.parametrize("deg", [0, 1, 2, 3])
 def test_standalone_dense_bitwise_and_against_torch(deg, layout):
     widths = [3, 3, 4, 1, 3 * (deg + 1) ** 2]
-    r = _renderer(N, deg, seed=40 + deg)
+    r = synthetic_renderer(N, deg, seed=40 + deg)
     buf = _Buffers(N, widths, layout)
     rng = np.random.default_rng(deg)
-    P, M, V = _host(_params(r)), [np.zeros((N, w), np.float32) for w in widths], [np.zeros((N, w), np.float32) for w in widths]
+    P, M, V = host(_params(r)), [np.zeros((N, w), np.float32) for w in widths], [np.zeros((N, w), np.float32) for w in widths]
     p0, seq = [a.copy() for a in P], []
     for t in range(1, 6):
         g = _rand_grads(rng, N, widths)
@@ -98,9 +81,9 @@ def test_standalone_dense_bitwise_and_against_torch(deg, layout):
         _Buffers.fill(buf.g, g)
         _step(r, buf, t)
         P, M, V = A.step(P, g, M, V, LR6, B1, B2, EPS, t)
-    got = _host(_params(r)) + _host(buf.m) + _host(buf.v)
+    got = host(_params(r)) + host(buf.m) + host(buf.v)
     for k, (a, b) in enumerate(zip(got, P + M + V)):
-        assert _bits_equal(a, b), (k, np.flatnonzero(a.view(np.uint32) != b.view(np.uint32))[:5])
+        assert same_bits(a, b), (k, np.flatnonzero(a.view(np.uint32) != b.view(np.uint32))[:5])
     for k in range(5):                                         # torch: one run per group, the SH columns as two
         for j, cs in enumerate([slice(None)] if k < 4 else [slice(0, 3), slice(3, None)]):
             if cs.start == 3 and widths[4] == 3:
@@ -114,7 +97,7 @@ def test_standalone_dense_bitwise_and_against_torch(deg, layout):
 @pytest.mark.parametrize("deg", [0, 3])
 def test_standalone_selective_leaves_dead_rows_alone(deg, layout):
     widths = [3, 3, 4, 1, 3 * (deg + 1) ** 2]
-    r = _renderer(N, deg, seed=50 + deg)
+    r = synthetic_renderer(N, deg, seed=50 + deg)
     buf = _Buffers(N, widths, layout)
     rng = np.random.default_rng(10 + deg)
     for t in (1, 2):                                           # dense steps first: non-zero moments
@@ -127,19 +110,19 @@ def test_standalone_selective_leaves_dead_rows_alone(deg, layout):
         a[dead & (rng.random(N) < 0.5)] = -0.0                 # some dead rows are all -0
     g[4][np.flatnonzero(dead)[::3], 0] = -0.0                 # and some mix +0 and -0
     _Buffers.fill(buf.g, g)
-    before = _host(_params(r)) + _host(buf.m) + _host(buf.v)
+    before = host(_params(r)) + host(buf.m) + host(buf.v)
     _step(r, buf, 3, selective=True)
-    after = _host(_params(r)) + _host(buf.m) + _host(buf.v)
+    after = host(_params(r)) + host(buf.m) + host(buf.v)
     P, M, V = A.step(before[0:5], g, before[5:10], before[10:15], LR6, B1, B2, EPS, 3)   # the dense step
     for a, b, d in zip(after, before, P + M + V):
-        assert _bits_equal(a[dead], b[dead])
-        assert _bits_equal(a[~dead], d[~dead])
+        assert same_bits(a[dead], b[dead])
+        assert same_bits(a[~dead], d[~dead])
     assert 0.3 < dead.mean() < 0.7
 
 
 def test_null_gradient_freezes_group_and_zero_rate_still_moves_moments():
     deg, widths = 1, [3, 3, 4, 1, 12]
-    r = _renderer(N, deg, seed=60)
+    r = synthetic_renderer(N, deg, seed=60)
     buf = _Buffers(N, widths, "flat")
     rng = np.random.default_rng(60)
     _Buffers.fill(buf.m, [rng.standard_normal((N, w)).astype(np.float32) * 0.01 for w in widths])
@@ -147,18 +130,18 @@ def test_null_gradient_freezes_group_and_zero_rate_still_moves_moments():
     g = _rand_grads(rng, N, widths)
     _Buffers.fill(buf.g, g)
     lr = list(LR6); lr[3] = 0.0                                # opacities: lr 0
-    before = _host(_params(r)) + _host(buf.m) + _host(buf.v)
+    before = host(_params(r)) + host(buf.m) + host(buf.v)
     r._begin()
     r.ctx.adam_step(buf.struct(buf.g, null=(1,)), buf.struct(buf.m), buf.struct(buf.v), lr, B1, B2, EPS, 4)
-    after = _host(_params(r)) + _host(buf.m) + _host(buf.v)
+    after = host(_params(r)) + host(buf.m) + host(buf.v)
     g2 = list(g); g2[1] = None
     P, M, V = A.step(before[0:5], g2, before[5:10], before[10:15], lr, B1, B2, EPS, 4)
     for a, b in zip(after, P + M + V):
-        assert _bits_equal(a, b)
+        assert same_bits(a, b)
     for k in (1, 6, 11):                                       # scales frozen: p, m, v untouched
-        assert _bits_equal(after[k], before[k])
-    assert _bits_equal(after[3], before[3])                    # lr 0: p unchanged ...
-    assert not _bits_equal(after[8], before[8]) and not _bits_equal(after[13], before[13])   # ... m and v moved
+        assert same_bits(after[k], before[k])
+    assert same_bits(after[3], before[3])                      # lr 0: p unchanged ...
+    assert not same_bits(after[8], before[8]) and not same_bits(after[13], before[13])       # ... m and v moved
     # a frozen group may come without moments at all
     r.ctx.adam_step(buf.struct(buf.g, null=(1,)), buf.struct(buf.m, null=(1,)), buf.struct(buf.v, null=(1,)), lr, B1, B2, EPS, 5)
 
@@ -173,7 +156,7 @@ def test_2d_renderer_step_and_no_fused_form():
     assert opt.lr_vector() == [1e-3, 2e-3, 3e-3, 4e-3, 5e-3, 0.0]
     sd = r.splatData
     params = [sd.means, sd.scales, sd.rotations, sd.opacities, sd.colors]
-    P = _host(params)
+    P = host(params)
     M, V = [np.zeros((N, w), np.float32) for w in widths], [np.zeros((N, w), np.float32) for w in widths]
     rng = np.random.default_rng(70)
     for t in (1, 2):
@@ -181,9 +164,9 @@ def test_2d_renderer_step_and_no_fused_form():
         r.splatGrads.flat.copy_(torch.from_numpy(np.concatenate([a.reshape(-1) for a in g])))
         opt.step()
         P, M, V = A.step(P, g, M, V, opt.lr_vector(), B1, B2, EPS, t)
-    got = _host(params) + A.split_flat(opt.exp_avg.cpu().numpy(), N, widths) + A.split_flat(opt.exp_avg_sq.cpu().numpy(), N, widths)
+    got = host(params) + A.split_flat(opt.exp_avg.cpu().numpy(), N, widths) + A.split_flat(opt.exp_avg_sq.cpu().numpy(), N, widths)
     for a, b in zip(got, P + M + V):
-        assert _bits_equal(a, b)
+        assert same_bits(a, b)
     dC = torch.zeros((3, H, W), device="cuda")
     with pytest.raises(B.GsError) as e:
         r.ctx.backward_adam(dC.data_ptr(), opt._struct(opt.exp_avg), opt._struct(opt.exp_avg_sq), opt.lr_vector(), B1, B2, EPS, 3)
@@ -228,27 +211,13 @@ def test_fused_backward_adam_equals_backward_then_step_c3(selective):
     _fused_vs_unfused(1_000_000, 1920, 1080, 3, selective)
 
 
-def _perturbed_start(n, Wi, Hi, deg):
-    """The scene and start of tests/test_gpu_loss.py::test_sgd_step_and_training_reduces_loss."""
-    from gaussiansplat_amd import renderer as R, synthetic
-    target = synthetic.make_scene(n, Wi, Hi, deg, seed=1)
-    cam = synthetic.scene_camera(Wi)
-    rt = R.getRenderer("GAUSSIAN_3D", (Wi, Hi, 3), (16, 16), None, target)
-    R.forward(rt, (R.preprocess(rt, cam), R.compactIdxs(rt))[0])
-    gt = rt.imageData.clone()
-    start = {k: v.copy() for k, v in target.items()}
-    start["shs"] = (start["shs"] + 0.2 * np.random.default_rng(2).standard_normal(start["shs"].shape)).astype(np.float32)
-    start["opacities"] = (start["opacities"] - 0.5).astype(np.float32)
-    return start, cam, gt
-
-
 def test_trajectory_against_torch_adam():
     """Three trainStep(optimizer=Adam) iterations against a loop that takes gs_backward's gradients and steps torch.optim.Adam."""
     import torch
     from gaussiansplat_amd import renderer as R, train as TR
     from gaussiansplat_amd.optim import Adam
     n, Wi, Hi, deg = 3000, 128, 96, 1
-    start, cam, gt = _perturbed_start(n, Wi, Hi, deg)
+    start, cam, gt = perturbed_start(n, Wi, Hi, deg)
     r1 = R.getRenderer("GAUSSIAN_3D", (Wi, Hi, 3), (16, 16), None, start, deterministic=True, tile_parts=1)
     lf1 = TR.getLossFunction((Wi, Hi, 3), 11, 3, renderer=r1)
     opt = Adam(r1, lr=RATES)
@@ -283,7 +252,7 @@ def test_adam_for_3dgs_beats_the_sgd_run():
     from gaussiansplat_amd import renderer as R, train as TR
     from gaussiansplat_amd.optim import Adam
     n, Wi, Hi, deg = 3000, 128, 96, 1
-    start, cam, gt = _perturbed_start(n, Wi, Hi, deg)
+    start, cam, gt = perturbed_start(n, Wi, Hi, deg)
     extent = float(np.linalg.norm(start["means"].max(0) - start["means"].min(0)) / 2)
     finals = {}
     for name in ("sgd", "adam"):
@@ -305,7 +274,7 @@ def test_multi_view_flat_buffer_step():
     from gaussiansplat_amd.optim import Adam
     n, deg = 3000, 2
     widths = [3, 3, 4, 1, 27]
-    r = _renderer(n, deg, seed=90, deterministic=True, tile_parts=1)
+    r = synthetic_renderer(n, deg, seed=90, deterministic=True, tile_parts=1)
     hv = D.HipViewRenderer(r)
     cams = [synthetic.scene_camera(W, view=v) for v in (0, 1)]
     dCs = [torch.as_tensor(synthetic.make_dC(W, H, 600 + v)).cuda() for v in (0, 1)]
@@ -313,21 +282,21 @@ def test_multi_view_flat_buffer_step():
     torch.cuda.synchronize()
     g = A.split_flat(flat.cpu().numpy().copy(), n, widths)
     assert any(np.any(a != 0) for a in g)
-    P = _host(_params(r))
+    P = host(_params(r))
     opt = Adam(r, lr=RATES)
     opt.step(flat)
     zeros = [np.zeros((n, w), np.float32) for w in widths]
     P, M, V = A.step(P, g, zeros, zeros, opt.lr_vector(), B1, B2, EPS, 1)
-    got = _host(_params(r)) + A.split_flat(opt.exp_avg.cpu().numpy(), n, widths) + A.split_flat(opt.exp_avg_sq.cpu().numpy(), n, widths)
+    got = host(_params(r)) + A.split_flat(opt.exp_avg.cpu().numpy(), n, widths) + A.split_flat(opt.exp_avg_sq.cpu().numpy(), n, widths)
     for a, b in zip(got, P + M + V):
-        assert _bits_equal(a, b)
+        assert same_bits(a, b)
 
 
 def test_invalid_arguments_are_refused_and_write_nothing():
     import torch
     from gaussiansplat_amd import backend as B, renderer as R, synthetic
     deg, widths = 1, [3, 3, 4, 1, 12]
-    r = _renderer(N, deg, seed=95)
+    r = synthetic_renderer(N, deg, seed=95)
     cam = synthetic.scene_camera(W)
     # gs_backward_adam before any gs_forward fails like gs_backward
     buf = _Buffers(N, widths, "separate")

@@ -11,7 +11,7 @@ import functools
 import numpy as np
 import pytest
 
-from common import hip_context, rel_l2, scene_and_cameras
+from common import GRADS, hip_context, refused, rel_l2, same_bits, scene_and_cameras
 
 pytestmark = pytest.mark.gpu
 
@@ -19,7 +19,6 @@ BG = (1.0, 0.25, 0.6)
 SH_C0 = 0.28209479177387814
 PIX_ATOL, PIX_RTOL = 1e-4, 1e-4                                            # tests/test_gpu_parity.py
 GRAD_REL_L2 = 1e-3
-GRADS = ("means", "scales", "quats", "opacities", "shs")
 GRADS_2D = ("means", "scales", "rots", "opacities", "colors")
 LR6 = (1e-3, 4e-3, 2e-3, 5e-2, 2.5e-3, 1.25e-4)
 B1, B2, EPS = 0.9, 0.999, 1e-8
@@ -210,13 +209,6 @@ def test_gradients_2d_are_the_oracle_twins(oracle, t_min):
 FN, FW, FH, FDEG = 1281, 128, 96, 1
 
 
-def _bits(t):
-    import torch
-    if isinstance(t, torch.Tensor):
-        t = t.detach().cpu().numpy()
-    return np.ascontiguousarray(t, np.float32).view(np.uint32)
-
-
 class _Rig:
     """One deterministic ctx over a device copy of a scene, on the legacy default stream (in order with torch's copies)."""
 
@@ -290,8 +282,8 @@ def test_backward_adam_equals_backward_then_adam_step_under_a_background(selecti
         res[how] = [t.cpu().numpy().copy() for t in rig.p + mt + vt]
         rig.close()
     for k, (a, b) in enumerate(zip(res["fused"], res["steps"])):
-        assert np.array_equal(_bits(a), _bits(b)), k
-    assert not np.array_equal(_bits(res["fused"][0]), _bits(res["black"][0]))   # the background reached the step of the means
+        assert same_bits(a, b), k
+    assert not same_bits(res["fused"][0], res["black"][0])                      # the background reached the step of the means
 
 
 def test_backward_sgd_equals_backward_then_sgd_step_under_a_background():
@@ -311,18 +303,11 @@ def test_backward_sgd_equals_backward_then_sgd_step_under_a_background():
         res[how] = [t.cpu().numpy().copy() for t in rig.p]
         rig.close()
     for k, (a, b) in enumerate(zip(res["fused"], res["steps"])):
-        assert np.array_equal(_bits(a), _bits(b)), k
-    assert not np.array_equal(_bits(res["fused"][0]), _bits(res["black"][0]))
+        assert same_bits(a, b), k
+    assert not same_bits(res["fused"][0], res["black"][0])
 
 
 # ---------------------------------------------------------------- e. contract
-def _refused(call, text):
-    from gaussiansplat_amd import backend as B
-    with pytest.raises(B.GsError) as e:
-        call()
-    assert e.value.code == B.GS_ERR_INVALID and text in str(e.value), str(e.value)
-
-
 def test_contract_default_refusals_and_the_frame():
     from gaussiansplat_amd import backend as B
     ctx = _ctx3d("small")
@@ -342,7 +327,7 @@ def test_contract_default_refusals_and_the_frame():
     ctx.set_background((0.5, 0.25, 0.125))                                # the value in force: the frame stands
     ctx.backward(dC, g)
     ctx.set_background(BG)                                                # a changed value: the image is stale ...
-    _refused(lambda: ctx.backward(dC, g), "gs_forward first")
+    refused(lambda: ctx.backward(dC, g), "gs_forward first")
     img, tr = ctx.forward_host()                                          # ... the lists are not: no gs_bin needed
     ctx.backward(dC, g)
     black = _ctx3d("small")

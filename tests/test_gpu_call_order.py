@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from common import hip_context, scene_and_cameras
+from common import hip_context, refused, scene_and_cameras
 from gaussiansplat_amd import synthetic
 
 pytestmark = pytest.mark.gpu
@@ -17,14 +17,6 @@ N2D = 32
 LR6, B1, B2, EPS = [1e-3] * 6, 0.9, 0.999, 1e-8
 COMPOSITE_ONLY, PARAMS_ONLY, PARAMS_SH = 2, 4, 8            # GS_BWD_* (include/gsplat.h)
 KEYS = ("means", "scales", "quats", "opacities", "shs")
-
-
-def _refused(call, text, code=None):
-    from gaussiansplat_amd import backend as B
-    with pytest.raises(B.GsError) as e:
-        call()
-    assert e.value.code == (B.GS_ERR_INVALID if code is None else code), str(e.value)
-    assert text in str(e.value), str(e.value)
 
 
 def _scene(seed=3):
@@ -80,9 +72,9 @@ def test_fresh_ctx_refuses_every_call_out_of_order():
     g = ctx.grads_alloc()
     scratch = torch.zeros(4 * N + 64, dtype=torch.float32, device="cuda")
     p = scratch.data_ptr()
-    _refused(ctx.preprocess, "gs_preprocess: gs_set_camera first")
-    _refused(ctx.bin, "gs_bin: gs_preprocess first")
-    _refused(ctx.forward_device, "gs_forward: gs_bin first")
+    refused(ctx.preprocess, "gs_preprocess: gs_set_camera first")
+    refused(ctx.bin, "gs_bin: gs_preprocess first")
+    refused(ctx.forward_device, "gs_forward: gs_bin first")
     for call in (lambda: ctx._chk(ctx.L.gs_backward(ctx.h, C.c_void_p(dC.data_ptr()), 1, C.byref(g))),
                  lambda: ctx.backward(dC.data_ptr(), g, overwrite=True),
                  lambda: ctx.backward(dC.data_ptr(), g, phase="composite"),
@@ -90,37 +82,37 @@ def test_fresh_ctx_refuses_every_call_out_of_order():
                  lambda: ctx.backward_sgd(dC.data_ptr(), 1e-3),
                  lambda: ctx.backward_adam(dC.data_ptr(), mo.m, mo.v, LR6, B1, B2, EPS, 1),
                  lambda: ctx.backward_adam(dC.data_ptr(), mo.m, mo.v, LR6, B1, B2, EPS, 1, selective=True)):
-        _refused(call, "gs_backward: gs_forward first")
-    _refused(lambda: ctx.get_array(B.ARR_DEPTH_KEY), "gs_get_array: gs_preprocess first")
-    _refused(lambda: ctx.get_array(B.ARR_TILE_RECT), "gs_get_array: gs_preprocess first")
-    _refused(lambda: ctx.get_array(B.ARR_SORT_IDXS), "gs_get_array: gs_bin first")
-    _refused(lambda: ctx.get_array(B.ARR_TILE_RANGES), "gs_get_array: gs_bin first")
-    _refused(lambda: ctx.get_array(B.ARR_GRAD2D), "gs_get_array: gs_backward first")
-    _refused(lambda: ctx.color_grads_pack(p), "gs_color_grads_pack: gs_backward first")
-    _refused(lambda: ctx.color_rows_pack(None, N, p, p + 64, p + 4 * 64 + 12 * N), "gs_color_rows_pack: gs_backward first")
-    _refused(ctx.tile_parts_of_frame, "gs_get_tile_parts: gs_forward first")
-    _refused(ctx.work_counters, "gs_get_work_counters: gs_forward first")
-    _refused(ctx.work_counters_ex, "gs_get_work_counters_ex: gs_forward first")
-    _refused(ctx.list_stats, "gs_get_list_stats: gs_forward first")
-    _refused(ctx.tail_fill_blocks, "gs_debug_tail_fill: gs_forward first")
-    _refused(ctx.bin_path_of_frame, "gs_get_bin_path: gs_bin first")
-    _refused(lambda: ctx.time_composite(0, 0, 1), "gs_debug_time_composite: gs_forward first")
+        refused(call, "gs_backward: gs_forward first")
+    refused(lambda: ctx.get_array(B.ARR_DEPTH_KEY), "gs_get_array: gs_preprocess first")
+    refused(lambda: ctx.get_array(B.ARR_TILE_RECT), "gs_get_array: gs_preprocess first")
+    refused(lambda: ctx.get_array(B.ARR_SORT_IDXS), "gs_get_array: gs_bin first")
+    refused(lambda: ctx.get_array(B.ARR_TILE_RANGES), "gs_get_array: gs_bin first")
+    refused(lambda: ctx.get_array(B.ARR_GRAD2D), "gs_get_array: gs_backward first")
+    refused(lambda: ctx.color_grads_pack(p), "gs_color_grads_pack: gs_backward first")
+    refused(lambda: ctx.color_rows_pack(None, N, p, p + 64, p + 4 * 64 + 12 * N), "gs_color_rows_pack: gs_backward first")
+    refused(ctx.tile_parts_of_frame, "gs_get_tile_parts: gs_forward first")
+    refused(ctx.work_counters, "gs_get_work_counters: gs_forward first")
+    refused(ctx.work_counters_ex, "gs_get_work_counters_ex: gs_forward first")
+    refused(ctx.list_stats, "gs_get_list_stats: gs_forward first")
+    refused(ctx.tail_fill_blocks, "gs_debug_tail_fill: gs_forward first")
+    refused(ctx.bin_path_of_frame, "gs_get_bin_path: gs_bin first")
+    refused(lambda: ctx.time_composite(0, 0, 1), "gs_debug_time_composite: gs_forward first")
     # the frame step by step: each call opens the next one and nothing beyond it
     ctx.set_camera(T, P, float(np.float32(cam.fx)), float(np.float32(cam.fy)), float(np.float32(cam.near)), float(np.float32(cam.far)),
                    cam.eye, cam.lookAt, W, H)
     ctx.preprocess()
     assert ctx.get_array(B.ARR_DEPTH_KEY).shape == (N,)
-    _refused(lambda: ctx.get_array(B.ARR_SORT_IDXS), "gs_get_array: gs_bin first")
-    _refused(ctx.forward_device, "gs_forward: gs_bin first")
+    refused(lambda: ctx.get_array(B.ARR_SORT_IDXS), "gs_get_array: gs_bin first")
+    refused(ctx.forward_device, "gs_forward: gs_bin first")
     ctx.bin()
     assert ctx.get_array(B.ARR_SORT_IDXS).shape == (N,) and ctx.bin_path_of_frame() in (0, 1, 2, 3)
-    _refused(lambda: ctx.backward(dC.data_ptr(), g), "gs_backward: gs_forward first")
-    _refused(ctx.tile_parts_of_frame, "gs_get_tile_parts: gs_forward first")
+    refused(lambda: ctx.backward(dC.data_ptr(), g), "gs_backward: gs_forward first")
+    refused(ctx.tile_parts_of_frame, "gs_get_tile_parts: gs_forward first")
     ctx.forward_device()
     assert ctx.tile_parts_of_frame() in (1, 2, 4) and ctx.time_composite(0, 0, 1) >= 0.0
-    _refused(lambda: ctx.time_composite(1, 0, 1), "gs_debug_time_composite: gs_backward first")
-    _refused(lambda: ctx.get_array(B.ARR_GRAD2D), "gs_get_array: gs_backward first")
-    _refused(lambda: ctx.color_grads_pack(p), "gs_color_grads_pack: gs_backward first")
+    refused(lambda: ctx.time_composite(1, 0, 1), "gs_debug_time_composite: gs_backward first")
+    refused(lambda: ctx.get_array(B.ARR_GRAD2D), "gs_get_array: gs_backward first")
+    refused(lambda: ctx.color_grads_pack(p), "gs_color_grads_pack: gs_backward first")
     ctx.backward(dC.data_ptr(), g, overwrite=True)
     assert ctx.time_composite(1, 0, 1) >= 0.0 and ctx.get_array(B.ARR_GRAD2D).shape == (N, 10)
     ctx.close()
@@ -144,32 +136,32 @@ def test_what_each_call_leaves_of_a_complete_frame():
                  lambda: ctx.backward_adam(dC.data_ptr(), mo.m, mo.v, LR6, B1, B2, EPS, 2)):
         _frame(ctx, dC, g)
         call()
-        _refused(ctx.bin, "gs_bin: gs_preprocess first")
-        _refused(ctx.forward_device, "gs_forward: gs_bin first")
-        _refused(lambda: ctx.backward(dC.data_ptr(), g), "gs_backward: gs_forward first")
-        _refused(lambda: ctx.get_array(B.ARR_DEPTH_KEY), "gs_get_array: gs_preprocess first")
+        refused(ctx.bin, "gs_bin: gs_preprocess first")
+        refused(ctx.forward_device, "gs_forward: gs_bin first")
+        refused(lambda: ctx.backward(dC.data_ptr(), g), "gs_backward: gs_forward first")
+        refused(lambda: ctx.get_array(B.ARR_DEPTH_KEY), "gs_get_array: gs_preprocess first")
     # other output buffers: the lists stand, the picture does not
     _frame(ctx, dC, g)
     ctx.bind_outputs()
-    _refused(lambda: ctx.backward(dC.data_ptr(), g), "gs_backward: gs_forward first")
-    _refused(lambda: ctx.get_array(B.ARR_GRAD2D), "gs_get_array: gs_backward first")
+    refused(lambda: ctx.backward(dC.data_ptr(), g), "gs_backward: gs_forward first")
+    refused(lambda: ctx.get_array(B.ARR_GRAD2D), "gs_get_array: gs_backward first")
     ctx.forward_device()                                                    # accepted without a new gs_bin
     ctx.backward(dC.data_ptr(), g, overwrite=True)
     # a new preprocess
     ctx.preprocess()
-    _refused(ctx.forward_device, "gs_forward: gs_bin first")
-    _refused(lambda: ctx.backward(dC.data_ptr(), g), "gs_backward: gs_forward first")
+    refused(ctx.forward_device, "gs_forward: gs_bin first")
+    refused(lambda: ctx.backward(dC.data_ptr(), g), "gs_backward: gs_forward first")
     # a new bin
     _frame(ctx, dC, g)
     ctx.bin()
-    _refused(lambda: ctx.backward(dC.data_ptr(), g), "gs_backward: gs_forward first")
-    _refused(lambda: ctx.get_array(B.ARR_GRAD2D), "gs_get_array: gs_backward first")
+    refused(lambda: ctx.backward(dC.data_ptr(), g), "gs_backward: gs_forward first")
+    refused(lambda: ctx.get_array(B.ARR_GRAD2D), "gs_get_array: gs_backward first")
     # a second forward: the first one's composite adjoint is gone
     _frame(ctx, dC, g)
     ctx.forward_device()
-    _refused(lambda: ctx.backward(dC.data_ptr(), g, phase="params"), "gs_backward: GS_BWD_PARAMS_ONLY needs a GS_BWD_COMPOSITE_ONLY call on this frame")
-    _refused(lambda: ctx.get_array(B.ARR_GRAD2D), "gs_get_array: gs_backward first")
-    _refused(lambda: ctx.time_composite(1, 0, 1), "gs_debug_time_composite: gs_backward first")
+    refused(lambda: ctx.backward(dC.data_ptr(), g, phase="params"), "gs_backward: GS_BWD_PARAMS_ONLY needs a GS_BWD_COMPOSITE_ONLY call on this frame")
+    refused(lambda: ctx.get_array(B.ARR_GRAD2D), "gs_get_array: gs_backward first")
+    refused(lambda: ctx.time_composite(1, 0, 1), "gs_debug_time_composite: gs_backward first")
     ctx.backward(dC.data_ptr(), g, overwrite=True)                          # ... and the frame is still good for a whole backward
     ctx.synchronize()
     ctx.close()
@@ -209,23 +201,23 @@ def test_flag_errors_one_fault_per_call():
     dC, mo = _dC_dev(), _Moments()
     g = ctx.grads_alloc()
     ctx.preprocess(); ctx.bin(); ctx.forward_device()
-    _refused(lambda: _backward_ex(ctx, dC.data_ptr(), g, COMPOSITE_ONLY | PARAMS_ONLY), "gs_backward: COMPOSITE_ONLY and PARAMS_ONLY exclude each other")
-    _refused(lambda: _backward_ex(ctx, dC.data_ptr(), g, PARAMS_SH), "gs_backward: GS_BWD_PARAMS_SH / _GEOM need GS_BWD_PARAMS_ONLY")
-    _refused(lambda: ctx.backward_sgd(dC.data_ptr(), 0.0), "gs_backward_sgd: lr must be non-zero")
-    _refused(lambda: _backward_ex(ctx, 0, g, 1), "gs_backward: NULL argument")
-    _refused(lambda: _backward_ex(ctx, dC.data_ptr(), None, 1), "gs_backward: NULL argument")
-    _refused(lambda: ctx.backward_sgd(0, 1e-3), "gs_backward: NULL argument")
-    _refused(lambda: ctx.backward_adam(0, mo.m, mo.v, LR6, B1, B2, EPS, 1), "gs_backward_adam: NULL argument")
-    _refused(lambda: ctx._chk(ctx.L.gs_backward_ex(ctx.h, C.c_void_p(dC.data_ptr()), 7, C.byref(g), 1)), "gs_backward: bad mem")
+    refused(lambda: _backward_ex(ctx, dC.data_ptr(), g, COMPOSITE_ONLY | PARAMS_ONLY), "gs_backward: COMPOSITE_ONLY and PARAMS_ONLY exclude each other")
+    refused(lambda: _backward_ex(ctx, dC.data_ptr(), g, PARAMS_SH), "gs_backward: GS_BWD_PARAMS_SH / _GEOM need GS_BWD_PARAMS_ONLY")
+    refused(lambda: ctx.backward_sgd(dC.data_ptr(), 0.0), "gs_backward_sgd: lr must be non-zero")
+    refused(lambda: _backward_ex(ctx, 0, g, 1), "gs_backward: NULL argument")
+    refused(lambda: _backward_ex(ctx, dC.data_ptr(), None, 1), "gs_backward: NULL argument")
+    refused(lambda: ctx.backward_sgd(0, 1e-3), "gs_backward: NULL argument")
+    refused(lambda: ctx.backward_adam(0, mo.m, mo.v, LR6, B1, B2, EPS, 1), "gs_backward_adam: NULL argument")
+    refused(lambda: ctx._chk(ctx.L.gs_backward_ex(ctx.h, C.c_void_p(dC.data_ptr()), 7, C.byref(g), 1)), "gs_backward: bad mem")
     ctx.backward(dC.data_ptr(), g, overwrite=True)                          # none of them touched the frame
     ctx.synchronize()
     ctx.close()
     c2 = _ctx2d()
     g2 = c2.grads_alloc()
     c2.preprocess(); c2.bin(); c2.forward_device()
-    _refused(lambda: _backward_ex(c2, dC.data_ptr(), g2, PARAMS_ONLY | PARAMS_SH), "gs_backward: GS_BWD_PARAMS_SH / _GEOM: 3-D renderer only", B.GS_ERR_UNSUPPORTED)
-    _refused(lambda: c2.backward_sgd(dC.data_ptr(), 1e-3), "gs_backward_sgd: 3-D renderer only", B.GS_ERR_UNSUPPORTED)
-    _refused(lambda: c2.backward_adam(dC.data_ptr(), mo.m, mo.v, LR6, B1, B2, EPS, 1), "gs_backward_adam: 3-D renderer only", B.GS_ERR_UNSUPPORTED)
+    refused(lambda: _backward_ex(c2, dC.data_ptr(), g2, PARAMS_ONLY | PARAMS_SH), "gs_backward: GS_BWD_PARAMS_SH / _GEOM: 3-D renderer only", B.GS_ERR_UNSUPPORTED)
+    refused(lambda: c2.backward_sgd(dC.data_ptr(), 1e-3), "gs_backward_sgd: 3-D renderer only", B.GS_ERR_UNSUPPORTED)
+    refused(lambda: c2.backward_adam(dC.data_ptr(), mo.m, mo.v, LR6, B1, B2, EPS, 1), "gs_backward_adam: 3-D renderer only", B.GS_ERR_UNSUPPORTED)
     c2.backward(dC.data_ptr(), g2, overwrite=True)
     got = c2.grads_read_2d(g2)
     assert all(np.all(np.isfinite(v)) for v in got.values()) and np.any(got["colors"] != 0)
@@ -240,11 +232,11 @@ def test_a_refused_call_changes_nothing():
         g = ctx.grads_alloc()
         ctx.preprocess(); ctx.bin(); ctx.forward_device()
         if refuse:
-            _refused(lambda: ctx.backward_adam(dC.data_ptr(), mo.m, mo.v, LR6, 1.0, B2, EPS, 1), "gs_backward_adam: betas must lie in [0, 1)")
-            _refused(lambda: ctx.backward_adam(dC.data_ptr(), mo.m, mo.v, LR6, B1, -0.5, EPS, 1, selective=True), "gs_backward_adam: betas must lie in [0, 1)")
-            _refused(lambda: ctx.backward_sgd(dC.data_ptr(), 0.0), "gs_backward_sgd: lr must be non-zero")
-            _refused(lambda: _backward_ex(ctx, dC.data_ptr(), g, 1 | COMPOSITE_ONLY | PARAMS_ONLY), "exclude each other")
-            _refused(lambda: _backward_ex(ctx, dC.data_ptr(), g, 1 | PARAMS_ONLY), "needs a GS_BWD_COMPOSITE_ONLY call on this frame")
+            refused(lambda: ctx.backward_adam(dC.data_ptr(), mo.m, mo.v, LR6, 1.0, B2, EPS, 1), "gs_backward_adam: betas must lie in [0, 1)")
+            refused(lambda: ctx.backward_adam(dC.data_ptr(), mo.m, mo.v, LR6, B1, -0.5, EPS, 1, selective=True), "gs_backward_adam: betas must lie in [0, 1)")
+            refused(lambda: ctx.backward_sgd(dC.data_ptr(), 0.0), "gs_backward_sgd: lr must be non-zero")
+            refused(lambda: _backward_ex(ctx, dC.data_ptr(), g, 1 | COMPOSITE_ONLY | PARAMS_ONLY), "exclude each other")
+            refused(lambda: _backward_ex(ctx, dC.data_ptr(), g, 1 | PARAMS_ONLY), "needs a GS_BWD_COMPOSITE_ONLY call on this frame")
         ctx.backward(dC.data_ptr(), g, overwrite=True)
         out.append({k: v.copy() for k, v in ctx.grads_read(g, DEG).items()})
         ctx.close()

@@ -21,25 +21,19 @@ import pytest
 import torch
 
 import camera_ref
-from common import hip_context, scene_and_cameras
+from common import hip_context, on_torch_stream, refused, run_frame, same_bits, scene_and_cameras
 from gaussiansplat_amd import synthetic
 
 pytestmark = pytest.mark.gpu
 
 
 def _ctx(sc, cam, T, P, W, H, deg, **kw):
-    ctx = hip_context(sc, cam, T, P, W, H, deg, **kw)
-    ctx.set_stream(torch.cuda.current_stream().cuda_stream or 1)
-    return ctx
+    return on_torch_stream(hip_context(sc, cam, T, P, W, H, deg, **kw))
 
 
-def _frame(ctx, dC, deg, phase="all"):
-    """preprocess .. backward (overwriting); returns image, transmittance and the gradients read back"""
-    ctx.preprocess(); ctx.bin()
-    img, tr = ctx.forward_host()
-    g = ctx.grads_alloc()
-    ctx.backward(np.ascontiguousarray(dC, np.float32), g, overwrite=True, phase=phase)
-    return img, tr, g
+def _frame(ctx, dC, deg):
+    """preprocess .. backward (overwriting): the frame gs_backward_camera follows"""
+    return run_frame(ctx, dC, deg, overwrite=True)
 
 
 def _identity(got40, d_means, means, T, keep=None):
@@ -77,10 +71,6 @@ def _scale_relation(got40, d_scales, cam):
     assert mass > 0 and abs(lhs - rhs) <= 2.0 ** -22 * mass, (lhs, rhs, mass)
 
 
-def _bytes(a):
-    return np.ascontiguousarray(a, np.float32).tobytes()
-
-
 # ---------------------------------------------------------------- 1. consistency with d_means
 
 @pytest.mark.parametrize("deg", [1, 3])
@@ -89,7 +79,7 @@ def test_d_T_is_the_outer_product_sum_of_the_device_d_means(deg, det):
     n, W, H = 2000, 128, 96
     sc, cam, T, P, _ = scene_and_cameras(n, W, H, deg, 500 + deg)
     ctx = _ctx(sc, cam, T, P, W, H, deg, deterministic=det, t_min=1e-5)
-    _, _, g = _frame(ctx, synthetic.make_dC(W, H, 500 + deg), deg)
+    g = _frame(ctx, synthetic.make_dC(W, H, 500 + deg), deg)["g"]
     got = ctx.backward_camera()
     assert got.shape == (40,) and got.dtype == np.float32 and np.isfinite(got).all()
     gr = ctx.grads_read(g, deg)
@@ -150,7 +140,7 @@ def test_reduction_shapes(n):
         sc["means"][0] = (8.0, 0.0, 0.0)
         sc["scales"][0] = -1.0
     ctx = _ctx(sc, cam, T, P, W, H, deg, deterministic=True, t_min=1e-5, slab_mode=0 if n > 1000 else 1)
-    _, _, g = _frame(ctx, synthetic.make_dC(W, H, 600), deg)
+    g = _frame(ctx, synthetic.make_dC(W, H, 600), deg)["g"]
     assert ctx.num_rounds == 1                                                    # what the case ran: one binning round
     got = ctx.backward_camera()
     dm = ctx.grads_read(g, deg)["means"]
@@ -185,7 +175,7 @@ def test_two_calls_and_both_memory_kinds_give_the_same_bytes(det):
     out = torch.full((40,), 7.0, dtype=torch.float32, device="cuda")
     ctx.backward_camera(out.data_ptr())
     torch.cuda.synchronize()
-    assert a.any() and len(_bytes(a)) == 160 and _bytes(a) == _bytes(b) == _bytes(out.cpu().numpy())
+    assert a.any() and a.nbytes == 160 and same_bits(a, b) and same_bits(a, out)
 
 
 def _twin_run(sc, cam, T, P, W, H, deg, dC, with_camera):
@@ -212,7 +202,7 @@ def test_the_frame_is_untouched_and_fresh_contexts_agree():
     a, cg_a, _ = _twin_run(sc, cam, T, P, W, H, deg, dC, True)
     b, _, _ = _twin_run(sc, cam, T, P, W, H, deg, dC, False)
     c, cg_c, _ = _twin_run(sc, cam, T, P, W, H, deg, dC, True)
-    assert cg_a.any() and _bytes(cg_a) == _bytes(cg_c)                              # deterministic mode: two fresh contexts, the same bytes
+    assert cg_a.any() and same_bits(cg_a, cg_c)                                     # deterministic mode: two fresh contexts, the same bytes
     assert a["g2d"].any() and a["img"].any()
     for k in ("img", "tr", "g2d"):
         assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
@@ -223,13 +213,6 @@ def test_the_frame_is_untouched_and_fresh_contexts_agree():
 
 # ---------------------------------------------------------------- 5. refusals
 
-def _refused(code, text, fn):
-    from gaussiansplat_amd import backend as B
-    with pytest.raises(B.GsError) as e:
-        fn()
-    assert e.value.code == code and text in str(e.value), (e.value.code, str(e.value))
-
-
 def test_refusals_leave_the_frame_usable():
     from gaussiansplat_amd import backend as B
     n, W, H, deg = 500, 64, 48, 1
@@ -237,41 +220,40 @@ def test_refusals_leave_the_frame_usable():
     dC = synthetic.make_dC(W, H, 720)
     INVALID, UNSUPPORTED = -1, -5
     ctx = _ctx(sc, cam, T, P, W, H, deg, deterministic=True)
-    _refused(INVALID, "gs_backward first", ctx.backward_camera)                    # no frame at all
+    refused(ctx.backward_camera, "gs_backward first", INVALID)                     # no frame at all
     ctx.preprocess(); ctx.bin()
-    _refused(INVALID, "gs_backward first", ctx.backward_camera)                    # before gs_forward
+    refused(ctx.backward_camera, "gs_backward first", INVALID)                     # before gs_forward
     img, tr = ctx.forward_host()
-    _refused(INVALID, "gs_backward first", ctx.backward_camera)                    # after gs_forward without a backward
+    refused(ctx.backward_camera, "gs_backward first", INVALID)                     # after gs_forward without a backward
     g = ctx.grads_alloc()
     ctx.backward(dC, g, overwrite=True, phase="composite")
-    _refused(INVALID, "NULL argument", lambda: ctx.backward_camera(0))             # out == NULL
+    refused(lambda: ctx.backward_camera(0), "NULL argument", INVALID)              # out == NULL
     got = ctx.backward_camera()                                                     # ... and after GS_BWD_COMPOSITE_ONLY alone it succeeds
     ctx.backward(dC, g, overwrite=True, phase="params")
     grads = ctx.grads_read(g, deg)
     twin = _ctx(sc, cam, T, P, W, H, deg, deterministic=True)                      # the same frame without a refused call in it
-    img2, tr2, g2 = _frame(twin, dC, deg)
-    assert np.array_equal(img, img2) and np.array_equal(tr, tr2) and _bytes(got) == _bytes(twin.backward_camera()) and got.any()
-    want = twin.grads_read(g2, deg)
+    f2 = _frame(twin, dC, deg)
+    assert np.array_equal(img, f2["img"]) and np.array_equal(tr, f2["tr"]) and same_bits(got, twin.backward_camera()) and got.any()
+    want = twin.grads_read(f2["g"], deg)
     for k in grads:
         assert np.array_equal(grads[k].view(np.uint32), want[k].view(np.uint32)), k
     # after gs_backward_sgd the frame is gone: the stage check refuses; the next frame is served
     ctx.preprocess(); ctx.bin(); ctx.forward_host()
     d = torch.as_tensor(dC).cuda()
     ctx.backward_sgd(d.data_ptr(), 1e-4)
-    _refused(INVALID, "gs_backward first", ctx.backward_camera)
+    refused(ctx.backward_camera, "gs_backward first", INVALID)
     _frame(ctx, dC, deg)
     assert np.isfinite(ctx.backward_camera()).all()
     # the 2-D renderer has no camera
     s2 = synthetic.make_scene_2d(200, W, H, seed=3)
-    c2 = B.Context(deterministic=True)
-    c2.set_stream(torch.cuda.current_stream().cuda_stream or 1)
+    c2 = on_torch_stream(B.Context(deterministic=True))
     c2.set_model_2d_host(s2["means"], s2["scales"], s2["rots"], s2["opacities"], s2["colors"])
     c2.set_image_size(W, H)
     c2.preprocess(); c2.bin()
     i2, _ = c2.forward_host()
     g2d = c2.grads_alloc()
     c2.backward(dC, g2d, overwrite=True)
-    _refused(UNSUPPORTED, "3-D renderer only", c2.backward_camera)
+    refused(c2.backward_camera, "3-D renderer only", UNSUPPORTED)
     c2.backward(dC, g2d, overwrite=True, phase="params")                            # the frame is still there
     assert i2.any()
 
@@ -287,7 +269,7 @@ def test_planted_gaussians_contribute_nothing():
     keep = np.ones(n, bool); keep[[100, 200, 300]] = False
     for det in (False, True):
         ctx = _ctx(sc, cam, T, P, W, H, deg, deterministic=det)
-        _, _, g = _frame(ctx, synthetic.make_dC(W, H, 730), deg)
+        g = _frame(ctx, synthetic.make_dC(W, H, 730), deg)["g"]
         got = ctx.backward_camera()
         dm = ctx.grads_read(g, deg)["means"]
         assert np.isfinite(got).all() and got[:16].any() and not dm[~keep].any()
@@ -302,17 +284,17 @@ def test_active_degree_below_the_stored_one_equals_the_truncated_model():
     dC = synthetic.make_dC(W, H, 740)
     full = _ctx(sc, cam, T, P, W, H, 3, deterministic=True)
     full.set_active_sh_degree(1)
-    _, _, g = _frame(full, dC, 3)
+    g = _frame(full, dC, 3)["g"]
     a = full.backward_camera()
     _identity(a, full.grads_read(g, 3)["means"], sc["means"], T)
     cut = dict(sc, shs=np.ascontiguousarray(sc["shs"][:, :4]))
     trunc = _ctx(cut, cam, T, P, W, H, 1, deterministic=True)
     _frame(trunc, dC, 1)
     b = trunc.backward_camera()
-    assert a[32:38].any() and _bytes(a) == _bytes(b)
+    assert a[32:38].any() and same_bits(a, b)
     full.set_active_sh_degree(-1)
     _frame(full, dC, 3)
-    assert _bytes(full.backward_camera()) != _bytes(a)                               # the higher bands do reach the camera
+    assert not same_bits(full.backward_camera(), a)                                  # the higher bands do reach the camera
 
 
 def test_background_colour():
@@ -324,7 +306,7 @@ def test_background_colour():
         ctx = _ctx(sc, cam, T, P, W, H, deg, deterministic=True)
         if bg:
             ctx.set_background(bg)
-        _, _, g = _frame(ctx, dC, deg)
+        g = _frame(ctx, dC, deg)["g"]
         got = ctx.backward_camera()
         _identity(got, ctx.grads_read(g, deg)["means"], sc["means"], T)
         outs.append(got)

@@ -11,18 +11,14 @@ edges, slots beyond the old limit of 64, and the cap switched off."""
 import numpy as np
 import pytest
 
-from common import hip_context, rel_l2, scene_and_cameras
+from common import GRADS, hip_context, one_wave_per_tile, rel_l2, run_frame, scene_and_cameras
 
 pytestmark = pytest.mark.gpu
-GRADS = ("means", "scales", "quats", "opacities", "shs")
 
 
 @pytest.fixture(autouse=True)
 def _one_wave_per_tile(monkeypatch):
-    """Frames with capped lists are composited by one wave per tile (gs_config.tile_parts); the plain frames they are compared with
-    BIT FOR BIT here must be too: on these small grids the default would give a tile two or four waves, each testing its entries against
-    its own pixels (differences below 2^-27 per entry, tests/test_gpu_parts.py)."""
-    monkeypatch.setenv("GSPLAT_TILE_PARTS", "1")
+    one_wave_per_tile(monkeypatch)
 
 
 def _set_cam(ctx, cam, W, H):
@@ -32,20 +28,7 @@ def _set_cam(ctx, cam, W, H):
                    cam.eye, cam.lookAt, W, H)
 
 
-def _frame(ctx, dC, deg, slot=None):
-    if slot is not None:
-        ctx.set_view_slot(slot)
-    ctx.preprocess(); ctx.bin()
-    img, tr = ctx.forward_host()
-    st = ctx.list_stats()
-    g = ctx.grads_alloc()
-    ctx.backward(dC, g)
-    grads = ctx.grads_read(g, deg)
-    from gaussiansplat_amd import backend as B
-    return dict(img=img, tr=tr, grads=grads, wc=ctx.work_counters_ex(), st=st, inst=ctx.num_instances, g2d=ctx.get_array(B.ARR_GRAD2D))
-
-
-def _same_bits(a, b, det=True, oracle_grads=None):
+def _same_frames(a, b, det=True, oracle_grads=None):
     assert np.array_equal(a["img"], b["img"]) and np.array_equal(a["tr"], b["tr"])
     assert a["wc"]["walked_fwd"] == b["wc"]["walked_fwd"] == b["wc"]["walked_bwd"]
     assert a["wc"]["evaluated_fwd"] == b["wc"]["evaluated_fwd"] == b["wc"]["evaluated_bwd"]
@@ -83,7 +66,7 @@ def test_capped_lists_from_slot_history_are_invisible(oracle, det):
     sc, cam, T, P, ocam = _dense_scene(n, W, H, deg, 31)
     dC = synthetic.make_dC(W, H, 31)
     plain = hip_context(sc, cam, T, P, W, H, deg, deterministic=det, list_cap=1, slab_mode=0)
-    ref = _frame(plain, dC, deg, slot=7)
+    ref = run_frame(plain, dC, deg, slot=7, g2d=True)
     assert not ref["st"]["capped"] and ref["st"]["listed"] == ref["inst"]
     assert ref["wc"]["walked_fwd"] < 0.5 * ref["inst"]                         # the scene is dense enough for caps to matter
     og = None
@@ -91,14 +74,14 @@ def test_capped_lists_from_slot_history_are_invisible(oracle, det):
         o0 = O.render(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"], deg, ocam, order=1, t_min=1e-5, omp=True)
         og = O.backward(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"], deg, ocam, o0["ranges"], o0["ids"], dC, t_min=1e-5, omp=True)
     ctx = hip_context(sc, cam, T, P, W, H, deg, deterministic=det, list_cap=2, slab_mode=0)
-    f1 = _frame(ctx, dC, deg, slot=7)                                          # no history yet: full lists
+    f1 = run_frame(ctx, dC, deg, slot=7, g2d=True)                             # no history yet: full lists
     assert not f1["st"]["capped"]
-    _same_bits(ref, f1, det, og)
+    _same_frames(ref, f1, det, og)
     for rep in range(3):                                                       # history from the same view: capped, nothing to extend
-        f = _frame(ctx, dC, deg, slot=7)
+        f = run_frame(ctx, dC, deg, slot=7, g2d=True)
         assert f["st"]["capped"] and f["st"]["extended_segments"] == 0, f["st"]
         assert f["wc"]["walked_fwd"] <= f["st"]["listed"] < 0.8 * f["inst"], (f["st"], f["inst"], f["wc"])
-        _same_bits(ref, f, det, og)
+        _same_frames(ref, f, det, og)
     # the full ranges are always there; asking for the ids writes the unwritten rest, and the frame still finishes
     ctx.set_view_slot(7); ctx.preprocess(); ctx.bin()
     oref = O.render(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"], deg, ocam, order=1, t_min=1e-5, omp=True)
@@ -115,9 +98,9 @@ def test_capped_lists_from_slot_history_are_invisible(oracle, det):
         if det:
             assert np.array_equal(got[k], ref["grads"][k]), k
     # a frame under another slot has no history: full lists again
-    f = _frame(ctx, dC, deg, slot=2000)                                        # (slots up to 4095: the old limit was 64)
+    f = run_frame(ctx, dC, deg, slot=2000, g2d=True)                           # (slots up to 4095: the old limit was 64)
     assert not f["st"]["capped"]
-    _same_bits(ref, f, det, og)
+    _same_frames(ref, f, det, og)
     plain.close(); ctx.close()
 
 
@@ -135,19 +118,19 @@ def test_camera_jump_under_a_reused_slot_extends_lists_in_the_kernel():
     ctx = hip_context(sc, cam, T, P, W, H, deg, deterministic=True, list_cap=2, slab_mode=0)
     plain = hip_context(sc, cam, T, P, W, H, deg, deterministic=True, list_cap=1, slab_mode=0)
     _set_cam(ctx, camA, W, H); _set_cam(plain, camA, W, H)
-    a0 = _frame(plain, dC, deg, slot=5)
+    a0 = run_frame(plain, dC, deg, slot=5, g2d=True)
     for _ in range(2):
-        a = _frame(ctx, dC, deg, slot=5)
-        _same_bits(a0, a)
+        a = run_frame(ctx, dC, deg, slot=5, g2d=True)
+        _same_frames(a0, a)
     assert a["st"]["capped"]
     _set_cam(ctx, camB, W, H); _set_cam(plain, camB, W, H)                     # the jump: slot 5 now shows view B
-    b0 = _frame(plain, dC, deg, slot=5)
-    b = _frame(ctx, dC, deg, slot=5)
+    b0 = run_frame(plain, dC, deg, slot=5, g2d=True)
+    b = run_frame(ctx, dC, deg, slot=5, g2d=True)
     assert b["st"]["capped"] and b["st"]["extended_segments"] > 0, b["st"]
-    _same_bits(b0, b)
-    b2 = _frame(ctx, dC, deg, slot=5)                                          # the history has caught up
+    _same_frames(b0, b)
+    b2 = run_frame(ctx, dC, deg, slot=5, g2d=True)                             # the history has caught up
     assert b2["st"]["capped"] and b2["st"]["extended_segments"] == 0, b2["st"]
-    _same_bits(b0, b2)
+    _same_frames(b0, b2)
     ctx.close(); plain.close()
 
 
@@ -165,15 +148,15 @@ def test_minimum_caps_everywhere(oracle, n, W, H, deg, grow, super16):
     gref = O.backward(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"], deg, ocam, oref["ranges"], oref["ids"], dC, t_min=1e-5, omp=True)
     for det in (True, False):
         plain = hip_context(sc, cam, T, P, W, H, deg, deterministic=det, list_cap=1, slab_mode=0)
-        ref = _frame(plain, dC, deg); plain.close()
+        ref = run_frame(plain, dC, deg, g2d=True); plain.close()
         ctx = hip_context(sc, cam, T, P, W, H, deg, deterministic=det, slab_mode=0, debug_flags=B.GS_DEBUG_TINY_CAPS | (B.GS_DEBUG_SUPER16 if super16 else 0))
         for rep in range(2):
-            f = _frame(ctx, dC, deg)
+            f = run_frame(ctx, dC, deg, g2d=True)
             assert f["st"]["capped"]
             if n >= 40_000:
                 assert f["st"]["extended_segments"] > 0
             assert f["st"]["listed"] <= f["inst"]
-            _same_bits(ref, f, det, None if det else gref)
+            _same_frames(ref, f, det, None if det else gref)
         ctx.close()
     assert np.all(np.abs(f["img"] - oref["image"]) <= 1e-4 + 1e-4 * np.abs(oref["image"]))
     assert np.all(np.abs(f["tr"] - oref["trans"]) <= 1e-4 + 1e-4 * np.abs(oref["trans"]))

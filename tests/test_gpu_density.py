@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import density_ref as D
+from common import bits, dev, host, perturbed_start, refused, same_bits, synthetic_renderer
 
 pytestmark = pytest.mark.gpu
 
@@ -15,46 +16,9 @@ SENTINEL = f32(-777.25)
 PAD = 64                                    # rows of SENTINEL behind every destination: nothing may be written there
 
 
-def _renderer(n, deg, seed, W=128, H=96, scene=None, **kw):
-    import torch
-    from gaussiansplat_amd import renderer as R, synthetic
-    if n == 0:                                  # (getRenderer reshapes its arrays by their row count: an empty model is built by hand)
-        z = lambda w: torch.empty((0, w), device="cuda")
-        return R.GaussianRenderer3D(R.SplatData3D(means=z(3), scales=z(3), shs=z(3 * (deg + 1) ** 2), quaternions=z(4), opacities=z(1)), (W, H), deg, **kw)
-    scene = scene if scene is not None else synthetic.make_scene(n, W, H, deg, seed=seed)
-    return R.getRenderer("GAUSSIAN_3D", (W, H, 3), (16, 16), None, scene, **kw)
-
-
 def _model(r):
     sd = r.splatData
     return [sd.means, sd.scales, sd.quaternions, sd.opacities, sd.shs]
-
-
-def _host(ts):
-    import torch
-    torch.cuda.synchronize()
-    return [t.detach().cpu().numpy().reshape(t.shape[0], int(np.prod(t.shape[1:]))).copy() for t in ts]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, f32).view(np.uint32)
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def _same_bits_nan(a, b):
-    """Bit for bit, except that any NaN equals any NaN: which NaN an invalid operation produces (sign, payload) is the one thing
-    IEEE 754 leaves open, and x86 and gfx950 differ in it."""
-    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-    return a.shape == b.shape and bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
-
-
-def _cuda(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else np.asarray(a, dtype))).cuda()
 
 
 def _frame(r, cam, dC):
@@ -79,7 +43,7 @@ def test_accumulate_matches_the_reference_bit_for_bit(deterministic):
     scene["means"][out[3:6]] = (-3.0 * e).astype(f32)        # beyond `far`
     scene["means"][out[6:9]] = np.array([0.0, 40.0, 0.0], f32)   # in depth, far above the frame
     scene["means"][out[9:12], 1] = np.nan
-    r = _renderer(n, deg, 0, W, H, scene=scene, export_debug=True, deterministic=deterministic, tile_parts=1)
+    r = synthetic_renderer(n, deg, 0, W, H, scene=scene, export_debug=True, deterministic=deterministic, tile_parts=1)
     stats = DensityStats(r)
     ref = (np.zeros(n, f32), np.zeros(n, np.int32), np.zeros(n, np.int32))
     for v, cam in enumerate(cams):
@@ -99,12 +63,12 @@ def test_accumulate_matches_the_reference_bit_for_bit(deterministic):
     print("accumulate (deterministic=%d): %.1f %% of the gaussians have grad_sum > 0, %d visible in both views, largest extent %d px"
           % (deterministic, 100 * touched, int((cnt == 2).sum()), int(mx.max())))
     assert touched >= 0.30 and not cnt[out].any() and not mx[out].any()          # the conditions the comparison stands on
-    assert _same_bits_nan(gs, ref[0]), np.flatnonzero(_bits(gs) != _bits(ref[0]))[:8]
+    assert same_bits(gs, ref[0], nan_equal=True), np.flatnonzero(bits(gs) != bits(ref[0]))[:8]
     assert np.array_equal(cnt, ref[1]) and np.array_equal(mx, ref[2])
     assert np.isnan(ref[0][out[9:12]]).all() or not ref[0][out[9:12]].any()      # (a NaN mean gives a NaN or a zero gradient, never a finite one)
     g2x, c2x, m2x = twice.grad_sum.cpu().numpy(), twice.count.cpu().numpy(), twice.max_extent.cpu().numpy()
     with np.errstate(invalid="ignore"):
-        assert _same_bits_nan(g2x, one[0] + one[0]) and _same_bits_nan(g2x, f32(2.0) * one[0])
+        assert same_bits(g2x, one[0] + one[0], nan_equal=True) and same_bits(g2x, f32(2.0) * one[0], nan_equal=True)
     assert np.array_equal(c2x, 2 * one[1]) and np.array_equal(m2x, one[2])
 
 
@@ -143,8 +107,8 @@ def test_decide_matches_the_reference_on_thresholds_and_nans():
     scene["scales"][k, 1] = np.nan; k += 1
     scene["scales"][k, 0] = np.nan; cnt[k], gs[k] = 2, 1.0; k += 1
     scene["opacities"][k] = np.nan; k += 1
-    r = _renderer(n, deg, 0, scene=scene)
-    t_gs, t_cnt, t_ext = _cuda(gs), _cuda(cnt), _cuda(ext)
+    r = synthetic_renderer(n, deg, 0, scene=scene)
+    t_gs, t_cnt, t_ext = dev(gs, None), dev(cnt, None), dev(ext, None)
     st = B.GsDensityStats(t_gs.data_ptr(), t_cnt.data_ptr(), t_ext.data_ptr())
     action = torch.full((n,), -5, dtype=torch.int32, device="cuda")
     r._begin()
@@ -157,13 +121,13 @@ def test_decide_matches_the_reference_on_thresholds_and_nans():
     # the children of these split actions shrink by THIS decide's log_shrink
     assert r.ctx.density_plan(action.data_ptr()) == c
     noise = rng.standard_normal((n, 2, 3)).astype(f32)
-    model = _host(_model(r))
+    model = host(_model(r))
     new, _ = D.restructure(model, want, noise, log_shrink=ls)
     dst = [torch.full((D.n_out(c) + PAD, a.shape[1]), float(SENTINEL), device="cuda") for a in model]
-    t_noise = _cuda(noise)
+    t_noise = dev(noise, None)
     r.ctx.density_restructure(action.data_ptr(), t_noise.data_ptr(), B.GsGrads(*[t.data_ptr() for t in dst]), [], [], D.n_out(c))
-    for a, b in zip(_host(dst), new):
-        assert _same_bits_nan(a[:len(b)], b) and np.all(a[len(b):] == SENTINEL)
+    for a, b in zip(host(dst), new):
+        assert same_bits(a[:len(b)], b, nan_equal=True) and np.all(a[len(b):] == SENTINEL)
     # +Inf / 0 switch the world-scale and extent tests off; grad_threshold = +Inf switches densification off
     q = density_params(scene_extent=4.0, grad_threshold=math.inf, percent_dense=0.012, min_opacity=0.1, max_world_fraction=None, max_extent_px=0)
     r.ctx.density_decide(st, q, action.data_ptr())
@@ -182,7 +146,7 @@ def _restructure_case(r, n, deg, pattern, nsets, rng):
     import torch
     from gaussiansplat_amd import backend as B
     widths = [3, 3, 4, 1, 3 * (deg + 1) ** 2]
-    model = _host(_model(r))
+    model = host(_model(r))
     act = _actions(pattern, n, rng)
     c = D.counts(act)
     no = D.n_out(c)
@@ -191,32 +155,32 @@ def _restructure_case(r, n, deg, pattern, nsets, rng):
     null = (1, 2) if nsets else None                                            # set 1 comes without its quaternion array
     ref_sets = [[None if null == (t, i) else a for i, a in enumerate(s)] for t, s in enumerate(sets)]
     new, new_sets = D.restructure(model, act, noise, sets=ref_sets)
-    t_act = _cuda(act)
-    t_noise = _cuda(noise) if noise is not None else None
+    t_act = dev(act, None)
+    t_noise = dev(noise, None) if noise is not None else None
     dst = [torch.full((no + PAD, w), float(SENTINEL), device="cuda") for w in widths]
-    t_src = [[_cuda(a) for a in s] for s in sets]
+    t_src = [[dev(a, None) for a in s] for s in sets]
     t_dst = [[torch.full((no + PAD, w), float(SENTINEL), device="cuda") for w in widths] for _ in range(nsets)]
     struct = lambda ts, t: B.GsGrads(*[None if null == (t, i) else x.data_ptr() for i, x in enumerate(ts)])
     r._begin()
     assert r.ctx.density_plan(t_act.data_ptr()) == c, (pattern, c)
     r.ctx.density_restructure(t_act.data_ptr(), t_noise.data_ptr() if t_noise is not None else None, B.GsGrads(*[t.data_ptr() for t in dst]),
                               [struct(s, t) for t, s in enumerate(t_src)], [struct(s, t) for t, s in enumerate(t_dst)], no)
-    for k, (a, b) in enumerate(zip(_host(dst), new)):
-        assert _same_bits(a[:no], b), (pattern, nsets, k, np.argwhere(_bits(a[:no]) != _bits(b))[:4])
+    for k, (a, b) in enumerate(zip(host(dst), new)):
+        assert same_bits(a[:no], b), (pattern, nsets, k, np.argwhere(bits(a[:no]) != bits(b))[:4])
         assert np.all(a[no:] == SENTINEL), (pattern, nsets, k)
     for t in range(nsets):
-        for i, a in enumerate(_host(t_dst[t])):
+        for i, a in enumerate(host(t_dst[t])):
             if null == (t, i):
                 assert np.all(a == SENTINEL)                                    # skipped: untouched
             else:
-                assert _same_bits(a[:no], new_sets[t][i]) and np.all(a[no:] == SENTINEL), (pattern, t, i)
+                assert same_bits(a[:no], new_sets[t][i]) and np.all(a[no:] == SENTINEL), (pattern, t, i)
     return c
 
 
 @pytest.mark.parametrize("deg", [0, 3])
 @pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 1000])
 def test_restructure_matches_the_reference_bit_for_bit(n, deg):
-    r = _renderer(n, deg, seed=30 + deg)
+    r = synthetic_renderer(n, deg, seed=30 + deg)
     rng = np.random.default_rng(1000 * deg + n)
     for pattern in ("mixed", "keep", "prune", "split", "clone"):
         for nsets in (0, 2):
@@ -231,7 +195,7 @@ def test_restructure_matches_the_reference_bit_for_bit(n, deg):
 def test_restructure_more_than_1024_chunks():
     """300 001 gaussians are 1172 chunks of 256: a thread of the one scan workgroup sums two of them."""
     n, deg = 300_001, 3
-    r = _renderer(n, deg, seed=33)
+    r = synthetic_renderer(n, deg, seed=33)
     c = _restructure_case(r, n, deg, "mixed", 2, np.random.default_rng(33))
     assert min(c) > 30_000
 
@@ -242,18 +206,13 @@ def test_refusals_write_nothing():
     from gaussiansplat_amd import backend as B, renderer as R, synthetic
     from gaussiansplat_amd.density import DensityStats, density_params
     n, deg, W, H = 600, 1, 128, 96
-    r = _renderer(n, deg, seed=50)
+    r = synthetic_renderer(n, deg, seed=50)
     cam = synthetic.scene_camera(W)
     stats = DensityStats(r)
     for t in (stats.grad_sum, stats.count, stats.max_extent):
         t.fill_(3)
     snap = [t.clone() for t in (stats.grad_sum, stats.count, stats.max_extent)]
     p = density_params(scene_extent=4.0)
-
-    def refused(call, code=B.GS_ERR_INVALID):
-        with pytest.raises(B.GsError) as e:
-            call()
-        assert e.value.code == code, str(e.value)
 
     # accumulate before a backward: no frame at all, then a frame that is rendered only
     r._begin()
@@ -265,7 +224,7 @@ def test_refusals_write_nothing():
     act = np.random.default_rng(50).integers(0, 4, n).astype(np.int32)
     c = D.counts(act)
     no = D.n_out(c)
-    t_act, t_noise = _cuda(act), _cuda(np.random.default_rng(51).standard_normal((n, 2, 3)).astype(f32))
+    t_act, t_noise = dev(act, None), dev(np.random.default_rng(51).standard_normal((n, 2, 3)).astype(f32), None)
     widths = [3, 3, 4, 1, 12]
     dst = [torch.full((no + PAD, w), float(SENTINEL), device="cuda") for w in widths]
     g = lambda ts: B.GsGrads(*[t.data_ptr() for t in ts])
@@ -288,11 +247,11 @@ def test_refusals_write_nothing():
     r.ctx.set_model_device(n, deg, [t.data_ptr() for t in _model(r)])           # the model "changed": the plan is gone
     refused(go)
     bad = act.copy(); bad[n // 2] = 7
-    t_bad = _cuda(bad)
+    t_bad = dev(bad, None)
     refused(lambda: r.ctx.density_plan(t_bad.data_ptr()))
     refused(lambda: go(a=t_bad))
     bad[n // 2] = -1
-    t_bad.copy_(_cuda(bad))
+    t_bad.copy_(dev(bad, None))
     refused(lambda: r.ctx.density_plan(t_bad.data_ptr()))
     # a bad struct_size, NaN thresholds
     action = torch.full((n,), -5, dtype=torch.int32, device="cuda")
@@ -306,7 +265,7 @@ def test_refusals_write_nothing():
     for call in (lambda: r2.ctx.density_accumulate(stats.struct()), lambda: r2.ctx.density_decide(stats.struct(), p, action.data_ptr()),
                  lambda: r2.ctx.density_plan(t_act.data_ptr()),
                  lambda: r2.ctx.density_restructure(t_act.data_ptr(), t_noise.data_ptr(), g(dst), [], [], no), lambda: r2.ctx.opacity_reset(-4.0)):
-        refused(call, B.GS_ERR_UNSUPPORTED)
+        refused(call, code=B.GS_ERR_UNSUPPORTED)
     torch.cuda.synchronize()
     for a, b in zip(snap, (stats.grad_sum, stats.count, stats.max_extent)):
         assert torch.equal(a, b)
@@ -335,25 +294,25 @@ def test_opacity_reset_is_exact():
     scene["opacities"][6] = np.inf
     scene["opacities"][7] = -np.inf
     scene["opacities"][8] = f32(logit(0.01))
-    r = _renderer(n, deg, 0, scene=scene)
+    r = synthetic_renderer(n, deg, 0, scene=scene)
     m, v = torch.ones(n, device="cuda"), torch.full((n,), 2.0, device="cuda")
     r._begin()
     mx = float(f32(logit(0.01)))
-    o0 = _host([r.splatData.opacities])[0]
+    o0 = host([r.splatData.opacities])[0]
     r.ctx.opacity_reset(mx, m.data_ptr(), 0)                                    # one moment array, the other NULL
     want, _, _ = D.opacity_reset(o0, mx)
-    assert _same_bits(_host([r.splatData.opacities])[0], want) and np.isnan(want[5, 0]) and want[6, 0] == f32(mx) and want[7, 0] == -np.inf
+    assert same_bits(host([r.splatData.opacities])[0], want) and np.isnan(want[5, 0]) and want[6, 0] == f32(mx) and want[7, 0] == -np.inf
     assert not m.any() and not torch.signbit(m).any() and bool((v == 2.0).all())
     r.ctx.opacity_reset(-1e30, 0, 0)                                            # both NULL
     want, _, _ = D.opacity_reset(want, -1e30)
-    assert _same_bits(_host([r.splatData.opacities])[0], want)
+    assert same_bits(host([r.splatData.opacities])[0], want)
     # through the module: the opacities' words of Adam's two flat moment buffers, and nothing else of them
-    r = _renderer(n, deg, 0, scene=scene)
+    r = synthetic_renderer(n, deg, 0, scene=scene)
     opt = Adam(r, lr=1e-3)
     opt.exp_avg.fill_(1.0); opt.exp_avg_sq.fill_(2.0)
     reset_opacity(r, opt, 0.01)
     want, _, _ = D.opacity_reset(o0, mx)
-    assert _same_bits(_host([r.splatData.opacities])[0], want)
+    assert same_bits(host([r.splatData.opacities])[0], want)
     lo = opt._offsets[3]
     for buf, val in ((opt.exp_avg, 1.0), (opt.exp_avg_sq, 2.0)):
         assert not buf[lo:lo + n].any() and bool((buf[:lo] == val).all()) and bool((buf[lo + n:] == val).all())
@@ -363,20 +322,6 @@ def test_opacity_reset_is_exact():
 RATES = dict(means=1e-3, scales=4e-3, quaternions=2e-3, opacities=5e-2, sh_dc=2.5e-3, sh_rest=1.25e-4)
 
 
-def _perturbed_start(n, Wi, Hi, deg):
-    """The scene and start of tests/test_gpu_adam.py::test_adam_for_3dgs_beats_the_sgd_run."""
-    from gaussiansplat_amd import renderer as R, synthetic
-    target = synthetic.make_scene(n, Wi, Hi, deg, seed=1)
-    cam = synthetic.scene_camera(Wi)
-    rt = R.getRenderer("GAUSSIAN_3D", (Wi, Hi, 3), (16, 16), None, target)
-    R.forward(rt, (R.preprocess(rt, cam), R.compactIdxs(rt))[0])
-    gt = rt.imageData.clone()
-    start = {k: v.copy() for k, v in target.items()}
-    start["shs"] = (start["shs"] + 0.2 * np.random.default_rng(2).standard_normal(start["shs"].shape)).astype(np.float32)
-    start["opacities"] = (start["opacities"] - 0.5).astype(np.float32)
-    return start, cam, gt
-
-
 def test_end_to_end_restructured_renderer_equals_a_fresh_one():
     import torch
     from gaussiansplat_amd import renderer as R, train as TR
@@ -384,7 +329,7 @@ def test_end_to_end_restructured_renderer_equals_a_fresh_one():
     from gaussiansplat_amd.optim import Adam
     n, Wi, Hi, deg = 3000, 128, 96, 1
     widths = [3, 3, 4, 1, 12]
-    start, cam, gt = _perturbed_start(n, Wi, Hi, deg)
+    start, cam, gt = perturbed_start(n, Wi, Hi, deg)
     r = R.getRenderer("GAUSSIAN_3D", (Wi, Hi, 3), (16, 16), None, start, deterministic=True, tile_parts=1)
     lf = TR.getLossFunction((Wi, Hi, 3), 11, 3, renderer=r)
     opt = Adam(r, lr=RATES)
@@ -396,7 +341,7 @@ def test_end_to_end_restructured_renderer_equals_a_fresh_one():
         R.backward(r, dC)
         stats.accumulate()
         opt.step()
-    model = _host(_model(r))
+    model = host(_model(r))
     gs, cnt, ext = stats.grad_sum.cpu().numpy(), stats.count.cpu().numpy(), stats.max_extent.cpu().numpy()
     split_flat = lambda flat: [a.reshape(n, w).copy() for a, w in zip(np.split(flat.cpu().numpy(), np.cumsum([w * n for w in widths])[:-1]), widths)]
     moments = [split_flat(opt.exp_avg), split_flat(opt.exp_avg_sq)]
@@ -418,12 +363,12 @@ def test_end_to_end_restructured_renderer_equals_a_fresh_one():
     print("end to end: %d gaussians -> %d (survivors %d, clones %d, splits %d, pruned %d)" % (n, no, *c))
     assert got == dict(survivors=c[0], clones=c[1], splits=c[2], pruned=c[3], n=no) and min(c) > 100
     assert r.nGaussians == no == r.ctx.num_gaussians and opt.step_count == 4
-    for a, b in zip(_host(_model(r)), new):
-        assert _same_bits(a, b)
+    for a, b in zip(host(_model(r)), new):
+        assert same_bits(a, b)
     split_new = lambda flat: [a.reshape(no, w) for a, w in zip(np.split(flat.cpu().numpy(), np.cumsum([w * no for w in widths])[:-1]), widths)]
     for flat, ref in ((opt.exp_avg, new_m[0]), (opt.exp_avg_sq, new_m[1])):
         for a, b in zip(split_new(flat), ref):
-            assert _same_bits(a, b)
+            assert same_bits(a, b)
             assert a[:c[0]].any() and not a[c[0]:].any()                        # survivors carried over, new rows zero
     assert stats.grad_sum.numel() == no and not stats.grad_sum.any() and not stats.count.any() and not stats.max_extent.any()
     assert r.splatGrads.flat.numel() == sum(widths) * no and not r.splatGrads.flat.any()
@@ -449,7 +394,7 @@ def test_end_to_end_restructured_renderer_equals_a_fresh_one():
     opt.step()
     torch.cuda.synchronize()
     assert opt.step_count == 5 and not torch.equal(before, opt.exp_avg) and int(stats.count.sum()) > 0
-    assert all(np.isfinite(a).all() for a in _host(_model(r)))
+    assert all(np.isfinite(a).all() for a in host(_model(r)))
 
 
 def test_densify_and_prune_refuses_a_renderer_that_shares_its_gradients_and_honours_max_gaussians():
@@ -457,14 +402,14 @@ def test_densify_and_prune_refuses_a_renderer_that_shares_its_gradients_and_hono
     from gaussiansplat_amd import renderer as R, synthetic
     from gaussiansplat_amd.density import DensityStats, densify_and_prune
     n, W, H, deg = 1000, 128, 96, 1
-    r = _renderer(n, deg, seed=70)
+    r = synthetic_renderer(n, deg, seed=70)
     second = R.GaussianRenderer3D(r.splatData, (W, H), deg, share_grads_with=r)
     with pytest.raises(ValueError, match="share_grads_with"):
         densify_and_prune(second, DensityStats(second), scene_extent=4.0)
     stats = DensityStats(r)
     _frame(r, synthetic.scene_camera(W), torch.as_tensor(synthetic.make_dC(W, H, 70)).cuda())
     stats.accumulate()
-    opac = _host([r.splatData.opacities])[0]
+    opac = host([r.splatData.opacities])[0]
     faint = int((opac < f32(math.log(0.2 / 0.8))).sum())
     # every visible gaussian with a gradient would densify: more than max_gaussians, so only the pruning happens
     got = densify_and_prune(r, stats, scene_extent=4.0, grad_threshold=0.0, min_opacity=0.2, max_world_fraction=None, max_gaussians=n)
@@ -477,7 +422,7 @@ def test_training_with_the_controller_changes_n_and_reduces_the_loss():
     from gaussiansplat_amd.density import DensityController
     from gaussiansplat_amd.optim import Adam
     n, Wi, Hi, deg = 3000, 128, 96, 1
-    start, cam, gt = _perturbed_start(n, Wi, Hi, deg)
+    start, cam, gt = perturbed_start(n, Wi, Hi, deg)
     extent = float(np.linalg.norm(start["means"].max(0) - start["means"].min(0)) / 2)
     sixth = {k: v[:n // 6].copy() for k, v in start.items()}
     finals = {}

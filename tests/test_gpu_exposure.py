@@ -15,14 +15,11 @@ import pytest
 
 import adam_ref as AR
 import exposure_ref as ER
+from common import render, same_bits, small_scene_renderer
 
 pytestmark = pytest.mark.gpu
 
 CASES = [(W, H, wt) for (W, H) in ER.SHAPES for wt in (False, True)]
-
-
-def _same_bits(a, b):
-    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
 
 
 @functools.lru_cache(maxsize=None)
@@ -86,16 +83,16 @@ def _check_dE(dE, r, W, H):
 def test_exposure_against_the_restatement(ctx, W, H, weighted):
     r = _ref(W, H, weighted)
     out, d_img, dE = _run(ctx, r, W, H)
-    assert _same_bits(out, r["out"])
-    assert _same_bits(d_img, r["dx"])
+    assert same_bits(out, r["out"])
+    assert same_bits(d_img, r["dx"])
     _check_dE(dE, r, W, H)
     _, in_place, dE2 = _run(ctx, r, W, H, in_place=True)
-    assert _same_bits(in_place, d_img)                                       # d_img == d_out: the same bits as written apart
-    assert _same_bits(dE2, dE)                                               # two calls: bit-equal
+    assert same_bits(in_place, d_img)                                        # d_img == d_out: the same bits as written apart
+    assert same_bits(dE2, dE)                                                # two calls: bit-equal
     _, no_dE, none = _run(ctx, r, W, H, want_dE=False)
-    assert none is None and _same_bits(no_dE, d_img)                         # d_exposure == NULL: the same d_img bits
+    assert none is None and same_bits(no_dE, d_img)                          # d_exposure == NULL: the same d_img bits
     _, no_dE_in_place, _ = _run(ctx, r, W, H, in_place=True, want_dE=False)
-    assert _same_bits(no_dE_in_place, d_img)
+    assert same_bits(no_dE_in_place, d_img)
 
 
 @pytest.mark.parametrize("W,H,weighted", [(129, 33, True), (129, 33, False), (320, 200, True), (320, 200, False)], ids=lambda v: str(v))
@@ -105,11 +102,11 @@ def test_exposure_with_every_base_four_bytes_past_a_16_byte_boundary(ctx, W, H, 
     aligned = _run(ctx, r, W, H)
     for in_place in (False, True):
         out, d_img, dE = _run(ctx, r, W, H, off=1, in_place=in_place)
-        assert _same_bits(out, r["out"]) and _same_bits(d_img, r["dx"])
+        assert same_bits(out, r["out"]) and same_bits(d_img, r["dx"])
         _check_dE(dE, r, W, H)
-        assert _same_bits(dE, aligned[2])                                    # the pixel -> lane mapping does not depend on the alignment
+        assert same_bits(dE, aligned[2])                                     # the pixel -> lane mapping does not depend on the alignment
     _, no_dE, _ = _run(ctx, r, W, H, off=1, want_dE=False)
-    assert _same_bits(no_dE, r["dx"])
+    assert same_bits(no_dE, r["dx"])
 
 
 def test_exposure_gradient_does_not_depend_on_what_the_ctx_did_before():
@@ -125,25 +122,11 @@ def test_exposure_gradient_does_not_depend_on_what_the_ctx_did_before():
     first = _run(fresh, big, 320, 200)
     used.close(); fresh.close()
     for p, q in zip(a + again, b + first):
-        assert _same_bits(p, q)
+        assert same_bits(p, q)
     _check_dE(a[2], small, 129, 33)
 
 
 # ---------------------------------------------------------------- the frame stays as it was
-def _small_scene():
-    import common
-    from gaussiansplat_amd import renderer as R
-    W, H, deg = 64, 48, 1
-    sc, cam, *_ = common.scene_and_cameras(300, W, H, deg, seed=5)
-    r = R.getRenderer("GAUSSIAN_3D", (W, H, 3), (16, 16), None, sc, deterministic=True, tile_parts=1)
-    return r, cam, W, H
-
-
-def _render(r, cam):
-    from gaussiansplat_amd import renderer as R
-    tps = R.preprocess(r, cam); R.compactIdxs(r); R.forward(r, tps)
-
-
 def test_exposure_calls_are_legal_anywhere_and_leave_the_frame_alone():
     """apply and backward before any frame, between forward and backward of a real frame and after the backward: imageData and
     splatGrads come out as in a run without them, bit for bit (deterministic mode, one wave per tile)"""
@@ -151,18 +134,18 @@ def test_exposure_calls_are_legal_anywhere_and_leave_the_frame_alone():
     from gaussiansplat_amd import renderer as R, synthetic
     runs = []
     for with_calls in (False, True):
-        r, cam, W, H = _small_scene()
+        r, cam, W, H = small_scene_renderer(300, 5)
         case = _ref(W, H, True)
         dC = torch.as_tensor(synthetic.make_dC(W, H, 4)).cuda()
 
         def calls():
             if with_calls:
                 out, d_img, dE = _run(r.ctx, case, W, H)
-                assert _same_bits(out, case["out"]) and _same_bits(d_img, case["dx"])
+                assert same_bits(out, case["out"]) and same_bits(d_img, case["dx"])
                 _check_dE(dE, case, W, H)
         r._begin()
         calls()                                                              # before any frame: no model's frame, no camera's
-        _render(r, cam)
+        render(r, cam)
         image = r.imageData.clone()
         calls()                                                              # between forward and backward
         R.backward(r, dC)
@@ -181,7 +164,7 @@ def test_exposure_adam_steps_one_view_at_a_time():
     with adam_ref.hyper at that VIEW's own step count, bit for bit; view 1's row, moments and count never change"""
     import torch
     from gaussiansplat_amd.appearance import Exposure
-    r, cam, W, H = _small_scene()
+    r, cam, W, H = small_scene_renderer(300, 5)
     lr, betas, eps = 0.01, (0.9, 0.999), 1e-15
     e = Exposure(r, 4, lr=lr, betas=betas, eps=eps)
     rng = np.random.default_rng(17)
@@ -191,7 +174,7 @@ def test_exposure_adam_steps_one_view_at_a_time():
         x = rng.standard_normal((3, H, W)).astype(np.float32)
         d = rng.standard_normal((3, H, W)).astype(np.float32)
         out = e.apply(view, torch.as_tensor(x).cuda())
-        assert _same_bits(out.cpu().numpy(), ER.forward(x, table[view]))
+        assert same_bits(out.cpu().numpy(), ER.forward(x, table[view]))
         e.backward(view, torch.as_tensor(d).cuda())
         g = e._grad.cpu().numpy().reshape(3, 4)
         exact, A = ER.backward_exposure(x, d, None)
@@ -201,18 +184,18 @@ def test_exposure_adam_steps_one_view_at_a_time():
         h = AR.hyper([lr], betas[0], betas[1], eps, counts[view])
         table[view], m[view], v[view] = AR.update(table[view], m[view], v[view], g, h, h["step_size"][0])
         assert e.step_counts == counts
-        assert _same_bits(e.table.cpu().numpy(), table) and _same_bits(e.exp_avg.cpu().numpy(), m) and _same_bits(e.exp_avg_sq.cpu().numpy(), v)
+        assert same_bits(e.table.cpu().numpy(), table) and same_bits(e.exp_avg.cpu().numpy(), m) and same_bits(e.exp_avg_sq.cpu().numpy(), v)
     assert counts == [1, 0, 3, 1] and np.array_equal(table[1], ER.identity()) and not m[1].any() and not v[1].any()
     assert np.abs(table[2] - ER.identity()).max() > 0.02                    # three steps of about the rate each
-    assert _same_bits(e.exposure(2), table[2])
+    assert same_bits(e.exposure(2), table[2])
     # lr = 0 keeps the row and moves the moments
     e.set_lr(0.0)
     x = rng.standard_normal((3, H, W)).astype(np.float32); d = rng.standard_normal((3, H, W)).astype(np.float32)
     e.apply(2, torch.as_tensor(x).cuda()); e.backward(2, torch.as_tensor(d).cuda()); g = e._grad.cpu().numpy().reshape(3, 4); e.step(2)
     h = AR.hyper([0.0], betas[0], betas[1], eps, 4)
     p2, m2, v2 = AR.update(table[2], m[2], v[2], g, h, h["step_size"][0])
-    assert _same_bits(p2, table[2]) and not _same_bits(m2, m[2]) and not _same_bits(v2, v[2])
-    assert _same_bits(e.exposure(2), table[2]) and _same_bits(e.exp_avg[2].cpu().numpy(), m2) and _same_bits(e.exp_avg_sq[2].cpu().numpy(), v2)
+    assert same_bits(p2, table[2]) and not same_bits(m2, m[2]) and not same_bits(v2, v[2])
+    assert same_bits(e.exposure(2), table[2]) and same_bits(e.exp_avg[2].cpu().numpy(), m2) and same_bits(e.exp_avg_sq[2].cpu().numpy(), v2)
     assert e.step_counts == [1, 0, 4, 1]
     # a checkpoint carries the table, the moments, the counts and the rate
     sd = e.state_dict()
@@ -225,15 +208,15 @@ def test_exposure_adam_steps_one_view_at_a_time():
 def test_mask_target_is_the_weight_times_the_target_exactly():
     import torch
     from gaussiansplat_amd.appearance import Exposure
-    r, cam, W, H = _small_scene()
+    r, cam, W, H = small_scene_renderer(300, 5)
     case = _ref(W, H, True)
     e = Exposure(r, 2, weights=[None, case["w"]])
     gt = torch.as_tensor(np.array(case["x"])).cuda()
     assert e.mask_target(0, gt) is gt
     masked = e.mask_target(1, gt).cpu().numpy()
-    assert _same_bits(masked, case["w"][None] * (case["x"] + np.float32(0)))
+    assert same_bits(masked, case["w"][None] * (case["x"] + np.float32(0)))
     out = e.apply(1, gt).cpu().numpy()                                       # the table's identity row with the view's weight: the same
-    assert _same_bits(out, masked)
+    assert same_bits(out, masked)
 
 
 # ---------------------------------------------------------------- refusals
@@ -300,14 +283,14 @@ def test_exposure_refusals_leave_the_outputs_untouched(ctx):
         assert bool((t == S).all())
     r = _ref(5, 7, True)                                                     # the context still works
     o, dx, g = _run(ctx, r, 5, 7)
-    assert _same_bits(o, r["out"]) and _same_bits(dx, r["dx"])
+    assert same_bits(o, r["out"]) and same_bits(dx, r["dx"])
 
 
 # ---------------------------------------------------------------- through train.trainStep
 def _train_run(exposure_of, iterations=2):
     import torch
     from gaussiansplat_amd import optim, train as TR
-    r, cam, W, H = _small_scene()
+    r, cam, W, H = small_scene_renderer(300, 5)
     gt = torch.rand((3, H, W), generator=torch.Generator().manual_seed(9)).cuda()
     lf = TR.getLossFunction((W, H, 3), 11, 3, renderer=r)
     opt = optim.Adam(r, lr=1e-2)
@@ -345,12 +328,12 @@ def test_masked_step_compares_the_masked_images_and_the_fused_optimiser_follows(
     w = _ref(64, 48, True)["w"]
     params = []
     for fused in (False, True):
-        r, cam, W, H = _small_scene()
+        r, cam, W, H = small_scene_renderer(300, 5)
         gt = torch.rand((3, H, W), generator=torch.Generator().manual_seed(9)).cuda()
         lf = TR.getLossFunction((W, H, 3), 11, 3, renderer=r)
         e = Exposure(r, 2, weights=[None, w])
         if not fused:
-            _render(r, cam)
+            render(r, cam)
             wt = torch.as_tensor(np.array(w)).cuda()
             by_hand = lf(wt[None] * r.imageData, wt[None] * gt)
         opt = optim.Adam(r, lr=1e-2, fused=fused)
@@ -361,7 +344,7 @@ def test_masked_step_compares_the_masked_images_and_the_fused_optimiser_follows(
         params.append([t.cpu().numpy().copy() for t in (d.means, d.scales, d.quaternions, d.opacities, d.shs)] + [e.table.cpu().numpy(), np.array(losses)])
         assert e.step_counts == [0, 2] and np.abs(e.exposure(1) - ER.identity()).max() > 0.005
     for a, b in zip(*params):
-        assert _same_bits(a, b)
+        assert same_bits(a, b)
 
 
 def test_exposure_fit_recovers_a_known_affine():
@@ -371,8 +354,8 @@ def test_exposure_fit_recovers_a_known_affine():
     import torch
     from gaussiansplat_amd import train as TR
     from gaussiansplat_amd.appearance import Exposure
-    r, cam, W, H = _small_scene()
-    _render(r, cam)
+    r, cam, W, H = small_scene_renderer(300, 5)
+    render(r, cam)
     image = r.imageData.cpu().numpy()
     star = (ER.identity() + np.array([[0.2, -0.05, 0.1, 0.05], [0.1, -0.2, 0.05, -0.1], [-0.1, 0.15, 0.2, 0.1]], np.float32)).astype(np.float32)
     assert abs(float(np.abs(star - ER.identity()).max()) - 0.2) < 1e-7

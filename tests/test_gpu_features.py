@@ -16,20 +16,13 @@ import pytest
 import torch
 
 import torch_ref
-from common import hip_context, rel_l2, scene_and_cameras
+from common import GRADS, dev, hip_context, on_torch_stream, refused, rel_l2, scene_and_cameras
 
 pytestmark = pytest.mark.gpu
-GRADS = ("means", "scales", "quats", "opacities", "shs")
-
-
-def _dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a, np.float32)).cuda()
 
 
 def _ctx(sc, cam, T, P, W, H, deg, **kw):
-    ctx = hip_context(sc, cam, T, P, W, H, deg, **kw)
-    ctx.set_stream(torch.cuda.current_stream().cuda_stream or 1)          # torch's current stream; 0, the legacy default stream, is 1 here
-    return ctx
+    return on_torch_stream(hip_context(sc, cam, T, P, W, H, deg, **kw))
 
 
 def _scene(n, W, H, deg, seed, grow=3.0, dop=4.0):
@@ -51,7 +44,7 @@ def _bound_forward(ctx, W, H):
 
 
 def _render_features(ctx, feat, W, H, want_trans=True):
-    f = feat if isinstance(feat, torch.Tensor) else _dev(feat)
+    f = feat if isinstance(feat, torch.Tensor) else dev(feat)
     out = torch.full((3, H, W), -7.0, dtype=torch.float32, device="cuda")
     tr = torch.full((H, W), -7.0, dtype=torch.float32, device="cuda") if want_trans else None
     ctx.render_features(f.data_ptr(), out.data_ptr(), tr.data_ptr() if want_trans else 0)
@@ -67,13 +60,6 @@ def _grad_tensors(n, deg):
 def _gs_grads(ts):
     from gaussiansplat_amd import backend as B
     return B.GsGrads(*(t.data_ptr() for t in ts))
-
-
-def _refused(code, fn):
-    from gaussiansplat_amd import backend as B
-    with pytest.raises(B.GsError) as e:
-        fn()
-    assert e.value.code == code, (e.value.code, code, str(e.value))
 
 
 # ---------------------------------------------------------------- 1. depth values
@@ -116,8 +102,8 @@ def test_view_depth_equals_ts_row_2_bit_for_bit():
     dz[7] = -0.0
     base = rng.standard_normal((n, 3)).astype(np.float32)
     base[14] = np.nan
-    dm = _dev(base)
-    ctx.view_depth_backward(_dev(dz).data_ptr(), dm.data_ptr())
+    dm = dev(base)
+    ctx.view_depth_backward(dev(dz).data_ptr(), dm.data_ptr())
     torch.cuda.synchronize()
     Tf = np.ascontiguousarray(T, np.float32).reshape(-1)
     want_dm = base.copy()
@@ -272,7 +258,7 @@ def test_feature_gradients_against_fp64_autograd(oracle, det, t_min):
     want, F64 = _reference_grads(oracle, sc, cam, T, P, ocam, W, H, deg, t_min, dF, feat)
     ctx = _ctx(sc, cam, T, P, W, H, deg, t_min=t_min, deterministic=det, slab_mode=0)
     img, tr = _bound_forward(ctx, W, H)                                    # (kept: the frame's image lives in these two)
-    f_d, dF_d = _dev(feat), _dev(dF)
+    f_d, dF_d = dev(feat), dev(dF)
     F, _ = _render_features(ctx, f_d, W, H)
     assert np.all(np.abs(F.cpu().numpy() - F64) <= 2e-4 + 1e-4 * np.abs(F64))       # |feat| <= 2
     runs = []
@@ -345,7 +331,7 @@ def _three_frames(sc, cam, T, P, W, H, deg, dC, mode, feat, dF):
     n = sc["means"].shape[0]
     ctx = _ctx(sc, cam, T, P, W, H, deg, deterministic=True, slab_mode=0)
     ctx.set_view_slot(2)
-    dC_d, f_d, dF_d = _dev(dC), _dev(feat), _dev(dF)
+    dC_d, f_d, dF_d = dev(dC), dev(feat), dev(dF)
     out = {}
     for frame in range(3):
         img, tr = _bound_forward(ctx, W, H)
@@ -402,8 +388,8 @@ def test_refusals_leave_the_frame_as_it_was():
     from gaussiansplat_amd import backend as B, synthetic
     n, W, H, deg = 2000, 80, 56, 1                                         # (depth slabs need 1024 gaussians or more)
     sc, cam, T, P, ocam = _scene(n, W, H, deg, 87)
-    dC = _dev(synthetic.make_dC(W, H, 87))
-    feat = _dev(np.random.default_rng(87).uniform(0.0, 1.0, (n, 3)).astype(np.float32))
+    dC = dev(synthetic.make_dC(W, H, 87))
+    feat = dev(np.random.default_rng(87).uniform(0.0, 1.0, (n, 3)).astype(np.float32))
     out = torch.zeros((3, H, W), dtype=torch.float32, device="cuda"); tro = torch.zeros((H, W), dtype=torch.float32, device="cuda")
     d_feat = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
     fp, op, tp, dp = feat.data_ptr(), out.data_ptr(), tro.data_ptr(), d_feat.data_ptr()
@@ -413,20 +399,20 @@ def test_refusals_leave_the_frame_as_it_was():
         ctx.bind_outputs(img.data_ptr(), tr.data_ptr())
         ctx.preprocess(); ctx.bin()
         if poke:                                                           # a call before gs_forward
-            _refused(B.GS_ERR_INVALID, lambda: ctx.render_features(fp, op, tp))
-            _refused(B.GS_ERR_INVALID, lambda: ctx.backward_features(fp, op, dC.data_ptr(), dp, None))
+            refused(lambda: ctx.render_features(fp, op, tp), code=B.GS_ERR_INVALID)
+            refused(lambda: ctx.backward_features(fp, op, dC.data_ptr(), dp, None), code=B.GS_ERR_INVALID)
         ctx.forward_device(img.data_ptr(), tr.data_ptr())
         if poke:
             ip, trp = img.data_ptr(), tr.data_ptr()
             for o, t in ((ip, tp), (op, trp), (ip + 4, tp), (trp, tp), (op, ip + 8 * W * H), (op, op + 4 * W * H), (op, op)):   # overlapping outputs
-                _refused(B.GS_ERR_INVALID, lambda: ctx.render_features(fp, o, t))
-            _refused(B.GS_ERR_INVALID, lambda: ctx.render_features(0, op, tp))                     # NULL pointers
-            _refused(B.GS_ERR_INVALID, lambda: ctx.render_features(fp, 0, tp))
+                refused(lambda: ctx.render_features(fp, o, t), code=B.GS_ERR_INVALID)
+            refused(lambda: ctx.render_features(0, op, tp), code=B.GS_ERR_INVALID)                 # NULL pointers
+            refused(lambda: ctx.render_features(fp, 0, tp), code=B.GS_ERR_INVALID)
             for args in ((0, op, dC.data_ptr(), dp), (fp, 0, dC.data_ptr(), dp), (fp, op, 0, dp), (fp, op, dC.data_ptr(), 0)):
-                _refused(B.GS_ERR_INVALID, lambda: ctx.backward_features(*args, None))
-            _refused(B.GS_ERR_INVALID, lambda: ctx.view_depth(0))
-            _refused(B.GS_ERR_INVALID, lambda: ctx.view_depth_backward(0, dp))
-            _refused(B.GS_ERR_INVALID, lambda: ctx.view_depth_backward(dp, 0))
+                refused(lambda: ctx.backward_features(*args, None), code=B.GS_ERR_INVALID)
+            refused(lambda: ctx.view_depth(0), code=B.GS_ERR_INVALID)
+            refused(lambda: ctx.view_depth_backward(0, dp), code=B.GS_ERR_INVALID)
+            refused(lambda: ctx.view_depth_backward(dp, 0), code=B.GS_ERR_INVALID)
         gt = _grad_tensors(n, deg)
         ctx.backward(dC.data_ptr(), _gs_grads(gt))
         torch.cuda.synchronize()
@@ -443,8 +429,8 @@ def test_refusals_leave_the_frame_as_it_was():
     slab = _ctx(sc, cam, T, P, W, H, deg, deterministic=True, slab_mode=1, slab_fractions=(0.3, 0.6), tile_parts=1)
     img, tr = _bound_forward(slab, W, H)
     assert slab.num_rounds > 1
-    _refused(B.GS_ERR_UNSUPPORTED, lambda: slab.render_features(fp, op, tp))
-    _refused(B.GS_ERR_UNSUPPORTED, lambda: slab.backward_features(fp, op, dC.data_ptr(), dp, None))
+    refused(lambda: slab.render_features(fp, op, tp), code=B.GS_ERR_UNSUPPORTED)
+    refused(lambda: slab.backward_features(fp, op, dC.data_ptr(), dp, None), code=B.GS_ERR_UNSUPPORTED)
     gt = _grad_tensors(n, deg)
     slab.backward(dC.data_ptr(), _gs_grads(gt))
     torch.cuda.synchronize()
@@ -454,8 +440,7 @@ def test_refusals_leave_the_frame_as_it_was():
 
     # the 2-D renderer
     s2 = synthetic.make_scene_2d(500, W, H, 88)
-    c2 = B.Context(order=B.ORDER_INDEX, deterministic=True)
-    c2.set_stream(torch.cuda.current_stream().cuda_stream or 1)
+    c2 = on_torch_stream(B.Context(order=B.ORDER_INDEX, deterministic=True))
     c2.set_model_2d_host(s2["means"], s2["scales"], s2["rots"], s2["opacities"], s2["colors"])
     c2.set_image_size(W, H)
 
@@ -463,10 +448,10 @@ def test_refusals_leave_the_frame_as_it_was():
         c2.preprocess(); c2.bin()
         i2, t2 = c2.forward_host()
         if poke:
-            _refused(B.GS_ERR_UNSUPPORTED, lambda: c2.render_features(fp, op, tp))
-            _refused(B.GS_ERR_UNSUPPORTED, lambda: c2.backward_features(fp, op, dC.data_ptr(), dp, None))
-            _refused(B.GS_ERR_UNSUPPORTED, lambda: c2.view_depth(dp))
-            _refused(B.GS_ERR_UNSUPPORTED, lambda: c2.view_depth_backward(dp, dp))
+            refused(lambda: c2.render_features(fp, op, tp), code=B.GS_ERR_UNSUPPORTED)
+            refused(lambda: c2.backward_features(fp, op, dC.data_ptr(), dp, None), code=B.GS_ERR_UNSUPPORTED)
+            refused(lambda: c2.view_depth(dp), code=B.GS_ERR_UNSUPPORTED)
+            refused(lambda: c2.view_depth_backward(dp, dp), code=B.GS_ERR_UNSUPPORTED)
         g = c2.grads_alloc()
         c2.backward(dC.data_ptr(), g, overwrite=True)
         return [i2, t2] + list(c2.grads_read_2d(g).values())

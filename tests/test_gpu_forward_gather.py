@@ -24,9 +24,8 @@ import functools
 import numpy as np
 import pytest
 
-from common import hip_context, scene_and_cameras
+from common import GRADS, halves, hip_context, run_frame, scene_and_cameras
 
-GRADS = ("means", "scales", "quats", "opacities", "shs")
 ALWAYS_ORDER = 2
 T_MIN = 1e-5
 LENGTHS = (1, 63, 64, 65, 127, 128, 129, 0, 2, 191, 192, 193, 255, 256, 257, 320)      # tile t of the 4 x 4 grid lists LENGTHS[t] entries
@@ -109,28 +108,17 @@ def test_oracle_early_out_stays_inside_its_literal_walk(name):
 def _frame(ctx, dC, deg, slot=None, segments=False):
     """segments: heavy tiles' backward runs as list segments, each testing its entries against its OWN live rectangle: the walked counts agree,
     the evaluated counts need not (as on small grids, tests/test_gpu_parts.py)"""
-    if slot is not None:
-        ctx.set_view_slot(slot)
-    ctx.preprocess(); ctx.bin()
-    img, tr = ctx.forward_host()
-    st = ctx.list_stats()
-    g = ctx.grads_alloc()
-    ctx.backward(dC, g)
-    wc = ctx.work_counters_ex()
-    assert wc["walked_fwd"] == wc["walked_bwd"] and (segments or wc["evaluated_fwd"] == wc["evaluated_bwd"]), wc
-    return dict(img=img, tr=tr, grads=ctx.grads_read(g, deg), wc=wc, st=st, inst=ctx.num_instances)
+    f = run_frame(ctx, dC, deg, slot=slot)
+    assert f["wc"]["walked_fwd"] == f["wc"]["walked_bwd"] and (segments or f["wc"]["evaluated_fwd"] == f["wc"]["evaluated_bwd"]), f["wc"]
+    return f
 
 
-def _same_bits(a, b, grads=True):
+def _same_frames(a, b, grads=True):
     assert np.array_equal(a["img"], b["img"]) and np.array_equal(a["tr"], b["tr"])
     assert a["wc"] == b["wc"], (a["wc"], b["wc"])
     if grads:
         for k in GRADS:
             assert np.array_equal(a["grads"][k], b["grads"][k]), k
-
-
-def _halves(col):
-    return (col >> np.uint64(32)).astype(np.int64), (col & np.uint64(0xFFFFFFFF)).astype(np.int64)
 
 
 @pytest.mark.gpu
@@ -158,8 +146,8 @@ def test_forward_walk_prefetch(name):
         assert base["wc"]["walked_fwd"] == ref["instances"]                  # nothing freezes: every list is walked to its end
     if name == "early":
         assert base["wc"]["walked_fwd"] < ref["instances"]
-        h1, h2 = _halves(ctx.tile_clock(0, 10)[:, 8])                       # evaluated entries while the live pixels fill 1 / 2 slots ...
-        h3, h4 = _halves(ctx.tile_clock(0, 10)[:, 9])                       # ... 3 / 4 slots (3: the walk stays at K = 4)
+        h1, h2 = halves(ctx.tile_clock(0, 10)[:, 8])                        # evaluated entries while the live pixels fill 1 / 2 slots ...
+        h3, h4 = halves(ctx.tile_clock(0, 10)[:, 9])                        # ... 3 / 4 slots (3: the walk stays at K = 4)
         assert h1.sum() > 0 and h2.sum() > 0 and h4.sum() > 0, (h1, h2, h3, h4)
     ctx.close()
 
@@ -180,7 +168,7 @@ def test_forward_walk_prefetch(name):
         ctx, frames = run(frames=3, list_cap=cap, tile_parts=1)
         ctx.close()
         for f in frames:
-            _same_bits(base, f)
+            _same_frames(base, f)
         if name == "caps" and cap == 2:
             assert frames[1]["st"]["capped"] and frames[2]["st"]["capped"]
 
@@ -190,8 +178,8 @@ def test_forward_walk_prefetch(name):
         ctx, frames = run(frames=2, schedule=schedule, debug_flags=ALWAYS_ORDER)
         ctx.close()
         res[schedule] = frames[-1]
-        _same_bits(base, frames[-1])
-    _same_bits(res[1], res[3])
+        _same_frames(base, frames[-1])
+    _same_frames(res[1], res[3])
 
     if name == "caps":
         # (a) the minimum cap on every tile: every busy tile extends its list
@@ -199,7 +187,7 @@ def test_forward_walk_prefetch(name):
         ctx.close()
         for f in frames:
             assert f["st"]["capped"] and f["st"]["extended_segments"] > 0 and f["st"]["listed"] <= f["inst"], f["st"]
-            _same_bits(base, f)
+            _same_frames(base, f)
         # (b) a wrong history: the slot saw the scene from the other side (view 0), where the transparent third lies elsewhere
         camB = synthetic.scene_camera(W, view=0)
         ctx = hip_context(sc, cam, T, P, W, H, deg, t_min=T_MIN, deterministic=True, slab_mode=0, list_cap=2, tile_parts=1)
@@ -213,7 +201,7 @@ def test_forward_walk_prefetch(name):
         jump = _frame(ctx, dC, deg, slot)
         ctx.close()
         assert jump["st"]["capped"] and jump["st"]["extended_segments"] > 0, jump["st"]
-        _same_bits(base, jump)
+        _same_frames(base, jump)
 
     if name == "grid":
         # the production set-up: the second frame of a view slot runs on the slot's launch order, heavy tiles split into several waves

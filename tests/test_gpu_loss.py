@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import loss_ref as LR
+from common import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -174,16 +175,11 @@ def test_three_iteration_trajectory_against_an_oracle_side_loop(oracle, fused):
 
 
 # ---------------------------------------------------------------- the loss kernels on flat, smooth and tiny images (tests/loss_ref.py)
-def _dev(a):
-    import torch
-    return torch.as_tensor(np.array(a, np.float32)).cuda()                  # a copy: the shared cases are read-only
-
-
 def _loss_device(ctx, img, gt, lam, want_dC=True, want_loss=True):
     """(loss, dC) through the device path: images and dC resident, dC filled with NaN first"""
     import torch
     Cn, H, W = img.shape
-    x, y = _dev(img), _dev(gt)
+    x, y = dev(img), dev(gt)
     d = torch.full((Cn, H, W), float("nan"), device="cuda")
     loss = ctx.loss_device(x.data_ptr(), y.data_ptr(), d.data_ptr() if want_dC else 0, W, H, Cn, lam, want_loss)
     torch.cuda.synchronize()

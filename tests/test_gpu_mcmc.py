@@ -2,12 +2,14 @@
 restatement of include/gsplat.h (tests/mcmc_ref.py): CDF, dead list, draws, noise and regulariser gradients bit for bit; the relocation's
 opacity and scales within one float32 ulp (both sides evaluate in double and round once, tests/test_mcmc_host.py), everything it copies and
 everything it must not touch bit for bit; the refusals; growth through mcmc.grow; a short training run with the MCMC schedule."""
+import functools
 import math
 
 import numpy as np
 import pytest
 
 import mcmc_ref as M
+from common import dev, host, refused, same_bits, synthetic_renderer
 
 pytestmark = pytest.mark.gpu
 
@@ -17,9 +19,7 @@ MIN_LOGIT = math.log(MIN_OPACITY / (1.0 - MIN_OPACITY))
 SENTINEL = -7
 
 
-def _renderer(n, deg, seed, W=64, H=64, **kw):
-    from gaussiansplat_amd import renderer as R, synthetic
-    return R.getRenderer("GAUSSIAN_3D", (W, H, 3), (16, 16), None, synthetic.make_scene(n, W, H, deg, seed=seed), **kw)
+_renderer = functools.partial(synthetic_renderer, W=64, H=64)
 
 
 def _model(r):
@@ -27,29 +27,13 @@ def _model(r):
     return [sd.means, sd.scales, sd.quaternions, sd.opacities, sd.shs]
 
 
-def _host(ts):
-    import torch
-    torch.cuda.synchronize()
-    return [t.detach().cpu().numpy().reshape(t.shape[0], -1).copy() for t in ts]
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def _within_one_ulp(a, ref):
     a, ref = np.asarray(a, np.float64), np.asarray(ref, f32)
     return bool(np.all(np.abs(a - ref.astype(np.float64)) <= np.spacing(np.abs(ref)).astype(np.float64)))
 
 
-def _cuda(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def _set_opacities(r, o):
-    r.splatData.opacities.copy_(_cuda(np.asarray(o, f32).reshape(-1, 1)))
+    r.splatData.opacities.copy_(dev(np.asarray(o, f32).reshape(-1, 1)))
 
 
 def _plan(r, n):
@@ -106,7 +90,7 @@ def test_sample_equals_searchsorted(n):
     for m in (0, 1, 64, 65, 5000):
         u = rng.random(m).astype(f32)
         u[:min(m, len(edge))] = edge[:m]
-        tu = _cuda(u) if m else torch.empty(0, device="cuda")
+        tu = dev(u, None) if m else torch.empty(0, device="cuda")
         src = torch.full((m + 8,), SENTINEL, dtype=torch.int32, device="cuda")
         r.ctx.mcmc_sample(cdf.data_ptr(), n, tu.data_ptr(), m, src.data_ptr())
         s = src.cpu().numpy()
@@ -118,7 +102,7 @@ def test_sample_equals_searchsorted(n):
     cdf0, _, counts0 = _plan(r, n)
     assert counts0 == (0, n, 0)
     src = torch.full((64,), SENTINEL, dtype=torch.int32, device="cuda")
-    r.ctx.mcmc_sample(cdf0.data_ptr(), n, _cuda(rng.random(64).astype(f32)).data_ptr(), 64, src.data_ptr())
+    r.ctx.mcmc_sample(cdf0.data_ptr(), n, dev(rng.random(64).astype(f32)).data_ptr(), 64, src.data_ptr())
     assert bool((src == SENTINEL).all())
 
 
@@ -161,31 +145,31 @@ def test_relocate_matches_the_reference(deg, from_plan):
         free = np.setdiff1d(np.arange(n), sources)
         dst = rng.choice(free, m, replace=False).astype(np.int32)           # alive or dead, pairwise distinct, no source
         dst[-2] = -3; dst[-1] = n
-        t_dst = _cuda(dst)
+        t_dst = dev(dst, None)
         dst_ptr = t_dst.data_ptr()
     sets, structs = _moment_sets(_model(r), 42)
-    before = _host(_model(r))
-    sets_before = [[None if t is None else _host([t])[0] for t in s] for s in sets]
-    t_src = _cuda(src)
+    before = host(_model(r))
+    sets_before = [[None if t is None else host([t])[0] for t in s] for s in sets]
+    t_src = dev(src, None)
     r.ctx.mcmc_relocate(t_src.data_ptr(), dst_ptr, m, MIN_OPACITY, structs)
-    after = _host(_model(r))
+    after = host(_model(r))
     new, new_sets, cnt = M.relocate(before, src, dst, MIN_OPACITY, sets_before)
     ok = (src >= 0) & (src < n) & (dst >= 0) & (dst < n)
     assert sorted(cnt[sources].tolist()) == [1, 2, 49, 50, 51, 200] and cnt.sum() == ok.sum()
     touched = np.zeros(n, bool)
     touched[sources] = True; touched[dst[ok]] = True
     for i in (0, 2, 4):                                                      # means, quaternions, SH rows: copied, or kept, bit for bit
-        assert _same_bits(after[i], new[i]), i
+        assert same_bits(after[i], new[i]), i
     for i in (1, 3):                                                         # scales, opacities: the statement's values within one ulp; the rest every bit
-        assert _same_bits(after[i][~touched], before[i][~touched]), i
+        assert same_bits(after[i][~touched], before[i][~touched]), i
         assert _within_one_ulp(after[i][touched], new[i][touched]), i
-        assert _same_bits(after[i][dst[ok]], after[i][src[ok]]), i           # a destination carries exactly its source's new values
+        assert same_bits(after[i][dst[ok]], after[i][src[ok]]), i            # a destination carries exactly its source's new values
     assert (after[3][sources] < before[3][sources]).all() and (after[1][sources] < before[1][sources]).all()
-    for s_after, s_before in zip([[None if t is None else _host([t])[0] for t in s] for s in sets], sets_before):
+    for s_after, s_before in zip([[None if t is None else host([t])[0] for t in s] for s in sets], sets_before):
         for a, b in zip(s_after, s_before):
             if b is None:
                 continue
-            assert _same_bits(a[~touched], b[~touched])
+            assert same_bits(a[~touched], b[~touched])
             assert not a[touched].view(np.uint32).any()                      # +0, every bit
     # a fresh plan: what was dead and relocated is alive now (its source's corrected opacity is above the threshold or clamped at it)
     if from_plan:
@@ -211,30 +195,30 @@ def test_grow_extends_the_model_and_the_renderer_renders():
         mcmc.grow(_renderer(10, deg, seed=51), opt, cap_max=10 ** 6)
     for cap, want in ((5000, int(1.05 * n)), (4400, 4400), (4400, 4400)):
         n0 = r.nGaussians
-        before = _host(_model(r))
+        before = host(_model(r))
         mom_before = [m.clone() for m in (opt.exp_avg, opt.exp_avg_sq)]
         off_before = opt._offsets
         got = mcmc.grow(r, opt, cap_max=cap, generator=gen)
         assert got["n"] == want == r.nGaussians == min(cap, int(1.05 * n0)) and got["added"] == want - n0
-        after = _host(_model(r))
+        after = host(_model(r))
         assert all(a.shape[0] == want for a in after) and opt.step_count == 5 and opt.exp_avg.numel() == r.splatGrads.flat.numel()
         if not got["added"]:
-            assert got["src"] is None and all(_same_bits(a, b) for a, b in zip(after, before))
+            assert got["src"] is None and all(same_bits(a, b) for a, b in zip(after, before))
             continue
         src = got["src"].cpu().numpy()
         ext = [np.concatenate([b, np.zeros((want - n0, b.shape[1]), f32)]) for b in before]
         new, _, cnt = M.relocate(ext, src, np.arange(n0, want), MIN_OPACITY)
         for i in (0, 2, 4):                                                  # the old rows unchanged, the new ones copies of their sources
-            assert _same_bits(after[i], new[i])
+            assert same_bits(after[i], new[i])
         srcs = cnt > 0
         for i in (1, 3):
-            assert _same_bits(after[i][:n0][~srcs[:n0]], before[i][~srcs[:n0]]) and _within_one_ulp(after[i], new[i])
+            assert same_bits(after[i][:n0][~srcs[:n0]], before[i][~srcs[:n0]]) and _within_one_ulp(after[i], new[i])
         # moments: old rows carried over, rows of sources and of the new gaussians +0
         for mb, ma in zip(mom_before, (opt.exp_avg, opt.exp_avg_sq)):
             for ob, oa, wd in zip(off_before, opt._offsets, (3, 3, 4, 1, after[4].shape[1])):
                 b = mb[ob:ob + n0 * wd].reshape(n0, wd).cpu().numpy()
                 a = ma[oa:oa + want * wd].reshape(want, wd).cpu().numpy()
-                assert _same_bits(a[:n0][~srcs[:n0]], b[~srcs[:n0]]) and not a[:n0][srcs[:n0]].any() and not a[n0:].any()
+                assert same_bits(a[:n0][~srcs[:n0]], b[~srcs[:n0]]) and not a[:n0][srcs[:n0]].any() and not a[n0:].any()
     cam = synthetic.scene_camera(W)
     R.forward(r, (R.preprocess(r, cam), R.compactIdxs(r))[0])
     img = r.imageData.cpu().numpy()
@@ -247,7 +231,7 @@ def test_noise_matches_the_reference_bit_for_bit(n):
     r = _renderer(n, 0, seed=60 + n)
     rng = np.random.default_rng(60 + n)
     q = (rng.normal(0, 1, (n, 4)) * rng.uniform(0.2, 3.0, (n, 1))).astype(f32)      # raw: not normalised
-    r.splatData.quaternions.copy_(_cuda(q))
+    r.splatData.quaternions.copy_(dev(q, None))
     o = rng.uniform(-9.0, 3.0, n).astype(f32)
     o[:min(n, 3)] = np.array([MIN_LOGIT, -5.0, -5.6], f32)[:min(n, 3)]           # sig on both sides of gate_t
     _set_opacities(r, o)
@@ -255,20 +239,20 @@ def test_noise_matches_the_reference_bit_for_bit(n):
     if n > 40:
         z[10:20] = 0.0
         z[21] = np.inf                                                        # the result would not be finite: the mean is kept
-    tz = _cuda(z)
+    tz = dev(z, None)
     r._begin()
     for lr in (80.0, 1e-3):
-        before = _host(_model(r))
+        before = host(_model(r))
         r.ctx.mcmc_noise(tz.data_ptr(), lr, 100.0, 0.005)
-        after = _host(_model(r))
+        after = host(_model(r))
         ref = M.noise(before[0], before[1], before[2], before[3], z, lr, 100.0, 0.005)
-        assert _same_bits(after[0], ref)
-        assert all(_same_bits(a, b) for a, b in zip(after[1:], before[1:]))
+        assert same_bits(after[0], ref)
+        assert all(same_bits(a, b) for a, b in zip(after[1:], before[1:]))
         if n > 40:
-            assert _same_bits(after[0][10:20], before[0][10:20]) and _same_bits(after[0][21], before[0][21]) and (after[0] != before[0]).any()
-    before = _host(_model(r))
+            assert same_bits(after[0][10:20], before[0][10:20]) and same_bits(after[0][21], before[0][21]) and (after[0] != before[0]).any()
+    before = host(_model(r))
     r.ctx.mcmc_noise(tz.data_ptr(), 0.0)                                     # lr == 0: nothing
-    assert all(_same_bits(a, b) for a, b in zip(_host(_model(r)), before))
+    assert all(same_bits(a, b) for a, b in zip(host(_model(r)), before))
 
 
 def test_regularize_matches_the_reference_bit_for_bit():
@@ -278,31 +262,31 @@ def test_regularize_matches_the_reference_bit_for_bit():
     r = _renderer(n, 1, seed=70)
     rng = np.random.default_rng(70)
     _set_opacities(r, rng.uniform(-9.0, 20.0, n).astype(f32))
-    model = _host(_model(r))
-    d_op = _cuda(rng.normal(0, 1e-4, (n, 1)).astype(f32))
-    d_sc = _cuda(rng.normal(0, 1e-4, (n, 3)).astype(f32))
+    model = host(_model(r))
+    d_op = dev(rng.normal(0, 1e-4, (n, 1)).astype(f32))
+    d_sc = dev(rng.normal(0, 1e-4, (n, 3)).astype(f32))
     c_o, c_s = M.reg_coefficients(0.01, 0.02, n)
     r._begin()
-    h_op, h_sc = _host([d_op, d_sc])
+    h_op, h_sc = host([d_op, d_sc])
     r.ctx.mcmc_regularize(B.GsGrads(None, d_sc.data_ptr(), None, d_op.data_ptr(), None), float(c_o), float(c_s))
     ref_o, ref_s = M.regularize(h_op, h_sc, model[3], model[1], c_o, c_s)
-    a_op, a_sc = _host([d_op, d_sc])
-    assert _same_bits(a_op.reshape(-1), ref_o) and _same_bits(a_sc, ref_s) and (a_op != h_op).any() and (a_sc != h_sc).any()
+    a_op, a_sc = host([d_op, d_sc])
+    assert same_bits(a_op.reshape(-1), ref_o) and same_bits(a_sc, ref_s) and (a_op != h_op).any() and (a_sc != h_sc).any()
     # a NULL d_scales, then a zero coefficient: that half is skipped
     r.ctx.mcmc_regularize(B.GsGrads(None, None, None, d_op.data_ptr(), None), float(c_o), float(c_s))
     ref_o2, _ = M.regularize(a_op, None, model[3], model[1], c_o, c_s)
-    b_op, b_sc = _host([d_op, d_sc])
-    assert _same_bits(b_op.reshape(-1), ref_o2) and _same_bits(b_sc, a_sc)
+    b_op, b_sc = host([d_op, d_sc])
+    assert same_bits(b_op.reshape(-1), ref_o2) and same_bits(b_sc, a_sc)
     r.ctx.mcmc_regularize(B.GsGrads(None, d_sc.data_ptr(), None, d_op.data_ptr(), None), 0.0, float(c_s))
-    c_op, c_sc = _host([d_op, d_sc])
-    assert _same_bits(c_op, b_op) and _same_bits(c_sc, M.regularize(None, b_sc, model[3], model[1], c_o, c_s)[1])
-    assert all(_same_bits(a, b) for a, b in zip(_host(_model(r)), model))
+    c_op, c_sc = host([d_op, d_sc])
+    assert same_bits(c_op, b_op) and same_bits(c_sc, M.regularize(None, b_sc, model[3], model[1], c_o, c_s)[1])
+    assert all(same_bits(a, b) for a, b in zip(host(_model(r)), model))
     # through the module: the renderer's own gradient buffer, coefficients lambda / N and lambda / (3 N)
     r.splatGrads.flat.zero_()
     mcmc.regularize(r, opacity_reg=0.01, scale_reg=0.02)
-    g_op, g_sc = _host([r.splatGrads.Δopacities.reshape(n, 1), r.splatGrads.Δscales.reshape(n, 3)])
+    g_op, g_sc = host([r.splatGrads.Δopacities.reshape(n, 1), r.splatGrads.Δscales.reshape(n, 3)])
     z_o, z_s = M.regularize(np.zeros(n, f32), np.zeros((n, 3), f32), model[3], model[1], c_o, c_s)
-    assert _same_bits(g_op.reshape(-1), z_o) and _same_bits(g_sc, z_s)
+    assert same_bits(g_op.reshape(-1), z_o) and same_bits(g_sc, z_s)
     assert not bool(r.splatGrads.Δmeans.any()) and not bool(r.splatGrads.Δshs.any())
 
 
@@ -316,18 +300,13 @@ def test_refusals_write_nothing():
     o[:50] = -8.0
     _set_opacities(r, o)
     snap = [t.clone() for t in _model(r)]
-    src = _cuda(np.full(20, 100, np.int32))
-    dst = _cuda(np.arange(200, 220, dtype=np.int32))
+    src = dev(np.full(20, 100, np.int32), None)
+    dst = dev(np.arange(200, 220, dtype=np.int32), None)
     z = torch.randn((n, 3), device="cuda")
     grad_arrays = [torch.zeros_like(t) for t in _model(r)]
     grads = B.GsGrads(*[t.data_ptr() for t in grad_arrays])
     sets, structs = _moment_sets(_model(r), 81)
     sets_snap = [[None if t is None else t.clone() for t in s] for s in sets]
-
-    def refused(call, code=B.GS_ERR_INVALID):
-        with pytest.raises(B.GsError) as e:
-            call()
-        assert e.value.code == code, str(e.value)
 
     r._begin()
     rel = lambda s=src.data_ptr(), d=dst.data_ptr(), m=20, mo=MIN_OPACITY, st=structs: r.ctx.mcmc_relocate(s, d, m, mo, st)
@@ -356,7 +335,7 @@ def test_refusals_write_nothing():
                  lambda: r2.ctx.mcmc_sample(cdf.data_ptr(), n, z.data_ptr(), 4, src.data_ptr()),
                  lambda: r2.ctx.mcmc_relocate(src.data_ptr(), dst.data_ptr(), 20, MIN_OPACITY, []),
                  lambda: r2.ctx.mcmc_noise(z.data_ptr(), 1.0), lambda: r2.ctx.mcmc_regularize(grads, 0.1, 0.1)):
-        refused(call, B.GS_ERR_UNSUPPORTED)
+        refused(call, code=B.GS_ERR_UNSUPPORTED)
     torch.cuda.synchronize()
     for a, b in zip(snap, _model(r)):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))

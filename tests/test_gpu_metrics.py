@@ -11,14 +11,11 @@ import numpy as np
 import pytest
 
 import metrics_ref as MR
+from common import render, same_bits, small_scene_renderer
 
 pytestmark = pytest.mark.gpu
 
 BIG = (3, 49, 193)
-
-
-def _same_bits(a, b):
-    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
 
 
 def _check(sums, smap, img, gt, S64, weight=None):
@@ -57,7 +54,7 @@ def test_metrics_family_against_the_float64_restatement(ctx, name):
         assert sums[3] == float(np.prod(shape))                              # w = 1: the count, exactly
         _check(sums, smap, c.img, c.gt, c.S)
         without_map, none = ctx.image_metrics_host(c.img, c.gt, None, False)
-        assert none is None and _same_bits(without_map, sums), shape          # the map is an output, not an input of the sums
+        assert none is None and same_bits(without_map, sums), shape           # the map is an output, not an input of the sums
 
 
 @pytest.mark.parametrize("name", ["uniform", "flat_noise"])
@@ -73,9 +70,9 @@ def test_metrics_weights(ctx, name):
         for w in (mask, wf):
             sums, smap = ctx.image_metrics_host(c.img, c.gt, w, True)
             _check(sums, smap, c.img, c.gt, c.S, w)
-            assert _same_bits(smap, map_plain)                               # the map is that of the whole unweighted images
+            assert same_bits(smap, map_plain)                                # the map is that of the whole unweighted images
         ones, map_ones = ctx.image_metrics_host(c.img, c.gt, np.ones(shape[1:], np.float32), True)
-        assert _same_bits(ones, plain) and _same_bits(map_ones, map_plain)
+        assert same_bits(ones, plain) and same_bits(map_ones, map_plain)
         zeros, _ = ctx.image_metrics_host(c.img, c.gt, np.zeros(shape[1:], np.float32), False)
         assert zeros[3] == 0.0 and np.isnan(B.metrics_finish(zeros)).all()
 
@@ -103,37 +100,24 @@ def _device_call(ctx, img, gt, weight=None, want_map=True):
     return sums.cpu().numpy(), smap.cpu().numpy() if want_map else None
 
 
-def _small_scene():
-    from gaussiansplat_amd import renderer as R, synthetic
-    n, W, H, deg = 2000, 64, 48, 1
-    scene = synthetic.make_scene(n, W, H, deg, 1)
-    r = R.getRenderer("GAUSSIAN_3D", (W, H, 3), (16, 16), None, scene, deterministic=True, tile_parts=1)
-    return r, W, H
-
-
-def _render(r, cam):
-    from gaussiansplat_amd import renderer as R
-    tps = R.preprocess(r, cam); R.compactIdxs(r); R.forward(r, tps)
-
-
 def test_metrics_are_bitwise_reproducible(ctx):
     from gaussiansplat_amd import backend as B, synthetic
     c = MR.case("smooth_near", BIG)
     w = np.random.default_rng(3).random(BIG[1:], dtype=np.float32)
     first = ctx.image_metrics_host(c.img, c.gt, w, True)
     again = ctx.image_metrics_host(c.img, c.gt, w, True)
-    assert _same_bits(first[0], again[0]) and _same_bits(first[1], again[1])
+    assert same_bits(first[0], again[0]) and same_bits(first[1], again[1])
     dev = _device_call(ctx, c.img, c.gt, w)
-    assert _same_bits(first[0], dev[0]) and _same_bits(first[1], dev[1])
+    assert same_bits(first[0], dev[0]) and same_bits(first[1], dev[1])
     fresh = B.Context()
     other = fresh.image_metrics_host(c.img, c.gt, w, True)
     fresh.close()
-    assert _same_bits(first[0], other[0]) and _same_bits(first[1], other[1])
-    r, W, H = _small_scene()                                                  # a context that has rendered frames, under two view slots
+    assert same_bits(first[0], other[0]) and same_bits(first[1], other[1])
+    r, _, W, H = small_scene_renderer(2000, 1)                                # a context that has rendered frames, under two view slots
     for view in (0, 1, 0):
-        _render(r, synthetic.scene_camera(W, view))
+        render(r, synthetic.scene_camera(W, view))
     used = r.ctx.image_metrics_host(c.img, c.gt, w, True)
-    assert _same_bits(first[0], used[0]) and _same_bits(first[1], used[1])
+    assert same_bits(first[0], used[0]) and same_bits(first[1], used[1])
 
 
 def test_metrics_scratch_follows_the_image_size():
@@ -147,7 +131,7 @@ def test_metrics_scratch_follows_the_image_size():
     _check(s_tiny, m_tiny, tiny.img, tiny.gt, tiny.S)
     again = c.image_metrics_host(big.img, big.gt, None, True)
     c.close()
-    assert _same_bits(first[0], again[0]) and _same_bits(first[1], again[1])
+    assert same_bits(first[0], again[0]) and same_bits(first[1], again[1])
 
 
 def test_metrics_refusals_leave_sums_and_map_untouched(ctx):
@@ -179,11 +163,11 @@ def test_metrics_between_forward_and_backward_change_no_gradient():
     from gaussiansplat_amd import metrics as M, renderer as R, synthetic
     out = []
     for with_metrics in (False, True):
-        r, W, H = _small_scene()
+        r, _, W, H = small_scene_renderer(2000, 1)
         cam = synthetic.scene_camera(W)
         dC = torch.as_tensor(synthetic.make_dC(W, H, 4)).cuda()
         gt = torch.rand((3, H, W), generator=torch.Generator().manual_seed(8)).cuda()
-        _render(r, cam)
+        render(r, cam)
         image = r.imageData.clone()
         if with_metrics:
             m = M.image_metrics(r, r.imageData, gt, want_map=True)
@@ -201,7 +185,7 @@ def test_evaluate_views_one_by_one_and_leaves_the_renderer_as_found():
     import dataclasses
     import torch
     from gaussiansplat_amd import metrics as M, synthetic
-    r, W, H = _small_scene()
+    r, _, W, H = small_scene_renderer(2000, 1)
     cams = [dataclasses.replace(synthetic.scene_camera(W, v), id=10 + v) for v in range(3)]
     g = torch.Generator().manual_seed(21)
     targets = [torch.rand((3, H, W), generator=g) for _ in range(2)] + [torch.rand((4, H, W), generator=g)]
@@ -209,18 +193,18 @@ def test_evaluate_views_one_by_one_and_leaves_the_renderer_as_found():
     train_cam = synthetic.scene_camera(W, 5)
     r.background = (0.25, 0.5, 0.75)
     r.active_sh_degree = 0
-    _render(r, train_cam)
+    render(r, train_cam)
     res = M.evaluate(r, cams, targets, weights, background=(1.0, 0.0, 0.5))
     assert r.camera is train_cam and r.background == (0.25, 0.5, 0.75) and r.active_sh_degree == 0
     assert len(res.per_view) == 3
-    _render(r, None)                                                          # None: "the last camera" is the training view again
+    render(r, None)                                                           # None: "the last camera" is the training view again
     again = r.imageData.clone()
-    _render(r, train_cam)
+    render(r, train_cam)
     assert torch.equal(again, r.imageData)
     # each view rendered alone, over the evaluation background
     r.background = (1.0, 0.0, 0.5)
     for v in range(3):
-        _render(r, cams[v])
+        render(r, cams[v])
         gt = targets[v].cuda()
         if gt.shape[0] == 4:                                                  # straight alpha over the evaluation background, four fp32 operations
             bg = torch.tensor([1.0, 0.0, 0.5], device="cuda")[:, None, None]
@@ -240,7 +224,7 @@ def test_evaluate_runs_under_the_2d_renderer():
     from gaussiansplat_amd import metrics as M, renderer as R, synthetic
     W, H = 80, 48
     r = R.getRenderer("GAUSSIAN_2D", (W, H, 3), (16, 16), None, synthetic.make_scene_2d(500, W, H, 3))
-    _render(r, None)
+    render(r, None)
     own = r.imageData.clone()
     other = torch.rand((3, H, W), generator=torch.Generator().manual_seed(2))
     res = M.evaluate(r, None, [own, other])
@@ -258,7 +242,7 @@ def test_training_with_an_evaluator_changes_no_loss():
     from gaussiansplat_amd import synthetic, train as TR
     runs = []
     for with_eval in (False, True):
-        r, W, H = _small_scene()
+        r, _, W, H = small_scene_renderer(2000, 1)
         cam = synthetic.scene_camera(W, 0)
         g = torch.Generator().manual_seed(33)
         gt = torch.rand((3, H, W), generator=g).cuda()

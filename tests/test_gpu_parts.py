@@ -15,19 +15,10 @@ pixel strips and walking the tile's list on its own.  What must hold:
 import numpy as np
 import pytest
 
-from common import hip_context, rel_l2, scene_and_cameras
+from common import GRADS, hip_context, rel_l2, run_frame, scene_and_cameras
 
 pytestmark = pytest.mark.gpu
-GRADS = ("means", "scales", "quats", "opacities", "shs")
 PIX_ATOL, PIX_RTOL, GRAD_REL_L2 = 1e-4, 1e-4, 1e-3
-
-
-def _frame(ctx, dC, deg):
-    ctx.preprocess(); ctx.bin()
-    img, tr = ctx.forward_host()
-    g = ctx.grads_alloc()
-    ctx.backward(dC, g)
-    return img, tr, ctx.grads_read(g, deg), ctx.work_counters_ex()
 
 
 @pytest.mark.parametrize("n,W,H,deg,seed,boost", [(10_000, 256, 256, 0, 1235, 0.0),      # C1
@@ -44,7 +35,8 @@ def test_every_partition_meets_the_oracle_bars(oracle, n, W, H, deg, seed, boost
     gref = O.backward(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"], deg, ocam, ref["ranges"], ref["ids"], dC,
                       t_min=1e-5, omp=True)
     ctx = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=1e-5, tile_parts=parts)
-    img, tr, grads, wc = _frame(ctx, dC, deg)
+    f = run_frame(ctx, dC, deg)
+    img, tr, grads, wc = f["img"], f["tr"], f["grads"], f["wc"]
     ctx.close()
     assert np.all(np.abs(img - ref["image"]) <= PIX_ATOL + PIX_RTOL * np.abs(ref["image"])), np.abs(img - ref["image"]).max()
     assert np.all(np.abs(tr - ref["trans"]) <= PIX_ATOL + PIX_RTOL * np.abs(ref["trans"]))
@@ -65,17 +57,17 @@ def test_partitions_agree(cull):
     out = {}
     for parts in (1, 2, 4):
         ctx = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=1e-5, tile_parts=parts, alpha_cull=cull, deterministic=True)
-        out[parts] = _frame(ctx, dC, deg)
+        out[parts] = run_frame(ctx, dC, deg)
         ctx.close()
-    assert 0 < out[1][3]["walked_fwd"] < 0.9 * 8_000 * 40                      # (the early-out is at work: pixels freeze)
+    assert 0 < out[1]["wc"]["walked_fwd"] < 0.9 * 8_000 * 40                   # (the early-out is at work: pixels freeze)
     for parts in (2, 4):
         a, b = out[1], out[parts]
         if not cull:
-            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+            assert np.array_equal(a["img"], b["img"]) and np.array_equal(a["tr"], b["tr"])
         else:
-            assert np.abs(a[0] - b[0]).max() <= 1e-6 and np.abs(a[1] - b[1]).max() <= 1e-6
+            assert np.abs(a["img"] - b["img"]).max() <= 1e-6 and np.abs(a["tr"] - b["tr"]).max() <= 1e-6
         for k in GRADS:
-            assert rel_l2(b[2][k], a[2][k]) <= 1e-5, (k, rel_l2(b[2][k], a[2][k]))
+            assert rel_l2(b["grads"][k], a["grads"][k]) <= 1e-5, (k, rel_l2(b["grads"][k], a["grads"][k]))
 
 
 def test_automatic_choice_and_frames_without_early_out(oracle):
@@ -89,15 +81,15 @@ def test_automatic_choice_and_frames_without_early_out(oracle):
         res = {}
         for parts in (0, expect):
             ctx = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=1e-5, tile_parts=parts, alpha_cull=False, deterministic=True)
-            res[parts] = _frame(ctx, dC, deg)
+            res[parts] = run_frame(ctx, dC, deg)
             assert ctx.tile_parts_of_frame() == expect
             ctx.close()
-        assert np.array_equal(res[0][0], res[expect][0]) and np.array_equal(res[0][1], res[expect][1])
+        assert np.array_equal(res[0]["img"], res[expect]["img"]) and np.array_equal(res[0]["tr"], res[expect]["tr"])
         for k in GRADS:
             if expect > 1:
-                assert np.array_equal(res[0][2][k], res[expect][2][k]), k
+                assert np.array_equal(res[0]["grads"][k], res[expect]["grads"][k]), k
             else:       # a grid with a launch order: the automatic mode may split the few tiles that stand above an even share (below)
-                assert rel_l2(res[0][2][k], res[expect][2][k]) <= 1e-5, k
+                assert rel_l2(res[0]["grads"][k], res[expect]["grads"][k]) <= 1e-5, k
     sc, cam, T, P, ocam = scene_and_cameras(3_000, 160, 96, 1, 9)
     ctx = hip_context(sc, cam, T, P, 160, 96, 1, order=1, t_min=0.0, tile_parts=4)
     ctx.preprocess(); ctx.bin(); ctx.forward_host()
@@ -115,7 +107,7 @@ def _slot_frames(ctx, dC, deg, nframes=2):
     out = None
     for _ in range(nframes):
         ctx.set_view_slot(0)
-        out = _frame(ctx, dC, deg)
+        out = run_frame(ctx, dC, deg)
     return out
 
 
@@ -148,15 +140,15 @@ def test_heavy_tiles_split_by_the_launch_order(oracle, cull):
         ctx.close()
     a, b = res[1], res[0]
     if not cull:
-        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+        assert np.array_equal(a["img"], b["img"]) and np.array_equal(a["tr"], b["tr"])
     else:
-        assert np.abs(a[0] - b[0]).max() <= 1e-6 and np.abs(a[1] - b[1]).max() <= 1e-6
+        assert np.abs(a["img"] - b["img"]).max() <= 1e-6 and np.abs(a["tr"] - b["tr"]).max() <= 1e-6
     for k in GRADS:
-        assert rel_l2(b[2][k], a[2][k]) <= 1e-5, (k, rel_l2(b[2][k], a[2][k]))
+        assert rel_l2(b["grads"][k], a["grads"][k]) <= 1e-5, (k, rel_l2(b["grads"][k], a["grads"][k]))
     if cull:                                                                   # against the oracle, with the production settings
         ref = O.render(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"], deg, ocam, order=1, t_min=1e-5, omp=True)
         gref = O.backward(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"], deg, ocam, ref["ranges"], ref["ids"], dC, t_min=1e-5, omp=True)
-        img, tr, grads = b[0], b[1], b[2]
+        img, tr, grads = b["img"], b["tr"], b["grads"]
         assert np.all(np.abs(img - ref["image"]) <= PIX_ATOL + PIX_RTOL * np.abs(ref["image"])), np.abs(img - ref["image"]).max()
         assert np.all(np.abs(tr - ref["trans"]) <= PIX_ATOL + PIX_RTOL * np.abs(ref["trans"]))
         for k in GRADS:
@@ -175,13 +167,13 @@ def test_split_entries_are_whole_tiles_for_capped_lists_and_uniform_scenes():
     res = {}
     for name, kw in (("whole", dict(tile_parts=1, list_cap=1)), ("capped_under_split_order", dict(tile_parts=0, list_cap=2))):
         ctx = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=1e-5, deterministic=True, debug_flags=ALWAYS_ORDER, **kw)
-        res[name] = _slot_frames(ctx, dC, deg, nframes=3) + (ctx.list_stats(),)
+        res[name] = dict(_slot_frames(ctx, dC, deg, nframes=3), st=ctx.list_stats())
         ctx.close()
     a, b = res["whole"], res["capped_under_split_order"]
-    assert b[4]["capped"]
-    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    assert b["st"]["capped"]
+    assert np.array_equal(a["img"], b["img"]) and np.array_equal(a["tr"], b["tr"])
     for k in GRADS:
-        assert np.array_equal(a[2][k], b[2][k]), k
+        assert np.array_equal(a["grads"][k], b["grads"][k]), k
     # the uniform BASELINE scene on a grid with more tiles than wave slots: no tile stands above an even share
     n, W, H = 250_000, 1920, 1080
     sc, cam, T, P, ocam = scene_and_cameras(n, W, H, deg, seed)
@@ -211,24 +203,24 @@ def test_heavy_tiles_backward_as_list_segments(oracle):
         ctx = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=1e-5, tile_parts=parts, deterministic=True, debug_flags=ALWAYS_ORDER)
         for _ in range(4):
             ctx.set_view_slot(0)
-            res[parts] = _frame(ctx, dC, deg)
+            res[parts] = run_frame(ctx, dC, deg)
         ctx.close()
     # the segments really ran: clocked backward launch (float atomics) of the same frame, records per workgroup; the segment units come first
     ctx = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=1e-5, tile_parts=0, debug_flags=ALWAYS_ORDER)
     for _ in range(3):
         ctx.set_view_slot(0)
-        _frame(ctx, dC, deg)
+        run_frame(ctx, dC, deg)
     clk = ctx.tile_clock(1, -30)
     nseg_units = 8 * (FRONT // 24) * 7
     assert clk.shape[0] > nseg_units + FRONT and int((clk[:nseg_units, 1] > 0).sum()) >= 8, int((clk[:nseg_units, 1] > 0).sum())
     ctx.close()
     a, b = res[1], res[0]
-    assert np.abs(a[0] - b[0]).max() <= 1e-6 and np.abs(a[1] - b[1]).max() <= 1e-6
+    assert np.abs(a["img"] - b["img"]).max() <= 1e-6 and np.abs(a["tr"] - b["tr"]).max() <= 1e-6
     for k in GRADS:
-        assert rel_l2(b[2][k], a[2][k]) <= 1e-5, (k, rel_l2(b[2][k], a[2][k]))
-        e = rel_l2(b[2][k], np.asarray(gref[k]).reshape(b[2][k].shape))
+        assert rel_l2(b["grads"][k], a["grads"][k]) <= 1e-5, (k, rel_l2(b["grads"][k], a["grads"][k]))
+        e = rel_l2(b["grads"][k], np.asarray(gref[k]).reshape(b["grads"][k].shape))
         assert e <= GRAD_REL_L2, (k, e)
-    assert b[3]["walked_bwd"] == b[3]["walked_fwd"] or b[3]["walked_bwd"] >= a[3]["walked_bwd"]
+    assert b["wc"]["walked_bwd"] == b["wc"]["walked_fwd"] or b["wc"]["walked_bwd"] >= a["wc"]["walked_bwd"]
 
 
 @pytest.mark.parametrize("n,W,H,deg,seed,boost,segs", [(10_000, 256, 256, 0, 1235, 0.0, 2),       # C1: 256 tiles, two segments x four pixel parts
@@ -247,15 +239,15 @@ def test_small_grids_backward_as_list_segments(oracle, n, W, H, deg, seed, boost
     gref = O.backward(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"], deg, ocam, ref["ranges"], ref["ids"], dC, t_min=1e-5, omp=True)
     ctx = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=1e-5, tile_parts=0, deterministic=True)
     ctx.set_view_slot(2)
-    first = _frame(ctx, dC, deg)                                               # no history yet: pixel parts
+    first = run_frame(ctx, dC, deg)                                            # no history yet: pixel parts
     for _ in range(2):
         ctx.set_view_slot(2)
-        got = _frame(ctx, dC, deg)                                             # list segments
+        got = run_frame(ctx, dC, deg)                                          # list segments
     ctx.close()
-    assert np.array_equal(first[0], got[0]) and np.array_equal(first[1], got[1])
-    assert np.all(np.abs(got[0] - ref["image"]) <= PIX_ATOL + PIX_RTOL * np.abs(ref["image"]))
+    assert np.array_equal(first["img"], got["img"]) and np.array_equal(first["tr"], got["tr"])
+    assert np.all(np.abs(got["img"] - ref["image"]) <= PIX_ATOL + PIX_RTOL * np.abs(ref["image"]))
     for k in GRADS:
-        assert rel_l2(got[2][k], first[2][k]) <= 1e-5, (k, rel_l2(got[2][k], first[2][k]))
-        e = rel_l2(got[2][k], np.asarray(gref[k]).reshape(got[2][k].shape))
+        assert rel_l2(got["grads"][k], first["grads"][k]) <= 1e-5, (k, rel_l2(got["grads"][k], first["grads"][k]))
+        e = rel_l2(got["grads"][k], np.asarray(gref[k]).reshape(got["grads"][k].shape))
         assert e <= GRAD_REL_L2, (k, e)
-    assert got[3]["walked_bwd"] >= first[3]["walked_bwd"] > 0                   # (the segments' sum is the tile's whole walk; a part's count is its own)
+    assert got["wc"]["walked_bwd"] >= first["wc"]["walked_bwd"] > 0             # (the segments' sum is the tile's whole walk; a part's count is its own)

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import pergaussian_ref as PR
+from common import hip_context, run_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -34,27 +35,11 @@ def _ctx(s, **kw):
         ctx.set_model_2d_host(sc["means"], sc["scales"], sc["rots"], sc["opacities"], sc["colors"])
         ctx.set_image_size(s["W"], s["H"])
         return ctx
-    from common import hip_context
     return hip_context(sc, s["cam"], s["T"], s["P"], s["W"], s["H"], s["deg"], order=1, **kw)
 
 
-def _frame(ctx, s, slot=None, overwrite=False, two_phases=False):
-    from gaussiansplat_amd import backend as B
-    if slot is not None:
-        ctx.set_view_slot(slot)
-    ctx.preprocess(); ctx.bin()
-    rounds = ctx.num_rounds
-    ctx.forward_host()
-    st = ctx.list_stats()
-    g = ctx.grads_alloc()
-    if two_phases:
-        ctx.backward(s["dC"], g, overwrite=overwrite, phase="composite")
-        ctx.backward(s["dC"], g, overwrite=overwrite, phase="params")
-    else:
-        ctx.backward(s["dC"], g, overwrite=overwrite)
-    grads = ctx.grads_read_2d(g) if s["kind"] == "2d" else ctx.grads_read(g, s["deg"])
-    return dict(g2d=ctx.get_array(B.ARR_GRAD2D), grads=grads, wc=ctx.work_counters_ex(), st=st, rounds=rounds,
-                parts=ctx.tile_parts_of_frame(), fill=ctx.tail_fill_blocks())
+def _frame(ctx, s, **kw):
+    return run_frame(ctx, s["dC"], s["deg"], kind=s["kind"], g2d=True, **kw)
 
 
 def _worst(err, bound, sel):
@@ -211,7 +196,8 @@ def test_overwrite_with_and_without_tail_fill(oracle, name, no_fill):
     ctx = _ctx(s, t_min=1e-5, deterministic=True, bin_path=3, tile_parts=1, debug_flags=B.GS_DEBUG_NO_TAIL_FILL if no_fill else 0)
     for frame in (1, 2):
         f = _frame(ctx, s, overwrite=True)
-        assert (f["fill"] == (0, 0)) if no_fill else (f["fill"][1] > 0), f["fill"]
+        fill = ctx.tail_fill_blocks()
+        assert (fill == (0, 0)) if no_fill else (fill[1] > 0), fill
         _check(name, 1e-5, f, f"overwrite no_fill={int(no_fill)} frame {frame}", True, may_drop=True)
     ctx.close()
 
@@ -221,6 +207,6 @@ def test_composite_then_params(oracle, name):
     """GS_BWD_COMPOSITE_ONLY followed by GS_BWD_PARAMS_ONLY (a multi-GPU host runs the phases apart)"""
     s = PR.scene(name)
     ctx = _ctx(s, t_min=1e-5, tile_parts=1)
-    f = _frame(ctx, s, two_phases=True)
+    f = _frame(ctx, s, phases=("composite", "params"))
     ctx.close()
     _check(name, 1e-5, f, "composite only, then params only", False, may_drop=True)

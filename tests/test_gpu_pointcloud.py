@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import knn_ref as K
+from common import bits, dev, on_torch_stream, refused, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -35,28 +36,23 @@ def refs(clouds):
     return {name: K.knn_mean_dist2(p) for name, p in clouds.items()}
 
 
-def _cuda(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, f32)).cuda()
-
-
 def _knn(ctx, pts):
     """dist2 of the host array pts through the raw call, with the checks every case shares: the pad behind dist2 and the points are untouched"""
     import torch
     n = len(pts)
-    tp = _cuda(pts)
+    tp = dev(pts)
     out = torch.full((n + PAD,), float(SENTINEL), dtype=torch.float32, device="cuda")
-    ctx.set_stream(torch.cuda.current_stream().cuda_stream or 1)          # torch's current stream; 0, the legacy default stream, is 1 here
+    on_torch_stream(ctx)
     ctx.knn_mean_dist2(tp.data_ptr(), n, out.data_ptr())
     torch.cuda.synchronize()
     got = out.cpu().numpy()
     assert np.all(got[n:] == SENTINEL)
-    assert K.same_bits(tp.cpu().numpy(), pts)
+    assert same_bits(tp.cpu().numpy(), pts, nan_equal=True)
     return got[:n]
 
 
 def _mismatch(got, want):
-    return np.flatnonzero(~((K.bits(got) == K.bits(want)) | (np.isnan(got) & np.isnan(want))))
+    return np.flatnonzero(~((bits(got) == bits(want)) | (np.isnan(got) & np.isnan(want))))
 
 
 # ---------------------------------------------------------------- 1. bit for bit against the NumPy brute force
@@ -82,7 +78,7 @@ def test_python_knn_mean_dist2_on_a_tensor(ctx, clouds, refs):
     from gaussiansplat_amd import pointcloud
     pts = clouds["nonfinite"]
     for c in (None, ctx):                                                # a short-lived ctx of its own, or the caller's
-        got = pointcloud.knn_mean_dist2(_cuda(pts), c).cpu().numpy()
+        got = pointcloud.knn_mean_dist2(dev(pts), c).cpu().numpy()
         assert _mismatch(got, refs["nonfinite"]).size == 0
     with pytest.raises(TypeError):
         pointcloud.knn_mean_dist2(pts)                                   # host memory: there is no CPU path
@@ -95,7 +91,7 @@ def test_larger_cloud_matches_torch_brute_force(ctx, kind):
     from gaussiansplat_amd import synthetic
     n = 30001
     pts = K.uniform(n, 21) if kind == "uniform" else synthetic.make_scene(n, 1920, 1080, 0, seed=22, clustered=True)["means"]
-    want = K.torch_brute(_cuda(pts))
+    want = K.torch_brute(dev(pts))
     assert np.isfinite(want).all() and np.count_nonzero(want > 0) > n // 2
     got = _knn(ctx, pts)
     bad = _mismatch(got, want)
@@ -110,7 +106,7 @@ def test_a_search_between_forward_and_backward_leaves_the_frame_untouched():
     scene = synthetic.make_scene(n, W, H, deg, seed=31)
     cam = synthetic.scene_camera(W)
     dC = torch.as_tensor(synthetic.make_dC(W, H, 32)).cuda()
-    pts = _cuda(K.uniform(5000, 33))
+    pts = dev(K.uniform(5000, 33))
     want = K.knn_mean_dist2(pts.cpu().numpy())
     res = []
     for with_knn in (False, True):
@@ -128,7 +124,7 @@ def test_a_search_between_forward_and_backward_leaves_the_frame_untouched():
             assert _mismatch(d2.cpu().numpy(), want).size == 0
     (img0, tr0, g0), (img1, tr1, g1) = res
     assert float(tr0.min()) < 1.0 and np.count_nonzero(g0) > g0.size // 10      # a real frame with real gradients
-    assert K.same_bits(img0, img1) and K.same_bits(tr0, tr1) and K.same_bits(g0, g1)
+    assert same_bits(img0, img1, nan_equal=True) and same_bits(tr0, tr1, nan_equal=True) and same_bits(g0, g1, nan_equal=True)
 
 
 # ---------------------------------------------------------------- 4. gs_init_from_points
@@ -165,22 +161,22 @@ def test_init_from_points_matches_numpy(ctx, deg, with_colors):
     import torch
     n, k3 = 1000, 3 * (deg + 1) ** 2
     pts, col, d2 = _init_inputs(n)
-    tp, tc, td = _cuda(pts), _cuda(col), _cuda(d2)
+    tp, tc, td = dev(pts), dev(col), dev(d2)
     dst = _dst(n, k3)
     logit = f32(math.log(0.1 / 0.9))
-    ctx.set_stream(torch.cuda.current_stream().cuda_stream or 1)          # torch's current stream; 0, the legacy default stream, is 1 here
+    on_torch_stream(ctx)
     ctx.init_from_points(tp.data_ptr(), tc.data_ptr() if with_colors else None, td.data_ptr(), n, deg, float(logit), _grads(dst))
     torch.cuda.synchronize()
     means, scales, quats, opac, shs = (t.cpu().numpy() for t in dst)
     for a in (means, scales, quats, opac, shs):
         assert np.all(a[n:] == SENTINEL)
-    assert K.same_bits(means[:n], pts)
-    assert K.same_bits(quats[:n], np.tile(np.array([1.0, 0.0, 0.0, 0.0], f32), (n, 1)))
-    assert K.same_bits(opac[:n], np.full((n, 1), logit, f32))
+    assert same_bits(means[:n], pts, nan_equal=True)
+    assert same_bits(quats[:n], np.tile(np.array([1.0, 0.0, 0.0, 0.0], f32), (n, 1)), nan_equal=True)
+    assert same_bits(opac[:n], np.full((n, 1), logit, f32), nan_equal=True)
     want_sh = np.zeros((n, k3), f32)                                     # +0.0
     if with_colors:
         want_sh[:, :3] = (col - f32(0.5)) / SH_C0
-    assert K.same_bits(shs[:n], want_sh)
+    assert same_bits(shs[:n], want_sh, nan_equal=True)
     with np.errstate(invalid="ignore"):
         v = np.where(d2 > f32(1e-7), d2, f32(1e-7))                      # a NaN compares false
     assert v[0] == v[1] == v[2] == v[4] == f32(1e-7) and v[3] == np.inf and v[5] > f32(1e-7)
@@ -188,9 +184,9 @@ def test_init_from_points_matches_numpy(ctx, deg, with_colors):
         want_s = (0.5 * np.log(v.astype(np.float64))).astype(f32)
     assert want_s[3] == np.inf and want_s[6] == 0.0
     s = scales[:n]
-    assert K.same_bits(s[:, 0], s[:, 1]) and K.same_bits(s[:, 0], s[:, 2])
+    assert same_bits(s[:, 0], s[:, 1], nan_equal=True) and same_bits(s[:, 0], s[:, 2], nan_equal=True)
     fin = np.isfinite(want_s)
-    assert K.same_bits(s[~fin, 0], want_s[~fin])
+    assert same_bits(s[~fin, 0], want_s[~fin], nan_equal=True)
     steps = np.abs(_ordered(s[fin, 0]) - _ordered(want_s[fin]))
     print("init_from_points deg %d: scales differ from float32(0.5 * log(float64(v))) by at most %d float steps (%d of %d rows differ)"
           % (deg, int(steps.max()), int(np.count_nonzero(steps)), int(fin.sum())))
@@ -202,46 +198,41 @@ def test_refusals_return_their_code_and_write_nothing(ctx):
     from gaussiansplat_amd import backend as B
     n, deg, k3 = 200, 1, 12
     pts, col, d2 = _init_inputs(n)
-    tp, tc, td = _cuda(pts), _cuda(col), _cuda(d2)
+    tp, tc, td = dev(pts), dev(col), dev(d2)
     dst = _dst(n, k3)
-    ctx.set_stream(torch.cuda.current_stream().cuda_stream or 1)          # torch's current stream; 0, the legacy default stream, is 1 here
+    on_torch_stream(ctx)
     P, Cc, D = tp.data_ptr(), tc.data_ptr(), td.data_ptr()
 
-    def refused(code, call):
-        with pytest.raises(B.GsError) as e:
-            call()
-        assert e.value.code == code, e.value
-
     for bad_deg in (-1, 4):
-        refused(B.GS_ERR_INVALID, lambda: ctx.init_from_points(P, Cc, D, n, bad_deg, -2.0, _grads(dst)))
-    refused(B.GS_ERR_INVALID, lambda: ctx.init_from_points(None, Cc, D, n, deg, -2.0, _grads(dst)))
-    refused(B.GS_ERR_INVALID, lambda: ctx.init_from_points(P, Cc, None, n, deg, -2.0, _grads(dst)))
-    refused(B.GS_ERR_INVALID, lambda: ctx.init_from_points(P, Cc, D, -1, deg, -2.0, _grads(dst)))
+        refused(lambda: ctx.init_from_points(P, Cc, D, n, bad_deg, -2.0, _grads(dst)), code=B.GS_ERR_INVALID)
+    refused(lambda: ctx.init_from_points(None, Cc, D, n, deg, -2.0, _grads(dst)), code=B.GS_ERR_INVALID)
+    refused(lambda: ctx.init_from_points(P, Cc, None, n, deg, -2.0, _grads(dst)), code=B.GS_ERR_INVALID)
+    refused(lambda: ctx.init_from_points(P, Cc, D, -1, deg, -2.0, _grads(dst)), code=B.GS_ERR_INVALID)
     for i in range(5):                                                   # a NULL destination
         g = _grads(dst)
         setattr(g, B.GsGrads._fields_[i][0], None)
-        refused(B.GS_ERR_INVALID, lambda: ctx.init_from_points(P, Cc, D, n, deg, -2.0, g))
+        refused(lambda: ctx.init_from_points(P, Cc, D, n, deg, -2.0, g), code=B.GS_ERR_INVALID)
     g = _grads(dst)
     g.d_scales = g.d_means + 4                                           # two destinations overlap
-    refused(B.GS_ERR_INVALID, lambda: ctx.init_from_points(P, Cc, D, n, deg, -2.0, g))
+    refused(lambda: ctx.init_from_points(P, Cc, D, n, deg, -2.0, g), code=B.GS_ERR_INVALID)
     for src in (P, Cc, D):                                               # a destination overlaps a source
         g = _grads(dst)
         g.d_opacities = src
-        refused(B.GS_ERR_INVALID, lambda: ctx.init_from_points(P, Cc, D, n, deg, -2.0, g))
+        refused(lambda: ctx.init_from_points(P, Cc, D, n, deg, -2.0, g), code=B.GS_ERR_INVALID)
     # the search
     out = torch.full((n + PAD,), float(SENTINEL), dtype=torch.float32, device="cuda")
-    refused(B.GS_ERR_INVALID, lambda: ctx.knn_mean_dist2(None, n, out.data_ptr()))
-    refused(B.GS_ERR_INVALID, lambda: ctx.knn_mean_dist2(P, n, None))
-    refused(B.GS_ERR_INVALID, lambda: ctx.knn_mean_dist2(P, -1, out.data_ptr()))
-    refused(B.GS_ERR_INVALID, lambda: ctx.knn_mean_dist2(P, n, P + 4 * (3 * n - 1)))        # dist2 starts on the last float of points
-    refused(B.GS_ERR_INVALID, lambda: ctx.knn_mean_dist2(P + 4, n - 1, P))                  # ... or ends inside them
-    refused(B.GS_ERR_UNSUPPORTED, lambda: ctx.knn_mean_dist2(P, 2 ** 31, out.data_ptr()))
+    refused(lambda: ctx.knn_mean_dist2(None, n, out.data_ptr()), code=B.GS_ERR_INVALID)
+    refused(lambda: ctx.knn_mean_dist2(P, n, None), code=B.GS_ERR_INVALID)
+    refused(lambda: ctx.knn_mean_dist2(P, -1, out.data_ptr()), code=B.GS_ERR_INVALID)
+    refused(lambda: ctx.knn_mean_dist2(P, n, P + 4 * (3 * n - 1)), code=B.GS_ERR_INVALID)   # dist2 starts on the last float of points
+    refused(lambda: ctx.knn_mean_dist2(P + 4, n - 1, P), code=B.GS_ERR_INVALID)             # ... or ends inside them
+    refused(lambda: ctx.knn_mean_dist2(P, 2 ** 31, out.data_ptr()), code=B.GS_ERR_UNSUPPORTED)
     ctx.knn_mean_dist2(P, 0, out.data_ptr())                             # n == 0: fine, nothing enqueued
     ctx.knn_mean_dist2(None, 0, None)
     torch.cuda.synchronize()
     for t in dst + [out]:
         assert bool((t == float(SENTINEL)).all())
-    assert K.same_bits(tp.cpu().numpy(), pts) and K.same_bits(tc.cpu().numpy(), col) and K.same_bits(td.cpu().numpy(), d2)
+    assert same_bits(tp.cpu().numpy(), pts, nan_equal=True) and same_bits(tc.cpu().numpy(), col, nan_equal=True) and same_bits(td.cpu().numpy(), d2, nan_equal=True)
 
 
 # ---------------------------------------------------------------- 5. end to end
@@ -264,16 +255,16 @@ def test_renderer_from_a_point_cloud():
     # what from_points built is what the contract says, from the reference search
     v = np.maximum(K.knn_mean_dist2(means), f32(1e-7))
     steps = np.abs(_ordered(scene["scales"][:, 0]) - _ordered((0.5 * np.log(v.astype(np.float64))).astype(f32)))
-    assert steps.max() <= 1 and K.same_bits(scene["means"], means)
-    assert K.same_bits(scene["opacities"], np.full(n, f32(math.log(0.1 / 0.9)), f32))
-    assert K.same_bits(scene["shs"][:, 0, :], (colours - f32(0.5)) / SH_C0) and not scene["shs"][:, 1:, :].any()
+    assert steps.max() <= 1 and same_bits(scene["means"], means, nan_equal=True)
+    assert same_bits(scene["opacities"], np.full(n, f32(math.log(0.1 / 0.9)), f32), nan_equal=True)
+    assert same_bits(scene["shs"][:, 0, :], (colours - f32(0.5)) / SH_C0, nan_equal=True) and not scene["shs"][:, 1:, :].any()
     r2 = R.getRenderer("GAUSSIAN_3D", (W, H, 3), (16, 16), None, scene, deterministic=True, tile_parts=1)
     imgs = []
     for r in (r1, r2):
         R.forward(r, (R.preprocess(r, cams[0]), R.compactIdxs(r))[0])
         torch.cuda.synchronize()
         imgs.append((r.imageData.cpu().numpy().copy(), r.transmittance.cpu().numpy().copy()))
-    assert K.same_bits(imgs[0][0], imgs[1][0]) and K.same_bits(imgs[0][1], imgs[1][1])
+    assert same_bits(imgs[0][0], imgs[1][0], nan_equal=True) and same_bits(imgs[0][1], imgs[1][1], nan_equal=True)
     assert float(imgs[0][1].min()) < 1.0 and float(imgs[0][0].max()) > 0.0
     R.resetGrads(r1)
     R.backward(r1, torch.as_tensor(synthetic.make_dC(W, H, 53)).cuda())

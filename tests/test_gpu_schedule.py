@@ -4,10 +4,9 @@ and float-atomic gradients equal to atomic-order noise."""
 import numpy as np
 import pytest
 
-from common import hip_context, rel_l2, scene_and_cameras
+from common import GRADS, hip_context, rel_l2, scene_and_cameras
 
 pytestmark = pytest.mark.gpu
-GRADS = ("means", "scales", "quats", "opacities", "shs")
 
 
 @pytest.mark.parametrize("n,W,H,deg,scale_shift,t_min", [

@@ -7,6 +7,8 @@ aligned), 128 x 96 pixels (48 tiles); one case at N = 300, 64 x 48 with separate
 import numpy as np
 import pytest
 
+from common import bits, same_bits
+
 pytestmark = pytest.mark.gpu
 
 W, H, N = 128, 96, 1281
@@ -31,13 +33,6 @@ def _twin_scene(sc, active):
     tw = dict(sc)
     tw["shs"] = np.ascontiguousarray(sc["shs"][:, :(active + 1) ** 2, :])
     return tw
-
-
-def _bits(t):
-    import torch
-    if isinstance(t, torch.Tensor):
-        t = t.detach().cpu().numpy()
-    return np.ascontiguousarray(t, np.float32).view(np.uint32)
 
 
 class _Rig:
@@ -162,7 +157,7 @@ def test_default_minus_one_and_own_degree_are_the_same_renderer():
         rig.close()
     for other in res[1:]:
         for a, b in zip(res[0], other):
-            assert np.array_equal(_bits(a), _bits(b))
+            assert same_bits(a, b)
     assert np.isfinite(res[0][6]).all() and np.any(res[0][6][:, 12:] != 0)   # the band-2 gradients are there
 
 
@@ -192,9 +187,9 @@ def _overwrite_case(stored, active, n, w, h, fill_flag, layouts):
             if phases == "all":                                            # the composite launch carried the zero fill of d_shs, or did not
                 assert (rig.ctx.tail_fill_blocks()[1] > 0) == (fill_flag == 0), tag
             for k in range(4):
-                assert np.array_equal(_bits(got[k]), _bits(want[k])), (tag, k)
-            assert np.array_equal(_bits(got[4][:, :ka3]), _bits(want[4])), tag
-            assert not _bits(got[4][:, ka3:]).any(), (tag, "an inactive float is not +0")
+                assert same_bits(got[k], want[k]), (tag, k)
+            assert same_bits(got[4][:, :ka3], want[4]), tag
+            assert not bits(got[4][:, ka3:]).any(), (tag, "an inactive float is not +0")
     rig.close()
 
 
@@ -228,10 +223,10 @@ def test_backward_accumulate_two_views(stored, active, layout):
             _backward(rig, gg, _dC(v), overwrite=False)
     got, want = g.host(), gt.host()
     for k in range(4):
-        assert np.array_equal(_bits(got[k]), _bits(want[k])), k
-    assert np.array_equal(_bits(got[4][:, :ka3]), _bits(want[4]))
-    assert np.array_equal(_bits(got[4][:, ka3:]), _bits(start[4][:, ka3:]))     # neither read nor written
-    assert not np.array_equal(_bits(got[4][:, :ka3]), _bits(start[4][:, :ka3]))
+        assert same_bits(got[k], want[k]), k
+    assert same_bits(got[4][:, :ka3], want[4])
+    assert same_bits(got[4][:, ka3:], start[4][:, ka3:])                        # neither read nor written
+    assert not same_bits(got[4][:, :ka3], start[4][:, :ka3])
     full.close(); tw.close()
 
 
@@ -262,11 +257,11 @@ def test_backward_adam_equals_backward_then_adam_step(stored, active, selective)
         res.append([t.cpu().numpy().copy() for t in rig.p] + m.host() + v.host())
         rig.close()
     for k, (a, b) in enumerate(zip(*res)):
-        assert np.array_equal(_bits(a), _bits(b)), k
+        assert same_bits(a, b), k
     ka3 = _k3(active)
     shs0 = sc["shs"].reshape(N, -1)
-    moved = (_bits(res[0][4]) != _bits(shs0)).any(axis=1)
-    assert (_bits(res[0][4][:, ka3:]) != _bits(shs0[:, ka3:])).any()      # old moments move the inactive floats of the rows that are stepped
+    moved = (bits(res[0][4]) != bits(shs0)).any(axis=1)
+    assert (bits(res[0][4][:, ka3:]) != bits(shs0[:, ka3:])).any()        # old moments move the inactive floats of the rows that are stepped
     if selective:
         assert 0 < moved.sum() < N                                          # ... and dead rows stay as they were
     else:
@@ -292,11 +287,11 @@ def test_backward_sgd_equals_backward_then_sgd_step(stored, active):
         res.append([t.cpu().numpy().copy() for t in rig.p])
         rig.close()
     for k, (a, b) in enumerate(zip(*res)):
-        assert np.array_equal(_bits(a), _bits(b)), k
+        assert same_bits(a, b), k
     ka3 = _k3(active)
     shs0 = sc["shs"].reshape(N, -1)
-    assert np.array_equal(_bits(res[0][4][:, ka3:]), _bits(shs0[:, ka3:]))
-    assert not np.array_equal(_bits(res[0][4][:, :ka3]), _bits(shs0[:, :ka3]))
+    assert same_bits(res[0][4][:, ka3:], shs0[:, ka3:])
+    assert not same_bits(res[0][4][:, :ka3], shs0[:, :ka3])
 
 
 # ---------------------------------------------------------------- 6. exchange kernels
@@ -311,12 +306,12 @@ def test_exchange_kernels_rebuild_the_active_bands(stored, active, overwrite):
     dense = rng.standard_normal((3, N, 3)).astype(np.float32)
     dense[rng.random((3, N)) < 0.6] = 0.0                                 # untouched gaussians
     dense[1] = 0.0                                                          # a view that touches nothing
-    bits, counts, rows = D.pack_touched_rows(torch.from_numpy(dense))
+    mask, counts, rows = D.pack_touched_rows(torch.from_numpy(dense))
     cap = int(counts.max()) + 5
     padded = torch.full((3, cap, 3), float("nan"), dtype=torch.float32)
     for v, r in enumerate(rows):
         padded[v, :r.shape[0]] = r
-    d_dense, d_bits, d_rows = torch.from_numpy(dense).cuda(), bits.cuda().contiguous(), padded.cuda().contiguous()
+    d_dense, d_bits, d_rows = torch.from_numpy(dense).cuda(), mask.cuda().contiguous(), padded.cuda().contiguous()
     ka3, ks3 = _k3(active), _k3(stored)
     start = rng.standard_normal((N, ks3)).astype(np.float32) if not overwrite else np.full((N, ks3), np.nan, np.float32)
     full, tw = _Rig(sc, stored, active), _Rig(_twin_scene(sc, active), active)
@@ -333,11 +328,11 @@ def test_exchange_kernels_rebuild_the_active_bands(stored, active, overwrite):
     for kind in ("views", "touched"):
         got, want = res["full", kind], res["twin", kind]
         assert np.isfinite(want).all() and np.any(want != start[:, :ka3])
-        assert np.array_equal(_bits(got[:, :ka3]), _bits(want)), kind
+        assert same_bits(got[:, :ka3], want), kind
         if overwrite:
-            assert not _bits(got[:, ka3:]).any(), kind
+            assert not bits(got[:, ka3:]).any(), kind
         else:
-            assert np.array_equal(_bits(got[:, ka3:]), _bits(start[:, ka3:])), kind
+            assert same_bits(got[:, ka3:], start[:, ka3:]), kind
     full.close(); tw.close()
 
 
@@ -397,7 +392,7 @@ def test_contract_the_request_survives_set_model():
     img = rig.ctx.forward_host()[0]
     tw = _Rig(_twin_scene(other, 1), 1)
     tw.frame(0)
-    assert np.array_equal(_bits(img), _bits(tw.ctx.forward_host()[0]))
+    assert same_bits(img, tw.ctx.forward_host()[0])
     p0 = [torch.as_tensor(np.ascontiguousarray(other[k], np.float32).reshape(300, -1)[:, :w]).cuda().contiguous()
           for k, w in zip(("means", "scales", "quats", "opacities", "shs"), (3, 3, 4, 1, 3))]
     rig.ctx.set_model_device(300, 0, [t.data_ptr() for t in p0])           # a model below the request: its own degree, the request kept

@@ -17,13 +17,12 @@ import os
 import numpy as np
 import pytest
 
-from common import hip_context, rel_l2, scene_and_cameras
+from common import GRADS, hip_context, rel_l2, scene_and_cameras
 
 pytestmark = pytest.mark.gpu
 
 PIX_ATOL, PIX_RTOL = 1e-4, 1e-4
 GRAD_REL_L2 = 1e-3
-GRADS = ("means", "scales", "quats", "opacities", "shs")
 _REPORT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "parity_sizes.json")
 
 

@@ -6,28 +6,14 @@ import os
 import numpy as np
 import pytest
 
-from common import hip_context, rel_l2, scene_and_cameras
+from common import GRADS, hip_context, one_wave_per_tile, rel_l2, run_frame, scene_and_cameras
 
 pytestmark = pytest.mark.gpu
-GRADS = ("means", "scales", "quats", "opacities", "shs")
 
 
 @pytest.fixture(autouse=True)
 def _one_wave_per_tile(monkeypatch):
-    """Frames binned in depth slabs are composited by one wave per tile (gs_config.tile_parts); the plain frames they are compared with
-    BIT FOR BIT here must be too: on these small grids the default would give a tile two or four waves, each testing its entries against
-    its own pixels (differences below 2^-27 per entry, tests/test_gpu_parts.py)."""
-    monkeypatch.setenv("GSPLAT_TILE_PARTS", "1")
-
-
-def _frame(ctx, dC, deg):
-    ctx.preprocess(); ctx.bin()
-    rounds = ctx.num_rounds
-    img, tr = ctx.forward_host()
-    g = ctx.grads_alloc()
-    ctx.backward(dC, g)
-    grads = ctx.grads_read(g, deg)
-    return rounds, img, tr, grads, ctx.work_counters_ex()
+    one_wave_per_tile(monkeypatch)
 
 
 # radix32 = (bin_path, rank_mode): the same frames on the 32-bit radix path (gs_bin2.hip), whose slab rounds drop the instances of
@@ -52,36 +38,36 @@ def test_forced_slabs_bit_identical_to_classic(oracle, fractions, rounds, radix3
     res = {}
     for det in (True, False):
         c0 = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=t_min, deterministic=det, slab_mode=0, **path)
-        r0 = _frame(c0, dC, deg); c0.close()
-        assert r0[0] == 1
+        r0 = run_frame(c0, dC, deg); c0.close()
+        assert r0["rounds"] == 1
         c1 = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=t_min, deterministic=det, slab_mode=1, slab_fractions=fractions, **path)
-        r1 = _frame(c1, dC, deg)
-        assert r1[0] == rounds, r1[0]
+        r1 = run_frame(c1, dC, deg)
+        assert r1["rounds"] == rounds, r1["rounds"]
         if radix32:                                                          # not by falling back: several rounds, on the radix path, two passes, several chunks
             assert c1.num_rounds > 1 and c1.bin_path_of_frame() == 2, (c1.num_rounds, c1.bin_path_of_frame())
             assert ((W + 15) // 16) * ((H + 15) // 16) > 256 and c1.num_instances > 4096, c1.num_instances
         with pytest.raises(Exception):
             c1.get_array(13)                                                # lists are spread over the rounds
         c1.close()
-        assert np.array_equal(r0[1], r1[1]) and np.array_equal(r0[2], r1[2])            # image, transmittance: bit-identical
-        assert r1[2].min() >= 0.0                                                          # no sign flag left behind
-        assert r0[4]["walked_fwd"] >= r1[4]["walked_fwd"] > 0 and r1[4]["walked_bwd"] == r1[4]["walked_fwd"]
-        assert r1[4]["evaluated_fwd"] == r0[4]["evaluated_fwd"] == r1[4]["evaluated_bwd"]
+        assert np.array_equal(r0["img"], r1["img"]) and np.array_equal(r0["tr"], r1["tr"])   # image, transmittance: bit-identical
+        assert r1["tr"].min() >= 0.0                                                       # no sign flag left behind
+        assert r0["wc"]["walked_fwd"] >= r1["wc"]["walked_fwd"] > 0 and r1["wc"]["walked_bwd"] == r1["wc"]["walked_fwd"]
+        assert r1["wc"]["evaluated_fwd"] == r0["wc"]["evaluated_fwd"] == r1["wc"]["evaluated_bwd"]
         for k in GRADS:
             if det:
-                assert np.array_equal(r0[3][k], r1[3][k]), k
+                assert np.array_equal(r0["grads"][k], r1["grads"][k]), k
             else:
-                assert rel_l2(r1[3][k].reshape(-1), r0[3][k].reshape(-1)) <= 1e-5, k
+                assert rel_l2(r1["grads"][k].reshape(-1), r0["grads"][k].reshape(-1)) <= 1e-5, k
         res[det] = r1
     if radix32:
         return                                                              # (the oracle bars below are this scene's on the small image: held by the cases above)
     ref = O.render(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"], deg, ocam, order=1, t_min=t_min)
     gref = O.backward(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"], deg, ocam, ref["ranges"], ref["ids"], dC, t_min=t_min)
-    img, tr = res[False][1], res[False][2]
+    img, tr = res[False]["img"], res[False]["tr"]
     assert np.all(np.abs(img - ref["image"]) <= 1e-4 + 1e-4 * np.abs(ref["image"]))
     assert np.all(np.abs(tr - ref["trans"]) <= 1e-4 + 1e-4 * np.abs(ref["trans"]))
     for k in GRADS:
-        assert rel_l2(res[False][3][k].reshape(-1), gref[k].reshape(-1)) <= 1e-3, k
+        assert rel_l2(res[False]["grads"][k].reshape(-1), gref[k].reshape(-1)) <= 1e-3, k
 
 
 def test_auto_slabs_after_a_dense_frame():
@@ -95,26 +81,26 @@ def test_auto_slabs_after_a_dense_frame():
     sc["scales"] = sc["scales"] + np.float32(1.5)                           # dense: under 10 % of the instances are walked
     dC = synthetic.make_dC(W, H, 3)
     ctx = hip_context(sc, cam, T, P, W, H, deg, t_min=1e-5, deterministic=True, slab_max_ratio=0.15)
-    frames = [_frame(ctx, dC, deg) for _ in range(4)]
-    share = frames[0][4]["walked_fwd"] / ctx.num_instances
+    frames = [run_frame(ctx, dC, deg) for _ in range(4)]
+    share = frames[0]["wc"]["walked_fwd"] / ctx.num_instances
     assert share < 0.15, share
-    assert frames[0][0] == 1 and frames[-1][0] == 3, [f[0] for f in frames]
+    assert frames[0]["rounds"] == 1 and frames[-1]["rounds"] == 3, [f["rounds"] for f in frames]
     for f in frames[1:]:
-        assert np.array_equal(f[1], frames[0][1]) and np.array_equal(f[2], frames[0][2])
+        assert np.array_equal(f["img"], frames[0]["img"]) and np.array_equal(f["tr"], frames[0]["tr"])
         for k in GRADS:
-            assert np.array_equal(f[3][k], frames[0][3][k]), k
-        assert f[4]["evaluated_fwd"] == frames[0][4]["evaluated_fwd"]
+            assert np.array_equal(f["grads"][k], frames[0]["grads"][k]), k
+        assert f["wc"]["evaluated_fwd"] == frames[0]["wc"]["evaluated_fwd"]
     ctx.close()
     ctx = hip_context(sc, cam, T, P, W, H, deg, t_min=1e-5, deterministic=True)
-    again = [_frame(ctx, dC, deg) for _ in range(3)]
-    assert [f[0] for f in again] == [1, 1, 1] and share > 0.03
-    assert np.array_equal(again[-1][1], frames[0][1])
+    again = [run_frame(ctx, dC, deg) for _ in range(3)]
+    assert [f["rounds"] for f in again] == [1, 1, 1] and share > 0.03
+    assert np.array_equal(again[-1]["img"], frames[0]["img"])
     ctx.close()
     n, W, H, deg = synthetic.CONFIGS["C3"]
     sc, cam, T, P, ocam = scene_and_cameras(n, W, H, deg, 1236)
     ctx = hip_context(sc, cam, T, P, W, H, deg, t_min=1e-5)
     dC = synthetic.make_dC(W, H, 3)
-    assert [_frame(ctx, dC, deg)[0] for _ in range(3)] == [1, 1, 1]
+    assert [run_frame(ctx, dC, deg)["rounds"] for _ in range(3)] == [1, 1, 1]
     ctx.close()
 
 
@@ -126,7 +112,7 @@ def test_sparse_scene_stays_classic():
     sc["scales"] = sc["scales"] - np.float32(1.5)
     dC = synthetic.make_dC(W, H, 5)
     ctx = hip_context(sc, cam, T, P, W, H, deg, t_min=1e-5)
-    rounds = [_frame(ctx, dC, deg)[0] for _ in range(4)]
+    rounds = [run_frame(ctx, dC, deg)["rounds"] for _ in range(4)]
     assert rounds == [1, 1, 1, 1], rounds
     ctx.close()
 
@@ -148,13 +134,13 @@ def test_slab_resume_with_negative_transmittance():
     res = []
     for kw in (dict(slab_mode=0), dict(slab_mode=1, slab_fractions=(0.07, 0.3)), dict(slab_mode=1, slab_fractions=(0.01, 0.02, 0.5))):
         ctx = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=1e-5, deterministic=True, **kw)
-        res.append(_frame(ctx, dC, deg))
+        res.append(run_frame(ctx, dC, deg))
         ctx.close()
-    assert res[0][0] == 1 and res[1][0] == 3 and res[2][0] == 4
+    assert res[0]["rounds"] == 1 and res[1]["rounds"] == 3 and res[2]["rounds"] == 4
     for r in res[1:]:
-        assert np.array_equal(r[1], res[0][1]) and np.array_equal(r[2], res[0][2], equal_nan=True)
+        assert np.array_equal(r["img"], res[0]["img"]) and np.array_equal(r["tr"], res[0]["tr"], equal_nan=True)
         for k in GRADS:
-            assert np.array_equal(r[3][k], res[0][3][k], equal_nan=True), k
+            assert np.array_equal(r["grads"][k], res[0]["grads"][k], equal_nan=True), k
 
 
 def test_forced_slabs_with_super_tiles_of_16(oracle):
@@ -166,12 +152,12 @@ def test_forced_slabs_with_super_tiles_of_16(oracle):
     sc["scales"] = sc["scales"] + np.float32(1.3)
     dC = synthetic.make_dC(W, H, 23)
     c0 = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=1e-4, deterministic=True, slab_mode=0)
-    r0 = _frame(c0, dC, deg); c0.close()
+    r0 = run_frame(c0, dC, deg); c0.close()
     for flags in (B.GS_DEBUG_SUPER16, 0):
         c1 = hip_context(sc, cam, T, P, W, H, deg, order=1, t_min=1e-4, deterministic=True, slab_mode=1, slab_fractions=(0.12, 0.4), debug_flags=flags)
-        r1 = _frame(c1, dC, deg); c1.close()
-        assert r1[0] == 3
-        assert np.array_equal(r0[1], r1[1]) and np.array_equal(r0[2], r1[2])
-        assert r1[4]["walked_bwd"] == r1[4]["walked_fwd"] and r1[4]["evaluated_fwd"] == r0[4]["evaluated_fwd"] == r1[4]["evaluated_bwd"]
+        r1 = run_frame(c1, dC, deg); c1.close()
+        assert r1["rounds"] == 3
+        assert np.array_equal(r0["img"], r1["img"]) and np.array_equal(r0["tr"], r1["tr"])
+        assert r1["wc"]["walked_bwd"] == r1["wc"]["walked_fwd"] and r1["wc"]["evaluated_fwd"] == r0["wc"]["evaluated_fwd"] == r1["wc"]["evaluated_bwd"]
         for k in GRADS:
-            assert np.array_equal(r0[3][k], r1[3][k]), k
+            assert np.array_equal(r0["grads"][k], r1["grads"][k]), k

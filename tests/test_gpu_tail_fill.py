@@ -5,10 +5,9 @@ float-atomic gradients within the bar test_gpu_schedule.py sets for two launches
 import numpy as np
 import pytest
 
-from common import hip_context, rel_l2, scene_and_cameras
+from common import bits, hip_context, rel_l2, same_bits, scene_and_cameras
 
 pytestmark = pytest.mark.gpu
-GRADS = ("means", "scales", "quats", "opacities", "shs")
 NO_TAIL_FILL = 32                      # GS_DEBUG_NO_TAIL_FILL
 ATOMIC_BAR = 1e-5                      # test_gpu_schedule.py: float-atomic gradients of two launches of the same frame
 # 2-D model: log-scales U[0, 1) as the reference draws them (splat.jl:74-87; footprints of a few pixels).  With U[0, 3) (footprints of a
@@ -17,14 +16,6 @@ ATOMIC_BAR = 1e-5                      # test_gpu_schedule.py: float-atomic grad
 # of sums of this size, as in test_gpu_schedule.py's scenes.  Measured, largest rel-L2 of four twin runs: 6.3e-6 at U[0, 3), 9.4e-7 at U[0, 2),
 # 1.5e-7 at U[0, 1); the 3-D cases of this file: at most 1.5e-6.
 SCALE_HI_2D = 1.0
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
 def assert_same(out, ref, det, what):
@@ -219,7 +210,7 @@ def test_poisoned_destination():
         ctx.close()
     for a, b in zip(*outs):
         assert not np.isnan(a).any() and not np.isnan(b).any()
-        assert np.array_equal(bits(a), bits(b))
+        assert same_bits(a, b)
         shs = a[11 * n:].reshape(n, K3)
         untouched = ~np.any(shs != 0.0, axis=1)
         assert untouched[:64].all() and 64 <= untouched.sum() < n

@@ -9,10 +9,11 @@ one wave per tile, one binning round, records by tile in tile order (variant 10)
 import numpy as np
 import pytest
 
+from common import halves
+
 pytestmark = pytest.mark.gpu
 N, W, H, DEG = 3000, 72, 40, 1
 GX, GY = 5, 3
-LO = np.uint64(0xFFFFFFFF)
 # log-scale shift of the dense frame.  Measured with the library of the commit before this test (d72859a): at 1.0 no pixel of this small
 # scene freezes and no tile packs, at 2.0 thirteen of the fifteen tiles pack, at 3.0 all do and every tile stops before the end of its list
 DENSE_GROW = 3.0
@@ -47,16 +48,12 @@ def dense():
     return _records(1e-5, grow=DENSE_GROW)
 
 
-def _halves(col):
-    return (col >> np.uint64(32)).astype(np.int64), (col & LO).astype(np.int64)
-
-
 def _hists(clk):
     """[tiles, 3, 4]: the evaluated entries by the slots K = 1 .. 4 of the three packings (words 8 .. 13)"""
     h = np.zeros((clk.shape[0], 3, 4), np.int64)
     for w in range(3):
-        h[:, w, 0], h[:, w, 1] = _halves(clk[:, 8 + 2 * w])
-        h[:, w, 2], h[:, w, 3] = _halves(clk[:, 9 + 2 * w])
+        h[:, w, 0], h[:, w, 1] = halves(clk[:, 8 + 2 * w])
+        h[:, w, 2], h[:, w, 3] = halves(clk[:, 9 + 2 * w])
     return h
 
 
@@ -69,15 +66,15 @@ def _tile_geometry():
 def test_forward_record_without_early_out_has_closed_forms(ragged):
     clk, listed = ragged["fwd"], ragged["listed"]
     w, h, P, A = _tile_geometry()
-    walked, ev = _halves(clk[:, 3])
+    walked, ev = halves(clk[:, 3])
     print("listed", listed, "ev", ev, "word14", clk[:, 14])
     assert listed.sum() > 0 and ev.sum() > 0
     assert np.array_equal(walked, listed)
     assert ev.sum() == ragged["wc"]["evaluated_fwd"]
     slots = (P + 63) // 64
-    ex, ideal = _halves(clk[:, 6])
+    ex, ideal = halves(clk[:, 6])
     assert np.array_equal(ex, 4 * ev) and np.array_equal(ideal, ev * slots)
-    alive, pix = _halves(clk[:, 7])
+    alive, pix = halves(clk[:, 7])
     assert np.array_equal(alive, ev * A) and np.array_equal(pix, ev * P)
     want = np.zeros((GX * GY, 3, 4), np.int64)
     t = np.arange(GX * GY)
@@ -92,19 +89,19 @@ def test_forward_record_without_early_out_has_closed_forms(ragged):
 
 def test_backward_record_without_early_out_matches_the_forward(ragged):
     f, b = ragged["fwd"], ragged["bwd"]
-    ev = _halves(f[:, 3])[1]
+    ev = halves(f[:, 3])[1]
     assert np.array_equal(b[:, 3], f[:, 3])
-    ex, ideal = _halves(b[:, 6])
+    ex, ideal = halves(b[:, 6])
     print("backward strip slots", ex, "of", 4 * ev)
-    assert (ex <= 4 * ev).all() and np.array_equal(ideal, _halves(f[:, 6])[1])
+    assert (ex <= 4 * ev).all() and np.array_equal(ideal, halves(f[:, 6])[1])
     assert np.array_equal(b[:, 7], f[:, 7])
 
 
 def test_forward_record_of_a_dense_frame_is_consistent_and_packs(dense):
     clk = dense["fwd"]
-    walked, ev = _halves(clk[:, 3])
-    ex, ideal = _halves(clk[:, 6])
-    alive, pix = _halves(clk[:, 7])
+    walked, ev = halves(clk[:, 3])
+    ex, ideal = halves(clk[:, 6])
+    alive, pix = halves(clk[:, 7])
     print("listed", dense["listed"], "walked", walked, "ev", ev, "exec", ex, "ideal", ideal, "alive", alive, "pix", pix)
     assert ev.sum() > 0 and (walked < dense["listed"]).any()                   # pixels froze before their lists ended
     assert np.array_equal(_hists(clk).sum(axis=2), np.repeat(ev[:, None], 3, axis=1))

@@ -1,52 +1,28 @@
-"""MCMC densification without a GPU: the statements of csrc/gs_mcmc.h in a host build (tests/mcmc_host.cpp, built by tests/mcmc.mk) against the
+"""MCMC densification without a GPU: the statements of csrc/gs_mcmc.h in a host build (tests/mcmc_host.cpp, built by tests/Makefile) against the
 NumPy restatement (tests/mcmc_ref.py) -- weights, draws, noise and regulariser gradients bit for bit, the relocation within one float32 ulp --,
 properties of the restatement itself, and the argument checks of gaussiansplat_amd.mcmc that need no device."""
 import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import mcmc_ref as M
+from common import host_program, run_host, same_bits
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 MIN_OPACITY = 0.005
 MIN_LOGIT = f32(math.log(MIN_OPACITY / (1.0 - MIN_OPACITY)))
 
 
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 @pytest.fixture(scope="module")
 def host_exe(tmp_path_factory):
-    from gaussiansplat_amd import build as gbuild
-    d = tmp_path_factory.mktemp("mcmc_host")
-    subprocess.run(["make", "-C", os.path.join(ROOT, "tests"), "-f", "mcmc.mk", "mcmc-host", f"OUT={d}", f"HIPCC={gbuild._hipcc()}"],
-                   check=True, capture_output=True, text=True)
-    return d, str(d / "mcmc_host")
+    return host_program("mcmc", tmp_path_factory.mktemp("mcmc_host"))
 
 
 def _run(host_exe, mode, n, head, arrays, outs):
     """head: packed scalars behind the int64 n; arrays: the inputs; outs: [(dtype, count)] of the outputs."""
-    dirn, exe = host_exe
-    fin, fout = str(dirn / "in.bin"), str(dirn / "out.bin")
-    with open(fin, "wb") as fh:
-        fh.write(np.int64(n).tobytes())
-        fh.write(head)
-        for a in arrays:
-            fh.write(np.ascontiguousarray(a).tobytes())
-    subprocess.run([exe, mode, fin, fout], check=True, timeout=120)
-    raw = open(fout, "rb").read()
-    res, at = [], 0
-    for dt, cnt in outs:
-        res.append(np.frombuffer(raw, dt, cnt, at).copy())
-        at += cnt * np.dtype(dt).itemsize
-    assert at == len(raw)
-    return res
+    return run_host(host_exe, [mode], np.int64(n).tobytes() + head, arrays, outs)
 
 
 def _edge_opacities():
@@ -63,7 +39,7 @@ def test_weights_equal_the_restatement_bit_for_bit(host_exe):
     o = _edge_opacities()
     (w,) = _run(host_exe, "weight", len(o), f32(MIN_LOGIT).tobytes(), [o], [(np.uint32, len(o))])
     ref = M.weights(o, MIN_LOGIT)
-    assert _same_bits(w, ref)
+    assert same_bits(w, ref)
     assert not w[:6][[0, 1, 2, 3, 5]].any() and w[4] > 0                     # NaN, +Inf (its sigmoid is NaN), -Inf, at and below the threshold: 0
     assert (w[8:12] == 2 ** 24).all() and w.max() == 2 ** 24                # a sigmoid that rounds to 1: the weight of one
     assert w[12] == 0                                                       # exp overflows: Inf / Inf
@@ -84,7 +60,7 @@ def test_draws_equal_searchsorted_bit_for_bit(host_exe):
     u = np.concatenate([edge, np.array(on, f32), u])
     (src,) = _run(host_exe, "draw", len(o), np.int64(len(u)).tobytes(), [cdf, u], [(np.int32, len(u))])
     ref = M.sample(cdf, u)
-    assert _same_bits(src, ref)
+    assert same_bits(src, ref)
     # every target of a small CDF whose total is a power of two: u = j / 2048 is exact, t = j -- every boundary is hit exactly, and then the
     # NEXT gaussian with a weight is taken
     ws = rng.integers(0, 4, 700).astype(np.uint64)
@@ -92,8 +68,8 @@ def test_draws_equal_searchsorted_bit_for_bit(host_exe):
     small = np.cumsum(ws, dtype=np.uint64)
     us = (np.arange(2048) / 2048.0).astype(f32)
     (ss,) = _run(host_exe, "draw", len(small), np.int64(len(us)).tobytes(), [small, us], [(np.int32, len(us))])
-    assert np.array_equal(M.targets(us, 2048), np.arange(2048, dtype=np.uint64)) and _same_bits(ss, M.sample(small, us))
-    assert _same_bits(ss, np.repeat(np.arange(700), ws.astype(np.int64)).astype(np.int32))     # gaussian i owns exactly w[i] targets
+    assert np.array_equal(M.targets(us, 2048), np.arange(2048, dtype=np.uint64)) and same_bits(ss, M.sample(small, us))
+    assert same_bits(ss, np.repeat(np.arange(700), ws.astype(np.int64)).astype(np.int32))      # gaussian i owns exactly w[i] targets
     w = M.weights(o, MIN_LOGIT)
     assert (w[ref] > 0).all() and ref.min() >= 0 and ref.max() < len(o)       # a dead gaussian is never drawn
     assert ref[0] == ref[3] == ref[4] == ref[5] == np.flatnonzero(w)[0]       # 0, -1, NaN, -0: the first gaussian with a weight
@@ -115,8 +91,8 @@ def test_noise_equals_the_restatement_bit_for_bit(host_exe):
     for lr, gk, gt in ((80.0, 100.0, 0.005), (1e-3, 100.0, 0.005), (5.0, 0.0, 0.5)):
         (out,) = _run(host_exe, "noise", n, np.array([lr, gk, gt], f32).tobytes(), [means, scales, quats, opac, z], [(f32, 3 * n)])
         ref = M.noise(means, scales, quats, opac, z, lr, gk, gt)
-        assert _same_bits(out.reshape(n, 3), ref)
-        assert _same_bits(ref[[5, 20, 21]], means[[5, 20, 21]]) and np.array_equal(ref[10:20], means[10:20])
+        assert same_bits(out.reshape(n, 3), ref)
+        assert same_bits(ref[[5, 20, 21]], means[[5, 20, 21]]) and np.array_equal(ref[10:20], means[10:20])
         assert (ref != means).any(axis=1).sum() > n // 2 or lr < 1e-2
 
 
@@ -132,7 +108,7 @@ def test_regulariser_gradients_equal_the_restatement_bit_for_bit(host_exe):
     out_o, out_s = _run(host_exe, "reg", n, np.array([c_o, c_s], f32).tobytes(), [opac, scales, d_op, d_sc], [(f32, n), (f32, 3 * n)])
     ref_o, ref_s = M.regularize(d_op, d_sc, opac, scales, c_o, c_s)
     nan = np.isnan(ref_o)
-    assert np.array_equal(nan, np.isnan(out_o)) and _same_bits(out_o[~nan], ref_o[~nan]) and _same_bits(out_s.reshape(n, 3), ref_s)
+    assert np.array_equal(nan, np.isnan(out_o)) and same_bits(out_o[~nan], ref_o[~nan]) and same_bits(out_s.reshape(n, 3), ref_s)
     assert (ref_o[~nan] >= d_op[~nan]).all() and (ref_s > d_sc).any()
 
 
@@ -166,8 +142,8 @@ def test_relocation_within_one_float_ulp_of_the_restatement(host_exe):
 
 
 def test_host_program_checks_itself_without_arguments(host_exe):
-    """what `make -C tests -f mcmc.mk sanitize-mcmc` runs under ASan + UBSan: the built-in scene"""
-    r = subprocess.run([host_exe[1]], capture_output=True, text=True, timeout=120)
+    """what `make -C tests sanitize-mcmc` runs under ASan + UBSan: the built-in scene"""
+    r = subprocess.run([host_exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "0 mismatches" in r.stdout, r.stdout + r.stderr
 
 
@@ -197,23 +173,23 @@ def test_relocate_leaves_everything_else_untouched_and_clamps():
     touched[[5, 6, 7, 8, 9, 10]] = True
     touched[dst[:-3]] = True
     for a, b in zip(model, new):                                             # c = 0 sources and everything else: every bit
-        assert _same_bits(a[~touched], b[~touched])
+        assert same_bits(a[~touched], b[~touched])
     for i in (0, 2, 4):                                                      # sources keep means, quaternions, SH rows
-        assert _same_bits(model[i][5:11], new[i][5:11])
-    assert _same_bits(new[0][dst[:-3]], model[0][src[:-3]]) and _same_bits(new[4][dst[:-3]], model[4][src[:-3]])
+        assert same_bits(model[i][5:11], new[i][5:11])
+    assert same_bits(new[0][dst[:-3]], model[0][src[:-3]]) and same_bits(new[4][dst[:-3]], model[4][src[:-3]])
     assert (new[3][5:11, 0] < model[3][5:11, 0]).all() and (new[1][5:11] < model[1][5:11]).all()
     assert new[3][7, 0] == f32(math.log(float(f32(MIN_OPACITY))) - math.log1p(-float(f32(MIN_OPACITY))))   # the clamp engages at min_opacity
-    assert _same_bits(new[3][dst[3:23], 0], np.full(20, new[3][7, 0], f32))
+    assert same_bits(new[3][dst[3:23], 0], np.full(20, new[3][7, 0], f32))
     # a draw count above 50 equals the count-50 result
     a = M.relocate_values(model[3][8:11, 0], model[1][8:11], [50, 50, 50], MIN_OPACITY)
     b = M.relocate_values(model[3][8:11, 0], model[1][8:11], [50, 51, 200], MIN_OPACITY)
-    assert _same_bits(a[0], b[0]) and _same_bits(a[1], b[1])
+    assert same_bits(a[0], b[0]) and same_bits(a[1], b[1])
     for s_old, s_new in zip(sets, new_sets):
         for x, y in zip(s_old, s_new):
             if x is None:
                 assert y is None
                 continue
-            assert not y[touched].any() and not np.signbit(y[touched]).any() and _same_bits(x[~touched], y[~touched])
+            assert not y[touched].any() and not np.signbit(y[touched]).any() and same_bits(x[~touched], y[~touched])
 
 
 # ---------------------------------------------------------------- gaussiansplat_amd.mcmc: argument checks (no GPU)

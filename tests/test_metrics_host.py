@@ -2,16 +2,13 @@
 build (tests/metrics_host.cpp), gs_metrics_finish through ctypes, and the argument checks of train.Evaluator."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import metrics_ref as MR
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from common import host_program, run_host
 
 
 def test_the_two_float64_restatements_agree_per_pixel():
@@ -121,27 +118,15 @@ def test_metrics_finish_refuses_null(backend):
 # ---------------------------------------------------------------- csrc/gs_metrics.h in a host build
 @pytest.fixture(scope="module")
 def host_exe(tmp_path_factory):
-    from gaussiansplat_amd import build as gbuild
-    d = tmp_path_factory.mktemp("metrics_host")
-    exe = str(d / "metrics_host")
-    subprocess.run([gbuild._hipcc(), "-O2", "-std=c++17", "-x", "hip", "--cuda-host-only", "-Wall", "-I", gbuild.CSRC,
-                    os.path.join(ROOT, "tests", "metrics_host.cpp"), "-o", exe], check=True, capture_output=True, text=True)
-    return d, exe
+    return host_program("metrics", tmp_path_factory.mktemp("metrics_host"))
 
 
 def _run_host(host_exe, img, gt, weight=None):
-    d, exe = host_exe
-    fin, fout = str(d / "in.bin"), str(d / "out.bin")
     Cn, H, W = img.shape
-    with open(fin, "wb") as fh:
-        fh.write(np.array([Cn, H, W, int(weight is not None)], np.int32).tobytes())
-        fh.write(np.ascontiguousarray(img, np.float32).tobytes()); fh.write(np.ascontiguousarray(gt, np.float32).tobytes())
-        if weight is not None:
-            fh.write(np.ascontiguousarray(weight, np.float32).tobytes())
-    subprocess.run([exe, fin, fout], check=True, timeout=60)
-    o = np.fromfile(fout, np.float64)
-    assert o.size == 8 + img.size
-    return o[:4], o[4:8], o[8:].reshape(img.shape)
+    arrays = [np.asarray(a, np.float32) for a in (img, gt) + ((weight,) if weight is not None else ())]
+    sums, fin, S = run_host(host_exe, [], np.array([Cn, H, W, int(weight is not None)], np.int32).tobytes(), arrays,
+                            [(np.float64, 4), (np.float64, 4), (np.float64, img.size)])
+    return sums, fin, S.reshape(img.shape)
 
 
 @pytest.mark.parametrize("name,shape", [("uniform", (3, 17, 65)), ("flat_noise", (2, 33, 129)), ("two_consts", (3, 2, 3))],

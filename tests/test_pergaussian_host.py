@@ -5,17 +5,13 @@ The statements that decide tile ids and depth keys are __host__ __device__ funct
 every operation is individually rounded on both sides.  So that nothing passes on empty work, the oracle's output alone must show that at
 least a quarter of the rectangles are non-empty and that every planted row is there and gives its kind of result."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from common import scene_and_cameras
-from gaussiansplat_amd import build as gbuild
+from common import bits, host_program, run_host, same_bits, scene_and_cameras
 from gaussiansplat_amd import synthetic
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N3, W3, H3, SEED3 = 4096, 400, 300, 31
 N2, W2, H2, SEED2 = 1024, 200, 150, 32
 NAN, INF = np.float32("nan"), np.float32("inf")
@@ -23,16 +19,6 @@ NAN, INF = np.float32("nan"), np.float32("inf")
 NAN_MEAN, INF_SCALE, SCALE_90, TZ_ZERO, SINGULAR, OFF_SCREEN, LEFT, RIGHT, TOP, BOTTOM = range(10)
 # ... and of the 2-D set (no depth, and + 0.3 I keeps its covariance regular)
 NAN_MEAN2, INF_SCALE2, SCALE_90_2, OFF_SCREEN2, LEFT2, RIGHT2, TOP2, BOTTOM2 = range(8)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32).reshape(-1)
-
-
-def same_bits(got, want):
-    g, w = bits(got), bits(want)
-    nan = np.isnan(g.view(np.float32)) & np.isnan(w.view(np.float32))
-    return bool(np.all((g == w) | nan))
 
 
 def oracle_rects(O, bbs, gx, gy):
@@ -102,30 +88,20 @@ def sets(oracle):
 @pytest.fixture(scope="module")
 def host(sets, tmp_path_factory):
     """What the host build of the header computes from the oracle's cov2d and mu and from the raw inputs"""
-    d = tmp_path_factory.mktemp("pergaussian_host")
-    exe, fin, fout = str(d / "pergaussian_host"), str(d / "in.bin"), str(d / "out.bin")
-    subprocess.run([gbuild._hipcc(), "-O2", "-std=c++17", "-x", "hip", "--cuda-host-only", "-ffp-contract=off", "-Wall", "-I", gbuild.CSRC,
-                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "pergaussian_host.cpp"), "-o", exe],
-                   check=True, capture_output=True, text=True)
+    exe = host_program("pergaussian", tmp_path_factory.mktemp("pergaussian_host"))
     s = sets
     nz, nx, na, nq, nf = len(s["z"]), len(s["x"]), len(s["ang"]), len(s["quats"]), len(s["words"])
     fixed = np.empty((nf, 3), np.uint32)
     fixed[:, 0] = (s["words"].view(np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
     fixed[:, 1] = (s["words"].view(np.uint64) >> np.uint64(32)).astype(np.uint32)
     fixed[:, 2] = s["comp"].view(np.uint32)
-    parts = [np.array([N3, W3, H3, N2, W2, H2, nz, nx, na, nq, nf], np.uint32), bits(s["pre3"]["cov2d"]), bits(s["pre3"]["mu"]),
-             bits(s["pre2"]["cov2d"]), bits(s["pre2"]["mu"]), bits(s["z"]), bits(s["x"]), bits(s["ang"]), bits(s["quats"]), fixed.reshape(-1)]
-    np.concatenate(parts).tofile(fin)
-    subprocess.run([exe, fin, fout], check=True, timeout=60)
-    w = np.fromfile(fout, np.uint32)
-    out, p = {}, 0
-    for key, cnt, shape in (("invcov3", 4 * N3, (N3, 4)), ("bbs3", 4 * N3, (N3, 4)), ("rect3", 4 * N3, (N3, 4)), ("invcov2", 4 * N2, (N2, 4)),
-                            ("bbs2", 4 * N2, (N2, 4)), ("rect2", 4 * N2, (N2, 4)), ("keys", 3 * nz, (3, nz)), ("exp", nx, (nx,)), ("sin", na, (na,)),
-                            ("cos", na, (na,)), ("R", 9 * nq, (nq, 3, 3)), ("fixed", nf, (nf,))):
-        out[key] = w[p:p + cnt].reshape(shape).view(np.uint32 if key == "keys" else np.int32 if key.startswith("rect") else np.float32)
-        p += cnt
-    assert p == len(w)
-    return out
+    arrays = [np.asarray(a, np.float32) for a in (s["pre3"]["cov2d"], s["pre3"]["mu"], s["pre2"]["cov2d"], s["pre2"]["mu"], s["z"], s["x"], s["ang"], s["quats"])]
+    layout = (("invcov3", (N3, 4)), ("bbs3", (N3, 4)), ("rect3", (N3, 4)), ("invcov2", (N2, 4)), ("bbs2", (N2, 4)), ("rect2", (N2, 4)), ("keys", (3, nz)),
+              ("exp", (nx,)), ("sin", (na,)), ("cos", (na,)), ("R", (nq, 3, 3)), ("fixed", (nf,)))
+    dtype = lambda key: np.uint32 if key == "keys" else np.int32 if key.startswith("rect") else np.float32
+    res = run_host(exe, [], np.array([N3, W3, H3, N2, W2, H2, nz, nx, na, nq, nf], np.uint32).tobytes(), arrays + [fixed],
+                   [(dtype(key), int(np.prod(shape))) for key, shape in layout])
+    return {key: a.reshape(shape) for (key, shape), a in zip(layout, res)}
 
 
 def test_the_oracle_output_is_real_work(sets):
@@ -149,8 +125,8 @@ def test_the_oracle_output_is_real_work(sets):
 def test_conic_box_and_tile_rectangle(sets, host):
     for tag in ("3", "2"):
         pre = sets["pre" + tag]
-        assert same_bits(host["invcov" + tag], pre["invcov"])
-        assert same_bits(host["bbs" + tag], pre["bbs"])
+        assert same_bits(host["invcov" + tag], pre["invcov"], nan_equal=True)
+        assert same_bits(host["bbs" + tag], pre["bbs"], nan_equal=True)
         assert np.array_equal(host["rect" + tag], pre["rect"])
 
 
@@ -163,9 +139,9 @@ def test_depth_keys(sets, host):
 
 def test_exp_and_sincos(sets, host):
     O = sets["O"]
-    assert same_bits(host["exp"], np.array([O.expf(float(v)) for v in sets["x"]], np.float32))
+    assert same_bits(host["exp"], np.array([O.expf(float(v)) for v in sets["x"]], np.float32), nan_equal=True)
     sc = np.array([O.sincosf(float(v)) for v in sets["ang"]], np.float32)
-    assert same_bits(host["sin"], sc[:, 0]) and same_bits(host["cos"], sc[:, 1])
+    assert same_bits(host["sin"], sc[:, 0], nan_equal=True) and same_bits(host["cos"], sc[:, 1], nan_equal=True)
 
 
 def test_quat_to_rot(sets, host):
@@ -181,9 +157,9 @@ def test_quat_to_rot(sets, host):
     R[:, 0, 2] = two * (x * z + w * y)
     R[:, 1, 2] = two * (y * z - w * x)
     R[:, 2, 2] = one - two * (x * x + y * y)
-    assert same_bits(host["R"], R)
+    assert same_bits(host["R"], R, nan_equal=True)
 
 
 def test_fixed_to_float(sets, host):
     inv = np.where(sets["comp"] >= 6, 2.0 ** -28, 2.0 ** -40)
-    assert same_bits(host["fixed"], (sets["words"].astype(np.float64) * inv).astype(np.float32))
+    assert same_bits(host["fixed"], (sets["words"].astype(np.float64) * inv).astype(np.float32), nan_equal=True)

@@ -7,19 +7,17 @@ the three smallest.  It also reports how many (query, box) pairs it pruned and o
 neither "opened everything" nor "pruned everything" passes.  Then ply.load_points, PointCloud's refusals and camera.scene_extent."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import knn_ref as K
+from common import bits, host_program, run_host, same_bits
 from gaussiansplat_amd import backend
 from gaussiansplat_amd import build as gbuild
 from gaussiansplat_amd import ply
 from gaussiansplat_amd.camera import default_camera, scene_extent
 from gaussiansplat_amd.pointcloud import PointCloud
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -34,21 +32,12 @@ def refs(clouds):
 
 @pytest.fixture(scope="module")
 def host(clouds, tmp_path_factory):
-    d = tmp_path_factory.mktemp("knn_host")
-    exe, fin, fout = str(d / "knn_host"), str(d / "in.bin"), str(d / "out.bin")
-    subprocess.run([gbuild._hipcc(), "-O2", "-std=c++17", "-x", "hip", "--cuda-host-only", "-ffp-contract=off", "-Wall", "-I", gbuild.CSRC,
-                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "knn_host.cpp"), "-o", exe],
-                   check=True, capture_output=True, text=True)
+    exe = host_program("knn", tmp_path_factory.mktemp("knn_host"))
     names = list(clouds)
-    with open(fin, "wb") as fh:
-        np.array([len(names)], np.uint32).tofile(fh)
-        for name in names:
-            np.array([len(clouds[name])], np.uint32).tofile(fh)
-            np.ascontiguousarray(clouds[name], np.float32).tofile(fh)
-    r = subprocess.run([exe, fin, fout], check=True, timeout=120, capture_output=True, text=True)
-    flat = np.fromfile(fout, np.float32)
+    arrays = [a for name in names for a in (np.uint32(len(clouds[name])), np.asarray(clouds[name], np.float32))]
+    (flat,), printed = run_host(exe, [], np.uint32(len(names)).tobytes(), arrays, [(np.float32, sum(len(clouds[name]) for name in names))], stdout=True)
     out, p = {}, 0
-    lines = r.stdout.strip().splitlines()
+    lines = printed.strip().splitlines()
     assert len(lines) == len(names)
     for k, name in enumerate(names):
         n = len(clouds[name])
@@ -76,7 +65,7 @@ def test_every_cloud_fits_the_cpu_pipeline_and_the_reference_shows_its_case(clou
 def test_cpu_pipeline_matches_brute_force_bit_for_bit(clouds, refs, host):
     for name in clouds:
         got, want = host[name]["dist2"], refs[name]
-        bad = np.flatnonzero(~((K.bits(got) == K.bits(want)) | (np.isnan(got) & np.isnan(want))))
+        bad = np.flatnonzero(~((bits(got) == bits(want)) | (np.isnan(got) & np.isnan(want))))
         assert bad.size == 0, (name, bad[:8], got[bad[:8]], want[bad[:8]])
 
 
@@ -119,12 +108,12 @@ def test_load_points_with_and_without_colours(tmp_path):
     write_points_ply(str(tmp_path / "c.ply"), pts, rgb)
     pc = ply.load_points(str(tmp_path / "c.ply"))
     assert isinstance(pc, PointCloud) and len(pc) == 37 and pc.sh_degree == 3 and pc.opacity == 0.1
-    assert K.same_bits(pc.points, pts)
-    assert pc.colors.dtype == np.float32 and K.same_bits(pc.colors, rgb.astype(np.float32) / np.float32(255.0))
+    assert same_bits(pc.points, pts, nan_equal=True)
+    assert pc.colors.dtype == np.float32 and same_bits(pc.colors, rgb.astype(np.float32) / np.float32(255.0), nan_equal=True)
     assert pc.colors[0].tolist() == [0.0, 0.0, 0.0] and pc.colors[1].tolist() == [1.0, 1.0, 1.0]
     write_points_ply(str(tmp_path / "p.ply"), pts, None, extra=False)
     pc = ply.load_points(str(tmp_path / "p.ply"), sh_degree=1, opacity=0.25)
-    assert pc.colors is None and K.same_bits(pc.points, pts) and pc.sh_degree == 1 and pc.opacity == 0.25
+    assert pc.colors is None and same_bits(pc.points, pts, nan_equal=True) and pc.sh_degree == 1 and pc.opacity == 0.25
 
 
 def test_pointcloud_refusals():

@@ -3,18 +3,13 @@
 Host code, compiled alone and run without a device: every launcher of an SH kernel goes through it, so what it refuses and which
 (degree, strided) pair it hands on is pinned here against the rule written out independently: degree 0..3, stride >= 3 K, a stride above
 3 K (an active degree below the stored one) only for degrees 0..2 -- there is no strided degree-3 kernel."""
-import os
 import subprocess
 
-from gaussiansplat_amd import build as gbuild
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from common import host_program
 
 
-def test_dispatch_validates_once_and_names_existing_instantiations_only(tmp_path):
-    exe = str(tmp_path / "sh_dispatch_host")
-    subprocess.run([gbuild._hipcc(), "-std=c++17", "-x", "hip", "--cuda-host-only", "-Wall", "-I", gbuild.CSRC, "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "sh_dispatch_host.cpp"), "-o", exe], check=True, capture_output=True, text=True)
+def test_dispatch_validates_once_and_names_existing_instantiations_only(tmp_path_factory):
+    exe = host_program("sh_dispatch", tmp_path_factory.mktemp("sh_dispatch_host"))
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split("\n")
     rows = [line.split() for line in out if line]
     assert len(rows) == 8 * 82
