@@ -17,19 +17,14 @@ while other views train.  Held-out views are measured without exposure (train.Ev
 """
 from __future__ import annotations
 
-import math
-
 import numpy as np
+
+from ._checks import betas_eps, integer, positive
+from .renderer import as_device_tensor
 
 
 def _check_lr(lr) -> float:
-    try:
-        v = float(lr)
-    except (TypeError, ValueError):
-        raise ValueError(f"Exposure: lr must be a number, got {lr!r}") from None
-    if not math.isfinite(v) or v < 0.0:
-        raise ValueError(f"Exposure: lr must be finite and >= 0, got {v}")
-    return v
+    return positive("Exposure: lr", lr, allow_zero=True)
 
 
 class Exposure:
@@ -40,17 +35,9 @@ class Exposure:
     once).  Argument errors are ValueErrors raised before any GPU call."""
 
     def __init__(self, renderer, n_views: int, weights=None, lr: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-15):
-        if isinstance(n_views, bool) or int(n_views) != n_views or n_views < 1:
-            raise ValueError(f"Exposure: n_views must be a positive integer, not {n_views!r}")
-        self.n_views = int(n_views)
+        self.n_views = integer("Exposure", "n_views", n_views, 1)
         self.lr = _check_lr(lr)
-        b1, b2 = (float(b) for b in betas)
-        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
-            raise ValueError(f"Exposure: betas must lie in [0, 1), got {tuple(betas)}")
-        eps = float(eps)
-        if not math.isfinite(eps) or eps <= 0.0:
-            raise ValueError(f"Exposure: eps must be finite and > 0, got {eps}")
-        self.betas, self.eps = (b1, b2), eps
+        self.betas, self.eps = betas_eps("Exposure", betas, eps)
         shape = tuple(int(s) for s in renderer.imageData.shape)
         if len(shape) != 3 or shape[0] != 3:
             raise ValueError(f"Exposure: the renderer's image must be [3, H, W], not {shape}")
@@ -92,12 +79,7 @@ class Exposure:
         return int(view)
 
     def _image(self, img, what: str):
-        import torch
-        dev = self.table.device
-        t = img if isinstance(img, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(img, np.float32))
-        if tuple(t.shape) != (3, self.H, self.W):
-            raise ValueError(f"Exposure.{what}: the image must be [3, {self.H}, {self.W}], not {tuple(t.shape)}")
-        return t.to(dev, torch.float32).contiguous()
+        return as_device_tensor(img, self.table.device, (3, self.H, self.W), f"Exposure.{what}: the image")
 
     def _wptr(self, v: int) -> int:
         w = self.weights[v]
@@ -116,10 +98,7 @@ class Exposure:
         x = self._image(img, "apply")
         if self._out is None:
             self._out = torch.empty((3, self.H, self.W), dtype=torch.float32, device=self.table.device)
-        r = self.renderer
-        r._begin()
-        r.ctx.exposure_apply(x.data_ptr(), self.table[v].data_ptr(), self._wptr(v), self.W, self.H, self._out.data_ptr())
-        r._end()
+        self.renderer._begin().exposure_apply(x.data_ptr(), self.table[v].data_ptr(), self._wptr(v), self.W, self.H, self._out.data_ptr())
         self._x, self._x_view = x, v
         return self._out
 
@@ -130,11 +109,8 @@ class Exposure:
         if self._x is None or self._x_view != v:
             raise ValueError(f"Exposure.backward: apply(view={v}, img) first")
         d = self._image(d_out, "backward")
-        r = self.renderer
-        r._begin()
-        r.ctx.exposure_backward(self._x.data_ptr(), d.data_ptr(), self.table[v].data_ptr(), self._wptr(v), self.W, self.H, d.data_ptr(),
-                                self._grad.data_ptr() if want_grad else 0)
-        r._end()
+        self.renderer._begin().exposure_backward(self._x.data_ptr(), d.data_ptr(), self.table[v].data_ptr(), self._wptr(v), self.W, self.H,
+                                                 d.data_ptr(), self._grad.data_ptr() if want_grad else 0)
         if want_grad:
             self._have_grad = v
         return d
@@ -145,11 +121,8 @@ class Exposure:
         if self._have_grad != v:
             raise ValueError(f"Exposure.step: backward(view={v}, ...) with want_grad first")
         t = self.step_counts[v] + 1
-        r = self.renderer
-        r._begin()
-        r.ctx.exposure_adam(self.table[v].data_ptr(), self._grad.data_ptr(), self.exp_avg[v].data_ptr(), self.exp_avg_sq[v].data_ptr(),
-                            self.lr, self.betas[0], self.betas[1], self.eps, t)
-        r._end()
+        self.renderer._begin().exposure_adam(self.table[v].data_ptr(), self._grad.data_ptr(), self.exp_avg[v].data_ptr(),
+                                             self.exp_avg_sq[v].data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps, t)
         self.step_counts[v] = t
         self._have_grad = -1
 
@@ -163,10 +136,7 @@ class Exposure:
         g = self._image(gt, "mask_target")
         if self._masked is None:
             self._masked = torch.empty((3, self.H, self.W), dtype=torch.float32, device=self.table.device)
-        r = self.renderer
-        r._begin()
-        r.ctx.exposure_apply(g.data_ptr(), self._identity.data_ptr(), self._wptr(v), self.W, self.H, self._masked.data_ptr())
-        r._end()
+        self.renderer._begin().exposure_apply(g.data_ptr(), self._identity.data_ptr(), self._wptr(v), self.W, self.H, self._masked.data_ptr())
         self._keep_gt = g
         return self._masked
 

@@ -396,10 +396,16 @@ class Context:
         """d rgb of the last backward, packed [n, 3] into a device buffer (colour-factored exchange)."""
         self._chk(self.L.gs_color_grads_pack(self.h, int(drgb_ptr)))
 
-    def sh_grads_from_views(self, cam_records: np.ndarray, drgb_ptr: int, d_shs_ptr: int, overwrite: bool = True):
-        """cam_records [nviews, 38] host float32 {T16, P16, eye3, lookAt3}; drgb [nviews, n, 3] device."""
+    @staticmethod
+    def _camera_records(cam_records) -> np.ndarray:
+        """[nviews, 38] host float32 {T16, P16, eye3, lookAt3} (distributed.view_records), contiguous."""
         cr = np.ascontiguousarray(cam_records, np.float32)
         assert cr.ndim == 2 and cr.shape[1] == 38
+        return cr
+
+    def sh_grads_from_views(self, cam_records: np.ndarray, drgb_ptr: int, d_shs_ptr: int, overwrite: bool = True):
+        """cam_records [nviews, 38] host float32 {T16, P16, eye3, lookAt3}; drgb [nviews, n, 3] device."""
+        cr = self._camera_records(cam_records)
         self._chk(self.L.gs_sh_grads_from_views(self.h, cr.shape[0], cr.ctypes.data, int(drgb_ptr), int(d_shs_ptr), 1 if overwrite else 0))
 
     def color_rows_pack(self, drgb_ptr: "int | None", n: int, bits_ptr: int, rows_ptr: int, count_ptr: int):
@@ -410,8 +416,7 @@ class Context:
     def sh_grads_from_touched(self, cam_records: np.ndarray, bits_ptr: int, rows_ptr: int, rows_cap: int, d_shs_ptr: int,
                               overwrite: bool = True):
         """cam_records as sh_grads_from_views; bits [nviews, ceil(n / 32)] int32 and rows [nviews, rows_cap, 3] float32, device."""
-        cr = np.ascontiguousarray(cam_records, np.float32)
-        assert cr.ndim == 2 and cr.shape[1] == 38
+        cr = self._camera_records(cam_records)
         self._chk(self.L.gs_sh_grads_from_touched(self.h, cr.shape[0], cr.ctypes.data, int(bits_ptr), int(rows_ptr), int(rows_cap), int(d_shs_ptr),
                                                   1 if overwrite else 0))
 
@@ -425,22 +430,19 @@ class Context:
         self._chk(self.L.gs_grads_alloc(self.h, C.byref(g)))
         return g
 
-    def grads_read(self, grads: GsGrads, sh_degree: int) -> dict:
-        n, k3 = self.num_gaussians, 3 * (sh_degree + 1) ** 2
-        out = dict(means=np.empty((n, 3), np.float32), scales=np.empty((n, 3), np.float32), quats=np.empty((n, 4), np.float32),
-                   opacities=np.empty((n,), np.float32), shs=np.empty((n, k3), np.float32))
-        self._chk(self.L.gs_grads_read(self.h, C.byref(grads), *(out[k].ctypes.data for k in
-                                                                   ("means", "scales", "quats", "opacities", "shs"))))
+    def _grads_read(self, grads: GsGrads, **rows) -> dict:
+        """gs_grads_read into five host arrays, named and shaped [n, *rows[name]] in the order of the gs_grads slots."""
+        n = self.num_gaussians
+        out = {k: np.empty((n,) + row, np.float32) for k, row in rows.items()}
+        self._chk(self.L.gs_grads_read(self.h, C.byref(grads), *(a.ctypes.data for a in out.values())))
         return out
+
+    def grads_read(self, grads: GsGrads, sh_degree: int) -> dict:
+        return self._grads_read(grads, means=(3,), scales=(3,), quats=(4,), opacities=(), shs=(3 * (sh_degree + 1) ** 2,))
 
     def grads_read_2d(self, grads: GsGrads) -> dict:
         """SplatGrads2D (splat.jl:28-34) from a gs_grads whose slots are read as (means, scales, rotations, opacities, colors)."""
-        n = self.num_gaussians
-        out = dict(means=np.empty((n, 2), np.float32), scales=np.empty((n, 2), np.float32), rots=np.empty((n,), np.float32),
-                   opacities=np.empty((n,), np.float32), colors=np.empty((n, 3), np.float32))
-        self._chk(self.L.gs_grads_read(self.h, C.byref(grads), *(out[k].ctypes.data for k in
-                                                                   ("means", "scales", "rots", "opacities", "colors"))))
-        return out
+        return self._grads_read(grads, means=(2,), scales=(2,), rots=(), opacities=(), colors=(3,))
 
     def loss_host(self, img: np.ndarray, gt: np.ndarray, lam: float = 0.1):
         """(loss, dC) for host images [C, H, W] (src/loss.jl:62-72 and its gradient)."""
@@ -475,21 +477,23 @@ class Context:
     def sgd_step(self, lr: float, grads: GsGrads):
         self._chk(self.L.gs_sgd_step(self.h, lr, C.byref(grads)))
 
+    @staticmethod
+    def _adam_args(exp_avg: GsGrads, exp_avg_sq: GsGrads, lr, beta1, beta2, eps, step, selective, flags) -> tuple:
+        """The arguments gs_adam_step and gs_backward_adam share, from the moments on."""
+        return (C.byref(exp_avg), C.byref(exp_avg_sq), (C.c_float * GS_ADAM_GROUPS)(*[float(x) for x in lr]), beta1, beta2, eps, int(step),
+                (GS_ADAM_SELECTIVE if selective else 0) if flags is None else int(flags))
+
     def adam_step(self, grads: GsGrads, exp_avg: GsGrads, exp_avg_sq: GsGrads, lr, beta1: float, beta2: float, eps: float, step: int,
                   selective: bool = False, flags: "int | None" = None):
         """gs_adam_step: Adam on the resident model from the gradients of `grads` (a NULL array freezes its group); exp_avg /
         exp_avg_sq: caller-owned moment arrays of the same layout; lr: GS_ADAM_GROUPS rates; step counts from 1."""
-        lr6 = (C.c_float * GS_ADAM_GROUPS)(*[float(x) for x in lr])
-        f = (GS_ADAM_SELECTIVE if selective else 0) if flags is None else int(flags)
-        self._chk(self.L.gs_adam_step(self.h, C.byref(grads), C.byref(exp_avg), C.byref(exp_avg_sq), lr6, beta1, beta2, eps, int(step), f))
+        self._chk(self.L.gs_adam_step(self.h, C.byref(grads), *self._adam_args(exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, selective, flags)))
 
     def backward_adam(self, dC_ptr: int, exp_avg: GsGrads, exp_avg_sq: GsGrads, lr, beta1: float, beta2: float, eps: float, step: int,
                       selective: bool = False, flags: "int | None" = None):
         """gs_backward_adam: backward and gs_adam_step in one pass on the resident model (3-D renderer); dC on the device."""
-        lr6 = (C.c_float * GS_ADAM_GROUPS)(*[float(x) for x in lr])
-        f = (GS_ADAM_SELECTIVE if selective else 0) if flags is None else int(flags)
-        self._chk(self.L.gs_backward_adam(self.h, int(dC_ptr), GS_MEM_DEVICE, C.byref(exp_avg), C.byref(exp_avg_sq), lr6,
-                                          beta1, beta2, eps, int(step), f))
+        self._chk(self.L.gs_backward_adam(self.h, int(dC_ptr), GS_MEM_DEVICE,
+                                          *self._adam_args(exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, selective, flags)))
 
     # -- density control (3-D renderer): statistics, clone / split / prune, opacity reset
     def density_accumulate(self, stats: GsDensityStats):

@@ -23,29 +23,9 @@ import math
 
 from . import backend as B
 from . import renderer as R
+from ._checks import integer, logit, positive, probability  # noqa: F401  (logit: imported from here by callers)
 
 LOG_SHRINK_3DGS = math.log(1.6)         # the children of a split are 1.6 times smaller
-
-
-def _positive(name: str, v, allow_zero: bool = False) -> float:
-    try:
-        f = float(v)
-    except (TypeError, ValueError):
-        raise ValueError(f"density: {name} must be a number, got {v!r}") from None
-    if not math.isfinite(f) or f < 0.0 or (f == 0.0 and not allow_zero):
-        raise ValueError(f"density: {name} must be finite and {'>= 0' if allow_zero else '> 0'}, got {f}")
-    return f
-
-
-def _probability(name: str, v) -> float:
-    f = _positive(name, v)
-    if not f < 1.0:
-        raise ValueError(f"density: {name} must lie in (0, 1), got {f}")
-    return f
-
-
-def logit(p: float) -> float:
-    return math.log(p / (1.0 - p))
 
 
 def density_params(*, scene_extent, grad_threshold=2e-4, percent_dense=0.01, min_opacity=0.005, max_world_fraction=0.1,
@@ -53,14 +33,14 @@ def density_params(*, scene_extent, grad_threshold=2e-4, percent_dense=0.01, min
     """The thresholds of gs_density_decide from the 3DGS hyper-parameters: a densified gaussian is split when its largest scale exceeds
     percent_dense * scene_extent (else cloned); a gaussian is pruned below min_opacity, above max_extent_px pixels (0: off) or when
     the scale it would keep exceeds max_world_fraction * scene_extent (None: off).  grad_threshold = inf turns densification off."""
-    extent = _positive("scene_extent", scene_extent)
+    extent = positive("density: scene_extent", scene_extent)
     gt = float(grad_threshold)
     if math.isnan(gt) or gt < 0.0:
         raise ValueError(f"density: grad_threshold must be >= 0 (inf: no densification), got {gt}")
-    pd = _positive("percent_dense", percent_dense)
-    mo = _probability("min_opacity", min_opacity)
+    pd = positive("density: percent_dense", percent_dense)
+    mo = probability("density: min_opacity", min_opacity)
     if max_world_fraction is not None:
-        mw = _positive("max_world_fraction", max_world_fraction)
+        mw = positive("density: max_world_fraction", max_world_fraction)
     px = int(max_extent_px)
     if px < 0:
         raise ValueError(f"density: max_extent_px must be >= 0 (0: off), got {px}")
@@ -72,18 +52,13 @@ def density_params(*, scene_extent, grad_threshold=2e-4, percent_dense=0.01, min
                              max_extent_px=px)
 
 
-def _require_3d(renderer, who: str):
-    if not isinstance(renderer, R.GaussianRenderer3D):
-        raise ValueError(f"{who}: needs the 3-D renderer")
-
-
 class DensityStats:
     """Three device tensors of one element per gaussian -- grad_sum (float32: sum over the accumulated views of |d L / d mu'| in NDC
     units), count (int32: views in which the gaussian was visible), max_extent (int32: its largest pixel extent) -- and the two calls
     that maintain them.  accumulate() belongs between backward and the optimiser step: the step drops the frame."""
 
     def __init__(self, renderer):
-        _require_3d(renderer, "DensityStats")
+        R.require_3d(renderer, "DensityStats")
         self.renderer = renderer
         self.resize(renderer.nGaussians)
 
@@ -104,9 +79,7 @@ class DensityStats:
         r = self.renderer
         if self.grad_sum.numel() != r.nGaussians:
             raise ValueError("DensityStats.accumulate: the renderer's number of gaussians changed; resize() first")
-        r._begin()
-        r.ctx.density_accumulate(self.struct())
-        r._end()
+        r._begin().density_accumulate(self.struct())
 
 
 def densify_and_prune(renderer, stats: DensityStats, optimizer=None, *, scene_extent, grad_threshold=2e-4, percent_dense=0.01,
@@ -118,7 +91,7 @@ def densify_and_prune(renderer, stats: DensityStats, optimizer=None, *, scene_ex
     zeroed.  If the new size would exceed max_gaussians the decision is made again without densification (pruning only).
     generator: the torch.Generator the normals of the split are drawn from (n x 2 x 3 of them, whatever is split)."""
     import torch
-    _require_3d(renderer, "densify_and_prune")
+    R.require_3d(renderer, "densify_and_prune")
     renderer.check_resize(optimizer, "densify_and_prune")
     if max_gaussians is not None and int(max_gaussians) < 1:
         raise ValueError(f"density: max_gaussians must be >= 1 or None, got {max_gaussians}")
@@ -129,8 +102,7 @@ def densify_and_prune(renderer, stats: DensityStats, optimizer=None, *, scene_ex
     if stats.grad_sum.numel() != n:
         raise ValueError("densify_and_prune: stats do not match the renderer's number of gaussians")
     dev = renderer.splatData.means.device
-    ctx = renderer.ctx
-    renderer._begin()
+    ctx = renderer._begin()
     action = torch.empty(n, dtype=torch.int32, device=dev)
     st = stats.struct()
     ctx.density_decide(st, params, action.data_ptr())
@@ -140,8 +112,7 @@ def densify_and_prune(renderer, stats: DensityStats, optimizer=None, *, scene_ex
         ctx.density_decide(st, density_params(grad_threshold=math.inf, **kw), action.data_ptr())
         survivors, clones, splits, pruned = ctx.density_plan(action.data_ptr())
         n_out = survivors + clones + 2 * splits
-    gdev = generator.device if generator is not None else dev
-    noise = torch.randn((n, 2, 3), generator=generator, device=gdev, dtype=torch.float32).to(dev).contiguous()
+    noise = R.draw(torch.randn, (n, 2, 3), generator, dev)
     new = renderer.alloc_model(n_out, zero=False)                # every row is written by the restructure
     src_sets, dst_sets, moments = [], [], ()
     if optimizer is not None:                                   # the flat layout depends on n: the moments move into new flat buffers
@@ -149,7 +120,6 @@ def densify_and_prune(renderer, stats: DensityStats, optimizer=None, *, scene_ex
         src_sets = optimizer.moment_structs()
     ctx.density_restructure(action.data_ptr(), noise.data_ptr(), B.GsGrads(*(t.data_ptr() for t in R.model_arrays(new))), src_sets, dst_sets, n_out)
     renderer.adopt_model(new, "densify_and_prune")
-    renderer._end()
     if optimizer is not None:
         optimizer._rebind(*moments)
     stats.resize(n_out)
@@ -158,16 +128,14 @@ def densify_and_prune(renderer, stats: DensityStats, optimizer=None, *, scene_ex
 
 def reset_opacity(renderer, optimizer=None, opacity: float = 0.01):
     """opacity = min(opacity, logit(`opacity`)) on the resident model; the opacities' Adam moments of `optimizer` become zero."""
-    _require_3d(renderer, "reset_opacity")
-    p = _probability("opacity", opacity)
+    R.require_3d(renderer, "reset_opacity")
+    p = probability("density: opacity", opacity)
     m = v = 0
     if optimizer is not None:
         if optimizer.renderer is not renderer:
             raise ValueError("reset_opacity: the optimiser belongs to another renderer")
         m, v = optimizer.moment_ptrs("opacities")
-    renderer._begin()
-    renderer.ctx.opacity_reset(logit(p), m, v)
-    renderer._end()
+    renderer._begin().opacity_reset(logit(p), m, v)
 
 
 class DensityController:
@@ -183,8 +151,7 @@ class DensityController:
                  max_extent_px: int = 0, max_gaussians=None, generator=None):
         for name, v, lo in (("from_iter", from_iter, 0), ("until_iter", until_iter, 0), ("interval", interval, 1),
                             ("opacity_reset_interval", opacity_reset_interval, 0)):
-            if isinstance(v, bool) or not isinstance(v, int) or v < lo:
-                raise ValueError(f"DensityController: {name} must be an integer >= {lo}, got {v!r}")
+            integer("DensityController", name, v, lo, strict=True)
         if until_iter < from_iter:
             raise ValueError(f"DensityController: until_iter ({until_iter}) lies before from_iter ({from_iter})")
         if max_gaussians is not None and (isinstance(max_gaussians, bool) or not isinstance(max_gaussians, int) or max_gaussians < 1):
@@ -192,7 +159,7 @@ class DensityController:
         self.kw = dict(scene_extent=scene_extent, grad_threshold=grad_threshold, percent_dense=percent_dense, min_opacity=min_opacity,
                        max_world_fraction=max_world_fraction, max_extent_px=max_extent_px)
         density_params(**self.kw)                               # validates the thresholds
-        self.reset_opacity_to = _probability("reset_opacity_to", reset_opacity_to)
+        self.reset_opacity_to = probability("density: reset_opacity_to", reset_opacity_to)
         self.from_iter, self.until_iter, self.interval, self.opacity_reset_interval = from_iter, until_iter, interval, opacity_reset_interval
         self.max_gaussians, self.generator = max_gaussians, generator
         self.iteration = 0                                      # completed iterations

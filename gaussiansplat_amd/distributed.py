@@ -261,12 +261,11 @@ class HipViewRenderer:
         from . import renderer as R
         R.resetGrads(self.r)
 
-    def render_view(self, camera, dC) -> None:
+    def render_view(self, camera, dC, **backward_kw) -> None:
+        """The frame under `camera` and its backward on the rank's own renderer; the other render_view_* add what differs behind it."""
         from . import renderer as R
-        tps = R.preprocess(self.r, camera)
-        R.compactIdxs(self.r)
-        R.forward(self.r, tps)
-        R.backward(self.r, dC)
+        R.renderFrame(self.r, camera)
+        R.backward(self.r, dC, **backward_kw)
         self.last_ctx = self.r.ctx
 
     # ---- several views of one rank on `pipeline_depth` streams (multi_view_step(pipeline=True))
@@ -294,41 +293,33 @@ class HipViewRenderer:
         nothing there touches what the other twin uses -- then the per-gaussian chain, which accumulates into the shared
         gradient buffer and therefore waits (event) for the chain of the view before it.  The first view overwrites (the lazy
         reset), the others accumulate, in view order: the same sums, bit for bit, as render_view in a loop."""
-        import numpy as np
         import torch
         from . import renderer as R
         r = self.r
         dev = r.imageData.device
-        dCs = [(d if isinstance(d, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(d, np.float32))).to(dev, torch.float32).contiguous()
-               for d in dCs]                                                # (uploads, if any, on the caller's stream: before `start`)
-        for d in dCs:                                                       # the checks R.backward makes, before anything is enqueued
-            if tuple(d.shape) != tuple(r.imageData.shape):
-                raise ValueError(f"dC has shape {tuple(d.shape)}, the image is {tuple(r.imageData.shape)}")
+        # uploads, if any, on the caller's stream: before `start`; the checks R.backward makes, before anything is enqueued
+        dCs = [R.as_device_tensor(d, dev, r.imageData.shape, "dC") for d in dCs]
         cur = torch.cuda.current_stream(dev)
         start = torch.cuda.Event(); start.record(cur)
         overwrite = r._grads_lazy_zero
         prev_chain = None
-        active = r.active_sh_degree                                        # the twins are ctxs of their own: they follow the rank's renderer
-        for t, _ in self._twins():
-            if t is not r and getattr(t, "_active_sh_sent", None) != active:
-                t.active_sh_degree = t._active_sh_sent = active
-        bg = r.background                                                  # ... and its background
-        for t, _ in self._twins():
-            if t is not r and getattr(t, "_background_sent", None) != bg:
-                t.background = t._background_sent = bg
+        # the twins are ctxs of their own: they follow the rank's renderer in its active SH degree and its background
+        follow = dict(active_sh_degree=r.active_sh_degree, background=r.background)
+        for t in (t for t, _ in self._twins() if t is not r):
+            for name, value in follow.items():
+                if getattr(t, "_sent_" + name, None) != value:
+                    setattr(t, name, value); setattr(t, "_sent_" + name, value)
         for i, (cam, dC) in enumerate(zip(cameras, dCs)):
             t, st = self._twins()[i % self.pipeline_depth]
             with torch.cuda.stream(st):
                 if i < self.pipeline_depth:
                     st.wait_event(start)                                   # inputs and the previous step's readers of the gradient buffer
-                tps = R.preprocess(t, cam)
-                R.compactIdxs(t)
-                R.forward(t, tps)
+                R.renderFrame(t, cam)
                 t._dC_keepalive = dC
-                t.ctx.backward(dC.data_ptr(), t._grads, overwrite=False, phase="composite")
+                t._begin().backward(dC.data_ptr(), t._grads, overwrite=False, phase="composite")
                 if prev_chain is not None:
                     st.wait_event(prev_chain)
-                t.ctx.backward(dC.data_ptr(), t._grads, overwrite=overwrite, phase="params")
+                t._begin().backward(dC.data_ptr(), t._grads, overwrite=overwrite, phase="params")
                 prev_chain = torch.cuda.Event(); prev_chain.record(st)
             overwrite = False
             self.last_ctx = t.ctx
@@ -338,14 +329,10 @@ class HipViewRenderer:
     # ---- the last view of a rank in two steps (multi_view_step(overlap=True))
     def render_view_until_sh(self, camera, dC) -> None:
         from . import renderer as R
-        tps = R.preprocess(self.r, camera)
-        R.compactIdxs(self.r)
-        R.forward(self.r, tps)
         self._dC = dC
-        R.backward(self.r, dC, phase="composite")
+        self.render_view(camera, dC, phase="composite")
         R.backward(self.r, dC, phase="params_sh")
         self._mid_split = True
-        self.last_ctx = self.r.ctx
 
     def finish_geometry(self) -> None:
         from . import renderer as R
@@ -355,7 +342,9 @@ class HipViewRenderer:
     # ---- colour-factored exchange
     @property
     def geometry_floats(self) -> int:
-        return 11 * self.r.nGaussians
+        """Floats of the flat buffer in front of Δshs: the offset of the last array of the layout."""
+        from . import renderer as R
+        return R.layout_of(self.r._splatGrads)[0][4]
 
     def color_slots(self, nviews: int):
         import torch
@@ -366,12 +355,8 @@ class HipViewRenderer:
         return self._slots
 
     def render_view_factored(self, camera, dC, slot) -> None:
-        from . import renderer as R
-        tps = R.preprocess(self.r, camera)
-        R.compactIdxs(self.r)
-        R.forward(self.r, tps)
-        R.backward(self.r, dC, skip_shs=True)
-        self.r.ctx.color_grads_pack(slot.data_ptr())
+        self.render_view(camera, dC, skip_shs=True)
+        self.r._begin().color_grads_pack(slot.data_ptr())
 
     # ---- touched-rows exchange on the device
     def touched_buffers(self, nviews: int):
@@ -389,30 +374,23 @@ class HipViewRenderer:
 
     def render_view_touched(self, camera, dC, i: int) -> None:
         """render_view_factored without the dense slot: view i of touched_buffers is packed straight from the ctx's sums"""
-        from . import renderer as R
         bits, rows, counts = self._touched
-        tps = R.preprocess(self.r, camera)
-        R.compactIdxs(self.r)
-        R.forward(self.r, tps)
-        R.backward(self.r, dC, skip_shs=True)
-        self.r.ctx.color_rows_pack(None, self.r.nGaussians, bits[i].data_ptr(), rows[i].data_ptr(), counts[i].data_ptr())
+        self.render_view(camera, dC, skip_shs=True)
+        self.r._begin().color_rows_pack(None, self.r.nGaussians, bits[i].data_ptr(), rows[i].data_ptr(), counts[i].data_ptr())
         self.device_touched_packs = getattr(self, "device_touched_packs", 0) + 1     # introspection: the device path was taken
-        self.last_ctx = self.r.ctx
 
     def sh_from_touched(self, cameras, bits_all, rows_all, rows_cap: int) -> None:
         R_ = self.r
         H, W = R_.transmittance.shape
         assert bits_all.is_contiguous() and rows_all.is_contiguous() and rows_all.shape[1] == rows_cap
-        R_._begin()
-        R_.ctx.sh_grads_from_touched(view_records(cameras, W, H), bits_all.data_ptr(), rows_all.data_ptr(), rows_cap,
-                                     R_.splatGrads.Δshs.data_ptr(), overwrite=True)
+        R_._begin().sh_grads_from_touched(view_records(cameras, W, H), bits_all.data_ptr(), rows_all.data_ptr(), rows_cap,
+                                          R_.splatGrads.Δshs.data_ptr(), overwrite=True)
         self.device_touched_rebuilds = getattr(self, "device_touched_rebuilds", 0) + 1
 
     def sh_from_views(self, cameras, drgb_all) -> None:
         R_ = self.r
         H, W = R_.transmittance.shape
-        R_._begin()
-        R_.ctx.sh_grads_from_views(view_records(cameras, W, H), drgb_all.contiguous().data_ptr(), R_.splatGrads.Δshs.data_ptr(), overwrite=True)
+        R_._begin().sh_grads_from_views(view_records(cameras, W, H), drgb_all.contiguous().data_ptr(), R_.splatGrads.Δshs.data_ptr(), overwrite=True)
 
 
 def factored_one_view_step(hv: "HipViewRenderer", camera, dC, cam_records, gathered, group=None) -> None:
@@ -427,12 +405,10 @@ def factored_one_view_step(hv: "HipViewRenderer", camera, dC, cam_records, gathe
     from . import renderer as R
     r = hv.r
     world = dist.get_world_size(group) if dist.is_initialized() else 1
-    tps = R.preprocess(r, camera)
-    R.compactIdxs(r)
-    R.forward(r, tps)
+    R.renderFrame(r, camera)
     R.backward(r, dC, phase="composite")
     slot = hv.color_slots(1)
-    r.ctx.color_grads_pack(slot.data_ptr())
+    r._begin().color_grads_pack(slot.data_ptr())
     work = dist.all_gather_into_tensor(gathered, slot.reshape(-1), group=group, async_op=True) if world > 1 else None
     R.backward(r, dC, skip_shs=True, phase="params")
     flat = r.splatGrads.flat
@@ -442,7 +418,7 @@ def factored_one_view_step(hv: "HipViewRenderer", camera, dC, cam_records, gathe
         src = gathered
     else:
         src = slot
-    r.ctx.sh_grads_from_views(cam_records, src.data_ptr(), r.splatGrads.Δshs.data_ptr(), overwrite=True)
+    r._begin().sh_grads_from_views(cam_records, src.data_ptr(), r.splatGrads.Δshs.data_ptr(), overwrite=True)
 
 
 def view_records(cameras, W: int, H: int):

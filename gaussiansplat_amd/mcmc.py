@@ -22,29 +22,26 @@ from __future__ import annotations
 import math
 
 from . import renderer as R
-from .density import _positive, _probability, _require_3d, logit
+from ._checks import integer, logit, positive, probability
 
 
 def _plan(renderer, min_opacity: float):
-    """gs_mcmc_plan on the renderer's model: (cdf, dead, (alive, dead count, total)); the renderer's stream is bound."""
+    """gs_mcmc_plan on the renderer's model: (cdf, dead, (alive, dead count, total))."""
     import torch
     n = renderer.nGaussians
     dev = renderer.splatData.means.device
     cdf = torch.empty(max(n, 1), dtype=torch.int64, device=dev)          # uint64 words: torch has no unsigned 64-bit arithmetic, nor is any done here
     dead = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    renderer._begin()
-    counts = renderer.ctx.mcmc_plan(logit(min_opacity), cdf.data_ptr(), dead.data_ptr())
+    counts = renderer._begin().mcmc_plan(logit(min_opacity), cdf.data_ptr(), dead.data_ptr())
     return cdf, dead, counts
 
 
 def _draw(renderer, cdf, m: int, generator):
     """m sources from the plan's CDF by m uniform numbers of `generator`: an int32 device tensor."""
     import torch
-    dev = cdf.device
-    gdev = generator.device if generator is not None else dev
-    u = torch.rand(m, generator=generator, device=gdev, dtype=torch.float32).to(dev).contiguous()
-    src = torch.empty(m, dtype=torch.int32, device=dev)
-    renderer.ctx.mcmc_sample(cdf.data_ptr(), renderer.nGaussians, u.data_ptr(), m, src.data_ptr())
+    u = R.draw(torch.rand, m, generator, cdf.device)
+    src = torch.empty(m, dtype=torch.int32, device=cdf.device)
+    renderer._begin().mcmc_sample(cdf.data_ptr(), renderer.nGaussians, u.data_ptr(), m, src.data_ptr())
     return src
 
 
@@ -61,15 +58,14 @@ def relocate(renderer, optimizer=None, *, min_opacity=0.005, generator=None) -> 
     source and copies get the opacity and scales that leave the rendered result unchanged, their rows of `optimizer`'s moments become
     zero.  Returns dict(alive, dead, relocated, src): relocated is 0 when nothing is dead or nothing is alive; src is the int32 device
     tensor of the draws (None when nothing was relocated)."""
-    _require_3d(renderer, "relocate")
-    mo = _probability("min_opacity", min_opacity)
+    R.require_3d(renderer, "relocate")
+    mo = probability("density: min_opacity", min_opacity)
     sets = _moment_sets(renderer, optimizer, "relocate")
     cdf, dead_list, (alive, dead, total) = _plan(renderer, mo)   # dead_list: what the ctx's plan points at; it lives until the relocation is enqueued
     if dead == 0 or total == 0:
         return dict(alive=alive, dead=dead, relocated=0, src=None)
     src = _draw(renderer, cdf, dead, generator)
-    renderer.ctx.mcmc_relocate(src.data_ptr(), None, dead, mo, sets)
-    renderer._end()
+    renderer._begin().mcmc_relocate(src.data_ptr(), None, dead, mo, sets)
     return dict(alive=alive, dead=dead, relocated=dead, src=src)
 
 
@@ -79,12 +75,11 @@ def grow(renderer, optimizer=None, *, cap_max, growth=1.05, min_opacity=0.005, g
     (optim.Adam) gets moment buffers of the new size -- old rows carried over, rows of sources and new gaussians zero, step_count kept.
     Returns dict(n, added, src)."""
     import torch
-    _require_3d(renderer, "grow")
+    R.require_3d(renderer, "grow")
     renderer.check_resize(optimizer, "grow")
-    if isinstance(cap_max, bool) or not isinstance(cap_max, int) or cap_max < 1:
-        raise ValueError(f"mcmc: cap_max must be an integer >= 1, got {cap_max!r}")
-    g = _positive("growth", growth)
-    mo = _probability("min_opacity", min_opacity)
+    integer("mcmc", "cap_max", cap_max, 1, strict=True)
+    g = positive("density: growth", growth)
+    mo = probability("density: min_opacity", min_opacity)
     n = renderer.nGaussians
     added = max(0, min(cap_max, int(g * n)) - n)
     if added == 0:
@@ -102,8 +97,7 @@ def grow(renderer, optimizer=None, *, cap_max, growth=1.05, min_opacity=0.005, g
         *moments, sets = optimizer.resized_moments(n_out, zero=True, keep_rows=n)
     renderer.adopt_model(new, "grow")
     dst = torch.arange(n, n_out, dtype=torch.int32, device=new.means.device)
-    renderer.ctx.mcmc_relocate(src.data_ptr(), dst.data_ptr(), added, mo, sets)
-    renderer._end()
+    renderer._begin().mcmc_relocate(src.data_ptr(), dst.data_ptr(), added, mo, sets)
     if optimizer is not None:
         optimizer._rebind(*moments)
     return dict(n=n_out, added=added, src=src)
@@ -113,33 +107,27 @@ def inject_noise(renderer, lr, *, gate_k=100.0, gate_t=0.005, generator=None):
     """means += lr * gate * Sigma z with z standard normals of `generator`, Sigma the covariance the renderer draws and
     gate = 1 / (1 + exp(gate_k * (sigmoid(opacity) - gate_t))): opaque gaussians stay, transparent ones explore.  lr == 0: nothing."""
     import torch
-    _require_3d(renderer, "inject_noise")
-    rate = _positive("lr", lr, allow_zero=True)
+    R.require_3d(renderer, "inject_noise")
+    rate = positive("density: lr", lr, allow_zero=True)
     for name, v in (("gate_k", gate_k), ("gate_t", gate_t)):
         if not math.isfinite(float(v)):
             raise ValueError(f"mcmc: {name} must be finite, got {v!r}")
     if rate == 0.0 or renderer.nGaussians == 0:
         return
-    dev = renderer.splatData.means.device
-    gdev = generator.device if generator is not None else dev
-    z = torch.randn((renderer.nGaussians, 3), generator=generator, device=gdev, dtype=torch.float32).to(dev).contiguous()
-    renderer._begin()
-    renderer.ctx.mcmc_noise(z.data_ptr(), rate, float(gate_k), float(gate_t))
-    renderer._end()
+    z = R.draw(torch.randn, (renderer.nGaussians, 3), generator, renderer.splatData.means.device)
+    renderer._begin().mcmc_noise(z.data_ptr(), rate, float(gate_k), float(gate_t))
 
 
 def regularize(renderer, *, opacity_reg=0.01, scale_reg=0.01):
     """Adds the gradients of opacity_reg * mean(sigmoid(opacity)) + scale_reg * mean(exp(scale)) to renderer.splatGrads: between the
     backward and the optimiser step.  The frame stands."""
-    _require_3d(renderer, "regularize")
-    lo, ls = _positive("opacity_reg", opacity_reg, allow_zero=True), _positive("scale_reg", scale_reg, allow_zero=True)
+    R.require_3d(renderer, "regularize")
+    lo, ls = positive("density: opacity_reg", opacity_reg, allow_zero=True), positive("density: scale_reg", scale_reg, allow_zero=True)
     n = renderer.nGaussians
     if n == 0 or (lo == 0.0 and ls == 0.0):
         return
     renderer.splatGrads                                          # a pending resetGrads zero-fills here: the sums start from zeros, not stale values
-    renderer._begin()
-    renderer.ctx.mcmc_regularize(renderer._grads, lo / n, ls / (3 * n))   # double here, rounded once to float at the call
-    renderer._end()
+    renderer._begin().mcmc_regularize(renderer._grads, lo / n, ls / (3 * n))   # double here, rounded once to float at the call
 
 
 class MCMCController:
@@ -155,17 +143,16 @@ class MCMCController:
     def __init__(self, *, cap_max, means_lr=None, noise_lr=5e5, from_iter: int = 500, until_iter: int = 25000, interval: int = 100,
                  min_opacity=0.005, opacity_reg=0.01, scale_reg=0.01, growth=1.05, generator=None):
         for name, v, lo in (("cap_max", cap_max, 1), ("from_iter", from_iter, 0), ("until_iter", until_iter, 0), ("interval", interval, 1)):
-            if isinstance(v, bool) or not isinstance(v, int) or v < lo:
-                raise ValueError(f"MCMCController: {name} must be an integer >= {lo}, got {v!r}")
+            integer("MCMCController", name, v, lo, strict=True)
         if until_iter < from_iter:
             raise ValueError(f"MCMCController: until_iter ({until_iter}) lies before from_iter ({from_iter})")
         self.cap_max = cap_max
-        self.means_lr = None if means_lr is None else _positive("means_lr", means_lr, allow_zero=True)
-        self.noise_lr = _positive("noise_lr", noise_lr, allow_zero=True)
-        self.min_opacity = _probability("min_opacity", min_opacity)
-        self.opacity_reg = _positive("opacity_reg", opacity_reg, allow_zero=True)
-        self.scale_reg = _positive("scale_reg", scale_reg, allow_zero=True)
-        self.growth = _positive("growth", growth)
+        self.means_lr = None if means_lr is None else positive("density: means_lr", means_lr, allow_zero=True)
+        self.noise_lr = positive("density: noise_lr", noise_lr, allow_zero=True)
+        self.min_opacity = probability("density: min_opacity", min_opacity)
+        self.opacity_reg = positive("density: opacity_reg", opacity_reg, allow_zero=True)
+        self.scale_reg = positive("density: scale_reg", scale_reg, allow_zero=True)
+        self.growth = positive("density: growth", growth)
         if self.growth < 1.0:
             raise ValueError(f"MCMCController: growth must be >= 1, got {self.growth}")
         self.from_iter, self.until_iter, self.interval, self.generator = from_iter, until_iter, interval, generator

@@ -26,21 +26,11 @@ def _finish(sums, ssim_map=None) -> Metrics:
     return Metrics(float(o[B.METRIC_MSE]), float(o[B.METRIC_MAE]), float(o[B.METRIC_SSIM]), float(o[B.METRIC_PSNR]), ssim_map)
 
 
-def _device_tensor(t, dev, shape, what):
-    import torch
-    t = t if isinstance(t, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(t, np.float32))
-    t = t.to(dev, torch.float32).contiguous()
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    return t
-
-
 def _metrics_into(renderer, img, gt, weight, sums_row, smap=None):
     """gs_image_metrics with device pointers on the renderer's stream: the four sums into `sums_row` (a float64 device tensor).  No sync."""
     Cn, H, W = img.shape
-    renderer._begin()
-    renderer.ctx.image_metrics_device(img.data_ptr(), gt.data_ptr(), weight.data_ptr() if weight is not None else 0, W, H, Cn,
-                                      smap.data_ptr() if smap is not None else 0, sums_row.data_ptr())
+    renderer._begin().image_metrics_device(img.data_ptr(), gt.data_ptr(), weight.data_ptr() if weight is not None else 0, W, H, Cn,
+                                           smap.data_ptr() if smap is not None else 0, sums_row.data_ptr())
 
 
 def image_metrics(renderer_or_ctx, img, gt, weight=None, want_map: bool = False) -> Metrics:
@@ -55,11 +45,11 @@ def image_metrics(renderer_or_ctx, img, gt, weight=None, want_map: bool = False)
     import torch
     r = renderer_or_ctx
     dev = r.imageData.device
-    img = _device_tensor(img, dev, None, "img")
+    img = R.as_device_tensor(img, dev, None, "img")
     if img.ndim != 3:
         raise ValueError("image_metrics: img must be a [C, H, W] image")
-    gt = _device_tensor(gt, dev, img.shape, "gt")
-    w = None if weight is None else _device_tensor(weight, dev, img.shape[1:], "weight")
+    gt = R.as_device_tensor(gt, dev, img.shape, "gt")
+    w = None if weight is None else R.as_device_tensor(weight, dev, img.shape[1:], "weight")
     sums = torch.empty(B.GS_METRIC_SUMS, dtype=torch.float64, device=dev)
     smap = torch.empty_like(img) if want_map else None
     _metrics_into(r, img, gt, w, sums, smap)
@@ -90,19 +80,16 @@ def evaluate(renderer, cameras, targets, weights=None, background=None) -> EvalR
         if background is not None:
             renderer.background = background
         for v in range(V):
-            tps = R.preprocess(renderer, cameras[v])
-            R.compactIdxs(renderer)
-            R.forward(renderer, tps)
-            gt = _device_tensor(targets[v], dev, None, "target")
+            R.renderFrame(renderer, cameras[v])
+            gt = R.as_device_tensor(targets[v], dev, None, "target")
             if gt.ndim != 3 or gt.shape[0] not in (3, 4) or tuple(gt.shape[1:]) != (H, W):
                 raise ValueError(f"evaluate: target {v} must be [3, {H}, {W}] or [4, {H}, {W}], not {tuple(gt.shape)}")
             if gt.shape[0] == 4:
                 rgb = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-                renderer._begin()
-                renderer.ctx.compose_target(gt.data_ptr(), W, H, rgb.data_ptr())
+                renderer._begin().compose_target(gt.data_ptr(), W, H, rgb.data_ptr())
                 keep.append(gt)
                 gt = rgb
-            w = None if weights[v] is None else _device_tensor(weights[v], dev, (H, W), "weight")
+            w = None if weights[v] is None else R.as_device_tensor(weights[v], dev, (H, W), "weight")
             _metrics_into(renderer, renderer.imageData, gt, w, sums[v])
             keep += [gt, w]
         host = sums.cpu().numpy()                                           # the one read-back

@@ -17,6 +17,7 @@ import math
 
 from . import backend as B
 from . import renderer as R
+from ._checks import betas_eps, integer, positive
 
 GROUPS_3D = ("means", "scales", "quaternions", "opacities", "sh_dc", "sh_rest")
 GROUPS_2D = ("means", "scales", "rotations", "opacities", "colors")     # colors -> lr[4]; lr[5] unused
@@ -27,13 +28,7 @@ def _is_2d(renderer) -> bool:
 
 
 def _check_rate(name: str, value) -> float:
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        raise ValueError(f"Adam: lr[{name!r}] must be a number, got {value!r}") from None
-    if not math.isfinite(v) or v < 0.0:
-        raise ValueError(f"Adam: lr[{name!r}] must be finite and >= 0, got {v}")
-    return v
+    return positive(f"Adam: lr[{name!r}]", value, allow_zero=True)
 
 
 class ExponentialLR:
@@ -49,11 +44,7 @@ class ExponentialLR:
         self.lr_init, self.lr_final = _check_rate("lr_init", lr_init), _check_rate("lr_final", lr_final)
         if (self.lr_init == 0.0) != (self.lr_final == 0.0):
             raise ValueError("ExponentialLR: lr_init and lr_final must both be > 0, or both 0 (a log-linear decay cannot reach or leave 0)")
-        if isinstance(max_steps, bool) or int(max_steps) != max_steps or max_steps < 1:
-            raise ValueError(f"ExponentialLR: max_steps must be a positive integer, not {max_steps!r}")
-        if isinstance(delay_steps, bool) or int(delay_steps) != delay_steps or delay_steps < 0:
-            raise ValueError(f"ExponentialLR: delay_steps must be an integer >= 0, not {delay_steps!r}")
-        self.max_steps, self.delay_steps = int(max_steps), int(delay_steps)
+        self.max_steps, self.delay_steps = integer("ExponentialLR", "max_steps", max_steps, 1), integer("ExponentialLR", "delay_steps", delay_steps, 0)
         self.delay_mult = float(delay_mult)
         if not math.isfinite(self.delay_mult) or self.delay_mult < 0.0:
             raise ValueError(f"ExponentialLR: delay_mult must be finite and >= 0, got {delay_mult!r}")
@@ -82,16 +73,10 @@ class Adam:
         self.is_2d = _is_2d(renderer)
         self.groups = GROUPS_2D if self.is_2d else GROUPS_3D
         self.lr = self._rates(lr)
-        b1, b2 = (float(b) for b in betas)
-        for b in (b1, b2):
-            if not (0.0 <= b < 1.0):
-                raise ValueError(f"Adam: betas must lie in [0, 1), got {tuple(betas)}")
-        eps = float(eps)
-        if not math.isfinite(eps) or eps <= 0.0:
-            raise ValueError(f"Adam: eps must be finite and > 0, got {eps}")
+        self.betas, self.eps = betas_eps("Adam", betas, eps)
         if fused and self.is_2d:
             raise ValueError("Adam: fused=True needs the 3-D renderer (gs_backward_adam)")
-        self.betas, self.eps, self.selective, self.fused = (b1, b2), eps, bool(selective), bool(fused)
+        self.selective, self.fused = bool(selective), bool(fused)
         self.step_count = 0
         import torch
         flat = renderer._splatGrads.flat
@@ -164,36 +149,27 @@ class Adam:
         raise TypeError("Adam.step: grads must be None, a flat tensor, a SplatGrads3D / 2D or a backend.GsGrads")
 
     # -- steps
+    def _step_args(self) -> tuple:
+        """What gs_adam_step and gs_backward_adam take behind the gradients: moments, rates, betas, eps and the number of the step about to run."""
+        return (self._struct(self.exp_avg), self._struct(self.exp_avg_sq), self.lr_vector(), self.betas[0], self.betas[1], self.eps,
+                self.step_count + 1)
+
     def step(self, grads=None):
         """One Adam step from `grads` (default renderer.splatGrads); the model is updated in place on the device."""
         g = self._grads_struct(grads)
-        r = self.renderer
-        t = self.step_count + 1
-        r._begin()
-        r.ctx.adam_step(g, self._struct(self.exp_avg), self._struct(self.exp_avg_sq), self.lr_vector(), self.betas[0], self.betas[1],
-                        self.eps, t, selective=self.selective)
-        r._end()
-        self.step_count = t
+        self.renderer._begin().adam_step(g, *self._step_args(), selective=self.selective)
+        self.step_count += 1
 
     def backward_step(self, dC):
         """Backward of the current frame and the Adam step in one pass (gs_backward_adam, 3-D renderer).  renderer.splatGrads is
         not filled."""
-        import numpy as np
-        import torch
         r = self.renderer
         if self.is_2d:
             raise ValueError("Adam.backward_step needs the 3-D renderer (gs_backward_adam)")
-        d = dC if isinstance(dC, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(dC, np.float32))
-        d = d.to(r.imageData.device, torch.float32).contiguous()
-        if tuple(d.shape) != tuple(r.imageData.shape):
-            raise ValueError("Adam.backward_step: dC must have the shape of renderer.imageData")
+        d = R.as_device_tensor(dC, r.imageData.device, r.imageData.shape, "Adam.backward_step: dC")
         r._dC_keepalive = d
-        t = self.step_count + 1
-        r._begin()
-        r.ctx.backward_adam(d.data_ptr(), self._struct(self.exp_avg), self._struct(self.exp_avg_sq), self.lr_vector(), self.betas[0],
-                            self.betas[1], self.eps, t, selective=self.selective)
-        r._end()
-        self.step_count = t
+        r._begin().backward_adam(d.data_ptr(), *self._step_args(), selective=self.selective)
+        self.step_count += 1
 
     # -- the number of gaussians changes (renderer.adopt_model): moment buffers of the new size first, _rebind once the renderer has adopted
     def resized_moments(self, n_out: int, zero: bool, keep_rows: int = 0) -> tuple:
@@ -235,15 +211,10 @@ class Adam:
         if step < 0:
             raise ValueError("Adam.load_state_dict: negative step")
         lr = self._rates(state["lr"])
-        b1, b2 = (float(b) for b in state["betas"])
-        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
-            raise ValueError("Adam.load_state_dict: betas must lie in [0, 1)")
-        eps = float(state["eps"])
-        if not math.isfinite(eps) or eps <= 0.0:
-            raise ValueError("Adam.load_state_dict: eps must be finite and > 0")
+        betas, eps = betas_eps("Adam.load_state_dict", state["betas"], state["eps"], got=False)
         self.exp_avg.copy_(state["exp_avg"].reshape(-1))
         self.exp_avg_sq.copy_(state["exp_avg_sq"].reshape(-1))
-        self.step_count, self.lr, self.betas, self.eps = step, lr, (b1, b2), eps
+        self.step_count, self.lr, self.betas, self.eps = step, lr, betas, eps
         self.selective = bool(state.get("selective", self.selective))
 
 
@@ -256,14 +227,7 @@ class CameraAdam:
     def __init__(self, camera, lr_eye: float, lr_lookat: float, lr_focal: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8):
         import numpy as np
         self.lr = dict(eye=_check_rate("eye", lr_eye), lookAt=_check_rate("lookAt", lr_lookat), focal=_check_rate("focal", lr_focal))
-        b1, b2 = (float(b) for b in betas)
-        for b in (b1, b2):
-            if not (0.0 <= b < 1.0):
-                raise ValueError(f"CameraAdam: betas must lie in [0, 1), got {tuple(betas)}")
-        eps = float(eps)
-        if not math.isfinite(eps) or eps <= 0.0:
-            raise ValueError(f"CameraAdam: eps must be finite and > 0, got {eps}")
-        self.betas, self.eps = (b1, b2), eps
+        self.betas, self.eps = betas_eps("CameraAdam", betas, eps)
         self._template = camera
         # the parameter vector: eye[3], lookAt[3], fx, fy
         self.x = np.concatenate([np.asarray(camera.eye, np.float64).reshape(3), np.asarray(camera.lookAt, np.float64).reshape(3),

@@ -128,7 +128,86 @@ def model_arrays(splatData: SplatData3D) -> tuple:
     return splatData.means, splatData.scales, splatData.quaternions, splatData.opacities, splatData.shs
 
 
-class GaussianRenderer3D:               # renderer.jl:205-219
+def as_device_tensor(value, device, shape, name: str):
+    """value (a tensor, an array, nested numbers) as a contiguous float32 tensor on `device`; shape None: any, else a ValueError that
+    names `name`.  A tensor that already is all that comes back as the same object: no copy.  A caller that queues a library call on the
+    result keeps it referenced until the call has run (_dC_keepalive, _keep*)."""
+    import torch
+    t = value if isinstance(value, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(value, np.float32))
+    t = t.to(device, torch.float32).contiguous()
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def draw(fn, shape, generator, device):
+    """fn (torch.rand, torch.randn) float32 numbers of `shape` on `device`, drawn on the generator's own device so that the caller's
+    generator decides them."""
+    import torch
+    gdev = generator.device if generator is not None else device
+    return fn(shape, generator=generator, device=gdev, dtype=torch.float32).to(device).contiguous()
+
+
+class _Renderer:
+    """What the two renderers share: the output tensors, the context and its stream bind, the lazily zeroed gradients, the background."""
+
+    def __init__(self, imgSize, tensor_device, **ctx_kw):
+        import torch
+        W, H = int(imgSize[0]), int(imgSize[1])
+        self.imageData = torch.zeros((3, H, W), dtype=torch.float32, device=tensor_device)     # CUDA.zeros(imgSize...)
+        self.transmittance = torch.ones((H, W), dtype=torch.float32, device=tensor_device)     # CUDA.ones(imgSize[1:2])
+        self.camera: Camera | None = None
+        self.ctx = B.Context(**ctx_kw)
+        # the library enqueues on the caller's CURRENT torch stream (re-read at every API call), like any torch
+        # op: no cross-stream fences, so consecutive calls run back to back on the GPU
+        self._stream_handle = None
+
+    def _begin(self) -> B.Context:
+        """The way into the library: bind the ctx to torch's current stream (handle 0 = the legacy default stream = GS_STREAM_LEGACY;
+        an unchanged handle costs no call) and return it."""
+        h = _current_stream_handle(self.imageData.device) or 1
+        if h != self._stream_handle:
+            self.ctx.set_stream(h)
+            self._stream_handle = h
+        return self.ctx
+
+    @property
+    def background(self) -> tuple:
+        """The colour behind the last splat, three floats (default black): forward() leaves C + T * background in imageData, and
+        backward() differentiates that image -- transparent pixels of a white-background dataset then carry a gradient.  Setting it
+        keeps the tile lists and drops the image: render again before the next backward.  It survives a restructured model."""
+        return self.ctx.background
+
+    @background.setter
+    def background(self, rgb):
+        self.ctx.set_background(rgb)
+
+    @property
+    def splatGrads(self):
+        """renderer.splatGrads (renderer.jl:207).  resetGrads is lazy: the zero fill is skipped when the
+        next backward overwrites anyway, and materialised here if somebody looks first."""
+        if self._grads_lazy_zero:
+            self._splatGrads.flat.zero_()
+            self._grads_lazy_zero = False
+        return self._splatGrads
+
+    def _set_grads(self, splatGrads):
+        self._splatGrads = splatGrads
+        self._grads_lazy_zero = False       # True: resetGrads() pending, the next backward overwrites
+        self._grads = grads_struct(splatGrads.flat, layout_of(splatGrads)[0])
+
+    # scratch arrays of the reference struct, fetched on demand (export_debug for the fp32 ones)
+    @property
+    def positions(self): return self.ctx.get_array(B.ARR_MU)
+    @property
+    def cov2ds(self): return self.ctx.get_array(B.ARR_COV2D)
+    @property
+    def invCov2ds(self): return self.ctx.get_array(B.ARR_INVCOV)
+    @property
+    def bbs(self): return self.ctx.get_array(B.ARR_BBS)
+
+
+class GaussianRenderer3D(_Renderer):    # renderer.jl:205-219
     def __init__(self, splatData: SplatData3D, imgSize, sh_degree: int, device: int = 0, order: int = B.ORDER_DEPTH_DESC,
                  t_min: float = 1e-5, export_debug: bool = False, profile_stages: bool = False, deterministic: bool = False,
                  alpha_cull: bool = True, rank_mode: int = 1, slab_mode: int = 1, schedule: int = 0, share_grads_with=None,
@@ -136,34 +215,23 @@ class GaussianRenderer3D:               # renderer.jl:205-219
         """background: (r, g, b) behind the last splat (the `background` property); None: black, the reference's frame.
         share_grads_with: another GaussianRenderer3D over the same splatData whose gradient buffer this one accumulates into
         (a second view in flight, distributed.HipViewRenderer): no buffer of its own is allocated."""
-        import torch
         self._shares_grads = share_grads_with is not None   # (a resize replaces the buffer: only its owner may, check_resize)
-        W, H = int(imgSize[0]), int(imgSize[1])
-        dev = splatData.means.device
-        self.imageData = torch.zeros((3, H, W), dtype=torch.float32, device=dev)      # CUDA.zeros(imgSize...)
-        self.transmittance = torch.ones((H, W), dtype=torch.float32, device=dev)      # CUDA.ones(imgSize[1:2])
+        super().__init__(imgSize, splatData.means.device, device=device, order=order, t_min=t_min, export_debug=export_debug,
+                         profile_stages=profile_stages, deterministic=deterministic, alpha_cull=alpha_cull, rank_mode=rank_mode,
+                         slab_mode=slab_mode, schedule=schedule, **ctx_kw)
         self.sh_degree = sh_degree
-        self.camera: Camera | None = None
-        self.ctx = B.Context(device=device, order=order, t_min=t_min, export_debug=export_debug, profile_stages=profile_stages,
-                             deterministic=deterministic, alpha_cull=alpha_cull, rank_mode=rank_mode, slab_mode=slab_mode, schedule=schedule, **ctx_kw)
-        # the library enqueues on the caller's CURRENT torch stream (re-read at every API call), like any torch
-        # op: no cross-stream fences, so consecutive calls run back to back on the GPU
-        self._stream_handle = None
-        self._begin()
         self._set_model(splatData, share_grads_with._splatGrads if share_grads_with is not None else None)
         if background is not None:
             self.background = background
 
-    # -- the model and its size.  These three methods are the only code that assigns splatData, nGaussians, _splatGrads, _grads_lazy_zero
-    # and _grads (DESIGN.md 5.8m): a strategy that changes the number of gaussians allocates with alloc_model, fills the arrays through the
+    # -- the model and its size.  These three methods are the only code that assigns splatData and nGaussians, and the only callers of
+    # _set_grads (DESIGN.md 5.8m): a strategy that changes the number of gaussians allocates with alloc_model, fills the arrays through the
     # library and hands them to adopt_model; optim.Adam follows with resized_moments / _rebind
     def _set_model(self, splatData: SplatData3D, shared_grads=None):
         self.splatData = splatData
         self.nGaussians = splatData.means.shape[0]
-        self._splatGrads = shared_grads if shared_grads is not None else initGrads(splatData)
-        self._grads_lazy_zero = False       # True: resetGrads() pending, the next backward overwrites
-        self._grads = grads_struct(self._splatGrads.flat, layout_of(self._splatGrads)[0])
-        self.ctx.set_model_device(self.nGaussians, self.sh_degree, [t.data_ptr() for t in model_arrays(splatData)])
+        self._set_grads(shared_grads if shared_grads is not None else initGrads(splatData))
+        self._begin().set_model_device(self.nGaussians, self.sh_degree, [t.data_ptr() for t in model_arrays(splatData)])
 
     def check_resize(self, optimizer, who: str):
         """A call that changes the number of gaussians needs the renderer that owns its gradient buffer, and that renderer's optimiser."""
@@ -190,27 +258,6 @@ class GaussianRenderer3D:               # renderer.jl:205-219
         self._set_model(new_data)
 
     @property
-    def background(self) -> tuple:
-        """The colour behind the last splat, three floats (default black): forward() leaves C + T * background in imageData, and
-        backward() differentiates that image -- transparent pixels of a white-background dataset then carry a gradient.  Setting it
-        keeps the tile lists and drops the image: render again before the next backward.  It survives a restructured model."""
-        return self.ctx.background
-
-    @background.setter
-    def background(self, rgb):
-        self.ctx.set_background(rgb)
-
-    @property
-    def splatGrads(self) -> SplatGrads3D:
-        """renderer.splatGrads (renderer.jl:207).  resetGrads is lazy: the zero fill is skipped when the
-        next backward overwrites anyway, and materialised here if somebody looks first."""
-        if self._grads_lazy_zero:
-            import torch
-            self._splatGrads.flat.zero_()
-            self._grads_lazy_zero = False
-        return self._splatGrads
-
-    @property
     def active_sh_degree(self) -> int:
         """The SH degree the kernels evaluate: the model's own unless a lower one was set (the degree schedule of a training run,
         train.SHDegreeSchedule; a viewer drawing a degree-3 model at degree 0).  Setting it (-1: the model's own again) changes
@@ -220,16 +267,6 @@ class GaussianRenderer3D:               # renderer.jl:205-219
     @active_sh_degree.setter
     def active_sh_degree(self, degree: int):
         self.ctx.set_active_sh_degree(int(degree))
-
-    def _begin(self):
-        """Bind the ctx to torch's current stream (handle 0 = the legacy default stream = GS_STREAM_LEGACY)."""
-        h = _current_stream_handle(self.imageData.device) or 1
-        if h != self._stream_handle:
-            self.ctx.set_stream(h)
-            self._stream_handle = h
-
-    def _end(self):                 # kept for callers written against the fenced version: nothing to do
-        pass
 
     def _set_view(self, camera):
         cam = camera or self.camera or default_camera()
@@ -257,22 +294,13 @@ class GaussianRenderer3D:               # renderer.jl:205-219
             self.ctx.set_view_slot(slot)
             self._view_slot = slot
 
-    # scratch arrays of the reference struct, fetched on demand (export_debug for the fp32 ones)
     @property
     def sortIdxs(self): return self.ctx.get_array(B.ARR_SORT_IDXS)
     @property
-    def positions(self): return self.ctx.get_array(B.ARR_MU)
-    @property
-    def cov2ds(self): return self.ctx.get_array(B.ARR_COV2D)
-    @property
     def cov3ds(self): return self.ctx.get_array(B.ARR_COV3D)
-    @property
-    def invCov2ds(self): return self.ctx.get_array(B.ARR_INVCOV)
-    @property
-    def bbs(self): return self.ctx.get_array(B.ARR_BBS)
 
 
-class GaussianRenderer2D:               # renderer.jl:7-18
+class GaussianRenderer2D(_Renderer):     # renderer.jl:7-18
     """The 2-D image-fitting renderer: same binning and composite kernels as the 3-D one behind a different
     preprocess (cov2d.jl:3-28).  The reference's own 2-D constructors reference undefined names (renderer.jl:38-82)
     and its backward (splat.jl:271-396) is not the adjoint of any one forward; this is the consistent version
@@ -280,43 +308,19 @@ class GaussianRenderer2D:               # renderer.jl:7-18
 
     def __init__(self, splatData: SplatData2D, imgSize, device: int = 0, t_min: float = 1e-5, export_debug: bool = False,
                  profile_stages: bool = False, deterministic: bool = False, alpha_cull: bool = True, background=None):
-        import torch
+        super().__init__(imgSize, splatData.means.device, device=device, order=B.ORDER_INDEX, t_min=t_min, export_debug=export_debug,
+                         profile_stages=profile_stages, deterministic=deterministic, alpha_cull=alpha_cull)
         self.splatData = splatData
-        self._splatGrads = initGrads2D(splatData)
-        self._grads_lazy_zero = False
-        self._grads = grads_struct(self._splatGrads.flat, layout_of(self._splatGrads)[0])
-        W, H = int(imgSize[0]), int(imgSize[1])
-        dev = splatData.means.device
-        self.imageData = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
-        self.transmittance = torch.ones((H, W), dtype=torch.float32, device=dev)
         self.nGaussians = splatData.means.shape[0]
-        self.camera = None
-        self.ctx = B.Context(device=device, order=B.ORDER_INDEX, t_min=t_min, export_debug=export_debug, profile_stages=profile_stages,
-                             deterministic=deterministic, alpha_cull=alpha_cull)
-        self._stream_handle = None
-        self._begin()
-        self.ctx.set_model_2d_device(self.nGaussians, [t.data_ptr() for t in (splatData.means, splatData.scales, splatData.rotations,
-                                                                              splatData.opacities, splatData.colors)])
+        self._set_grads(initGrads2D(splatData))
+        self._begin().set_model_2d_device(self.nGaussians, [t.data_ptr() for t in (splatData.means, splatData.scales, splatData.rotations,
+                                                                                   splatData.opacities, splatData.colors)])
         if background is not None:
             self.background = background
-
-    splatGrads = GaussianRenderer3D.splatGrads
-    background = GaussianRenderer3D.background
-    _begin = GaussianRenderer3D._begin
-    _end = GaussianRenderer3D._end
 
     def _set_view(self, camera=None):
         H, W = self.transmittance.shape
         self.ctx.set_image_size(W, H)
-
-    @property
-    def positions(self): return self.ctx.get_array(B.ARR_MU)
-    @property
-    def cov2ds(self): return self.ctx.get_array(B.ARR_COV2D)
-    @property
-    def invCov2ds(self): return self.ctx.get_array(B.ARR_INVCOV)
-    @property
-    def bbs(self): return self.ctx.get_array(B.ARR_BBS)
 
 
 def initData2D(nGaussians: int, seed: int = 0) -> dict:
@@ -402,8 +406,7 @@ def preprocess(renderer, camera: Camera | None = None):
     instead) and forward.jl:9-33 (2-D: no camera).  Returns `tps` lazily (the reference returns the clip-space
     positions only to hand them to forward()); None for the 2-D renderer."""
     renderer._set_view(camera)
-    renderer._begin()
-    renderer.ctx.preprocess()
+    renderer._begin().preprocess()
     return _LazyTps(renderer) if isinstance(renderer, GaussianRenderer3D) else None
 
 
@@ -425,23 +428,24 @@ class _LazyTps:
 def compactIdxs(renderer, threads=(16, 16), blocks=None):
     """forward.jl:118-161: builds the per-tile splat lists (tile|depth keys, radix sort, ranges)."""
     gx, gy = blocks if blocks is not None else (0, 0)
-    renderer._begin()
-    renderer.ctx.bin(int(gx), int(gy))
+    renderer._begin().bin(int(gx), int(gy))
 
 
 def _bind_outputs(renderer):
-    """renderer.imageData / renderer.transmittance ARE the library's output buffers (gs_bind_outputs: no copy).  The raw
+    """The way into the library for a call that reads or writes the frame's image: _begin(), and
+    renderer.imageData / renderer.transmittance ARE the library's output buffers (gs_bind_outputs: no copy).  The raw
     pointers are re-read at every forward / backward: if the caller replaced a tensor since, the new one is bound (and a
-    backward then refuses to run on a forward that wrote somewhere else)."""
+    backward then refuses to run on a forward that wrote somewhere else).  Returns the ctx; the pointers bound are renderer._bound_out."""
+    ctx = renderer._begin()
     img, tr = renderer.imageData, renderer.transmittance
     H, W = tr.shape
     if tuple(img.shape) != (3, H, W) or not img.is_contiguous() or not tr.is_contiguous():
         raise ValueError("renderer.imageData must be a contiguous [3, H, W] tensor matching renderer.transmittance [H, W]")
     key = (img.data_ptr(), tr.data_ptr())
     if getattr(renderer, "_bound_out", None) != key:
-        renderer.ctx.bind_outputs(*key)                         # (the ctx falls back to the binned frame: a new forward is due)
+        ctx.bind_outputs(*key)                                  # (the ctx falls back to the binned frame: a new forward is due)
         renderer._bound_out = key
-    return key
+    return ctx
 
 
 def forward(renderer, tps=None, threads=(16, 16), blocks=None):
@@ -449,9 +453,15 @@ def forward(renderer, tps=None, threads=(16, 16), blocks=None):
     Contract: the two tensors stay the library's buffers until the frame's last backward -- the backward reads the rendered
     colours from renderer.imageData, so editing it in place between forward and backward changes the gradients, and
     replacing it makes backward() raise (render again first)."""
-    renderer._begin()
-    ip, tp = _bind_outputs(renderer)
-    renderer.ctx.forward_device(ip, tp)
+    _bind_outputs(renderer).forward_device(*renderer._bound_out)
+
+
+def renderFrame(renderer, camera: Camera | None = None):
+    """preprocess -> compactIdxs -> forward under `camera`: the frame of a training step, of an evaluated view, of every view of a
+    multi-view step."""
+    tps = preprocess(renderer, camera)
+    compactIdxs(renderer)
+    forward(renderer, tps)
 
 
 def backward(renderer, ΔC, skip_shs: bool = False, phase: str = "all"):
@@ -460,31 +470,23 @@ def backward(renderer, ΔC, skip_shs: bool = False, phase: str = "all"):
     per-view colour gradients (distributed.multi_view_step(sync="factored")).
     phase: "all" (default); "composite" then "params" (split backward); or "composite", "params_sh", "params_geom": the
     per-gaussian chain in two steps, so that the all-reduce of Δshs can start while the geometry chain still runs."""
-    import torch
-    dC = ΔC if isinstance(ΔC, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(ΔC, np.float32))
-    dC = dC.to(renderer.imageData.device, torch.float32).contiguous()
-    assert dC.shape == renderer.imageData.shape
+    dC = as_device_tensor(ΔC, renderer.imageData.device, renderer.imageData.shape, "ΔC")
     renderer._dC_keepalive = dC
-    renderer._begin()
-    _bind_outputs(renderer)                                     # a replaced imageData is caught here: the ctx then reports "gs_forward first"
+    ctx = _bind_outputs(renderer)                               # a replaced imageData is caught here: the ctx then reports "gs_forward first"
     grads = renderer._grads
     if skip_shs:
-        grads = B.GsGrads(grads.d_means, grads.d_scales, grads.d_quats, grads.d_opacities, None)
-    renderer.ctx.backward(dC.data_ptr(), grads, overwrite=renderer._grads_lazy_zero, phase=phase)
+        grads = _without_shs(grads)
+    ctx.backward(dC.data_ptr(), grads, overwrite=renderer._grads_lazy_zero, phase=phase)
     if phase not in ("composite", "params_sh"):                 # "params_sh" is followed by "params_geom" with the same overwrite flag
         renderer._grads_lazy_zero = False
 
 
+def _without_shs(g: B.GsGrads) -> B.GsGrads:
+    """The gradient arrays without Δshs: a call that leaves the SH gradients alone."""
+    return B.GsGrads(g.d_means, g.d_scales, g.d_quats, g.d_opacities, None)
+
+
 # ---------------------------------------------------------------- feature maps (3-D renderer): depth, opacity, per-gaussian features
-
-def _feature_tensor(renderer, t, shape, what):
-    import torch
-    t = t if isinstance(t, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(t, np.float32))
-    t = t.to(renderer.imageData.device, torch.float32).contiguous()
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    return t
-
 
 def renderFeatures(renderer, feat):
     """Composite three per-gaussian floats over the frame forward() rendered: feat [n, 3] -> (F [3, H, W], T [H, W]) with
@@ -493,12 +495,10 @@ def renderFeatures(renderer, feat):
     (a frame binned in depth slabs is refused: pass slab_mode=0 to getRenderer).  Wider features are rendered in triples."""
     import torch
     H, W = renderer.transmittance.shape
-    f = _feature_tensor(renderer, feat, (renderer.nGaussians, 3), "feat")
+    f = as_device_tensor(feat, renderer.imageData.device, (renderer.nGaussians, 3), "feat")
     F = torch.empty((3, H, W), dtype=torch.float32, device=f.device)
     T = torch.empty((H, W), dtype=torch.float32, device=f.device)
-    renderer._begin()
-    _bind_outputs(renderer)
-    renderer.ctx.render_features(f.data_ptr(), F.data_ptr(), T.data_ptr())
+    _bind_outputs(renderer).render_features(f.data_ptr(), F.data_ptr(), T.data_ptr())
     return F, T
 
 
@@ -508,17 +508,13 @@ def backwardFeatures(renderer, feat, F, dF):
     here).  F is what renderFeatures returned for this feat on this frame.  Legal before, between or after backward()."""
     import torch
     H, W = renderer.transmittance.shape
-    n = renderer.nGaussians
-    f = _feature_tensor(renderer, feat, (n, 3), "feat")
-    F = _feature_tensor(renderer, F, (3, H, W), "F")
-    dF = _feature_tensor(renderer, dF, (3, H, W), "dF")
+    n, dev = renderer.nGaussians, renderer.imageData.device
+    f = as_device_tensor(feat, dev, (n, 3), "feat")
+    F = as_device_tensor(F, dev, (3, H, W), "F")
+    dF = as_device_tensor(dF, dev, (3, H, W), "dF")
     d_feat = torch.empty((n, 3), dtype=torch.float32, device=f.device)
     renderer.splatGrads                                         # a pending lazy reset becomes zeros now: this call accumulates
-    renderer._begin()
-    _bind_outputs(renderer)
-    g = renderer._grads
-    renderer.ctx.backward_features(f.data_ptr(), F.data_ptr(), dF.data_ptr(), d_feat.data_ptr(),
-                                   B.GsGrads(g.d_means, g.d_scales, g.d_quats, g.d_opacities, None))
+    _bind_outputs(renderer).backward_features(f.data_ptr(), F.data_ptr(), dF.data_ptr(), d_feat.data_ptr(), _without_shs(renderer._grads))
     return d_feat
 
 
@@ -527,8 +523,7 @@ def viewDepth(renderer):
     computes it (ts[3, :] of the reference's tValues)."""
     import torch
     z = torch.empty((renderer.nGaussians,), dtype=torch.float32, device=renderer.imageData.device)
-    renderer._begin()
-    renderer.ctx.view_depth(z.data_ptr())
+    renderer._begin().view_depth(z.data_ptr())
     return z
 
 
@@ -560,7 +555,7 @@ def backwardDepth(renderer, dD):
     feat, planes, z = st
     d_feat = backwardFeatures(renderer, feat, planes, dD)
     dz = (d_feat[:, 0] + 2.0 * z * d_feat[:, 1]).contiguous()
-    renderer.ctx.view_depth_backward(dz.data_ptr(), renderer._grads.d_means)
+    renderer._begin().view_depth_backward(dz.data_ptr(), renderer._grads.d_means)
     return d_feat
 
 
@@ -592,14 +587,17 @@ def backwardCamera(renderer) -> CameraGrads:
     """The gradient of the frame's loss with respect to the view (gs_backward_camera): call it after backward() on the frame and BEFORE
     anything steps the model -- the chain is recomputed from the resident parameters.  The frame and renderer.splatGrads stay as they
     are.  The 2-D renderer has no camera: the library's error (GS_ERR_UNSUPPORTED) is raised."""
-    renderer._begin()
-    return CameraGrads.from_flat(renderer.ctx.backward_camera())
+    return CameraGrads.from_flat(renderer._begin().backward_camera())
+
+
+def require_3d(renderer, who: str):
+    if not isinstance(renderer, GaussianRenderer3D):
+        raise ValueError(f"{who}: needs the 3-D renderer")
 
 
 def resetGrads(renderer_or_grads):
     """splat.jl:158-173."""
-    import torch
-    if isinstance(renderer_or_grads, (GaussianRenderer3D, GaussianRenderer2D)):
+    if isinstance(renderer_or_grads, _Renderer):
         renderer_or_grads._grads_lazy_zero = True      # zero fill deferred: see GaussianRenderer3D.splatGrads
     else:
         renderer_or_grads.flat.zero_()

@@ -22,6 +22,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import renderer as R
+from ._checks import integer
 
 
 def kernelWindow(windowSize: int = 11, σ: float = 1.5) -> np.ndarray:
@@ -49,35 +50,23 @@ class LossFunction:
         target the loss compares the frame against.  The result is a scratch tensor kept here and overwritten by the next call."""
         import torch
         dev = self.r.imageData.device
-        rgba = rgba if isinstance(rgba, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(rgba, np.float32))
-        rgba = rgba.to(dev, torch.float32).contiguous()
-        if tuple(rgba.shape) != (4, self.H, self.W):
-            raise ValueError(f"compose_target: the target must be [4, {self.H}, {self.W}], not {tuple(rgba.shape)}")
+        rgba = R.as_device_tensor(rgba, dev, (4, self.H, self.W), "compose_target: the target")
         if self._target is None:
             self._target = torch.empty((3, self.H, self.W), dtype=torch.float32, device=dev)
-        self.r._begin()
-        self.r.ctx.compose_target(rgba.data_ptr(), self.W, self.H, self._target.data_ptr())
-        self.r._end()
+        self.r._begin().compose_target(rgba.data_ptr(), self.W, self.H, self._target.data_ptr())
         self._keep_rgba = rgba
         return self._target
 
     def _ptrs(self, img, gt):
-        import torch
-        dev = self.r.imageData.device
-        img = img if isinstance(img, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(img, np.float32))
-        gt = gt if isinstance(gt, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(gt, np.float32))
-        img = img.to(dev, torch.float32).contiguous(); gt = gt.to(dev, torch.float32).contiguous()
-        assert tuple(img.shape) == (self.C, self.H, self.W) == tuple(gt.shape)
-        return img, gt
+        dev, shape = self.r.imageData.device, (self.C, self.H, self.W)
+        return R.as_device_tensor(img, dev, shape, "the loss's image"), R.as_device_tensor(gt, dev, shape, "the loss's target")
 
     def value_and_grad(self, img, gt, want_loss: bool = True):
         import torch
         img, gt = self._ptrs(img, gt)
         if self._dC is None:
             self._dC = torch.empty_like(img)
-        self.r._begin()
-        val = self.r.ctx.loss_device(img.data_ptr(), gt.data_ptr(), self._dC.data_ptr(), self.W, self.H, self.C, self.λ, want_loss)
-        self.r._end()
+        val = self.r._begin().loss_device(img.data_ptr(), gt.data_ptr(), self._dC.data_ptr(), self.W, self.H, self.C, self.λ, want_loss)
         self._keep = (img, gt)
         return val, self._dC
 
@@ -100,8 +89,7 @@ class SHDegreeSchedule:
     density.DensityController does, so one schedule serves one training run."""
 
     def __init__(self, every: int = 1000, start: int = 0, max_degree: "int | None" = None):
-        if int(every) != every or every < 1:
-            raise ValueError(f"SHDegreeSchedule: every must be a positive integer, not {every!r}")
+        integer("SHDegreeSchedule", "every", every, 1)
         if int(start) != start or not 0 <= start <= 3:
             raise ValueError(f"SHDegreeSchedule: start must be in 0..3, not {start!r}")
         if max_degree is not None and (int(max_degree) != max_degree or not 0 <= max_degree <= 3):
@@ -143,7 +131,7 @@ class RandomBackground:
 
     def apply(self, renderer) -> tuple:
         """Set the renderer's background for the iteration about to run and count it.  Returns the colour."""
-        if not isinstance(renderer, (R.GaussianRenderer3D, R.GaussianRenderer2D)):
+        if not isinstance(renderer, R._Renderer):
             raise ValueError("RandomBackground: apply needs a GaussianRenderer3D or GaussianRenderer2D")
         rgb = self.draw()
         renderer.background = rgb
@@ -195,16 +183,17 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
     the one above on that gradient, so every optimiser form, the fused ones included, density control, the SH schedule, the backgrounds,
     pose and freeze_model run unchanged.  One without the other, or a view out of range, is a ValueError.  None: the same calls in the
     same order as without the arguments."""
+    fused = fused_sgd or (optimizer is not None and optimizer.fused)        # a fused form is in use: no frame is left behind the backward
     if (exposure is None) != (view is None):
         raise ValueError("trainStep: exposure and view go together (the view names the row of the exposure table)")
     if exposure is not None:
         view = exposure._view(view)
     if pose is not None and camera is not None:
         raise ValueError("trainStep: camera and pose exclude each other (the iteration renders under pose.camera)")
-    if pose is not None and (fused_sgd or (optimizer is not None and optimizer.fused)):
+    if pose is not None and fused:
         raise ValueError("trainStep: pose refinement needs the unfused backward (no fused_sgd, no Adam(fused=True)): "
                          "the fused forms leave no frame to take the camera gradient from")
-    if freeze_model and (fused_sgd or (optimizer is not None and optimizer.fused)):
+    if freeze_model and fused:
         raise ValueError("trainStep: freeze_model needs the unfused backward (no fused_sgd, no Adam(fused=True)): "
                          "the fused forms step the model inside the backward")
     if pose is not None:
@@ -214,7 +203,7 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
                          "could not follow the colour")
     if optimizer is not None and fused_sgd:
         raise ValueError("trainStep: fused_sgd and optimizer exclude each other (make the optimiser with fused=True instead)")
-    if density is not None and (fused_sgd or (optimizer is not None and optimizer.fused)):
+    if density is not None and fused:
         raise ValueError("trainStep: density control needs the unfused backward (no fused_sgd, no Adam(fused=True)): "
                          "the fused forms leave no frame to accumulate statistics from")
     if sh_schedule is not None:
@@ -223,9 +212,7 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
         background.apply(renderer)
     elif background is not None:
         renderer.background = background
-    tps = R.preprocess(renderer, camera)
-    R.compactIdxs(renderer)
-    R.forward(renderer, tps)
+    R.renderFrame(renderer, camera)
     if getattr(gtimg, "ndim", 0) == 3 and gtimg.shape[0] == 4:
         gtimg = lossFunc.compose_target(gtimg)
     if exposure is None:
@@ -235,39 +222,25 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
         loss, ΔC = lossFunc.value_and_grad(adjusted, exposure.mask_target(view, gtimg), want_loss)
         ΔC = exposure.backward(view, ΔC)
         exposure.step(view)
-    if optimizer is not None:
-        if optimizer.fused:
+    if fused:                                                    # backward and update in one pass: renderer.splatGrads is not filled
+        if optimizer is not None:
             optimizer.backward_step(ΔC)
-            return loss
-        R.backward(renderer, ΔC)
-        if pose is not None:
-            _pose_step(renderer, pose)
-        if density is not None:
-            density.accumulate(renderer)
-        if not freeze_model:
-            optimizer.step()
-        R.resetGrads(renderer)
-        if density is not None:
-            density.after_step(renderer, optimizer)
-        return loss
-    if fused_sgd:
-        renderer._dC_keepalive = ΔC
-        renderer._begin()
-        renderer.ctx.backward_sgd(ΔC.data_ptr(), float(lr))
-        renderer._end()
+        else:
+            renderer._dC_keepalive = ΔC
+            renderer._begin().backward_sgd(ΔC.data_ptr(), float(lr))
         return loss
     R.backward(renderer, ΔC)
     if pose is not None:
         _pose_step(renderer, pose)
     if density is not None:
         density.accumulate(renderer)
-    if not freeze_model:
-        renderer._begin()
-        renderer.ctx.sgd_step(float(lr), renderer._grads)    # param .-= lr * Δparam (train.jl:42-46)
-        renderer._end()
-    R.resetGrads(renderer)                                   # train.jl:55
+    if not freeze_model and optimizer is not None:
+        optimizer.step()
+    elif not freeze_model:
+        renderer._begin().sgd_step(float(lr), renderer._grads)   # param .-= lr * Δparam (train.jl:42-46)
+    R.resetGrads(renderer)                                       # train.jl:55
     if density is not None:
-        density.after_step(renderer, None)
+        density.after_step(renderer, optimizer)
     return loss
 
 
@@ -279,8 +252,7 @@ class Evaluator:
     evaluation cameras ids of their own: the id names the view slot, and the training views keep their launch-order history."""
 
     def __init__(self, cameras, targets, every: int, weights=None, background=None):
-        if isinstance(every, bool) or int(every) != every or every < 1:
-            raise ValueError(f"Evaluator: every must be a positive integer, not {every!r}")
+        integer("Evaluator", "every", every, 1)
         self.targets = list(targets)
         V = len(self.targets)
         self.cameras = [None] * V if cameras is None else list(cameras)

@@ -312,3 +312,26 @@ def test_bound_output_buffers(oracle):
     with pytest.raises(Exception):
         ctx.bind_outputs(i3.data_ptr(), 0)                          # both or neither
     ctx.close()
+
+
+def test_render_frame_is_the_three_calls_and_a_refused_backward_leaves_the_frame():
+    """renderer.renderFrame against preprocess, compactIdxs, forward made one by one: image, transmittance and sortIdxs bit for bit.  A dC of
+    the wrong shape is a ValueError raised before the library is entered: a correct backward right after it runs on the frame that stands."""
+    import torch
+    from common import render, same_bits, small_scene_renderer
+    from gaussiansplat_amd import renderer as R, synthetic
+    a, cam, W, H = small_scene_renderer(300, 31)
+    b = small_scene_renderer(300, 31)[0]
+    render(a, cam)
+    R.renderFrame(b, cam)
+    torch.cuda.synchronize()
+    assert float(a.imageData.abs().max()) > 0.0
+    assert same_bits(a.imageData, b.imageData) and same_bits(a.transmittance, b.transmittance) and same_bits(a.sortIdxs, b.sortIdxs)
+    dC = synthetic.make_dC(W, H, 31)
+    R.backward(a, dC)
+    for bad in (np.zeros((3, W, H), np.float32), np.zeros((H, W), np.float32), torch.zeros((3, H, W + 1), device="cuda")):
+        with pytest.raises(ValueError, match="ΔC"):
+            R.backward(b, bad)
+    R.backward(b, dC)
+    torch.cuda.synchronize()
+    assert float(a.splatGrads.flat.abs().max()) > 0.0 and same_bits(a.splatGrads.flat, b.splatGrads.flat)

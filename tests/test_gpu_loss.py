@@ -82,7 +82,7 @@ def test_sgd_step_and_training_reduces_loss():
     l0, dC = lf.value_and_grad(r.imageData, gt)
     R.backward(r, dC)
     g = r.splatGrads.Δshs.clone()
-    r._begin(); r.ctx.sgd_step(0.5, r._grads); r._end(); torch.cuda.synchronize()
+    r._begin(); r.ctx.sgd_step(0.5, r._grads); torch.cuda.synchronize()
     assert torch.allclose(r.splatData.shs, before - 0.5 * g, rtol=1e-6, atol=1e-7)
     R.resetGrads(r)
     losses = TR.train(r, gt, 2.0, lf, iterations=25, camera=cam)

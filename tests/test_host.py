@@ -155,3 +155,106 @@ def test_view_record_is_kept_with_the_camera_and_follows_its_fields():
     assert len(g.ctx.built) == 1 and g.ctx.built[0][8:] == (80, 48)
     R.GaussianRenderer3D._set_view(f, a)
     assert len(f.ctx.built) == 5                        # (one record per camera: the other size pushed it out)
+
+
+# ---------------------------------------------------------------- the mirror's one coercion function
+
+def test_as_device_tensor_coerces_checks_and_passes_through():
+    """renderer.as_device_tensor: float64 NumPy comes out float32 and contiguous, a strided tensor comes out contiguous, a tensor that
+    already matches is returned as the same object (no copy), and a wrong shape is a ValueError that carries the given name."""
+    import pytest
+    import torch
+    from gaussiansplat_amd import renderer as R
+    cpu = torch.device("cpu")
+    a = np.arange(24, dtype=np.float64).reshape(2, 3, 4)
+    t = R.as_device_tensor(a[:, ::-1], cpu, (2, 3, 4), "a")
+    assert isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and np.array_equal(t.numpy(), a[:, ::-1].astype(np.float32))
+    s = torch.arange(12, dtype=torch.float32).reshape(3, 4).t()
+    assert not s.is_contiguous()
+    c = R.as_device_tensor(s, cpu, (4, 3), "s")
+    assert c.is_contiguous() and torch.equal(c, s)
+    m = torch.zeros((3, 4, 5), dtype=torch.float32)
+    assert R.as_device_tensor(m, cpu, (3, 4, 5), "m") is m and R.as_device_tensor(m, cpu, None, "m") is m
+    with pytest.raises(ValueError, match="the_name"):
+        R.as_device_tensor(m, cpu, (3, 5, 4), "the_name")
+    with pytest.raises(ValueError, match="the_name"):
+        R.as_device_tensor(a, cpu, (4, 3, 2), "the_name")
+
+
+# ---------------------------------------------------------------- the order of a training step's library calls, pinned literally
+
+def _recording_renderer():
+    """A GaussianRenderer3D built by hand (no getRenderer, no library): 4 x 4 CPU images, five gaussians, a context that records the name
+    of every method called on it; the stream bind and the view are logged as <bind> and <view>."""
+    import torch
+    from gaussiansplat_amd import renderer as R
+    log = []
+
+    class Ctx:
+        def __getattr__(self, name):
+            def call(*a, **k):
+                log.append(name)
+                return np.zeros(R.B.GS_CAMERA_GRAD_FLOATS, np.float32) if name == "backward_camera" else None
+            return call
+
+    class Rec(R.GaussianRenderer3D):
+        def __init__(self):
+            z = lambda *s: torch.zeros(s, dtype=torch.float32)
+            self.splatData = R.SplatData3D(means=z(5, 3), scales=z(5, 3), shs=z(5, 12), quaternions=z(5, 4), opacities=z(5, 1))
+            self.nGaussians, self.sh_degree, self.camera, self.ctx = 5, 1, None, Ctx()
+            self.imageData, self.transmittance = z(3, 4, 4), torch.ones((4, 4), dtype=torch.float32)
+            self._splatGrads = R.initGrads(self.splatData)
+            self._grads_lazy_zero = False
+            self._grads = R.grads_struct(self._splatGrads.flat, R.layout_of(self._splatGrads)[0])
+
+        def _begin(self):
+            log.append("<bind>")
+            return self.ctx
+
+        def _set_view(self, camera):
+            log.append("<view>")
+            self.camera = camera
+
+    return Rec(), log
+
+
+def test_train_step_library_call_order():
+    """trainStep in six forms against a recording context: every list is literal; a <bind> stands before every library call."""
+    from gaussiansplat_amd import optim, train as TR
+    gt = np.zeros((3, 4, 4), np.float32)
+    frame = ["<view>", "<bind>", "preprocess", "<bind>", "bin", "<bind>", "bind_outputs", "forward_device", "<bind>", "loss_device"]
+    frame2 = [x for x in frame if x != "bind_outputs"]              # the second step of a renderer: its outputs are bound already
+
+    def run(**kw):
+        r, log = _recording_renderer()
+        loss = TR.getLossFunction((4, 4), 11, 3, renderer=r)
+        stubs = {}
+        if "optimizer" in kw:
+            fused = kw["optimizer"]
+            stubs["optimizer"] = type("Opt", (), dict(fused=fused, renderer=r, step=lambda self: log.append("opt.step"),
+                                                      backward_step=lambda self, dC: log.append("opt.backward_step")))()
+        if kw.get("density"):
+            stubs["density"] = type("Den", (), dict(accumulate=lambda self, rr: log.append("density.accumulate"),
+                                                    after_step=lambda self, rr, opt: log.append("density.after_step")))()
+        if kw.get("pose"):
+            stubs["pose"] = type("Pose", (), dict(camera=synthetic.scene_camera(64, 0), step=lambda self, g: log.append("pose.step")))()
+        rest = {k: v for k, v in kw.items() if k not in ("optimizer", "density", "pose")}
+        TR.trainStep(r, gt, 0.1, loss, want_loss=False, **stubs, **rest)
+        first = list(log)
+        del log[:]
+        TR.trainStep(r, gt, 0.1, loss, want_loss=False, **stubs, **rest)
+        assert log == [x for x in first if x != "bind_outputs"]
+        return first
+
+    assert run() == frame + ["<bind>", "backward", "<bind>", "sgd_step"]
+    assert run(fused_sgd=True) == frame + ["<bind>", "backward_sgd"]
+    assert run(optimizer=False) == frame + ["<bind>", "backward", "opt.step"]
+    assert run(optimizer=False, density=True) == frame + ["<bind>", "backward", "density.accumulate", "opt.step", "density.after_step"]
+    assert run(density=True) == frame + ["<bind>", "backward", "density.accumulate", "<bind>", "sgd_step", "density.after_step"]
+    assert run(optimizer=True) == frame + ["opt.backward_step"]
+    assert run(freeze_model=True) == frame + ["<bind>", "backward"]
+    assert run(optimizer=False, freeze_model=True) == frame + ["<bind>", "backward"]
+    assert run(pose=True) == frame + ["<bind>", "backward", "<bind>", "backward_camera", "pose.step", "<bind>", "sgd_step"]
+    assert run(optimizer=False, pose=True, density=True) == frame + ["<bind>", "backward", "<bind>", "backward_camera", "pose.step",
+                                                                      "density.accumulate", "opt.step", "density.after_step"]
+    assert frame2 == ["<view>", "<bind>", "preprocess", "<bind>", "bin", "<bind>", "forward_device", "<bind>", "loss_device"]

@@ -35,4 +35,4 @@ def timeit(f, k=50):
     torch.cuda.synchronize(); return (time.perf_counter() - t0) / k * 1e3
 print({"loss_and_grad_ms": round(timeit(lambda: lossFunc.value_and_grad(r.imageData, gt, False)), 3)})
 r._begin(); g = r._grads
-print({"sgd_step_ms": round(timeit(lambda: r.ctx.sgd_step(1e-4, g)), 3)}); r._end()
+print({"sgd_step_ms": round(timeit(lambda: r.ctx.sgd_step(1e-4, g)), 3)})
