@@ -3,7 +3,7 @@
     python -m gaussiansplat_amd.build [--force] [--tag NAME -DMACRO=... ...]
 
 --tag NAME builds lib_NAME/libgsplat_hip.so with the given -D macros (e.g. --tag seg1k -DL2_SEG=1024): a variant for a same-box
-A/B run, loaded with GSPLAT_HIP_LIB=.../lib_NAME/libgsplat_hip.so (tools/ab_libs.sh).  The kernel variants that lost their A/B
+A/B run, loaded with GSPLAT_HIP_LIB=.../lib_NAME/libgsplat_hip.so (tools/ab.py --libs lib lib_NAME).  The kernel variants that lost their A/B
 in rounds 1-3 (persistent ticket queues, the reduction tree, the software-pipelined backward, the 64-VGPR forward) and their
 environment switches are no longer in the tree: profiles/HISTORY.md names the commit that last had them.
 

@@ -11,7 +11,7 @@ import torch
 cfg = sys.argv[1] if len(sys.argv) > 1 else "C3"
 # variant tens digit = scheduling (gs_composite.hip: apply_sched_variant): 1 one wave per tile in tile order, 3 (or 0) the frame's
 # longest-first launch order (production); + 1000 the other alpha_cull setting; + 10000 with the two work-counter atomics per tile.
-# Other kernel BODIES are compared as whole libraries: python -m gaussiansplat_amd.build --tag NAME -D... and tools/ab_libs.sh.
+# Other kernel BODIES are compared as whole libraries: python -m gaussiansplat_amd.build --tag NAME -D... and tools/ab.py --libs.
 variants_f = [int(v) for v in (sys.argv[2].split(",") if len(sys.argv) > 2 else ["10", "30"])]
 variants_b = [int(v) for v in (sys.argv[3].split(",") if len(sys.argv) > 3 else ["10", "30"])]
 n, W, H, deg = synthetic.CONFIGS[cfg]

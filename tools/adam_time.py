@@ -14,14 +14,9 @@ Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a call of its
 from __future__ import annotations
 
 import argparse
-import json
-import os
 import statistics
-import sys
 
-import numpy as np
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _timing import emit, event_ms, interleaved
 
 
 def main():
@@ -42,16 +37,10 @@ def main():
     zero = dict(means=0.0, scales=0.0, quaternions=0.0, opacities=0.0, sh_dc=0.0, sh_rest=0.0)
     opt = {k: Adam(r, lr=zero, selective=sel, fused=fu) for k, sel, fu in
            (("dense", False, False), ("selective", True, False), ("fused_dense", False, True), ("fused_selective", True, True))}
-    ev = lambda: torch.cuda.Event(enable_timing=True)
 
     def frame():
         tps = R.preprocess(r, cam); R.compactIdxs(r); R.forward(r, tps)
         return lf.value_and_grad(r.imageData, gt, want_loss=False)[1]
-
-    def timed(fn):
-        s, e = ev(), ev()
-        s.record(); fn(); e.record(); torch.cuda.synchronize()
-        return s.elapsed_time(e)
 
     def bwd(kind):
         dC = frame()
@@ -64,33 +53,27 @@ def main():
                 R.resetGrads(r); R.backward(r, dC); opt[kind.split("_")[1]].step()
             else:
                 opt["fused_" + kind.split("_")[1]].backward_step(dC)
-        return timed(run)
+        return event_ms(run)
 
     def step_only(kind):
         dC = frame()
         R.resetGrads(r); R.backward(r, dC); torch.cuda.synchronize()
-        return timed(lambda: opt[kind].step())
+        return event_ms(lambda: opt[kind].step())
 
     def iteration(kind):
         o = {"sgd": None, "sgd_fused": None, "adam": opt["dense"], "adam_selective": opt["selective"], "adam_fused": opt["fused_dense"],
              "adam_fused_selective": opt["fused_selective"]}[kind]
-        return timed(lambda: TR.trainStep(r, gt, 0.0 if kind == "sgd" else 1e-30, lf, cam, want_loss=False, fused_sgd=kind == "sgd_fused",
-                                          optimizer=o))
+        return event_ms(lambda: TR.trainStep(r, gt, 0.0 if kind == "sgd" else 1e-30, lf, cam, want_loss=False, fused_sgd=kind == "sgd_fused",
+                                             optimizer=o))
 
     variants = [("step_dense", lambda: step_only("dense")), ("step_selective", lambda: step_only("selective"))]
     variants += [("bwd_" + k, (lambda k=k: bwd(k))) for k in ("sgd_unfused", "sgd_fused", "adam_dense_unfused", "adam_selective_unfused",
                                                              "adam_dense_fused", "adam_selective_fused")]
     variants += [("iter_" + k, (lambda k=k: iteration(k))) for k in ("sgd", "sgd_fused", "adam", "adam_selective", "adam_fused",
                                                                     "adam_fused_selective")]
-    for _, fn in variants:                                      # warm-up: view-slot history, allocations
-        fn(); fn()
-    times = {k: [] for k, _ in variants}
-    for _ in range(a.reps):
-        for k, fn in variants:
-            times[k].append(fn())
+    times = interleaved(variants, a.reps, warmup=2)             # warm-up: view-slot history, allocations
     med = {k: statistics.median(v) for k, v in times.items()}
     n_floats = n * (11 + 3 * (deg + 1) ** 2)
-    touched = None
     dC = frame()
     R.resetGrads(r); R.backward(r, dC)
     g = r.splatGrads.flat
@@ -102,11 +85,7 @@ def main():
                step_dense_tbps=7 * 4 * n_floats / (med["step_dense"] * 1e-3) / 1e12,
                fused_selective_over_dense=med["bwd_adam_selective_fused"] / med["bwd_adam_dense_fused"],
                device=torch.cuda.get_device_name(0))
-    print(json.dumps(res, indent=1))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(res, a.out, indent=1)
 
 
 if __name__ == "__main__":

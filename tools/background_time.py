@@ -13,12 +13,8 @@ it must wait at, the blend does.
 from __future__ import annotations
 
 import argparse
-import json
-import os
-import statistics
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _timing import emit, event_ms, interleaved, stat
 
 BG = (1.0, 0.25, 0.6)
 
@@ -37,46 +33,31 @@ def main():
     r = R.getRenderer("GAUSSIAN_3D", (W, H, 3), (16, 16), None, scene, profile_stages=True)
     px = W * H
     src, dst = torch.rand(7 * px // 2, device="cuda"), torch.empty(7 * px // 2, device="cuda")   # 14 B per pixel each way
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
     def frame():
         tps = R.preprocess(r, cam); R.compactIdxs(r); R.forward(r, tps)
         torch.cuda.synchronize()
         return r.ctx.stage_times()["composite_fwd"]
 
-    def copy():
-        torch.cuda.synchronize()
-        e0.record(); dst.copy_(src); e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1)
+    def with_background(bg):
+        r.background = bg
+        frame()                                                 # the colour changed: one frame to settle, the next one counts
+        return frame()
 
-    times = dict(off=[], on=[], copy=[])
-    for rep in range(a.reps + 2):                               # two untimed rounds: view-slot history, allocations, code objects
-        for name, bg in (("off", (0.0, 0.0, 0.0)), ("on", BG)):
-            r.background = bg
-            frame()                                             # the colour changed: one frame to settle, the next one counts
-            t = frame()
-            if rep >= 2:
-                times[name].append(t)
-        c = copy()
-        if rep >= 2:
-            times["copy"].append(c)
+    # two untimed calls of each: view-slot history, allocations, code objects
+    times = interleaved(dict(off=lambda: with_background((0.0, 0.0, 0.0)), on=lambda: with_background(BG),
+                             copy=lambda: event_ms(lambda: dst.copy_(src))), a.reps, warmup=2)
     r.background = (0.0, 0.0, 0.0)
-    stat = lambda v: dict(median=statistics.median(v), min=min(v), max=max(v))
     res = dict(config=a.config, n=n, W=W, H=H, sh_degree=deg, reps=a.reps, unit="ms", device=torch.cuda.get_device_name(0), background=BG,
                blend_bytes=28 * px, copy_bytes=2 * src.numel() * 4,
                composite_fwd=dict(off=stat(times["off"]), on=stat(times["on"])), copy=stat(times["copy"]))
     res["added_median"] = res["composite_fwd"]["on"]["median"] - res["composite_fwd"]["off"]["median"]
     res["added_over_copy"] = res["added_median"] / res["copy"]["median"]
-    print(json.dumps(res, indent=1))
+    emit(res, a.out, indent=1)
     print("composite forward, background off  %.4f ms (min %.4f max %.4f)" % tuple(res["composite_fwd"]["off"][k] for k in ("median", "min", "max")))
     print("composite forward, background on   %.4f ms (min %.4f max %.4f)" % tuple(res["composite_fwd"]["on"][k] for k in ("median", "min", "max")))
     print("device-to-device copy, %d bytes     %.4f ms (min %.4f max %.4f)" % ((res["copy_bytes"],) + tuple(res["copy"][k] for k in ("median", "min", "max"))))
     print("added by the background: %.4f ms = %.2f x the copy" % (res["added_median"], res["added_over_copy"]))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Same-box A/B against an earlier commit's kernels:  tools/build_old_lib.sh COMMIT [TAG=old]  ->  gaussiansplat_amd/lib_TAG/libgsplat_hip.so
 # built from that commit's csrc/ + include/, every file with the flags that commit's own gaussiansplat_amd/build.py gives it (SOURCES); ABI functions added since (the ctypes binding
-# refuses a library without them) get a generated stub.  Then: GSPLAT_HIP_LIB=$PWD/gaussiansplat_amd/lib_TAG/libgsplat_hip.so python3 bench.py ...
+# refuses a library without them) get a generated stub.  Then: tools/ab.py --libs lib_TAG lib, or GSPLAT_HIP_LIB=$PWD/gaussiansplat_amd/lib_TAG/libgsplat_hip.so python3 bench.py ...
+# The one way to build another commit's library: it supersedes build_ref_lib.sh, whose hand-kept copy of the per-file flags had gone stale.
 set -e -o pipefail
 C=$1; TAG=${2:-old}
 W=$(mktemp -d)

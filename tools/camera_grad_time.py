@@ -10,13 +10,9 @@ repetition, after two warm-up frames:
   camera          gs_backward_camera(GS_MEM_DEVICE) on that frame, device events around the call (two launches)
 Median, min and max of `reps`; the share of gaussians with a live row (the others cost the camera kernel one 64-byte row read)."""
 import argparse
-import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _timing import emit, event_ms, stat
 
 
 def run(config, reps):
@@ -47,12 +43,8 @@ def run(config, reps):
         frame()
         torch.cuda.synchronize()
         bwd_ms.append(r.ctx.stage_times()["preprocess_bwd"])
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); r.ctx.backward_camera(out.data_ptr()); e1.record()
-        torch.cuda.synchronize()
-        cam_ms.append(e0.elapsed_time(e1))
+        cam_ms.append(event_ms(lambda: r.ctx.backward_camera(out.data_ptr())))
     g2d = r.ctx.get_array(B.ARR_GRAD2D)
-    stat = lambda v: {"median": statistics.median(v), "min": min(v), "max": max(v)}
     return {"config": config, "gaussians": n, "width": W, "height": H, "sh_degree": deg, "reps": reps,
             "live_row_share": float(np.count_nonzero(g2d.reshape(n, -1).any(axis=1))) / n,
             "finite": bool(np.isfinite(first).all()), "nonzero": bool(first.any()),
@@ -69,11 +61,7 @@ def main():
     import torch
     assert torch.cuda.is_available(), "needs a HIP device"
     res = {"device": torch.cuda.get_device_name(0), "results": [run(c, a.reps) for c in a.configs.split(",")]}
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(json.dumps(res, indent=1) + "\n")
+    emit(res, a.out)
     assert all(x["finite"] and x["nonzero"] for x in res["results"])
 
 

@@ -16,14 +16,11 @@ Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a call of its
 from __future__ import annotations
 
 import argparse
-import json
-import os
 import statistics
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _timing import emit, event_ms as timed, interleaved
 
 
 def main():
@@ -47,17 +44,11 @@ def main():
     opt = Adam(r, lr=zero)
     never = DensityController(scene_extent=1.0, from_iter=10 ** 9, until_iter=10 ** 9, interval=1, opacity_reset_interval=0)
     stats = DensityStats(r)
-    ev = lambda: torch.cuda.Event(enable_timing=True)
 
     def frame():
         tps = R.preprocess(r, cam); R.compactIdxs(r); R.forward(r, tps)
         dC = lf.value_and_grad(r.imageData, gt, want_loss=False)[1]
         R.resetGrads(r); R.backward(r, dC)
-
-    def timed(fn):
-        s, e = ev(), ev()
-        s.record(); fn(); e.record(); torch.cuda.synchronize()
-        return s.elapsed_time(e)
 
     def iteration(with_stats):
         return timed(lambda: TR.trainStep(r, gt, 0.0, lf, cam, want_loss=False, optimizer=opt, density=never if with_stats else None))
@@ -88,12 +79,7 @@ def main():
     variants = [("iter_adam", lambda: iteration(False)), ("iter_adam_accumulate", lambda: iteration(True)), ("accumulate", accumulate),
                 ("decide", lambda: timed(lambda: r.ctx.density_decide(stats.struct(), params, scratch_action.data_ptr()))),
                 ("plan", lambda: timed(lambda: r.ctx.density_plan(act.data_ptr()))), ("restructure", restructure)]
-    for _, fn in variants:                                      # warm-up: view-slot history, allocations
-        fn(); fn()
-    times = {k: [] for k, _ in variants}
-    for _ in range(a.reps):
-        for k, fn in variants:
-            times[k].append(fn())
+    times = interleaved(variants, a.reps, warmup=2)             # warm-up: view-slot history, allocations
     med = {k: statistics.median(v) for k, v in times.items()}
     # the whole densify_and_prune, once per fresh renderer (it changes the model): thresholds from the statistics of four frames
     whole = []
@@ -128,11 +114,7 @@ def main():
                restructure_counts=dict(survivors=counts[0], clones=counts[1], splits=counts[2], pruned=counts[3], n_out=n_out),
                restructure_bytes=restructure_bytes, restructure_tbps=restructure_bytes / (med["restructure"] * 1e-3) / 1e12,
                densify_and_prune_shares=shares, device=torch.cuda.get_device_name(0))
-    print(json.dumps(res, indent=1))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(res, a.out, indent=1)
 
 
 if __name__ == "__main__":

@@ -14,13 +14,9 @@ records for a device copy.  Checks: the HIP d_img against a torch restatement in
 against the einsum form (bits, and the largest difference: the library behind einsum chooses its own order); the HIP dE against the
 float64 sum within P 2^-53 A + 2^-24 |exact| + 2^-149, and bit-equal between the first and the last call."""
 import argparse
-import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _timing import emit, event_ms, interleaved
 
 COPY_TBS = 6.29                     # DESIGN: a device copy on MI355X
 BYTES = {"apply": 24, "backward": 36}
@@ -71,13 +67,7 @@ def main():
         return torch.stack([(E[0, k] * gg[0] + E[1, k] * gg[1]) + E[2, k] * gg[2] for k in range(3)])
 
     def timed(f, w):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.batch):
-            f(w)
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / a.batch * 1e3      # us per call
+        return event_ms(lambda: f(w), a.batch) * 1e3    # us per call
 
     res = {"device": torch.cuda.get_device_name(0), "width": W, "height": H, "pairs": a.pairs, "batch": a.batch, "copy_TBs": COPY_TBS, "cases": {}}
     ok = True
@@ -89,7 +79,8 @@ def main():
         first = dE.cpu().numpy().copy()
         case = {}
         for stage, hip, ref in (("apply", hip_apply, torch_apply), ("backward", hip_backward, torch_backward)):
-            pairs = [(timed(hip, w), timed(ref, w)) for _ in range(a.pairs)]
+            t = interleaved({"hip": lambda: timed(hip, w), "torch": lambda: timed(ref, w)}, a.pairs, warmup=0)
+            pairs = list(zip(t["hip"], t["torch"]))
             nbytes = (BYTES[stage] + (4 if w is not None else 0)) * P
             med = statistics.median(p[0] for p in pairs)
             case[stage] = {"hip_us": [p[0] for p in pairs], "torch_us": [p[1] for p in pairs], "hip_median_us": med,
@@ -114,11 +105,7 @@ def main():
         res["cases"][name] = case
     res["hip_not_slower_in_any_pair"] = all(c[s]["hip_not_slower_in_any_pair"] for c in res["cases"].values() for s in ("apply", "backward"))
     ctx.close()
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(json.dumps(res, indent=1) + "\n")
+    emit(res, a.out)
     assert ok, "the HIP path missed a check (see the JSON)"
 
 

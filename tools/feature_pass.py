@@ -13,12 +13,8 @@ the frame's composite backward under tile_parts = 1, plus the geometry chain.  -
 from __future__ import annotations
 
 import argparse
-import json
-import os
-import statistics
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _timing import emit, event_ms, interleaved, stat
 
 
 def main():
@@ -35,23 +31,15 @@ def main():
     cam = synthetic.scene_camera(W)
     r = R.getRenderer("GAUSSIAN_3D", (W, H, 3), (16, 16), None, scene, profile_stages=True, slab_mode=0, tile_parts=a.tile_parts)
     dC = torch.as_tensor(synthetic.make_dC(W, H, 7)).cuda()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
-    def timed(fn):
-        torch.cuda.synchronize()
-        e0.record(); fn(); e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1)
-
-    stages = dict(composite_fwd=[], composite_bwd=[], preprocess_bwd=[])
-    for rep in range(a.reps + 3):                                 # three untimed frames: view-slot history, allocations, code objects
+    def frame():
         tps = R.preprocess(r, cam); R.compactIdxs(r); R.forward(r, tps)
         R.resetGrads(r); R.backward(r, dC)
         torch.cuda.synchronize()
-        st = r.ctx.stage_times()
-        if rep >= 3:
-            for k in stages:
-                stages[k].append(st[k])
+        return r.ctx.stage_times()
+
+    frames = interleaved({"frame": frame}, a.reps, warmup=3)["frame"]     # three untimed frames: view-slot history, allocations, code objects
+    stages = {k: [st[k] for st in frames] for k in ("composite_fwd", "composite_bwd", "preprocess_bwd")}
     tps = R.preprocess(r, cam); R.compactIdxs(r); R.forward(r, tps)  # the frame the feature calls run over (between its forward and backward)
     z = R.viewDepth(r)
     feat = torch.stack((z, z * z, torch.ones_like(z)), 1).contiguous()
@@ -67,15 +55,9 @@ def main():
         backward_features=lambda: r.ctx.backward_features(feat.data_ptr(), F.data_ptr(), dF.data_ptr(), d_feat.data_ptr(), grads),
         backward_features_no_chain=lambda: r.ctx.backward_features(feat.data_ptr(), F.data_ptr(), dF.data_ptr(), d_feat.data_ptr(), None),
         copy_64n_bytes=lambda: dst.copy_(src))
-    times = {k: [] for k in calls}
-    for rep in range(a.reps + 5):
-        for k, fn in calls.items():                               # interleaved: clock ramps and neighbours hit all alike
-            t = timed(fn)
-            if rep >= 5:
-                times[k].append(t)
+    times = interleaved({k: (lambda fn=fn: event_ms(fn)) for k, fn in calls.items()}, a.reps, warmup=5)
     R.backward(r, dC)                                             # the frame goes on
     torch.cuda.synchronize()
-    stat = lambda v: dict(median=statistics.median(v), min=min(v), max=max(v))
     res = dict(config=a.config, n=n, W=W, H=H, sh_degree=deg, reps=a.reps, unit="ms", device=torch.cuda.get_device_name(0),
                tile_parts_asked=a.tile_parts, tile_parts_of_frame=r.ctx.tile_parts_of_frame(), payload_bytes=128 * n,
                frame={k: stat(v) for k, v in stages.items()}, calls={k: stat(v) for k, v in times.items()})
@@ -83,11 +65,7 @@ def main():
     res["render_minus_composite_fwd"] = m(res["calls"]["render_features"]) - m(res["frame"]["composite_fwd"])
     res["backward_no_chain_minus_composite_bwd"] = m(res["calls"]["backward_features_no_chain"]) - m(res["frame"]["composite_bwd"])
     res["chain"] = m(res["calls"]["backward_features"]) - m(res["calls"]["backward_features_no_chain"])
-    print(json.dumps(res, indent=1))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(res, a.out, indent=1)
 
 
 if __name__ == "__main__":

@@ -20,8 +20,9 @@ tools/isa_same.py (parent = REV) on the two assemblies, which says which instant
 The tool reads waits and register names only; it looks for no particular instruction beyond the loads, moves and waits named above."""
 import argparse, os, re, subprocess, sys, tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "-fno-slp-vectorize"]   # build.py: COMMON + gs_composite.hip's
+from _flags import ROOT, hipcc_flags
+
+FLAGS = hipcc_flags("gs_composite.hip")
 REMARK = re.compile(r"remark:\s+(VGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill): (\d+)")
 
 

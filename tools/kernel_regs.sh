@@ -1,10 +1,11 @@
 #!/bin/bash
 # VGPRs / spills / occupancy of every kernel of one translation unit (hipcc's kernel-resource-usage remarks).
 # usage: tools/kernel_regs.sh gs_composite.hip [extra -D flags]
+set -e -o pipefail
 src=gaussiansplat_amd/csrc/$1
-case "$1" in gs_composite.hip|gs_loss.hip) noslp=-fno-slp-vectorize;; *) noslp=;; esac   # as gaussiansplat_amd/build.py compiles them
+flags=$(python3 "$(dirname "$0")/_flags.py" "$1")                    # as gaussiansplat_amd/build.py compiles it
 shift
-/opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wno-unused-function $noslp "$@" -c "$src" -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 |
+/opt/rocm/bin/hipcc $flags "$@" -c "$src" -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 |
 python3 -c '
 import re, sys
 cur = None; rows = {}

@@ -12,15 +12,13 @@ would not be working).  The 100 k results of the two are also compared bit for b
 from __future__ import annotations
 
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _timing import ROOT, emit, event_ms, interleaved, stat
+
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
@@ -40,42 +38,30 @@ def main():
                   clustered_1m=synthetic.make_scene(1_000_000, 1920, 1080, 0, seed=3, clustered=True)["means"])
     ctx = B.Context()
     ctx.set_stream(torch.cuda.current_stream().cuda_stream or 1)          # torch's current stream; 0, the legacy default stream, is 1 here
-    ev = lambda: torch.cuda.Event(enable_timing=True)
 
-    def timed(fn):
-        s, e = ev(), ev()
-        s.record(); fn(); e.record(); torch.cuda.synchronize()
-        return s.elapsed_time(e)
+    def measure(name, fn):                                                # two warm-up runs, then `reps`
+        s = stat(interleaved({name: lambda: event_ms(fn)}, a.reps, warmup=2)[name])
+        med[name], spread[name] = s["median"], (s["min"], s["max"])
 
     med, spread, results = {}, {}, {}
     for name, pts in clouds.items():
         tp = torch.from_numpy(np.ascontiguousarray(pts, np.float32)).cuda()
         out = torch.empty(tp.shape[0], dtype=torch.float32, device="cuda")
         call = lambda: ctx.knn_mean_dist2(tp.data_ptr(), tp.shape[0], out.data_ptr())
-        for _ in range(2):
-            timed(call)
-        t = [timed(call) for _ in range(a.reps)]
-        med[name], spread[name] = statistics.median(t), (min(t), max(t))
+        measure(name, call)
         results[name] = out.cpu().numpy()
-        print(f"{name}: median {med[name]:.3f} ms (min {min(t):.3f}, max {max(t):.3f})", flush=True)
+        print(f"{name}: median {med[name]:.3f} ms (min {spread[name][0]:.3f}, max {spread[name][1]:.3f})", flush=True)
     same, ratio = None, None
     if not a.skip_brute:
         tp = torch.from_numpy(clouds["uniform_100k"]).cuda()
         brute = {}
         run = lambda: brute.update(r=K.torch_brute(tp))
-        for _ in range(2):
-            timed(run)
-        t = [timed(run) for _ in range(a.reps)]
-        med["torch_brute_100k"], spread["torch_brute_100k"] = statistics.median(t), (min(t), max(t))
+        measure("torch_brute_100k", run)
         same = K.same_bits(results["uniform_100k"], brute["r"])
         ratio = med["torch_brute_100k"] / med["uniform_100k"]
     res = dict(box=a.box, lib=os.path.relpath(B.LIB_PATH, ROOT), reps=a.reps, median_ms=med, min_max_ms=spread, brute_over_hip_100k=ratio, bit_identical_100k=same,
                device=torch.cuda.get_device_name(0))
-    print(json.dumps(res, indent=1))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(res, a.out, indent=1)
     ctx.close()
     if not a.skip_brute and (not same or not ratio > 1.0):
         print("FAILED: the search must equal the brute force and be faster than it at 100 k", file=sys.stderr)

@@ -27,7 +27,8 @@ import subprocess
 import sys
 import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _flags import ROOT, hipcc_flags
+
 COST = [
     (r"v_(exp|rcp|log|rsq|sqrt)_f32", "transcendental", 8.2),
     (r"v_(med3|min3|max3|min|max)_f32|v_cndmask_b32", "select_minmax", 4.2),
@@ -102,8 +103,8 @@ def main():
     src = os.path.join(ROOT, "gaussiansplat_amd", "csrc", "gs_composite.hip")
     with tempfile.TemporaryDirectory() as td:
         s_path = os.path.join(td, "c.s")
-        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-slp-vectorize", "-S", "--cuda-device-only", "-o", s_path, src] + os.environ.get("LOOP_COST_FLAGS", "").split(),
-                       check=True, capture_output=True)
+        subprocess.run(["/opt/rocm/bin/hipcc", *hipcc_flags("gs_composite.hip"), "-S", "--cuda-device-only", "-o", s_path, src]
+                       + os.environ.get("LOOP_COST_FLAGS", "").split(), check=True, capture_output=True)
         asm = open(s_path).read()
     names = re.findall(r"^(_Z20composite_(?:fwd|bwd)_kernel\S*?):", asm, re.M)
     # the production instantiations: early-out, 5 waves, cull; forward <EARLY=1, 5, CULL=1, CLK=0, SLAB=0, SNAP=0>, backward <EARLY=1, 6, DET=0, CULL=1, CLK=0, PAIR=0>
@@ -132,7 +133,6 @@ def main():
             # region spans them: the counts are of all three together, not of one entry
             info["note"] = "spans the forward's 4-, 2- and 1-slot loops: per-entry figures are NOT those of one loop"
         res[k] = info
-    sys.path.insert(0, ROOT)
     import bench
     res["csrc_sha"] = bench.csrc_sha()
     if out:

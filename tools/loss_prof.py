@@ -4,14 +4,12 @@
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python3 tools/loss_prof.py [W H reps]
 
 Prints the hipEvent time per call; the per-kernel split comes from the profiler."""
-import json
-import os
 import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from gaussiansplat_amd import backend as B  # noqa: E402
+from _timing import emit, event_ms
+from gaussiansplat_amd import backend as B
 
 W = int(sys.argv[1]) if len(sys.argv) > 1 else 1920
 H = int(sys.argv[2]) if len(sys.argv) > 2 else 1080
@@ -22,13 +20,8 @@ img = (gt + 0.1 * torch.randn_like(gt)).clamp(0, 1)
 dC = torch.empty_like(img)
 for _ in range(3):
     ctx.loss_device(img.data_ptr(), gt.data_ptr(), dC.data_ptr(), W, H, 3, 0.1, want_loss=False)
-torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 ctx.set_stream(torch.cuda.current_stream().cuda_stream or 1)
-e0.record()
-for _ in range(reps):
-    ctx.loss_device(img.data_ptr(), gt.data_ptr(), dC.data_ptr(), W, H, 3, 0.1, want_loss=False)
-e1.record(); torch.cuda.synchronize()
+ms = event_ms(lambda: ctx.loss_device(img.data_ptr(), gt.data_ptr(), dC.data_ptr(), W, H, 3, 0.1, want_loss=False), batch=reps)
 val = ctx.loss_device(img.data_ptr(), gt.data_ptr(), dC.data_ptr(), W, H, 3, 0.1, want_loss=True)
-print(json.dumps({"W": W, "H": H, "us_per_call": e0.elapsed_time(e1) / reps * 1e3, "loss": val,
-                  "algorithmic_bytes": 4 * 3 * W * H * 3, "note": "reads img + gt, writes dC (12 B per pixel-channel); the five window statistics stay in LDS/registers"}))
+emit({"W": W, "H": H, "us_per_call": ms * 1e3, "loss": val,
+      "algorithmic_bytes": 4 * 3 * W * H * 3, "note": "reads img + gt, writes dC (12 B per pixel-channel); the five window statistics stay in LDS/registers"})

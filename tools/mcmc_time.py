@@ -19,14 +19,9 @@ its own (--reps 5 is plenty there).
 from __future__ import annotations
 
 import argparse
-import json
-import os
 import statistics
-import sys
 
-import numpy as np
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _timing import emit, event_ms as timed, interleaved
 
 MIN_OPACITY = 0.005
 
@@ -46,13 +41,7 @@ def one_size(n, reps):
     opac0 = d.opacities.clone()
     means0 = d.means.clone()
     dead_rows = torch.randperm(n, device="cuda", generator=gen)[:n // 20]
-    ev = lambda: torch.cuda.Event(enable_timing=True)
     r._begin()
-
-    def timed(fn):
-        s, e = ev(), ev()
-        s.record(); fn(); e.record(); torch.cuda.synchronize()
-        return s.elapsed_time(e)
 
     def restore():
         d.opacities.copy_(opac0); d.means.copy_(means0)
@@ -101,23 +90,15 @@ def one_size(n, reps):
     g_struct = r._grads
     c_o, c_s = 0.01 / n, 0.01 / (3 * n)
 
-    def burst(fn, k=20):                                         # k calls behind one another between one pair of events: the pair's own cost and the
-        def go():                                                # first launch's latency are shared by k, what remains is the kernel (or the launch rate)
-            for _ in range(k):
-                fn()
-        return timed(go) / k
+    burst = lambda fn: timed(fn, batch=20)                       # twenty calls behind one another between one pair of events: the pair's own cost and
+                                                                 # the first launch's latency are shared, what remains is the kernel (or the launch rate)
 
     variants = [("noise", lambda: timed(lambda: r.ctx.mcmc_noise(z.data_ptr(), 80.0, 100.0, 0.005))), ("torch_noise", lambda: timed(torch_noise)),
                 ("noise_burst", lambda: burst(lambda: r.ctx.mcmc_noise(z.data_ptr(), 80.0, 100.0, 0.005))),
                 ("regularize_burst", lambda: burst(lambda: r.ctx.mcmc_regularize(g_struct, c_o, c_s))),
                 ("regularize", lambda: timed(lambda: mcmc.regularize(r))), ("torch_regularize", lambda: timed(torch_regularize)),
                 ("relocate", relocate), ("torch_relocate", torch_relocate)]
-    for _, fn in variants:
-        fn(); fn()
-    times = {k: [] for k, _ in variants}
-    for _ in range(reps):
-        for k, fn in variants:
-            times[k].append(fn())
+    times = interleaved(variants, reps, warmup=2)
     med = {k: statistics.median(v) for k, v in times.items()}
     # growth changes n: a fresh renderer per round
     grow_t, torch_grow_t = [], []
@@ -149,11 +130,7 @@ def main():
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     res = dict(device=torch.cuda.get_device_name(0), sizes=[one_size(int(s), a.reps) for s in a.sizes.split(",")])
-    print(json.dumps(res, indent=1))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(res, a.out, indent=1)
 
 
 if __name__ == "__main__":

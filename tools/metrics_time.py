@@ -13,13 +13,9 @@ stream; a call's time is the batch's over `batch`.  Variants:
 Median, min and max per call; ratio = metrics median over loss median.  The sums of the first and the last metrics call are compared
 bit for bit, and with the float64 NumPy restatement kept here (separable, another summation order) where --check is given."""
 import argparse
-import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _timing import emit, event_ms, interleaved, stat
 
 
 def inputs(Cn, H, W, seed=7):
@@ -81,21 +77,11 @@ def main():
     variants["metrics"]()
     torch.cuda.synchronize()
     first = sums.cpu().numpy().copy()
-    ms = {k: [] for k in variants}
-    for _ in range(a.reps):
-        for k, f in variants.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.batch):
-                f()
-            e1.record()
-            torch.cuda.synchronize()
-            ms[k].append(e0.elapsed_time(e1) / a.batch)
+    ms = interleaved({k: (lambda f=f: event_ms(f, a.batch)) for k, f in variants.items()}, a.reps, warmup=0)
     variants["metrics"]()
     torch.cuda.synchronize()
     last = sums.cpu().numpy().copy()
     fin = B.metrics_finish(last)
-    stat = lambda v: {"median": statistics.median(v), "min": min(v), "max": max(v)}
     res = {"device": torch.cuda.get_device_name(0), "width": W, "height": H, "channels": Cn, "reps": a.reps, "batch": a.batch,
            "ms_per_call": {k: stat(v) for k, v in ms.items()},
            "ratio_metrics_over_loss": statistics.median(ms["metrics"]) / statistics.median(ms["loss"]),
@@ -105,11 +91,7 @@ def main():
     if a.check:
         res["ssim_minus_float64_restatement"] = float(fin[B.METRIC_SSIM]) - restate_mean_ssim(img, gt)
     ctx.close()
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(json.dumps(res, indent=1) + "\n")
+    emit(res, a.out)
     assert res["bitwise_reproducible"] and np.isfinite(last).all()
     assert not a.check or abs(res["ssim_minus_float64_restatement"]) <= 1e-10
 

@@ -12,12 +12,8 @@ narrower model.
 from __future__ import annotations
 
 import argparse
-import json
-import os
-import statistics
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _timing import emit, interleaved, stat
 
 
 def main():
@@ -51,30 +47,25 @@ def main():
 
     degrees = list(range(deg, -1, -1))
     forms = ("overwrite", "adam_fused")
-    times = {(d, f): ([], []) for d in degrees for f in forms}
-    for rep in range(a.reps + 2):                               # two untimed rounds: view-slot history, allocations, code objects
-        for d in degrees:
-            r.active_sh_degree = d
-            for f in forms:
-                frame(f)                                        # the degree changed: one frame to settle, the next one counts
-                p, b = frame(f)
-                if rep >= 2:
-                    times[d, f][0].append(p); times[d, f][1].append(b)
+
+    def at_degree(d, f):
+        r.active_sh_degree = d
+        frame(f)                                                # the degree changed: one frame to settle, the next one counts
+        return frame(f)
+
+    # two untimed calls of each: view-slot history, allocations, code objects
+    pairs = interleaved({(d, f): (lambda d=d, f=f: at_degree(d, f)) for d in degrees for f in forms}, a.reps, warmup=2)
+    times = {k: list(zip(*v)) for k, v in pairs.items()}        # (preprocess samples, per-gaussian backward samples)
     r.active_sh_degree = -1
-    stat = lambda v: dict(median=statistics.median(v), min=min(v), max=max(v))
     res = dict(config=a.config, n=n, W=W, H=H, stored_degree=deg, reps=a.reps, unit="ms", device=torch.cuda.get_device_name(0),
                stages={f"active{d}": {f: dict(preprocess=stat(times[d, f][0]), preprocess_bwd=stat(times[d, f][1])) for f in forms}
                        for d in degrees})
-    print(json.dumps(res, indent=1))
+    emit(res, a.out, indent=1)
     print("active  form        preprocess (median ms)  per-gaussian backward (median ms)")
     for d in degrees:
         for f in forms:
             s = res["stages"][f"active{d}"][f]
             print(f"{d:6d}  {f:<10s}  {s['preprocess']['median']:22.4f}  {s['preprocess_bwd']['median']:33.4f}")
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
 
 
 if __name__ == "__main__":

@@ -12,14 +12,8 @@ window ending in a synchronise (median of `reps` after a warm-up of each):
   factored  the plain colour-factored path: gs_color_grads_pack + gs_sh_grads_from_views over dense slots
 All three must leave the same d_shs, bit for bit; the script fails otherwise."""
 import argparse
-import json
-import os
-import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _timing import emit, event_ms, host_clock_ms, interleaved, stat
 
 
 def main():
@@ -80,27 +74,18 @@ def main():
         torch.cuda.synchronize()
         results[name] = d_shs.cpu().numpy().view(np.uint32).copy()
     same = all(np.array_equal(results["factored"], v) for v in results.values())
-    ev_ms = {k: [] for k in variants}
-    host_ms = {k: [] for k in variants}
-    for _ in range(a.reps):
-        for name, f in variants.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            e0.record(); f(); e1.record()
-            torch.cuda.synchronize()
-            host_ms[name].append((time.perf_counter() - t0) * 1e3)
-            ev_ms[name].append(e0.elapsed_time(e1))
+
+    def both_clocks(f):                                                    # the host clock runs around the events' window
+        ev = []
+        host = host_clock_ms(lambda: ev.append(event_ms(f)), k=1)
+        return ev[0], host
+
+    both = interleaved({k: (lambda f=f: both_clocks(f)) for k, f in variants.items()}, a.reps, warmup=0)
     out = {"config": a.config, "gaussians": n, "views": V, "reps": a.reps, "touched_share": float(counts.cpu()[0]) / n,
            "same_bits": bool(same),
-           "device_events_ms": {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in ev_ms.items()},
-           "host_clock_ms": {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in host_ms.items()}}
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(json.dumps(out, indent=1) + "\n")
+           "device_events_ms": {k: stat([e for e, _ in v]) for k, v in both.items()},
+           "host_clock_ms": {k: stat([h for _, h in v]) for k, v in both.items()}}
+    emit(out, a.out)
     assert same, "the three paths left different d_shs"
 
 
