@@ -42,6 +42,8 @@ SOURCES = {
     # no SLP vectoriser: a v_pk_*_f32 issues at the cost of two plain operations on gfx950, and forming the pairs costs moves
     # (C3 1.328 -> 1.294 ms, C5 4.38 -> 4.26, same box, profiles/r04q_ab_no_slp.log; round 2's kernels had measured the opposite)
     "gs_composite.hip": ["-fno-slp-vectorize"],
+    # the launch orders, the summing kernels and the clock probe: once part of gs_composite.hip, built as that unit is so that their code stays what it was
+    "gs_order.hip": ["-fno-slp-vectorize"],
     # the SLP vectoriser turns the stencil into v_pk_* (no faster than two plain ops on gfx950) plus 270 register moves per loop body
     "gs_loss.hip": ["-fno-slp-vectorize"],
     # Adam: the per-float update must round exactly as documented in include/gsplat.h (and as gs_sh_bwd_kernel's fused form does)

@@ -93,7 +93,10 @@ int gs_create(gs_ctx **out, int device, const gs_config *cfg) {
     if ((e = hipHostMalloc((void **)&c->pinned, sizeof(PinnedWords), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess) { delete c; return hipfail(nullptr, e, "hipHostMalloc"); }
     if ((e = hipHostMalloc((void **)&c->pinned_split, sizeof(uint32_t) * 2 * (GS_MAX_VIEW_SLOTS + 1), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess) {
         (void)hipGetLastError(); c->pinned_split = nullptr;              // (speed only: without it every order counts as "may hold split tiles")
-    } else std::memset(c->pinned_split, 0, sizeof(uint32_t) * 2 * (GS_MAX_VIEW_SLOTS + 1));
+    } else {
+        std::memset(c->pinned_split, 0, sizeof(uint32_t) * 2 * (GS_MAX_VIEW_SLOTS + 1));
+        for (size_t k = 0; k < c->slots.size(); ++k) c->slots[k].split_words = c->pinned_split + 2 * k;      // each slot knows its own two words
+    }
     for (auto &pair : c->ev)
         for (hipEvent_t &ev : pair) if ((e = hipEventCreate(&ev)) != hipSuccess) { delete c; return hipfail(nullptr, e, "hipEventCreate"); }
     if ((e = hipEventCreateWithFlags(&c->ev_count, hipEventDisableTiming | hipEventReleaseToSystem)) != hipSuccess) { delete c; return hipfail(nullptr, e, "hipEventCreate"); }

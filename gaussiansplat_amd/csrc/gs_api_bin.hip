@@ -29,8 +29,7 @@ static void plan_rounds(const gs_ctx *c, gs_ctx::BinPlan &p) {
     int R = 1;
     if (c->cfg.slab_fractions[0] > 0.0f) {                                  // tests / experiments: explicit fractions
         for (int k = 0; k < 3 && k + 1 < GS_MAX_ROUNDS && c->cfg.slab_fractions[k] > 0.0f; ++k) { f[k] = c->cfg.slab_fractions[k]; R = k + 2; }
-    } else if (c->cfg.slab_mode == 1 && c->walked_ratio >= 0.0 && c->walked_ratio < slab_max_ratio(c)) {
-        const double rho = c->walked_ratio;
+    } else if (const double rho = c->feedback.walked_ratio(); c->cfg.slab_mode == 1 && rho >= 0.0 && rho < slab_max_ratio(c)) {
         f[0] = std::min(0.9, std::max(0.02, 2.0 * rho + 0.02));
         f[1] = std::min(0.95, std::max(f[0] + 0.05, 6.0 * rho + 0.05));
         R = 3;
@@ -97,9 +96,7 @@ static int two_level_count(gs_ctx *c, const uint32_t *perm_slab, int64_t n_all, 
     GsBin3L1 b = two_level_args(c, perm_slab, n_all, nr, sdone, 0, 0);
     if (to_host) {                                                          // where settle_totals reads them: the pinned copy of the counter block
         b.host_totals = c->pinned->counters.totals; b.host_walked = c->pinned->counters.work; b.walked_src = c->counters.as<uint32_t>();
-        // the previous forward's walked entries, per tile (valid only if that forward ran on this grid: prev_counters_valid)
-        if (!c->counters_here()) c->prev_counters_valid = false;
-        b.tile_walked = c->prev_counters_valid ? c->last_walked : nullptr; b.n_tile_walked = (int)c->ntiles();
+        b.tile_walked = c->feedback.previous_walk(c->grid_key()); b.n_tile_walked = (int)c->ntiles();   // the previous forward's walked entries, per tile
     }
     HIPCHK(c, gs_bin3_l1_count(b, c->stream));
     return GS_OK;
@@ -148,7 +145,7 @@ static int two_level_lists(gs_ctx *c, const uint32_t *perm_slab, int64_t n_all, 
 #define GS_LIST_CAP_MAX_RATIO 0.15
 static int list_cap_source(gs_ctx *c, const uint32_t **out) {
     *out = nullptr;
-    const int64_t ntiles = c->ntiles(), grid = c->grid_key();
+    const int64_t ntiles = c->ntiles();
     if (c->bin.path != Path::TWO_LEVEL || c->bin.n_rounds != 1 || c->cfg.list_cap == 1 || !(c->cfg.t_min > 0.0f) || ntiles <= 0) return GS_OK;
     if (c->cfg.debug_flags & GS_DEBUG_TINY_CAPS) {          // tests: every tile capped at the minimum, whatever it walked
         if (c->zero_tiles.cap < sizeof(uint32_t) * (size_t)ntiles) {
@@ -160,11 +157,8 @@ static int list_cap_source(gs_ctx *c, const uint32_t **out) {
     }
     // Engages where it pays (measured, profiles/r04b_kernel_stats_*): the write pass is bound by its entries only when most of them
     // are never walked -- C5 (6 % walked): 591 -> 129 us; at C3 (28 % walked) the pass goes 45 -> 37 us and the cap pass costs that.
-    if (c->cfg.list_cap != 2 && (ntiles <= c->wave_slots || !(c->walked_ratio >= 0.0 && c->walked_ratio < GS_LIST_CAP_MAX_RATIO))) return GS_OK;
-    const int k = order_index(c);
-    if (k == GS_MAX_VIEW_SLOTS && c->cfg.schedule != 4) return GS_OK;          // frames without a slot: history only under schedule 4
-    if (c->slots[k].walked_grid != grid || !c->slots[k].walked().p) return GS_OK;
-    *out = c->slots[k].walked().as<uint32_t>();
+    if (c->cfg.list_cap != 2 && (ntiles <= c->wave_slots || !(c->feedback.walked_ratio() >= 0.0 && c->feedback.walked_ratio() < GS_LIST_CAP_MAX_RATIO))) return GS_OK;
+    if (const gs_ctx::ViewSlot *vs = c->history_slot()) *out = vs->history(c->grid_key()).walk;   // (frames without a slot: history only under schedule 4)
     return GS_OK;
 }
 
@@ -255,16 +249,11 @@ static void dsort_feedback(gs_ctx *c) {
 }
 
 // The frame's totals have arrived on the host, however they travelled (the pinned counter block; the radix paths' copies): coarse instances listed, fine
-// instances of round 0's slab and of all n; walked_prev: the u64 sum of the previous forward's walk, read only while prev_counters_valid says it was sent.
+// instances of round 0's slab and of all n; walked_prev: the u64 sum of the previous forward's walk, read only when one was sent (WalkFeedback::sum_arrived).
 static int totals_arrived(gs_ctx *c, uint32_t coarse, uint32_t fine_slab, uint32_t fine_all, const uint32_t *walked_prev) {
     if (fine_all == 0xFFFFFFFFu)
         return fail(c, GS_ERR_UNSUPPORTED, "gs_bin: more than 2^32 - 2 tile instances (32-bit list offsets); reduce the scene or the image");
-    if (c->prev_counters_valid && c->prev_n_inst > 0) {
-        unsigned long long w = 0;
-        std::memcpy(&w, walked_prev, sizeof(w));
-        c->walked_ratio = (double)w / (double)c->prev_n_inst;
-    }
-    c->prev_counters_valid = false;
+    c->feedback.sum_arrived(walked_prev);
     c->n_inst = (int64_t)fine_all;
     c->n_coarse = (int64_t)coarse;
     c->round_gen[0] = c->bin.n_rounds > 1 ? (int64_t)fine_slab : c->n_inst;
@@ -291,9 +280,9 @@ int settle_totals(gs_ctx *c, bool *redo, bool may_relist) {
     if (int rc = totals_arrived(c, coarse, fine_slab, h.totals[2], h.work)) return rc;
     if (!c->live.spec_lists || c->live.speculation_held(coarse, fine_slab)) return GS_OK;
     if (!may_relist) { c->fall_back(gs_ctx::Stage::PREPROCESSED); return GS_OK; }                  // the frame is being abandoned (a new gs_preprocess / gs_bin follows)
-    // a list outgrew its buffer: nothing was listed (all ranges empty).  Grow and list again with the real totals -- in FULL: the caps'
-    // source is the slot's walked array, and the forward that just ran on the empty lists has overwritten it with zeros (rare frame:
-    // a model that outgrew its buffers; full lists are the fast choice there)
+    // a list outgrew its buffer: nothing was listed (all ranges empty).  Grow and list again with the real totals -- in FULL.  (The caps'
+    // source would still stand: the slot's walk is double buffered, and the forward that just ran on the empty lists wrote the OTHER
+    // buffer.  But this is a rare frame -- a model that outgrew its buffers -- and full lists are the fast choice there)
     HIPCHK(c, c->ids.ensure(sizeof(uint32_t) * (size_t)(c->n_inst ? c->n_inst : 1)));
     c->live.relist_in_full();
     {
@@ -351,8 +340,7 @@ static int bin_small(gs_ctx *c) {
     a.n = (int)c->n; a.gx = c->gx; a.gy = c->gy; a.ntiles = (int)nt;
     a.ranges = c->ranges.as<uint32_t>(); a.ids = c->ids.as<uint32_t>(); a.totals = c->bin_totals();
     a.host_totals = c->pinned->counters.totals; a.host_walked = c->pinned->counters.work; a.walked_src = c->counters.as<uint32_t>();
-    if (!c->counters_here()) c->prev_counters_valid = false;
-    a.tile_walked = c->prev_counters_valid ? c->last_walked : nullptr; a.n_tile_walked = (int)nt;
+    a.tile_walked = c->feedback.previous_walk(c->grid_key()); a.n_tile_walked = (int)nt;
     {   // the rows the composite backward accumulates into (64 B per gaussian; nothing touches them between here and that kernel)
         HIPCHK(c, c->g2d.ensure(c->g2d_bytes()));                          // (this path has n >= 1: every row of the model, no more)
         a.zero = c->g2d.as<uint4>(); a.zero_words16 = c->g2d_bytes() / sizeof(uint4);
@@ -435,9 +423,8 @@ static int bin_radix(gs_ctx *c) {
     // ranges) is enqueued BEFORE the host waits, so the GPU stays busy while the host wakes up and launches the instance passes.
     HIPCHK(c, hipMemcpyAsync(&h->readback[0], c->offsets.as<uint32_t>() + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&h->readback[1], c->offsets.as<uint32_t>() + n0, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (!c->counters_here()) c->prev_counters_valid = false;
-    if (c->prev_counters_valid) {
-        HIPCHK(c, gs_launch_sum_tiles(c->last_walked, c->tile_work.as<uint32_t>(), (int)c->ntiles(), c->counters.as<unsigned long long>(), c->stream));
+    if (const uint32_t *walk = c->feedback.previous_walk(c->grid_key())) {
+        HIPCHK(c, gs_launch_sum_tiles(walk, c->tile_work.as<uint32_t>(), (int)c->ntiles(), c->counters.as<unsigned long long>(), c->stream));
         HIPCHK(c, hipMemcpyAsync(h->walked_prev, c->counters.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipEventRecord(c->ev_count, c->stream));

@@ -7,21 +7,17 @@ using Stage = gs_ctx::Stage;
 using BackwardPlan = gs_ctx::BackwardPlan;
 using Update = BackwardPlan::Update;
 
-// Launch order of the frame's forward (gs_config.schedule 3 / 4): what the last forward under the same view slot measured, else
-// (schedule 4) what this ctx's previous slot-less forward measured; null = no history: tile order.  *split: the order's split-count word.
-static const uint32_t *forward_order(gs_ctx *c, const uint32_t **split) {
-    const int64_t ntiles = c->ntiles();
-    if (!lpt_schedule(c) || ntiles <= 0 || ntiles > GS_LPT_MAX_TILES) return nullptr;
-    const int k = order_index(c);
-    if (k == GS_MAX_VIEW_SLOTS && c->cfg.schedule != 4) return nullptr;
-    gs_ctx::ViewSlot &vs = c->slots[k];
-    if (vs.tiles != c->grid_key()) return nullptr;                        // (the order's length and groups belong to one grid)
-    if (c->order_pending) {                                              // (long complete by now; an event wait on the stream costs nothing)
-        if (hipStreamWaitEvent(c->stream, c->ev_order, 0) != hipSuccess) return nullptr;
-        c->order_pending = false;
-    }
-    *split = c->split_word(k, vs.sel);
-    return vs.order[vs.sel].as<uint32_t>();
+using History = gs_ctx::ViewSlot::History;
+
+// the frame's launches run over a launch order (gs_config.schedule 3 / 4; the order kernel refuses grids beyond 8K-class images)
+static bool frame_has_orders(const gs_ctx *c) { return c->lpt_schedule() && c->ntiles() > 0 && c->ntiles() <= GS_LPT_MAX_TILES; }
+// Launch order of the frame's forward: what the last forward under the same view slot measured, else (schedule 4) what this ctx's previous
+// slot-less forward measured (h: the history slot's, gs_forward); null = no history: tile order.  A lookup: await_order_kernel comes first.
+static const uint32_t *forward_order(const gs_ctx *c, const History &h) { return frame_has_orders(c) ? h.order : nullptr; }
+// the main stream waits for the order kernel in flight, if any (long complete by now; an event wait on the stream costs nothing)
+static int await_order_kernel(gs_ctx *c) {
+    if (c->order_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_order, 0)); c->order_pending = false; }
+    return GS_OK;
 }
 
 // pixel parts (waves per tile, each owning 4 / parts of its pixel strips) that fit the wave slots when a tile runs as `units` waves already
@@ -33,8 +29,9 @@ static int parts_that_fit(const gs_ctx *c, int units) {
 // In which mode do this frame's composite launches run, and why: decided HERE, once per frame, from the config, the grid, the lists as
 // gs_bin left them, the forward's launch order and the walk history of the view slot (null: none on this grid).  Beside it: lpt_schedule
 // and lpt_front (gs_ctx.h), which are properties of ctx and grid -- they fix the layout of every order of a slot.
-static void plan_frame(gs_ctx *c, const uint32_t *order, const uint32_t *order_split, const uint32_t *hist) {   // order_split: the order's word of pinned_split
+static void plan_frame(gs_ctx *c, const History &h) {
     gs_ctx::FramePlan p;
+    const uint32_t *const order = forward_order(c, h), *const hist = h.walk;
     const int want = c->cfg.tile_parts;
     // launches that composite whole tiles, one wave each: no early-out, slab rounds, capped lists
     const bool whole = !(c->cfg.t_min > 0.0f) || c->bin.n_rounds > 1 || c->live.frame_capped;
@@ -42,15 +39,15 @@ static void plan_frame(gs_ctx *c, const uint32_t *order, const uint32_t *order_s
     p.order = p.bwd_order = order;
     // The backward runs in the forward's order while the order kernel works beside it, on the side stream, for the slot's next frame; else
     // (a slot's first frame; no side stream) it waits for that kernel and takes the fresh order: build_frame_order then sets bwd_order
-    p.side = order && use_side_stream(c);
-    p.front = lpt_front(c);
+    p.side = order && c->use_side_stream();
+    p.front = c->lpt_front();
     p.split = p.front > 0 && p.parts == 1 && c->bin.n_rounds == 1;            // heavy tiles run as the orders' split entries say (full lists: asked at every launch, frame_capped is live)
     // neither snapshot mode looks at cfg.deterministic, so deterministic gradients depend on the slot's history
-    const bool may_split = !order_split || *order_split != 0u;            // (the order kernel's count; 0xFFFFFFFF: not reported yet)
-    if (order && p.split && c->snap_walked.p && may_split) {
+    const bool may_split = !h.order_split || *h.order_split != 0u;        // (the order kernel's count; 0xFFFFFFFF: not reported yet)
+    if (order && p.split && c->snap_walked.buf.p && may_split) {
         p.snap = Snap::HEAVY;                                              // ... and leave snapshots for the list segments of their backward
-        p.snap_walked = c->snap_walked.as<uint32_t>() + (size_t)c->snap_parity * GS_SEG_SLOTS;
-    } else if (hist && want == 0 && p.parts > 1 && !lpt_schedule(c) && c->kind == 0 && c->ntiles() > 0) {
+        p.snap_walked = c->snap_walked.of_frame();
+    } else if (hist && want == 0 && p.parts > 1 && !c->lpt_schedule() && c->kind == 0 && c->ntiles() > 0) {
         // small grids (the automatic choice gave pixel parts: full lists, one round, at most half as many tiles as wave slots; no launch order):
         // with the slot's previous walk at hand EVERY tile's backward runs as list segments instead, the forward's waves leave the
         // snapshots.  Two segments, and as many pixel parts on top as still fit the wave slots (C1: 4 x 2 waves per tile; C2: 1 x 2)
@@ -82,7 +79,7 @@ GsCompositeArgs composite_args(gs_ctx *c, bool bwd, int r, bool debug) {
     }
     a.ranges = r == 0 ? c->ranges.as<uint32_t>() : c->ranges_r[r].as<uint32_t>(); a.ids = c->ids.as<uint32_t>() + c->round_ids_off[r];
     if (bwd) c->rows_mut(c->g2d).into(a);
-    a.tile_order = bwd || debug ? p.bwd_order : p.order; a.order_len = a.tile_order ? lpt_order_entries(c) : 0;
+    a.tile_order = bwd || debug ? p.bwd_order : p.order; a.order_len = a.tile_order ? c->lpt_order_entries() : 0;
     a.parts = bwd ? p.bwd_parts : p.parts;
     a.split_ok = a.tile_order && p.split && !c->live.frame_capped;
     if (c->live.frame_capped && c->bin.n_rounds == 1) {
@@ -95,7 +92,7 @@ GsCompositeArgs composite_args(gs_ctx *c, bool bwd, int r, bool debug) {
     if (bwd ? p.bwd_segments : !debug) {                                   // snapshots: the forward leaves them, the backward starts its list segments from them
         if (p.snap == Snap::ALL) { a.snap = c->snap.as<float>(); a.seg_hist = p.seg_hist; a.seg_n = p.seg_n; }
         if (p.snap == Snap::HEAVY && a.split_ok) {
-            a.snap = c->snap.as<float>(); a.seg_len = order_seg_len(c, a.tile_order); a.front = p.front; a.snap_walked = p.snap_walked;
+            a.snap = c->snap.as<float>(); a.seg_len = c->order_seg_len(a.tile_order); a.front = p.front; a.snap_walked = p.snap_walked;
         }
     }
     return a;
@@ -107,40 +104,39 @@ GsCompositeArgs composite_args(gs_ctx *c, bool bwd, int r, bool debug) {
 // the backward waits for it: it is its only source of a longest-first order.
 static int build_frame_order(gs_ctx *c) {
     gs_ctx::FramePlan &p = c->plan;
-    const int64_t ntiles = c->ntiles();
-    if (!lpt_schedule(c) || ntiles <= 0 || ntiles > GS_LPT_MAX_TILES) return GS_OK;
-    const int k = order_index(c);
-    gs_ctx::ViewSlot &vs = c->slots[k];
+    if (!frame_has_orders(c)) return GS_OK;
+    gs_ctx::ViewSlot &vs = c->storage_slot();
     const int dst = vs.order_dst(p.order != nullptr);
     DevBuf &ob = vs.order[dst];
-    HIPCHK(c, ob.ensure(sizeof(uint32_t) * ((size_t)lpt_order_entries(c) + GS_SEG_SLOTS + 16)));
+    HIPCHK(c, ob.ensure(sizeof(uint32_t) * ((size_t)c->lpt_order_entries() + GS_SEG_SLOTS + 16)));
     // heavy tiles: the order kernel also sizes the backward's list segments (from what this forward walked) and re-arms the walked
     // lengths of the NEXT frame's snapshots (this frame's are being read by its backward)
-    const uint32_t *walked = p.front > 0 ? c->last_walked : nullptr;
-    uint32_t *rearm = nullptr, *nsplit = c->split_word(k, dst);
+    const uint32_t *walked = p.front > 0 ? c->feedback.walk : nullptr;
+    uint32_t *rearm = nullptr, *nsplit = vs.split_word(dst);
     if (nsplit) *nsplit = 0xFFFFFFFFu;                                     // unknown until the order kernel has stored its count
     if (p.front > 0) {
-        if (!c->snap_walked.p) {
-            HIPCHK(c, c->snap_walked.ensure(sizeof(uint32_t) * 2 * GS_SEG_SLOTS));
-            HIPCHK(c, hipMemsetAsync(c->snap_walked.p, 0, sizeof(uint32_t) * 2 * GS_SEG_SLOTS, c->stream));
+        if (!c->snap_walked.buf.p) {
+            HIPCHK(c, c->snap_walked.buf.ensure(sizeof(uint32_t) * 2 * GS_SEG_SLOTS));
+            HIPCHK(c, hipMemsetAsync(c->snap_walked.buf.p, 0, sizeof(uint32_t) * 2 * GS_SEG_SLOTS, c->stream));
         }
-        rearm = c->snap_walked.as<uint32_t>() + (size_t)(c->snap_parity ^ 1) * GS_SEG_SLOTS;
+        rearm = c->snap_walked.to_rearm();
     }
+    if (int rc = await_order_kernel(c)) return rc;                         // (never two in flight; gs_forward has waited already)
     if (p.side) {
-        if (c->order_pending) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_order, 0));      // (never two in flight)
         HIPCHK(c, hipEventRecord(c->ev_main, c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0));
     }
     HIPCHK(c, gs_launch_tile_lpt_order(c->tile_work.as<uint32_t>(), 0, c->gx, c->gy, ob.as<uint32_t>(), p.side ? c->side : c->stream, nullptr, 0, p.front,
-                                       lpt_split_div(c), walked, rearm, nsplit));
+                                       c->lpt_split_div(), walked, rearm, nsplit));
     if (p.side) {
         HIPCHK(c, hipEventRecord(c->ev_order, c->side));
         c->order_pending = true;
         vs.order_written(dst, c->grid_key());
-        // (tile_work is rewritten by the next forward of this ctx: it waits for ev_order first, see forward_order / gs_forward)
+        // (tile_work is rewritten by the next forward of this ctx: it waits for ev_order first, await_order_kernel in gs_forward)
     } else {
         p.bwd_order = ob.as<uint32_t>();
         // with p.order (no side stream) the fresh order sits in order[dst] but sel is not flipped: the slot's forwards keep the old one
+        // (the single place a slot's order is written: a fix flips here, order_written(dst, ...))
         vs.order_written(vs.sel, c->grid_key());
     }
     return GS_OK;
@@ -173,7 +169,7 @@ int gs_set_view_slot(gs_ctx *c, int32_t slot) {
 }
 
 // the composite launch of round r of the frame (r = 0 unless the frame is binned in depth slabs)
-static int enqueue_forward_round(gs_ctx *c, int r) {
+static int enqueue_forward_round(gs_ctx *c, int r, uint32_t *walk_dst) {        // walk_dst: where the frame's per-tile walk goes
     gs_ctx::FramePlan &p = c->plan;
     if (p.snap != Snap::NONE && !c->live.frame_capped) {                         // this launch leaves snapshots (composite_args)
         HIPCHK(c, c->snap.ensure(sizeof(float) * (p.snap == Snap::ALL ? (size_t)c->ntiles() * (size_t)(p.seg_n - 1) * 4 * 256 : (size_t)GS_SEG_SLOTS * GS_SEG_SNAP_FLOATS)));
@@ -181,7 +177,7 @@ static int enqueue_forward_round(gs_ctx *c, int r) {
     }
     GsCompositeArgs a = composite_args(c, false, r);
     a.resume = r > 0; a.final_round = r == c->bin.n_rounds - 1;
-    a.tile_work = c->tile_work.as<uint32_t>(); a.tile_walked = const_cast<uint32_t *>(c->last_walked);
+    a.tile_work = c->tile_work.as<uint32_t>(); a.tile_walked = walk_dst;
     p.bwd_segments = a.snap && (p.side || !p.order);                       // snapshots left, and (HEAVY) the backward takes the order they belong to
     if (a.snap) { a.bw_walked = c->tile_walked_b.as<uint32_t>(); a.bw_work = c->tile_work_b.as<uint32_t>(); }   // (its waves zero the segmented tiles' words)
     if (c->bin.n_rounds > 1) { a.tile_pos = c->tile_pos.as<uint32_t>(); a.tile_done = c->tile_done.as<uint8_t>(); a.tile_dead = c->tile_dead.as<unsigned long long>(); }
@@ -209,18 +205,12 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
     }
     HIPCHK(c, c->counters.ensure(GS_COUNTER_BYTES));
     HIPCHK(c, c->tile_work.ensure(sizeof(uint32_t) * nt1));
-    c->counters_grid = c->grid_key();
-    // the per-tile walked counts go to the frame's view slot (its next frame's list caps and segment lengths), else to the ctx's own array
-    gs_ctx::ViewSlot *vs = order_index(c) < GS_MAX_VIEW_SLOTS || c->cfg.schedule == 4 ? &c->slots[order_index(c)] : nullptr;
-    const uint32_t *hist = nullptr;                                        // the slot's previous walk of this grid
-    if (vs) {
-        HIPCHK(c, vs->walk_dst().ensure(sizeof(uint32_t) * nt1));
-        if (vs->walked_grid == c->counters_grid) hist = vs->walked().as<uint32_t>();
-        c->last_walked = vs->walk_dst().as<uint32_t>();
-    } else {
-        HIPCHK(c, c->tile_walked.ensure(sizeof(uint32_t) * nt1));
-        c->last_walked = c->tile_walked.as<uint32_t>();
-    }
+    // the per-tile walked counts go to the frame's history slot (its next frame's list caps and segment lengths), else to the ctx's own array
+    const int64_t grid = c->grid_key();
+    gs_ctx::ViewSlot *const vs = c->history_slot();
+    DevBuf &walk_buf = vs ? vs->walk_dst() : c->feedback.own;
+    HIPCHK(c, walk_buf.ensure(sizeof(uint32_t) * nt1));
+    uint32_t *const walk_dst = walk_buf.as<uint32_t>();
     const int R = c->bin.n_rounds;
     if (R > 1) {
         HIPCHK(c, c->tile_pos.ensure(sizeof(uint32_t) * nt1));
@@ -228,10 +218,9 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
         HIPCHK(c, c->tile_dead.ensure(sizeof(unsigned long long) * 4 * nt1));
         HIPCHK(c, hipMemsetAsync(c->tile_pos.p, 0, sizeof(uint32_t) * ntiles, c->stream));
     }
-    c->snap_parity ^= 1;                                                   // (the order kernel behind the previous forward re-armed this parity)
-    const uint32_t *order_split = nullptr, *const order = forward_order(c, &order_split);
-    if (c->order_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_order, 0)); c->order_pending = false; }     // the order kernel in flight reads tile_work
-    plan_frame(c, order, order_split, hist);
+    c->snap_walked.next_frame();
+    if (int rc = await_order_kernel(c)) return rc;                         // the order kernel in flight writes the slot's order and reads tile_work
+    plan_frame(c, vs ? vs->history(grid) : History{});                     // the slot's newest order and previous walk, as far as they are of this grid
     // The zero fill of the 2-D gradient rows (64 B per gaussian) rides at the END of the forward's grid (round 0): workgroups appended behind
     // the tiles', which the dispatcher hands out last, into the launch's ragged end -- no fill command and no kernel boundary in front of the
     // composite backward.  Plain stores: the backward's atomics must find the rows where the in-line fill leaves them.
@@ -245,23 +234,23 @@ int gs_forward(gs_ctx *c, float *image, float *transmittance, int mem) {
                        gs_composite_fill_blocks(c->g2d.p, c->g2d_bytes()) > 0;
     for (int r = 0; r < R; ++r) {
         if (r > 0) { if (int rc = bin_round(c, r)) return rc; }
-        if (int rc = enqueue_forward_round(c, r)) return rc;
+        if (int rc = enqueue_forward_round(c, r, walk_dst)) return rc;
         if (r == 0) {
             // the frame's totals: by now the composite is enqueued behind the lists, so the GPU has work while the host looks
             bool redo = false;
             if (int rc = settle_totals(c, &redo, true)) return rc;
-            if (redo) { if (int rc = enqueue_forward_round(c, 0)) return rc; }     // the lists outgrew a buffer and were rebuilt: composite again, same plan
+            if (redo) { if (int rc = enqueue_forward_round(c, 0, walk_dst)) return rc; }     // the lists outgrew a buffer and were rebuilt: composite again, same plan
         }
     }
     if (c->fwd_fills_g2d) c->live.g2d_clean = true;                             // (a forward enqueued again after settle_totals filled again: idempotent)
-    if (vs) vs->walk_written(c->counters_grid);
+    if (vs) vs->walk_written(grid);
+    c->feedback.forward_enqueued(c->n_inst, grid, walk_dst);               // (n_inst: settled behind round 0)
     if (int rc = build_frame_order(c)) return rc;
     const hipMemcpyKind kind = mem == GS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (image && image != c->img()) HIPCHK(c, hipMemcpyAsync(image, c->img(), sizeof(float) * 3 * px, kind, c->stream));
     if (transmittance && transmittance != c->tr()) HIPCHK(c, hipMemcpyAsync(transmittance, c->tr(), sizeof(float) * px, kind, c->stream));
     if (mem == GS_MEM_HOST && (image || transmittance)) HIPCHK(c, hipStreamSynchronize(c->stream));
     c->reach(Stage::RENDERED);
-    c->prev_counters_valid = true; c->prev_n_inst = c->n_inst;
     return GS_OK;
 }
 

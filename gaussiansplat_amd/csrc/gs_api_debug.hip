@@ -240,7 +240,7 @@ int gs_debug_tail_fill(gs_ctx *c, int32_t blocks[2]) {
 
 int gs_debug_tile_clock_rows(gs_ctx *c) {
     if (!c) return GS_ERR_INVALID;
-    if (lpt_schedule(c)) return lpt_order_entries(c) + gs_seg_units(lpt_front(c));
+    if (c->lpt_schedule()) return c->lpt_order_entries() + gs_seg_units(c->lpt_front());
     // small grids: blocks of one part x the most waves a tile is given (pixel parts x list segments of the backward); 0: one wave per tile
     const int len = (((int)c->ntiles() + 7) / 8) * 8;
     const int units = c->plan.parts * (c->plan.snap == gs_ctx::FramePlan::Snap::ALL ? 4 * c->plan.seg_n : 1);   // (an upper bound: at most four parts on top of the segments)
@@ -265,7 +265,7 @@ int gs_rank_probe_result(const gs_ctx *c) { return c ? c->rank_probe : -1; }
 static int sum_work_counters(gs_ctx *c) {
     unsigned long long *w = c->counters.as<unsigned long long>();
     const int nt = (int)c->ntiles();
-    HIPCHK(c, gs_launch_sum_tiles(c->last_walked, c->tile_work.as<uint32_t>(), nt, w, c->stream));
+    HIPCHK(c, gs_launch_sum_tiles(c->feedback.walk, c->tile_work.as<uint32_t>(), nt, w, c->stream));
     if (c->stage >= Stage::COMPOSITE_ADJOINT && c->tile_walked_b.p && c->tile_work_b.p)
         HIPCHK(c, gs_launch_sum_tiles(c->tile_walked_b.as<uint32_t>(), c->tile_work_b.as<uint32_t>(), nt, w + 2, c->stream));
     else HIPCHK(c, hipMemsetAsync(w + 2, 0, 16, c->stream));

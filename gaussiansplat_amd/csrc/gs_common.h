@@ -350,10 +350,12 @@ inline int gs_composite_fill_blocks(const void *dst, unsigned long long bytes) {
 }
 // the written entries of capped lists, summed over the tiles: out[0] = sum ext[t].x
 hipError_t gs_launch_sum_listed(const uint2 *ext, int n, unsigned long long *out, hipStream_t s);
-// longest-first launch order of the tiles for a plain launch (gs_composite.hip: groups of 8 x 8 tiles dealt to the XCDs by work,
-// GS_LPT_BUCKETS work classes inside an XCD's list; one workgroup).  order: gs_lpt_order_len(gx, gy) entries, holes = 0xFFFFFFFF.
+// longest-first launch order of the tiles for a plain launch (gs_order.hip: groups of 8 x 8 tiles dealt to the XCDs by work,
+// GS_LPT_BUCKETS work classes inside an XCD's list; one workgroup).  order: gs_lpt_order_len(gx, gy) entries, holes = GS_LPT_NONE.
 // zero14 (may be null): fourteen 64-bit words zeroed on the way (the backward's work and ticket counters: saves a memset command)
 #define GS_LPT_MAX_TILES 35000
+#define GS_LPT_NONE 0xFFFFFFFFu
+#define GS_ORDER_TILE_MASK 0x0FFFFFFFu     // an order's entry: tile | part << 28 | log2(parts) << 30 (tile_of_block, gs_composite.hip)
 int gs_lpt_order_len(int gx, int gy);
 // out[0] = shader cycles (s_memtime), out[1] = 100 MHz ticks (s_memrealtime) of one wave over ~20 us: the chip's clock right now
 hipError_t gs_launch_clock_probe(unsigned long long *out, hipStream_t s);

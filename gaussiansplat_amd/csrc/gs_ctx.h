@@ -19,7 +19,8 @@
 // What the ctx holds it owns: DevBuf frees itself, ~gs_ctx releases the communicator, events, streams and pinned blocks -- no list to keep.
 // What every entry point needs is written ONCE, here: the refusals they share (need_3d, need_mem, need_model, need_image_size, need_stage, overlaps), the sizes
 // (n1, ntiles, pixels), a buffer of gradient rows in the ctx's mode (gs_ctx::rows), the model head of an argument struct (model_head), the per-gaussian
-// chain's arguments (chain_args), the export_debug arrays (gs_ctx::Dbg, DBG_WIDTH); what changes behind a frame's plans is one value (gs_ctx::FrameLive).
+// chain's arguments (chain_args), the export_debug arrays (gs_ctx::Dbg, DBG_WIDTH); what changes behind a frame's plans is one value (gs_ctx::FrameLive);
+// what a frame takes from EARLIER frames has one owner each (HISTORY: ViewSlot, WalkFeedback, the order kernel's hand-off; the kernel itself: gs_order.hip).
 #pragma once
 #include "../../include/gsplat.h"
 #include "gs_common.h"
@@ -162,35 +163,12 @@ struct gs_ctx {
     int64_t ev_cnt[GS_STAGE_COUNT] = {};
     DevBuf counters;                         // GS_COUNTER_BYTES: 4 x u64 {walked, evaluated} of the forward and of the backward (sum_work_counters), ...
     DevBuf tile_work, tile_clock;            // per-tile evaluated entries of the forward (the launch orders' input); debug clocks
-    // ---- longest-first launch orders (gs_config.schedule 3 / 4).  After every forward ONE order kernel turns the frame's per-tile
-    // work into a launch order: this frame's backward uses it, and so does the NEXT forward rendered under the same view slot.
-    int view_slot = -1;                      // gs_set_view_slot: the slot of the frame being rendered (-1: none)
-    // Index GS_MAX_VIEW_SLOTS = frames without a slot.  A slot owns two double buffers, each tagged with the grid (grid_key) it is valid for:
-    struct ViewSlot {
-        // launch orders: [sel] is the newest one; a frame that runs on it has its order kernel write the OTHER buffer (on the side stream,
-        // while the frame's backward still reads [sel]), a frame without history writes [sel] itself
-        DevBuf order[2];
-        int sel = 0;
-        int64_t tiles = 0;                   // grid of order[sel] (0: no history)
-        int order_dst(bool in_use) const { return in_use ? sel ^ 1 : sel; }
-        void order_written(int buf, int64_t grid) { sel = buf; tiles = grid; }          // order[buf] is the newest one now
-        // per tile: list entries the slot's forwards walked (the next frame's list caps and segment lengths): [wsel] = the last completed
-        // forward's, which the frame being rendered may still read while it writes its own into the other one
-        DevBuf walkbuf[2];
-        int wsel = 0;
-        int64_t walked_grid = 0;             // grid of walkbuf[wsel] (0: none yet)
-        DevBuf &walked() { return walkbuf[wsel]; }
-        DevBuf &walk_dst() { return walkbuf[wsel ^ 1]; }
-        void walk_written(int64_t grid) { wsel ^= 1; walked_grid = grid; }      // the frame's forward is enqueued: its walk is the slot's history now
-    };
-    std::vector<ViewSlot> slots;             // GS_MAX_VIEW_SLOTS + 1 (allocated at gs_create; device buffers on first use)
-    const uint32_t *last_walked = nullptr;   // per-tile walked counts of the most recent forward (the slot's array, or tile_walked)
-    int wave_slots = 5120;                   // CUs x 4 SIMDs x 5 BY DEFINITION (gs_create): the unit of every threshold; the backward holds six waves per SIMD by now
+    int wave_slots = 5120;                  // CUs x 4 SIMDs x 5 BY DEFINITION (gs_create): the unit of every threshold; the backward holds six waves per SIMD by now
     DevBuf tile_nopen, smax, tile_ext, zero_tiles;   // capped lists (gs_config.list_cap; FrameLive::frame_capped)
     // ---- the frame's LIVE state: what calls behind the plans change.  gs_bin starts every frame with a fresh value, so a member added here cannot be
     // forgotten in a reset.  Written by two_level_lists (capped lists), bin_small / gs_forward (g2d_clean), depth_order, gs_get_array's list completion, and
-    // the member functions.  What outlives a gs_bin is NOT here: n_inst, n_coarse, round_gen, round_ids_off, pending_totals, fwd_fills_g2d, the fill-block
-    // counts, last_walked, counters_grid, the depth sort's feedback words, the view slots' history.
+    // the member functions.  What outlives a gs_bin is NOT here: the frame's totals (n_inst, n_coarse, round_gen, round_ids_off, pending_totals), fwd_fills_g2d
+    // and the fill-block counts, the depth sort's feedback words -- and the HISTORY below the plans: the view slots, `feedback`, the order kernel's hand-off.
     struct FrameLive {
         bool frame_capped = false;           // capped lists (gs_config.list_cap): the tile lists were written only as far as the slot's history says they
                                              // are walked; gs_get_array(GS_ARR_SORTED_IDS / _KEYS) completes them and clears it
@@ -252,17 +230,90 @@ struct gs_ctx {
         bool fill_shs = false;               // the composite launch carries the zero fill of d_shs: the SH kernel stores live rows only (shs_zeroed)
         bool model_changes() const { return fused(); }   // the frame falls back to nothing when the call succeeds
     };
-    // ---- heavy tiles: list segments of the backward
-    DevBuf snap, snap_walked;                // the forward's snapshots (HEAVY: of the split tiles, ALL: of every tile); HEAVY: their walked lengths, two frame parities
-    uint32_t *pinned_split = nullptr;        // coherent pinned host words, two per view slot (one per order buffer): split tiles of that order, as its
-                                             // order kernel counted them (0xFFFFFFFF: the kernel has not reported yet); null: unknown, assume some
-    uint32_t *split_word(int slot, int buf) { return pinned_split ? pinned_split + 2 * slot + buf : nullptr; }
-    int snap_parity = 0;                     // the parity of snap_walked this frame's forward writes (and its backward reads); the order kernel
-                                             // behind every forward re-arms the other one and the parities swap
-    // ---- side stream: the order kernel (needed by the slot's NEXT frame, not by this one) runs beside the backward composite
+    // ================ HISTORY: what a frame takes from the frames before it, each with ONE owner here: a view slot's launch order and its per-tile walk
+    // (ViewSlot), the ctx's walked share (WalkFeedback), the order kernel's hand-off.  (The depth sort's feedback words keep their own rules: further down.)
+    // ---- longest-first launch orders (gs_config.schedule 3 / 4).  After every forward ONE order kernel turns the frame's per-tile
+    // work into a launch order: this frame's backward uses it, and so does the NEXT forward rendered under the same view slot.
+    int view_slot = -1;                      // gs_set_view_slot: the slot of the frame being rendered (-1: none)
+    // Index GS_MAX_VIEW_SLOTS = frames without a slot.  A slot owns two double buffers, each tagged with the grid (grid_key) it is valid for:
+    struct ViewSlot {
+        // launch orders: [sel] is the newest one; a frame that runs on it has its order kernel write the OTHER buffer (on the side stream,
+        // while the frame's backward still reads [sel]), a frame without history writes [sel] itself
+        DevBuf order[2]; int sel = 0;
+        int64_t tiles = 0;                   // grid of order[sel] (0: no history)
+        uint32_t *split_words = nullptr;     // coherent pinned host words, one per order buffer (gs_create): split tiles of that order, as its order
+                                             // kernel counted them (0xFFFFFFFF: the kernel has not reported yet); null: unknown, assume some
+        uint32_t *split_word(int buf) const { return split_words ? split_words + buf : nullptr; }
+        int order_dst(bool in_use) const { return in_use ? sel ^ 1 : sel; }
+        void order_written(int buf, int64_t grid) { sel = buf; tiles = grid; }          // order[buf] is the newest one now
+        // per tile: list entries the slot's forwards walked (the next frame's list caps and segment lengths): [wsel] = the last completed
+        // forward's, which the frame being rendered may still read while it writes its own into the other one
+        DevBuf walkbuf[2]; int wsel = 0;
+        int64_t walked_grid = 0;             // grid of walkbuf[wsel] (0: none yet)
+        DevBuf &walk_dst() { return walkbuf[wsel ^ 1]; }
+        void walk_written(int64_t grid) { wsel ^= 1; walked_grid = grid; }      // the frame's forward is enqueued: its walk is the slot's history now
+        // what a frame on `grid` may READ of the slot, each null unless made on this grid: newest order, its split word, previous walk (the ONE tag compare)
+        struct History { const uint32_t *order, *order_split, *walk; };
+        History history(int64_t grid) const {
+            const bool o = tiles == grid, w = walked_grid == grid;
+            return {o ? order[sel].as<uint32_t>() : nullptr, o ? split_word(sel) : nullptr, w ? walkbuf[wsel].as<uint32_t>() : nullptr};
+        }
+    };
+    std::vector<ViewSlot> slots;             // GS_MAX_VIEW_SLOTS + 1 (allocated at gs_create; device buffers on first use)
+    uint32_t *pinned_split = nullptr;        // the slots' split words (ViewSlot::split_words): one pinned block, freed with the ctx
+    // The slot of the frame being rendered, asked two ways.  STORAGE: where its order kernel writes -- never null: a slot-less frame's backward needs an order
+    // too.  HISTORY: whose order and walk it may read, where its forward leaves its walk -- null for a slot-less frame unless schedule 4: nothing says two such
+    // frames show one view, so under schedule 3 the last slot's order is storage no later frame reads, and the walk goes to feedback.own
+    ViewSlot &storage_slot() { return slots[view_slot >= 0 ? view_slot : GS_MAX_VIEW_SLOTS]; }
+    ViewSlot *history_slot() { return view_slot >= 0 || cfg.schedule == 4 ? &storage_slot() : nullptr; }
+    // A launch order is built only when there are more tiles than wave slots (wave_slots: 256 CUs x 4 SIMDs x 5 on MI355X).  Below that the isolated
+    // kernels do gain from it (C2, 2500 tiles: forward 68 -> 61 us, backward 145 -> 122 us, tools/xcd_order.py C2 -- in tile order the
+    // heavy tiles of the image centre land on neighbouring SIMDs), but the frame does not: its forward is bound by cold gathers, not by
+    // balance, and the order kernel is one more launch in a frame that is bound by launches (C2 0.382 -> 0.400 ms, C1 0.183 -> 0.205 ms
+    // with it, same box; 0.393 / 0.197 with the kernel on the side stream).
+    bool lpt_schedule() const { return (cfg.schedule == 3 || cfg.schedule == 4) && (ntiles() > wave_slots || (cfg.debug_flags & GS_DEBUG_ALWAYS_ORDER)); }
+    // Heavy tiles (round 5): the launch orders reserve a front region for the extra parts of split tiles (tile_lpt_order_kernel) when the
+    // ctx may use them at all: automatic tile_parts, the early-out on, and a grid on which the frame-wide 2 / 4 waves per tile cannot engage.
+    // A property of the ctx and the grid, so every order of a slot has one layout; whether a LAUNCH honours the split entries is decided
+    // per frame (plan_frame: FramePlan::split).
+    int lpt_front() const { return (lpt_schedule() && cfg.tile_parts == 0 && cfg.t_min > 0.0f && 2 * ntiles() > wave_slots && ntiles() <= GS_LPT_MAX_TILES) ? GS_LPT_FRONT : 0; }
+    int lpt_order_entries() const { return lpt_front() + gs_lpt_order_len(gx, gy); }   // = workgroups of a launch over the order
+    // the words behind an order's entries: list entries per backward segment of the split tiles (GS_SEG_SLOTS of them)
+    const uint32_t *order_seg_len(const uint32_t *order) const { return order + lpt_order_entries(); }
+    int lpt_split_div() const { return wave_slots * 4 / 5; }      // a tile with more work than an even share of ~4 waves per SIMD is split
+    // The side stream (order kernel beside the backward) costs four more runtime calls per frame: it pays when the composite kernels
+    // are long, and costs when the frame is bound by the host's launch rate (config C2, together with the zero fill it once carried: + 9 %).
+    bool use_side_stream() const { return n >= 262144 || (cfg.debug_flags & GS_DEBUG_ALWAYS_ORDER); }
+    // ---- the ctx's walk feedback: the share of its list entries the last completed forward walked (slab rounds, capped lists).  The forward leaves per-tile
+    // counts; the NEXT frame's binning sums them on their way to the host (previous_walk), where the sum meets its instance count (sum_arrived)
+    struct WalkFeedback {
+        DevBuf own;                          // per-tile walk of forwards without a history slot
+        const uint32_t *walk = nullptr;      // per-tile walked counts of the most recent forward (a slot's array, or `own`) ...
+        int64_t grid = 0, n_inst = 0;        // ... the grid (grid_key) it was written for, and the frame's instances
+        bool sum_due = false;                // a forward has been enqueued whose walk no binning has sent to the host yet
+        double ratio = -1.0; double walked_ratio() const { return ratio; }   // entries walked / instances of the last completed frame (-1: none yet)
+        // binning a frame on grid g: the walk to sum for the host, or null (none due, or not of this grid: never sent)
+        const uint32_t *previous_walk(int64_t g) { if (grid != g || !walk) sum_due = false; return sum_due ? walk : nullptr; }
+        void forward_enqueued(int64_t inst, int64_t g, const uint32_t *dst) { n_inst = inst; grid = g; walk = dst; sum_due = true; }
+        // the frame's totals are on the host; sum: the u64 previous_walk's kernel stored, read only when one was sent
+        void sum_arrived(const uint32_t *sum) {
+            if (sum_due && n_inst > 0) { unsigned long long w = 0; std::memcpy(&w, sum, sizeof(w)); ratio = (double)w / (double)n_inst; }
+            sum_due = false;
+        }
+    } feedback;
+    // ---- the order kernel's hand-off.  On the side stream the kernel (needed by the slot's NEXT frame, not by this one) runs beside the backward composite
     hipStream_t side = nullptr;
     hipEvent_t ev_main = nullptr, ev_order = nullptr;
-    bool order_pending = false;              // an order kernel is in flight on the side stream (ev_order)
+    bool order_pending = false;              // an order kernel is in flight on the side stream (ev_order): await_order_kernel (gs_api_composite.hip)
+    // heavy tiles, list segments of the backward: walked lengths of the forward's snapshots, two frame parities (the order kernel re-arms the NEXT frame's)
+    struct SnapWalked {
+        DevBuf buf; int parity = 0;
+        void next_frame() { parity ^= 1; }   // (the order kernel behind the previous forward re-armed this parity)
+        uint32_t *slice(int p) const { return buf.as<uint32_t>() + (size_t)p * GS_SEG_SLOTS; }
+        uint32_t *of_frame() const { return slice(parity); }         // this frame's forward writes it, its backward reads it
+        uint32_t *to_rearm() const { return slice(parity ^ 1); }
+    } snap_walked;
+    DevBuf snap;                             // the forward's snapshots (HEAVY: of the split tiles, ALL: of every tile)
     // ---- speculative binning: the lists are enqueued with the capacities of the buffers at hand while the frame's totals travel
     bool pending_totals = false;             // ev_count recorded, pinned totals not read yet (the speculation itself: FrameLive::spec_lists)
     int64_t n_coarse = 0;                    // coarse instances listed by the frame (two-level and small paths; 0 on the radix paths)
@@ -280,11 +331,9 @@ struct gs_ctx {
     uint32_t *ext_count() { return &counters.as<CounterBlock>()->ext_count; }
     // ---- per-tile work counters of the composite launches (walked / evaluated list entries): counters[0..3] hold their sums only
     // after sum_work_counters() (gs_get_work_counters, the radix binning paths); the two-level path sums the walked counts of the
-    // previous forward inside l1_rowscan on their way to the host
-    DevBuf tile_walked, tile_walked_b, tile_work_b;
+    // previous forward inside l1_rowscan on their way to the host.  The forward's walked counts: feedback.walk; the backward's:
+    DevBuf tile_walked_b, tile_work_b;
     hipError_t ensure_bwd_counters() { const hipError_t e = tile_walked_b.ensure(sizeof(uint32_t) * ntiles1()); return e != hipSuccess ? e : tile_work_b.ensure(sizeof(uint32_t) * ntiles1()); }
-    int64_t counters_grid = 0;               // the grid (grid_key) the forward's per-tile counters were written for
-    bool counters_here() const { return counters_grid == grid_key() && last_walked; }   // ... is the one at hand
     // ---- depth sort in two steps (gs_depth_sort_buckets; gs_config.depth_sort)
     DevBuf key_range;                        // two frame parities of the key-range accumulators the preprocess kernel fills
     int range_parity = 0;                    // parity of the frame being built
@@ -322,9 +371,6 @@ struct gs_ctx {
     float *bound_image = nullptr, *bound_trans = nullptr;   // gs_bind_outputs: caller-owned device buffers the forward writes directly
     float *img() { return bound_image ? bound_image : image.as<float>(); }
     float *tr() { return bound_trans ? bound_trans : trans.as<float>(); }
-    double walked_ratio = -1.0;              // entries walked / instances of the last completed frame (-1: none yet)
-    int64_t prev_n_inst = 0;
-    bool prev_counters_valid = false;        // `counters` holds the walked count of a completed forward
     int64_t frame_id = 0, ev_frame[GS_STAGE_COUNT] = {};   // a stage may run once per binning round: ev_cnt counts frames, not launches
     int64_t ev_counted[GS_STAGE_COUNT] = {};               // last frame whose pair of this stage was added to ev_cnt
     DevBuf grads_flat;                       // gs_grads_alloc
@@ -463,31 +509,7 @@ inline int bind_device(gs_ctx *c) {
     return GS_OK;
 }
 
-// A launch order is built only when there are more tiles than wave slots (gs_ctx::wave_slots: 256 CUs x 4 SIMDs x 5 on MI355X).  Below that the isolated
-// kernels do gain from it (C2, 2500 tiles: forward 68 -> 61 us, backward 145 -> 122 us, tools/xcd_order.py C2 -- in tile order the
-// heavy tiles of the image centre land on neighbouring SIMDs), but the frame does not: its forward is bound by cold gathers, not by
-// balance, and the order kernel is one more launch in a frame that is bound by launches (C2 0.382 -> 0.400 ms, C1 0.183 -> 0.205 ms
-// with it, same box; 0.393 / 0.197 with the kernel on the side stream).
-inline bool lpt_schedule(const gs_ctx *c) {
-    return (c->cfg.schedule == 3 || c->cfg.schedule == 4) && (c->ntiles() > c->wave_slots || (c->cfg.debug_flags & GS_DEBUG_ALWAYS_ORDER));
-}
-// Heavy tiles (round 5): the launch orders reserve a front region for the extra parts of split tiles (tile_lpt_order_kernel) when the
-// ctx may use them at all: automatic tile_parts, the early-out on, and a grid on which the frame-wide 2 / 4 waves per tile cannot engage.
-// A property of the ctx and the grid, so every order of a slot has one layout; whether a LAUNCH honours the split entries is decided
-// per frame (plan_frame: FramePlan::split).
-inline int lpt_front(const gs_ctx *c) {
-    const int64_t ntiles = c->ntiles();
-    return (lpt_schedule(c) && c->cfg.tile_parts == 0 && c->cfg.t_min > 0.0f && 2 * ntiles > c->wave_slots && ntiles <= GS_LPT_MAX_TILES) ? GS_LPT_FRONT : 0;
-}
-// the words behind an order's entries: list entries per backward segment of the split tiles (GS_SEG_SLOTS of them)
-inline const uint32_t *order_seg_len(const gs_ctx *c, const uint32_t *order) { return order + lpt_front(c) + gs_lpt_order_len(c->gx, c->gy); }
-inline int lpt_order_entries(const gs_ctx *c) { return lpt_front(c) + gs_lpt_order_len(c->gx, c->gy); }   // = workgroups of a launch over the order
-inline int lpt_split_div(const gs_ctx *c) { return c->wave_slots * 4 / 5; }      // a tile with more work than an even share of ~4 waves per SIMD is split
-// The side stream (order kernel beside the backward) costs four more runtime calls per frame: it pays when the composite kernels
-// are long, and costs when the frame is bound by the host's launch rate (config C2, together with the zero fill it once carried: + 9 %).
-inline bool use_side_stream(const gs_ctx *c) { return c->n >= 262144 || (c->cfg.debug_flags & GS_DEBUG_ALWAYS_ORDER); }
 inline uint32_t *key_range_of(const gs_ctx *c, int parity) { return c->key_range.as<uint32_t>() + (size_t)parity * gs_depth_range_parity_words(); }   // one frame parity's accumulators
-inline int order_index(const gs_ctx *c) { return c->view_slot >= 0 ? c->view_slot : GS_MAX_VIEW_SLOTS; }   // index into gs_ctx::slots of the frame being rendered
 
 // ---------------------------------------------------------------- across the translation units
 // gs_api_bin.hip

@@ -10,6 +10,7 @@
 Fixed seeds; every ctx whose gradients are recorded is deterministic (fixed-point gradient sums), and the two cases with float atomics
 record no gradients (C1_small_float_atomics; tile_clock: counts only), so every array must be EQUAL.  Arrays above 4096 elements are kept as a
 blake2b digest of their bytes.  A call the library refuses is recorded with its message: the refusal must be alike on both sides.
+History (case_history): what frames inherit under a view slot, across slots, grids, an abandoned frame and without slots, small and at C3 scale.
 Per frame: image, T, the five gradient arrays, tile ranges, sorted ids, sortIdxs, num_instances / _coarse_instances / _rounds,
 bin_path_of_frame, list_stats, work_counters_ex; and the counting words of the composite kernels' debug record on one small frame.
 The per-gaussian kernels beyond a frame: a density cycle (statistics, actions, plan, the restructured model and one moment set), the five
@@ -108,6 +109,11 @@ def scene(cfg, n=None):
     return _scenes[(cfg, n)], n, W, H, deg
 
 
+def synthetic_config(cfg):
+    from gaussiansplat_amd import synthetic
+    return synthetic.CONFIGS[cfg]
+
+
 def set_model(ctx, sc, n, deg):
     ctx.set_model_host(sc["means"], sc["scales"], sc["quats"], sc["opacities"], sc["shs"].reshape(n, -1), deg)
 
@@ -151,6 +157,48 @@ def case_grow(R):
     assert inst[1] > cap, ("the second frame did not outgrow the first frame's ids buffer", inst, cap)
     R.put("grow/first_frame_capacity", cap)
     ctx.close()
+
+
+def case_history(R, name, n, W, H, deg, seed, grow=0.0, **kw):
+    """What frames inherit (gs_ctx.h, HISTORY): the sequences of tests/test_gpu_history.py, three frames per step, one after another on ONE ctx --
+    same slot; slot A, slot B, slot A; the grid transposed and back; gs_set_view_slot between gs_bin and gs_forward; a frame abandoned after gs_bin
+    -- then three slot-less frames under schedule 3 and under schedule 4, each on a ctx of its own.  Deterministic; under the default tile_parts the
+    gradient bits depend on the history a frame ran on, so equal arrays say that both libraries read the same history."""
+    from gaussiansplat_amd import backend as B, synthetic
+    sc = synthetic.make_scene(n, W, H, deg, seed=seed)
+    sc["scales"] = (sc["scales"] + np.float32(grow)).astype(np.float32)
+    dC = {(W, H): synthetic.make_dC(W, H, 1), (H, W): synthetic.make_dC(H, W, 1)}
+
+    def step(ctx, g, tag, slot, view=0, w=W, h=H, frames=3, between=None):
+        for k in range(frames):
+            ctx.set_view_slot(slot)
+            set_cam(ctx, w, h, view)
+            ctx.preprocess(); ctx.bin()
+            if between is not None:
+                ctx.set_view_slot(between)
+            img, tr = ctx.forward_host()
+            ctx.backward(dC[(w, h)], g, overwrite=True)
+            t = "%s/%s_f%d" % (name, tag, k)
+            R.put(t + "/image", img); R.put(t + "/T", tr)
+            R.call(t + "/grads", lambda: ctx.grads_read(g, deg))
+            R.call(t + "/stats", lambda: dict({k: int(v) for k, v in ctx.list_stats().items()}, num_instances=ctx.num_instances, num_rounds=ctx.num_rounds,
+                                              tile_parts=ctx.tile_parts_of_frame(), tile_clock_rows=ctx.tile_clock_rows(), **ctx.work_counters_ex()))
+
+    ctx = B.Context(deterministic=True, **kw)
+    set_model(ctx, sc, n, deg)
+    g = ctx.grads_alloc()
+    step(ctx, g, "same_slot", 0)
+    step(ctx, g, "slot_b", 1, view=4); step(ctx, g, "slot_a_again", 0)
+    step(ctx, g, "transposed", 0, w=H, h=W); step(ctx, g, "grid_back", 0)
+    step(ctx, g, "slot_changed_after_bin", 0, frames=1, between=2); step(ctx, g, "second_slot", 2)
+    ctx.set_view_slot(0); set_cam(ctx, W, H, 0); ctx.preprocess(); ctx.bin()          # abandoned: binned, never rendered
+    step(ctx, g, "after_abandoned", 0)
+    ctx.close()
+    for schedule in (3, 4):
+        ctx = B.Context(deterministic=True, **dict(kw, schedule=schedule))
+        set_model(ctx, sc, n, deg)
+        step(ctx, ctx.grads_alloc(), "slotless_schedule_%d" % schedule, -1)
+        ctx.close()
 
 
 def case_2d(R):
@@ -531,6 +579,14 @@ def record(path):
     case_3d(R, "C1_order_index", "C1", frames=2, order=B.ORDER_INDEX)
     case_3d(R, "C2_super16", "C2", frames=2, debug_flags=B.GS_DEBUG_SUPER16)
     case_3d(R, "C2_wide_cursors", "C2", frames=2, debug_flags=B.GS_DEBUG_WIDE_CURSORS)
+    # small frames with the paths forced on (capped lists + orders + side stream; list segments; slab rounds), then C3 scale (8160 tiles, above the wave
+    # slots) under the defaults: n = 1 000 000 with the order kernel on the side stream, n = 200 000 without
+    small = dict(n=3000, W=160, H=96, deg=1, seed=41, grow=2.0)
+    case_history(R, "history_small_caps", bin_path=3, list_cap=2, slab_mode=0, debug_flags=B.GS_DEBUG_ALWAYS_ORDER, **small)
+    case_history(R, "history_small_segments", slab_mode=0, tile_parts=0, **small)
+    case_history(R, "history_small_slabs", bin_path=3, slab_max_ratio=0.15, list_cap=1, **small)
+    for n in (1_000_000, 200_000):
+        case_history(R, "history_C3_n%d" % n, n, *synthetic_config("C3")[1:], seed=1236)
     case_2d(R)
     case_empty(R)
     case_tile_clock(R)
@@ -593,7 +649,7 @@ def run(lib_a, lib_b, log=None):
     files = []
     for tag, lib in (("a", lib_a), ("b", lib_b)):
         f = os.path.join(out, "compare_libs_%s.npz" % tag)
-        rc = subprocess.run(["timeout", "-k", "10", "420", sys.executable, os.path.abspath(__file__), "record", f],
+        rc = subprocess.run(["timeout", "-k", "10", "560", sys.executable, os.path.abspath(__file__), "record", f],
                             env=dict(os.environ, GSPLAT_HIP_LIB=os.path.abspath(lib))).returncode
         if rc != 0:
             sys.exit("record with %s ended with status %d: nothing more is run" % (lib, rc))
