@@ -28,6 +28,8 @@ STAGES = ("preprocess", "depth_sort", "count_scan", "emit", "tile_sort", "ranges
 GS_CAMERA_GRAD_FLOATS = 40  # gs_backward_camera
 GS_METRIC_SUMS = 4          # gs_image_metrics
 GS_EXPOSURE_FLOATS = 12     # csrc/gs_exposure.h: a row of the exposure table, 3 x 4 row-major
+GS_BILAGRID_FLOATS = 12     # gs_bilagrid_*: a vertex of a bilateral grid, 3 x 4 row-major
+GS_BILAGRID_MAX_DIM = 64    # ... and the most vertices along an axis
 (METRIC_MSE, METRIC_MAE, METRIC_SSIM, METRIC_PSNR, GS_METRIC_COUNT) = range(5)   # GS_METRIC_*
 GS_ABI_VERSION = 3          # load() refuses a library that reports another version
 GS_DEBUG_WIDE_CURSORS = 1
@@ -145,6 +147,10 @@ ABI = {
     "gs_exposure_apply": Sig(_i, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gs_exposure_backward": Sig(_i, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "gs_exposure_adam": Sig(_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i64]),
+    "gs_bilagrid_apply": Sig(_i, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "gs_bilagrid_backward": Sig(_i, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "gs_bilagrid_tv": Sig(_i, [_vp, _vp, _i32, _i32, _i32, _f, _vp, _vp]),
+    "gs_bilagrid_adam": Sig(_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _i64]),
     "gs_num_gaussians": Sig(_i64, [_vp]),
     "gs_num_instances": Sig(_i64, [_vp]),
     "gs_num_coarse_instances": Sig(_i64, [_vp]),
@@ -640,6 +646,31 @@ class Context:
         """gs_exposure_adam: one Adam step of a row of 12 floats (gs_adam_step's update); step counts from 1 and is the row's own."""
         self._chk(self.L.gs_exposure_adam(self.h, int(exposure_ptr or 0), int(d_exposure_ptr or 0), int(exp_avg_ptr or 0),
                                           int(exp_avg_sq_ptr or 0), float(lr), float(beta1), float(beta2), float(eps), int(step)))
+
+    # -- per-view bilateral grid: needs no model, camera or frame, and leaves the ctx's frame as it is.  Device pointers, no sync
+    def bilagrid_apply(self, img_ptr: int, grid_ptr: int, dims, weight_ptr: int, W: int, H: int, out_ptr: int):
+        """gs_bilagrid_apply: out [3, H, W] = w * (A img + b) per pixel, [A | b] sliced from the grid [Gz, Gy, Gx, 12]; dims = (Gx, Gy, Gz)."""
+        gx, gy, gz = dims
+        self._chk(self.L.gs_bilagrid_apply(self.h, int(img_ptr or 0), int(grid_ptr or 0), int(gx), int(gy), int(gz), int(weight_ptr or 0),
+                                           int(W), int(H), int(out_ptr or 0)))
+
+    def bilagrid_backward(self, img_ptr: int, d_out_ptr: int, grid_ptr: int, dims, weight_ptr: int, W: int, H: int, d_img_ptr: int,
+                          d_grid_ptr: int = 0):
+        """gs_bilagrid_backward: d_img (may be d_out itself) and, unless d_grid_ptr is 0, every float of d_grid (overwritten)."""
+        gx, gy, gz = dims
+        self._chk(self.L.gs_bilagrid_backward(self.h, int(img_ptr or 0), int(d_out_ptr or 0), int(grid_ptr or 0), int(gx), int(gy), int(gz),
+                                              int(weight_ptr or 0), int(W), int(H), int(d_img_ptr or 0), int(d_grid_ptr or 0)))
+
+    def bilagrid_tv(self, grid_ptr: int, dims, coef: float, d_grid_ptr: int = 0, tv_ptr: int = 0):
+        """gs_bilagrid_tv: the total variation into one device float64 (tv_ptr) and the gradient of coef * tv added to d_grid; 0: not wanted."""
+        gx, gy, gz = dims
+        self._chk(self.L.gs_bilagrid_tv(self.h, int(grid_ptr or 0), int(gx), int(gy), int(gz), float(coef), int(d_grid_ptr or 0), int(tv_ptr or 0)))
+
+    def bilagrid_adam(self, grid_ptr: int, d_grid_ptr: int, exp_avg_ptr: int, exp_avg_sq_ptr: int, n_floats: int, lr: float, beta1: float,
+                      beta2: float, eps: float, step: int):
+        """gs_bilagrid_adam: one Adam step of a view's grid (gs_adam_step's update); step counts from 1 and is the view's own."""
+        self._chk(self.L.gs_bilagrid_adam(self.h, int(grid_ptr or 0), int(d_grid_ptr or 0), int(exp_avg_ptr or 0), int(exp_avg_sq_ptr or 0),
+                                          int(n_floats), float(lr), float(beta1), float(beta2), float(eps), int(step)))
 
     def reset_grads(self, grads: GsGrads):
         self._chk(self.L.gs_reset_grads(self.h, C.byref(grads)))

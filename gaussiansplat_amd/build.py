@@ -68,6 +68,9 @@ SOURCES = {
     # per-view exposure: the affine, its adjoints and the row's Adam step are specified operation by operation (tests/exposure_ref.py matches bit for bit)
     "gs_exposure.hip": ["-ffp-contract=off"],
     "gs_api_exposure.hip": [],
+    # per-view bilateral grid: cell, slice, affine and adjoints are specified operation by operation (tests/bilagrid_ref.py matches bit for bit)
+    "gs_bilagrid.hip": ["-ffp-contract=off"],
+    "gs_api_bilagrid.hip": [],
     # MCMC densification: weights, draws, noise and regularisers are specified operation by operation (tests/mcmc_ref.py matches bit for bit)
     "gs_mcmc.hip": ["-ffp-contract=off"],
     "gs_api_mcmc.hip": ["-ffp-contract=off"],

@@ -12,6 +12,7 @@
 //   gs_api_camera.hip     the camera gradient (gs_backward_camera)
 //   gs_api_metrics.hip    evaluation metrics (gs_image_metrics, gs_metrics_finish)
 //   gs_api_exposure.hip   the per-view exposure stage (gs_exposure_apply, gs_exposure_backward, gs_exposure_adam)
+//   gs_api_bilagrid.hip   the per-view bilateral grid (gs_bilagrid_apply, gs_bilagrid_backward, gs_bilagrid_tv, gs_bilagrid_adam)
 //   gs_api_mcmc.hip       MCMC densification (gs_mcmc_plan / _sample / _relocate / _noise / _regularize)
 //   gs_background.hip     the background colour's two elementwise kernels (the forward's epilogue, gs_compose_target)
 //   gs_api_debug.hip      introspection and profiling hooks (gs_get_array, stage timers, tile clocks, counters, isolated composite launches)

@@ -16,6 +16,8 @@ adds the other half of the 3DGS recipe: statistics after every backward, clone /
 (metrics.evaluate, csrc/gs_metrics.hip), without changing what the iterations compute.
 `exposure=appearance.Exposure(...)` with `view=v` puts the per-view exposure stage between the frame and the loss: a learned 3 x 4 colour
 affine per training view and per-view pixel weights (csrc/gs_exposure.hip); the optimisers see its d_img where they saw the loss's.
+`bilagrid=appearance.BilateralGrid(...)` with `view=v` puts a per-view bilateral grid there instead: a lattice of such affines indexed by
+pixel position and luminance, for what changes across a photograph (csrc/gs_bilagrid.hip).
 """
 from __future__ import annotations
 
@@ -154,7 +156,7 @@ def _pose_step(renderer, pose):
 
 def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, want_loss: bool = True, fused_sgd: bool = False,
               optimizer=None, density=None, sh_schedule=None, background=None, pose=None, freeze_model: bool = False, exposure=None,
-              view=None):
+              view=None, bilagrid=None):
     """One iteration of train.jl:33-56 as intended (see module docstring).
     fused_sgd (3-D renderer): backward and the parameter update in one pass (gs_backward_sgd) -- the same parameters bit for
     bit (deterministic mode), but renderer.splatGrads is not filled.
@@ -182,12 +184,20 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
     gradient into the frame's, in place, and keeps the row's gradient; exposure.step(view) steps the row; the rest of the iteration is
     the one above on that gradient, so every optimiser form, the fused ones included, density control, the SH schedule, the backgrounds,
     pose and freeze_model run unchanged.  One without the other, or a view out of range, is a ValueError.  None: the same calls in the
-    same order as without the arguments."""
+    same order as without the arguments.
+    bilagrid (appearance.BilateralGrid) with view (its grid): the same stage with a per-view bilateral grid in the place of the affine --
+    apply, mask_target, backward (which also adds the grid's total-variation gradient) and step, exactly where exposure's sit.  The two are
+    alternatives: both at once is a ValueError, and so is one of bilagrid and view without the other."""
     fused = fused_sgd or (optimizer is not None and optimizer.fused)        # a fused form is in use: no frame is left behind the backward
-    if (exposure is None) != (view is None):
-        raise ValueError("trainStep: exposure and view go together (the view names the row of the exposure table)")
-    if exposure is not None:
-        view = exposure._view(view)
+    if exposure is not None and bilagrid is not None:
+        raise ValueError("trainStep: exposure and bilagrid are alternatives (one appearance stage between the frame and the loss)")
+    appearance = exposure if exposure is not None else bilagrid              # the stage of this iteration, or None
+    if (appearance is None) != (view is None):
+        if bilagrid is None:
+            raise ValueError("trainStep: exposure and view go together (the view names the row of the exposure table)")
+        raise ValueError("trainStep: bilagrid and view go together (the view names the grid of the table)")
+    if appearance is not None:
+        view = appearance._view(view)
     if pose is not None and camera is not None:
         raise ValueError("trainStep: camera and pose exclude each other (the iteration renders under pose.camera)")
     if pose is not None and fused:
@@ -215,13 +225,13 @@ def trainStep(renderer, gtimg, lr: float, lossFunc: LossFunction, camera=None, w
     R.renderFrame(renderer, camera)
     if getattr(gtimg, "ndim", 0) == 3 and gtimg.shape[0] == 4:
         gtimg = lossFunc.compose_target(gtimg)
-    if exposure is None:
+    if appearance is None:
         loss, ΔC = lossFunc.value_and_grad(renderer.imageData, gtimg, want_loss)
     else:
-        adjusted = exposure.apply(view, renderer.imageData)
-        loss, ΔC = lossFunc.value_and_grad(adjusted, exposure.mask_target(view, gtimg), want_loss)
-        ΔC = exposure.backward(view, ΔC)
-        exposure.step(view)
+        adjusted = appearance.apply(view, renderer.imageData)
+        loss, ΔC = lossFunc.value_and_grad(adjusted, appearance.mask_target(view, gtimg), want_loss)
+        ΔC = appearance.backward(view, ΔC)
+        appearance.step(view)
     if fused:                                                    # backward and update in one pass: renderer.splatGrads is not filled
         if optimizer is not None:
             optimizer.backward_step(ΔC)
@@ -277,7 +287,8 @@ class Evaluator:
 
 
 def train(renderer, gtimg, lr: float, lossFunc: LossFunction, iterations: int = 100, camera=None, log_every: int = 0, optimizer=None,
-          density=None, sh_schedule=None, background=None, pose=None, freeze_model: bool = False, evaluator=None, exposure=None, view=None):
+          density=None, sh_schedule=None, background=None, pose=None, freeze_model: bool = False, evaluator=None, exposure=None, view=None,
+          bilagrid=None):
     """train.jl:16-59 without the GUI; the reference loops `while score < 0.99` on a score it never updates.
     optimizer: an optim.Adam that replaces the SGD update (lr is then ignored); density: a density.DensityController,
     sh_schedule: an SHDegreeSchedule, background: a colour or a RandomBackground, pose: an optim.CameraAdam that refines the view,
@@ -285,11 +296,12 @@ def train(renderer, gtimg, lr: float, lossFunc: LossFunction, iterations: int = 
     evaluator: an Evaluator; after iteration `it` with (it + 1) % evaluator.every == 0 its views are rendered and measured
     (evaluator.history).  The evaluation leaves the renderer's camera, background and active SH degree as they were; None: the same
     calls in the same order as without the argument.
-    exposure, view: an appearance.Exposure and the row of this target's view (trainStep); the evaluator's views are measured without it."""
+    exposure, view: an appearance.Exposure and the row of this target's view (trainStep); the evaluator's views are measured without it.
+    bilagrid: an appearance.BilateralGrid in the place of exposure (trainStep); the evaluator's views get no grid either."""
     losses = []
     for it in range(iterations):
         l = trainStep(renderer, gtimg, lr, lossFunc, camera, want_loss=True, optimizer=optimizer, density=density, sh_schedule=sh_schedule,
-                      background=background, pose=pose, freeze_model=freeze_model, exposure=exposure, view=view)
+                      background=background, pose=pose, freeze_model=freeze_model, exposure=exposure, view=view, bilagrid=bilagrid)
         losses.append(l)
         if log_every and it % log_every == 0:
             print(f"loss : {l}")                             # loss.jl:69

@@ -20,6 +20,7 @@
  *   gs_exposure_apply         (none: the reference's loss sees the raw frame) out = w (M rgb + b), a 3 x 4 colour affine per view and a mask
  *   gs_exposure_backward      (none: the reference's loss sees the raw frame) its adjoints into the image and into the 12 floats
  *   gs_exposure_adam          (none: the reference's loss sees the raw frame) the Adam step of one view's 12 floats
+ *   gs_bilagrid_apply / _backward / _tv / _adam  (none: the reference's loss sees the raw frame) a per-view bilateral grid of colour affines
  *
  * Conventions
  *   - plain C: pointers + sizes, no exceptions; every function returns 0 (GS_OK) or a
@@ -685,6 +686,50 @@ int gs_exposure_backward(gs_ctx *ctx, const float *img, const float *d_out, cons
  * lr == 0 leaves the row unchanged and still updates the moments.  GS_ERR_INVALID, nothing written: a NULL pointer, step < 1, a beta
  * outside [0, 1), eps not finite or not > 0, lr negative or not finite, any two of the four rows overlapping. */
 int gs_exposure_adam(gs_ctx *ctx, float *exposure, const float *d_exposure, float *exp_avg, float *exp_avg_sq, float lr, float beta1,
+                     float beta2, float eps, int64_t step);
+
+/* ---- per-view bilateral grid: local colour correction between gs_forward and the loss ---- */
+
+/* A lattice of 3 x 4 colour affines per view, indexed by pixel position and pixel luminance, sliced per pixel and applied to the colour: what
+ * a single affine per view (gs_exposure_*) cannot absorb -- vignetting, local tone mapping, a blown-out corner.  Images are planar [3, H, W]
+ * float32; weight: [H, W] float32 or NULL; grid: [Gz][Gy][Gx][12] float32, the 12 floats of a vertex A[r][k] row-major 3 x 4 as a row of the
+ * exposure table; 1 <= Gx, Gy, Gz <= GS_BILAGRID_MAX_DIM; the identity grid has [I | 0] at every vertex.  Float32, one rounding per operation,
+ * no fma contraction, in the order written in csrc/gs_bilagrid.h (restated in tests/bilagrid_ref.py):
+ *   pixel (column c, row r): gx = c sx, sx = (Gx - 1) / (W - 1) (0 when W == 1), gy likewise, gz = clamp(l, 0, 1) (Gz - 1) with the luminance
+ *       l = 0.299 x0 + 0.587 x1 + 0.114 x2 (a NaN l gives 0); on each axis the cell i0 = min((int)g, max(n - 2, 0)), i1 = min(i0 + 1, n - 1),
+ *       f = g - i0; A = the trilinear interpolation of the eight vertex rows, as three nested a + f (b - a), x innermost: equal corners give
+ *       that value exactly.  This is torch.nn.functional.grid_sample(bilinear, border, align_corners=True) at (c / (W - 1), r / (H - 1), l).
+ *   gs_bilagrid_apply     a_r = ((A[r][0] x0 + A[r][1] x1) + A[r][2] x2) + A[r][3];   out_r = w a_r   (no weight: out_r = a_r)
+ *   gs_bilagrid_backward  g_r = w d_r (no weight: d_r);  d_img_k = ((A[0][k] g0 + A[1][k] g1) + A[2][k] g2) + lam_k dl, where dl, the gradient
+ *                         through the luminance, is (Gz - 1) sum_m dA[m] dA_m/dfz with dA[r][k] = g_r x_k (x_3 = 1) when 0 < l < 1, else 0; and,
+ *                         unless d_grid is NULL, d_grid[v][4 r + k] = the sum over every (pixel, corner) whose vertex is v of
+ *                         (double)u ((double)g_r (double)x_k), u the corner's trilinear weight in float32 -- added in double in a fixed order
+ *                         without atomics and rounded to float once.  OVERWRITTEN, all Gz Gy Gx 12 floats: a vertex no pixel touches gets +0.
+ *   gs_bilagrid_tv        tv = sum over the axes with n >= 2 of mean((G[+1] - G)^2), differences in float32, squares and sums in double, written
+ *                         to tv_out (one DEVICE double; may be NULL); and, unless d_grid is NULL, the gradient of coef * tv ADDED to d_grid in
+ *                         float32 (csrc/gs_bilagrid.h states the order).  coef must be finite and >= 0.
+ * The identity grid without a weight returns x for every finite x (the bits but for -0, which becomes +0); with a weight it returns w * x
+ * exactly.  d_img may be d_out itself (in place).  Results are bitwise reproducible call to call and independent of what the ctx did before, of
+ * the alignment of the buffers, of d_img being d_out and of d_grid being asked for.
+ * Every pointer is a DEVICE pointer on the ctx's device; the work is enqueued on the ctx stream, no synchronise.  Needs no model, camera or
+ * frame and works under both renderers; image, transmittance, gradient sums, stage, view-slot history and stage timers stay as they were.
+ * GS_ERR_INVALID, nothing written, enqueued or allocated: a NULL ctx, img, grid, out, d_out or d_img; W or H <= 0; 3 * W * H >= 2^31; a grid
+ * dimension outside 1..GS_BILAGRID_MAX_DIM; out overlapping img, weight or grid; d_img overlapping img, weight, grid or d_grid, or d_out in any
+ * way but d_img == d_out; d_grid overlapping img, d_out, weight or grid; in gs_bilagrid_tv a bad coef or any two of grid, d_grid and tv_out
+ * overlapping. */
+#define GS_BILAGRID_FLOATS 12
+#define GS_BILAGRID_MAX_DIM 64
+int gs_bilagrid_apply(gs_ctx *ctx, const float *img, const float *grid, int32_t Gx, int32_t Gy, int32_t Gz, const float *weight, int32_t W,
+                      int32_t H, float *out);
+int gs_bilagrid_backward(gs_ctx *ctx, const float *img, const float *d_out, const float *grid, int32_t Gx, int32_t Gy, int32_t Gz,
+                         const float *weight, int32_t W, int32_t H, float *d_img, float *d_grid);
+int gs_bilagrid_tv(gs_ctx *ctx, const float *grid, int32_t Gx, int32_t Gy, int32_t Gz, float coef, float *d_grid, double *tv_out);
+/* One Adam step of the n_floats floats of a view's grid from d_grid, with its own moments (zero before the first step): gs_adam_step's update
+ * and host scalars exactly (t = step counts from 1 and is the VIEW's own count).  Device pointers, enqueued on the ctx stream, no synchronise;
+ * the ctx's frame stays as it was.  lr == 0 leaves the grid unchanged and still updates the moments.  GS_ERR_INVALID, nothing written: a NULL
+ * pointer, n_floats outside 1..64^3 * 12, step < 1, a beta outside [0, 1), eps not finite or not > 0, lr negative or not finite, any two of the
+ * four arrays overlapping. */
+int gs_bilagrid_adam(gs_ctx *ctx, float *grid, const float *d_grid, float *exp_avg, float *exp_avg_sq, int64_t n_floats, float lr, float beta1,
                      float beta2, float eps, int64_t step);
 
 /* ---- introspection (parity tests, profiling) ------------------------------------------- */

@@ -416,6 +416,33 @@ hip_exposureAdam!(r::HipRenderer, exposure::Ptr{Float32}, dExposure::Ptr{Float32
                    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, Cfloat, Cfloat, Int64),
                    r.ctx, exposure, dExposure, expAvg, expAvgSq, lr, beta1, beta2, eps, Int64(step)))
 
+# per-view bilateral grid (gs_bilagrid_apply / _backward / _tv / _adam): a lattice [12, Gx, Gy, Gz] (column-major: 12 floats per vertex, x
+# fastest among the vertices) of 3 x 4 colour affines indexed by pixel position and luminance, sliced per pixel and applied between
+# hip_forward! and the loss.  Every array is a DEVICE pointer; enqueued on the ctx stream, no synchronise; the frame stays as it was.  weight,
+# dGrid and tvOut may be C_NULL; dImg may be dOut.  hip_bilagridTv! ADDS the gradient of coef * tv to dGrid and writes tv to one device Float64.
+const GS_BILAGRID_FLOATS = 12
+const GS_BILAGRID_MAX_DIM = 64
+hip_bilagridApply!(r::HipRenderer, img::Ptr{Float32}, grid::Ptr{Float32}, dims::NTuple{3, Integer}, weight::Ptr{Float32}, W::Integer, H::Integer,
+                   out::Ptr{Float32}) =
+    check(r, ccall((:gs_bilagrid_apply, libgs), Cint,
+                   (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Int32, Ptr{Float32}, Int32, Int32, Ptr{Float32}),
+                   r.ctx, img, grid, dims[1], dims[2], dims[3], weight, W, H, out))
+hip_bilagridBackward!(r::HipRenderer, img::Ptr{Float32}, dOut::Ptr{Float32}, grid::Ptr{Float32}, dims::NTuple{3, Integer}, weight::Ptr{Float32},
+                      W::Integer, H::Integer, dImg::Ptr{Float32}, dGrid::Ptr{Float32} = Ptr{Float32}(C_NULL)) =
+    check(r, ccall((:gs_bilagrid_backward, libgs), Cint,
+                   (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Int32, Ptr{Float32}, Int32, Int32, Ptr{Float32}, Ptr{Float32}),
+                   r.ctx, img, dOut, grid, dims[1], dims[2], dims[3], weight, W, H, dImg, dGrid))
+hip_bilagridTv!(r::HipRenderer, grid::Ptr{Float32}, dims::NTuple{3, Integer}, coef::Real, dGrid::Ptr{Float32} = Ptr{Float32}(C_NULL),
+                tvOut::Ptr{Float64} = Ptr{Float64}(C_NULL)) =
+    check(r, ccall((:gs_bilagrid_tv, libgs), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int32, Int32, Int32, Cfloat, Ptr{Float32}, Ptr{Float64}),
+                   r.ctx, grid, dims[1], dims[2], dims[3], coef, dGrid, tvOut))
+# one Adam step of a view's grid (nFloats = 12 Gx Gy Gz) with its own moments; `step` counts from 1 and is the view's own
+hip_bilagridAdam!(r::HipRenderer, grid::Ptr{Float32}, dGrid::Ptr{Float32}, expAvg::Ptr{Float32}, expAvgSq::Ptr{Float32}, nFloats::Integer, lr::Real,
+                  step::Integer; beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-15) =
+    check(r, ccall((:gs_bilagrid_adam, libgs), Cint,
+                   (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64, Cfloat, Cfloat, Cfloat, Cfloat, Int64),
+                   r.ctx, grid, dGrid, expAvg, expAvgSq, Int64(nFloats), lr, beta1, beta2, eps, Int64(step)))
+
 # the active SH degree (3-D renderer): evaluate bands 0 .. degree on rows that keep the model's stride; -1 = the model's own degree.
 # The request is the ctx's (it survives a later gs_set_model); a change of the effective degree drops the frame.
 hip_setActiveShDegree!(r::HipRenderer, degree::Integer = -1) =
